@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--d 30] [--rank 64]
                     [--shard trains|cores] [--op compress|apply|hadamard|add|scale|dot|orthogonalize]
+                    [--dump-outputs DIR]
 
 One STEP = one pass of the hot path over one batch of B independent synthetic trains resident in HBM:
     y_b = tt_compress!(Δ(d) * x_b, rank)       for b = 1..B      (src/solvers/euler.jl:55's operator)
@@ -126,6 +127,18 @@ def host_info():
     return info
 
 
+def blas_start_threads():
+    """Smallest thread count the BLAS libraries loaded for the oracle report before any limit is applied, or None."""
+    try:
+        from threadpoolctl import threadpool_info
+        import numpy  # noqa: F401
+        import scipy.linalg  # noqa: F401
+        n = [p.get("num_threads") for p in threadpool_info() if p.get("user_api") == "blas" and p.get("num_threads")]
+        return min(n) if n else None
+    except Exception:
+        return None
+
+
 def cpu_baseline(d, rank, budget_s=20.0):
     """Oracle (reference algorithm, lean: without the discarded orthogonalize) on ALL host cores this process may use:
     (i) one independent train per process, 1 BLAS thread each; (ii) one train with all BLAS threads.  value = best."""
@@ -134,6 +147,12 @@ def cpu_baseline(d, rank, budget_s=20.0):
     quota = cgroup_cpu_quota()
     if quota:                                       # more processes than twice the quota only add scheduling noise
         cores = max(1, min(cores, 2 * int(quota + 0.999)))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:              # the CPU share the environment grants this job, when it says so
+        cores = min(cores, int(omp))
+    # OpenBLAS sizes its buffers for the thread count it started with (OMP_NUM_THREADS, capped by the visible CPUs) and
+    # segfaults in gesdd when threadpool_limits raises it past that: the all-threads leg stays within it
+    blas_threads = blas_start_threads() or cores
     t1 = _cpu_worker((d, rank, 30, 1, False, 1))                  # calibrate on one train, one thread
     reps = max(1, min(8, int(budget_s / max(t1, 1e-3))))
     ctx = mp.get_context("spawn")
@@ -144,13 +163,14 @@ def cpu_baseline(d, rank, budget_s=20.0):
         wall = time.perf_counter() - t0
     multi = cores * reps * d / wall
     single = d / t1
-    tall = _cpu_worker((d, rank, 30, max(1, min(3, reps)), False, cores)) / max(1, min(3, reps))
+    tall_threads = max(1, min(cores, blas_threads))
+    tall = _cpu_worker((d, rank, 30, max(1, min(3, reps)), False, tall_threads)) / max(1, min(3, reps))
     one_train_all_threads = d / tall
     # `cores` in the record = the EFFECTIVE parallelism: the box's CPU share is a cgroup quota far below the visible hardware
     # threads, so N processes deliver multi / single cores' worth of work, not N (round 2 printed the process count: 256)
     eff = max(1.0, multi / single)
     cands = [(multi, round(eff, 1), "%d procs x 1 BLAS thread" % cores), (single, 1, "1 proc x 1 BLAS thread"),
-             (one_train_all_threads, round(max(1.0, one_train_all_threads / single), 1), "1 proc x %d BLAS threads" % cores)]
+             (one_train_all_threads, round(max(1.0, one_train_all_threads / single), 1), "1 proc x %d BLAS threads" % tall_threads)]
     value, used, how = max(cands)
     # the reference-FAITHFUL flavour (with the orthogonalize that _tt_bond_truncate! computes and tt_compress! discards,
     # src/tt_tools.jl:769,779) on one train and one core, if the lean timing says it fits ~15 s
@@ -190,10 +210,52 @@ def verify_against_oracle(T, dy, seeds_by_slot, d, r, slots):
     return len(slots), worst
 
 
+def dump_outputs(dy, seeds, outdir, budget_bytes=48 << 20, n_sample=32, n_entries=4096):
+    """--dump-outputs DIR: what the timed step returned to its caller, written after the timed region as DIR/<name>.npy (float64).
+    The batch is ~1.7 GB at C3, so a fixed sample of `n_sample` trains is written (slots drawn by a seeded permutation):
+      train_ids.npy    (S,)            global train index of each sampled train (its input is rand_tt(seed = 30 + id))
+      ranks.npy        (S, d+1)        output ranks
+      entries.npy      (S, n_entries)  tensor entries y[i_1..i_d] at multi-indices drawn with a fixed seed
+      norms.npy        (S,)            ||y||_F
+      cores_<id>.npy   (sum_k n r_k r_k+1,)  the cores of train <id>, core k as (n, r_k, r_k+1) in Fortran order, concatenated;
+                                       for the sampled trains, in sample order, as long as they fit `budget_bytes`
+    entries and norms do not depend on the gauge (the signs / rotations an SVD may choose), cores do.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    order = np.random.default_rng(20240601).permutation(dy.batch)[:n_sample]
+    rng = np.random.default_rng(20240602)
+    idx = np.stack([rng.integers(0, n, size=n_entries) for n in dy.dims], axis=1)          # (n_entries, d)
+    ids, rks, entries, norms, total = [], [], [], [], 0
+    for b in order:
+        y = dy.download(int(b))
+        gid = seeds[int(b)] - 30
+        flat = np.concatenate([np.ravel(c, order="F") for c in y.ttv_vec]).astype(np.float64)
+        if total + flat.nbytes <= budget_bytes:
+            np.save(os.path.join(outdir, "cores_%06d.npy" % gid), flat)
+            total += flat.nbytes
+        else:
+            budget_bytes = total                    # later trains' cores are not written either: a prefix of the sample
+        v = np.ones((n_entries, 1, 1))
+        g = np.ones((1, 1))
+        for k, c in enumerate(y.ttv_vec):
+            v = np.matmul(v, c[idx[:, k]])                                            # (n_entries, 1, r_k+1)
+            g = sum(c[s].T @ g @ c[s] for s in range(c.shape[0]))                     # Gram of the left part
+        ids.append(gid)
+        rks.append(y.ttv_rks)
+        entries.append(v[:, 0, 0])
+        norms.append(np.sqrt(max(float(g[0, 0]), 0.0)))
+    arrays = {"train_ids": np.array(ids, dtype=np.float64), "ranks": np.array(rks, dtype=np.float64),
+              "entries": np.array(entries, dtype=np.float64), "norms": np.array(norms, dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # the compress step on one configuration (headline C3, sub-record C2)
 # ------------------------------------------------------------------------------------------------------------------
-def run_compress_config(T, D, d, r, B, steps, warmup, rank, world, barrier, dist, red_device, verify):
+def run_compress_config(T, D, d, r, B, steps, warmup, rank, world, barrier, dist, red_device, verify, dump_dir=None):
     """W untimed + K timed launches of ttn_apply_compress over B synthetic trains per rank; returns the measured record of
     this rank's view (value = whole job: max-over-ranks wall time)."""
     A = T.Delta(d)
@@ -228,6 +290,8 @@ def run_compress_config(T, D, d, r, B, steps, warmup, rank, world, barrier, dist
            "value": round(T.shard.cores_per_second(world, B, d, elapsed / steps), 1), "k_avg_s": k_avg_s, "flops": flops,
            "achieved": flops / k_avg_s / 1e12, "frac": round(flops / k_avg_s / 1e12 / FP64_PEAK_TFLOPS, 4), "out_rks": out_rks,
            "jacobi_sweeps": sweeps[0]}
+    if dump_dir:
+        rec["dumped_bytes"] = dump_outputs(dy, seeds, dump_dir)
     if verify:
         slots = sorted({0, B // 2, B - 1})
         n, worst = verify_against_oracle(T, dy, seeds, d, r, slots)
@@ -617,10 +681,15 @@ def main():
                                                         "the multi-process path on a box with fewer GPUs than ranks)")
     ap.add_argument("--op", default="compress", choices=["compress", "apply", "hadamard", "add", "scale", "dot", "orthogonalize"],
                     help="compress (default) = the headline apply+round step; the others print the roofline line of that kernel alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the trains the last step computed to DIR/<name>.npy "
+                         "(float64, < 64 MB; see dump_outputs) so that two builds can be compared output for output")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, form the process group, all-reduce the world size and print it (no GPU needed: the "
                          "launcher test of tests/test_distributed_gloo.py)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.op != "compress" or args.shard != "trains"):
+        raise SystemExit("--dump-outputs writes the headline step's outputs: it needs --op compress --shard trains")
 
     # ---- launcher: N > 1 without a torchrun environment -> start the ranks as a child BEFORE anything touches a GPU ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -682,7 +751,7 @@ def main():
             dist.barrier()
 
     head = run_compress_config(T, D, d, r, B, args.steps, args.warmup, rank, world, barrier, dist, red_device,
-                               verify=(rank == 0 and not args.no_verify))
+                               verify=(rank == 0 and not args.no_verify), dump_dir=args.dump_outputs if rank == 0 else None)
     extras = {}
     if rank == 0 and not args.no_single:
         extras["batch_sweep"] = batch_sweep(T, D, d, r)
