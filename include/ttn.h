@@ -247,7 +247,8 @@ int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y);
  * (csrc/ttn_ortho_ramp.h: one wave per train over the rank-ramp sites; csrc/ttn_ortho512.h: Cholesky-QR steps with a measured
  * orthogonality check over the tall sites and the centre core; the 1024-thread k_orthogonalize for the left sweep and for trains the
  * other two refuse) and the call reads one word back between them (it synchronises the library stream once); every other train
- * class is one asynchronous launch.  TTN_ORTHO512 = 0 / 1, TTN_ORTHO_RAMP = 0, TTN_ORTHO_CHOLQR = 0 / 1 switch routes off for A/B runs. */
+ * class is one asynchronous launch.  TTN_ORTHO512 = 0 / 1 forbids / forces the multi-kernel form; TTN_ORTHO_CHOLQR = 1 switches its
+ * Cholesky-QR steps off (A/B runs, parity tests of the general route). */
 int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y);
 
 /* ---- parity instrumentation: singular values seen by the last ttn_compress / ttn_bond_truncate --
@@ -271,23 +272,8 @@ int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const do
 
 /* self-test of the symmetric eigensolver used by the Gram routes (csrc/ttn_eig_kernels.h): G host, n x n (n = 64 or 128),
  * column-major, symmetric positive definite; sig[nev] = sqrt of the nev largest eigenvalues (descending), X[128*r] = sig_j * u_j (r <= 64);
- * ticks_rc[0] = device clock ticks (s_memtime), [1] = return code of the device routine, [2..5] = ticks of the four phases
- * (tridiagonalisation, bisection, twisted factorisations, back-transformation); ticks_rc has 6 entries. */
+ * ticks_rc[0] = device clock ticks of the whole routine, [1] = its return code; ticks_rc has 2 entries. */
 int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, double* sig, double* X, int64_t* ticks_rc);
-/* micro-benchmark hook: the same workgroup GEMM on ONE compute unit, `reps` times back to back on device-resident zeros;
- * cycles_out receives the shader-clock cycles (s_memtime) of the whole loop.  Used to price the dense phases against the
- * per-CU fp64 MFMA peak (128 flop/clk/CU). */
-int ttn_bench_gemm(int64_t m, int64_t n, int64_t k, int ta, int tb, int64_t reps, int64_t* cycles_out);
-/* same for the LDS-resident building blocks on an n x n SPD test matrix (n <= 128): what = 0 set-up only, 1 set-up + Cholesky,
- * 2 set-up + one-sided Jacobi of the matrix columns; sweeps_out (may be NULL) receives the Jacobi sweep count of the last rep */
-int ttn_bench_lds(int what, int64_t n, int64_t reps, int64_t* cycles_out, int64_t* sweeps_out);
-
-/* diagnostic: with TTN_PROF=1 in the environment ttn_compress records s_memtime ticks per phase
- * (merge, scale, LQ, Jacobi, sort/rank, split) for every train; out8 receives train b's 16 counters */
-int ttn_prof_get(int64_t b, int64_t* out8);
-/* per bond step (first 120 steps): (p << 32) | jacobi_sweeps, p = short side of the merged matrix */
-int ttn_prof_steps(int64_t b, int64_t* out120);
-int ttn_prof_fine(int64_t b, int64_t* out64);       /* TTN_PROF_STEP=k: 64 fine-grained cycle counters of bond step k of train b */
 /* diagnostics of the last ttn_orthogonalize that took the multi-launch form (csrc/ttn_ortho_ramp.h, ttn_ortho512.h): the four state
  * words of train b = {next site of the right-to-left sweep, buffer of the last right factor, buffer of the last left factor,
  * 1 if k_ortho512 finished the train (0: the 1024-thread kernel took it over from `next site`)}. */

@@ -30,7 +30,6 @@ int ttn_wg512_init(void);
 size_t ttn_wg512_compress_args_bytes(void);
 int ttn_wg512_launch_compress(const void* args, size_t nbytes, int grid, hipStream_t stream);
 int ttn_wg512_selftest_eig(const double* G, double* Vst, int n, int r, int nev, double* sig, double* Xout, long long* clk, hipStream_t stream);
-int ttn_wg512_bench_gemm(int m, int n, int k, double* A, double* B, double* C, int ta, int tb, int reps, long long* cycles, int grid, hipStream_t stream);
 int ttn_wg512_selftest_gemm(int m, int n, int k, double* A, double* B, double* C, double alpha, double beta, int ta, int tb, hipStream_t stream);
 }
 
@@ -51,8 +50,6 @@ void* g_scratch = nullptr;
 size_t g_scratch_bytes = 0;
 double* g_dout = nullptr;     // per-train double outputs (dot)
 std::vector<hipEvent_t> g_slots;   // ttn_event_record slots
-int g_prof_batch = 0;
-long long* g_prof = nullptr;       // TTN_PROF=1 diagnostic phase counters of the last compress launch
 int g_dout_cap = 0;
 
 int fail(int code, const char* what) {
@@ -84,13 +81,6 @@ int ensure_scratch(size_t bytes) {
     return TTN_OK;
 }
 bool g_have_launch_ms = false;     // g_ev0 / g_ev1 bracket the last ttn_dot / ttn_orthogonalize kernel (ttn_last_launch_ms)
-int ensure_prof(int batch) {        // TTN_PROF=1: 200 counters per train, zeroed
-    static int prof_cap = 0;
-    if (prof_cap < batch) { if (g_prof) hipFree(g_prof); g_prof = nullptr; HIPCHK(hipMalloc((void**)&g_prof, sizeof(long long) * 200 * batch)); prof_cap = batch; }
-    HIPCHK(hipMemsetAsync(g_prof, 0, sizeof(long long) * 200 * batch, g_stream));
-    g_prof_batch = batch;
-    return TTN_OK;
-}
 int ensure_batch_bufs(int batch) {
     if (batch > g_dout_cap) {
         if (g_dout) { HIPCHK(hipStreamSynchronize(g_stream)); HIPCHK(hipFree(g_dout)); }
@@ -195,10 +185,6 @@ int ttn_init(int device) {
                                (int)(DOT_LDS_BYTES(DOT_MAX_D))));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_selftest_gemm), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)(sizeof(double) * GEMM_LDS_TOTAL)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bench_gemm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(double) * GEMM_LDS_TOTAL)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bench_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(COMPRESS_LDS_BYTES)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tdvp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TDVP_LDS_BYTES));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
     static_assert(sizeof(CompressArgs) > 0, "");
@@ -805,14 +791,6 @@ static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, dou
     P.fused_first_real = fused_first_real;
     if (P.fused) { P.op = fuseA->dev(); P.x = fusex->dev(); }
     else { memset(&P.op, 0, sizeof(P.op)); memset(&P.x, 0, sizeof(P.x)); }
-    P.prof = nullptr;
-    { const char* e = getenv("TTN_PROF_STEP"); P.prof_step = e ? atoi(e) : -1; }
-    if (getenv("TTN_PROF")) {
-        { int rcp = ensure_prof(psi->batch); if (rcp) return rcp; }
-        P.prof = g_prof;
-    }
-    { const char* e = getenv("TTN_JTOL"); P.jtol_mult = e ? atof(e) : 1.0; }
-    { const char* e = getenv("TTN_JNEG"); P.jneg_mult = e ? atof(e) : 1.0; }
     { const char* e = getenv("TTN_FAST"); P.fast = e ? atoi(e) : 1; }
     if (compress_use_wg512(psi->batch)) {
         HIPCHK(hipMemsetAsync(g_next_train, 0, sizeof(int), g_stream));
@@ -1002,9 +980,6 @@ static int launch_chain(int kind, ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, int n, int
     P.sv_out = nullptr; P.sv_steps = 0;
     P.status = z->d_status;                 // the handle the chain writes (kind 2: in place on z)
     P.sweep_stats = z->d_status + batch;
-    P.prof = nullptr; P.prof_step = -1;
-    { const char* e = getenv("TTN_JTOL"); P.jtol_mult = e ? atof(e) : 1.0; }
-    { const char* e = getenv("TTN_JNEG"); P.jneg_mult = e ? atof(e) : 1.0; }
     P.fast = 0;
     P.fused = 0;
     P.rank_rule = rank_rule;
@@ -1139,8 +1114,6 @@ int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol)
     P.pmax = (int)pmax; P.qmax = (int)qmax;
     P.status = z->d_status;
     P.sweep_stats = z->d_status + batch;
-    { const char* e = getenv("TTN_JTOL"); P.jtol_mult = e ? atof(e) : 1.0; }
-    { const char* e = getenv("TTN_JNEG"); P.jneg_mult = e ? atof(e) : 1.0; }
     H.tensors = d_in;
     H.total = total;
     H.index = (int)index - 1;
@@ -1423,8 +1396,6 @@ static int two_site_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, d
     Q.C.status = x->d_status;
     Q.C.sweep_stats = x->d_status + batch;
     Q.C.pmax = (int)pmax; Q.C.qmax = (int)qmax;
-    { const char* e = getenv("TTN_JTOL"); Q.C.jtol_mult = e ? atof(e) : 1.0; }
-    { const char* e = getenv("TTN_JNEG"); Q.C.jneg_mult = e ? atof(e) : 1.0; }
     Q.tol = tol;
     Q.rmax = (int)std::min<int64_t>(rmax, 1 << 30);
     Q.pmax = (int)pmax; Q.qmax = (int)qmax;
@@ -1552,39 +1523,6 @@ int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps) {
     return check_status(psi);
 }
 
-// diagnostic: per-phase cycle counters (100 MHz s_memtime ticks) of train b from the last TTN_PROF=1 compress launch
-int ttn_prof_get(int64_t b, int64_t* out8) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!g_prof || !out8) return fail(TTN_ERR_ARG, "no profile (set TTN_PROF=1)");
-    long long tmp[16];
-    HIPCHK(hipMemcpyAsync(tmp, g_prof + 16 * b, sizeof(tmp), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int i = 0; i < 16; ++i) out8[i] = tmp[i];
-    return TTN_OK;
-}
-int ttn_prof_steps(int64_t b, int64_t* out120) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!g_prof || !out120) return fail(TTN_ERR_ARG, "no profile (set TTN_PROF=1)");
-    long long tmp[120];
-    HIPCHK(hipMemcpyAsync(tmp, g_prof + 16LL * g_prof_batch + 120 * b, sizeof(tmp), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int i = 0; i < 120; ++i) out120[i] = tmp[i];
-    return TTN_OK;
-}
-
-int ttn_prof_fine(int64_t b, int64_t* out64) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!g_prof || !out64) return fail(TTN_ERR_ARG, "no profile (set TTN_PROF=1)");
-    long long tmp[64];
-    HIPCHK(hipMemcpyAsync(tmp, g_prof + 136LL * g_prof_batch + 64 * b, sizeof(tmp), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int i = 0; i < 64; ++i) out64[i] = tmp[i];
-    return TTN_OK;
-}
-
 int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
@@ -1607,8 +1545,6 @@ int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
     P.scratch = (double*)g_scratch; P.scratch_stride = per_train;
     P.ramax = (int)ramax; P.rbmax = (int)rbmax; P.nmax = (int)nmax;
     P.out = g_dout;
-    P.prof = nullptr;
-    if (getenv("TTN_PROF")) { int rcp = ensure_prof(a->batch); if (rcp) return rcp; P.prof = g_prof; }
     HIPCHK(hipEventRecord(g_ev0, g_stream));
     hipLaunchKernelGGL(k_dot_fused, dim3(a->batch), dim3(TTN_WG), DOT_LDS_BYTES(d), g_stream, P);
     HIPCHK(hipGetLastError());
@@ -1676,9 +1612,7 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
     P.center = (int)center - 1;
     P.scratch = (double*)g_scratch; P.scratch_stride = per_train;
     P.mmax = (int)mm; P.rmax = (int)rmax;
-    { const char* e = getenv("TTN_ORTHO_CHOLQR"); P.no_cholqr = e ? (atoi(e) == 0 ? 3 : (atoi(e) == 1 ? 2 : 0)) : 0; }
-    P.prof = nullptr;
-    if (getenv("TTN_PROF")) { int rcp = ensure_prof(x->batch); if (rcp) return rcp; P.prof = g_prof; }
+    { const char* e = getenv("TTN_ORTHO_CHOLQR"); P.no_cholqr = (e && atoi(e) == 1) ? 2 : 0; }
     // Rank <= 64 QTT trains: the ramp sites at the right end by one wave per train (csrc/ttn_ortho_ramp.h), the tall sites and the
     // centre core by the 512-thread kernel (two workgroups per CU, csrc/ttn_ortho512.h), the 1024-thread kernel before them for the
     // left sweep and after them only for the trains they did not finish.  Measured against the single launch (d = 30, rank 64, centre
@@ -1687,7 +1621,7 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
     bool use512 = nmax == 2 && rmax <= 64 && d <= TTN_MAX_D * 8 && center < d;
     for (int k = 0; k < d; ++k) use512 = use512 && x->dims[k] == 2;
     { const char* e = getenv("TTN_ORTHO512"); if (e) use512 = atoi(e) != 0 && nmax == 2 && rmax <= 64 && d <= TTN_MAX_D * 8; }
-    P.mode = 0; P.trains = nullptr; P.ramp = 0;
+    P.mode = 0; P.trains = nullptr;
     P.state = reinterpret_cast<int*>((double*)g_scratch + (size_t)per_train * x->batch);
     g_ortho_state = P.state;
     HIPCHK(hipEventRecord(g_ev0, g_stream));
@@ -1696,13 +1630,10 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
         int* left = P.state + 4 * (size_t)x->batch;                            // count, then the list of trains k_ortho512 did not finish
         HIPCHK(hipMemsetAsync(left, 0, sizeof(int), g_stream));
         // the ramp sites at the right end (wide / square LQ steps) go to one wave per train (csrc/ttn_ortho_ramp.h); the 1024-thread
-        // kernel then only runs the left sweep, and not at all when the centre is the first site.  TTN_ORTHO_RAMP = 0: without.
-        { const char* e = getenv("TTN_ORTHO_RAMP"); P.ramp = e ? (atoi(e) != 0) : 1; }
-        if (!P.ramp || P.center > 0) hipLaunchKernelGGL(k_orthogonalize, dim3(x->batch), dim3(TTN_WG), ORTHO_LDS_BYTES, g_stream, P);
-        if (P.ramp) {
-            P.mode = P.center > 0 ? 4 : 5;
-            hipLaunchKernelGGL(k_ortho_ramp, dim3((x->batch + ORAMP_WG / 64 - 1) / (ORAMP_WG / 64)), dim3(ORAMP_WG), 0, g_stream, P, (int)x->batch);
-        }
+        // kernel then only runs the left sweep, and not at all when the centre is the first site.
+        if (P.center > 0) hipLaunchKernelGGL(k_orthogonalize, dim3(x->batch), dim3(TTN_WG), ORTHO_LDS_BYTES, g_stream, P);
+        P.mode = P.center > 0 ? 4 : 5;
+        hipLaunchKernelGGL(k_ortho_ramp, dim3((x->batch + ORAMP_WG / 64 - 1) / (ORAMP_WG / 64)), dim3(ORAMP_WG), 0, g_stream, P, (int)x->batch);
         hipLaunchKernelGGL(k_ortho512, dim3(x->batch), dim3(O5_WG), O5_LDS_BYTES(d), g_stream, P);
         // the 512-thread kernel finishes a train (centre core included) unless it had to stop — a refused step, a site outside its
         // class: the third launch takes only those trains (1024 heavy workgroups cost 4 ms of dispatch even when they do nothing)
@@ -1754,7 +1685,7 @@ int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const do
 }
 
 // self-test of the 128 x 128 symmetric eigensolver of the Gram route: G (host, column-major) -> sig[nev] = sqrt(eigenvalues)
-// descending, X[128 * r] = sqrt(lam_j) u_j, cycles (s_memtime ticks) and the return code of the device routine
+// descending, X[128 * r] = sqrt(lam_j) u_j, device clock ticks of the whole routine and its return code
 int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, double* sig, double* X, int64_t* ticks_rc) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
@@ -1765,7 +1696,7 @@ int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, doub
     HIPCHK(hipMalloc((void**)&dV, sizeof(double) * 128 * 128));
     HIPCHK(hipMalloc((void**)&dS, sizeof(double) * 128));
     HIPCHK(hipMalloc((void**)&dX, sizeof(double) * 128 * 64));
-    HIPCHK(hipMalloc((void**)&dC, sizeof(long long) * 16));
+    HIPCHK(hipMalloc((void**)&dC, sizeof(long long) * 2));
     HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * n * n, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemsetAsync(dX, 0, sizeof(double) * 128 * 64, g_stream));
     if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {
@@ -1775,61 +1706,13 @@ int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, doub
     hipLaunchKernelGGL(k_selftest_eig128, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, dG, dV, (int)n, (int)r, (int)nev, dS, dX, dC);
     HIPCHK(hipGetLastError());
     }
-    long long hc[16] = {0};
+    long long hc[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(sig, dS, sizeof(double) * nev, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(X, dX, sizeof(double) * 128 * r, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(hc, dC, sizeof(long long) * 16, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(hc, dC, sizeof(hc), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
-    if (ticks_rc) { ticks_rc[0] = hc[0]; ticks_rc[1] = hc[1]; for (int t = 2; t < 6; ++t) ticks_rc[t] = hc[t + 1] - hc[t]; }   // tridiag, bisect, twisted, back-transform
+    if (ticks_rc) { ticks_rc[0] = hc[0]; ticks_rc[1] = hc[1]; }
     hipFree(dG); hipFree(dV); hipFree(dS); hipFree(dX); hipFree(dC);
-    return TTN_OK;
-}
-
-int ttn_bench_gemm(int64_t m, int64_t n, int64_t k, int ta, int tb, int64_t reps, int64_t* cycles_out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!cycles_out || m < 1 || n < 1 || k < 1 || reps < 1) return fail(TTN_ERR_ARG, "bad argument");
-    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-    long long* dcy = nullptr;
-    // TTN_BENCH_GRID workgroups at once, each on its own operands (default 1: one CU busy); TTN_WG512_SELFTEST: the 512-thread build
-    const int grid = getenv("TTN_BENCH_GRID") ? std::max(1, atoi(getenv("TTN_BENCH_GRID"))) : 1;
-    HIPCHK(hipMalloc((void**)&dA, sizeof(double) * m * k * grid));
-    HIPCHK(hipMalloc((void**)&dB, sizeof(double) * k * n * grid));
-    HIPCHK(hipMalloc((void**)&dC, sizeof(double) * m * n * grid));
-    HIPCHK(hipMalloc((void**)&dcy, sizeof(long long)));
-    HIPCHK(hipMemsetAsync(dA, 0, sizeof(double) * m * k * grid, g_stream));
-    HIPCHK(hipMemsetAsync(dB, 0, sizeof(double) * k * n * grid, g_stream));
-    HIPCHK(hipMemsetAsync(dC, 0, sizeof(double) * m * n * grid, g_stream));
-    if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {
-        const int rc512 = ttn_wg512_bench_gemm((int)m, (int)n, (int)k, dA, dB, dC, ta, tb, (int)reps, dcy, grid, g_stream);
-        if (rc512) return hipfail((hipError_t)rc512, "k_bench_gemm (512-thread build)");
-    } else {
-    hipLaunchKernelGGL(k_bench_gemm, dim3(grid), dim3(TTN_WG), sizeof(double) * GEMM_LDS_TOTAL, g_stream, (int)m, (int)n, (int)k,
-                       dA, dB, dC, ta, tb, (int)reps, dcy);
-    HIPCHK(hipGetLastError());
-    }
-    long long cy = 0;
-    HIPCHK(hipMemcpyAsync(&cy, dcy, sizeof(long long), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    *cycles_out = cy;
-    hipFree(dA); hipFree(dB); hipFree(dC); hipFree(dcy);
-    return TTN_OK;
-}
-
-int ttn_bench_lds(int what, int64_t n, int64_t reps, int64_t* cycles_out, int64_t* sweeps_out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!cycles_out || n < 1 || n > 128 || reps < 1 || what < 0 || what > 2) return fail(TTN_ERR_ARG, "bad argument");
-    long long* dout = nullptr;
-    HIPCHK(hipMalloc((void**)&dout, 2 * sizeof(long long)));
-    hipLaunchKernelGGL(k_bench_lds, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, what, (int)n, (int)reps, dout);
-    HIPCHK(hipGetLastError());
-    long long h[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(h, dout, sizeof(h), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    *cycles_out = h[0];
-    if (sweeps_out) *sweeps_out = h[1];
-    hipFree(dout);
     return TTN_OK;
 }
 

@@ -18,7 +18,7 @@
 //   chol_lds128_teams               blocked LDS Cholesky with lookahead, one or two matrices at once
 //   wg_svd_cols / wg_rank_rule / wg_check_diag, wg_materialize_core / wg_fused_merge, wg_bond_step, k_compress
 //                                   the bond step (routes F / G / H, fused apply) and the persistent sweep kernel
-//   k_dot, k_selftest_gemm, k_bench_gemm, k_bench_lds
+//   k_dot, k_selftest_gemm
 // Sibling headers (included after this one by ttn_api.hip): ttn_eig_kernels.h (symmetric eigensolver of the Gram routes, called
 // from the bond step through the forward declarations below), ttn_ortho_kernels.h, ttn_hsvd_kernels.h (ttv_decomp, SVD moves),
 // ttn_als_kernels.h (als_linsolve / mals_linsolve).
@@ -34,13 +34,8 @@
 // latency-bound phase (an eigensolver's serial chain, a Cholesky pivot, a Jacobi sweep) while the other streams MFMAs; the
 // latency-bound waves issue first.  Levels: TTN_PRIO_BASE for everything that is not a matrix product, 0 inside the matrix-product
 // routines, higher inside the eigensolver (ttn_eig_kernels.h).
-#ifdef TTN_PRIO_BASE
 #define TTN_SETPRIO_GEMM() __builtin_amdgcn_s_setprio(0)
 #define TTN_SETPRIO_BASE() __builtin_amdgcn_s_setprio(TTN_PRIO_BASE)
-#else
-#define TTN_SETPRIO_GEMM()
-#define TTN_SETPRIO_BASE()
-#endif
 // LDS leading dimension (doubles) of the staged chunks, 145 = 17 mod 32.  Two access patterns meet here:
 //  * a k-fast operand is staged by 16 lanes that walk k (coalesced global reads) and store to As[kk*LD + r]: an even LD
 //    puts all 16 stores on ONE bank pair (16-way conflict: measured 49 % of the MFMA peak with LD = 144, stores alone
@@ -61,19 +56,6 @@
 #define TTN_LDS_COLS (TTN_LDS_IMG / 128)           // columns of a leading-dimension-128 image
 #define GEMM_LDS_DOUBLES (TTN_LDS_IMG + 512)       // LDS region every GEMM may use (the one-shot small GEMM uses all of it): the
                                                    // image + room for the odd leading dimensions of a 64x64x128 one-shot product
-// Call-boundary policy of the big building blocks (experiments: -DTTN_NI_JACOBI=inline etc.)
-#ifndef TTN_NI_JACOBI
-#define TTN_NI_JACOBI __noinline__
-#endif
-#ifndef TTN_NI_CHOL
-#define TTN_NI_CHOL __noinline__
-#endif
-#ifndef TTN_NI_GEMM
-#define TTN_NI_GEMM __noinline__
-#endif
-#ifndef TTN_NI_GEMMS
-#define TTN_NI_GEMMS __noinline__
-#endif
 #define QR_NB 16                         // Householder panel width
 #define JACOBI_MAX_SWEEPS 40
 
@@ -284,7 +266,7 @@ __device__ inline void gemm_publish_amax(const lds_gdesc* dsc, double cmax) {
 // WR = wave rows of the 16-wave grid (WR x 16/WR waves, 32x32 outputs per wave): 4 -> 128x128 output tiles, 2 -> 64x256
 // (for m <= 64 and wide n, where half the waves of the square grid would idle).
 template <int WR>
-__device__ TTN_NI_GEMM void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
+__device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
     const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
     constexpr int WCN = TTN_NWAVES / WR;                 // wave columns
     constexpr int BM = 32 * WR, BN = 32 * WCN;
@@ -388,9 +370,6 @@ __device__ TTN_NI_GEMM void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
                 _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs0[bkk[u] * LDB + bc[u]] = bv0[u];
             }
             __syncthreads();
-#ifdef TTN_GEMM_PRIO
-            __builtin_amdgcn_s_setprio(TTN_GEMM_PRIO);       // experiment: the matrix-pipe phase ahead of a co-resident workgroup's latency-bound phase
-#endif
             for (int c = 0; c < nch; ++c) {
                 // The staging work of the other chunks is placed BETWEEN this wave's MFMA groups: an MFMA occupies the
                 // matrix pipe for 64 clk, so the VALU/LDS/global instructions issued behind it run under the MFMAs of
@@ -420,9 +399,6 @@ __device__ TTN_NI_GEMM void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
 #undef GEMM_MFMA_STEP
                 __syncthreads();
             }
-#ifdef TTN_GEMM_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
 #undef GEMM_FILL_TAB
 #undef GEMM_LOAD
 #undef GEMM_STORE
@@ -469,7 +445,7 @@ __device__ TTN_NI_GEMM void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
 __device__ inline int small_ld(int x) { const int t = (x + 15) & ~15; return (((t & 31) == 16) ? t : t + 16) + 1; }   // == 17 mod 32 (see GEMM_LD)
 __device__ inline int tight_ld(int x) { return ((x + 15) & ~15) + 1; }                                             // odd: conflict-free k-fast stores
 
-__device__ TTN_NI_GEMMS void wg_gemm_small_impl(const GemmDesc* dsc_, double* lds) {
+__device__ __noinline__ void wg_gemm_small_impl(const GemmDesc* dsc_, double* lds) {
     const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
     const int m = uni32(dsc->m), n = uni32(dsc->n), k = uni32(dsc->k);
     const View A = ldsView(&dsc->A), B = ldsView(&dsc->B), C = ldsView(&dsc->C);
@@ -630,7 +606,7 @@ __device__ inline void wg_gemm(int m, int n, int k, View A, View B, View C, doub
 // -------------------------------------------------------------------------------------------------
 #define SYRK_QMAX (2 * GEMM_TAB_ENTRIES - 128)           // k offsets tabulated once (32-bit entries behind the descriptor)
 template <int KC16, int JMAX, int MAXT>
-__device__ TTN_NI_GEMM void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
+__device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
     const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
     constexpr int KC = 16 * KC16, RG = TTN_WG / 16;                 // k per chunk; row groups (16 lanes walk k)
     const int p = uni32(dsc->m), q = uni32(dsc->k);
@@ -740,7 +716,7 @@ __device__ inline void wg_syrk(int p, int q, View A, View G, double alpha, doubl
 // tiled GEMM ran these shapes at 21 % of the matrix pipe with two workgroups per CU.
 // -------------------------------------------------------------------------------------------------
 #define GEMM_RA_NMAX (2 * GEMM_TAB_ENTRIES - 320)           // column offsets of B tabulated once
-__device__ TTN_NI_GEMM void wg_gemm_ra_impl(const GemmDesc* dsc_, double* lds) {
+__device__ __noinline__ void wg_gemm_ra_impl(const GemmDesc* dsc_, double* lds) {
     const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
     constexpr int CG = TTN_NWAVES / 4, NC = 16 * CG;                // column groups of waves; columns per chunk (32 / 64)
     constexpr int LD = (NC == 32) ? 49 : 81;                       // == 17 mod 32
@@ -1113,7 +1089,6 @@ __device__ __noinline__ void wg_lq_blocked(int p, int q, double* M2, int ld, dou
     lds_gemm = unip(lds_gemm); Ts = unip(Ts); Ss = unip(Ss); taus = unip(taus); red = unip(red);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = TTN_WG >> 6;
     const int rr = min(p, q);
-#ifndef TTN_NO_LDS_LQ
     if (Qout && rr == p && p <= 128 && 2LL * p * q <= GEMM_LDS_DOUBLES) {       // small cores: factor AND explicit Q' in LDS
         lq_lds_whole_q(p, q, M2, ld, Qout, lds_gemm, Ss, Ts);
         return;
@@ -1138,7 +1113,6 @@ __device__ __noinline__ void wg_lq_blocked(int p, int q, double* M2, int ld, dou
             return;
         }
     }
-#endif
     double* betas = Ss;                                  // QR_NB (Ss is free while a panel is being factored)
     double* scl = Ss + QR_NB;                            // QR_NB
     for (int j0 = 0; j0 < rr; j0 += QR_NB) {
@@ -1318,12 +1292,12 @@ __device__ __noinline__ void wg_lq_blocked(int p, int q, double* M2, int ld, dou
 // ordering, one wave per column pair, lanes over rows.  Returns the number of sweeps used
 // (negative if the sweep limit was hit).  X may live in LDS or in global memory.
 // -------------------------------------------------------------------------------------------------
-__device__ __noinline__ int wg_jacobi_cols(int m, int p, double* X, int ldx, int* flag /*LDS*/, double* red /*LDS*/, double tol_mult, double neg_mult, double* aneg_out /*LDS*/) {
+__device__ __noinline__ int wg_jacobi_cols(int m, int p, double* X, int ldx, int* flag /*LDS*/, double* red /*LDS*/, double* aneg_out /*LDS*/) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = TTN_WG >> 6;
     if (p < 2) { if (tid == 0) *aneg_out = 0.0; __syncthreads(); return 0; }
     const int pe = p + (p & 1);               // even number of slots; slot p (if odd) is a bye
     const int half = pe >> 1;
-    const double tol = tol_mult * sqrt((double)m) * DBL_EPSILON;
+    const double tol = sqrt((double)m) * DBL_EPSILON;
     // columns whose norm is below eps*sqrt(m)*(largest column norm) carry singular values below what fp64
     // can resolve against sigma_max; they are left alone (rotating pure rounding noise never converges)
     double amax = 0.0;
@@ -1333,7 +1307,7 @@ __device__ __noinline__ int wg_jacobi_cols(int m, int p, double* X, int ldx, int
         amax = fmax(amax, wave_sum(a));
     }
     amax = wg_max(amax, red);
-    const double aneg = neg_mult * neg_mult * (double)m * DBL_EPSILON * DBL_EPSILON * amax;
+    const double aneg = (double)m * DBL_EPSILON * DBL_EPSILON * amax;
     if (tid == 0) *aneg_out = aneg;
     int sweep = 0;
     for (; sweep < JACOBI_MAX_SWEEPS; ++sweep) {
@@ -1433,7 +1407,7 @@ __device__ inline double grp_from_next(double v) { return dpp_mov_f64<0x12C>(v);
 // negligible-column threshold of the WHOLE matrix instead of the one of the columns at hand (aneg_fixed < 0: compute it).
 template <int NT2, int LD>
 __device__ int jacobi_lds128_body(int m, int p, lds_f64* X, lds_f64* nrm2, int* flag, double* red,
-                                  double tol_mult, double neg_mult, double* aneg_out, int max_sweeps = JACOBI_MAX_SWEEPS,
+                                  double* aneg_out, int max_sweeps = JACOBI_MAX_SWEEPS,
                                   bool cross_only = false, double aneg_fixed = -1.0) {
     constexpr int CMASK = TTN_LDS_IMG / LD - 1;         // columns the LDS image holds, minus one
     constexpr int G = 4;                                // lane groups per wave = columns per block
@@ -1444,7 +1418,7 @@ __device__ int jacobi_lds128_body(int m, int p, lds_f64* X, lds_f64* nrm2, int* 
     const int sub = (lane & 3) | ((lane >> 4) << 2);
     const int roff = 2 * sub;                           // row offset inside a piece
 #define JOFF(t) (roff + CH * (t))
-    const double tol = tol_mult * sqrt((double)m) * DBL_EPSILON;
+    const double tol = sqrt((double)m) * DBL_EPSILON;
     const double tol2 = tol * tol;
     double aneg = 0.0;
     int sweep = 0;
@@ -1470,7 +1444,7 @@ __device__ int jacobi_lds128_body(int m, int p, lds_f64* X, lds_f64* nrm2, int* 
             if (aneg_fixed >= 0.0) aneg = aneg_fixed;
             else {
                 amax = wg_max(amax, red);
-                aneg = neg_mult * neg_mult * (double)m * DBL_EPSILON * DBL_EPSILON * amax;
+                aneg = (double)m * DBL_EPSILON * DBL_EPSILON * amax;
                 if (tid == 0) *aneg_out = aneg;
             }
         }
@@ -1641,15 +1615,15 @@ __device__ int jacobi_lds128_body(int m, int p, lds_f64* X, lds_f64* nrm2, int* 
 
 // Fast path of the one-sided Jacobi: p <= 128 columns of length m <= 128 in LDS, leading dimension 128; rows
 // [m, 128) of every column must be ZERO (the caller pads).  See jacobi_lds128_body.
-__device__ TTN_NI_JACOBI int wg_jacobi_lds128(int m, int p, double* Xg, double* nrm2g, int* flag, double* red,
-                                             double tol_mult, double neg_mult, double* aneg_out /*LDS*/) {
+__device__ __noinline__ int wg_jacobi_lds128(int m, int p, double* Xg, double* nrm2g, int* flag, double* red,
+                                             double* aneg_out /*LDS*/) {
     if (p < 2) { if (threadIdx.x == 0) *aneg_out = 0.0; __syncthreads(); return 0; }
     lds_f64* X = (lds_f64*)Xg;
     lds_f64* nrm2 = (lds_f64*)nrm2g;
-    if (m <= 32) return jacobi_lds128_body<1, 128>(m, p, X, nrm2, flag, red, tol_mult, neg_mult, aneg_out);
-    if (m <= 64) return jacobi_lds128_body<2, 128>(m, p, X, nrm2, flag, red, tol_mult, neg_mult, aneg_out);
-    if (m <= 96) return jacobi_lds128_body<3, 128>(m, p, X, nrm2, flag, red, tol_mult, neg_mult, aneg_out);     // the 96-column ramp step
-    return jacobi_lds128_body<4, 128>(m, p, X, nrm2, flag, red, tol_mult, neg_mult, aneg_out);
+    if (m <= 32) return jacobi_lds128_body<1, 128>(m, p, X, nrm2, flag, red, aneg_out);
+    if (m <= 64) return jacobi_lds128_body<2, 128>(m, p, X, nrm2, flag, red, aneg_out);
+    if (m <= 96) return jacobi_lds128_body<3, 128>(m, p, X, nrm2, flag, red, aneg_out);     // the 96-column ramp step
+    return jacobi_lds128_body<4, 128>(m, p, X, nrm2, flag, red, aneg_out);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1682,7 +1656,7 @@ __device__ inline void jb_store(const lds_f64* X, int col0_lds, double* Xg, int 
 
 template <int LD, int JBW>
 __device__ int jacobi_blocked_body(int m, int p, double* Xg, int ldx, double* Xlds, double* nrm2g, int* flag, double* red,
-                                   double tol_mult, double neg_mult, double* aneg_out /*LDS*/) {
+                                   double* aneg_out /*LDS*/) {
     static_assert(2 * JBW * LD <= TTN_LDS_IMG, "two column blocks must fit the LDS image");
     m = uni32(m); p = uni32(p); ldx = uni32(ldx);
     Xg = unip(Xg); Xlds = unip(Xlds); nrm2g = unip(nrm2g); flag = unip(flag); red = unip(red); aneg_out = unip(aneg_out);
@@ -1697,7 +1671,7 @@ __device__ int jacobi_blocked_body(int m, int p, double* Xg, int ldx, double* Xl
         amax = fmax(amax, wave_sum(a));
     }
     amax = wg_max(amax, red);
-    const double aneg = neg_mult * neg_mult * (double)m * DBL_EPSILON * DBL_EPSILON * amax;
+    const double aneg = (double)m * DBL_EPSILON * DBL_EPSILON * amax;
     if (tid == 0) *aneg_out = aneg;
     __syncthreads();
     const int nbk = (p + JBW - 1) / JBW;
@@ -1708,7 +1682,7 @@ __device__ int jacobi_blocked_body(int m, int p, double* Xg, int ldx, double* Xl
             __syncthreads();
             jb_load<LD, JBW>(X, 0, Xg, ldx, I * JBW, nI, m);
             __syncthreads();
-            const int r = jacobi_lds128_body<LD / 32, LD>(m, nI, X, nrm2, flag, red, tol_mult, neg_mult, aneg_out, 1, false, aneg);
+            const int r = jacobi_lds128_body<LD / 32, LD>(m, nI, X, nrm2, flag, red, aneg_out, 1, false, aneg);
             if (r < 0) { any = 1; jb_store<LD, JBW>(X, 0, Xg, ldx, I * JBW, nI, m); }
         }
         for (int I = 0; I + 1 < nbk; ++I)                                          // (b) between every two blocks
@@ -1718,7 +1692,7 @@ __device__ int jacobi_blocked_body(int m, int p, double* Xg, int ldx, double* Xl
                 jb_load<LD, JBW>(X, 0, Xg, ldx, I * JBW, JBW, m);
                 jb_load<LD, JBW>(X, JBW, Xg, ldx, J * JBW, nJ, m);
                 __syncthreads();
-                const int r = jacobi_lds128_body<LD / 32, LD>(m, JBW + nJ, X, nrm2, flag, red, tol_mult, neg_mult, aneg_out, 1, true, aneg);
+                const int r = jacobi_lds128_body<LD / 32, LD>(m, JBW + nJ, X, nrm2, flag, red, aneg_out, 1, true, aneg);
                 if (r < 0) {
                     any = 1;
                     jb_store<LD, JBW>(X, 0, Xg, ldx, I * JBW, JBW, m);
@@ -1732,14 +1706,14 @@ __device__ int jacobi_blocked_body(int m, int p, double* Xg, int ldx, double* Xl
 }
 // 128 < p <= 256 (ranks 65..128): image leading dimension 256, as many columns per block as two blocks fit the image
 __device__ __noinline__ int wg_jacobi_blocked256(int m, int p, double* Xg, int ldx, double* Xlds, double* nrm2g, int* flag, double* red,
-                                                 double tol_mult, double neg_mult, double* aneg_out /*LDS*/) {
-    return jacobi_blocked_body<256, TTN_LDS_IMG / 512>(m, p, Xg, ldx, Xlds, nrm2g, flag, red, tol_mult, neg_mult, aneg_out);
+                                                 double* aneg_out /*LDS*/) {
+    return jacobi_blocked_body<256, TTN_LDS_IMG / 512>(m, p, Xg, ldx, Xlds, nrm2g, flag, red, aneg_out);
 }
 #if TTN_LDS_COLS < 128
 // TTN_LDS_COLS < p <= 128 in the small-image build: the same blocked scheme with leading dimension 128
 __device__ __noinline__ int wg_jacobi_blocked128(int m, int p, double* Xg, int ldx, double* Xlds, double* nrm2g, int* flag, double* red,
-                                                 double tol_mult, double neg_mult, double* aneg_out /*LDS*/) {
-    return jacobi_blocked_body<128, TTN_LDS_IMG / 256>(m, p, Xg, ldx, Xlds, nrm2g, flag, red, tol_mult, neg_mult, aneg_out);
+                                                 double* aneg_out /*LDS*/) {
+    return jacobi_blocked_body<128, TTN_LDS_IMG / 256>(m, p, Xg, ldx, Xlds, nrm2g, flag, red, aneg_out);
 }
 #endif
 
@@ -1876,11 +1850,11 @@ __device__ int chol_lds128_teams(int n, double* Gg, double* red, int* flag, doub
     return bad;
 }
 
-__device__ TTN_NI_CHOL int wg_chol_lds128(int n, double* Gg, double* red, int* flag, double* pivmin_out /*LDS*/) {
+__device__ __noinline__ int wg_chol_lds128(int n, double* Gg, double* red, int* flag, double* pivmin_out /*LDS*/) {
     return chol_lds128_teams<1>(n, Gg, red, flag, pivmin_out);
 }
 // two n x n matrices (n <= TTN_LDS_COLS / 2) at Gg and Gg + TTN_LDS_IMG / 2; red: 64 doubles; pivmin_out: 2 doubles
-__device__ TTN_NI_CHOL int wg_chol2_lds128(int n, double* Gg, double* red64, int* flag, double* pivmin_out2 /*LDS*/) {
+__device__ __noinline__ int wg_chol2_lds128(int n, double* Gg, double* red64, int* flag, double* pivmin_out2 /*LDS*/) {
     return chol_lds128_teams<2>(n, Gg, red64, flag, pivmin_out2);
 }
 
@@ -1901,14 +1875,9 @@ struct CompressArgs {
     int sv_steps;
     int* status;           // [batch] device: 0 ok, 1 = Jacobi did not converge
     int* sweep_stats;      // [batch] device: total Jacobi sweeps (diagnostics)
-    double jtol_mult;      // Jacobi convergence threshold = jtol_mult * sqrt(m) * eps
-    long long* prof;       // null, or cycle counters per phase (TTN_PROF=1 diagnostic launches only)
-    double jneg_mult;      // columns below jneg_mult * sqrt(m) * eps * max column norm are treated as zero
     int fast;              // 0: Householder route only; odd: try the Gram / factored fast paths (verified a posteriori) first.
                            // Diagnostic bits (TTN_FAST): 2 no eigensolver in route G (Cholesky + Jacobi), 4 none in route F,
-                           // 8 no diagonal-left shortcut in route F, 16 no Jacobi polish after a failed conditioning test, 32 no CholeskyQR2,
-                           // 64 Gram / reflector / check matrices in their own scratch instead of the dead T buffer, 128 two-pass fused merge,
-                           // 512 no barrier-free (direct) form of the one-pass merge, 1024 no LDS-only path for the tiny steps
+                           // 8 no diagonal-left shortcut in route F, 16 no Jacobi polish after a failed conditioning test
     // fused apply (ttn_apply_compress): psi = A * x is never materialised.  During the FIRST L->R sweep core k+1 of psi
     // is still virtual (= A_{k+1} applied to x_{k+1}); psi's ranks already hold A.rks .* x.rks.
     int fused;
@@ -1918,7 +1887,6 @@ struct CompressArgs {
                            //    (_swap_adjacent_sites, src/qtt_tools.jl:680-685)
     int fused_first_real;  // fused bond range (k_single < 0, ascending): the left core of the first bond is already real (a boundary core
                            // imported from the left neighbour of a core-wise sharded chain); otherwise it is written out first
-    int prof_step;         // TTN_PROF_STEP: the phase counters of P.prof collect this step only (-1: every step)
     int* next_train;       // null: one workgroup per train (grid = batch).  Else a device counter (zeroed before the launch): the grid is
                            // PERSISTENT — workgroup w starts with train w and then pulls train gridDim.x + atomicAdd(next_train, 1)
                            // until the batch is exhausted (dynamic balancing of the data-dependent sweep counts, scratch per slot)
@@ -2154,13 +2122,13 @@ __device__ __noinline__ void wg_scale_t12_diag(const double* img, const double* 
 __device__ int wg_svd_cols(const CompressArgs& P, const BondCtx& S, int pj, double* X, int ldx, bool in_lds, int mlen = 0) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = TTN_WG >> 6;
     // mlen: column length if it is not pj (LDS image only: the polish step of the Gram route runs r columns of length q)
-    const int nsw = (in_lds && mlen) ? wg_jacobi_lds128(mlen, pj, X, S.nrm2, S.iflag, S.red, P.jtol_mult, P.jneg_mult, S.scal)
-                  : in_lds ? wg_jacobi_lds128(pj, pj, X, S.nrm2, S.iflag, S.red, P.jtol_mult, P.jneg_mult, S.scal)
+    const int nsw = (in_lds && mlen) ? wg_jacobi_lds128(mlen, pj, X, S.nrm2, S.iflag, S.red, S.scal)
+                  : in_lds ? wg_jacobi_lds128(pj, pj, X, S.nrm2, S.iflag, S.red, S.scal)
 #if TTN_LDS_COLS < 128
-                  : (pj <= 128) ? wg_jacobi_blocked128(pj, pj, X, ldx, S.ldsX, S.nrm2, S.iflag, S.red, P.jtol_mult, P.jneg_mult, S.scal)
+                  : (pj <= 128) ? wg_jacobi_blocked128(pj, pj, X, ldx, S.ldsX, S.nrm2, S.iflag, S.red, S.scal)
 #endif
-                  : (pj <= 256) ? wg_jacobi_blocked256(pj, pj, X, ldx, S.ldsX, S.nrm2, S.iflag, S.red, P.jtol_mult, P.jneg_mult, S.scal)
-                                : wg_jacobi_cols(pj, pj, X, ldx, S.iflag, S.red, P.jtol_mult, P.jneg_mult, S.scal);
+                  : (pj <= 256) ? wg_jacobi_blocked256(pj, pj, X, ldx, S.ldsX, S.nrm2, S.iflag, S.red, S.scal)
+                                : wg_jacobi_cols(pj, pj, X, ldx, S.iflag, S.red, S.scal);
     for (int c = wave; c < pj; c += nwaves) {
         double a = 0.0;
         for (int r = lane; r < (mlen ? mlen : pj); r += 64) { const double v = X[(long long)c * ldx + r]; a = fma(v, v, a); }
@@ -2261,7 +2229,7 @@ __device__ void wg_materialize_core(const CompressArgs& P, int b, int k) {
 // ---- the same merge in ONE pass, with the operator contraction in the GEMM epilogue (n2 = 2, small operator ranks) -----------------
 // The first version (wg_fused_merge below, still the general path) runs Rl separate GEMMs into a buffer T (Rl p n2 rho_r doubles,
 // 393 KB for the benchmark's steps), and a second pass reads T back, contracts with the operator core and writes M: measured inside
-// the kernel (TTN_PROF, 512-thread build, two workgroups per CU) 349 k clk for the three GEMMs — 14 % of the matrix pipe each: K = 64
+// the kernel (cycle counters, 512-thread build, two workgroups per CU) 349 k clk for the three GEMMs — 14 % of the matrix pipe each: K = 64
 // is all prologue — plus 191 k clk for the contraction pass, per bond step.  Here a wave keeps the Rl accumulators T_a'[16 rows,
 // 16 (j, nu) columns] of its tiles in registers: they share every B fragment (x is read once, not Rl times), and when the K loop is
 // done the lane that holds column (j, nu) forms its share sum_a' T_a' A[s, j, a', a] of the n2 Rr outputs of that (row, nu), adds its
@@ -2402,10 +2370,7 @@ __device__ __noinline__ bool wg_fused_merge_mfma(double* ck, const double* xc, c
 // MFMA operand registers, four k-steps ahead of their use: no LDS staging of C_k, no barrier between the staging of x and the epilogue.
 // Same tiling (a wave = one 16-row tile x two 16-column tiles x Rl accumulators), same epilogue.
 __device__ __noinline__ bool wg_fused_merge_direct(double* ck, const double* xc, const double* ac, double* M, int p, int q, int n1, int Dl,
-                                                   int rhl, int rhr, int Rl, int Rr, double* lds, double* amax_lds, double* red, long long* stamps) {
-    stamps = unip(stamps);
-#define FMD_STAMP(i) if (stamps && threadIdx.x == 0) stamps[i] = (long long)__builtin_amdgcn_s_memtime();
-    FMD_STAMP(0)
+                                                   int rhl, int rhr, int Rl, int Rr, double* lds, double* amax_lds, double* red) {
     ck = unip(ck); xc = unip(xc); ac = unip(ac); M = unip(M); lds = unip(lds); amax_lds = unip(amax_lds); red = unip(red);
     p = uni32(p); q = uni32(q); n1 = uni32(n1); Dl = uni32(Dl); rhl = uni32(rhl); rhr = uni32(rhr); Rl = uni32(Rl); Rr = uni32(Rr);
     constexpr int n2 = 2;
@@ -2445,7 +2410,6 @@ __device__ __noinline__ bool wg_fused_merge_direct(double* ck, const double* xc,
         }
     }
     __syncthreads();
-    FMD_STAMP(1)
     const long long ldk = (long long)n1 * Dl;                        // column stride of C_k as a (n1 Dl) x (Rl rho_l) matrix
     const int wr = wave % WR, wc = wave / WR;
     const int ksteps = rhl >> 2, ngrp = ksteps >> 2;                 // groups of four k-steps
@@ -2487,7 +2451,6 @@ __device__ __noinline__ bool wg_fused_merge_direct(double* ck, const double* xc,
                     for (int a1 = 0; a1 < 3; ++a1) cur[t][a1] = nxt[t][a1];
             }
 #undef FMD_LOAD
-            if (rb == 0 && c0 == 0) { FMD_STAMP(2) }
             // ---- epilogue: lane (li, lk) holds T_a'[row = lk + 4 reg][column li] of its two column tiles; column = j + n2 nu.
             // Both lanes of a (j = 0, 1) pair end up with all nout sums of their (row, nu); the pair then writes the nout consecutive
             // doubles M[row, nout nu ...] as two contiguous halves (lane j = 0 the first nout / 2, lane j = 1 the rest), 16 bytes at a
@@ -2555,22 +2518,18 @@ __device__ __noinline__ bool wg_fused_merge_direct(double* ck, const double* xc,
                 }
             }
             }
-            if (rb == 0 && c0 == 0) { FMD_STAMP(3) }
         }
     }
-    FMD_STAMP(4)
     cmax = wg_max(cmax, red);
     if (tid == 0) *amax_lds = cmax;
     __syncthreads();
-    FMD_STAMP(5)
-#undef FMD_STAMP
     return true;
 }
 
 
 #define FUSE_MAX_TERMS 16
 __device__ bool wg_fused_merge(const CompressArgs& P, int b, int k, int p, int q, const View& Am, double* M, double* Tbuf,
-                               long long tbuf_doubles, double* lds, double* amax_lds, double* red, long long* stamps = nullptr) {
+                               long long tbuf_doubles, double* lds, double* amax_lds, double* red) {
     const TTDev& T = P.tt;
     const int n1 = T.dims[k], n2 = T.dims[k + 1];
     const long long* rks = T.rks + (long long)b * (T.d + 1);
@@ -2586,8 +2545,8 @@ __device__ bool wg_fused_merge(const CompressArgs& P, int b, int k, int p, int q
     const double* ac = P.op.data + P.op.off[k + 1];
     TTN_SETPRIO_GEMM();
     struct PrioRestore { __device__ ~PrioRestore() { TTN_SETPRIO_BASE(); } } prio_restore_;
-    if (n2 == 2 && !(P.fast & 128) && !(P.fast & 512) && wg_fused_merge_direct(ck, xc, ac, M, p, q, n1, Dl, rhl, rhr, Rl, Rr, lds, amax_lds, red, stamps)) return true;
-    if (n2 == 2 && !(P.fast & 128) && wg_fused_merge_mfma(ck, xc, ac, M, p, q, n1, Dl, rhl, rhr, Rl, Rr, lds, amax_lds, red)) return true;
+    if (n2 == 2 && wg_fused_merge_direct(ck, xc, ac, M, p, q, n1, Dl, rhl, rhr, Rl, Rr, lds, amax_lds, red)) return true;
+    if (n2 == 2 && wg_fused_merge_mfma(ck, xc, ac, M, p, q, n1, Dl, rhl, rhr, Rl, Rr, lds, amax_lds, red)) return true;
     const long long ldk = (long long)n1 * Dl;                           // column stride of C_k viewed as (n1*Dl) x r_mid
     for (int a1 = 0; a1 < Rl; ++a1) {
         const View Av = mkview(ck + a1 * ldk, Am.r, plain((long long)Rl * ldk));
@@ -2640,16 +2599,14 @@ __device__ bool wg_fused_merge(const CompressArgs& P, int b, int k, int p, int q
 //   the rows are at most 256 long) with the same rotations applied to a p x p identity — rows of the result are sigma_i v_i^T, the
 //   rotated identity is U^T;  sort, rank rule, and U sqrt(S) / sqrt(S) V^T are written straight from LDS.
 // Same conventions as the Householder route: units of s0 = max |M|, negligible rows (norm^2 <= aneg) are left alone and come out as
-// exact zeros, convergence when a whole sweep rotates nothing (|g| <= tol sqrt(a b), tol = jtol_mult sqrt(q) eps).
+// exact zeros, convergence when a whole sweep rotates nothing (|g| <= tol sqrt(a b), tol = sqrt(q) eps).
 // -------------------------------------------------------------------------------------------------
-#ifndef SMALL_STEP_PMAX
 #define SMALL_STEP_PMAX 8
-#endif
 #define SMALL_STEP_QMAX 256
 // (Everything it needs of the kernel's argument block and of the step's context comes BY VALUE in SmallStepArgs: a reference to either
 // would force the caller — the force-inlined bond step, at its register limit — to keep them in memory: +280 spilled VGPRs, -6 % measured.)
 struct SmallStepArgs {
-    double jneg_mult, jtol_mult, truncerr;
+    double truncerr;
     long long max_bond;
     int rank_rule, pmax;
     double* sv_row;              // null, or the pmax singular values of this (train, step)
@@ -2668,7 +2625,7 @@ __device__ __noinline__ int wg_bond_small(SmallStepArgs Q, double* ck, double* c
     const int p = wide ? mr : mc, q = wide ? mc : mr;
     const View Ap = wide ? Am : tview(Bm);       // p x rm
     const View Bp = wide ? Bm : tview(Am);       // rm x q
-    Q.jneg_mult = unif64(Q.jneg_mult); Q.jtol_mult = unif64(Q.jtol_mult); Q.truncerr = unif64(Q.truncerr); Q.max_bond = uni64(Q.max_bond);
+    Q.truncerr = unif64(Q.truncerr); Q.max_bond = uni64(Q.max_bond);
     Q.rank_rule = uni32(Q.rank_rule); Q.pmax = uni32(Q.pmax); Q.sv_row = unip(Q.sv_row); Q.status_b = unip(Q.status_b);
     Q.red = unip(Q.red); Q.scal = unip(Q.scal); Q.sigs = unip(Q.sigs); Q.perm = unip(Q.perm); Q.iflag = unip(Q.iflag);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2705,8 +2662,8 @@ __device__ __noinline__ int wg_bond_small(SmallStepArgs Q, double* ck, double* c
         amax = fmax(amax, a);
     }
     amax = unif64(wg_max(amax, Q.red));
-    const double aneg = Q.jneg_mult * Q.jneg_mult * (double)q * DBL_EPSILON * DBL_EPSILON * amax;
-    const double tol = Q.jtol_mult * sqrt((double)q) * DBL_EPSILON, tol2 = tol * tol;
+    const double aneg = (double)q * DBL_EPSILON * DBL_EPSILON * amax;
+    const double tol = sqrt((double)q) * DBL_EPSILON, tol2 = tol * tol;
     if (tid == 0) Q.scal[0] = aneg;
     // ---- one-sided Jacobi on the rows ----
     const int pe = p + (p & 1), half = pe >> 1;
@@ -2817,7 +2774,7 @@ __device__ __noinline__ int wg_bond_small(SmallStepArgs Q, double* ck, double* c
 // (left rank, physical index of core k+1) and its column index from (physical index of core k, right rank), and the factors
 // are U and S*Vt instead of U sqrt(S), sqrt(S) Vt.  Only route H is used (the swapped matrices are rank deficient by design).
 // symmetric eigensolver of the Gram route (ttn_eig_kernels.h, included after this header by the translation unit)
-__device__ int wg_eig128(const double* Gg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork, long long* prof);
+__device__ int wg_eig128(const double* Gg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork);
 __device__ int wg_eig64(const double* Gg, int ldg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork);
 
 struct BondIO {
@@ -2871,7 +2828,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
     S.T1 = S.Cc + 128 * 128;
     S.T2 = S.T1 + 128 * 128;
     S.T3 = S.T2 + 128 * 128;
-    if (pq >= 3 * 128 * 128 && !(P.fast & 64)) {
+    if (pq >= 3 * 128 * 128) {
         // the Gram matrix, the reflector store and the check matrix take the place of the fused merge's T buffer / the LQ copy
         // (dead by the time they are written): 288 KB less footprint per train, and the lines are warm
         S.Ga = S.M2; S.Gb = S.M2 + 128 * 128; S.T2 = S.M2 + 2 * 128 * 128;
@@ -2885,14 +2842,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         else wg_materialize_core(P, b, k + 1);
     }
 
-    long long t_prev = P.prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    // fine-grained marks of ONE step (TTN_PROF_STEP): 64 more counters per train behind the phase and step tables
-#define FINE_MARK(id) if (P.prof && P.prof_step == step) { __syncthreads(); if (tid == 0) { long long t_now = (long long)__builtin_amdgcn_s_memtime(); P.prof[(long long)P.tt.batch * 136 + (long long)b * 64 + (id)] += t_now - t_fine; t_fine = t_now; } }
-    long long t_fine = t_prev;
-#define PROF_MARK(slot) if (P.prof) { __syncthreads(); if (tid == 0) { long long t_now = (long long)__builtin_amdgcn_s_memtime(); if (P.prof_step < 0 || P.prof_step == step) P.prof[(long long)b * 16 + (slot)] += t_now - t_prev; t_prev = t_now; } }
-
     const View Lfv = mkview(ck, Idx{Dl, (long long)n1, 1}, plain((long long)n1 * Dl));     // (mr x r)
-    int route = 2;                                        // 0 = F, 1 = G, 2 = H (for the diagnostics)
     int nsw_total = 0;
     bool done = false;
 
@@ -2902,7 +2852,6 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         double sa = 0.0, sb = 0.0;
         sa = wg_absmax(ck, (long long)n1 * Dl * rm, S.red);
         sb = wg_absmax(ck1, (long long)n2 * rm * Dr, S.red);
-        FINE_MARK(0)
         bool ok = (sa > 0.0) && (sb > 0.0);
         const double sA = wide ? sa : sb, sB = wide ? sb : sa;       // scale of A', B'
         const double s0 = sA * sB;
@@ -2912,10 +2861,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         bool diagA = false;
         if (ok) {
             wg_syrk(rm, p, tview(Ap), Gav, 1.0 / (sA * sA), lds);          // A'^T A'
-            FINE_MARK(1)
             wg_syrk(rm, q, Bp, Gbv, 1.0 / (sB * sB), lds);          // B' B'^T
-            FINE_MARK(2)
-            PROF_MARK(8)
             // A' = U D^(1/2) with orthonormal U (the left core of a bond step is left as U sqrt(S) by the step before it, so every
             // R->L step of a sweep that follows an L->R sweep sees this): then M = U (D^(1/2) B') and the SVD of M is U times the SVD
             // of the rm x q matrix N = D^(1/2) B' — no Cholesky factors, no core matrix, two output GEMMs instead of five.
@@ -2923,17 +2869,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             if (rm == 64 && !(P.fast & 4) && !(P.fast & 8)) {
                 const double wmax = wg_diag_test_t3(S.Ga, S.Gb, S.T3, S.Ss, S.red);      // (T3 = D^(1/2) (B' B'^T) D^(1/2), used if the test passes)
                 diagA = wmax <= FAST_DIAG_TOL;
-                if (P.prof && tid == 0) {            // diagnostics: largest off-diagonal level seen (1e-18 units), steps tested / taken
-                    long long* pf = P.prof + (long long)b * 16;
-                    const long long wl = (long long)fmin(wmax * 1e18, 9e18);
-                    if (wl > pf[12]) pf[12] = wl;
-                    pf[13] += 1; pf[14] += diagA ? 1 : 0;
-                }
             }
-            FINE_MARK(3)
             if (diagA) {
                 // (the Gram matrix of N = D^(1/2) B', D^(1/2) (B' B'^T) D^(1/2), is in T3 already)
-                FINE_MARK(4)
             } else if (rm <= TTN_LDS_COLS / 2) {
                 // both Cholesky factorisations at once, one per half of the workgroup (wg_chol2_lds128)
                 for (int e = tid; e < rm * 128; e += TTN_WG) if ((e & 127) < rm) { S.ldsX[e] = S.Ga[e]; S.ldsX[TTN_LDS_IMG / 2 + e] = S.Gb[e]; }
@@ -2959,13 +2897,11 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         }
         int r = 0, rk = 0;
         if (ok) {
-            PROF_MARK(9)
             int nsw = 1;
             if (diagA) {
                 ok = wg_eig64(S.T3, 128, S.T2, 64, 64, S.sigs, lds, reinterpret_cast<int*>(S.Ts), S.Ts + 64) == 0;
-                FINE_MARK(5)
                 for (int j = tid; j < 64; j += TTN_WG) S.perm[j] = j;
-                if (tid == 0) S.scal[0] = P.jneg_mult * P.jneg_mult * 64.0 * DBL_EPSILON * DBL_EPSILON * S.sigs[0] * S.sigs[0];
+                if (tid == 0) S.scal[0] = 64.0 * DBL_EPSILON * DBL_EPSILON * S.sigs[0] * S.sigs[0];
                 __syncthreads();
             } else {
             // core C = L_A^T L_B  (rm x rm)
@@ -2976,7 +2912,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                 wg_gemm(64, 64, 64, Ccv, tview(Ccv), mkview(S.T3, plain(1), plain(128)), 1.0, 0.0, lds);
                 ok = wg_eig64(S.T3, 128, S.T2, 64, 64, S.sigs, lds, reinterpret_cast<int*>(S.Ts), S.Ts + 64) == 0;
                 for (int j = tid; j < 64; j += TTN_WG) S.perm[j] = j;
-                if (tid == 0) S.scal[0] = P.jneg_mult * P.jneg_mult * 64.0 * DBL_EPSILON * DBL_EPSILON * S.sigs[0] * S.sigs[0];
+                if (tid == 0) S.scal[0] = 64.0 * DBL_EPSILON * DBL_EPSILON * S.sigs[0] * S.sigs[0];
                 __syncthreads();
             } else {
                 for (int e = tid; e < rm * 128; e += TTN_WG) { const int c = e >> 7, r_ = e & 127; S.ldsX[e] = (r_ < rm) ? S.Cc[c * 128 + r_] : 0.0; }
@@ -2986,12 +2922,10 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             }
             }
             ok = ok && (nsw > 0) && (S.sigs[rm - 1] * FAST_KAPPA_MAX >= S.sigs[0]) && (S.sigs[rm - 1] * S.sigs[rm - 1] > S.scal[0]);
-            PROF_MARK(10)
         }
         if (ok) {
             r = wg_rank_rule(P, S, rm, p, s0);
             rk = r < rm ? r : rm;                                           // columns that carry data
-            FINE_MARK(6)
             // X_s[:, j] = x_j * (sqrt(s0)/sA) / sigma_j^2.5 -> T1 ;  X_t[:, j] = x_j * (sqrt(s0)/sB) / sigma_j^1.5 -> T2
             const double fa = sqrt(s0) / sA, fb = sqrt(s0) / sB;
             if (diagA) {
@@ -3014,12 +2948,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             double* RfT = S.M + (long long)p * rk;                          // rk x q, row-major (ld = q)
             const View Lft = mkview(LfT, plain(1), plain(p));
             const View Rft = mkview(RfT, plain(q), plain(1));
-            FINE_MARK(7)
             if (diagA) {
                 wg_gemm_ra(rk, p, rm, tview(T1v), tview(Ap), tview(Lft), 1.0, lds);          // Lf^T = T1^T A'^T: the short operand in registers
-                FINE_MARK(8)
                 wg_gemm_ra(rk, q, rm, tview(T2v), Bp, Rft, 1.0, lds);
-                FINE_MARK(9)
             } else {
             // Lf = A' * (L_B * (C^T * X_s))     (ldsX is free again: use it as the second temporary)
             wg_gemm(rm, rk, rm, tview(Ccv), T1v, mkview(S.T3, plain(1), plain(128)), 1.0, 0.0, lds);
@@ -3031,13 +2962,10 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             }
             // a-posteriori check: Lf^T Lf = Sigma, Rf Rf^T = Sigma
             wg_syrk(rk, p, tview(Lft), mkview(S.T1, plain(1), plain(128)), 1.0, lds);
-            FINE_MARK(10)
             wg_syrk(rk, q, Rft, mkview(S.T2, plain(1), plain(128)), 1.0, lds);
-            FINE_MARK(11)
             const double e1 = wg_check_diag_tab(S.sigs, S.T1, 128, rk, s0, S.Ts, S.red);
             const double e2 = wg_check_diag_tab(S.sigs, S.T2, 128, rk, s0, S.Ts, S.red);
             ok = (e1 <= FAST_CHECK_TOL) && (e2 <= FAST_CHECK_TOL);
-            FINE_MARK(12)
             if (ok) {
                 if (P.sv_out && step < P.sv_steps) {
                     double* so = P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax;
@@ -3049,16 +2977,12 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                 const View Ro = wide ? Rfv : tview(Lfv);       // r x q
                 __syncthreads();
                 wg_copy_to_view(Lo, LfT, p, r, 1, p, rk, 1);               // Lo[row, j] = LfT[row + p j], columns j >= rk zero
-                FINE_MARK(13)
                 wg_copy_to_view(Ro, RfT, r, q, q, 1, rk, 0);               // Ro[j, col] = RfT[j q + col], rows j >= rk zero
-                FINE_MARK(14)
                 if (tid == 0) *io.rank_out = r;
                 __syncthreads();
                 done = true;
-                route = diagA ? 3 : 0;
             }
         }
-        PROF_MARK(6)
     }
 
     if (!done) {
@@ -3068,10 +2992,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         // apply 1/s0 as their alpha — no extra read-modify-write pass over the p x q matrix.
         bool merged = false;
         if (virt_live) {
-            FINE_MARK(26)
-            merged = wg_fused_merge(P, b, k, p, q, Am, S.M, S.M2, pq, lds, S.scal + 6, S.red,
-                                    (P.prof && P.prof_step == step) ? P.prof + (long long)P.tt.batch * 136 + (long long)b * 64 + 48 : nullptr);
-            FINE_MARK(27)
+            merged = wg_fused_merge(P, b, k, p, q, Am, S.M, S.M2, pq, lds, S.scal + 6, S.red);
             if (!merged) wg_materialize_core(P, b, k + 1);
         }
         double mx_swap = 0.0;
@@ -3088,11 +3009,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                     __syncthreads();
                 }
         } else if (!merged) wg_gemm(p, q, rm, Ap, Bp, Mv, 1.0, 0.0, lds, S.scal + 6);
-        PROF_MARK(0)
         const double mx = (SWAP != 0) ? mx_swap : unif64(S.scal[6]);
         const double s0 = (mx > 0.0) ? mx : 1.0;
         const double inv_s0 = 1.0 / s0;
-        PROF_MARK(1)
         const bool need_lq = q > p;
         const bool x_in_lds = p <= TTN_LDS_COLS;              // fast Jacobi: X in LDS with leading dimension 128
         double* X = x_in_lds ? S.ldsX : S.Xg;
@@ -3106,7 +3025,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         // CholeskyQR2 (above) instead of the Householder LQ when the plain Gram route finds the matrix too ill-conditioned for itself
         // (only where the Householder LQ cannot keep the whole matrix in LDS — 64 x 384, 32 x 384: there it wins 3x; against the in-LDS
         // LQ of a 64 x 128 step it is a draw, and the R->L ramp matrices are often too ill-conditioned for it anyway)
-        const bool cholqr_ok = SWAP == 0 && P.fast && !(P.fast & 32) && need_lq && x_in_lds && p >= 16 && p <= 64 && (long long)p * q > GEMM_LDS_DOUBLES;
+        const bool cholqr_ok = SWAP == 0 && P.fast && need_lq && x_in_lds && p >= 16 && p <= 64 && (long long)p * q > GEMM_LDS_DOUBLES;
         for (int attempt = (SWAP == 0 && P.fast && need_lq && (eig_ok || cholqr_ok || (x_in_lds && !lq_in_lds)) && p >= 2) ? 1 : 2; attempt <= 2 && !done; ++attempt) {
             bool ok = true;
             bool use_eig = false;
@@ -3117,7 +3036,6 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             if (attempt == 1) {
                 // =========================== route G: L = chol(M M^T) ===========================
                 wg_syrk(p, q, Mv, mkview(S.Ga, plain(1), plain(128)), inv_s0 * inv_s0, lds);
-                PROF_MARK(7)
                 // p = 128 with at most 64 vectors kept (the L->R steps of the benchmark sweep): eigen-decomposition of the Gram
                 // matrix itself — tridiagonalisation, bisection, twisted factorisations (ttn_eig_kernels.h) — instead of
                 // Cholesky + Jacobi on L; same outputs (sigs, perm, X = sigma_j u_j in LDS), same a-posteriori check below
@@ -3134,12 +3052,10 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                     // the part it drops (the solver only computes the kept eigenvalues)
                     { double t_ = 0.0; for (int i = tid; i < p; i += TTN_WG) t_ += S.Ga[i * 129]; gram_trace = unif64(wg_sum(t_, S.red)); }
                     ok = ((p == 64) ? wg_eig64(S.Ga, 128, S.Gb, r0, nev, S.sigs, lds, reinterpret_cast<int*>(S.Ts), S.Ts + 64)
-                                    : wg_eig128(S.Ga, S.Gb, r0, nev, S.sigs, lds, reinterpret_cast<int*>(S.Ts), S.Ts + 64,
-                                                (P.prof && P.prof_step == step) ? P.prof + (long long)P.tt.batch * 136 + (long long)b * 64 + 32 : nullptr)) == 0;
+                                    : wg_eig128(S.Ga, S.Gb, r0, nev, S.sigs, lds, reinterpret_cast<int*>(S.Ts), S.Ts + 64)) == 0;
                     for (int j = tid; j < p; j += TTN_WG) { S.perm[j] = j; if (j >= nev) S.sigs[j] = 0.0; }      // (sigs / perm hold pmax entries)
-                    if (tid == 0) S.scal[0] = P.jneg_mult * P.jneg_mult * (double)p * DBL_EPSILON * DBL_EPSILON * S.sigs[0] * S.sigs[0];
+                    if (tid == 0) S.scal[0] = (double)p * DBL_EPSILON * DBL_EPSILON * S.sigs[0] * S.sigs[0];
                     __syncthreads();
-                    PROF_MARK(11)
                 } else {
                 wg_img_load(S.ldsX, 0, S.Ga, p, S.red);
                 ok = wg_chol_lds128(p, S.ldsX, S.red, S.iflag, S.scal + 1) == 0;
@@ -3156,10 +3072,8 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                 if (cholqr) {
                     for (int e = tid; e < p * p; e += TTN_WG) { const int i = e % p, j = e / p; S.T1[i + 128 * j] = S.ldsX[i + 128 * j]; }       // L1 (the GEMM below takes the image)
                     wg_trsm_lower_cols(p, q, S.ldsX, S.M, q, inv_s0, S.M2, q);                                                           // Q1 = L1^-1 M / s0
-                    PROF_MARK(8)
                     const View Q1v = mkview(S.M2, plain(q), plain(1));
                     wg_syrk(p, q, Q1v, mkview(S.Cc, plain(1), plain(128)), 1.0, lds);
-                    PROF_MARK(9)
                     // Q1 Q1^T = I + E, |E| ~ eps cond(M)^2: the route needs |E| << 1 (CHOLQR_ORTH_MAX), else Householder
                     const double dev = wg_img_load(S.ldsX, 0, S.Cc, p, S.red);
                     ok = dev <= CHOLQR_ORTH_MAX && wg_chol_lds128(p, S.ldsX, S.red, S.iflag, S.scal + 1) == 0;
@@ -3167,11 +3081,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                         wg_img_load(S.ldsX, 64, S.T1, p, S.red);
                         wg_tril_mul_lds(p, S.ldsX);
                     }
-                    PROF_MARK(10)
                 }
                 for (int e = tid; e < p * 128; e += TTN_WG) if ((e & 127) >= p) S.ldsX[e] = 0.0;      // zero row padding for the Jacobi
                 __syncthreads();
-                PROF_MARK(11)
                 }
             } else {
                 // =========================== route H: Householder LQ ===========================
@@ -3181,7 +3093,6 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                     wg_lq_blocked(p, q, S.M2, q, S.Vb, S.Wb, nullptr, nullptr, lds, S.Ts, S.Ss, S.taus, S.red);
                 }
                 const double* Lsrc = need_lq ? S.M2 : S.M;               // row-major, ld = q
-#ifndef TTN_NO_PRESORT
                 // columns of L in order of decreasing norm (de Rijk): the rank-deficient L of the ramp steps converges in
                 // fewer sweeps that way; any column order is fine for the caller (wg_svd_cols sorts by sigma anyway)
                 if (need_lq && x_in_lds) {
@@ -3202,9 +3113,6 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                     __syncthreads();
                 }
                 const bool presort = need_lq && x_in_lds;
-#else
-                const bool presort = false;
-#endif
                 for (int e = tid; e < p * ldx; e += TTN_WG) {
                     const int r_ = e % ldx, c = e / ldx;              // X[r + ldx*c] = L[r][c]; rows >= p are zero padding
                     const double v = (r_ < p) ? Lsrc[(long long)r_ * q + c] * (need_lq ? 1.0 : inv_s0) : 0.0;
@@ -3212,7 +3120,6 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                     X[(long long)cd * ldx + r_] = (need_lq && c > r_) ? 0.0 : v;
                 }
                 __syncthreads();
-                PROF_MARK(2)
             }
             int nsw = 0;
             if (ok && !(attempt == 1 && use_eig)) {
@@ -3221,11 +3128,8 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                 if (attempt == 1) ok = nsw > 0;
                 else if (nsw < 0 && tid == 0) ttn_set_status(&P.status[b], 1);
             }
-            PROF_MARK(3)
             if (!ok) continue;
-            FINE_MARK(20)
             const int r = wg_rank_rule(P, S, p, p, s0);
-            FINE_MARK(21)
             if (SWAP != 0 && r > io.cap) {                                  // would not fit the slots: report, write nothing
                 if (tid == 0) { ttn_set_status(&P.status[b], 2); *io.rank_out = -1; }
                 __syncthreads();
@@ -3287,12 +3191,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                         double* so = P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax;
                         for (int i = tid; i < P.pmax; i += TTN_WG) so[i] = (i < p) ? S.sigs[i] * s0 : -1.0;
                     }
-                    if (P.prof && tid == 0) P.prof[(long long)b * 16 + 15] += 1;
                     if (tid == 0) *io.rank_out = r;
                     __syncthreads();
                     done = true;
-                    route = 1;
-                    PROF_MARK(5)
                     continue;
                 }
             }
@@ -3300,7 +3201,6 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                 double* so = P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax;
                 for (int i = tid; i < P.pmax; i += TTN_WG) so[i] = (i < p) ? S.sigs[i] * s0 : -1.0;
             }
-            PROF_MARK(4)
             // ---- outputs.  left factor (p x r): x_j * sqrt(s0)/sqrt(sig_j) ; right factor (r x q):
             //      (x_j^T M / s0) * sqrt(s0) / (sig_j*sqrt(sig_j)).  Columns the Jacobi left alone as numerically
             //      zero (norm^2 <= aneg) are not singular vectors relative to their own size: written as exact zeros.
@@ -3328,14 +3228,10 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             }
             }
             __syncthreads();
-            FINE_MARK(22)
             wg_gemm_ra(r, q, p, mkview(S.Us, plain(p), plain(1)), Mv, Ro, inv_s0, lds);
-            FINE_MARK(23)
             if (attempt == 1) {
                 wg_syrk(r, q, Ro, mkview(S.T2, plain(1), plain(128)), 1.0, lds);
-                FINE_MARK(24)
                 const double e2 = (r <= 128) ? wg_check_diag_tab(S.sigs, S.T2, 128, r, s0, S.Ts, S.red) : unif64(wg_check_diag(S, S.T2, 128, r, s0));
-                FINE_MARK(25)
                 if (!(e2 <= (cholqr ? CHOLQR_CHECK_TOL : FAST_CHECK_TOL))) continue;                     // redo with Householder (M is intact)
                 if (P.sv_out && step < P.sv_steps) {
                     double* so = P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax;
@@ -3345,18 +3241,10 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             if (tid == 0) *io.rank_out = r;
             __syncthreads();
             done = true;
-            route = attempt;
-            PROF_MARK(5)
         }
     }
-    if (tid == 0) {
-        P.sweep_stats[b] += nsw_total;
-        if (P.prof && step < 120)
-            P.prof[(long long)P.tt.batch * 16 + (long long)b * 120 + step] = ((long long)route << 48) | ((long long)p << 32) | (long long)nsw_total;
-    }
+    if (tid == 0) P.sweep_stats[b] += nsw_total;
     __syncthreads();
-#undef PROF_MARK
-#undef FINE_MARK
 }
 
 // tt_compress! form of the step: cores k, k+1 of train b of P.tt
@@ -3377,10 +3265,10 @@ __device__ __forceinline__ void wg_bond_step(const CompressArgs& P, int b, int k
     {
         const int mr = io.n1 * io.Dl, mc = io.n2 * io.Dr;
         const int p = mr <= mc ? mr : mc, q = mr <= mc ? mc : mr;
-        if (P.fast && !(P.fast & 1024) && p >= 2 && p <= SMALL_STEP_PMAX && q <= SMALL_STEP_QMAX && P.pmax >= p) {
+        if (P.fast && p >= 2 && p <= SMALL_STEP_PMAX && q <= SMALL_STEP_QMAX && P.pmax >= p) {
             if (virt) wg_materialize_core(P, b, k + 1);
             SmallStepArgs Q;
-            Q.jneg_mult = P.jneg_mult; Q.jtol_mult = P.jtol_mult; Q.truncerr = P.truncerr; Q.max_bond = P.max_bond; Q.rank_rule = P.rank_rule; Q.pmax = P.pmax;
+            Q.truncerr = P.truncerr; Q.max_bond = P.max_bond; Q.rank_rule = P.rank_rule; Q.pmax = P.pmax;
             Q.sv_row = (P.sv_out && step < P.sv_steps) ? P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax : nullptr;
             Q.status_b = P.status + b;
             // the step's LDS / scratch map (wg_bond_step_io): reduction scratch, scalars, flags; singular values and their order
@@ -3392,15 +3280,8 @@ __device__ __forceinline__ void wg_bond_step(const CompressArgs& P, int b, int k
             double* sig = scr + 2 * pq + (long long)QR_NB * P.qmax + (long long)P.pmax * QR_NB + 2LL * P.pmax * P.pmax;
             Q.sigs = sig + P.pmax;
             Q.perm = reinterpret_cast<int*>(Q.sigs + P.pmax);
-            const long long ts0 = P.prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
             const int nsw = wg_bond_small(Q, io.ck, io.ck1, io.n1, io.n2, io.Dl, io.rm, io.Dr, io.rank_out, lds);
-            if (threadIdx.x == 0) {
-                P.sweep_stats[b] += nsw;
-                if (P.prof) {
-                    if (P.prof_step < 0 || P.prof_step == step) P.prof[(long long)b * 16 + 3] += (long long)__builtin_amdgcn_s_memtime() - ts0;
-                    if (step < 120) P.prof[(long long)P.tt.batch * 16 + (long long)b * 120 + step] = (2LL << 48) | ((long long)p << 32) | (long long)nsw;
-                }
-            }
+            if (threadIdx.x == 0) P.sweep_stats[b] += nsw;
             __syncthreads();
             return;
         }
@@ -3435,10 +3316,7 @@ __global__ void TTN_KERNEL_BOUNDS k_compress(CompressArgs P) {
                 k = (i < d - 1) ? i : per_sweep - 1 - i;
                 virt = P.fused && step < d - 1;                                      // first L->R sweep of the fused op
             }
-            const long long ts_ = P.prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
             wg_bond_step(P, b, k, step, lds, virt);
-            if (P.prof && step < 120 && threadIdx.x == 0)            // bits 12..31 of the step word: kilo-cycles of the step
-                P.prof[(long long)P.tt.batch * 16 + (long long)b * 120 + step] |= ((((long long)__builtin_amdgcn_s_memtime() - ts_) >> 10) & 0xFFFFF) << 12;
         }
         if (!P.next_train) break;
         // next train of this slot: one atomic per train, broadcast through LDS (the bond step ends with a barrier, so nobody still
@@ -3578,7 +3456,6 @@ struct DotArgs {
     long long scratch_stride;
     int ramax, rbmax, nmax;
     double* out;                // [batch] device
-    long long* prof;            // TTN_PROF=1: s_memtime stamp after every site of train b at prof[16 * batch + 120 * b + k] (ttn_prof_steps)
 };
 
 // (the kernel: ttn_dot_kernels.h)
@@ -3595,48 +3472,4 @@ __global__ void TTN_KERNEL_BOUNDS k_selftest_gemm(int m, int n, int k, double* A
     if (ta & 2) wg_syrk(m, k, Av, mkview(C, plain(n), plain(1)), alpha, lds);               // ta & 2: C = alpha A A^T (n == m; B, beta unused)
     else if (ta & 4) wg_gemm_ra(m, n, k, Av, Bv, mkview(C, plain(n), plain(1)), alpha, lds);   // ta & 4: the register-A form (beta unused)
     else wg_gemm(m, n, k, Av, Bv, mkview(C, plain(n), plain(1)), alpha, beta, lds);
-}
-
-__global__ void TTN_KERNEL_BOUNDS k_bench_gemm(int m, int n, int k, double* A, double* B, double* C, int ta, int tb, int reps,
-                                                      long long* cycles) {
-    extern __shared__ double lds[];
-    // every workgroup of the grid works on its own copy of the operands (the buffers hold gridDim.x of them back to back): a grid
-    // of 2 x #CUs measures the GEMM with a second workgroup resident on the CU
-    A += (long long)blockIdx.x * m * k; B += (long long)blockIdx.x * k * n; C += (long long)blockIdx.x * m * n;
-    const View Av = (ta & 1) ? mkview(A, plain(1), plain(m)) : mkview(A, plain(k), plain(1));
-    const View Bv = tb ? mkview(B, plain(1), plain(k)) : mkview(B, plain(n), plain(1));
-    __syncthreads();
-    const long long t0 = __builtin_amdgcn_s_memtime();
-    for (int r = 0; r < reps; ++r) {
-        if (ta & 2) wg_syrk(m, k, Av, mkview(C, plain(n), plain(1)), 1.0, lds);            // the Gram-product routine (n == m)
-        else if (ta & 4) wg_gemm_ra(m, n, k, Av, Bv, mkview(C, plain(n), plain(1)), 1.0, lds);
-        else wg_gemm(m, n, k, Av, Bv, mkview(C, plain(n), plain(1)), 1.0, 0.0, lds);
-    }
-    __syncthreads();
-    const long long t1 = __builtin_amdgcn_s_memtime();
-    if (threadIdx.x == 0 && blockIdx.x == 0) *cycles = t1 - t0;
-}
-
-// LDS building-block micro-benchmark (ttn_bench_lds): G = I*n + smooth symmetric perturbation, then Cholesky or Jacobi.
-__global__ void TTN_KERNEL_BOUNDS k_bench_lds(int what, int n, int reps, long long* out) {
-    extern __shared__ double lds[];
-    double* red = lds + GEMM_LDS_TOTAL;
-    double* scal = red + 32;
-    int* iflag = (int*)(scal + 8);
-    double* nrm2 = scal + 16;
-    int sw = 0;
-    __syncthreads();
-    const long long t0 = __builtin_amdgcn_s_memtime();
-    for (int r = 0; r < reps; ++r) {
-        for (int e = threadIdx.x; e < 128 * 128; e += TTN_WG) {
-            const int c = e >> 7, i = e & 127;
-            lds[e] = (i < n && c < n) ? ((i == c) ? (double)n : 1.0 / (1.0 + (i > c ? i - c : c - i))) : 0.0;
-        }
-        __syncthreads();
-        if (what == 1) wg_chol_lds128(n, lds, red, iflag, scal + 1);
-        if (what == 2) sw = wg_jacobi_lds128(n, n, lds, nrm2, iflag, red, 1.0, 1.0, scal);
-        __syncthreads();
-    }
-    const long long t1 = __builtin_amdgcn_s_memtime();
-    if (threadIdx.x == 0) { out[0] = t1 - t0; out[1] = sw; }
 }

@@ -69,12 +69,9 @@ __device__ __forceinline__ dot_f64x2 dot_load2(const double* core, int p, int q,
 //   Mnxt : all zero on entry; receives M'[al, be] at Mnxt[DOT_AT(be, al)]
 //   Mzero: zeroed here (the accumulation target of the NEXT site)
 // FULL: ra = ra2 = rb = rb2 = 64 (the interior sites of a rank-64 train) — no masks, constant trip counts, addresses base + immediate.
-#define DOT_STAMP(i) if (FULL && stamps) ts_[i] = (long long)__builtin_amdgcn_s_memtime() - tstart;
 template <bool FULL>
 __device__ __forceinline__ void dot_site(const double* Ak, const double* Bk, int ra, int ra2, int rb, int rb2, const lds_f64* Mcur, lds_f64* Mnxt,
-                                         lds_f64* Mzero, long long* stamps = nullptr /* diagnostics: 8 waves x 8 accumulated phase clocks */) {
-    const long long tstart = (FULL && stamps) ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    long long ts_[6] = {0, 0, 0, 0, 0, 0};
+                                         lds_f64* Mzero) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int tr = wave & 3, tc = wave >> 2;
@@ -115,7 +112,6 @@ __device__ __forceinline__ void dot_site(const double* Ak, const double* Bk, int
                 t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv.y, t1, 0, 0, 0);
             }
         }
-        DOT_STAMP(0)
         // ---- partial M'[al, be] over a in this wave's block: sum_{z, r} A_k[z, al, 16 tr + 4 r + lk] * T_z[16 tr + 4 r + lk, be] — the
         //      accumulator register r of T_z is the B fragment of k-step r as it is ----
         const int nr = FULL ? 4 : min(4, (ra - 16 * tr + 3) >> 2);        // k-steps of this block that hold rows a < ra
@@ -141,7 +137,6 @@ __device__ __forceinline__ void dot_site(const double* Ak, const double* Bk, int
                         }
                     }
                 }
-                if (ta == 3) { DOT_STAMP(1) }
                 // M'[al = 16 ta + lk + 4 reg, be = 16 tc + li] += m[reg]     (entries beyond (ra2, rb2) are exact zeros: masked fragments)
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg)
@@ -149,14 +144,7 @@ __device__ __forceinline__ void dot_site(const double* Ak, const double* Bk, int
             }
         }
     }
-    DOT_STAMP(2)
     dot_lds_barrier();
-    DOT_STAMP(3)
-    if (FULL && stamps && (threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        const int slot = w < 4 ? w : (w == 4 ? 4 : (w == 8 ? 5 : (w == 12 ? 6 : (w == 15 ? 7 : -1))));
-        if (slot >= 0) for (int i = 0; i < 6; ++i) stamps[8 * slot + i] += ts_[i];
-    }
 }
 
 __device__ __noinline__ void dot_site_masked(const double* Ak, const double* Bk, int ra, int ra2, int rb, int rb2, const lds_f64* Mcur, lds_f64* Mnxt,
@@ -225,12 +213,10 @@ __global__ void __launch_bounds__(TTN_WG) k_dot_fused(DotArgs P) {
             double* Bk = Bbase + uni32(tab[6 * k + 4]);
             const int nx = cur == 2 ? 0 : cur + 1, sp = nx == 2 ? 0 : nx + 1;
             if (ra == DOT_RMAX && ra2 == DOT_RMAX && rb == DOT_RMAX && rb2 == DOT_RMAX)
-                dot_site<true>(Ak, Bk, ra, ra2, rb, rb2, img + cur * DOT_MS_DOUBLES, img + nx * DOT_MS_DOUBLES, img + sp * DOT_MS_DOUBLES,
-                               P.prof ? P.prof + 136LL * gridDim.x + 64LL * t : nullptr);
+                dot_site<true>(Ak, Bk, ra, ra2, rb, rb2, img + cur * DOT_MS_DOUBLES, img + nx * DOT_MS_DOUBLES, img + sp * DOT_MS_DOUBLES);
             else
                 dot_site_masked(Ak, Bk, ra, ra2, rb, rb2, img + cur * DOT_MS_DOUBLES, img + nx * DOT_MS_DOUBLES, img + sp * DOT_MS_DOUBLES);
             cur = nx;
-            if (P.prof && tid == 0 && k < 120) P.prof[16LL * gridDim.x + 120LL * t + (d - 1 - k)] = (long long)__builtin_amdgcn_s_memtime();
         }
         if (tid == 0) P.out[t] = (double)img[cur * DOT_MS_DOUBLES];
         return;

@@ -55,23 +55,6 @@ __device__ __forceinline__ double readlane_f64(double v, int idx) {
     r.i[1] = __builtin_amdgcn_readlane(u.i[1], idx);
     return r.d;
 }
-__device__ __forceinline__ void tridiag_reflector(int k, double x0, double x1, double xk1, int lane, lds_f64* vbuf, double* Vst,
-                                                  lds_f64* dg, lds_f64* e, lds_f64* beta, double dgk) {
-    // lanes hold entries lane, lane + 64 of column k (zero at and above the diagonal position k)
-    const double s2 = wave64_sum_mfma(fma(x0, x0, x1 * x1));
-    // sqrt and reciprocal from the hardware seeds + Newton steps (full fp64 accuracy; this chain is on the critical path)
-    const double alpha = (s2 > 0.0) ? -copysign(s2 * fast_rsqrt2(s2), xk1) : 0.0;
-    const double den = s2 - alpha * xk1;                           // = v'v / 2
-    double bta = 0.0;
-    if (den > 0.0) { bta = fast_rcp(den); bta = fma(fma(-den, bta, 1.0), bta, bta); }
-    const double v0 = x0 - ((lane == k + 1) ? alpha : 0.0), v1 = x1 - ((lane + 64 == k + 1) ? alpha : 0.0);
-    vbuf[lane] = v0; vbuf[lane + 64] = v1;
-    // global_store, not flat_store: a flat store also counts on lgkmcnt, and the LDS barrier right after would wait for it (~800 clk)
-    typedef __attribute__((address_space(1))) double gdouble;
-    gdouble* vg = (gdouble*)(unsigned long long)(Vst + k * 128);
-    vg[lane] = v0; vg[lane + 64] = v1;
-    if (lane == 0) { dg[k] = dgk; e[k] = alpha; beta[k] = bta; }
-}
 
 template <int N>
 __device__ __noinline__ void wg_tridiag(const double* Gg, int ldg, double* Vst, double* lds) {
@@ -92,12 +75,11 @@ __device__ __noinline__ void wg_tridiag(const double* Gg, int ldg, double* Vst, 
     double a[CW];
 #pragma unroll
     for (int j = 0; j < CW; ++j) a[j] = actv ? Gg[i + (long long)ldg * (CW * c + j)] : 0.0;
-#ifndef TTN_TRIDIAG_V1
-    // ---- schedule (round 2): the reflector is formed in TWO halves around a barrier, and the matrix-vector product runs on the
+    // ---- schedule: the reflector is formed in TWO halves around a barrier, and the matrix-vector product runs on the
     // known column x~ instead of v.  v_k = x~_k - alpha_k e_{k+1} (x~_k = column k of the current matrix below the diagonal), so
     //   A v_k = A x~_k - alpha_k A[:, k+1],   A[:, k+1] = row k+1 = the look-ahead buffer —
     // the product needs x~_k only, which wave 0 has ~100 clk after w_{k-1}, not the scalars alpha, beta that take it another ~900.
-    // Per column k, three LDS barriers as before:
+    // Per column k, three LDS barriers:
     //   S1  all: y = A x~_k (partial sums)            | wave 0 first: beta_k, v_k -> LDS / global, (d_k, e_k, beta_k)
     //   S2  wave 0: p = beta (y - alpha row_{k+1}), w_k = p - (beta/2)(p'v) v
     //   S3  others: A -= v w' + w v', row k+2 out      | wave 0: x~_{k+1} -> LDS, ||x~||^2, alpha_{k+1}   (first half of reflector k+1)
@@ -131,12 +113,11 @@ __device__ __noinline__ void wg_tridiag(const double* Gg, int ldg, double* Vst, 
         double v0 = 0.0, v1 = 0.0, w0 = 0.0, w1 = 0.0, bta = 0.0;
         // ---- S1 ----
         if (wave == 0) {
-#ifdef TTN_TRIDIAG_PRIO
             __builtin_amdgcn_s_setprio(TTN_TRIDIAG_PRIO);          // the serial chain of the column ahead of everybody's parallel work
-#endif
             if (rden > 0.0) { bta = fast_rcp(rden); bta = fma(fma(-rden, bta, 1.0), bta, bta); }
             v0 = rx0 - ((lane == k + 1) ? ralpha : 0.0); v1 = rx1 - ((lane + 64 == k + 1) ? ralpha : 0.0);
             vL[lane] = v0; vL[lane + 64] = v1;
+            // global_store, not flat_store: a flat store also counts on lgkmcnt, and the LDS barrier right after would wait for it (~800 clk)
             typedef __attribute__((address_space(1))) double gdouble;
             gdouble* vg = (gdouble*)(unsigned long long)(Vst + k * 128);
             vg[lane] = v0; vg[lane + 64] = v1;
@@ -187,15 +168,7 @@ __device__ __noinline__ void wg_tridiag(const double* Gg, int ldg, double* Vst, 
             ralpha = (s2 > 0.0) ? -copysign(s2 * fast_rsqrt2(s2), xk1) : 0.0;
             rden = s2 - ralpha * xk1;
         }
-        if (wave == 0) {
-#ifdef TTN_TRIDIAG_PRIO
-#ifdef TTN_EIG_PRIO
-            __builtin_amdgcn_s_setprio(TTN_EIG_PRIO);
-#else
-            __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
-        }
+        if (wave == 0) __builtin_amdgcn_s_setprio(TTN_EIG_PRIO);
         if (live) {
             // A -= v w' + w v'
             double vreg[NH], wreg[NH];
@@ -217,111 +190,6 @@ __device__ __noinline__ void wg_tridiag(const double* Gg, int ldg, double* Vst, 
             }
         }
     }
-#else
-    // prologue: rows 0 and 1 of the matrix; reflector 0
-    if (actv && i == 0) {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) wL[CW * c + j] = a[j];      // row 0 (wL is free here)
-    }
-    if (actv && i == 1) {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) xnext[CW * c + j] = a[j];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const double x0 = (lane > 0) ? wL[lane] : 0.0, x1 = TWO ? wL[lane + 64] : 0.0;
-        tridiag_reflector(0, x0, x1, wL[1], lane, vbuf0, Vst, dg, e, beta, wL[0]);
-    }
-    for (int k = 0; k < N - 2; ++k) {
-        lds_f64* vL = (k & 1) ? vbuf1 : vbuf0;
-        lds_f64* vN = (k & 1) ? vbuf0 : vbuf1;
-        lds_barrier();                                             // v_k, row k+1 (xnext) are visible
-        // p = A v (partial over the thread's 16 columns): lane l of a row of 16 lanes holds v[16c + l], the DPP multiply-add
-        // broadcasts it — 2 LDS reads per thread and step instead of 48
-        // A wave owns 64 rows of one 16-column chunk.  Once all its columns are <= k (v is zero there and the entries are never read
-        // again) or all its rows are <= k (finished rows: their w only feeds dead entries), it has nothing left to do but to keep its
-        // partial sums at zero: on average 7 of the 16 waves (N = 128) still work, and the phase is bound by the fp64 multiply-adds.
-        const bool live = actv && (CW * (c + 1) > k + 1) && ((TWO ? 64 * (wave & 1) : 0) + 63 > k);
-        double vreg[NH];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) vreg[h] = 0.0;
-        if (live) {
-#pragma unroll
-            for (int h = 0; h < NH; ++h) vreg[h] = vL[CW * c + 16 * h + (lane & 15)];
-            double pp = 0.0;
-            asm volatile("s_nop 1");
-#define EIG_MV(j) fmac_bcast<j>(pp, vreg[0], a[j]);
-            EIG_BCAST16(EIG_MV)
-#undef EIG_MV
-            if constexpr (NH == 2) {
-#define EIG_MV(j) fmac_bcast<j>(pp, vreg[1], a[16 + j]);
-                EIG_BCAST16(EIG_MV)
-#undef EIG_MV
-            }
-            part[c * 128 + i] = pp;
-        } else if (actv) part[c * 128 + i] = 0.0;
-        lds_barrier();
-        double v0 = 0.0, v1 = 0.0, w0 = 0.0, w1 = 0.0;
-        if (wave == 0) {
-#ifdef TTN_TRIDIAG_PRIO
-            __builtin_amdgcn_s_setprio(TTN_TRIDIAG_PRIO);          // the serial chain of the column ahead of everybody's parallel work
-#endif
-            const double bta = beta[k];
-            v0 = vL[lane]; v1 = TWO ? vL[lane + 64] : 0.0;
-            double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-            for (int cc = 0; cc < NC; ++cc) { p0 += part[cc * 128 + lane]; if (TWO) p1 += part[cc * 128 + lane + 64]; }
-            p0 *= bta; p1 *= bta;
-            const double Kc = 0.5 * bta * wave64_sum_mfma(fma(p0, v0, p1 * v1));
-            w0 = fma(-Kc, v0, p0); w1 = fma(-Kc, v1, p1);
-            wL[lane] = w0; if (TWO) wL[lane + 64] = w1;
-        }
-        lds_barrier();
-        // row k+2 of the UPDATED matrix goes to the look-ahead buffer the next step reads (two buffers alternate)
-        lds_f64* xn_r = (k & 1) ? xnext + 1152 : xnext;          // read this step (row k+1 before update k)
-        lds_f64* xn_w = (k & 1) ? xnext : xnext + 1152;          // written this step (row k+2 after update k)
-        // wave 0 first forms the next reflector (the other waves are busy with their share of the update meanwhile), then its own share
-        if (wave == 0 && k + 1 < N - 2) {
-            // column k+1 of the updated matrix: x - v w_{k+1} - w v_{k+1}, then reflector k+1 (entries <= k+1 are not part of it)
-            const double wk1 = wL[k + 1], vk1 = vL[k + 1];
-            const double c0 = fma(-v0, wk1, fma(-w0, vk1, xn_r[lane]));
-            const double c1 = TWO ? fma(-v1, wk1, fma(-w1, vk1, xn_r[lane + 64])) : 0.0;
-            // entries k+1 (the new diagonal) and k+2 by lane reads
-            const int kk = k + 1;
-            const double dgk = (kk < 64) ? readlane_f64(c0, kk) : readlane_f64(c1, kk - 64);
-            const double xk1 = (kk + 1 < 64) ? readlane_f64(c0, kk + 1) : readlane_f64(c1, kk + 1 - 64);
-            const double x0 = (lane > kk) ? c0 : 0.0, x1 = (TWO && lane + 64 > kk) ? c1 : 0.0;
-            tridiag_reflector(kk, x0, x1, xk1, lane, vN, Vst, dg, e, beta, dgk);
-#ifdef TTN_TRIDIAG_PRIO
-#ifdef TTN_EIG_PRIO
-            __builtin_amdgcn_s_setprio(TTN_EIG_PRIO);
-#else
-            __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
-        }
-        if (live) {
-            // A -= v w' + w v'
-            double wreg[NH];
-#pragma unroll
-            for (int h = 0; h < NH; ++h) wreg[h] = wL[CW * c + 16 * h + (lane & 15)];
-            const double nvi = -vL[i], nwi = -wL[i];
-            asm volatile("s_nop 1");
-#define EIG_UP(j) fmac_bcast<j>(a[j], wreg[0], nvi); fmac_bcast<j>(a[j], vreg[0], nwi);
-            EIG_BCAST16(EIG_UP)
-#undef EIG_UP
-            if constexpr (NH == 2) {
-#define EIG_UP(j) fmac_bcast<j>(a[16 + j], wreg[1], nvi); fmac_bcast<j>(a[16 + j], vreg[1], nwi);
-                EIG_BCAST16(EIG_UP)
-#undef EIG_UP
-            }
-            if (i == k + 2) {
-#pragma unroll
-                for (int j = 0; j < CW; ++j) xn_w[CW * c + j] = a[j];
-            }
-        }
-    }
-#endif
     // the last 2 x 2 block
     __syncthreads();
     if (actv && i == N - 2 && c == NC - 1) { dg[N - 2] = a[CW - 2]; e[N - 2] = a[CW - 1]; }
@@ -575,20 +443,15 @@ __device__ void wg_twisted(int r, double* lds, int* tw /*LDS 64 ints*/, lds_f64*
 // the tridiagonalisation has loaded it.
 template <int N>
 __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork /*LDS 64 ints*/,
-                                     double* dwork /*LDS 128*/, long long* prof) {
+                                     double* dwork /*LDS 128*/) {
     Gg = unip(Gg); Vst = unip(Vst); sig = unip(sig); lds = unip(lds); iwork = unip(iwork); dwork = unip(dwork);
     r = uni32(r); nev = uni32(nev); ldg = uni32(ldg);
     constexpr int RPL = N / 16;                                   // rows per lane in the back-transformation
     lds_f64* L = (lds_f64*)lds;
     lds_f64 *lam = L + EIG_TAIL + 256, *beta = L + EIG_TAIL + 384;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#define EIG_MARK(slot) if (prof && threadIdx.x == 0) prof[slot] = (long long)__builtin_amdgcn_s_memtime();
-    EIG_MARK(2)
-#ifdef TTN_EIG_PRIO
     __builtin_amdgcn_s_setprio(TTN_EIG_PRIO);                  // the whole solver is latency bound: ahead of a co-resident workgroup's GEMM phases
-#endif
     wg_tridiag<N>(Gg, ldg, Vst, lds);
-    EIG_MARK(3)
     // lanes per eigenvalue: the Sturm loop is issue bound, so the optimum is ONE busy wave per SIMD (4 waves) — 4 lanes for the
     // 33..64 eigenvalues of the headline steps (23 rounds of 5-section), 8 lanes for up to 32 (17 rounds of 9-section); more
     // eigenvalues than that (nev = N with truncerr > 0) simply occupy more waves
@@ -598,14 +461,10 @@ __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int
     int bad = 0;
     for (int j = tid; j < nev; j += TTN_WG) { const double l = lam[j]; sig[j] = (l > 0.0) ? sqrt(l) : 0.0; bad |= (j < r) && !(l > 0.0); }
     if (__syncthreads_or(bad)) {
-#ifdef TTN_EIG_PRIO
         __builtin_amdgcn_s_setprio(0); TTN_SETPRIO_BASE();
-#endif
         return 1;
     }
-    EIG_MARK(4)
     wg_twisted<N>(r, lds, iwork, (lds_f64*)dwork, const_cast<double*>(Gg));
-    EIG_MARK(5)
     // Z into registers: waves 0..7; a row of 16 lanes owns TWO columns (8 per wave), lane rc of the row holds rows RPL*rc ..
     // RPL*rc + RPL-1 of both — the dot products v_k' z are reductions over the 16 lanes of a row (4 DPP adds each): no LDS
     // reduction and no barrier in the loop.  The reflectors are staged in LDS once (the D+ / D- arrays are dead after the load of Z).
@@ -654,7 +513,6 @@ __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int
     }
     }
     __syncthreads();                                              // everyone has consumed D+ / D-: the image may be written
-    EIG_MARK(6)
     if (wave < 8) {
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
@@ -667,17 +525,14 @@ __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int
         }
     }
     __syncthreads();
-#ifdef TTN_EIG_PRIO
     __builtin_amdgcn_s_setprio(0); TTN_SETPRIO_BASE();
-#endif
     return 0;
-#undef EIG_MARK
 }
-__device__ int wg_eig128(const double* Gg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork, long long* prof) {
-    return wg_eig_n<128>(Gg, 128, Vst, r, nev, sig, lds, iwork, dwork, prof);
+__device__ int wg_eig128(const double* Gg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork) {
+    return wg_eig_n<128>(Gg, 128, Vst, r, nev, sig, lds, iwork, dwork);
 }
 __device__ int wg_eig64(const double* Gg, int ldg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork) {
-    return wg_eig_n<64>(Gg, ldg, Vst, r, nev, sig, lds, iwork, dwork, nullptr);
+    return wg_eig_n<64>(Gg, ldg, Vst, r, nev, sig, lds, iwork, dwork);
 }
 
 __global__ void TTN_KERNEL_BOUNDS k_selftest_eig128(const double* G, double* Vst, int n, int r, int nev, double* sig, double* Xout, long long* clk) {
@@ -685,7 +540,7 @@ __global__ void TTN_KERNEL_BOUNDS k_selftest_eig128(const double* G, double* Vst
     int* iwork = reinterpret_cast<int*>(lds + GEMM_LDS_TOTAL + 32);
     double* dwork = lds + GEMM_LDS_TOTAL + 32 + 64;
     const long long t0 = (long long)__builtin_amdgcn_s_memtime();
-    const int rc = (n == 64) ? wg_eig_n<64>(G, 64, Vst, r, nev, sig, lds, iwork, dwork, clk) : wg_eig_n<128>(G, 128, Vst, r, nev, sig, lds, iwork, dwork, clk);
+    const int rc = (n == 64) ? wg_eig_n<64>(G, 64, Vst, r, nev, sig, lds, iwork, dwork) : wg_eig_n<128>(G, 128, Vst, r, nev, sig, lds, iwork, dwork);
     const long long t1 = (long long)__builtin_amdgcn_s_memtime();
     if (threadIdx.x == 0) { clk[0] = t1 - t0; clk[1] = rc; }
     if (rc == 0) for (int e = threadIdx.x; e < 128 * r; e += TTN_WG) Xout[e] = lds[e];

@@ -130,8 +130,7 @@ __device__ __forceinline__ double of_gram(const lds_f64* W, lds_f64* G, int nbt,
 // Returns rl (= the new rank: full column rank) or 0 (bad pivot / orthogonality above the bar: nothing the caller relies on was changed
 // except Yj and Rout, which the general route rewrites).  FLg: the previous site's R in the layout of wg_qr_explicit
 // (FL[ga, be] = FLg[be + ynext * ga]); Rout receives R = L^T in the same layout.  All 16 waves, contains barriers.
-__device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const double* FLg, double* Rout, int rl, int rr, int ynext, double* lds,
-                                             long long* stamps) {
+__device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const double* FLg, double* Rout, int rl, int rr, int ynext, double* lds) {
     Xj = unip(Xj); Yj = unip(Yj); FLg = unip(FLg); Rout = unip(Rout); lds = unip(lds);
     rl = uni32(rl); rr = uni32(rr); ynext = uni32(ynext);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
@@ -142,8 +141,6 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
     lds_f64* misc = (lds_f64*)lds + OF_MISC;
     lds_i32* flag = (lds_i32*)misc;
     const int nbt = (ynext + 15) >> 4, nat = (rl + 15) >> 4;            // tile rows per s of W, tile columns of W
-    long long t_prev = stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
-#define OFS(i) if (stamps) { const long long now_ = (long long)__builtin_amdgcn_s_memtime(); if (tid == 0) stamps[i] += now_ - t_prev; t_prev = now_; }
     // ---- P0: FL image (zero padded), G := I, flags ----
     __syncthreads();
     for (int e = tid; e < 5248; e += TTN_WG) F[e] = 0.0;
@@ -152,7 +149,6 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
     __syncthreads();
     for (int e = tid; e < rr * ynext; e += TTN_WG) { const int ga = e / ynext, be = e - ga * ynext; F[OF_AT(ga, be)] = FLg[e]; }
     __syncthreads();
-    OFS(0)
     // ---- P1: W_s[be, al] = sum_ga FL[ga, be] X_j[s, al, ga]; wave (tr, tc) owns rows be = 16 tr + ., columns al = 16 tc + . ----
     {
         const int tr = wave & 3, tc = wave >> 2;
@@ -174,12 +170,10 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
         }
     }
     __syncthreads();
-    OFS(1)
     // ---- P2: G = W^T W; the FL image is dead: zero it for L^-1 ----
     for (int e = tid; e < 5248; e += TTN_WG) F[e] = 0.0;
     of_gram<false>(W, G, nbt, nat, rl);
     __syncthreads();
-    OFS(2)
     // ---- P3: blocked Cholesky of the leading 16 nat columns (the padding is the identity) ----
     if (wave == 0) {
         double dm = 0.0;
@@ -231,7 +225,6 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
         }
         __syncthreads();
     }
-    OFS(3)
     // ---- P4: off-diagonal blocks of X = L^-1, level by level: X_ij = -X_ii sum_{k = j}^{i - 1} L_ik X_kj ----
     for (int lev = 1; lev < nat; ++lev) {
         const int ib = lev + wave, jbk = wave;
@@ -253,7 +246,6 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
         }
         __syncthreads();
     }
-    OFS(4)
     // ---- P5: Q[rho][al'] = sum_{al <= al'} W[rho][al] X[al'][al]; wave (rb, ch): row block rb, column blocks {0, 3} / {1, 2} ----
     {
         const int rb = wave & 7, ch = wave >> 3;
@@ -291,7 +283,6 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
         }
         __syncthreads();
     }
-    OFS(5)
     // ---- P6: the orthogonality of Q, measured ----
     {
         double dev = of_gram<true>(W, G, nbt, nat, rl);
@@ -301,11 +292,8 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
         const double devmax = __longlong_as_double((long long)((__attribute__((address_space(3))) unsigned long long*)misc)[1]);
         if (!(unif64(devmax) <= ORTHO_FUSED_ACCEPT)) return 0;
     }
-    OFS(6)
     // ---- P7: R = L^T for the next site: Rout[i + rl c] = L[c][i], i <= c ----
     for (int e = tid; e < rl * rl; e += TTN_WG) { const int c = e / rl, i = e - c * rl; Rout[e] = (i <= c) ? (double)G[OF_G(c, i)] : 0.0; }
     __syncthreads();
-    OFS(7)
-#undef OFS
     return rl;
 }

@@ -20,11 +20,8 @@ struct OrthoArgs {
     // counter and the list of unfinished trains (int [1 + batch]).
     int mode;
     int* state;
-    int ramp;                   // mode 1 only: stop the right sweep at its first site (k_ortho_ramp, csrc/ttn_ortho_ramp.h, takes it from there)
     const int* trains;          // mode 3 only: the trains k_ortho512 did not finish (workgroup w takes train trains[w]); nullptr: b = blockIdx.x
-    int no_cholqr;              // bit 0: no Cholesky-QR steps on the general route, bit 1: no fused steps (TTN_ORTHO_CHOLQR = 0 sets both,
-                                // 1 only bit 1: diagnostics, parity tests of every route)
-    long long* prof;            // TTN_PROF=1: s_memtime stamp after every QR / LQ step of train b at prof[16 * batch + 120 * b + step] (ttn_prof_steps)
+    int no_cholqr;              // bit 1: no fused steps (TTN_ORTHO_CHOLQR = 1: diagnostics, parity tests of every route)
 };
 
 // Thin QR  T = Q R  of the column-major mm x nn matrix Tm (ld = mm) through the blocked Householder LQ of its
@@ -58,27 +55,21 @@ __device__ int wg_qr_explicit(int mm, int nn, double* Tm, double* Qb, double* Rb
 #define ORTHO_CHOLQR_ACCEPT 2.0e-13
 #define ORTHO_CHOLQR_SECOND 1.0e-6
 #define ORTHO_CHOLQR_PIVOT_MAX 1.0e8         // pivot ratio (a lower bound of cond^2) above which the attempt stops after the factorisation
-struct CholQrWork { double *Ga, *Cc, *L1g; double* scal; int* iflag; double* red; long long* stamps; };
-#define OQ_STAMP(i) if (Cw.stamps && threadIdx.x == 0) Cw.stamps[i] += (long long)__builtin_amdgcn_s_memtime() - t_prev_; if (Cw.stamps) t_prev_ = (long long)__builtin_amdgcn_s_memtime();
+struct CholQrWork { double *Ga, *Cc, *L1g; double* scal; int* iflag; double* red; };
 __device__ __noinline__ int wg_qr_cholqr(int mm, int nn, double* Tm, double* Qb, double* Rb, CholQrWork Cw, double* lds) {
     mm = uni32(mm); nn = uni32(nn); Tm = unip(Tm); Qb = unip(Qb); Rb = unip(Rb); lds = unip(lds);
     Cw.Ga = unip(Cw.Ga); Cw.Cc = unip(Cw.Cc); Cw.L1g = unip(Cw.L1g); Cw.scal = unip(Cw.scal); Cw.iflag = unip(Cw.iflag); Cw.red = unip(Cw.red);
     const int tid = threadIdx.x;
     const int p = nn, q = mm;
-    long long t_prev_ = Cw.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
     const View Mv = mkview(Tm, plain(q), plain(1));                          // M[i, c] = Tm[i * mm + c] = T[c, i]
     wg_syrk(p, q, Mv, mkview(Cw.Ga, plain(1), plain(128)), 1.0, lds);
-    OQ_STAMP(0)
     wg_img_load(lds, 0, Cw.Ga, p, Cw.red);
     if (wg_chol_lds128(p, lds, Cw.red, Cw.iflag, Cw.scal + 1) != 0) return 0;
     if (!(unif64(Cw.scal[1]) <= ORTHO_CHOLQR_PIVOT_MAX)) return 0;
     for (int e = tid; e < p * p; e += TTN_WG) { const int i = e % p, j = e / p; Cw.L1g[i + 128 * j] = lds[i + 128 * j]; }      // L1 (the Gram product below takes the image)
-    OQ_STAMP(1)
     wg_trsm_lower_cols(p, q, lds, Tm, q, 1.0, Qb, q);                        // Q1 = L1^-1 M, row-major p x q = Qb column-major mm x nn
-    OQ_STAMP(2)
     wg_syrk(p, q, mkview(Qb, plain(q), plain(1)), mkview(Cw.Cc, plain(1), plain(128)), 1.0, lds);
     const double dev = wg_img_load(lds, 0, Cw.Cc, p, Cw.red);
-    OQ_STAMP(3)
     const double* Lsrc = Cw.L1g;                                             // L[i, k] at Lsrc[i + 128 k]
     if (!(dev <= ORTHO_CHOLQR_ACCEPT)) {
         if (!(dev <= ORTHO_CHOLQR_SECOND)) return 0;
@@ -94,7 +85,6 @@ __device__ __noinline__ int wg_qr_cholqr(int mm, int nn, double* Tm, double* Qb,
         Rb[e] = (i <= c) ? Lsrc[c + 128 * i] : 0.0;
     }
     __syncthreads();
-    OQ_STAMP(4)
     return p;
 }
 
@@ -154,8 +144,6 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
     Cw.scal = W.Ss;                                                          // LDS words of the Householder panel matrices, dead outside wg_lq_blocked
     Cw.iflag = (int*)(W.Ss + 8);
     Cw.red = red;
-    Cw.stamps = P.prof ? P.prof + 136LL * gridDim.x + 64LL * b : nullptr;
-    if (P.prof && tid == 0) P.prof[16LL * gridDim.x + 120LL * b + 100] = (long long)__builtin_amdgcn_s_memtime();
     if (P.mode != 3 && tid == 0) dev_r_and_d_to_rks(d, X.dims, xr, 1024, yr);
     __syncthreads();
     const int ic = P.center;
@@ -182,7 +170,7 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
         const View Tv = mkview(Tm, plain(1), Idx{n, (long long)yl, (long long)mm});   // [al, (s + n*be)]
         wg_gemm(yl, n * rr, rl, FR, Xv, Tv, 1.0, 0.0, lds);
         double* Rn = which ? Rb0 : Rb1;
-        int rnew = (rr <= 64 && mm > rr && !(P.no_cholqr & 1)) ? wg_qr_cholqr(mm, rr, Tm, Qb, Rn, Cw, lds) : 0;
+        int rnew = (rr <= 64 && mm > rr) ? wg_qr_cholqr(mm, rr, Tm, Qb, Rn, Cw, lds) : 0;
         if (!rnew) rnew = wg_qr_explicit(mm, rr, Tm, Qb, Rn, W, lds);
         // Y_j[s, al, be] = Q[al + yl*s, be]
         for (long long e = tid; e < (long long)mm * rnew; e += TTN_WG) {
@@ -210,7 +198,7 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
     for (int j = jstart; j > ic; --j) {
         const int n = X.dims[j];
         const int ynext = uni32((int)yr[j + 1]), rl = uni32((int)xr[j]), rr = uni32((int)xr[j + 1]);
-        if (P.mode == 1 && (P.ramp || ortho512_eligible(n, rl, rr, ynext))) { jstop = j; break; }
+        if (P.mode == 1) { jstop = j; break; }
         double* Xj = X.data + (long long)b * X.stride + X.off[j];
         double* Yj = Y.data + (long long)b * Y.stride + Y.off[j];
         const int mm = ynext * n;
@@ -218,13 +206,13 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
         // the whole step in registers and LDS when the site is a tall QTT core of rank <= 64 (ttn_ortho_fused.h); 0 = not taken / refused
         int rnew = 0;
         if (n == 2 && rl <= 64 && rr <= 64 && ynext <= 64 && mm > rl && !(P.no_cholqr & 2))
-            rnew = ortho_step_fused(Xj, Yj, whichL ? Rd : Rc, Rn, rl, rr, ynext, lds, Cw.stamps ? Cw.stamps + 8 : nullptr);
+            rnew = ortho_step_fused(Xj, Yj, whichL ? Rd : Rc, Rn, rl, rr, ynext, lds);
         if (!rnew) {
         // Tt[(be + ynext*s), al] = sum_ga FL[ga,be] X_j[s,al,ga]  ==  (FL^T) * X2,  X2[ga, (s + n*al)]
         const View X2 = mkview(Xj, plain((long long)n * rl), plain(1));
         const View Tv = mkview(Tm, plain(1), Idx{n, (long long)ynext, (long long)mm});
         wg_gemm(ynext, n * rl, rr, tview(FL), X2, Tv, 1.0, 0.0, lds);
-        rnew = (rl <= 64 && mm > rl && !(P.no_cholqr & 1)) ? wg_qr_cholqr(mm, rl, Tm, Qb, Rn, Cw, lds) : 0;
+        rnew = (rl <= 64 && mm > rl) ? wg_qr_cholqr(mm, rl, Tm, Qb, Rn, Cw, lds) : 0;
         if (!rnew) rnew = wg_qr_explicit(mm, rl, Tm, Qb, Rn, W, lds);
         // Y_j[s, al, be] = Qt[(be + ynext*s), al]   (core shape (n, rnew, ynext))
         for (int e = tid; e < mm * rnew; e += TTN_WG) {
@@ -237,14 +225,11 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
         __syncthreads();
         FL = tview(mkview(Rn, plain(1), plain(rnew)));    // FL[ga, be] = Rt[be, ga]  (rl x rnew)
         whichL ^= 1;
-        if (P.prof && tid == 0 && d - 1 - j < 120) P.prof[16LL * gridDim.x + 120LL * b + (d - 1 - j)] = (long long)__builtin_amdgcn_s_memtime();
     }
     if (P.mode == 1) {                                    // hand over to k_ortho512 (and then to the mode-3 launch)
         if (tid == 0) { st[0] = jstop; st[1] = whichL; st[2] = which; st[3] = 0; }
         return;
     }
-#define OSTAMP(i) if (P.prof && tid == 0) P.prof[16LL * gridDim.x + 120LL * b + 100 + (i)] = (long long)__builtin_amdgcn_s_memtime();
-    OSTAMP(1)
     // ---- centre core: Y_i[s] = FR * X_i[s] * FL  (src/tt_tools.jl:537-541) ----
     {
         const int n = X.dims[ic];
@@ -255,10 +240,8 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
         const View Xv = mkview(Xi, plain(n), Idx{n, 1, (long long)n * rl});
         const View Tv = mkview(Tm, plain(1), Idx{n, (long long)yl, (long long)mm});
         wg_gemm(yl, n * rr, rl, FR, Xv, Tv, 1.0, 0.0, lds);
-        OSTAMP(2)
         const View Tmv = mkview(Tm, plain(1), plain(mm));                               // (mm x rr)
         const View Yv = mkview(Yi, Idx{yl, (long long)n, 1}, plain((long long)n * yl)); // [(al + yl*s), be']
         wg_gemm(mm, yn, rr, Tmv, FL, Yv, 1.0, 0.0, lds);
-        OSTAMP(3)
     }
 }

@@ -74,7 +74,6 @@ __global__ void __launch_bounds__(TTN_STREAM_TB) k_apply(TTODev A, TTDev x, TTDe
     const double* Xk = x.data + (long long)b * x.stride + x.off[k];
     double* Yk = y.data + (long long)b * y.stride + y.off[k];
     const long long P = (long long)Rl * rl;                           // left rank of Y
-#ifndef TTN_APPLY_BY_INPUT_FIBRE
     // n = 2, operator core in LDS: one thread = one OUTPUT row p = a' + Rl v' and TTN_APPLY_K consecutive output columns c = a + Rr v
     // (the layout of k_hadamard: Y_k is the Kronecker product of the operator core and X_k, slice by slice).  For every j the lanes of
     // a wave write consecutive rows: 16 bytes per lane, coalesced, non-temporal; the index arithmetic is paid once per K fibres, the
@@ -105,8 +104,6 @@ __global__ void __launch_bounds__(TTN_STREAM_TB) k_apply(TTODev A, TTDev x, TTDe
         }
         return;
     }
-#endif
-#ifndef TTN_APPLY_NO_TRANSPOSE
     // n = 2 and rl a multiple of 64 (the interior cores): a wave's 64 input fibres are 64 consecutive left indices of ONE
     // right index, so for every operator right index `ar` its Rl*64 output fibres are one contiguous run of Rl*64*16 bytes.
     // Per-lane stores would hit that run 16 bytes at a stride of Rl*16 (Rl partial passes over every cache line); instead the
@@ -143,7 +140,6 @@ __global__ void __launch_bounds__(TTN_STREAM_TB) k_apply(TTODev A, TTDev x, TTDe
         }
         return;
     }
-#endif
     for (unsigned int e = (unsigned int)first + threadIdx.x; e < (unsigned int)total; e += gridDim.x * blockDim.x) {
         const int vl = (int)(e % (unsigned int)rl), vr = (int)(e / (unsigned int)rl);
         const double* xs = Xk + (long long)n * e;
