@@ -189,6 +189,36 @@ int ttn_dmrg_linsolve_it(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, doubl
                          const int64_t* rmax_schedule, int it_solver, int64_t linsolv_maxiter, double linsolv_tol, int64_t itslv_thresh);
 int ttn_dmrg_cg_iterations(int64_t batch, int64_t* iters);
 
+/* dmrg_eigsolve(A, tt_start; N = 2, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+ * (src/solvers/dmrg.jl:501-578) and mals_eigsolve (src/solvers/mals.jl:335-425): the smallest eigenvalue of a real symmetric A and its
+ * eigenvector, by two-site sweeps with the walk, rank rules (cut_off_index / sv_trunc, clamped to the stage's rmax) and stage schedule
+ * of ttn_dmrg_linsolve; MALS takes the same per-sweep rmax plan (mals.jl:393, :413).  x receives orthogonalize(x0) first and leaves
+ * normalised, with the gauge flags the reference leaves.  Per train and micro-step: E[b * hist_len + t] = the local eigenvalue,
+ * r_hist[b * hist_len + t] = max(ttv_rks) after the micro-step's core move — the closing DMRG solve records both before its left move
+ * (dmrg.jl:539-540).  hist_len must equal ttn_eigsolve_history_len(mode = 1 DMRG / 0 MALS): 2 (d - 2) nsweeps + 1 for DMRG,
+ * 2 (d - 1) nsweeps for MALS, nsweeps = the full sweeps of the schedule; anything else is TTN_ERR_ARG.
+ * Local problem: the smallest eigenpair of 1/2 (K + K^T).  Dense (Householder tridiagonalisation, Sturm multisection, inverse
+ * iteration: |lambda - lambda_LAPACK| ~ 1e-15 ||K||) unless it_solver != 0 or it has more than the threshold unknowns (or more than
+ * 2048); then matrix-free thick-restart Lanczos, Krylov dimension 30, full reorthogonalisation, at most linsolv_maxiter restarts,
+ * stopped at a Ritz residual <= linsolv_tol.  The threshold is itslv_thresh for DMRG; mals_eigsolve does not forward itslv_thresh to
+ * its local solver in the reference (mals.jl:383-390, :403-410), so it is 256 there whatever is passed.  The reference's iterative
+ * solvers (KrylovKit eigsolve for DMRG, IterativeSolvers lobpcg for MALS) reach the same eigenpair to linsolv_tol, not the same bits.
+ * Every local eigenvector is signed so that its first entry of largest modulus is positive: a batch gives the trains of single calls.
+ * Refused before any launch: bad schedules (as ttn_dmrg_linsolve), n_i cap_i above 256, two-site problems above 65 536 unknowns, and a
+ * capacity / batch whose workspace — G and H slots, dense K of up to min(N, threshold)^2, Lanczos basis (30 + 1 + 10 + R_max) N_max —
+ * does not fit in device memory (TTN_ERR_CAPACITY).  A Lanczos solve that exhausts its restarts with a residual above
+ * 1e3 linsolv_tol: TTN_ERR_NO_CONVERGENCE (below that the current Ritz pair is kept, as KrylovKit does).  Synchronises. */
+int ttn_dmrg_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
+                      const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                      int64_t hist_len, double* E, int64_t* r_hist);
+int ttn_mals_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
+                      const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                      int64_t hist_len, double* E, int64_t* r_hist);
+int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_t* sweep_schedule, int64_t* len);
+/* Per train of the last eigensolve: operator applications of its Lanczos solves (0: every local problem dense) and the largest final
+ * Lanczos residual norm. */
+int ttn_eigsolve_stats(int64_t batch, int64_t* lanczos_applies, double* lanczos_residual);
+
 /* --- TDVP local contractions (src/solvers/tdvp.jl:29-43, :205-208), batched, Float64 (cplx = 0) or ComplexF64
  * (cplx = 1: interleaved re/im pairs, as Julia stores them).  Tensors are column-major in the layouts tdvp1sweep! / tdvp2sweep! hold
  * them in — sites (l, s, r) = permutedims(ttv_vec[k], (2,1,3)), operator cores (a, s, b, s') = permutedims(tto_vec[k], (3,1,4,2))

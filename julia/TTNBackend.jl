@@ -8,7 +8,7 @@
 module TTNBackend
 
 using TensorTrainNumerics
-import TensorTrainNumerics: TTvector, TToperator, orthogonalize, tt_compress!, _tt_bond_truncate!, hadamard, add!, r_and_d_to_rks, zeros_tt,
+import TensorTrainNumerics: TTvector, TToperator, dmrg_eigsolve, mals_eigsolve, orthogonalize, tt_compress!, _tt_bond_truncate!, hadamard, add!, r_and_d_to_rks, zeros_tt,
     _applyH1_lsr, _applyH0, _update_left_env, _update_right_env, _applyH2_lsr
 import Base: *, +
 
@@ -225,6 +225,56 @@ end
 # Status is sticky per handle: ttn_compress_status(h, C_NULL) returns the first error any compress / sweep / swap / solver call
 # recorded on h since the last query (capacity -5, Jacobi sweep limit -9, singular local system -10) and clears it.
 # ccall((:ttn_status_all, LIB), Cint, ()) answers for every live handle and for handles freed with an unread code, in one synchronisation.
+
+# ---- Two-site eigensolvers (src/solvers/dmrg.jl:501-578, src/solvers/mals.jl:335-425) --------------------------------------------
+# One train through the handle API: upload A and tt_start, solve on the device, download the eigenvector.  The rank capacity is the
+# reference's buffer bound min(rmax, prod(dims[1:k]), prod(dims[k+1:end])) clamped to n_k * rank <= 256 (the device's SVD core moves).
+function _eigsolve_dev(sym::Symbol, mode::Int, A::TToperator{Float64, N}, x0::TTvector{Float64, N}, tol, sweep_schedule, rmax_schedule,
+                       it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh) where {N}
+    dims = _dims(x0.ttv_dims)
+    ss, rs = Int64[sweep_schedule...], Int64[rmax_schedule...]
+    length(ss) == length(rs) || throw(AssertionError("Sweep schedule error"))
+    rtop = maximum(rs)
+    cap = Int64[k == 0 || k == N ? 1 : max(min(rtop, prod(dims[1:k]), prod(dims[(k + 1):end]), div(256, max(dims[k], dims[k + 1]))), x0.ttv_rks[k + 1])
+                for k in 0:N]
+    hl = Ref{Int64}(0)
+    _chk(ccall((:ttn_eigsolve_history_len, LIB), Cint, (Cint, Int64, Int64, Ptr{Int64}, Ref{Int64}), Cint(mode), N, length(ss), ss, hl))
+    hA, hx0, hx = Ref{Ptr{Cvoid}}(), Ref{Ptr{Cvoid}}(), Ref{Ptr{Cvoid}}()
+    pa, px = _ptrs(A.tto_vec), _ptrs(x0.ttv_vec)
+    GC.@preserve A x0 pa px begin
+        _chk(ccall((:ttn_tto_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}), N, dims, A.tto_rks, pa, hA))
+        _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, dims, x0.ttv_rks, 1, hx0))
+        _chk(ccall((:ttn_tt_upload, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Int64}), hx0[], 0, px, x0.ttv_rks, x0.ttv_ot))
+    end
+    _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, dims, cap, 1, hx))
+    E = zeros(Float64, max(hl[], 1))
+    r_hist = zeros(Int64, max(hl[], 1))
+    _chk(ccall(sym == :dmrg ? (:ttn_dmrg_eigsolve, LIB) : (:ttn_mals_eigsolve, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Ptr{Int64}, Ptr{Int64}, Cint, Int64, Float64, Int64, Int64, Ptr{Float64}, Ptr{Int64}),
+        hA[], hx0[], hx[], tol, length(ss), ss, rs, Cint(it_solver), linsolv_maxiter, linsolv_tol, itslv_thresh, hl[], E, r_hist))
+    rks, ot = zeros(Int64, N + 1), zeros(Int64, N)
+    _chk(ccall((:ttn_tt_ranks, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), hx[], 0, rks, ot))
+    x = zeros_tt(Float64, x0.ttv_dims, rks)
+    px = _ptrs(x.ttv_vec)
+    GC.@preserve x px _chk(ccall((:ttn_tt_download, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}), hx[], 0, px))
+    x.ttv_ot .= ot
+    ccall((:ttn_tt_free, LIB), Cint, (Ptr{Cvoid},), hx0[]); ccall((:ttn_tt_free, LIB), Cint, (Ptr{Cvoid},), hx[])
+    ccall((:ttn_tto_free, LIB), Cint, (Ptr{Cvoid},), hA[])
+    return E[1:hl[]], x, r_hist[1:hl[]]
+end
+
+function dmrg_eigsolve(A::TToperator{Float64, D}, tt_start::TTvector{Float64, D}; N = 2, tol = 1.0e-12, sweep_schedule = [2],
+                       rmax_schedule = [isqrt(prod(tt_start.ttv_dims))], it_solver = false, linsolv_maxiter = 200,
+                       linsolv_tol = max(sqrt(tol), 1.0e-8), itslv_thresh = 256) where {D}
+    N == 2 || error("dmrg_eigsolve: only the two-site scheme N = 2 runs on the device")
+    return _eigsolve_dev(:dmrg, 1, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+end
+
+function mals_eigsolve(A::TToperator{Float64, N}, tt_start::TTvector{Float64, N}; tol = 1.0e-12, sweep_schedule = [2],
+                       rmax_schedule = [round(Int, sqrt(prod(tt_start.ttv_dims)))], it_solver = false, linsolv_maxiter = 200,
+                       linsolv_tol = max(sqrt(tol), 1.0e-8), itslv_thresh = 256) where {N}
+    return _eigsolve_dev(:mals, 0, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+end
 
 # ---- TDVP local contractions (src/solvers/tdvp.jl:29-43, :205-208) ------------------------------------------------------------
 # The five @tensor kernels of tdvp1sweep! / tdvp2sweep!, for Float64 and ComplexF64 arrays in the layouts the sweeps hold

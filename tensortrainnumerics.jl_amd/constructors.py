@@ -154,3 +154,76 @@ def rand_tt(dims: Sequence[int], rks, seed: int = 0) -> TTvector:
         shape = (int(dims[k]), int(rks[k]), int(rks[k + 1]))
         y.ttv_vec[k] = portable_randn(shape[0] * shape[1] * shape[2], seed * 1000003 + k).reshape(shape, order="F")
     return y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Spin-chain Hamiltonians (src/tt_operators.jl:56-64, :162-260): rank-5 open-boundary TT operators on d spin-1/2 sites, Float64 only.
+# ---------------------------------------------------------------------------------------------------------------------
+_PAULI_X = np.array([[0.0, 1.0], [1.0, 0.0]])
+_PAULI_Z = np.array([[1.0, 0.0], [0.0, -1.0]])
+_Y_REAL = np.array([[0.0, -1.0], [1.0, 0.0]])        # sigma_y = i * _Y_REAL
+
+
+def _pauli_axis(mu) -> str:
+    a = str(mu).lstrip(":").lower()
+    if a not in ("x", "y", "z"):
+        from ._lib import TTNError
+        raise TTNError(f"unknown Pauli axis {mu!r}: use 'x', 'y' or 'z'")
+    return a
+
+
+def _pauli_pair_factors(mu, nu):
+    """Real factors (P1, P2) with P1 (x) P2 = sigma_mu (x) sigma_nu (src/tt_operators.jl:56-64): sigma_y (x) sigma_y = (-Y) (x) Y, Y real."""
+    a, b = _pauli_axis(mu), _pauli_axis(nu)
+    if a == "y" and b == "y":
+        return -_Y_REAL, _Y_REAL.copy()
+    if a == "y" or b == "y":
+        from ._lib import TTNError
+        raise TTNError("a single sigma_y factor is complex: only real (Float64) operators are offered")
+    m = {"x": _PAULI_X, "z": _PAULI_Z}
+    return m[a].copy(), m[b].copy()
+
+
+def heisenberg_xyz_tto(d: int, jx: float = 1.0, jy: float = 1.0, jz: float = 1.0, lam: float = 0.0, field="x") -> TToperator:
+    """H = jx sum_k X_k X_{k+1} + jy sum_k Y_k Y_{k+1} + jz sum_k Z_k Z_{k+1} + lam sum_k P_k (P = the field's Pauli matrix), as the
+    reference's direct rank-5 TT operator (src/tt_operators.jl:162-217).  A field along y with lam != 0 is complex: TTNError."""
+    assert d >= 2, "Heisenberg XYZ chain needs at least 2 spin sites"
+    f = _pauli_axis(field)
+    if f == "y":
+        if lam != 0.0:
+            from ._lib import TTNError
+            raise TTNError("field = :y with lam != 0 gives a complex operator: only real (Float64) operators are offered")
+        Pf = np.zeros((2, 2))
+    else:
+        Pf = _PAULI_X if f == "x" else _PAULI_Z
+    Px1, Px2 = _pauli_pair_factors("x", "x")
+    Py1, Py2 = _pauli_pair_factors("y", "y")
+    Pz1, Pz2 = _pauli_pair_factors("z", "z")
+    Id = np.eye(2)
+    rks = [1] + [5] * (d - 1) + [1]
+    out = zeros_tto((2,) * d, rks)
+    c = out.tto_vec[0]
+    c[:, :, 0, 0], c[:, :, 0, 1], c[:, :, 0, 2], c[:, :, 0, 3], c[:, :, 0, 4] = lam * Pf, jx * Px1, jy * Py1, jz * Pz1, Id
+    for k in range(1, d - 1):
+        c = out.tto_vec[k]
+        c[:, :, 0, 0], c[:, :, 1, 0], c[:, :, 2, 0], c[:, :, 3, 0], c[:, :, 4, 0] = Id, Px2, Py2, Pz2, lam * Pf
+        c[:, :, 4, 1], c[:, :, 4, 2], c[:, :, 4, 3], c[:, :, 4, 4] = jx * Px1, jy * Py1, jz * Pz1, Id
+    c = out.tto_vec[d - 1]
+    c[:, :, 0, 0], c[:, :, 1, 0], c[:, :, 2, 0], c[:, :, 3, 0], c[:, :, 4, 0] = Id, Px2, Py2, Pz2, lam * Pf
+    return out
+
+
+def ising_tto(d: int, J: float = 1.0, h: float = 0.0, interaction="z", field="x") -> TToperator:
+    """J sum_k S_k S_{k+1} (S = the interaction axis) + h sum_k P_k (src/tt_operators.jl:219-237)."""
+    a = _pauli_axis(interaction)
+    return heisenberg_xyz_tto(d, jx=J if a == "x" else 0.0, jy=J if a == "y" else 0.0, jz=J if a == "z" else 0.0, lam=h, field=field)
+
+
+def xxz_tto(d: int, J: float = 1.0, Delta: float = 1.0, h: float = 0.0, field="z") -> TToperator:
+    """J (H_xx + H_yy) + J Delta H_zz + h H_field (src/tt_operators.jl:239-248)."""
+    return heisenberg_xyz_tto(d, jx=J, jy=J, jz=J * Delta, lam=h, field=field)
+
+
+def xxx_tto(d: int, J: float = 1.0, h: float = 0.0, field="z") -> TToperator:
+    """J (H_xx + H_yy + H_zz) + h H_field (src/tt_operators.jl:250-259)."""
+    return heisenberg_xyz_tto(d, jx=J, jy=J, jz=J, lam=h, field=field)

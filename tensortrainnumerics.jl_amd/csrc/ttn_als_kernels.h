@@ -189,6 +189,24 @@ __device__ __noinline__ int wg_lu_solve(int N, double* K_, double* rhs_, int* pi
     return 0;
 }
 
+// out = K_s v = 1/2 (K + K^T) v for the two-site operator K[(ab,cd),(ef,gh)] = sum_z G_z[ab,ef] H_z[cd,gh] (see wg_cg_two_site below):
+// 2 R_z products na x nb x na into the slab W (na * nb * Rz doubles) and two na x nb x (R_z nb) products against the stacked H.
+// Shared by the matrix-free linear (wg_cg_two_site) and eigen (ttn_eigsolve_kernels.h) local solvers.
+__device__ inline void wg_two_site_apply(int na, int nb, int Rz, double* G, double* H, double* v, double* out, double* W, double* lds) {
+    const long long N = (long long)na * nb;
+    const View Vv = mkview(v, plain(1), plain(na));
+    const View Ov = mkview(out, plain(1), plain(na));
+    const View Wcat = mkview(W, plain(1), plain(na));                                            // na x (Rz nb): column gh + nb z
+    for (int z = 0; z < Rz; ++z)                                                                  // W_z = G_z V
+        wg_gemm(na, nb, na, mkview(G + (long long)na * na * z, plain(1), plain(na)), Vv, mkview(W + N * z, plain(1), plain(na)), 1.0, 0.0, lds);
+    // out = 1/2 sum_z W_z H_z^T:  B[(gh, z), cd] = H[z, cd, gh]
+    wg_gemm(na, nb, Rz * nb, Wcat, mkview(H, Idx{nb, (long long)Rz * nb, 1}, plain(Rz)), Ov, 0.5, 0.0, lds);
+    for (int z = 0; z < Rz; ++z)                                                                  // W_z = G_z^T V
+        wg_gemm(na, nb, na, tview(mkview(G + (long long)na * na * z, plain(1), plain(na))), Vv, mkview(W + N * z, plain(1), plain(na)), 1.0, 0.0, lds);
+    // out += 1/2 sum_z W_z H_z:    B[(gh, z), cd] = H[z, gh, cd]
+    wg_gemm(na, nb, Rz * nb, Wcat, mkview(H, Idx{nb, (long long)Rz, 1}, plain((long long)Rz * nb)), Ov, 0.5, 1.0, lds);
+}
+
 // -------------------------------------------------------------------------------------------------
 // Matrix-free local solve of the two-site solvers (src/solvers/dmrg.jl:92-171, the branch `it_solver || N > itslv_thresh`):
 // conjugate gradients on the SYMMETRISED local operator
@@ -210,19 +228,7 @@ __device__ __noinline__ int wg_cg_two_site(int na, int nb, int Rz, double* G, do
     const int N = na * nb;
     const int tid = threadIdx.x;
     // out = K_s v
-    auto apply = [&](double* v, double* out) {
-        const View Vv = mkview(v, plain(1), plain(na));
-        const View Ov = mkview(out, plain(1), plain(na));
-        const View Wcat = mkview(W, plain(1), plain(na));                                        // na x (Rz nb): column gh + nb z
-        for (int z = 0; z < Rz; ++z)                                                              // W_z = G_z V
-            wg_gemm(na, nb, na, mkview(G + (long long)na * na * z, plain(1), plain(na)), Vv, mkview(W + (long long)N * z, plain(1), plain(na)), 1.0, 0.0, lds);
-        // out = 1/2 sum_z W_z H_z^T:  B[(gh, z), cd] = H[z, cd, gh]
-        wg_gemm(na, nb, Rz * nb, Wcat, mkview(H, Idx{nb, (long long)Rz * nb, 1}, plain(Rz)), Ov, 0.5, 0.0, lds);
-        for (int z = 0; z < Rz; ++z)                                                              // W_z = G_z^T V
-            wg_gemm(na, nb, na, tview(mkview(G + (long long)na * na * z, plain(1), plain(na))), Vv, mkview(W + (long long)N * z, plain(1), plain(na)), 1.0, 0.0, lds);
-        // out += 1/2 sum_z W_z H_z:    B[(gh, z), cd] = H[z, gh, cd]
-        wg_gemm(na, nb, Rz * nb, Wcat, mkview(H, Idx{nb, (long long)Rz, 1}, plain((long long)Rz * nb)), Ov, 0.5, 1.0, lds);
-    };
+    auto apply = [&](double* v, double* out) { wg_two_site_apply(na, nb, Rz, G, H, v, out, W, lds); };
     auto dot = [&](const double* u, const double* v) {
         double a = 0.0;
         for (int e = tid; e < N; e += TTN_WG) a = fma(u[e], v[e], a);
@@ -270,12 +276,13 @@ struct AlsEnv {
                         uni32((int)E.br[i]), uni32((int)E.br[(i) + 1])}
 #define WG_FOR(total) for (long long e_ = threadIdx.x; e_ < (long long)(total); e_ += TTN_WG)
 struct AlsSite { int n, rl, rr, Rl, Rr, bl, br; };
-__device__ __noinline__ void als_update_G(const AlsEnv& E, int i) {
+// The operator part alone (G_{i+1} from G_i): als_update_G below, and the eigensolvers, which have no right-hand side.
+__device__ __noinline__ void als_update_G_op(const AlsEnv& E, int i) {
     double* T1 = E.T1; double* T2 = E.T2;
     const AlsSite s = SITE(i);
     const AlsSite s2 = SITE(i + 1);
-    const double *x = XC(i), *A2 = AC(i + 1), *Gi = GP(i), *Gbi = GBP(i), *b2 = BC(i + 1);
-    double *Go = GP(i + 1), *Gbo = GBP(i + 1);
+    const double *x = XC(i), *A2 = AC(i + 1), *Gi = GP(i);
+    double *Go = GP(i + 1);
     // T1[l, ph, be, L] = sum_{m, ch} Gi[l, ph, m, ch, L] x[m, ch, be]
     WG_FOR((long long)s.n * s.rl * s.rr * s.Rr) {
         long long t = e_; const int l = t % s.n; t /= s.n; const int ph = t % s.rl; t /= s.rl; const int be = t % s.rr; const int L = (int)(t / s.rr);
@@ -305,6 +312,14 @@ __device__ __noinline__ void als_update_G(const AlsEnv& E, int i) {
         Go[e_] = a;
     }
     __syncthreads();
+}
+__device__ __noinline__ void als_update_G(const AlsEnv& E, int i) {
+    als_update_G_op(E, i);
+    double* T1 = E.T1;
+    const AlsSite s = SITE(i);
+    const AlsSite s2 = SITE(i + 1);
+    const double *x = XC(i), *Gbi = GBP(i), *b2 = BC(i + 1);
+    double *Gbo = GBP(i + 1);
     // Gb: T1[al, ph] = sum_{j, ch} x[j, ch, al] Gb_i[j, ch, ph] ; Gb_{i+1}[i', al, be] = sum_ph b2[i', ph, be] T1[al, ph]
     WG_FOR((long long)s.rr * s.br) {
         const int al = (int)(e_ % s.rr), ph = (int)(e_ / s.rr);
@@ -320,6 +335,44 @@ __device__ __noinline__ void als_update_G(const AlsEnv& E, int i) {
         double a = 0.0;
         for (int ph = 0; ph < s.br; ++ph) a = fma(b2[ii + s2.n * (ph + (long long)s2.bl * be)], T1[al + (long long)s.rr * ph], a);
         Gbo[e_] = a;
+    }
+    __syncthreads();
+}
+
+// The operator part of the MALS right environment (mals.jl:10-13): H_{i-1} from core i+1 of x (current ranks E.xr), A_i and H_i.
+// k_mals_linsolve adds the right-hand side part; the eigensolvers have none.
+__device__ __noinline__ void mals_update_H_op(const AlsEnv& E, int i) {
+    const int n1 = uni32(E.x.dims[i]), n2 = uni32(E.x.dims[i + 1]);
+    const int r1 = uni32((int)E.xr[i + 1]), r2 = uni32((int)E.xr[i + 2]);
+    const int Ra = uni32((int)E.A.rks[i]), Rz = uni32((int)E.A.rks[i + 1]);
+    const double *x = XC(i + 1), *A = AC(i), *Hi = HP(i);
+    double *Ho = HP(i - 1);
+    // T1[z, j, xx, be] = sum_{k, y} Hi[z, j, xx, k, y] x[k, be, y]
+    WG_FOR((long long)Rz * n2 * r2 * r1) {
+        long long t = e_; const int z = t % Rz; t /= Rz; const int j = t % n2; t /= n2; const int xx = t % r2; const int be = (int)(t / r2);
+        double a = 0.0;
+        for (int y = 0; y < r2; ++y)
+            for (int k = 0; k < n2; ++k)
+                a = fma(Hi[z + Rz * (j + n2 * (xx + (long long)r2 * (k + (long long)n2 * y)))], x[k + n2 * (be + (long long)r1 * y)], a);
+        E.T1[e_] = a;
+    }
+    __syncthreads();
+    // T2[z, al, be] = sum_{j, xx} x[j, al, xx] T1[z, j, xx, be]
+    WG_FOR((long long)Rz * r1 * r1) {
+        long long t = e_; const int z = t % Rz; t /= Rz; const int al = t % r1; const int be = (int)(t / r1);
+        double a = 0.0;
+        for (int xx = 0; xx < r2; ++xx)
+            for (int j = 0; j < n2; ++j)
+                a = fma(x[j + n2 * (al + (long long)r1 * xx)], E.T1[z + Rz * (j + n2 * (xx + (long long)r2 * be))], a);
+        E.T2[e_] = a;
+    }
+    __syncthreads();
+    // H_{i-1}[a, ii, al, l, be] = sum_z T2[z, al, be] A[ii, l, a, z]
+    WG_FOR((long long)Ra * n1 * r1 * n1 * r1) {
+        long long t = e_; const int a_ = t % Ra; t /= Ra; const int ii = t % n1; t /= n1; const int al = t % r1; t /= r1; const int l = t % n1; const int be = (int)(t / n1);
+        double a = 0.0;
+        for (int z = 0; z < Rz; ++z) a = fma(E.T2[z + Rz * (al + (long long)r1 * be)], A[ii + n1 * (l + n1 * (a_ + (long long)Ra * z))], a);
+        Ho[e_] = a;
     }
     __syncthreads();
 }
@@ -582,40 +635,12 @@ __global__ void __launch_bounds__(TTN_WG) k_mals_linsolve(MalsArgs Q) {
 
     // H_{i-1}, Hb_{i-1} from core i+1 of x, A_i, b_i and H_i, Hb_i   (mals.jl:10-13, :60-66)
     auto update_H = [&](int i) {
+        mals_update_H_op(E, i);
         const int n1 = uni32(P.x.dims[i]), n2 = uni32(P.x.dims[i + 1]);
         const int r1 = uni32((int)xr[i + 1]), r2 = uni32((int)xr[i + 2]);
-        const int Ra = uni32((int)P.A.rks[i]), Rz = uni32((int)P.A.rks[i + 1]);
         const int ba = uni32((int)br_[i]), bz = uni32((int)br_[i + 1]);
-        const double *x = XC(i + 1), *A = AC(i), *Hi = HP(i), *Hbi = HBP(i), *bb = BC(i);
-        double *Ho = HP(i - 1), *Hbo = HBP(i - 1);
-        // T1[z, j, xx, be] = sum_{k, y} Hi[z, j, xx, k, y] x[k, be, y]
-        WG_FOR((long long)Rz * n2 * r2 * r1) {
-            long long t = e_; const int z = t % Rz; t /= Rz; const int j = t % n2; t /= n2; const int xx = t % r2; const int be = (int)(t / r2);
-            double a = 0.0;
-            for (int y = 0; y < r2; ++y)
-                for (int k = 0; k < n2; ++k)
-                    a = fma(Hi[z + Rz * (j + n2 * (xx + (long long)r2 * (k + (long long)n2 * y)))], x[k + n2 * (be + (long long)r1 * y)], a);
-            T1[e_] = a;
-        }
-        __syncthreads();
-        // T2[z, al, be] = sum_{j, xx} x[j, al, xx] T1[z, j, xx, be]
-        WG_FOR((long long)Rz * r1 * r1) {
-            long long t = e_; const int z = t % Rz; t /= Rz; const int al = t % r1; const int be = (int)(t / r1);
-            double a = 0.0;
-            for (int xx = 0; xx < r2; ++xx)
-                for (int j = 0; j < n2; ++j)
-                    a = fma(x[j + n2 * (al + (long long)r1 * xx)], T1[z + Rz * (j + n2 * (xx + (long long)r2 * be))], a);
-            T2[e_] = a;
-        }
-        __syncthreads();
-        // H_{i-1}[a, ii, al, l, be] = sum_z T2[z, al, be] A[ii, l, a, z]
-        WG_FOR((long long)Ra * n1 * r1 * n1 * r1) {
-            long long t = e_; const int a_ = t % Ra; t /= Ra; const int ii = t % n1; t /= n1; const int al = t % r1; t /= r1; const int l = t % n1; const int be = (int)(t / n1);
-            double a = 0.0;
-            for (int z = 0; z < Rz; ++z) a = fma(T2[z + Rz * (al + (long long)r1 * be)], A[ii + n1 * (l + n1 * (a_ + (long long)Ra * z))], a);
-            Ho[e_] = a;
-        }
-        __syncthreads();
+        const double *x = XC(i + 1), *Hbi = HBP(i), *bb = BC(i);
+        double *Hbo = HBP(i - 1);
         // Hb: T1[ga, ch] = sum_{j, a} x[j, ch, a] Hbi[ga, j, a] ; Hb_{i-1}[be, ii, ch] = sum_ga b[ii, be, ga] T1[ga, ch]
         WG_FOR((long long)bz * r1) {
             const int ga = (int)(e_ % bz), ch = (int)(e_ / bz);

@@ -10,6 +10,7 @@
 #include "ttn_hsvd_kernels.h"
 #include "ttn_als_kernels.h"
 #include "ttn_als_grid.h"
+#include "ttn_eigsolve_kernels.h"
 #include "ttn_eig_kernels.h"
 #include "ttn_tdvp_kernels.h"
 #include "ttn_densefact_kernels.h"
@@ -172,6 +173,8 @@ int ttn_init(int device) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mals_linsolve), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)COMPRESS_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_als_linsolve), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)COMPRESS_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_two_site_eig), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)COMPRESS_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ttv_decomp), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)COMPRESS_LDS_BYTES));
@@ -1470,6 +1473,217 @@ int ttn_dmrg_cg_iterations(int64_t batch, int64_t* iters) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!iters || batch < 0 || (size_t)batch > g_cg_iters_host.size()) return fail(TTN_ERR_ARG, "ttn_dmrg_cg_iterations: no two-site solve of that batch size has run");
     for (int64_t t = 0; t < batch; ++t) iters[t] = g_cg_iters_host[(size_t)t];
+    return TTN_OK;
+}
+
+// ---- dmrg_eigsolve / mals_eigsolve (csrc/ttn_eigsolve_kernels.h) ---------------------------------------------------------------
+// Both walk full sweeps of the same plan as dmrg_linsolve (dmrg_sweep_plan): DMRG windows 0..d-3 forward, d-2..1 backward, then the closing
+// solve at window 0 (one history entry more); MALS windows 0..d-2 forward, d-2..0 backward (mals.jl:393-418, sweep s capped at plan[s]).
+static int status_code_to_error(int st);
+static std::vector<int> g_lz_iters_host;       // Lanczos operator applications per train of the last eigensolve (ttn_eigsolve_stats)
+static std::vector<double> g_lz_res_host;      // largest final Lanczos residual per train of the last eigensolve
+
+static int eig_plan(const char* who, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule, std::vector<int64_t>& plan) {
+    static std::string msg;
+    auto bad = [&](const char* what) { msg = std::string(who) + ": " + what; return fail(TTN_ERR_ARG, msg.c_str()); };
+    if (n_stages < 1 || !sweep_schedule) return bad("empty schedule");
+    for (int64_t j = 0; j < n_stages; ++j) {
+        // the reference's while-loops (dmrg.jl:523-528, mals.jl:372-378) only terminate for positive, strictly increasing stage ends
+        if (sweep_schedule[j] < 1 || (j && sweep_schedule[j] <= sweep_schedule[j - 1])) return bad("sweep_schedule must be positive and strictly increasing");
+        if (rmax_schedule && rmax_schedule[j] < 1) return bad("bad rmax_schedule");
+    }
+    if (sweep_schedule[n_stages - 1] - 1 > TTN_DMRG_MAX_SWEEPS) return bad("more than 32 sweeps in one call");
+    plan.clear();
+    int64_t n = 0, j = 0;
+    for (;;) {
+        ++n;
+        if (n == sweep_schedule[j]) { if (++j >= n_stages) break; }
+        plan.push_back(rmax_schedule ? rmax_schedule[j] : 1);
+    }
+    return TTN_OK;
+}
+
+static int64_t eig_hist_len(int mode, int64_t d, int64_t nsweeps) { return mode == 1 ? 2 * (d - 2) * nsweeps + 1 : 2 * (d - 1) * nsweeps; }
+
+int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_t* sweep_schedule, int64_t* len) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!len || (mode != 0 && mode != 1) || d < 2) return fail(TTN_ERR_ARG, "ttn_eigsolve_history_len: bad mode / d / len");
+    std::vector<int64_t> plan;
+    const int rc = eig_plan("ttn_eigsolve_history_len", n_stages, sweep_schedule, nullptr, plan);
+    if (rc) return rc;
+    *len = eig_hist_len(mode, d, (int64_t)plan.size());
+    return TTN_OK;
+}
+
+static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
+                             const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                             int64_t hist_len, double* E_out, int64_t* r_out) {
+    const char* who = mode == 1 ? "dmrg_eigsolve" : "mals_eigsolve";
+    static std::string msg;
+    auto err = [&](int code, const char* what) { msg = std::string(who) + ": " + what; return fail(code, msg.c_str()); };
+    NEED_INIT();
+    if (!A || !x0 || !x) return err(TTN_ERR_ARG, "null handle");
+    if (!rmax_schedule || !E_out || !r_out) return err(TTN_ERR_ARG, "null schedule / history buffer");
+    if (!same_dims(A->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->batch != x0->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    const int d = x0->d;
+    if (d < 2) return err(TTN_ERR_UNSUPPORTED, "needs at least two sites");
+    if (!(tol >= 0.0) || maxiter < 1 || !(linsolv_tol >= 0.0) || itslv_thresh < 0) return err(TTN_ERR_ARG, "bad tol / linsolv_maxiter / linsolv_tol / itslv_thresh");
+    std::vector<int64_t> plan;
+    int rc = eig_plan(who, n_stages, sweep_schedule, rmax_schedule, plan);
+    if (rc) return rc;
+    if (hist_len != eig_hist_len(mode, d, (int64_t)plan.size())) return err(TTN_ERR_ARG, "hist_len differs from ttn_eigsolve_history_len");
+    // ---- every size check before anything is launched ----
+    const std::vector<int64_t>& c = x->cap;
+    const std::vector<int64_t>& R = A->rks;
+    for (int k = 0; k <= d; ++k) if (c[k] < x0->bound[k]) return fail(TTN_ERR_CAPACITY, "rank capacity of the result handle is below the start ranks");
+    auto mx = [](long long a_, long long b_) { return a_ > b_ ? a_ : b_; };
+    std::vector<long long> off(4 * d, 0);
+    long long cur = 0, Nmax = 1, mmax = 1, t1 = 1, t2 = 1, Rzmax = 1;
+    for (int i = 0; i < d; ++i) {
+        const long long n = x0->dims[i];
+        off[i] = cur; cur += n * c[i] * n * c[i] * R[i + 1];
+        mmax = mx(mmax, mx(n * c[i], n * c[i + 1]));
+        t1 = mx(t1, n * c[i] * c[i + 1] * mx(R[i], R[i + 1]));
+        t2 = mx(t2, c[i + 1] * c[i + 1] * R[i + 1]);
+        Rzmax = mx(Rzmax, R[i + 1]);
+        if (i + 1 < d) {
+            const long long n2 = x0->dims[i + 1];
+            off[2 * d + i] = cur; cur += R[i + 1] * n2 * n2 * c[i + 2] * c[i + 2];
+            Nmax = mx(Nmax, n * c[i] * n2 * c[i + 2]);
+            t1 = mx(t1, R[i + 1] * n2 * c[i + 2] * c[i + 1]);
+            t2 = mx(t2, R[i + 1] * c[i + 1] * c[i + 1]);
+        }
+    }
+    if (mmax > 256) return err(TTN_ERR_UNSUPPORTED, "n_i * capacity above 256 (ranks above 128 for n = 2) is not supported by the SVD core moves");
+    if (Nmax > 65536) return err(TTN_ERR_UNSUPPORTED, "two-site problems above 65 536 unknowns are not supported");
+    // branch choice (dmrg.jl:237, mals.jl:181): matrix-free if it_solver or N > threshold.  mals_eigsolve does not forward itslv_thresh
+    // to K_eigmin_mals (mals.jl:383-390, :403-410), so its threshold is always the default 256 there — restated.
+    const long long thresh = mode == 1 ? (long long)itslv_thresh : 256;
+    const long long dense_max = it_solver ? 0 : std::min<long long>(TTN_DENSE_LOCAL_MAX, thresh);
+    const bool need_lz = it_solver || Nmax > dense_max;
+    const long long Kdim = std::min<long long>(Nmax, dense_max);
+    const long long pmax = std::min<long long>(mmax, 256), qmax = mmax;
+    EigArgs Rg;
+    memset(&Rg, 0, sizeof(Rg));
+    MalsArgs& Q = Rg.M;
+    AlsArgs& P = Q.L;
+    P.offK = cur; cur += Kdim * Kdim;
+    Rg.offEig = cur; cur += 8 + 8 * Kdim;
+    if (need_lz) { Rg.offLz = cur; Rg.lz_nmax = Nmax; cur += (TTN_LZ_M + 1 + TTN_LZ_KEEP + Rzmax) * Nmax + 5000; }
+    P.offPb = cur; cur += Nmax;
+    P.offT1 = cur; cur += t1;
+    P.offT2 = cur; cur += t2;
+    P.offVb = cur; cur += QR_NB * qmax;
+    P.offWb = cur; cur += QR_NB * qmax;
+    Q.offM2 = cur; cur += Nmax;
+    Q.offXg = cur; cur += pmax * pmax;
+    Q.offUs = cur; cur += pmax * pmax;
+    Q.offSig = cur; cur += 4 * pmax + 64;
+    long long cmax = 1;
+    for (int k = 0; k <= d; ++k) cmax = mx(cmax, c[k]);
+    P.offTm = cur; cur += mmax * cmax;                      // the QR re-orthonormalisation of every core move
+    P.offQb = cur; cur += mmax * cmax;
+    P.offRb = cur; cur += cmax * cmax;
+    P.offTst = cur; cur += ((cmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64;
+    const long long per_train = cur;
+    const int batch = x->batch;
+    const size_t need = sizeof(double) * (size_t)per_train * batch + sizeof(long long) * (size_t)(4 * d) + 64;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        if (need > g_scratch_bytes && need - g_scratch_bytes > free_b)
+            return err(TTN_ERR_CAPACITY, "the workspace of this capacity and batch (G / H slots, dense K, Lanczos basis) does not fit in device memory");
+    }
+    rc = ttn_orthogonalize(x0, 1, x);                       // dmrg.jl:522, mals.jl:355
+    if (rc) return rc;
+    static std::vector<long long> h_off;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    rc = ensure_scratch(need);
+    if (rc) return rc;
+    rc = ensure_batch_bufs(batch);
+    if (rc) return rc;
+    double* base = (double*)g_scratch;
+    long long* d_tab = (long long*)(base + (size_t)per_train * batch);
+    h_off = off;
+    HIPCHK(hipMemcpyAsync(d_tab, h_off.data(), sizeof(long long) * h_off.size(), hipMemcpyHostToDevice, g_stream));
+    // device history and Lanczos statistics
+    static double* d_hE = nullptr; static long long* d_hR = nullptr; static size_t h_cap = 0;
+    static int* d_lzi = nullptr; static double* d_lzr = nullptr; static int lz_cap = 0;
+    const size_t hn = (size_t)batch * (size_t)hist_len;
+    if (h_cap < hn) {
+        if (d_hE) { hipFree(d_hE); hipFree(d_hR); }
+        HIPCHK(hipMalloc((void**)&d_hE, sizeof(double) * hn)); HIPCHK(hipMalloc((void**)&d_hR, sizeof(long long) * hn)); h_cap = hn;
+    }
+    if (lz_cap < batch) {
+        if (d_lzi) { hipFree(d_lzi); hipFree(d_lzr); }
+        HIPCHK(hipMalloc((void**)&d_lzi, sizeof(int) * batch)); HIPCHK(hipMalloc((void**)&d_lzr, sizeof(double) * batch)); lz_cap = batch;
+    }
+    P.A = A->dev(); P.b = x->dev(); P.x = x->dev();
+    P.scratch = base; P.scratch_stride = per_train;
+    P.off = d_tab;
+    P.status = x->d_status;
+    Q.C.status = x->d_status;
+    Q.C.sweep_stats = x->d_status + batch;
+    Q.C.pmax = (int)pmax; Q.C.qmax = (int)qmax;
+    Q.tol = tol;
+    Q.pmax = (int)pmax; Q.qmax = (int)qmax;
+    Q.mode = mode;
+    Q.nsweeps = (int)plan.size();
+    Q.rmax_final = (int)std::min<int64_t>(rmax_schedule[n_stages - 1], 1 << 30);
+    Q.rmax = Q.rmax_final;
+    int64_t rtop = 1;
+    for (size_t s_ = 0; s_ < plan.size(); ++s_) { Q.rmax_sweep[s_] = (int)std::min<int64_t>(plan[s_], 1 << 30); rtop = std::max(rtop, plan[s_]); }
+    if (mode == 1) rtop = std::max(rtop, rmax_schedule[n_stages - 1]);
+    Rg.hist_E = d_hE; Rg.hist_r = d_hR; Rg.hist_len = (int)hist_len;
+    Rg.lz_all = it_solver ? 1 : 0;
+    Rg.lz_above = (int)std::min<long long>(dense_max, 1LL << 30);
+    Rg.lz_maxrestart = (int)std::min<int64_t>(maxiter, 1 << 30);
+    Rg.lz_tol = linsolv_tol;
+    Rg.lz_iters = d_lzi; Rg.lz_res = d_lzr;
+    hipLaunchKernelGGL(k_two_site_eig, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Rg);
+    HIPCHK(hipGetLastError());
+    std::vector<int> st(batch);
+    g_lz_iters_host.assign(batch, 0);
+    g_lz_res_host.assign(batch, 0.0);
+    std::vector<long long> hr(hn);
+    if (hn) {
+        HIPCHK(hipMemcpyAsync(E_out, d_hE, sizeof(double) * hn, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hr.data(), d_hR, sizeof(long long) * hn, hipMemcpyDeviceToHost, g_stream));
+    }
+    HIPCHK(hipMemcpyAsync(g_lz_iters_host.data(), d_lzi, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(g_lz_res_host.data(), d_lzr, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(st.data(), x->d_status, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemsetAsync(x->d_status, 0, sizeof(int) * batch, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    for (size_t k = 0; k < hn; ++k) r_out[k] = (int64_t)hr[k];
+    for (int m = 1; m < d; ++m) x->bound[m] = std::min<int64_t>(x->cap[m], rtop);
+    x->bound[0] = 1; x->bound[d] = 1;
+    for (int bb = 0; bb < batch; ++bb)
+        for (int k = 0; k < d; ++k)         // mals: after the backward half sweep (right-orthogonal cores); dmrg: left_core_move! (dmrg.jl:566)
+            x->ot[(size_t)bb * d + k] = (k == 0) ? 0 : (mode == 0 ? 1 : -1);
+    for (int bb = 0; bb < batch; ++bb) if (st[bb] == TTN_EIG_STATUS_LANCZOS) return err(TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol");
+    for (int bb = 0; bb < batch; ++bb) if (st[bb]) return status_code_to_error(st[bb]);
+    return TTN_OK;
+}
+
+int ttn_dmrg_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule,
+                      int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh, int64_t hist_len, double* E, int64_t* r_hist) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return two_site_eigsolve(1, A, x0, x, tol, n_stages, sweep_schedule, rmax_schedule, it_solver, maxiter, linsolv_tol, itslv_thresh, hist_len, E, r_hist);
+}
+
+int ttn_mals_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule,
+                      int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh, int64_t hist_len, double* E, int64_t* r_hist) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return two_site_eigsolve(0, A, x0, x, tol, n_stages, sweep_schedule, rmax_schedule, it_solver, maxiter, linsolv_tol, itslv_thresh, hist_len, E, r_hist);
+}
+
+int ttn_eigsolve_stats(int64_t batch, int64_t* lanczos_applies, double* lanczos_residual) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!lanczos_applies || !lanczos_residual || batch < 0 || (size_t)batch > g_lz_iters_host.size())
+        return fail(TTN_ERR_ARG, "ttn_eigsolve_stats: no eigensolve of that batch size has run");
+    for (int64_t t = 0; t < batch; ++t) { lanczos_applies[t] = g_lz_iters_host[(size_t)t]; lanczos_residual[t] = g_lz_res_host[(size_t)t]; }
     return TTN_OK;
 }
 

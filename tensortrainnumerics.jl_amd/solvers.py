@@ -530,3 +530,108 @@ def dmrg_linsolve(A: TToperator, b: TTvector, tt_start: TTvector, tol: float = 1
     D.compress_status(dx)
     dx.max_ranks()
     return dx.download(0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dmrg_eigsolve, N = 2 (src/solvers/dmrg.jl:501-578) and mals_eigsolve (src/solvers/mals.jl:335-425) — csrc/ttn_eigsolve_kernels.h
+# ---------------------------------------------------------------------------------------------------------------------
+def _eig_schedules(who, sweep_schedule, rmax_schedule):
+    ss = [int(v) for v in sweep_schedule]
+    rs = [int(min(v, 2 ** 30)) for v in rmax_schedule]
+    if len(rs) != len(ss):
+        raise _lib.TTNError(f"{who}: Sweep schedule error (rmax_schedule and sweep_schedule differ in length)")     # dmrg.jl:513, mals.jl:346
+    if not ss or any(v < 1 for v in ss) or any(b <= a for a, b in zip(ss, ss[1:])) or any(v < 1 for v in rs):
+        raise _lib.TTNError(f"{who}: sweep_schedule must be positive and strictly increasing, rmax_schedule positive")
+    if ss[-1] - 1 > 32:
+        raise _lib.TTNError(f"{who}: more than 32 sweeps in one call")
+    return ss, rs
+
+
+def eigsolve_history_len(mode: int, d: int, sweep_schedule: Sequence[int]) -> int:
+    """Length of the E / r_hist history of one train: 2 (d - 2) nsweeps + 1 (DMRG, mode 1), 2 (d - 1) nsweeps (MALS, mode 0)."""
+    ss = [int(v) for v in sweep_schedule]
+    arr = (C.c_int64 * max(len(ss), 1))(*ss)
+    out = C.c_int64()
+    _lib.check(_lib.lib().ttn_eigsolve_history_len(int(mode), int(d), len(ss), arr, C.byref(out)))
+    return int(out.value)
+
+
+def _two_site_eigsolve_(mode, A: DeviceTTO, x0: DeviceTT, x: DeviceTT, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter,
+                        linsolv_tol, itslv_thresh):
+    who = "dmrg_eigsolve" if mode == 1 else "mals_eigsolve"
+    ss, rs = _eig_schedules(who, sweep_schedule, rmax_schedule)
+    if linsolv_tol is None:
+        linsolv_tol = max(math.sqrt(tol), 1.0e-8)                              # dmrg.jl:510, mals.jl:340
+    hl = eigsolve_history_len(mode, len(x0.dims), ss)
+    B = x0.batch
+    E = np.zeros((B, max(hl, 1)))
+    R = np.zeros((B, max(hl, 1)), dtype=np.int64)
+    arr = C.c_int64 * len(ss)
+    fn = _lib.lib().ttn_dmrg_eigsolve if mode == 1 else _lib.lib().ttn_mals_eigsolve
+    _lib.check(fn(A.h, x0.h, x.h, float(tol), len(ss), arr(*ss), arr(*rs), 1 if it_solver else 0, int(linsolv_maxiter), float(linsolv_tol),
+                  int(itslv_thresh), hl, E.ctypes.data_as(_lib.p_f64), R.ctypes.data_as(_lib.p_i64)))
+    return [list(map(float, E[b, :hl])) for b in range(B)], [list(map(int, R[b, :hl])) for b in range(B)]
+
+
+def dmrg_eigsolve_(A: DeviceTTO, x0: DeviceTT, x: DeviceTT, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
+                   rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
+                   linsolv_tol: float | None = None, itslv_thresh: int = 256):
+    """(E_b, r_hist_b) of dmrg_eigsolve(A, x0_b; N = 2, ...) for every train of the batch; x receives the eigenvectors (its capacity
+    bounds the adapted ranks).  Returns (E, r_hist): per-train lists."""
+    if rmax_schedule is None:
+        rmax_schedule = (math.isqrt(math.prod(x0.dims)),)                     # dmrg.jl:507
+    return _two_site_eigsolve_(1, A, x0, x, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+
+
+def mals_eigsolve_(A: DeviceTTO, x0: DeviceTT, x: DeviceTT, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
+                   rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
+                   linsolv_tol: float | None = None, itslv_thresh: int = 256):
+    """(E_b, r_hist_b) of mals_eigsolve(A, x0_b; ...) for every train of the batch.  itslv_thresh is accepted and, as in the reference
+    (mals.jl:383-390, :403-410), not used: the local threshold is 256."""
+    if rmax_schedule is None:
+        rmax_schedule = (int(round(math.sqrt(math.prod(x0.dims)))),)          # mals.jl:338
+    return _two_site_eigsolve_(0, A, x0, x, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+
+
+def eigsolve_stats(batch: int):
+    """(Lanczos operator applications, largest final Lanczos residual) per train of the last eigensolve."""
+    it = (C.c_int64 * batch)()
+    res = (C.c_double * batch)()
+    _lib.check(_lib.lib().ttn_eigsolve_stats(batch, it, res))
+    return [int(v) for v in it], [float(v) for v in res]
+
+
+def _eig_host(mode, A: TToperator, tt_start: TTvector, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol,
+              itslv_thresh):
+    who = "dmrg_eigsolve" if mode == 1 else "mals_eigsolve"
+    dims = tuple(tt_start.ttv_dims)
+    if rmax_schedule is None:
+        rmax_schedule = (math.isqrt(math.prod(dims)),) if mode == 1 else (int(round(math.sqrt(math.prod(dims)))),)
+    ss, rs = _eig_schedules(who, sweep_schedule, rmax_schedule)       # refusals before anything reaches the device
+    rtop = max(rs)
+    cap = dmrg_capacity(dims, tt_start.ttv_rks, rtop)                  # n_i * rank <= 256 (TTNError for start ranks beyond it)
+    dA = DeviceTTO(A)
+    dx0 = DeviceTT.from_host(tt_start)
+    dx = DeviceTT(dims, cap)
+    fn = dmrg_eigsolve_ if mode == 1 else mals_eigsolve_
+    E, R = fn(dA, dx0, dx, tol, ss, rs, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+    dx.max_ranks()
+    return E[0], dx.download(0), R[0]
+
+
+def dmrg_eigsolve(A: TToperator, tt_start: TTvector, N: int = 2, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
+                  rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
+                  linsolv_tol: float | None = None, itslv_thresh: int = 256):
+    """(E, x, r_hist) = dmrg_eigsolve(A, tt_start; N = 2, ...) (src/solvers/dmrg.jl:501-578) with the reference's keywords and defaults:
+    E the eigenvalue of every micro-step, x the normalised eigenvector train, r_hist max(ttv_rks) after every micro-step.  The rank
+    capacity is the reference's buffer bound clamped to n_i * rank <= 256 (dmrg_capacity)."""
+    if N != 2:
+        raise _lib.TTNError("dmrg_eigsolve: only the two-site scheme N = 2 is offered")
+    return _eig_host(1, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+
+
+def mals_eigsolve(A: TToperator, tt_start: TTvector, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
+                  rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
+                  linsolv_tol: float | None = None, itslv_thresh: int = 256):
+    """(E, x, r_hist) = mals_eigsolve(A, tt_start; ...) (src/solvers/mals.jl:335-425); rmax_schedule defaults to round(sqrt(prod(dims)))."""
+    return _eig_host(0, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
