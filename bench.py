@@ -3,7 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--d 30] [--rank 64]
                     [--shard trains|cores] [--op compress|apply|hadamard|add|scale|dot|orthogonalize]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One STEP = one pass of the hot path over one batch of B independent synthetic trains resident in HBM:
     y_b = tt_compress!(Δ(d) * x_b, rank)       for b = 1..B      (src/solvers/euler.jl:55's operator)
@@ -18,18 +18,24 @@ ranks come from RANK / WORLD_SIZE; launched as plain `python bench.py --gpus N` 
 B trains per GPU); torch.distributed (RCCL) carries only barriers and the max-over-ranks timing reduction.
 `--shard cores` measures the core-wise sharded pipeline (BASELINE config C4) instead.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the headline line, which
+also carries
   roofline     for the dominant kernel (k_compress): algorithmic fp64 flops of the sweep (merge GEMMs +
                Golub–Van-Loan thin-SVD count, evaluated on the actual rank profile) x B per launch / average launch
-               duration measured with HIP events on the library's stream; `traffic` = HBM bytes per launch from the
-               committed rocprofv3 PMC passes of this command (profiles/k_compress_traffic.json, written by
-               scratch/collect_profiles.sh — counters cannot be read from inside the process);
-  cpu_baseline the CPU oracle ("port": NumPy + LAPACK gesdd, the reference algorithm WITHOUT the discarded per-bond
-               orthogonalize) timed on this box's host cores: one train per core on all cores, and one train with
-               all BLAS threads; value = the best;
-  batch_sweep  the same step at B = 1, 8, 64, 256 (B = 1: latency of one train);
+               duration measured with HIP events on the library's stream during the timed steps; `traffic` = HBM bytes
+               per launch from the committed rocprofv3 PMC passes of this command (profiles/k_compress_traffic.json,
+               written by scratch/collect_profiles.sh — counters cannot be read from inside the process).
+`--full` adds every measurement and check beyond the headline (each one skipped by its --no-* option):
   verified     number of trains of the timed batch downloaded after the timed region and checked against the oracle
-               (ranks exact, tensor difference <= 1e-9).
+               (ranks exact, tensor difference <= 1e-9); the run aborts on a mismatch;
+  batch_sweep  the same step at B = 1, 8, 64, 128, 256 (B = 1: latency of one train), and drop_in: one train through
+               the stateless host-pointer entry points;
+  other_kernels  the `--op` measurement of the other hot-path kernels (N = 1);
+  c2           BASELINE config C2 (d = 20, rank 32), same op and batch;
+  core_sharded BASELINE config C4 after the headline (N > 1), under a watchdog;
+  cpu_baseline the CPU oracle ("port": NumPy + LAPACK gesdd, the reference algorithm WITHOUT the discarded per-bond
+               orthogonalize) timed on the host's cores: one train per core on all cores, and one train with
+               all BLAS threads; value = the best.
 `--op X` prints one roofline line for another hot-path kernel instead (HBM-bound: apply / hadamard / add / scale;
 fp64-MFMA-bound: dot / orthogonalize) on C3-shaped batches.
 """
@@ -658,7 +664,12 @@ def bench_op(args, T, D, emit=True):
     return res
 
 
-def main():
+def wants(args, part):
+    """Whether this run measures `part` beside the headline: only under --full, and not when --no-<part> skips it."""
+    return args.full and not getattr(args, "no_" + part)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -666,12 +677,15 @@ def main():
     ap.add_argument("--batch", type=int, default=1024, help="independent trains per GPU per step")
     ap.add_argument("--d", type=int, default=30)
     ap.add_argument("--rank", type=int, default=64)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-single", action="store_true", help="skip the batch sweep B = 1, 8, 64, 256")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-run check of downloaded trains against the oracle")
-    ap.add_argument("--no-c2", action="store_true", help="skip the C2 (d=20, rank 32) sub-record")
-    ap.add_argument("--no-ops", action="store_true", help="skip the other_kernels sub-record (apply / add / scale / hadamard / dot / orthogonalize)")
-    ap.add_argument("--no-core-sharded", action="store_true", help="N>1: skip the core-wise sharded (C4) sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle check, batch sweep, drop-in latency, other_kernels, C2, "
+                         "core-sharded (N>1) and cpu_baseline parts; a plain run measures the headline alone")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-single", action="store_true", help="--full: skip the batch sweep B = 1, 8, 64, 128, 256 and drop_in")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the post-run check of downloaded trains against the oracle")
+    ap.add_argument("--no-c2", action="store_true", help="--full: skip the C2 (d=20, rank 32) sub-record")
+    ap.add_argument("--no-ops", action="store_true", help="--full: skip the other_kernels sub-record (apply / add / scale / hadamard / dot / orthogonalize)")
+    ap.add_argument("--no-core-sharded", action="store_true", help="--full, N>1: skip the core-wise sharded (C4) sub-record")
     ap.add_argument("--core-sharded-timeout", type=int, default=240, help="N>1: watchdog of the C4 sub-record in seconds")
     ap.add_argument("--shard", default="trains", choices=["trains", "cores"],
                     help="N>1: 'trains' (default) = independent trains per GPU, no data-path collective; 'cores' = every chain cut "
@@ -687,9 +701,14 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, form the process group, all-reduce the world size and print it (no GPU needed: the "
                          "launcher test of tests/test_distributed_gloo.py)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.dump_outputs and (args.op != "compress" or args.shard != "trains"):
         raise SystemExit("--dump-outputs writes the headline step's outputs: it needs --op compress --shard trains")
+    return args
+
+
+def main():
+    args = parse_args()
 
     # ---- launcher: N > 1 without a torchrun environment -> start the ranks as a child BEFORE anything touches a GPU ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -751,15 +770,15 @@ def main():
             dist.barrier()
 
     head = run_compress_config(T, D, d, r, B, args.steps, args.warmup, rank, world, barrier, dist, red_device,
-                               verify=(rank == 0 and not args.no_verify), dump_dir=args.dump_outputs if rank == 0 else None)
+                               verify=(rank == 0 and wants(args, "verify")), dump_dir=args.dump_outputs if rank == 0 else None)
     extras = {}
-    if rank == 0 and not args.no_single:
+    if rank == 0 and wants(args, "single"):
         extras["batch_sweep"] = batch_sweep(T, D, d, r)
         extras["single_train"] = extras["batch_sweep"][0]
         extras["drop_in"] = drop_in_latency(T, d, r)
     # ---- the other hot-path kernels as driver-observed sub-records: the same measurement as `--op X`, on a batch of
     #      256 (streaming kernels: 3 GB of output per launch at most) or 1024 (dot / orthogonalize) C3-shaped trains; < 3 s in all ----
-    if rank == 0 and world == 1 and not args.no_ops and (d, r) == (30, 64):
+    if rank == 0 and world == 1 and wants(args, "ops") and (d, r) == (30, 64):
         import copy
         ops = {}
         for op, ob in (("apply", 256), ("add", 256), ("scale", 256), ("hadamard", 256), ("dot", 1024), ("orthogonalize", 1024)):
@@ -774,12 +793,12 @@ def main():
         extras["other_kernels"] = ops
     # ---- BASELINE config C2 (d = 20, rank 32) as a driver-observed sub-record, same op, same batch size (12 ms per step) ----
     c2 = None
-    if not args.no_c2 and (d, r) == (30, 64):
+    if wants(args, "c2") and (d, r) == (30, 64):
         c2 = run_compress_config(T, D, 20, 32, B, max(3, args.steps), 1, rank, world, barrier, dist, red_device,
-                                 verify=(rank == 0 and not args.no_verify))
+                                 verify=(rank == 0 and wants(args, "verify")))
     # ---- BASELINE config C4 (cores sharded over the GPUs) as a sub-record of the N > 1 line, guarded by a watchdog ----
     core_sharded = None
-    if world > 1 and not args.no_core_sharded:
+    if world > 1 and wants(args, "core_sharded"):
         core_sharded = guarded_core_sharded(args, T, D, torch, dist, rank, world, red_device, head if rank == 0 else None, extras, c2)
 
     if rank == 0:
@@ -791,7 +810,7 @@ def main():
                          "verified_max_rel_diff": c2.get("verified_max_rel_diff")}
         if core_sharded is not None:
             res["core_sharded"] = core_sharded
-        if not args.no_cpu and world == 1:
+        if wants(args, "cpu") and world == 1:
             res["cpu_baseline"] = cpu_baseline(d, r)
         print(json.dumps(res), flush=True)
     if dist is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # extra SQ counters of k_compress (one pass per set; --kernel-trace only, never with other trace domains)
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/pmc_extra; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-CMD="python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu --no-single --no-verify"
+CMD="python3 $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu --no-single --no-verify"
 i=0
 for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA" "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_MISC SQ_IFETCH SQ_INSTS_SMEM" "TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
