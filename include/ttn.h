@@ -304,6 +304,10 @@ int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const do
  * column-major, symmetric positive definite; sig[nev] = sqrt of the nev largest eigenvalues (descending), X[128*r] = sig_j * u_j (r <= 64);
  * ticks_rc[0] = device clock ticks of the whole routine, [1] = its return code; ticks_rc has 2 entries. */
 int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, double* sig, double* X, int64_t* ticks_rc);
+/* self-test of the dense symmetric eigensolver of the two-site eigensolvers (wg_sym_eig_smallest, csrc/ttn_eigsolve_kernels.h): A host,
+ * N x N, column-major, symmetric (both triangles); lam[k] = the k smallest eigenvalues ascending, Y[N*k] = their orthonormal vectors as
+ * columns (no sign normalisation).  1 <= N <= 2048, 1 <= k <= min(N, 16); TTN_ERR_ARG otherwise, before anything is launched. */
+int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, double* Y);
 /* diagnostics of the last ttn_orthogonalize that took the multi-launch form (csrc/ttn_ortho_ramp.h, ttn_ortho512.h): the four state
  * words of train b = {next site of the right-to-left sweep, buffer of the last right factor, buffer of the last left factor,
  * 1 if k_ortho512 finished the train (0: the 1024-thread kernel took it over from `next site`)}. */

@@ -93,6 +93,7 @@ SIGNATURES = {
     "ttn_dense_svd": (C.c_int, [C.c_int, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ttn_tdvp_contract_f64": (C.c_int, [C.c_int, C.c_int, i64, p_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ttn_selftest_eig128": (C.c_int, [C.c_void_p, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ttn_selftest_sym_eig": (C.c_int, [i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ttn_add": (C.c_int, [handle, handle, handle]),
     "ttn_scale": (C.c_int, [C.c_double, handle, handle]),
     "ttn_scale_batch": (C.c_int, [p_f64, handle, handle]),

@@ -1663,6 +1663,7 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
         for (int k = 0; k < d; ++k)         // mals: after the backward half sweep (right-orthogonal cores); dmrg: left_core_move! (dmrg.jl:566)
             x->ot[(size_t)bb * d + k] = (k == 0) ? 0 : (mode == 0 ? 1 : -1);
     for (int bb = 0; bb < batch; ++bb) if (st[bb] == TTN_EIG_STATUS_LANCZOS) return err(TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol");
+    for (int bb = 0; bb < batch; ++bb) if (st[bb] == TTN_EIG_STATUS_NONFINITE) return err(TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)");
     for (int bb = 0; bb < batch; ++bb) if (st[bb]) return status_code_to_error(st[bb]);
     return TTN_OK;
 }
@@ -1927,6 +1928,29 @@ int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, doub
     HIPCHK(hipStreamSynchronize(g_stream));
     if (ticks_rc) { ticks_rc[0] = hc[0]; ticks_rc[1] = hc[1]; }
     hipFree(dG); hipFree(dV); hipFree(dS); hipFree(dX); hipFree(dC);
+    return TTN_OK;
+}
+
+// self-test of the dense eigen routine of the two-site eigensolvers: A (host, N x N column-major, symmetric) -> lam[k] ascending, Y[N * k]
+// the orthonormal eigenvectors, computed by one workgroup calling wg_sym_eig_smallest as k_two_site_eig does (ld = N, 3N + 5N k scratch)
+int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, double* Y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!A || !lam || !Y || N < 1 || N > TTN_DENSE_LOCAL_MAX || k < 1 || k > std::min<int64_t>(N, TTN_NWAVES))
+        return fail(TTN_ERR_ARG, "ttn_selftest_sym_eig: need 1 <= N <= 2048 and 1 <= k <= min(N, 16)");
+    NEED_INIT();
+    double *dA = nullptr, *dL = nullptr, *dY = nullptr, *dW = nullptr;
+    HIPCHK(hipMalloc((void**)&dA, sizeof(double) * N * N));
+    HIPCHK(hipMalloc((void**)&dL, sizeof(double) * k));
+    HIPCHK(hipMalloc((void**)&dY, sizeof(double) * N * k));
+    HIPCHK(hipMalloc((void**)&dW, sizeof(double) * (3 * N + 5 * N * k)));
+    HIPCHK(hipMemcpyAsync(dA, A, sizeof(double) * N * N, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(dY, 0, sizeof(double) * N * k, g_stream));
+    hipLaunchKernelGGL(k_selftest_sym_eig, dim3(1), dim3(TTN_WG), 0, g_stream, (int)N, (int)k, dA, dL, dY, dW);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lam, dL, sizeof(double) * k, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(Y, dY, sizeof(double) * N * k, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    hipFree(dA); hipFree(dL); hipFree(dY); hipFree(dW);
     return TTN_OK;
 }
 

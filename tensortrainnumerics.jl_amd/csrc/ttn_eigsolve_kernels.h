@@ -19,6 +19,7 @@
 #define TTN_LZ_KEEP 10               // Ritz vectors kept by a thick restart
 #define TTN_LZ_LD 32                 // leading dimension of the projected matrices
 #define TTN_EIG_STATUS_LANCZOS 5     // per-train status: Lanczos exhausted its restarts with a residual above 1e3 * tol
+#define TTN_EIG_STATUS_NONFINITE 6   // per-train status: a local eigenvalue or eigenvector entry was NaN or infinite (the sweep stops there)
 
 // Workgroup maximum of values of any sign (wg_max pads the missing waves with 0.0, which is right for the moduli it is used on).
 __device__ inline double wg_max_signed(double v, double* red) {
@@ -177,6 +178,57 @@ __device__ void tri_inverse_iteration(int N, const double* dg, const double* e, 
     }
 }
 
+// Entry i of the fixed pseudo-random start vector of a recomputed vector j: uniform in [-1, 1) (splitmix64 of (j, i)), the same on every run.
+__device__ inline double tri_restart_entry(int i, int j) {
+    unsigned long long z = ((unsigned long long)(j + 1) << 32) + (unsigned long long)i + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (double)(z >> 11) * 0x1.0p-52 - 1.0;
+}
+
+// y_j -= sum_q (y_q^T y_j) y_q over the columns q < j of Y (modified Gram-Schmidt, one pass), by ONE thread.
+__device__ inline void tri_mgs(int N, const double* Y, int ldy, int j, double* yj) {
+    for (int q = 0; q < j; ++q) {
+        const double* yq = Y + (long long)q * ldy;
+        double s = 0.0;
+        for (int i = 0; i < N; ++i) s = fma(yq[i], yj[i], s);
+        for (int i = 0; i < N; ++i) yj[i] = fma(-s, yq[i], yj[i]);
+    }
+}
+
+// Vector j again, when the one from the common start collapsed under Gram-Schmidt (its eigenvalue repeats an earlier one to working
+// precision, so inverse iteration found an earlier vector's direction): three solves with the factors tri_inverse_iteration left in w
+// (T - lam_j I), from the pseudo-random start of j, each iterate orthogonalised (twice) against the columns q < j of Y before the solve
+// and once more at the end (LAPACK dstein's reorthogonalisation inside a cluster).  By ONE thread; y_j = Y column j, not normalised.
+__device__ void tri_inverse_iteration_restart(int N, const double* w, double* Y, int ldy, int j) {
+    const double* u0 = w; const double* u1 = w + N; const double* u2 = w + 2 * N; const double* l = w + 3 * N; const double* sw = w + 4 * N;
+    double* y = Y + (long long)j * ldy;
+    for (int i = 0; i < N; ++i) y[i] = tri_restart_entry(i, j);
+    for (int it = 0; it < 3; ++it) {
+        tri_mgs(N, Y, ldy, j, y);
+        tri_mgs(N, Y, ldy, j, y);
+        for (int i = 0; i + 1 < N; ++i) {
+            if (sw[i] != 0.0) { const double t = y[i]; y[i] = y[i + 1]; y[i + 1] = t; }
+            y[i + 1] -= l[i] * y[i];
+        }
+        for (int i = N - 1; i >= 0; --i) {
+            double a = y[i];
+            if (i + 1 < N) a -= u1[i] * y[i + 1];
+            if (i + 2 < N) a -= u2[i] * y[i + 2];
+            y[i] = a / u0[i];
+        }
+        double mx = 0.0;
+        for (int i = 0; i < N; ++i) mx = fmax(mx, fabs(y[i]));
+        double s = 0.0;
+        for (int i = 0; i < N; ++i) { y[i] /= mx; s = fma(y[i], y[i], s); }
+        s = 1.0 / sqrt(s);
+        for (int i = 0; i < N; ++i) y[i] *= s;
+    }
+    tri_mgs(N, Y, ldy, j, y);
+    tri_mgs(N, Y, ldy, j, y);
+}
+
 // y <- Q y for the reflectors wg_sym_tridiag left in A (H_{N-3} first), by ONE wave (the caller picks it).
 __device__ void wave_tri_backtransform(int N, const double* A, int ld, const double* tau, double* y) {
     const int lane = threadIdx.x & 63;
@@ -192,23 +244,30 @@ __device__ void wave_tri_backtransform(int N, const double* A, int ld, const dou
     }
 }
 
-// Flip the sign of v (length N) so that its first entry of largest modulus is positive.  iflag: one LDS int.
-__device__ void wg_fix_sign(long long N, double* v, double* red, int* iflag) {
+// Flip the sign of v (length N) so that its first entry of largest modulus is positive.  iflag: one LDS int.  Returns false, and leaves v
+// as it is, if an entry is NaN or infinite (they enter the maximum as +inf: fmax alone would drop a NaN, and an all-NaN v would find no
+// entry equal to the maximum and index v[0x7fffffff]).
+__device__ bool wg_fix_sign(long long N, double* v, double* red, int* iflag) {
     double vm = 0.0;
-    for (long long i = threadIdx.x; i < N; i += TTN_WG) vm = fmax(vm, fabs(v[i]));
+    for (long long i = threadIdx.x; i < N; i += TTN_WG) {
+        const double a = fabs(v[i]);
+        vm = fmax(vm, a <= 1.7976931348623157e308 ? a : __builtin_inf());
+    }
     if (threadIdx.x == 0) *iflag = 0x7fffffff;
     vm = unif64(wg_max(vm, red));
+    if (!(vm <= 1.7976931348623157e308)) return false;      // uniform: no barrier is skipped by part of the workgroup
     for (long long i = threadIdx.x; i < N; i += TTN_WG) if (fabs(v[i]) == vm) atomicMin(iflag, (int)i);
     __syncthreads();
     const int im = uni32(*iflag);
-    const bool neg = v[im] < 0.0;
+    const bool neg = im < N && v[im] < 0.0;
     __syncthreads();
     if (neg) for (long long i = threadIdx.x; i < N; i += TTN_WG) v[i] = -v[i];
     __syncthreads();
+    return true;
 }
 
 // The k smallest eigenpairs of the symmetric N x N matrix A (ld, destroyed): lam[0..k), the orthonormal vectors as the columns of Y
-// (N x k, leading dimension ldy).  work: 3N + 2N + k (6N) doubles.  k <= TTN_NWAVES (one wave back-transforms one vector).
+// (N x k, leading dimension ldy).  work: 3N + 5N k doubles.  k <= TTN_NWAVES (one wave back-transforms one vector).
 __device__ __noinline__ void wg_sym_eig_smallest(int N, double* A, int ld, int k, double* lam, double* Y, int ldy, double* work, double* red) {
     N = uni32(N); k = uni32(k); ld = uni32(ld); ldy = uni32(ldy); A = unip(A); lam = unip(lam); Y = unip(Y); work = unip(work); red = unip(red);
     double* dg = work; double* e = work + N; double* tau = work + 2 * N; double* vw = work + 3 * N;
@@ -227,18 +286,21 @@ __device__ __noinline__ void wg_sym_eig_smallest(int N, double* A, int ld, int k
     double* w = work + 3 * N;                                    // 5N doubles per thread are needed: the callers size `work` for it
     if ((int)threadIdx.x < k) tri_inverse_iteration(N, dg, e, lam[threadIdx.x], Y + (long long)threadIdx.x * ldy, w + (long long)threadIdx.x * 5 * N);
     __syncthreads();
-    // modified Gram-Schmidt over the k vectors (close eigenvalues give close inverse-iteration vectors), by thread 0
+    // modified Gram-Schmidt over the k vectors (close eigenvalues give close inverse-iteration vectors), by thread 0.  A unit vector whose
+    // remainder falls below 1/2 lay mostly in the span of the earlier ones: it is recomputed from another start (a repeated eigenvalue of a
+    // split tridiagonal gives the same vector twice, and the remainder is rounding, or exactly zero).  Above 1/2 the remainder keeps its
+    // accuracy, and the vectors are the plain inverse-iteration ones (k = 1 never gets here).
     if (threadIdx.x == 0) {
         for (int j = 1; j < k; ++j) {
             double* yj = Y + (long long)j * ldy;
-            for (int q = 0; q < j; ++q) {
-                const double* yq = Y + (long long)q * ldy;
-                double s = 0.0;
-                for (int i = 0; i < N; ++i) s = fma(yq[i], yj[i], s);
-                for (int i = 0; i < N; ++i) yj[i] = fma(-s, yq[i], yj[i]);
-            }
+            tri_mgs(N, Y, ldy, j, yj);
             double s = 0.0;
             for (int i = 0; i < N; ++i) s = fma(yj[i], yj[i], s);
+            if (!(s >= 0.25)) {
+                tri_inverse_iteration_restart(N, w + (long long)j * 5 * N, Y, ldy, j);
+                s = 0.0;
+                for (int i = 0; i < N; ++i) s = fma(yj[i], yj[i], s);
+            }
             s = 1.0 / sqrt(s);
             for (int i = 0; i < N; ++i) yj[i] *= s;
         }
@@ -247,6 +309,12 @@ __device__ __noinline__ void wg_sym_eig_smallest(int N, double* A, int ld, int k
     const int wave = threadIdx.x >> 6;
     if (wave < k) wave_tri_backtransform(N, A, ld, tau, Y + (long long)wave * ldy);
     __syncthreads();
+}
+
+// Unit-test hook (ttn_selftest_sym_eig): one workgroup runs wg_sym_eig_smallest exactly as the solver does (ld = ldy = N; work: 3N + 5N k).
+__global__ void __launch_bounds__(TTN_WG) k_selftest_sym_eig(int N, int k, double* A, double* lam, double* Y, double* work) {
+    __shared__ double red[64];
+    wg_sym_eig_smallest(N, A, N, k, lam, Y, N, work, red);
 }
 
 // ---- thick-restart Lanczos for the smallest eigenpair of K_s (wg_two_site_apply) ----
@@ -433,6 +501,7 @@ __global__ void __launch_bounds__(TTN_WG) k_two_site_eig(EigArgs R) {
     int lz_iters = 0;
     double lz_res = 0.0;
     bool lz_fail = false;
+    bool nonfinite = false;                      // uniform: set from workgroup-wide values
     auto eigsolve = [&](int i, int& a_out, int& b_out, bool v0_swapped) -> double {
         const int n1 = uni32(P.x.dims[i]), n2 = uni32(P.x.dims[i + 1]);
         const int rl = uni32((int)xr[i]), rr = uni32((int)xr[i + 2]);
@@ -485,7 +554,7 @@ __global__ void __launch_bounds__(TTN_WG) k_two_site_eig(EigArgs R) {
             wg_sym_eig_smallest(N, K, N, 1, ew, Pb, N, ew + 8, red);
             lam = unif64(ew[0]);
         }
-        wg_fix_sign(N, Pb, red, S.iflag);
+        if (!wg_fix_sign(N, Pb, red, S.iflag) || !(fabs(lam) <= 1.7976931348623157e308)) nonfinite = true;
         return lam;
     };
 
@@ -573,6 +642,7 @@ __global__ void __launch_bounds__(TTN_WG) k_two_site_eig(EigArgs R) {
         prev_dir = dir;
         const bool closing = mode == 1 && t == total - 1;
         if (tid == 0) { hE[t] = lam; if (closing) hR[t] = max_rank(); }  // dmrg.jl:539-540: the closing entries come before the left move
+        if (nonfinite) { status = TTN_EIG_STATUS_NONFINITE; break; }      // no core move of a NaN block
         const int n2 = uni32(P.x.dims[i + 1]);
         double* xi = XC(i);
         double* xn = XC(i + 1);
