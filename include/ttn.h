@@ -248,7 +248,9 @@ int ttn_tdvp_contract_f64(int op, int cplx, int64_t batch, const int64_t* dims7,
  * _svdtrunc), Float64 (cplx = 0) or ComplexF64 (cplx = 1, interleaved), column-major, DEVICE pointers, the library's stream.
  * ttn_dense_qr: Householder as LAPACK's geqr2 + org2r: A (m x n, overwritten) -> Q (m x r), R (r x n), r = min(m, n); asynchronous.
  * ttn_dense_svd: one-sided Jacobi, m >= n (pass the conjugate transpose otherwise): A (overwritten) -> U (m x n), s (n, descending),
- * Vh (n x n), A = U diag(s) Vh; synchronises (the caller reads s to choose the rank); TTN_ERR_NO_CONVERGENCE after 60 sweeps. */
+ * Vh (n x n), A = U diag(s) Vh; synchronises (the caller reads s to choose the rank); TTN_ERR_NO_CONVERGENCE after 60 sweeps.
+ * LAPACK's contract holds also where s has zeros: U has orthonormal columns and Vh orthonormal rows (U^H U = Vh Vh^H = I, n x n); the
+ * columns of U for singular values <= eps s_0 are completed to an orthonormal set (Gram-Schmidt, deterministic). */
 int ttn_dense_qr(int cplx, int64_t m, int64_t n, double* A, double* Q, double* R);
 int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* s, double* Vh);
 

@@ -1222,10 +1222,40 @@ def _tdvp_envs(A_lsr, M_asbs, Tc):
     return F
 
 
+class TTNError(RuntimeError):
+    """the error type of the library's host interface, restated here (the oracle imports nothing from the package)"""
+
+
+def _tdvp_real_parts(arrs, what):
+    """Julia's store of a complex array into a real one (`A_lsr[k] = AL`, `ψ.ttv_vec[k] = ...`: tdvp.jl:89, :148, :256, :297;
+    `F[i] = Tc.(F[i])`: :63-66): the real parts when the imaginary parts vanish (here: at most 1e-12 of the array's largest entry,
+    or of 1), an InexactError otherwise."""
+    out = []
+    for a in arrs:
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            if float(np.max(np.abs(np.imag(a)), initial=0.0)) > 1e-12 * max(1.0, float(np.max(np.abs(a), initial=0.0))):
+                raise TTNError(f"InexactError: {what} is real but the result has an imaginary part")
+            a = np.real(a)
+        out.append(a)
+    return out
+
+
+def _tdvp_envs_in(F, Tc):
+    """F[i] = Tc.(F[i])  (tdvp.jl:63-66)"""
+    if Tc is np.float64:
+        F = _tdvp_real_parts(F, "the state")
+    return [np.asarray(f, dtype=Tc) for f in F]
+
+
 def _tdvp_sync(psi: TTvector, A_lsr) -> TTvector:
-    """cores back to (s, l, r), ranks from the arrays, ttv_ot zeroed  (_sync_ranks_from_lsr!, tdvp.jl:8-18, :147-151)"""
+    """cores back to (s, l, r), ranks from the arrays, ttv_ot zeroed  (_sync_ranks_from_lsr!, tdvp.jl:8-18, :147-151).  A real ψ
+    keeps real cores or raises TTNError, untouched."""
     N = psi.N
-    psi.ttv_vec = [np.transpose(A_lsr[k], (1, 0, 2)).copy() for k in range(N)]
+    cores = [np.transpose(A_lsr[k], (1, 0, 2)).copy() for k in range(N)]
+    if not np.iscomplexobj(psi.ttv_vec[0]):
+        cores = _tdvp_real_parts(cores, "ψ")
+    psi.ttv_vec = cores
     psi.ttv_rks = [A_lsr[k].shape[0] for k in range(N)] + [A_lsr[N - 1].shape[2]]
     psi.ttv_ot = [0] * N
     return psi
@@ -1237,7 +1267,7 @@ def tdvp1sweep_(dt, psi: TTvector, H: TToperator, F=None, **kw):
     N = psi.N
     A = [np.transpose(psi.ttv_vec[k], (1, 0, 2)) for k in range(N)]
     M = [np.transpose(H.tto_vec[k], (2, 0, 3, 1)) for k in range(N)]
-    F = _tdvp_envs(A, M, Tc) if F is None else [np.asarray(f, dtype=Tc) for f in F]
+    F = _tdvp_envs(A, M, Tc) if F is None else _tdvp_envs_in(F, Tc)
     AC = A[0].astype(Tc)
     tm = _tdvp_real_or_complex_t(-1j * complex(dt))
     tp = _tdvp_real_or_complex_t(+1j * complex(dt))
@@ -1276,7 +1306,7 @@ def tdvp2sweep_(dt, psi: TTvector, H: TToperator, F=None, max_bond: int = 2 ** 6
     dth = complex(dt) / 2
     A = [np.transpose(psi.ttv_vec[k], (1, 0, 2)) for k in range(N)]
     M = [np.transpose(H.tto_vec[k], (2, 0, 3, 1)) for k in range(N)]
-    F = _tdvp_envs(A, M, Tc) if F is None else [np.asarray(f, dtype=Tc) for f in F]
+    F = _tdvp_envs(A, M, Tc) if F is None else _tdvp_envs_in(F, Tc)
     AC = A[0].astype(Tc)
     tm = _tdvp_real_or_complex_t(-1j * dth)
     tp = _tdvp_real_or_complex_t(+1j * dth)

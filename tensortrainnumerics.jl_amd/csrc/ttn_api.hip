@@ -2079,14 +2079,15 @@ int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* 
     if (m < n) return fail(TTN_ERR_ARG, "ttn_dense_svd: m >= n required (pass the conjugate transpose)");
     if (m > (1 << 20) || n > 4096) return fail(TTN_ERR_UNSUPPORTED, "ttn_dense_svd: matrix too large");
     const size_t w = cplx ? 2 : 1;
-    const size_t vw = sizeof(double) * w * (size_t)n * n, dwb = sizeof(double) * (size_t)n;
+    const size_t vw = sizeof(double) * w * (size_t)n * n, dwb = sizeof(double) * ((size_t)n + (size_t)m);
     int rc = ensure_scratch(vw + dwb + sizeof(int) * ((size_t)n + 2) + 64);
     if (rc) return rc;
     double* Vw = (double*)g_scratch;
     double* dw = Vw + w * (size_t)n * n;
-    int* iw = reinterpret_cast<int*>(dw + n);
-    if (cplx) hipLaunchKernelGGL(k_dense_svd<true>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, U, s, Vh, Vw, dw, iw, 60);
-    else hipLaunchKernelGGL(k_dense_svd<false>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, U, s, Vh, Vw, dw, iw, 60);
+    double* lw = dw + n;
+    int* iw = reinterpret_cast<int*>(lw + m);
+    if (cplx) hipLaunchKernelGGL(k_dense_svd<true>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, U, s, Vh, Vw, dw, lw, iw, 60);
+    else hipLaunchKernelGGL(k_dense_svd<false>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, U, s, Vh, Vw, dw, lw, iw, 60);
     HIPCHK(hipGetLastError());
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, iw + n, sizeof(int), hipMemcpyDeviceToHost, g_stream));

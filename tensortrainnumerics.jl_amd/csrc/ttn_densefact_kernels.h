@@ -9,7 +9,9 @@
 //   k_dense_svd  one-sided Jacobi (Hestenes) on the columns of A (m x n, m >= n; the caller passes A^H otherwise): plane rotations
 //                with a complex phase until every pair of columns is orthogonal to 8 eps sqrt(m) of the product of their norms, V accumulated,
 //                singular values = column norms, sorted descending; U (m x n), s (n), Vh (n x n).  One wave per column pair,
-//                round-robin tournament ordering: n - 1 rounds of n / 2 disjoint pairs per sweep, a barrier per round.
+//                round-robin tournament ordering: n - 1 rounds of n / 2 disjoint pairs per sweep, a barrier per round.  U keeps
+//                LAPACK's contract where s_k = 0: its columns are completed to an orthonormal set (below); Vh is a product of
+//                rotations and orthonormal as it stands.
 #pragma once
 #include "ttn_common.h"
 
@@ -28,6 +30,7 @@ template <> struct dfnum<false> {
     static __device__ __forceinline__ T sub(T a, T b) { return a - b; }
     static __device__ __forceinline__ T scale(T a, double s_) { return a * s_; }
     static __device__ __forceinline__ double abs2(T a) { return a * a; }
+    static __device__ __forceinline__ double absv(T a) { return fabs(a); }
     static __device__ __forceinline__ double re(T a) { return a; }
     static __device__ __forceinline__ double im(T) { return 0.0; }
     static __device__ __forceinline__ T make(double r, double) { return r; }
@@ -46,6 +49,7 @@ template <> struct dfnum<true> {
     static __device__ __forceinline__ T sub(T a, T b) { return T{a.x - b.x, a.y - b.y}; }
     static __device__ __forceinline__ T scale(T a, double s_) { return T{a.x * s_, a.y * s_}; }
     static __device__ __forceinline__ double abs2(T a) { return fma(a.x, a.x, a.y * a.y); }
+    static __device__ __forceinline__ double absv(T a) { return hypot(a.x, a.y); }
     static __device__ __forceinline__ double re(T a) { return a.x; }
     static __device__ __forceinline__ double im(T a) { return a.y; }
     static __device__ __forceinline__ T make(double r, double i) { return T{r, i}; }
@@ -134,11 +138,14 @@ __global__ void __launch_bounds__(TTN_DF_WG) k_dense_qr(int m, int n, double* A,
 // SVD by one-sided Jacobi.  m >= n.  G = A in place; V (n x n) accumulated in Vw; flags / norms / permutation in iw / dw (global).
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <bool CPLX>
-__global__ void __launch_bounds__(TTN_DF_WG) k_dense_svd(int m, int n, double* A, double* U, double* sv, double* Vh, double* Vw, double* dw, int* iw,
-                                                         int max_sweeps) {
+__global__ void __launch_bounds__(TTN_DF_WG) k_dense_svd(int m, int n, double* A, double* U, double* sv, double* Vh, double* Vw, double* dw, double* lw,
+                                                         int* iw, int max_sweeps) {
     typedef dfnum<CPLX> N;
     typedef typename N::T T;
     __shared__ int rotated;
+    __shared__ double red[40];
+    __shared__ double mv[TTN_DF_WG];
+    __shared__ int mi[TTN_DF_WG];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = TTN_DF_WG / 64;
     for (long long e = tid; e < (long long)n * n; e += TTN_DF_WG) N::store(Vw, e, (e % n == e / n) ? N::one() : N::zero());
     __syncthreads();
@@ -163,11 +170,15 @@ __global__ void __launch_bounds__(TTN_DF_WG) k_dense_svd(int m, int n, double* A
                     ga = N::add(ga, N::mul(N::conj(gp), gq));
                 }
                 al = wave_sum(al); be = wave_sum(be); ga = N::wsum(ga);
-                const double ag = sqrt(N::abs2(ga));
+                const double ag = N::absv(ga);
                 const double nn = sqrt(al * be);
                 // rotate above 2 eps sqrt(m) of the product of the norms; only pairs above 8 eps sqrt(m) keep the sweeps going (a pair at
                 // the rounding level of its own inner product would be rotated for ever: 1e-15 flat did not terminate on 16 x 16 blocks)
-                if (ag > tol_rot * nn && ag > 1.0e-290) {                 // (below: 1 / ag overflows; such a pair is two null columns)
+                // (below |ga| = 1e-154, |ga|^2 and al be are subnormal: the phase ga / |ga| loses its unit modulus, the rotation its
+                //  unitarity (V stopped being orthonormal at 1e-6) and the convergence test its meaning.  Such a pair is left as it is: its
+                //  columns carry singular values below eps s_0 unless the whole matrix is that small, and U's completion below
+                //  orthonormalises them.)
+                if (ag > tol_rot * nn && ag > 1.0e-154) {
                     if (lane == 0 && ag > tol_conv * nn) rotated = 1;
                     // columns [p q] <- [p q] J,  J = [[c, s ph], [-s conj(ph), c]],  ph = ga / |ga|: zeroes the (p, q) entry of G^H G
                     const T ph = N::scale(ga, 1.0 / ag);
@@ -217,5 +228,87 @@ __global__ void __launch_bounds__(TTN_DF_WG) k_dense_svd(int m, int n, double* A
     for (long long e = tid; e < (long long)n * n; e += TTN_DF_WG) {
         const int k = (int)(e % n), i = (int)(e / n);                    // Vh[k][i] = conj(V[i][perm k])
         N::store(Vh, e, N::conj(N::load(Vw, i + (long long)n * iw[k])));
+    }
+    __syncthreads();
+    // ---- orthonormal completion of U (LAPACK's contract) ----
+    // Columns k with s_k <= eps s_0 carry no reliable direction: an exact zero (a zero-padded bond, H = 0) gives a zero column, and
+    // the pair rotations of two columns near the underflow are skipped.  Each such column, in order, is projected off the columns
+    // before it twice (classical Gram-Schmidt, twice: CGS2).  A nonzero column keeps its own direction if half of its norm survives;
+    // otherwise (always for s_k = 0) it is replaced by the unit vector e_c of least leverage l_c = sum_{j<k} |U(c, j)|^2, whose
+    // projection has squared norm 1 - l_c >= (m - k) / m > 0.  Deterministic; when every s_k > eps s_0 this is one scan of s.
+    // Vw (free now) holds the projection coefficients, lw (m) the leverages.
+    int k0 = n;
+    for (int k = 0; k < n; ++k)
+        if (!(sv[k] > DBL_EPSILON * sv[0])) { k0 = k; break; }
+    if (k0 == n) return;
+    for (int i = tid; i < m; i += TTN_DF_WG) {
+        double l = 0.0;
+        for (int j = 0; j < k0; ++j) l += N::abs2(N::load(U, i + (long long)m * j));
+        lw[i] = l;
+    }
+    for (int k = k0; k < n; ++k) {
+        double nrm2 = 0.0;
+        for (int pass = (sv[k] > 0.0) ? 0 : 2; pass < 2; ++pass) {          // the column's own direction, projected twice
+            for (int j = wave; j < k; j += nwaves) {
+                T a = N::zero();
+                for (int i = lane; i < m; i += 64) a = N::add(a, N::mul(N::conj(N::load(U, i + (long long)m * j)), N::load(U, i + (long long)m * k)));
+                a = N::wsum(a);
+                if (lane == 0) N::store(Vw, j, a);
+            }
+            __syncthreads();
+            double part = 0.0;
+            for (int i = tid; i < m; i += TTN_DF_WG) {
+                T w = N::load(U, i + (long long)m * k);
+                for (int j = 0; j < k; ++j) w = N::sub(w, N::mul(N::load(U, i + (long long)m * j), N::load(Vw, j)));
+                N::store(U, i + (long long)m * k, w);
+                part += N::abs2(w);
+            }
+            nrm2 = wg_sum(part, red);
+        }
+        if (!(nrm2 > 0.25)) {                                           // (the column was unit length before the projection)
+            // the row of least leverage, lowest index on ties
+            double bv = 2.0;
+            int bi = m;
+            for (int i = tid; i < m; i += TTN_DF_WG)
+                if (lw[i] < bv) { bv = lw[i]; bi = i; }
+            mv[tid] = bv; mi[tid] = bi;
+            __syncthreads();
+            for (int h = TTN_DF_WG / 2; h > 0; h >>= 1) {
+                if (tid < h && (mv[tid + h] < mv[tid] || (mv[tid + h] == mv[tid] && mi[tid + h] < mi[tid]))) { mv[tid] = mv[tid + h]; mi[tid] = mi[tid + h]; }
+                __syncthreads();
+            }
+            const int c = mi[0];
+            // first projection exactly from U's own entries: e_c - sum_j U(:, j) conj(U(c, j))
+            for (int i = tid; i < m; i += TTN_DF_WG) {
+                T w = (i == c) ? N::one() : N::zero();
+                for (int j = 0; j < k; ++j) w = N::sub(w, N::mul(N::load(U, i + (long long)m * j), N::conj(N::load(U, c + (long long)m * j))));
+                N::store(U, i + (long long)m * k, w);
+            }
+            __syncthreads();
+            // the second projection
+            for (int j = wave; j < k; j += nwaves) {
+                T a = N::zero();
+                for (int i = lane; i < m; i += 64) a = N::add(a, N::mul(N::conj(N::load(U, i + (long long)m * j)), N::load(U, i + (long long)m * k)));
+                a = N::wsum(a);
+                if (lane == 0) N::store(Vw, j, a);
+            }
+            __syncthreads();
+            double part = 0.0;
+            for (int i = tid; i < m; i += TTN_DF_WG) {
+                T w = N::load(U, i + (long long)m * k);
+                for (int j = 0; j < k; ++j) w = N::sub(w, N::mul(N::load(U, i + (long long)m * j), N::load(Vw, j)));
+                N::store(U, i + (long long)m * k, w);
+                part += N::abs2(w);
+            }
+            nrm2 = wg_sum(part, red);
+            if (!(nrm2 > 0.0) && tid == 0) iw[n] = 1;                      // (cannot happen while the earlier columns are orthonormal)
+        }
+        const double inv = nrm2 > 0.0 ? 1.0 / sqrt(nrm2) : 0.0;
+        for (int i = tid; i < m; i += TTN_DF_WG) {
+            const T w = N::scale(N::load(U, i + (long long)m * k), inv);
+            N::store(U, i + (long long)m * k, w);
+            lw[i] += N::abs2(w);
+        }
+        __syncthreads();
     }
 }

@@ -132,10 +132,15 @@ def _applyH2_lsr(AAC, FL, FR, M1, M2):
 # reference's layouts ((l, s, r), (a, s, b, s'), column-major); the five contractions are this library's kernels, called through the
 # DEVICE-POINTER entry points of include/ttn.h; `exponentiate` is a Lanczos iteration around them whose vectors never leave the
 # device (its 30 x 30 tridiagonal projection is exponentiated on the host, as KrylovKit does).  torch is plumbing here: it owns
-# the device memory, runs on the library's own HIP stream (so kernels and tensor operations are one ordered queue), does the BLAS-1
-# work on the Lanczos vectors and the dense QR / SVD of the local matrices on the device (hipSOLVER) — the library's own QR / SVD
-# kernels are real-valued and work on TT handles; the local tensors of a real-time sweep are ComplexF64.  No CPU fallback: without
-# a GPU and the HIP library these functions raise.
+# the device memory, runs on the library's own HIP stream (so kernels and tensor operations are one ordered queue) and does the
+# BLAS-1 work on the Lanczos vectors; the dense QR / SVD of the local matrices, real or complex, are this library's kernels
+# (ttn_dense_qr / ttn_dense_svd, csrc/ttn_densefact_kernels.h).  No CPU fallback: without a GPU and the HIP library these functions
+# raise.
+#
+# dtypes: the state of a sweep is ComplexF64 when ψ or H is complex or when exp(-i dt H) is not real (-i dt has an imaginary part:
+# every real dt != 0), Float64 otherwise (real ψ and H in imaginary time, or dt = 0).  The reference computes in Tc and stores the
+# result back into ψ's own arrays (tdvp.jl:89, :148, :256, :297): a real ψ takes the real parts when the imaginary parts vanish
+# and raises (Julia's InexactError) otherwise.
 #
 # A Julia array of shape (i, j, k) in column-major order is held as a CONTIGUOUS torch tensor of shape (k, j, i).
 # ======================================================================================================================
@@ -177,13 +182,24 @@ def _jshape(t):
     return tuple(reversed(t.shape))
 
 
-def _cplx(t):
-    return 1 if t.is_complex() else 0
+def _operands(*ts):
+    """The check in front of every device-pointer call: the kernels read raw memory with ONE element type, so every tensor operand
+    must have the same dtype, float64 or complex128 (a real array read as interleaved complex is read past its end), live on the
+    GPU, and be contiguous and not a lazily conjugated view (torch.linalg.svd's Vh, x.conj()).  Raises TTNError before the library
+    is called; returns the `cplx` flag of the call."""
+    import torch
+    dts = {t.dtype for t in ts}
+    if len(dts) != 1 or not dts <= {torch.float64, torch.complex128}:
+        raise _lib.TTNError(f"device operands need one dtype, float64 or complex128: got {sorted(str(d) for d in dts)}")
+    if not all(t.is_contiguous() and not t.is_conj() for t in ts):
+        raise _lib.TTNError("device operand is a strided or lazily conjugated view: materialise it first")
+    if not all(t.is_cuda for t in ts):
+        raise _lib.TTNError(f"device operand on {[str(t.device) for t in ts]}, not all on the GPU")
+    return 1 if torch.float64 not in dts else 0
 
 
 def _p(t):
-    # the kernels read raw memory: a lazily conjugated view (torch.linalg.svd's Vh, x.conj()) or a strided one must be materialised first
-    assert t.is_contiguous() and not t.is_conj(), "device array is a view"
+    # (every caller has passed its operands through _operands first)
     return C.c_void_p(t.data_ptr())
 
 
@@ -193,48 +209,53 @@ def _own(t):
 
 
 def _d_applyH1(AC, FL, FR, M):
+    cplx = _operands(AC, FL, FR, M)
     torch, _ = _dev()
     Dl, d, Dr = _jshape(AC)
     a, _, b, _ = _jshape(M)
     out = torch.empty_like(AC)
-    _lib.check(_lib.lib().ttn_tdvp_apply_h1(_cplx(AC), 1, Dl, d, Dr, a, b, _p(FL), _p(AC), _p(M), _p(FR), _p(out), 1))
+    _lib.check(_lib.lib().ttn_tdvp_apply_h1(cplx, 1, Dl, d, Dr, a, b, _p(FL), _p(AC), _p(M), _p(FR), _p(out), 1))
     return out
 
 
 def _d_applyH0(Cm, FL, FR):
+    cplx = _operands(Cm, FL, FR)
     torch, _ = _dev()
     Dl, Dr = _jshape(Cm)
     a = _jshape(FL)[1]
     out = torch.empty_like(Cm)
-    _lib.check(_lib.lib().ttn_tdvp_apply_h0(_cplx(Cm), 1, Dl, Dr, a, _p(FL), _p(Cm), _p(FR), _p(out)))
+    _lib.check(_lib.lib().ttn_tdvp_apply_h0(cplx, 1, Dl, Dr, a, _p(FL), _p(Cm), _p(FR), _p(out)))
     return out
 
 
 def _d_left_env(A, M, FL):
+    cplx = _operands(A, M, FL)
     torch, _ = _dev()
     Dl, d, Dr = _jshape(A)
     a_in, _, a_out, _ = _jshape(M)
     out = torch.empty((Dr, a_out, Dr), dtype=A.dtype, device=A.device)
-    _lib.check(_lib.lib().ttn_tdvp_update_left_env(_cplx(A), 1, Dl, d, Dr, a_in, a_out, _p(A), _p(M), _p(FL), _p(out), 1))
+    _lib.check(_lib.lib().ttn_tdvp_update_left_env(cplx, 1, Dl, d, Dr, a_in, a_out, _p(A), _p(M), _p(FL), _p(out), 1))
     return out
 
 
 def _d_right_env(A, M, FR):
+    cplx = _operands(A, M, FR)
     torch, _ = _dev()
     Dl, d, Dr = _jshape(A)
     a_out, _, a_in, _ = _jshape(M)
     out = torch.empty((Dl, a_out, Dl), dtype=A.dtype, device=A.device)
-    _lib.check(_lib.lib().ttn_tdvp_update_right_env(_cplx(A), 1, Dl, d, Dr, a_out, a_in, _p(A), _p(M), _p(FR), _p(out), 1))
+    _lib.check(_lib.lib().ttn_tdvp_update_right_env(cplx, 1, Dl, d, Dr, a_out, a_in, _p(A), _p(M), _p(FR), _p(out), 1))
     return out
 
 
 def _d_applyH2(AAC, FL, FR, M1, M2):
+    cplx = _operands(AAC, FL, FR, M1, M2)
     torch, _ = _dev()
     Dl, d1, d2, Dr = _jshape(AAC)
     a, _, b, _ = _jshape(M1)
     c = _jshape(M2)[2]
     out = torch.empty_like(AAC)
-    _lib.check(_lib.lib().ttn_tdvp_apply_h2(_cplx(AAC), 1, Dl, d1, d2, Dr, a, b, c, _p(FL), _p(AAC), _p(M1), _p(M2), _p(FR), _p(out), 1))
+    _lib.check(_lib.lib().ttn_tdvp_apply_h2(cplx, 1, Dl, d1, d2, Dr, a, b, c, _p(FL), _p(AAC), _p(M1), _p(M2), _p(FR), _p(out), 1))
     return out
 
 
@@ -242,20 +263,23 @@ def _qr_j(Mt):
     """Thin QR of a Julia matrix (m x n, column-major) held as the contiguous torch tensor Mt of shape (n, m): returns (Qt, Rt), the
     column-major Q (m x r) and R (r x n) as torch tensors of shapes (r, m) and (n, r) — csrc/ttn_densefact_kernels.h (Householder,
     LAPACK's conventions), real or complex."""
+    cplx = _operands(Mt)
     torch, _ = _dev()
     n, m = Mt.shape
     r = min(m, n)
     W = _own(Mt).clone()
     Qt = torch.empty((r, m), dtype=Mt.dtype, device=Mt.device)
     Rt = torch.empty((n, r), dtype=Mt.dtype, device=Mt.device)
-    _lib.check(_lib.lib().ttn_dense_qr(_cplx(W), m, n, _p(W), _p(Qt), _p(Rt)))
+    _lib.check(_lib.lib().ttn_dense_qr(cplx, m, n, _p(W), _p(Qt), _p(Rt)))
     return Qt, Rt
 
 
 def _svd_j(Mt):
     """Thin SVD X = U diag(s) Vt of a Julia matrix X (m x n) held as the torch tensor Mt of shape (n, m): returns (Ut, s, Vtt) with
     U (m x k) as a tensor of shape (k, m), Vt (k x n) as a tensor of shape (n, k), k = min(m, n), s on the HOST (descending) —
-    one-sided Jacobi (csrc/ttn_densefact_kernels.h), on the matrix or on its conjugate transpose, whichever has fewer columns."""
+    one-sided Jacobi (csrc/ttn_densefact_kernels.h), on the matrix or on its conjugate transpose, whichever has fewer columns.  U and
+    Vt are orthonormal also where s has zeros (LAPACK's contract)."""
+    cplx = _operands(Mt)
     torch, _ = _dev()
     n, m = Mt.shape
     real_dt = torch.float64
@@ -264,13 +288,13 @@ def _svd_j(Mt):
         Ut = torch.empty((n, m), dtype=Mt.dtype, device=Mt.device)
         Vtt = torch.empty((n, n), dtype=Mt.dtype, device=Mt.device)
         sd = torch.empty((n,), dtype=real_dt, device=Mt.device)
-        _lib.check(_lib.lib().ttn_dense_svd(_cplx(W), m, n, _p(W), _p(Ut), _p(sd), _p(Vtt)))
+        _lib.check(_lib.lib().ttn_dense_svd(cplx, m, n, _p(W), _p(Ut), _p(sd), _p(Vtt)))
         return Ut, sd, Vtt
     W = _own(Mt.transpose(0, 1).conj()).clone()                   # X^H (n x m) as a tensor of shape (m, n)
     U2 = torch.empty((m, n), dtype=Mt.dtype, device=Mt.device)      # U' (n x m)
     V2 = torch.empty((m, m), dtype=Mt.dtype, device=Mt.device)      # V'h (m x m)
     sd = torch.empty((m,), dtype=real_dt, device=Mt.device)
-    _lib.check(_lib.lib().ttn_dense_svd(_cplx(W), n, m, _p(W), _p(U2), _p(sd), _p(V2)))
+    _lib.check(_lib.lib().ttn_dense_svd(cplx, n, m, _p(W), _p(U2), _p(sd), _p(V2)))
     return _own(V2.transpose(0, 1).conj()), sd, _own(U2.transpose(0, 1).conj())      # U = V'h^H, Vt = U'^H
 
 
@@ -351,12 +375,32 @@ def _svd_rank(s, max_bond, truncerr):
     return min(r, int(max_bond))
 
 
+def _sweep_is_complex(dt, psi, H):
+    """the dtype of a sweep's state (see the head of this section): complex when ψ or H is, or when -i dt is not real"""
+    return (isinstance(_real_or_complex_t(-1j * complex(dt)), complex) or any(np.iscomplexobj(c) for c in psi.ttv_vec)
+            or any(np.iscomplexobj(c) for c in H.tto_vec))
+
+
+def _real_parts(cores, what):
+    """A complex result stored into a real array: the real parts when every imaginary part is at most 1e-12 of the array's largest
+    entry (or of 1), else Julia's InexactError of that store (tdvp.jl:89, :148, :256, :297) as TTNError."""
+    out = []
+    for c in cores:
+        c = np.asarray(c)
+        if np.iscomplexobj(c):
+            if float(np.max(np.abs(np.imag(c)), initial=0.0)) > 1e-12 * max(1.0, float(np.max(np.abs(c), initial=0.0))):
+                raise _lib.TTNError(f"InexactError: {what} is real but the result has an imaginary part (the reference's store into "
+                                    "the real arrays of ψ fails the same way); pass a complex ψ or H")
+            c = np.real(c)
+        out.append(c)
+    return out
+
+
 class _State:
     """One train on the device: sites (l, s, r), operator cores (a, s, b, s'), environments F[0 .. N+1]."""
 
-    def __init__(self, psi, H, dt_is_complex):
+    def __init__(self, psi, H, cplx):
         torch, _ = _dev()
-        cplx = dt_is_complex or any(np.iscomplexobj(c) for c in psi.ttv_vec) or any(np.iscomplexobj(c) for c in H.tto_vec)
         self.dt = np.complex128 if cplx else np.float64
         self.N = psi.N
         self.dims = tuple(psi.ttv_dims)
@@ -446,15 +490,12 @@ def _sweep2(S: _State, dt, max_bond=2 ** 62, truncerr=0.0, **kw):
 
 
 def _state_to_host(S: _State, psi, force_real=False):
-    """sites back to (s, l, r), ranks from the arrays, ttv_ot zeroed  (_sync_ranks_from_lsr!, tdvp.jl:8-18, :147-151)"""
-    cores = []
-    for k in range(S.N):
-        c = np.transpose(_down(S.A[k]), (1, 0, 2))
-        if force_real:
-            assert float(np.max(np.abs(np.imag(c)))) <= 1e-12 * max(1.0, float(np.max(np.abs(c)))), "a real train picked up an imaginary part"
-            c = np.real(c)
-        cores.append(np.asfortranarray(c))
-    psi.ttv_vec = cores
+    """sites back to (s, l, r), ranks from the arrays, ttv_ot zeroed  (_sync_ranks_from_lsr!, tdvp.jl:8-18, :147-151); with
+    force_real, the real parts or TTNError (ψ untouched then)"""
+    cores = [np.transpose(_down(S.A[k]), (1, 0, 2)) for k in range(S.N)]
+    if force_real:
+        cores = _real_parts(cores, "ψ")
+    psi.ttv_vec = [np.asfortranarray(c) for c in cores]
     psi.ttv_rks = [int(_jshape(S.A[k])[0]) for k in range(S.N)] + [int(_jshape(S.A[S.N - 1])[2])]
     psi.ttv_ot = [0] * S.N
     return psi
@@ -464,30 +505,34 @@ def _envs_in(S: _State, F):
     torch, _ = _dev()
     if F is None:
         S.build_envs()
-    else:
-        S.F = [f.to(S.A[0].dtype) if torch.is_tensor(f) else _up(f, S.dt) for f in F]         # F[i] = Tc.(F[i])  (:63-66)
+        return
+    F = [f if torch.is_tensor(f) else _up(f, np.result_type(np.asarray(f).dtype, np.float64)) for f in F]
+    if S.dt == np.float64 and any(f.is_complex() for f in F):                             # Float64.(F[i]): InexactError unless real
+        F = [_up(f, np.float64) for f in _real_parts([_down(f) for f in F], "the state")]
+    S.F = [_own(f.to(S.A[0].dtype)) for f in F]                                                # F[i] = Tc.(F[i])  (:63-66)
 
 
 def tdvp1sweep_(dt, psi, H, F=None, **kw):
-    """tdvp1sweep!(dt, ψ, H, F = nothing; kwargs...) (tdvp.jl:45-152) on the device; mutates ψ (a host TTvector, real or complex cores)
+    """tdvp1sweep!(dt, ψ, H, F = nothing; kwargs...) (tdvp.jl:45-152) on the device; mutates ψ (a host TTvector, real or complex cores;
+    a real ψ stays real, or the call raises TTNError and leaves it as it was: see the dtype note above)
     and returns (ψ, F) with F the list of N + 2 environments as DEVICE arrays (pass it back in to carry them; `envs_to_host` reads
     them in the reference's index order)."""
     torch, stream = _dev()
     with torch.cuda.stream(stream):
-        S = _State(psi, H, isinstance(dt, complex))
+        S = _State(psi, H, _sweep_is_complex(dt, psi, H))
         _envs_in(S, F)
         _sweep1(S, dt, **kw)
-        return _state_to_host(S, psi), S.F
+        return _state_to_host(S, psi, force_real=not any(np.iscomplexobj(c) for c in psi.ttv_vec)), S.F
 
 
 def tdvp2sweep_(dt, psi, H, F=None, max_bond=2 ** 62, truncerr=0.0, **kw):
     """tdvp2sweep!(dt, ψ, H, F = nothing; max_bond, truncerr, kwargs...) (tdvp.jl:210-301) on the device."""
     torch, stream = _dev()
     with torch.cuda.stream(stream):
-        S = _State(psi, H, isinstance(dt, complex))
+        S = _State(psi, H, _sweep_is_complex(dt, psi, H))
         _envs_in(S, F)
         _sweep2(S, dt, max_bond=max_bond, truncerr=truncerr, **kw)
-        return _state_to_host(S, psi), S.F
+        return _state_to_host(S, psi, force_real=not any(np.iscomplexobj(c) for c in psi.ttv_vec)), S.F
 
 
 def envs_to_host(F):

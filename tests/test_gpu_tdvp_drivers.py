@@ -61,7 +61,7 @@ def test_tdvp1sweep_vs_oracle(T, d, r, dt):
 def test_tdvp2sweep_vs_oracle(T, d, r, dt, mb):
     H = O.tto_scale(0.3, O.Delta(d))
     psi = _rand_complex_tt(d, r, 200 + d)
-    # (truncerr 1e-8: a cut at 1e-12 of the norm sits in the rounding noise of the singular values, where LAPACK and hipSOLVER may
+    # (truncerr 1e-8: a cut at 1e-12 of the norm sits in the rounding noise of the singular values, where LAPACK and ttn_dense_svd may
     #  keep different ranks; the discarded weight bounds the distance of the two results)
     ref, _ = O.tdvp2sweep_(dt, O.copy_tt(psi), O._tdvp_complex_op(H), None, max_bond=mb, truncerr=1e-8)
     got, F = T.tdvp.tdvp2sweep_(dt, to_product(O.copy_tt(psi)), to_product(O._tdvp_complex_op(H)), None, max_bond=mb, truncerr=1e-8)

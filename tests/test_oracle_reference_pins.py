@@ -8,6 +8,7 @@ import math
 
 import numpy as np
 import pytest
+import scipy.linalg as sla
 
 from oracle import tt_oracle as O
 
@@ -574,6 +575,48 @@ def test_tdvp1sweep_zero_hamiltonian_is_the_identity():
     psi2, F = O.tdvp1sweep_(complex(0.1), O.copy_tt(psi), _zero_id(d, True), None)
     assert _tt_rel(psi2, psi) < 1e-12
     assert len(F) == psi.N + 2
+
+
+def test_tdvp1sweep_real_state_zero_mpo_stays_real():
+    """test/test_tdvp.jl:132-145: tdvp1sweep!(0.05, ψ, 0·id, nothing) on a REAL ψ.  Real dt makes exp(-i dt H) complex, so the sweep
+    computes in ComplexF64; the reference stores the result back into ψ's Float64 arrays (tdvp.jl:89, :148), which succeeds because
+    H = 0 leaves every imaginary part at zero.  The same for the two-site sweep (:256, :297)."""
+    d = 4
+    psi0 = O.orthogonalize(O.qtt_sin(d, lam=math.pi))
+    psi, F = O.tdvp1sweep_(0.05, O.copy_tt(psi0), _zero_id(d, False), None)
+    assert psi.ttv_dims == psi0.ttv_dims and len(F) == d + 2
+    assert all(not np.iscomplexobj(c) for c in psi.ttv_vec)
+    assert np.isfinite(O.norm(psi)) and _tt_rel(psi, psi0) < 1e-6
+    psi2, F2 = O.tdvp2sweep_(0.05, O.copy_tt(psi0), _zero_id(d, False), None)
+    assert all(not np.iscomplexobj(c) for c in psi2.ttv_vec) and _tt_rel(psi2, psi0) < 1e-10
+    # carried environments of that sweep: complex arrays without imaginary parts, accepted by a real state (F[i] = Tc.(F[i]))
+    psi3, _ = O.tdvp1sweep_(0.0, psi, _zero_id(d, False), F)
+    assert all(not np.iscomplexobj(c) for c in psi3.ttv_vec) and _tt_rel(psi3, psi0) < 1e-6
+
+
+@pytest.mark.parametrize("sweep", ["tdvp1sweep_", "tdvp2sweep_"])
+def test_tdvp_sweep_real_state_raises_on_a_complex_result(sweep):
+    """A real ψ under a real H != 0 and a real dt: the result is complex and the reference's store into ψ's real arrays is an
+    InexactError.  The oracle raises TTNError and leaves ψ as it was; in imaginary time (dt = 0.02im: exp(0.02 H) is real) ψ stays real."""
+    d = 5
+    run = getattr(O, sweep)
+    H = O.tto_scale(0.3, O.Delta(d))
+    psi0 = O.orthogonalize(O.rand_tt((2,) * d, 3, np.random.default_rng(11)))
+    for dt in (0.05, 0.05 + 0.02j):
+        psi = O.copy_tt(psi0)
+        with pytest.raises(O.TTNError, match="InexactError"):
+            run(dt, psi, H, None)
+        assert psi.ttv_rks == psi0.ttv_rks and all(a.dtype == np.float64 and np.array_equal(a, b) for a, b in zip(psi.ttv_vec, psi0.ttv_vec))
+    psi, _ = run(0.02j, O.copy_tt(psi0), H, None)
+    assert all(not np.iscomplexobj(c) for c in psi.ttv_vec)
+    Hd = O.tto_to_tensor(H).reshape(2 ** d, 2 ** d, order="F")
+    v0 = O.ttv_to_tensor(psi0).reshape(-1, order="F")
+    exact = sla.expm(0.02 * Hd) @ v0                                        # exp(-i (0.02 i) H) ψ0
+    got = O.ttv_to_tensor(psi).reshape(-1, order="F")
+    if sweep == "tdvp2sweep_":                                              # (ranks saturate: the two-site sweep is exact)
+        assert np.linalg.norm(got - exact) / np.linalg.norm(exact) < 1e-10
+    else:
+        assert np.linalg.norm(got - exact) / np.linalg.norm(exact) < 1e-2
 
 
 def test_tdvp_basic_behaviour():
