@@ -99,7 +99,9 @@ int ttn_compress(ttn_tt_t psi, int64_t max_bond, double truncerr, int64_t sweeps
 int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps);
 /* One query for a whole chain (synchronises once): the most severe failure code recorded on ANY live handle (left in place
  * there: ttn_compress_status of that handle still reports and clears it) or on a handle that was FREED before anybody queried it
- * (ttn_tt_free folds an unread code into a library-level word, cleared here).  A device-resident chain that creates and frees
+ * (ttn_tt_free folds an unread code into a library-level word, cleared here).  Most severe, here and wherever codes of several
+ * trains meet: Lanczos exhaustion, then a non-finite local eigenpair, a singular local system, ranks that differ from the start
+ * handle, a rank that outgrew its slot, a Jacobi sweep limit.  A device-resident chain that creates and frees
  * temporaries (RK4 stages, Krylov vectors) needs this once per time step / iteration instead of one query per compress. */
 int ttn_status_all(void);
 
@@ -260,7 +262,8 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
 /* out[b] = dot(a_b, b_b)      src/tt_operations.jl:239-250 ; out is HOST memory, length batch (synchronises) */
 int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out);
 /* HIP-event time of the KERNEL of the last ttn_dot / ttn_norm / ttn_orthogonalize call alone (ttn_dot itself goes on to copy the
- * results to the host and synchronises, which an event pair around the call would include) — what bench.py --op reports */
+ * results to the host and synchronises, which an event pair around the call would include) — what bench.py --op reports.  Its
+ * events are its own: such a call inside a ttn_timer_begin / ttn_timer_end region does not move the timer's start. */
 int ttn_last_launch_ms(float* ms);
 /* out[b] = norm(a_b) = sqrt(max(dot(a,a),0))   src/tt_operations.jl:465-470 */
 int ttn_norm(ttn_tt_t a, double* out);
@@ -291,6 +294,7 @@ int ttn_sv_capture(ttn_tt_t h, int enable);
 int ttn_sv_get(ttn_tt_t h, int64_t b, int64_t step, double* out, int64_t cap, int64_t* n);
 
 /* ---- timing on the library stream (HIP events) ------------------------------------------------- */
+/* begin / end bracket everything enqueued between them (events of their own, see ttn_last_launch_ms) */
 int ttn_timer_begin(void);
 int ttn_timer_end(float* ms);   /* synchronises */
 /* event slots (0..4095) recorded on the library stream without synchronising; elapsed() synchronises */
@@ -310,9 +314,10 @@ int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, doub
  * N x N, column-major, symmetric (both triangles); lam[k] = the k smallest eigenvalues ascending, Y[N*k] = their orthonormal vectors as
  * columns (no sign normalisation).  1 <= N <= 2048, 1 <= k <= min(N, 16); TTN_ERR_ARG otherwise, before anything is launched. */
 int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, double* Y);
-/* diagnostics of the last ttn_orthogonalize that took the multi-launch form (csrc/ttn_ortho_ramp.h, ttn_ortho512.h): the four state
+/* diagnostics of the last ttn_orthogonalize when it took the multi-launch form (csrc/ttn_ortho_ramp.h, ttn_ortho512.h): the four state
  * words of train b = {next site of the right-to-left sweep, buffer of the last right factor, buffer of the last left factor,
- * 1 if k_ortho512 finished the train (0: the 1024-thread kernel took it over from `next site`)}. */
+ * 1 if k_ortho512 finished the train (0: the 1024-thread kernel took it over from `next site`)}.  Read from the library's workspace:
+ * meaningful until the next call that uses it; TTN_ERR_ARG if b is outside the batch of that orthogonalize. */
 int ttn_debug_ortho_state(int64_t b, int64_t* out4);
 
 /* ---- stateless host-pointer entry points: the literal drop-ins for one train --------------------

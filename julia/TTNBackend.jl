@@ -222,8 +222,9 @@ end
 #         A, b, x0, x, tol, length(sweep_schedule), sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
 # (the keyword form, dmrg.jl:392-396: local systems above itslv_thresh unknowns — or all of them with it_solver — by matrix-free CG).
 #
-# Status is sticky per handle: ttn_compress_status(h, C_NULL) returns the first error any compress / sweep / swap / solver call
-# recorded on h since the last query (capacity -5, Jacobi sweep limit -9, singular local system -10) and clears it.
+# Status is sticky per handle: ttn_compress_status(h, C_NULL) returns the most severe error any compress / sweep / swap / solver call
+# recorded on h since the last query and clears it.  Most severe first: Lanczos exhaustion -9, a non-finite local eigenpair -9,
+# singular local system -10, ranks that differ from the start handle -1, capacity -5, Jacobi sweep limit -9.
 # ccall((:ttn_status_all, LIB), Cint, ()) answers for every live handle and for handles freed with an unread code, in one synchronisation.
 
 # ---- Two-site eigensolvers (src/solvers/dmrg.jl:501-578, src/solvers/mals.jl:335-425) --------------------------------------------

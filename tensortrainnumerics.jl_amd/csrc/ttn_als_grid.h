@@ -48,6 +48,7 @@ __global__ void __launch_bounds__(ALS_ASM_ROWS) k_als_assemble(AlsAssembleArgs Q
 }
 
 // ---- the panel k0 .. k0 + w - 1: the column loop of wg_lu_solve, one workgroup.  flag[0] = 1 on an exactly zero pivot column. ----
+#define LU_PANEL_LDS_BYTES (sizeof(double) * (128 * 128 + 64 + 64))     // dynamic LDS: the panel (up to 128 x 128), then its reduction words
 __global__ void __launch_bounds__(TTN_WG) k_lu_panel(double* K_, int N, int k0, int w, int* piv_, int* flag) {
     extern __shared__ double lds[];
     typedef __attribute__((address_space(1))) int gmem_i32;

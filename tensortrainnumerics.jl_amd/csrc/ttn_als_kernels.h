@@ -399,7 +399,7 @@ __global__ void __launch_bounds__(TTN_WG) k_als_linsolve(AlsArgs P) {
         const long long* xr = P.x.rks + (long long)b * (d + 1);
         bool bad = false;
         for (int k = 0; k <= d; ++k) bad |= (xr[k] != P.rfix[k]);
-        if (bad) { if (tid == 0) ttn_set_status(&P.status[b], 4); return; }
+        if (bad) { if (tid == 0) ttn_set_status(&P.status[b], TTN_ST_RANKS_DIFFER); return; }
     }
     const long long* br_ = P.b.rks + (long long)b * (d + 1);
     AlsEnv E;
@@ -563,7 +563,7 @@ __global__ void __launch_bounds__(TTN_WG) k_als_linsolve(AlsArgs P) {
             bwd_move(i);
         }
     }
-    if (!ok && tid == 0) ttn_set_status(&P.status[b], 3);
+    if (!ok && tid == 0) ttn_set_status(&P.status[b], TTN_ST_SINGULAR);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -743,7 +743,7 @@ __global__ void __launch_bounds__(TTN_WG) k_mals_linsolve(MalsArgs Q) {
         else { const int u = t % per; dir = u >= d - 2; i = dir ? 2 * (d - 2) - u : u; rmax = Q.rmax_sweep[t / per]; }
         i = uni32(i); dir = uni32(dir); rmax = uni32(rmax);
         int na, nb;
-        if (!ksolve(i, na, nb, prev_dir == 1)) { status = 3; break; }
+        if (!ksolve(i, na, nb, prev_dir == 1)) { status = TTN_ST_SINGULAR; break; }
         prev_dir = dir;
         const int n2 = uni32(P.x.dims[i + 1]);
         double* xi = XC(i);
@@ -753,7 +753,7 @@ __global__ void __launch_bounds__(TTN_WG) k_mals_linsolve(MalsArgs Q) {
             r = wg_hsvd_step(Q.C, b, S, mkview(Pb, plain(1), plain(na)), na, nb, M2, 2, n2, 0, xi, xn, Q.tol, (int)P.x.cap[i + 1], lds, rule, rmax);
         else                 // left_core_move_mals / left_core_move!: x_{i+1} <- V', x_i <- U S  (the step on the transposed view)
             r = wg_hsvd_step(Q.C, b, S, mkview(Pb, plain(na), plain(1)), nb, na, M2, 1, n2, 0, xn, xi, Q.tol, (int)P.x.cap[i + 1], lds, rule, rmax);
-        if (r < 0) { status = 2; break; }
+        if (r < 0) { status = TTN_ST_RANK_OVERFLOW; break; }
         if (tid == 0) xr[i + 1] = r;
         __syncthreads();
         if (dir == 0) als_update_G(E, i);

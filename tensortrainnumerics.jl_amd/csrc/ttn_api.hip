@@ -38,20 +38,18 @@ int ttn_wg512_selftest_gemm(int m, int n, int k, double* A, double* B, double* C
 // global state
 // ------------------------------------------------------------------------------------------------
 namespace {
-int* g_next_train = nullptr;  // train counter of the persistent k_compress grid
-int* g_pending_status = nullptr;   // failure codes of handles that were FREED before anybody queried them (ttn_status_all)
 std::set<struct ttn_tt_s*> g_live;  // every live ttn_tt handle (ttn_status_all walks them)
 std::recursive_mutex g_mu;
 bool g_init = false;
 int g_device = -1;
 hipStream_t g_stream = nullptr;
-hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;
+hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;                 // ttn_timer_begin / ttn_timer_end
+hipEvent_t g_launch_ev0 = nullptr, g_launch_ev1 = nullptr;   // the kernels of the last ttn_dot / ttn_orthogonalize (ttn_last_launch_ms)
+bool g_have_launch_ms = false;
+size_t g_ortho_state_off = 0;     // byte offset in g_scratch of the state words of the last ttn_orthogonalize (ttn_debug_ortho_state)
+int g_ortho_state_batch = 0;      // its batch; 0: none
 std::string g_err = "";
-void* g_scratch = nullptr;
-size_t g_scratch_bytes = 0;
-double* g_dout = nullptr;     // per-train double outputs (dot)
 std::vector<hipEvent_t> g_slots;   // ttn_event_record slots
-int g_dout_cap = 0;
 
 int fail(int code, const char* what) {
     g_err = what;
@@ -69,27 +67,32 @@ int hipfail(hipError_t e, const char* where) {
 #define NEED_INIT() \
     if (!g_init) return fail(TTN_ERR_NOT_INIT, "ttn_init has not been called")
 
-int ensure_scratch(size_t bytes) {
-    if (bytes <= g_scratch_bytes) return TTN_OK;
-    if (g_scratch) {
-        HIPCHK(hipStreamSynchronize(g_stream));
-        HIPCHK(hipFree(g_scratch));
-        g_scratch = nullptr;
-        g_scratch_bytes = 0;
+// Device memory the library keeps between calls.  ensure() grows it to exactly `n` bytes (after the stream has drained: a launch
+// in flight may still read the old allocation) and keeps it when it is already large enough; ttn_finalize releases every one.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t n) {
+        if (n <= bytes) return TTN_OK;
+        if (p) { HIPCHK(hipStreamSynchronize(g_stream)); HIPCHK(hipFree(p)); p = nullptr; bytes = 0; }
+        HIPCHK(hipMalloc(&p, n));
+        bytes = n;
+        return TTN_OK;
     }
-    HIPCHK(hipMalloc(&g_scratch, bytes));
-    g_scratch_bytes = bytes;
-    return TTN_OK;
-}
-bool g_have_launch_ms = false;     // g_ev0 / g_ev1 bracket the last ttn_dot / ttn_orthogonalize kernel (ttn_last_launch_ms)
-int ensure_batch_bufs(int batch) {
-    if (batch > g_dout_cap) {
-        if (g_dout) { HIPCHK(hipStreamSynchronize(g_stream)); HIPCHK(hipFree(g_dout)); }
-        HIPCHK(hipMalloc((void**)&g_dout, sizeof(double) * batch));
-        g_dout_cap = batch;
-    }
-    return TTN_OK;
-}
+    void release() { if (p) hipFree(p); p = nullptr; bytes = 0; }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+DevBuf g_scratch;          // per-call workspace of every launch
+DevBuf g_dout;             // [batch] doubles: dot results, the factors of ttn_scale_batch
+DevBuf g_next_train;       // train counter of the persistent k_compress grid
+DevBuf g_pending_status;   // one bit per failure code of handles FREED before anybody queried them (ttn_status_all)
+DevBuf g_which;            // [batch] scaled core per train when the gauge flags differ (scaled_core)
+DevBuf g_lu_flag;          // singular-pivot word of the grid form of als_linsolve
+DevBuf g_cg_iters;         // [batch] CG iterations of the last two-site linear solve
+DevBuf g_hist_E, g_hist_r; // [batch][hist_len] energy / rank history of the last two-site eigensolve
+DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-site eigensolve
+DevBuf* const g_bufs[] = {&g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
+                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -136,11 +139,12 @@ struct ttn_tto_s {
 
 static bool same_dims(const std::vector<int64_t>& a, const std::vector<int64_t>& b) { return a == b; }
 
-// ttn_tt_free: the largest failure code still recorded on the dying handle moves to the library-level word
-__global__ void k_fold_status(const int* status, int batch, int* pending) {
-    int m = 0;
-    for (int b = threadIdx.x; b < batch; b += 64) m = max(m, status[b]);
-    if (m) atomicMax(pending, m);
+// ttn_tt_free / ttn_status_all: bit `code` of the library-level word for every failure code recorded on the handle (which one is
+// reported is decided on the host, by the order of status_table)
+__global__ void k_fold_status(const int* status, int batch, unsigned* pending) {
+    unsigned m = 0;
+    for (int b = threadIdx.x; b < batch; b += 64) if (status[b]) m |= 1u << status[b];
+    if (m) atomicOr(pending, m);
 }
 
 extern "C" {
@@ -163,38 +167,30 @@ int ttn_init(int device) {
     if (g_init) return fail(TTN_ERR_ARG, "ttn_init: already bound to another device (call ttn_finalize first)");
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&g_ev0));
-    HIPCHK(hipEventCreate(&g_ev1));
-    // the compress / orthogonalize kernels use more than the default 64 KiB of dynamic LDS
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_compress), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(COMPRESS_LDS_BYTES)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_selftest_eig128), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)COMPRESS_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mals_linsolve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)COMPRESS_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_als_linsolve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)COMPRESS_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_two_site_eig), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)COMPRESS_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ttv_decomp), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)COMPRESS_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_swap_chain), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)COMPRESS_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_orthogonalize), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(ORTHO_LDS_BYTES)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ortho512), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(O5_LDS_BYTES(TTN_MAX_D * 8))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dot_fused), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(DOT_LDS_BYTES(DOT_MAX_D))));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_selftest_gemm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(double) * GEMM_LDS_TOTAL)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tdvp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TDVP_LDS_BYTES));
+    for (hipEvent_t* e : {&g_ev0, &g_ev1, &g_launch_ev0, &g_launch_ev1}) HIPCHK(hipEventCreate(e));
+    // the kernels that use more than the default 64 KiB of dynamic LDS
+    const struct { const void* fn; size_t lds; } lds_limits[] = {
+        {(const void*)k_compress, COMPRESS_LDS_BYTES},
+        {(const void*)k_selftest_eig128, COMPRESS_LDS_BYTES},
+        {(const void*)k_mals_linsolve, COMPRESS_LDS_BYTES},
+        {(const void*)k_als_linsolve, COMPRESS_LDS_BYTES},
+        {(const void*)k_two_site_eig, COMPRESS_LDS_BYTES},
+        {(const void*)k_ttv_decomp, COMPRESS_LDS_BYTES},
+        {(const void*)k_swap_chain, COMPRESS_LDS_BYTES},
+        {(const void*)k_orthogonalize, ORTHO_LDS_BYTES},
+        {(const void*)k_ortho512, O5_LDS_BYTES(TTN_MAX_D * 8)},
+        {(const void*)k_dot_fused, DOT_LDS_BYTES(DOT_MAX_D)},
+        {(const void*)k_selftest_gemm, sizeof(double) * GEMM_LDS_TOTAL},
+        {(const void*)k_tdvp, TDVP_LDS_BYTES},
+        {(const void*)k_lu_panel, LU_PANEL_LDS_BYTES},
+        {(const void*)k_lu_trail, sizeof(double) * GEMM_LDS_TOTAL},
+    };
+    for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
-    static_assert(sizeof(CompressArgs) > 0, "");
     if (ttn_wg512_compress_args_bytes() != sizeof(CompressArgs)) return fail(TTN_ERR_ARG, "ttn_init: the two kernel builds disagree on CompressArgs");
-    HIPCHK(hipMalloc((void**)&g_next_train, sizeof(int)));
-    HIPCHK(hipMalloc((void**)&g_pending_status, sizeof(int)));
-    HIPCHK(hipMemset(g_pending_status, 0, sizeof(int)));
+    { int rc = g_next_train.ensure(sizeof(int)); if (rc) return rc; }
+    { int rc = g_pending_status.ensure(sizeof(unsigned)); if (rc) return rc; }
+    HIPCHK(hipMemset(g_pending_status.p, 0, sizeof(unsigned)));
     g_device = device;
     g_init = true;
     return TTN_OK;
@@ -204,13 +200,10 @@ int ttn_finalize(void) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!g_init) return TTN_OK;
     hipStreamSynchronize(g_stream);
-    if (g_scratch) hipFree(g_scratch);
-    if (g_dout) hipFree(g_dout);
-    if (g_next_train) hipFree(g_next_train);
-    if (g_pending_status) hipFree(g_pending_status);
-    g_next_train = nullptr; g_pending_status = nullptr;
-    g_scratch = nullptr; g_scratch_bytes = 0; g_dout = nullptr; g_dout_cap = 0;
-    hipEventDestroy(g_ev0); hipEventDestroy(g_ev1);
+    for (DevBuf* b : g_bufs) b->release();
+    for (hipEvent_t e : {g_ev0, g_ev1, g_launch_ev0, g_launch_ev1}) hipEventDestroy(e);
+    g_have_launch_ms = false;
+    g_ortho_state_batch = 0;
     for (auto e : g_slots) if (e) hipEventDestroy(e);
     g_slots.clear();
     hipStreamDestroy(g_stream);
@@ -338,9 +331,9 @@ int ttn_tt_free(ttn_tt_t h) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!h) return TTN_OK;
     const bool was_live = g_live.erase(h) > 0;
-    if (g_init && was_live && h->d_status && g_pending_status) {
+    if (g_init && was_live && h->d_status) {
         // a failure recorded on this handle that nobody has queried survives the handle (ttn_status_all)
-        hipLaunchKernelGGL(k_fold_status, dim3(1), dim3(64), 0, g_stream, (const int*)h->d_status, h->batch, g_pending_status);
+        hipLaunchKernelGGL(k_fold_status, dim3(1), dim3(64), 0, g_stream, (const int*)h->d_status, h->batch, g_pending_status.as<unsigned>());
     }
     if (g_init) hipStreamSynchronize(g_stream);
     if (h->d_data) hipFree(h->d_data);
@@ -619,10 +612,8 @@ int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
 // The core scalar multiplication scales: the first one with ot == 0, else the first (tt_operations.jl:262).  Uniform over the batch
 // -> `which`; trains with different gauge flags (uploaded one by one, or zeroed by ttn_scale_batch) -> a per-train device table.
 static int scaled_core(ttn_tt_t x, int& which, const int*& which_b) {
-    static int* d_which = nullptr; static int which_cap = 0;
-    static std::vector<int> h_which;                     // must outlive the async upload
     const int d = x->d;
-    h_which.assign(x->batch, 0);
+    std::vector<int> h_which(x->batch, 0);
     bool uniform = true;
     for (int b = 0; b < x->batch; ++b) {
         for (int k = 0; k < d; ++k) if (x->ot[(size_t)b * d + k] == 0) { h_which[b] = k; break; }
@@ -631,14 +622,11 @@ static int scaled_core(ttn_tt_t x, int& which, const int*& which_b) {
     which = h_which[0];
     which_b = nullptr;
     if (uniform) return TTN_OK;
-    if (which_cap < x->batch) {
-        if (d_which) { HIPCHK(hipStreamSynchronize(g_stream)); HIPCHK(hipFree(d_which)); d_which = nullptr; }
-        HIPCHK(hipMalloc((void**)&d_which, sizeof(int) * x->batch));
-        which_cap = x->batch;
-    }
-    HIPCHK(hipMemcpyAsync(d_which, h_which.data(), sizeof(int) * x->batch, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));              // h_which is reused by the next call
-    which_b = d_which;
+    const int rc = g_which.ensure(sizeof(int) * x->batch);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(g_which.p, h_which.data(), sizeof(int) * x->batch, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));              // h_which is a local
+    which_b = g_which.as<int>();
     return TTN_OK;
 }
 
@@ -670,16 +658,16 @@ int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     const int d = x->d;
     for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_scale_batch: destination capacity too small");
-    int rc = ensure_batch_bufs(x->batch);
+    int rc = g_dout.ensure(sizeof(double) * x->batch);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g_dout, a, sizeof(double) * x->batch, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(g_dout.p, a, sizeof(double) * x->batch, hipMemcpyHostToDevice, g_stream));
     int which = 0;
     const int* which_b = nullptr;
     { int rc_ = scaled_core(x, which, which_b); if (rc_) return rc_; }
     long long maxsz = 0;
     for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)x->dims[k] * x->bound[k] * x->bound[k + 1]);
     if (x != y) hipLaunchKernelGGL(k_ranks_copy, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), x->dev());
-    hipLaunchKernelGGL(k_scale_batch, stream_grid((maxsz + 7) / 8, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), (const double*)g_dout, which, which_b);
+    hipLaunchKernelGGL(k_scale_batch, stream_grid((maxsz + 7) / 8, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), g_dout.as<const double>(), which, which_b);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g_stream));      // `a` is caller memory and g_dout is reused by ttn_dot
     y->bound = x->bound;
@@ -753,9 +741,9 @@ static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, in
         if (need[m] > psi->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_compress: a bond rank can grow beyond the handle's capacity (see ttn_compress_rank_bound)");
     if (pmax > 4096 || qmax > 16384) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress: merged matrix larger than 4096 x 16384");
     per_train = 2 * pmax * qmax + QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64 + 6 * 128 * 128;
-    int rc = ensure_scratch(sizeof(double) * (size_t)per_train * compress_slots(psi->batch));
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * compress_slots(psi->batch));
     if (rc) return rc;
-    return ensure_batch_bufs(psi->batch);
+    return g_dout.ensure(sizeof(double) * psi->batch);
 }
 
 static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, double truncerr, int64_t sweeps,
@@ -782,7 +770,7 @@ static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, dou
     P.sweeps = (int)sweeps;
     P.k_single = (int)k_single;
     P.k_first = (int)k_first; P.k_last = (int)k_last;
-    P.scratch = (double*)g_scratch;
+    P.scratch = g_scratch.as<double>();
     P.scratch_stride = per_train;
     P.pmax = (int)pmax; P.qmax = (int)qmax;
     P.sv_out = psi->sv_on ? psi->d_sv : nullptr;
@@ -796,8 +784,8 @@ static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, dou
     else { memset(&P.op, 0, sizeof(P.op)); memset(&P.x, 0, sizeof(P.x)); }
     { const char* e = getenv("TTN_FAST"); P.fast = e ? atoi(e) : 1; }
     if (compress_use_wg512(psi->batch)) {
-        HIPCHK(hipMemsetAsync(g_next_train, 0, sizeof(int), g_stream));
-        P.next_train = g_next_train;
+        HIPCHK(hipMemsetAsync(g_next_train.p, 0, sizeof(int), g_stream));
+        P.next_train = g_next_train.as<int>();
         const int rc512 = ttn_wg512_launch_compress(&P, sizeof(P), compress_slots(psi->batch), g_stream);
         if (rc512) return hipfail((hipError_t)rc512, "k_compress (512-thread build)");
     } else {
@@ -950,7 +938,6 @@ int ttn_stream_handle(void** stream) {
 // the scratch allocation, kind 2 in place on the handle's own slots.
 static int launch_chain(int kind, ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, int n, int nslots, int64_t work_cap, const std::vector<int>& ops,
                         const std::vector<int>& final_slots, double tol, int64_t rmax, int rank_rule) {
-    static std::vector<int> h_tab;                      // must outlive the async upload below
     ttn_tt_t ref = (kind == 1) ? x : z;
     const int batch = ref->batch;
     const long long pmax = (long long)n * work_cap, qmax = pmax;
@@ -960,16 +947,16 @@ static int launch_chain(int kind, ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, int n, int
     const long long srk_stride = 2 * nslots + 2;
     const long long per_train = per_compress + srk_stride + (long long)nslots * slot_doubles;
     const size_t tab_ints = ops.size() + final_slots.size();
-    HIPCHK(hipStreamSynchronize(g_stream));            // h_tab of the previous call is no longer in flight
-    int rc = ensure_scratch(sizeof(double) * (size_t)per_train * batch + sizeof(int) * tab_ints + 64);
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * batch + sizeof(int) * tab_ints + 64);
     if (rc) return rc;
-    rc = ensure_batch_bufs(batch);
+    rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
-    double* base = (double*)g_scratch;
+    double* base = g_scratch.as<double>();
     int* d_tab = (int*)(base + (size_t)per_train * batch);
-    h_tab.assign(ops.begin(), ops.end());
+    std::vector<int> h_tab(ops);
     h_tab.insert(h_tab.end(), final_slots.begin(), final_slots.end());
     HIPCHK(hipMemcpyAsync(d_tab, h_tab.data(), sizeof(int) * tab_ints, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));            // h_tab is a local
     ChainArgs Q;
     memset(&Q, 0, sizeof(Q));
     CompressArgs& P = Q.C;
@@ -1099,11 +1086,11 @@ int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol)
     const long long per_scr = QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64;
     const long long per_train = 3 * total + per_scr;
     const int batch = z->batch;
-    int rc = ensure_scratch(sizeof(double) * ((size_t)per_train * batch + (size_t)total * batch));
+    int rc = g_scratch.ensure(sizeof(double) * ((size_t)per_train * batch + (size_t)total * batch));
     if (rc) return rc;
-    rc = ensure_batch_bufs(batch);
+    rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
-    double* base = (double*)g_scratch;
+    double* base = g_scratch.as<double>();
     double* d_in = base + (size_t)per_train * batch;
     HIPCHK(hipMemcpyAsync(d_in, tensors, sizeof(double) * (size_t)total * batch, hipMemcpyHostToDevice, g_stream));
     HsvdArgs H;
@@ -1140,19 +1127,12 @@ int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol)
 // of k_als_linsolve, one workgroup).  Everything is enqueued on the library stream; one flag word carries a singular pivot column.
 static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std::vector<int64_t>& r, ttn_tto_t A, ttn_tt_t b, ttn_tt_t x, int sweep_count) {
     const int d = x->d, batch = x->batch;
-    static bool attr = false;
-    const size_t panel_lds = sizeof(double) * (128 * 128 + 64 + 64);
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lu_panel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)panel_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lu_trail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * GEMM_LDS_TOTAL)));
-        attr = true;
-    }
     double* scr = P.scratch;
     double* K = scr + P.offK;
     double* Pb = scr + P.offPb;
     int* piv = reinterpret_cast<int*>(scr + P.offPiv);
-    static int* d_flag = nullptr;
-    if (!d_flag) HIPCHK(hipMalloc((void**)&d_flag, sizeof(int)));
+    { const int rc = g_lu_flag.ensure(sizeof(int)); if (rc) return rc; }
+    int* d_flag = g_lu_flag.as<int>();
     const std::vector<int64_t>& R = A->rks;
     auto solve_site = [&](int i) -> int {
         const int n = (int)x->dims[i], rl = (int)r[i], rr = (int)r[i + 1];
@@ -1163,7 +1143,7 @@ static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std
         hipLaunchKernelGGL(k_als_assemble, dim3((N + ALS_ASM_ROWS - 1) / ALS_ASM_ROWS, (N + ALS_ASM_COLS - 1) / ALS_ASM_COLS), dim3(ALS_ASM_ROWS), 0, g_stream, Q);
         for (int k0 = 0; k0 < N; k0 += LU_NB) {
             const int w = std::min(LU_NB, N - k0);
-            hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(TTN_WG), panel_lds, g_stream, K, N, k0, w, piv, d_flag);
+            hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(TTN_WG), LU_PANEL_LDS_BYTES, g_stream, K, N, k0, w, piv, d_flag);
             hipLaunchKernelGGL(k_lu_rows, dim3((N + 1 + 255) / 256), dim3(256), 0, g_stream, K, Pb, N, k0, w, (const int*)piv, (const int*)d_flag);
             const int m = N - k0 - w;
             if (m > 0) {
@@ -1202,8 +1182,8 @@ static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std
         HIPCHK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
         if (h_flag) {                                   // LAPACK's SingularException: recorded on the handle like the one-workgroup form does
-            const int three = 3;
-            HIPCHK(hipMemcpyAsync(x->d_status + tb, &three, sizeof(int), hipMemcpyHostToDevice, g_stream));
+            const int singular = TTN_ST_SINGULAR;
+            HIPCHK(hipMemcpyAsync(x->d_status + tb, &singular, sizeof(int), hipMemcpyHostToDevice, g_stream));
             HIPCHK(hipStreamSynchronize(g_stream));
         }
     }
@@ -1265,17 +1245,16 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
     const long long per_train = cur;
     const int batch = x->batch;
     const int nslots = grid_path ? 1 : batch;          // the grid form works on one train at a time (K alone can be gigabytes)
-    static std::vector<long long> h_off;               // outlives the async upload
-    HIPCHK(hipStreamSynchronize(g_stream));
-    rc = ensure_scratch(sizeof(double) * (size_t)per_train * nslots + sizeof(long long) * (size_t)(5 * d + 1) + 64);
+    rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * nslots + sizeof(long long) * (size_t)(5 * d + 1) + 64);
     if (rc) return rc;
-    rc = ensure_batch_bufs(batch);
+    rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
-    double* base = (double*)g_scratch;
+    double* base = g_scratch.as<double>();
     long long* d_tab = (long long*)(base + (size_t)per_train * nslots);
-    h_off = off;
-    for (int k = 0; k <= d; ++k) h_off.push_back(r[k]);
+    std::vector<long long> h_off(off);
+    h_off.insert(h_off.end(), r.begin(), r.end());
     HIPCHK(hipMemcpyAsync(d_tab, h_off.data(), sizeof(long long) * h_off.size(), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));            // h_off is a local
     P.A = A->dev(); P.b = b->dev(); P.x = x->dev();
     P.sweep_count = (int)sweep_count;
     P.scratch = base; P.scratch_stride = per_train;
@@ -1305,8 +1284,161 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
     return TTN_OK;
 }
 
-// ---- mals_linsolve -----------------------------------------------------------------------------------------------
-// the two-site solvers: mode 0 = mals_linsolve, mode 1 = dmrg_linsolve (N = 2) with `plan` = the rank cap of every full sweep
+// ---- failure codes ------------------------------------------------------------------------------------------------
+// What each per-train code of the dense kernels (TtnStatus, csrc/ttn_common.h) means to a caller.  The first entry whose code any
+// train carries is the one reported.
+const struct { int code, err; const char* msg; } status_table[] = {
+    {TTN_ST_LANCZOS, TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol"},
+    {TTN_ST_NONFINITE, TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)"},
+    {TTN_ST_SINGULAR, TTN_ERR_SINGULAR, "als_linsolve: a local system K is singular"},
+    {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "als_linsolve: a train's ranks differ from the ranks of the start handle"},
+    {TTN_ST_RANK_OVERFLOW, TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)"},
+    {TTN_ST_JACOBI, TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit"},
+};
+
+// `seen`: bit c set for every code c recorded (k_fold_status builds the same word on the device).  `who` prefixes the message.
+static int status_error(unsigned seen, const char* who = nullptr) {
+    for (const auto& s : status_table)
+        if (seen & (1u << s.code)) return fail(s.err, who ? (std::string(who) + ": " + s.msg).c_str() : s.msg);
+    return TTN_OK;
+}
+
+// Failure codes of every dense kernel that wrote `h` since the last call, as bits of one word (synchronises).  The codes are sticky
+// on the device — a kernel only ever stores a non-zero code, so a failure inside a chain of launches survives the launches after
+// it — and are cleared here, on read.
+static int take_status(ttn_tt_t h, unsigned& seen) {
+    std::vector<int> st(h->batch);
+    HIPCHK(hipMemcpyAsync(st.data(), h->d_status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int) * h->batch, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    seen = 0;
+    for (int c : st) if (c) seen |= 1u << c;
+    return TTN_OK;
+}
+
+// ---- the two-site solvers (mals_linsolve / dmrg_linsolve, mals_eigsolve / dmrg_eigsolve) ---------------------------------------
+// The sweep plan of a stage schedule: plan[s] = the rank cap of full sweep s (rmax_schedule null: 1).  The reference's while-loops
+// (dmrg.jl:421-426, :523-528, mals.jl:372-378) only terminate for positive, strictly increasing stage ends.  Messages start with `who`;
+// more than TTN_DMRG_MAX_SWEEPS sweeps fail with `too_many`.
+static int sweep_plan(const char* who, int too_many, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule,
+                      std::vector<int64_t>& plan) {
+    auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
+    if (n_stages < 1 || !sweep_schedule) return bad(TTN_ERR_ARG, "empty schedule");
+    for (int64_t j = 0; j < n_stages; ++j) {
+        if (sweep_schedule[j] < 1 || (j && sweep_schedule[j] <= sweep_schedule[j - 1])) return bad(TTN_ERR_ARG, "sweep_schedule must be positive and strictly increasing");
+        if (rmax_schedule && rmax_schedule[j] < 1) return bad(TTN_ERR_ARG, "bad rmax_schedule");
+    }
+    if (sweep_schedule[n_stages - 1] - 1 > TTN_DMRG_MAX_SWEEPS) return bad(too_many, "more than 32 sweeps in one call");
+    plan.clear();
+    int64_t n = 0, j = 0;
+    for (;;) {
+        ++n;
+        if (n == sweep_schedule[j]) { if (++j >= n_stages) break; }
+        plan.push_back(rmax_schedule ? rmax_schedule[j] : 1);
+    }
+    return TTN_OK;
+}
+
+// Workspace of one train.  Slots per site i: G_i (off[i]) and, for the window (i, i+1), H_i (off[2d + i]); with a right-hand side
+// also its projections Gb_i (off[d + i]) and Hb_i (off[3d + i]).  `cur` is the end of what is laid out so far, in doubles.
+struct TwoSiteLayout {
+    std::vector<long long> off;
+    long long cur = 0, Nmax = 1, mmax = 1, t1 = 1, t2 = 1, Rzmax = 1, pmax = 1, qmax = 1;
+};
+
+// c: capacity ranks of the result, R: operator ranks, rb: bounds of the right-hand side (null: eigensolver, no rhs slots / terms)
+static TwoSiteLayout two_site_slots(const std::vector<int64_t>& dims, const std::vector<int64_t>& c, const std::vector<int64_t>& R,
+                                    const std::vector<int64_t>* rb) {
+    const int d = (int)dims.size();
+    auto mx = [](long long a_, long long b_) { return a_ > b_ ? a_ : b_; };
+    TwoSiteLayout L;
+    L.off.assign(4 * d, 0);
+    long long& cur = L.cur;
+    for (int i = 0; i < d; ++i) {
+        const long long n = dims[i];
+        L.off[i] = cur; cur += n * c[i] * n * c[i] * R[i + 1];
+        if (rb) { L.off[d + i] = cur; cur += n * c[i] * (*rb)[i + 1]; }
+        L.mmax = mx(L.mmax, mx(n * c[i], n * c[i + 1]));
+        L.t1 = mx(L.t1, n * c[i] * c[i + 1] * mx(R[i], R[i + 1]));
+        if (rb) L.t1 = mx(L.t1, mx(c[i + 1] * (*rb)[i + 1], c[i] * (*rb)[i + 1]));
+        L.t2 = mx(L.t2, c[i + 1] * c[i + 1] * R[i + 1]);
+        L.Rzmax = mx(L.Rzmax, R[i + 1]);
+        if (i + 1 < d) {
+            const long long n2 = dims[i + 1];
+            L.off[2 * d + i] = cur; cur += R[i + 1] * n2 * n2 * c[i + 2] * c[i + 2];
+            if (rb) { L.off[3 * d + i] = cur; cur += (*rb)[i + 1] * n2 * c[i + 2]; }
+            L.Nmax = mx(L.Nmax, n * c[i] * n2 * c[i + 2]);
+            L.t1 = mx(L.t1, R[i + 1] * n2 * c[i + 2] * c[i + 1]);
+            if (rb) L.t1 = mx(L.t1, (*rb)[i + 1] * c[i + 1]);
+            L.t2 = mx(L.t2, R[i + 1] * c[i + 1] * c[i + 1]);
+        }
+    }
+    L.pmax = std::min<long long>(L.mmax, 256);
+    L.qmax = L.mmax;
+    return L;
+}
+
+// the blocks of the SVD core moves, after each solver's local-solve blocks
+static void two_site_core_move_blocks(TwoSiteLayout& L, MalsArgs& Q) {
+    long long& cur = L.cur;
+    Q.L.offT1 = cur; cur += L.t1;
+    Q.L.offT2 = cur; cur += L.t2;
+    Q.L.offVb = cur; cur += QR_NB * L.qmax;
+    Q.L.offWb = cur; cur += QR_NB * L.qmax;
+    Q.offM2 = cur; cur += L.Nmax;
+    Q.offXg = cur; cur += L.pmax * L.pmax;
+    Q.offUs = cur; cur += L.pmax * L.pmax;
+    Q.offSig = cur; cur += 4 * L.pmax + 64;
+}
+
+static size_t two_site_bytes(const TwoSiteLayout& L, int batch) {
+    return sizeof(double) * (size_t)L.cur * batch + sizeof(long long) * L.off.size() + 64;
+}
+
+// Scratch for the batch, the slot table uploaded behind it, and the kernel arguments both solvers share.  b is the right-hand side
+// (the eigensolvers pass x); rmax caps the last stage.
+static int two_site_prelude(MalsArgs& Q, const TwoSiteLayout& L, ttn_tto_t A, ttn_tt_t b, ttn_tt_t x, double tol, int64_t rmax, int mode,
+                            const std::vector<int64_t>& plan) {
+    const int batch = x->batch;
+    int rc = g_scratch.ensure(two_site_bytes(L, batch));
+    if (rc) return rc;
+    rc = g_dout.ensure(sizeof(double) * batch);
+    if (rc) return rc;
+    double* base = g_scratch.as<double>();
+    long long* d_tab = (long long*)(base + (size_t)L.cur * batch);
+    HIPCHK(hipMemcpyAsync(d_tab, L.off.data(), sizeof(long long) * L.off.size(), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));            // L.off is the caller's
+    AlsArgs& P = Q.L;
+    P.A = A->dev(); P.b = b->dev(); P.x = x->dev();
+    P.scratch = base; P.scratch_stride = L.cur;
+    P.off = d_tab;
+    P.status = x->d_status;
+    Q.C.status = x->d_status;
+    Q.C.sweep_stats = x->d_status + batch;
+    Q.C.pmax = (int)L.pmax; Q.C.qmax = (int)L.qmax;
+    Q.tol = tol;
+    Q.rmax = (int)std::min<int64_t>(rmax, 1 << 30);
+    Q.rmax_final = Q.rmax;
+    Q.pmax = (int)L.pmax; Q.qmax = (int)L.qmax;
+    Q.mode = mode;
+    Q.nsweeps = (int)plan.size();
+    for (size_t s_ = 0; s_ < plan.size(); ++s_) Q.rmax_sweep[s_] = (int)std::min<int64_t>(plan[s_], 1 << 30);
+    return TTN_OK;
+}
+
+// What the solve leaves on the host side of x: ranks bounded by the largest cap of the plan (and rtop), and the orthogonality flags
+// (mals: after the backward half sweep, right-orthogonal cores, mals.jl:116-117; dmrg: left_core_move!, dmrg.jl:222-223, :440, :566)
+static void two_site_epilogue(ttn_tt_t x, int mode, const std::vector<int64_t>& plan, int64_t rtop) {
+    const int d = x->d;
+    for (int64_t r : plan) rtop = std::max(rtop, r);
+    for (int m = 1; m < d; ++m) x->bound[m] = std::min<int64_t>(x->cap[m], rtop);
+    x->bound[0] = 1; x->bound[d] = 1;
+    for (int bb = 0; bb < x->batch; ++bb)
+        for (int k = 0; k < d; ++k) x->ot[(size_t)bb * d + k] = (k == 0) ? 0 : (mode == 0 ? 1 : -1);
+}
+
+// ---- mals_linsolve / dmrg_linsolve --------------------------------------------------------------------------------
+// mode 0 = mals_linsolve, mode 1 = dmrg_linsolve (N = 2) with `plan` = the rank cap of every full sweep
 // Local solver of the two-site systems (dmrg.jl:92-97): conjugate gradients on the matrix-free operator if `it_solver` or the system
 // has more than `itslv_thresh` unknowns, dense LU otherwise.  The dense path holds K in memory and is limited to TTN_DENSE_LOCAL_MAX
 // unknowns; larger systems always take the matrix-free path.
@@ -1326,41 +1458,19 @@ static int two_site_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, d
     if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_mals_linsolve: needs at least two sites");
     int rc = ttn_orthogonalize(x0, 1, x);                  // mals.jl:252 (checks x's capacity against the start ranks)
     if (rc) return rc;
-    const std::vector<int64_t>& c = x->cap;
-    const std::vector<int64_t>& R = A->rks;
-    const std::vector<int64_t>& rb = b->bound;
-    auto mx = [](long long a_, long long b_) { return a_ > b_ ? a_ : b_; };
-    std::vector<long long> off(4 * d, 0);
-    long long cur = 0, Nmax = 1, mmax = 1, t1 = 1, t2 = 1;
-    for (int i = 0; i < d; ++i) {
-        const long long n = x0->dims[i];
-        off[i] = cur; cur += n * c[i] * n * c[i] * R[i + 1];
-        off[d + i] = cur; cur += n * c[i] * rb[i + 1];
-        mmax = mx(mmax, mx(n * c[i], n * c[i + 1]));
-        t1 = mx(t1, n * c[i] * c[i + 1] * mx(R[i], R[i + 1]));
-        t1 = mx(t1, mx(c[i + 1] * rb[i + 1], c[i] * rb[i + 1]));
-        t2 = mx(t2, c[i + 1] * c[i + 1] * R[i + 1]);
-        if (i + 1 < d) {
-            const long long n2 = x0->dims[i + 1];
-            off[2 * d + i] = cur; cur += R[i + 1] * n2 * n2 * c[i + 2] * c[i + 2];
-            off[3 * d + i] = cur; cur += rb[i + 1] * n2 * c[i + 2];
-            Nmax = mx(Nmax, n * c[i] * n2 * c[i + 2]);
-            t1 = mx(t1, mx(R[i + 1] * n2 * c[i + 2] * c[i + 1], rb[i + 1] * c[i + 1]));
-            t2 = mx(t2, R[i + 1] * c[i + 1] * c[i + 1]);
-        }
-    }
+    TwoSiteLayout L = two_site_slots(x0->dims, x->cap, A->rks, &b->bound);
+    const long long Nmax = L.Nmax;
     // mals_linsolve has no iterative branch in the reference (Hermitian(K) \ b, mals.jl:148-157): dense only
     const long long dense_max = ls.it_solver ? 0 : std::min<long long>(TTN_DENSE_LOCAL_MAX, mode == 1 ? ls.itslv_thresh : TTN_DENSE_LOCAL_MAX);
     const bool need_cg = mode == 1 && (ls.it_solver || Nmax > dense_max);
     if (!need_cg && Nmax > TTN_DENSE_LOCAL_MAX) return fail(TTN_ERR_UNSUPPORTED, "ttn_mals_linsolve: two-site systems above 2048 unknowns (n_i cap_i n_{i+1} cap_{i+2}) are not supported; lower the capacity of x");
-    if (mmax > 256) return fail(TTN_ERR_UNSUPPORTED, "two-site solvers: n_i * capacity above 256 (ranks above 128 for n = 2) is not supported by the SVD core moves");
+    if (L.mmax > 256) return fail(TTN_ERR_UNSUPPORTED, "two-site solvers: n_i * capacity above 256 (ranks above 128 for n = 2) is not supported by the SVD core moves");
     if (ls.maxiter < 1 || !(ls.tol >= 0.0)) return fail(TTN_ERR_ARG, "dmrg_linsolve: bad linsolv_maxiter / linsolv_tol");
-    const long long pmax = std::min<long long>(mmax, 256), qmax = mmax;
-    long long Rzmax = 1;
-    for (int i = 0; i <= d; ++i) Rzmax = mx(Rzmax, R[i]);
+    const long long Rzmax = std::max<long long>(L.Rzmax, A->rks[0]);
     MalsArgs Q;
     memset(&Q, 0, sizeof(Q));
     AlsArgs& P = Q.L;
+    long long& cur = L.cur;
     const long long Kdim = std::min<long long>(Nmax, dense_max);
     P.offK = cur; cur += Kdim * Kdim;
     if (need_cg) { Q.offCg = cur; Q.cg_nmax = Nmax; cur += (4 + Rzmax) * Nmax; }
@@ -1372,59 +1482,24 @@ static int two_site_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, d
     Q.cg_tol = ls.tol;
     P.offPb = cur; cur += Nmax;
     P.offPiv = cur; cur += Nmax / 2 + 8;
-    P.offT1 = cur; cur += t1;
-    P.offT2 = cur; cur += t2;
-    P.offVb = cur; cur += QR_NB * qmax;
-    P.offWb = cur; cur += QR_NB * qmax;
-    Q.offM2 = cur; cur += Nmax;
-    Q.offXg = cur; cur += pmax * pmax;
-    Q.offUs = cur; cur += pmax * pmax;
-    Q.offSig = cur; cur += 4 * pmax + 64;
-    const long long per_train = cur;
+    two_site_core_move_blocks(L, Q);
     const int batch = x->batch;
-    static std::vector<long long> h_off;
-    HIPCHK(hipStreamSynchronize(g_stream));
-    rc = ensure_scratch(sizeof(double) * (size_t)per_train * batch + sizeof(long long) * (size_t)(4 * d) + 64);
+    rc = two_site_prelude(Q, L, A, b, x, tol, rmax, mode, plan);
     if (rc) return rc;
-    rc = ensure_batch_bufs(batch);
-    if (rc) return rc;
-    double* base = (double*)g_scratch;
-    long long* d_tab = (long long*)(base + (size_t)per_train * batch);
-    h_off = off;
-    HIPCHK(hipMemcpyAsync(d_tab, h_off.data(), sizeof(long long) * h_off.size(), hipMemcpyHostToDevice, g_stream));
-    P.A = A->dev(); P.b = b->dev(); P.x = x->dev();
-    P.scratch = base; P.scratch_stride = per_train;
-    P.off = d_tab;
-    P.status = x->d_status;
-    Q.C.status = x->d_status;
-    Q.C.sweep_stats = x->d_status + batch;
-    Q.C.pmax = (int)pmax; Q.C.qmax = (int)qmax;
-    Q.tol = tol;
-    Q.rmax = (int)std::min<int64_t>(rmax, 1 << 30);
-    Q.pmax = (int)pmax; Q.qmax = (int)qmax;
-    Q.mode = mode;
-    Q.nsweeps = (int)plan.size();
-    Q.rmax_final = Q.rmax;
-    int64_t rtop = rmax;
-    for (size_t s_ = 0; s_ < plan.size(); ++s_) { Q.rmax_sweep[s_] = (int)std::min<int64_t>(plan[s_], 1 << 30); rtop = std::max(rtop, plan[s_]); }
-    static int* d_cg_iters = nullptr; static int cg_cap = 0;
     if (need_cg) {
-        if (cg_cap < batch) { if (d_cg_iters) hipFree(d_cg_iters); HIPCHK(hipMalloc((void**)&d_cg_iters, sizeof(int) * batch)); cg_cap = batch; }
-        HIPCHK(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * batch, g_stream));
-        Q.cg_iters = d_cg_iters;
+        rc = g_cg_iters.ensure(sizeof(int) * batch);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(g_cg_iters.p, 0, sizeof(int) * batch, g_stream));
+        Q.cg_iters = g_cg_iters.as<int>();
     }
     hipLaunchKernelGGL(k_mals_linsolve, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Q);
     HIPCHK(hipGetLastError());
     g_cg_iters_host.assign(batch, 0);
     if (need_cg) {
-        HIPCHK(hipMemcpyAsync(g_cg_iters_host.data(), d_cg_iters, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(g_cg_iters_host.data(), g_cg_iters.p, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
     }
-    for (int m = 1; m < d; ++m) x->bound[m] = std::min<int64_t>(x->cap[m], rtop);
-    x->bound[0] = 1; x->bound[d] = 1;
-    for (int bb = 0; bb < batch; ++bb)
-        for (int k = 0; k < d; ++k)         // mals: after the backward half sweep (mals.jl:116-117); dmrg: left_core_move! (dmrg.jl:222-223, :440)
-            x->ot[(size_t)bb * d + k] = (k == 0) ? 0 : (mode == 0 ? 1 : -1);
+    two_site_epilogue(x, mode, plan, rmax);
     return TTN_OK;
 }
 
@@ -1435,20 +1510,10 @@ int ttn_mals_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double t
 
 static int dmrg_linsolve_impl(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
                               const int64_t* rmax_schedule, const LocalSolver& ls) {
-    if (n_stages < 1 || !sweep_schedule || !rmax_schedule) return fail(TTN_ERR_ARG, "dmrg_linsolve: empty schedule");
-    for (int64_t j = 0; j < n_stages; ++j) {
-        // the reference's while-loop (dmrg.jl:421-426) only terminates for positive, strictly increasing stage ends
-        if (sweep_schedule[j] < 1 || (j && sweep_schedule[j] <= sweep_schedule[j - 1])) return fail(TTN_ERR_ARG, "dmrg_linsolve: sweep_schedule must be positive and strictly increasing");
-        if (rmax_schedule[j] < 1) return fail(TTN_ERR_ARG, "dmrg_linsolve: bad rmax_schedule");
-    }
+    if (!rmax_schedule) return fail(TTN_ERR_ARG, "dmrg_linsolve: empty schedule");
     std::vector<int64_t> plan;
-    int64_t n = 0, j = 0;
-    for (;;) {
-        ++n;
-        if (n == sweep_schedule[j]) { if (++j >= n_stages) break; }
-        plan.push_back(rmax_schedule[j]);
-        if ((int64_t)plan.size() > TTN_DMRG_MAX_SWEEPS) return fail(TTN_ERR_UNSUPPORTED, "dmrg_linsolve: more than 32 sweeps in one call");
-    }
+    const int rc = sweep_plan("dmrg_linsolve", TTN_ERR_UNSUPPORTED, n_stages, sweep_schedule, rmax_schedule, plan);
+    if (rc) return rc;
     return two_site_linsolve(A, b, x0, x, tol, rmax_schedule[n_stages - 1], 1, plan, ls);
 }
 
@@ -1477,31 +1542,10 @@ int ttn_dmrg_cg_iterations(int64_t batch, int64_t* iters) {
 }
 
 // ---- dmrg_eigsolve / mals_eigsolve (csrc/ttn_eigsolve_kernels.h) ---------------------------------------------------------------
-// Both walk full sweeps of the same plan as dmrg_linsolve (dmrg_sweep_plan): DMRG windows 0..d-3 forward, d-2..1 backward, then the closing
+// Both walk full sweeps of the same plan as dmrg_linsolve (sweep_plan): DMRG windows 0..d-3 forward, d-2..1 backward, then the closing
 // solve at window 0 (one history entry more); MALS windows 0..d-2 forward, d-2..0 backward (mals.jl:393-418, sweep s capped at plan[s]).
-static int status_code_to_error(int st);
 static std::vector<int> g_lz_iters_host;       // Lanczos operator applications per train of the last eigensolve (ttn_eigsolve_stats)
 static std::vector<double> g_lz_res_host;      // largest final Lanczos residual per train of the last eigensolve
-
-static int eig_plan(const char* who, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule, std::vector<int64_t>& plan) {
-    static std::string msg;
-    auto bad = [&](const char* what) { msg = std::string(who) + ": " + what; return fail(TTN_ERR_ARG, msg.c_str()); };
-    if (n_stages < 1 || !sweep_schedule) return bad("empty schedule");
-    for (int64_t j = 0; j < n_stages; ++j) {
-        // the reference's while-loops (dmrg.jl:523-528, mals.jl:372-378) only terminate for positive, strictly increasing stage ends
-        if (sweep_schedule[j] < 1 || (j && sweep_schedule[j] <= sweep_schedule[j - 1])) return bad("sweep_schedule must be positive and strictly increasing");
-        if (rmax_schedule && rmax_schedule[j] < 1) return bad("bad rmax_schedule");
-    }
-    if (sweep_schedule[n_stages - 1] - 1 > TTN_DMRG_MAX_SWEEPS) return bad("more than 32 sweeps in one call");
-    plan.clear();
-    int64_t n = 0, j = 0;
-    for (;;) {
-        ++n;
-        if (n == sweep_schedule[j]) { if (++j >= n_stages) break; }
-        plan.push_back(rmax_schedule ? rmax_schedule[j] : 1);
-    }
-    return TTN_OK;
-}
 
 static int64_t eig_hist_len(int mode, int64_t d, int64_t nsweeps) { return mode == 1 ? 2 * (d - 2) * nsweeps + 1 : 2 * (d - 1) * nsweeps; }
 
@@ -1509,7 +1553,7 @@ int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!len || (mode != 0 && mode != 1) || d < 2) return fail(TTN_ERR_ARG, "ttn_eigsolve_history_len: bad mode / d / len");
     std::vector<int64_t> plan;
-    const int rc = eig_plan("ttn_eigsolve_history_len", n_stages, sweep_schedule, nullptr, plan);
+    const int rc = sweep_plan("ttn_eigsolve_history_len", TTN_ERR_ARG, n_stages, sweep_schedule, nullptr, plan);
     if (rc) return rc;
     *len = eig_hist_len(mode, d, (int64_t)plan.size());
     return TTN_OK;
@@ -1519,8 +1563,7 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
                              const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
                              int64_t hist_len, double* E_out, int64_t* r_out) {
     const char* who = mode == 1 ? "dmrg_eigsolve" : "mals_eigsolve";
-    static std::string msg;
-    auto err = [&](int code, const char* what) { msg = std::string(who) + ": " + what; return fail(code, msg.c_str()); };
+    auto err = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
     NEED_INIT();
     if (!A || !x0 || !x) return err(TTN_ERR_ARG, "null handle");
     if (!rmax_schedule || !E_out || !r_out) return err(TTN_ERR_ARG, "null schedule / history buffer");
@@ -1530,31 +1573,14 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     if (d < 2) return err(TTN_ERR_UNSUPPORTED, "needs at least two sites");
     if (!(tol >= 0.0) || maxiter < 1 || !(linsolv_tol >= 0.0) || itslv_thresh < 0) return err(TTN_ERR_ARG, "bad tol / linsolv_maxiter / linsolv_tol / itslv_thresh");
     std::vector<int64_t> plan;
-    int rc = eig_plan(who, n_stages, sweep_schedule, rmax_schedule, plan);
+    int rc = sweep_plan(who, TTN_ERR_ARG, n_stages, sweep_schedule, rmax_schedule, plan);
     if (rc) return rc;
     if (hist_len != eig_hist_len(mode, d, (int64_t)plan.size())) return err(TTN_ERR_ARG, "hist_len differs from ttn_eigsolve_history_len");
     // ---- every size check before anything is launched ----
     const std::vector<int64_t>& c = x->cap;
-    const std::vector<int64_t>& R = A->rks;
     for (int k = 0; k <= d; ++k) if (c[k] < x0->bound[k]) return fail(TTN_ERR_CAPACITY, "rank capacity of the result handle is below the start ranks");
-    auto mx = [](long long a_, long long b_) { return a_ > b_ ? a_ : b_; };
-    std::vector<long long> off(4 * d, 0);
-    long long cur = 0, Nmax = 1, mmax = 1, t1 = 1, t2 = 1, Rzmax = 1;
-    for (int i = 0; i < d; ++i) {
-        const long long n = x0->dims[i];
-        off[i] = cur; cur += n * c[i] * n * c[i] * R[i + 1];
-        mmax = mx(mmax, mx(n * c[i], n * c[i + 1]));
-        t1 = mx(t1, n * c[i] * c[i + 1] * mx(R[i], R[i + 1]));
-        t2 = mx(t2, c[i + 1] * c[i + 1] * R[i + 1]);
-        Rzmax = mx(Rzmax, R[i + 1]);
-        if (i + 1 < d) {
-            const long long n2 = x0->dims[i + 1];
-            off[2 * d + i] = cur; cur += R[i + 1] * n2 * n2 * c[i + 2] * c[i + 2];
-            Nmax = mx(Nmax, n * c[i] * n2 * c[i + 2]);
-            t1 = mx(t1, R[i + 1] * n2 * c[i + 2] * c[i + 1]);
-            t2 = mx(t2, R[i + 1] * c[i + 1] * c[i + 1]);
-        }
-    }
+    TwoSiteLayout L = two_site_slots(x0->dims, c, A->rks, nullptr);
+    const long long Nmax = L.Nmax, mmax = L.mmax;
     if (mmax > 256) return err(TTN_ERR_UNSUPPORTED, "n_i * capacity above 256 (ranks above 128 for n = 2) is not supported by the SVD core moves");
     if (Nmax > 65536) return err(TTN_ERR_UNSUPPORTED, "two-site problems above 65 536 unknowns are not supported");
     // branch choice (dmrg.jl:237, mals.jl:181): matrix-free if it_solver or N > threshold.  mals_eigsolve does not forward itslv_thresh
@@ -1563,109 +1589,63 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     const long long dense_max = it_solver ? 0 : std::min<long long>(TTN_DENSE_LOCAL_MAX, thresh);
     const bool need_lz = it_solver || Nmax > dense_max;
     const long long Kdim = std::min<long long>(Nmax, dense_max);
-    const long long pmax = std::min<long long>(mmax, 256), qmax = mmax;
     EigArgs Rg;
     memset(&Rg, 0, sizeof(Rg));
     MalsArgs& Q = Rg.M;
     AlsArgs& P = Q.L;
+    long long& cur = L.cur;
     P.offK = cur; cur += Kdim * Kdim;
     Rg.offEig = cur; cur += 8 + 8 * Kdim;
-    if (need_lz) { Rg.offLz = cur; Rg.lz_nmax = Nmax; cur += (TTN_LZ_M + 1 + TTN_LZ_KEEP + Rzmax) * Nmax + 5000; }
+    if (need_lz) { Rg.offLz = cur; Rg.lz_nmax = Nmax; cur += (TTN_LZ_M + 1 + TTN_LZ_KEEP + L.Rzmax) * Nmax + 5000; }
     P.offPb = cur; cur += Nmax;
-    P.offT1 = cur; cur += t1;
-    P.offT2 = cur; cur += t2;
-    P.offVb = cur; cur += QR_NB * qmax;
-    P.offWb = cur; cur += QR_NB * qmax;
-    Q.offM2 = cur; cur += Nmax;
-    Q.offXg = cur; cur += pmax * pmax;
-    Q.offUs = cur; cur += pmax * pmax;
-    Q.offSig = cur; cur += 4 * pmax + 64;
+    two_site_core_move_blocks(L, Q);
     long long cmax = 1;
-    for (int k = 0; k <= d; ++k) cmax = mx(cmax, c[k]);
+    for (int k = 0; k <= d; ++k) cmax = std::max<long long>(cmax, c[k]);
     P.offTm = cur; cur += mmax * cmax;                      // the QR re-orthonormalisation of every core move
     P.offQb = cur; cur += mmax * cmax;
     P.offRb = cur; cur += cmax * cmax;
     P.offTst = cur; cur += ((cmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64;
-    const long long per_train = cur;
     const int batch = x->batch;
-    const size_t need = sizeof(double) * (size_t)per_train * batch + sizeof(long long) * (size_t)(4 * d) + 64;
     {
+        const size_t need = two_site_bytes(L, batch);
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        if (need > g_scratch_bytes && need - g_scratch_bytes > free_b)
+        if (need > g_scratch.bytes && need - g_scratch.bytes > free_b)
             return err(TTN_ERR_CAPACITY, "the workspace of this capacity and batch (G / H slots, dense K, Lanczos basis) does not fit in device memory");
     }
     rc = ttn_orthogonalize(x0, 1, x);                       // dmrg.jl:522, mals.jl:355
     if (rc) return rc;
-    static std::vector<long long> h_off;
-    HIPCHK(hipStreamSynchronize(g_stream));
-    rc = ensure_scratch(need);
+    const int64_t rmax = rmax_schedule[n_stages - 1];
+    rc = two_site_prelude(Q, L, A, x, x, tol, rmax, mode, plan);
     if (rc) return rc;
-    rc = ensure_batch_bufs(batch);
-    if (rc) return rc;
-    double* base = (double*)g_scratch;
-    long long* d_tab = (long long*)(base + (size_t)per_train * batch);
-    h_off = off;
-    HIPCHK(hipMemcpyAsync(d_tab, h_off.data(), sizeof(long long) * h_off.size(), hipMemcpyHostToDevice, g_stream));
     // device history and Lanczos statistics
-    static double* d_hE = nullptr; static long long* d_hR = nullptr; static size_t h_cap = 0;
-    static int* d_lzi = nullptr; static double* d_lzr = nullptr; static int lz_cap = 0;
     const size_t hn = (size_t)batch * (size_t)hist_len;
-    if (h_cap < hn) {
-        if (d_hE) { hipFree(d_hE); hipFree(d_hR); }
-        HIPCHK(hipMalloc((void**)&d_hE, sizeof(double) * hn)); HIPCHK(hipMalloc((void**)&d_hR, sizeof(long long) * hn)); h_cap = hn;
-    }
-    if (lz_cap < batch) {
-        if (d_lzi) { hipFree(d_lzi); hipFree(d_lzr); }
-        HIPCHK(hipMalloc((void**)&d_lzi, sizeof(int) * batch)); HIPCHK(hipMalloc((void**)&d_lzr, sizeof(double) * batch)); lz_cap = batch;
-    }
-    P.A = A->dev(); P.b = x->dev(); P.x = x->dev();
-    P.scratch = base; P.scratch_stride = per_train;
-    P.off = d_tab;
-    P.status = x->d_status;
-    Q.C.status = x->d_status;
-    Q.C.sweep_stats = x->d_status + batch;
-    Q.C.pmax = (int)pmax; Q.C.qmax = (int)qmax;
-    Q.tol = tol;
-    Q.pmax = (int)pmax; Q.qmax = (int)qmax;
-    Q.mode = mode;
-    Q.nsweeps = (int)plan.size();
-    Q.rmax_final = (int)std::min<int64_t>(rmax_schedule[n_stages - 1], 1 << 30);
-    Q.rmax = Q.rmax_final;
-    int64_t rtop = 1;
-    for (size_t s_ = 0; s_ < plan.size(); ++s_) { Q.rmax_sweep[s_] = (int)std::min<int64_t>(plan[s_], 1 << 30); rtop = std::max(rtop, plan[s_]); }
-    if (mode == 1) rtop = std::max(rtop, rmax_schedule[n_stages - 1]);
-    Rg.hist_E = d_hE; Rg.hist_r = d_hR; Rg.hist_len = (int)hist_len;
+    if ((rc = g_hist_E.ensure(sizeof(double) * hn)) || (rc = g_hist_r.ensure(sizeof(long long) * hn)) ||
+        (rc = g_lz_iters.ensure(sizeof(int) * batch)) || (rc = g_lz_res.ensure(sizeof(double) * batch)))
+        return rc;
+    Rg.hist_E = g_hist_E.as<double>(); Rg.hist_r = g_hist_r.as<long long>(); Rg.hist_len = (int)hist_len;
     Rg.lz_all = it_solver ? 1 : 0;
     Rg.lz_above = (int)std::min<long long>(dense_max, 1LL << 30);
     Rg.lz_maxrestart = (int)std::min<int64_t>(maxiter, 1 << 30);
     Rg.lz_tol = linsolv_tol;
-    Rg.lz_iters = d_lzi; Rg.lz_res = d_lzr;
+    Rg.lz_iters = g_lz_iters.as<int>(); Rg.lz_res = g_lz_res.as<double>();
     hipLaunchKernelGGL(k_two_site_eig, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Rg);
     HIPCHK(hipGetLastError());
-    std::vector<int> st(batch);
     g_lz_iters_host.assign(batch, 0);
     g_lz_res_host.assign(batch, 0.0);
     std::vector<long long> hr(hn);
     if (hn) {
-        HIPCHK(hipMemcpyAsync(E_out, d_hE, sizeof(double) * hn, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipMemcpyAsync(hr.data(), d_hR, sizeof(long long) * hn, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(E_out, g_hist_E.p, sizeof(double) * hn, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(hr.data(), g_hist_r.p, sizeof(long long) * hn, hipMemcpyDeviceToHost, g_stream));
     }
-    HIPCHK(hipMemcpyAsync(g_lz_iters_host.data(), d_lzi, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(g_lz_res_host.data(), d_lzr, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(st.data(), x->d_status, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemsetAsync(x->d_status, 0, sizeof(int) * batch, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
+    HIPCHK(hipMemcpyAsync(g_lz_iters_host.data(), g_lz_iters.p, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(g_lz_res_host.data(), g_lz_res.p, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
+    unsigned seen = 0;
+    rc = take_status(x, seen);                              // synchronises the copies above too
+    if (rc) return rc;
     for (size_t k = 0; k < hn; ++k) r_out[k] = (int64_t)hr[k];
-    for (int m = 1; m < d; ++m) x->bound[m] = std::min<int64_t>(x->cap[m], rtop);
-    x->bound[0] = 1; x->bound[d] = 1;
-    for (int bb = 0; bb < batch; ++bb)
-        for (int k = 0; k < d; ++k)         // mals: after the backward half sweep (right-orthogonal cores); dmrg: left_core_move! (dmrg.jl:566)
-            x->ot[(size_t)bb * d + k] = (k == 0) ? 0 : (mode == 0 ? 1 : -1);
-    for (int bb = 0; bb < batch; ++bb) if (st[bb] == TTN_EIG_STATUS_LANCZOS) return err(TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol");
-    for (int bb = 0; bb < batch; ++bb) if (st[bb] == TTN_EIG_STATUS_NONFINITE) return err(TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)");
-    for (int bb = 0; bb < batch; ++bb) if (st[bb]) return status_code_to_error(st[bb]);
-    return TTN_OK;
+    two_site_epilogue(x, mode, plan, mode == 1 ? rmax : 1);
+    return status_error(seen, who);
 }
 
 int ttn_dmrg_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule,
@@ -1688,41 +1668,17 @@ int ttn_eigsolve_stats(int64_t batch, int64_t* lanczos_applies, double* lanczos_
     return TTN_OK;
 }
 
-// Failure codes of every dense kernel that wrote `h` since the last call (synchronises).  The codes are sticky on the device —
-// a kernel only ever stores a non-zero code, so a failure inside a chain of launches survives the launches after it — and
-// are cleared here, on read.
-static int check_status(ttn_tt_t h) {
-    const int batch = h->batch;
-    std::vector<int> st(batch);
-    HIPCHK(hipMemcpyAsync(st.data(), h->d_status, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int) * batch, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int b = 0; b < batch; ++b) if (st[b] == 3) return fail(TTN_ERR_SINGULAR, "als_linsolve: a local system K is singular");
-    for (int b = 0; b < batch; ++b) if (st[b] == 4) return fail(TTN_ERR_DIMS, "als_linsolve: a train's ranks differ from the ranks of the start handle");
-    for (int b = 0; b < batch; ++b) if (st[b] == 2) return fail(TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)");
-    for (int b = 0; b < batch; ++b) if (st[b]) return fail(TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit");
-    return TTN_OK;
-}
-
-static int status_code_to_error(int st) {
-    if (st == 3) return fail(TTN_ERR_SINGULAR, "als_linsolve: a local system K is singular");
-    if (st == 4) return fail(TTN_ERR_DIMS, "als_linsolve: a train's ranks differ from the ranks of the start handle");
-    if (st == 2) return fail(TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)");
-    if (st) return fail(TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit");
-    return TTN_OK;
-}
-
 int ttn_status_all(void) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    int st = 0;
+    unsigned seen = 0;
     for (ttn_tt_s* h : g_live)
-        if (h->d_status) hipLaunchKernelGGL(k_fold_status, dim3(1), dim3(64), 0, g_stream, (const int*)h->d_status, h->batch, g_pending_status);
+        if (h->d_status) hipLaunchKernelGGL(k_fold_status, dim3(1), dim3(64), 0, g_stream, (const int*)h->d_status, h->batch, g_pending_status.as<unsigned>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&st, g_pending_status, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemsetAsync(g_pending_status, 0, sizeof(int), g_stream));
+    HIPCHK(hipMemcpyAsync(&seen, g_pending_status.p, sizeof(unsigned), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemsetAsync(g_pending_status.p, 0, sizeof(unsigned), g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
-    return status_code_to_error(st);
+    return status_error(seen);
 }
 
 int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps) {
@@ -1735,7 +1691,9 @@ int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps) {
         HIPCHK(hipStreamSynchronize(g_stream));
         for (int b = 0; b < psi->batch; ++b) total_jacobi_sweeps[b] = st[b];
     }
-    return check_status(psi);
+    unsigned seen = 0;
+    const int rc = take_status(psi, seen);
+    return rc ? rc : status_error(seen);
 }
 
 int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
@@ -1751,32 +1709,33 @@ int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
     for (int m = 0; m <= d; ++m) { ramax = std::max<long long>(ramax, a->bound[m]); rbmax = std::max<long long>(rbmax, b->bound[m]); }
     for (int k = 0; k < d; ++k) nmax = std::max<long long>(nmax, a->dims[k]);
     const long long per_train = (2 + nmax) * ramax * rbmax + 16;
-    int rc = ensure_scratch(sizeof(double) * (size_t)per_train * a->batch);
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * a->batch);
     if (rc) return rc;
-    rc = ensure_batch_bufs(a->batch);
+    rc = g_dout.ensure(sizeof(double) * a->batch);
     if (rc) return rc;
     DotArgs P;
     P.a = a->dev(); P.b = b->dev();
-    P.scratch = (double*)g_scratch; P.scratch_stride = per_train;
+    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
     P.ramax = (int)ramax; P.rbmax = (int)rbmax; P.nmax = (int)nmax;
-    P.out = g_dout;
-    HIPCHK(hipEventRecord(g_ev0, g_stream));
+    P.out = g_dout.as<double>();
+    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
     hipLaunchKernelGGL(k_dot_fused, dim3(a->batch), dim3(TTN_WG), DOT_LDS_BYTES(d), g_stream, P);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_ev1, g_stream));              // ttn_last_launch_ms: the kernel alone (this call goes on to copy and synchronise)
+    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));       // ttn_last_launch_ms: the kernel alone (this call goes on to copy and synchronise)
     g_have_launch_ms = true;
-    HIPCHK(hipMemcpyAsync(out, g_dout, sizeof(double) * a->batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * a->batch, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return TTN_OK;
 }
 
-// diagnostics: the per-train state words of the last three-launch orthogonalize (next site, buffers, sites taken by k_ortho512)
-static int* g_ortho_state = nullptr;
-extern "C" int ttn_debug_ortho_state(int64_t b, int64_t* out4) {
+// diagnostics: the per-train state words of the last orthogonalize (next site, buffers, sites taken by k_ortho512), read from the
+// workspace where that call left them (the workspace only grows, so the words stay in bounds until ttn_finalize)
+int ttn_debug_ortho_state(int64_t b, int64_t* out4) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!g_ortho_state || !out4) return fail(TTN_ERR_ARG, "no three-launch orthogonalize yet");
+    NEED_INIT();
+    if (!out4 || b < 0 || b >= g_ortho_state_batch) return fail(TTN_ERR_ARG, "ttn_debug_ortho_state: no orthogonalize of a batch with train b yet");
     int tmp[4];
-    HIPCHK(hipMemcpyAsync(tmp, g_ortho_state + 4 * b, sizeof(tmp), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(tmp, g_scratch.as<char>() + g_ortho_state_off + sizeof(tmp) * b, sizeof(tmp), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     for (int i = 0; i < 4; ++i) out4[i] = tmp[i];
     return TTN_OK;
@@ -1787,8 +1746,8 @@ int ttn_last_launch_ms(float* ms) {
     NEED_INIT();
     if (!ms) return fail(TTN_ERR_ARG, "null pointer");
     if (!g_have_launch_ms) return fail(TTN_ERR_ARG, "ttn_last_launch_ms: no ttn_dot / ttn_orthogonalize launch yet");
-    HIPCHK(hipEventSynchronize(g_ev1));
-    HIPCHK(hipEventElapsedTime(ms, g_ev0, g_ev1));
+    HIPCHK(hipEventSynchronize(g_launch_ev1));
+    HIPCHK(hipEventElapsedTime(ms, g_launch_ev0, g_launch_ev1));
     return TTN_OK;
 }
 
@@ -1818,14 +1777,14 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
     const long long mm = nmax * rmax;           // rows of the tall matrices
     const long long per_train = 2 * mm * rmax + 4 * rmax * rmax + 2 * QR_NB * mm + ((rmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64   // Tm, Qb, 4 R, Vb, Wb, T panels
                                 + 3 * 128 * 128;                                                                                  // Gram matrices / L1 of the Cholesky-QR steps
-    int rc = ensure_scratch(sizeof(double) * (size_t)per_train * x->batch + sizeof(int) * (5 * (size_t)x->batch + 16) + 64);
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch + sizeof(int) * (5 * (size_t)x->batch + 16) + 64);
     if (rc) return rc;
-    rc = ensure_batch_bufs(x->batch);
+    rc = g_dout.ensure(sizeof(double) * x->batch);
     if (rc) return rc;
     OrthoArgs P;
     P.x = x->dev(); P.y = y->dev();
     P.center = (int)center - 1;
-    P.scratch = (double*)g_scratch; P.scratch_stride = per_train;
+    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
     P.mmax = (int)mm; P.rmax = (int)rmax;
     { const char* e = getenv("TTN_ORTHO_CHOLQR"); P.no_cholqr = (e && atoi(e) == 1) ? 2 : 0; }
     // Rank <= 64 QTT trains: the ramp sites at the right end by one wave per train (csrc/ttn_ortho_ramp.h), the tall sites and the
@@ -1837,9 +1796,10 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
     for (int k = 0; k < d; ++k) use512 = use512 && x->dims[k] == 2;
     { const char* e = getenv("TTN_ORTHO512"); if (e) use512 = atoi(e) != 0 && nmax == 2 && rmax <= 64 && d <= TTN_MAX_D * 8; }
     P.mode = 0; P.trains = nullptr;
-    P.state = reinterpret_cast<int*>((double*)g_scratch + (size_t)per_train * x->batch);
-    g_ortho_state = P.state;
-    HIPCHK(hipEventRecord(g_ev0, g_stream));
+    g_ortho_state_off = sizeof(double) * (size_t)per_train * x->batch;
+    g_ortho_state_batch = x->batch;
+    P.state = reinterpret_cast<int*>(g_scratch.as<char>() + g_ortho_state_off);
+    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
     if (use512) {
         P.mode = 1;
         int* left = P.state + 4 * (size_t)x->batch;                            // count, then the list of trains k_ortho512 did not finish
@@ -1864,7 +1824,7 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
         hipLaunchKernelGGL(k_orthogonalize, dim3(x->batch), dim3(TTN_WG), ORTHO_LDS_BYTES, g_stream, P);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_ev1, g_stream));
+    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
     g_have_launch_ms = true;
     y->bound = yb;
     for (int b = 0; b < y->batch; ++b)
@@ -2002,9 +1962,9 @@ static int tdvp_launch(int op, int cplx, int64_t batch, int64_t Dl, int64_t d, i
     const long long mb = m_shared ? 1 : batch;
     const size_t work_d = (size_t)(w1 + w2) * es * batch;
     const size_t stage_d = host ? (size_t)es * ((nFL + nFR + nX + nOut) * batch + (nM1 + nM2) * mb) : 0;
-    int rc = ensure_scratch(sizeof(double) * (work_d + stage_d));
+    int rc = g_scratch.ensure(sizeof(double) * (work_d + stage_d));
     if (rc) return rc;
-    double* base = (double*)g_scratch;
+    double* base = g_scratch.as<double>();
     TdvpArgs P;
     memset(&P, 0, sizeof(P));
     P.op = op; P.cplx = cplx;
@@ -2065,10 +2025,10 @@ int ttn_dense_qr(int cplx, int64_t m, int64_t n, double* A, double* Q, double* R
     if (!A || !Q || !R || m < 1 || n < 1) return fail(TTN_ERR_ARG, "ttn_dense_qr: bad argument");
     if (m > (1 << 20) || n > (1 << 20)) return fail(TTN_ERR_UNSUPPORTED, "ttn_dense_qr: matrix too large");
     const int64_t r = std::min(m, n);
-    int rc = ensure_scratch(sizeof(double) * 2 * (size_t)r + 64);
+    int rc = g_scratch.ensure(sizeof(double) * 2 * (size_t)r + 64);
     if (rc) return rc;
-    if (cplx) hipLaunchKernelGGL(k_dense_qr<true>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, Q, R, (double*)g_scratch);
-    else hipLaunchKernelGGL(k_dense_qr<false>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, Q, R, (double*)g_scratch);
+    if (cplx) hipLaunchKernelGGL(k_dense_qr<true>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, Q, R, g_scratch.as<double>());
+    else hipLaunchKernelGGL(k_dense_qr<false>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, Q, R, g_scratch.as<double>());
     HIPCHK(hipGetLastError());
     return TTN_OK;
 }
@@ -2080,9 +2040,9 @@ int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* 
     if (m > (1 << 20) || n > 4096) return fail(TTN_ERR_UNSUPPORTED, "ttn_dense_svd: matrix too large");
     const size_t w = cplx ? 2 : 1;
     const size_t vw = sizeof(double) * w * (size_t)n * n, dwb = sizeof(double) * ((size_t)n + (size_t)m);
-    int rc = ensure_scratch(vw + dwb + sizeof(int) * ((size_t)n + 2) + 64);
+    int rc = g_scratch.ensure(vw + dwb + sizeof(int) * ((size_t)n + 2) + 64);
     if (rc) return rc;
-    double* Vw = (double*)g_scratch;
+    double* Vw = g_scratch.as<double>();
     double* dw = Vw + w * (size_t)n * n;
     double* lw = dw + n;
     int* iw = reinterpret_cast<int*>(lw + m);

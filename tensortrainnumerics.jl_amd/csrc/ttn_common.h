@@ -68,6 +68,16 @@ __host__ __device__ inline View tview(View v) { return View{v.p, v.c, v.r}; }
 __host__ __device__ inline View mkview(double* p, Idx r, Idx c) { return View{p, r, c}; }
 __host__ __device__ inline long long minstride(const Idx& d) { return d.q ? (d.lo < d.hi ? d.lo : d.hi) : d.lo; }
 
+// Per-train failure codes of the dense kernels.  The host maps each to a TTN_ERR_* code and a message (ttn_api.hip: status_table).
+enum TtnStatus : int {
+    TTN_ST_JACOBI = 1,           // a Jacobi SVD hit its sweep limit
+    TTN_ST_RANK_OVERFLOW = 2,    // a rank grew beyond the capacity of its handle / working slot
+    TTN_ST_SINGULAR = 3,         // a local linear system is singular
+    TTN_ST_RANKS_DIFFER = 4,     // a train's ranks differ from the bound of its handle (als_linsolve)
+    TTN_ST_LANCZOS = 5,          // Lanczos exhausted its restarts with a residual above 1e3 * tol
+    TTN_ST_NONFINITE = 6,        // a local eigenvalue or eigenvector entry was NaN or infinite (the sweep stops there)
+};
+
 // Per-train failure code of a handle (include/ttn.h: ttn_compress_status): the FIRST condition a train meets is kept — only the
 // workgroup that owns train b writes status[b], so a plain test is enough.
 __device__ inline void ttn_set_status(int* st, int code) { if (*st == 0) *st = code; }

@@ -18,8 +18,6 @@
 #define TTN_LZ_M 30                  // Krylov dimension of the matrix-free branch (KrylovKit.KrylovDefaults.krylovdim)
 #define TTN_LZ_KEEP 10               // Ritz vectors kept by a thick restart
 #define TTN_LZ_LD 32                 // leading dimension of the projected matrices
-#define TTN_EIG_STATUS_LANCZOS 5     // per-train status: Lanczos exhausted its restarts with a residual above 1e3 * tol
-#define TTN_EIG_STATUS_NONFINITE 6   // per-train status: a local eigenvalue or eigenvector entry was NaN or infinite (the sweep stops there)
 
 // Workgroup maximum of values of any sign (wg_max pads the missing waves with 0.0, which is right for the moduli it is used on).
 __device__ inline double wg_max_signed(double v, double* red) {
@@ -642,7 +640,7 @@ __global__ void __launch_bounds__(TTN_WG) k_two_site_eig(EigArgs R) {
         prev_dir = dir;
         const bool closing = mode == 1 && t == total - 1;
         if (tid == 0) { hE[t] = lam; if (closing) hR[t] = max_rank(); }  // dmrg.jl:539-540: the closing entries come before the left move
-        if (nonfinite) { status = TTN_EIG_STATUS_NONFINITE; break; }      // no core move of a NaN block
+        if (nonfinite) { status = TTN_ST_NONFINITE; break; }      // no core move of a NaN block
         const int n2 = uni32(P.x.dims[i + 1]);
         double* xi = XC(i);
         double* xn = XC(i + 1);
@@ -651,7 +649,7 @@ __global__ void __launch_bounds__(TTN_WG) k_two_site_eig(EigArgs R) {
             r = wg_hsvd_step(Q.C, b, S, mkview(Pb, plain(1), plain(na)), na, nb, M2, 2, n2, 0, xi, xn, Q.tol, (int)P.x.cap[i + 1], lds, rule, rmax);
         else
             r = wg_hsvd_step(Q.C, b, S, mkview(Pb, plain(na), plain(1)), nb, na, M2, 1, n2, 0, xn, xi, Q.tol, (int)P.x.cap[i + 1], lds, rule, rmax);
-        if (r < 0) { status = 2; break; }
+        if (r < 0) { status = TTN_ST_RANK_OVERFLOW; break; }
         if (tid == 0) xr[i + 1] = r;
         __syncthreads();
         reortho(i, r, dir);
@@ -660,7 +658,7 @@ __global__ void __launch_bounds__(TTN_WG) k_two_site_eig(EigArgs R) {
         if (dir == 0) als_update_G_op(E, i);
         else if (i > 0) mals_update_H_op(E, i);
     }
-    if (lz_fail && !status) status = TTN_EIG_STATUS_LANCZOS;
+    if (lz_fail && !status) status = TTN_ST_LANCZOS;
     if (tid == 0) {
         if (status) ttn_set_status(&P.status[b], status);
         if (R.lz_iters) R.lz_iters[b] = lz_iters;
