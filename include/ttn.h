@@ -216,7 +216,33 @@ int ttn_dmrg_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t 
 int ttn_mals_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
                       const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
                       int64_t hist_len, double* E, int64_t* r_hist);
-int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_t* sweep_schedule, int64_t* len);
+int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_t* sweep_schedule, int64_t* len);   /* mode 2: ALS */
+/* als_eigsolve(A, tt_start; sweep_schedule, rmax_schedule, noise_schedule, it_solver, itslv_thresh, maxiter, linsolv_tol)
+ * (src/solvers/als.jl:251-326) and als_gen_eigsolv(A, S, tt_start; sweep_schedule, rmax_schedule, it_solver, itslv_thresh)
+ * (src/solvers/als.jl:344-426): the smallest eigenvalue of a real symmetric A (of the pencil A x = lambda S x, S symmetric positive
+ * definite) and its eigenvector, by one-site sweeps at the fixed ranks of each stage.  x receives orthogonalize(x0) first; stage j > 0
+ * starts with increase_ranks(x, rmax_schedule[j]; noise = noise_schedule[j]) and orthogonalize, and the environments are rebuilt from
+ * the new train (for als_gen_eigsolv too: the reference zero-pads its stale right environments there).  E[b * hist_len + t] = the local
+ * eigenvalue of micro-step t; hist_len must equal ttn_eigsolve_history_len(mode = 2) = 2 (d - 1) (sweep_schedule[end] - 1).
+ * Local problem: the smallest eigenpair of K_s = 1/2 (K + K^T) (and of the pencil (K_s, S_s)).  Standard: dense (Householder, Sturm
+ * multisection, inverse iteration) unless the local size N = n_i r_{i-1} r_i is above 2048 or (it_solver and N > itslv_thresh), then
+ * thick-restart Lanczos from the current core, at most maxiter restarts, stopped at a Ritz residual <= linsolv_tol.  Generalized: dense
+ * (blocked Cholesky S_s = L L^T, the smallest pair of L^-1 K_s L^-T, x = L^-T y) when !it_solver and N <= min(itslv_thresh, 2048),
+ * otherwise LOBPCG with block size 1, no preconditioner, tol 1e-8, at most 500 iterations; the local vector leaves S-normalised.
+ * Every local eigenvector is signed so that its first entry of largest modulus is positive: a batch gives the trains of single calls.
+ * Noise blocks (noise_schedule null: none) are orthonormal blocks from a counter-based stream keyed by (seed, site, entry), scaled by
+ * the noise; noise = 0 pads with exact zeros.
+ * Refused before any launch: bad schedules (TTN_ERR_ARG, as ttn_dmrg_eigsolve), a stage rmax not above the maximum rank before it
+ * (TTN_ERR_ARG), d < 2, start ranks beyond what orthogonalize keeps, cores too flat for the QR core moves, local sizes above 65 536
+ * (TTN_ERR_UNSUPPORTED), a capacity of x below the ranks of a stage or a workspace that does not fit (TTN_ERR_CAPACITY).  Per train: a
+ * Lanczos / LOBPCG solve that ends with a residual above 1e3 tol: TTN_ERR_NO_CONVERGENCE; a non-finite local pair: the same, and the
+ * train stops; a local metric that is not positive definite: TTN_ERR_SINGULAR, and the train stops.  Operator applications and the
+ * largest final residual go to ttn_eigsolve_stats.  Synchronises. */
+int ttn_als_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule,
+                     const double* noise_schedule, int64_t seed, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                     int64_t hist_len, double* E);
+int ttn_als_gen_eigsolve(ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, const int64_t* sweep_schedule,
+                         const int64_t* rmax_schedule, int it_solver, int64_t itslv_thresh, int64_t hist_len, double* E);
 /* Per train of the last eigensolve: operator applications of its Lanczos solves (0: every local problem dense) and the largest final
  * Lanczos residual norm. */
 int ttn_eigsolve_stats(int64_t batch, int64_t* lanczos_applies, double* lanczos_residual);

@@ -8,7 +8,7 @@
 module TTNBackend
 
 using TensorTrainNumerics
-import TensorTrainNumerics: TTvector, TToperator, dmrg_eigsolve, mals_eigsolve, orthogonalize, tt_compress!, _tt_bond_truncate!, hadamard, add!, r_and_d_to_rks, zeros_tt,
+import TensorTrainNumerics: TTvector, TToperator, dmrg_eigsolve, mals_eigsolve, als_eigsolve, als_gen_eigsolv, orthogonalize, tt_compress!, _tt_bond_truncate!, hadamard, add!, r_and_d_to_rks, zeros_tt,
     _applyH1_lsr, _applyH0, _update_left_env, _update_right_env, _applyH2_lsr
 import Base: *, +
 
@@ -275,6 +275,68 @@ function mals_eigsolve(A::TToperator{Float64, N}, tt_start::TTvector{Float64, N}
                        rmax_schedule = [round(Int, sqrt(prod(tt_start.ttv_dims)))], it_solver = false, linsolv_maxiter = 200,
                        linsolv_tol = max(sqrt(tol), 1.0e-8), itslv_thresh = 256) where {N}
     return _eigsolve_dev(:mals, 0, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+end
+
+# ---- One-site eigensolvers (src/solvers/als.jl:251-426) ------------------------------------------------------------------------
+# Written against include/ttn.h and not executed (no Julia on the build machines).  The capacity of x is the largest rank any stage
+# holds: the start ranks, then r_and_d_to_rks(fill(rmax)) of every later stage.
+function _als_eig_dev(gen::Bool, A::TToperator{Float64, N}, S, x0::TTvector{Float64, N}, sweep_schedule, rmax_schedule, noise_schedule,
+                      seed, it_solver, maxiter, linsolv_tol, itslv_thresh) where {N}
+    dims = _dims(x0.ttv_dims)
+    ss, rs = Int64[sweep_schedule...], Int64[rmax_schedule...]
+    ns = Float64[noise_schedule...]
+    length(ss) == length(rs) == length(ns) || throw(AssertionError("Sweep schedule error"))
+    cap = Int64[x0.ttv_rks...]
+    for j in 2:length(rs)
+        cap = max.(cap, r_and_d_to_rks(vcat(1, fill(rs[j], N - 1), 1), x0.ttv_dims; rmax = rs[j]))
+    end
+    hl = Ref{Int64}(0)
+    _chk(ccall((:ttn_eigsolve_history_len, LIB), Cint, (Cint, Int64, Int64, Ptr{Int64}, Ref{Int64}), Cint(2), N, length(ss), ss, hl))
+    hA, hS, hx0, hx = Ref{Ptr{Cvoid}}(), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(), Ref{Ptr{Cvoid}}()
+    pa, px = _ptrs(A.tto_vec), _ptrs(x0.ttv_vec)
+    GC.@preserve A x0 pa px begin
+        _chk(ccall((:ttn_tto_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}), N, dims, A.tto_rks, pa, hA))
+        _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, dims, x0.ttv_rks, 1, hx0))
+        _chk(ccall((:ttn_tt_upload, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Int64}), hx0[], 0, px, x0.ttv_rks, x0.ttv_ot))
+    end
+    if gen
+        ps = _ptrs(S.tto_vec)
+        GC.@preserve S ps _chk(ccall((:ttn_tto_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}), N, dims, S.tto_rks, ps, hS))
+    end
+    _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, dims, cap, 1, hx))
+    E = zeros(Float64, max(hl[], 1))
+    if gen
+        _chk(ccall((:ttn_als_gen_eigsolve, LIB), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Cint, Int64, Int64, Ptr{Float64}),
+            hA[], hS[], hx0[], hx[], length(ss), ss, rs, Cint(it_solver), itslv_thresh, hl[], E))
+    else
+        _chk(ccall((:ttn_als_eigsolve, LIB), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Cint, Int64, Float64, Int64, Int64, Ptr{Float64}),
+            hA[], hx0[], hx[], length(ss), ss, rs, ns, Int64(seed), Cint(it_solver), maxiter, linsolv_tol, itslv_thresh, hl[], E))
+    end
+    rks, ot = zeros(Int64, N + 1), zeros(Int64, N)
+    _chk(ccall((:ttn_tt_ranks, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), hx[], 0, rks, ot))
+    x = zeros_tt(Float64, x0.ttv_dims, rks)
+    px = _ptrs(x.ttv_vec)
+    GC.@preserve x px _chk(ccall((:ttn_tt_download, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}), hx[], 0, px))
+    x.ttv_ot .= ot
+    ccall((:ttn_tt_free, LIB), Cint, (Ptr{Cvoid},), hx0[]); ccall((:ttn_tt_free, LIB), Cint, (Ptr{Cvoid},), hx[])
+    ccall((:ttn_tto_free, LIB), Cint, (Ptr{Cvoid},), hA[])
+    gen && ccall((:ttn_tto_free, LIB), Cint, (Ptr{Cvoid},), hS[])
+    return E[1:hl[]], x
+end
+
+function als_eigsolve(A::TToperator{Float64, N}, tt_start::TTvector{Float64, N}; sweep_schedule = [2],
+                      rmax_schedule = [maximum(tt_start.ttv_rks)], noise_schedule = zeros(length(rmax_schedule)), it_solver = false,
+                      itslv_thresh = 1024, maxiter = 200, linsolv_tol = 1.0e-8, seed = 0) where {N}
+    return _als_eig_dev(false, A, nothing, tt_start, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter, linsolv_tol,
+                        itslv_thresh)
+end
+
+function als_gen_eigsolv(A::TToperator{Float64, N}, S::TToperator{Float64, N}, tt_start::TTvector{Float64, N}; sweep_schedule = [2],
+                         rmax_schedule = [maximum(tt_start.ttv_rks)], tol = 1.0e-10, it_solver = false, itslv_thresh = 2500) where {N}
+    return _als_eig_dev(true, A, S, tt_start, sweep_schedule, rmax_schedule, zeros(length(rmax_schedule)), 0, it_solver, 1, 1.0e-8,
+                        itslv_thresh)
 end
 
 # ---- TDVP local contractions (src/solvers/tdvp.jl:29-43, :205-208) ------------------------------------------------------------

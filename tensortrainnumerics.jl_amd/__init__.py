@@ -9,7 +9,7 @@ from ._lib import TTNError, build, ensure_init, finalize
 from .constructors import (Delta, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn, qtt_cos, qtt_exp, qtt_sin, qtt_to_vector, rand_tt,
                            shift, toeplitz_to_qtto, xxx_tto, xxz_tto, zeros_tt, zeros_tto)
 from .device import DeviceTT, DeviceTTO, StreamTimer
-from .solvers import dmrg_eigsolve, mals_eigsolve
+from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, ttv_decomp
 from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, div, dot, euclidean_distance, hadamard, norm,
                  orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_)

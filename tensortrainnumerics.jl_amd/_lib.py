@@ -83,6 +83,8 @@ SIGNATURES = {
     "ttn_dmrg_eigsolve": (C.c_int, [handle, handle, handle, C.c_double, i64, p_i64, p_i64, C.c_int, i64, C.c_double, i64, i64, p_f64, p_i64]),
     "ttn_mals_eigsolve": (C.c_int, [handle, handle, handle, C.c_double, i64, p_i64, p_i64, C.c_int, i64, C.c_double, i64, i64, p_f64, p_i64]),
     "ttn_eigsolve_history_len": (C.c_int, [C.c_int, i64, i64, p_i64, p_i64]),
+    "ttn_als_eigsolve": (C.c_int, [handle, handle, handle, i64, p_i64, p_i64, p_f64, i64, C.c_int, i64, C.c_double, i64, i64, p_f64]),
+    "ttn_als_gen_eigsolve": (C.c_int, [handle, handle, handle, handle, i64, p_i64, p_i64, C.c_int, i64, i64, p_f64]),
     "ttn_eigsolve_stats": (C.c_int, [i64, p_i64, p_f64]),
     "ttn_tdvp_apply_h1": (C.c_int, [C.c_int, i64, i64, i64, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ttn_tdvp_apply_h0": (C.c_int, [C.c_int, i64, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

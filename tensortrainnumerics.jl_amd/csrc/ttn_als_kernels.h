@@ -377,6 +377,101 @@ __device__ __noinline__ void mals_update_H_op(const AlsEnv& E, int i) {
     __syncthreads();
 }
 
+// The operator part of the ALS right environment (als.jl:23-26): H_{i-1} (R_{i-1}, r_{i-1}, r_{i-1}) from core i of x, A_i and H_i.
+// k_als_linsolve adds the right-hand side part; the one-site eigensolvers (ttn_als_eig_kernels.h) have none.
+__device__ __noinline__ void als_update_H_op(const AlsEnv& E, int i) {
+    double* T1 = E.T1; double* T2 = E.T2;
+    const AlsSite s = SITE(i);
+    const double *x = XC(i), *A = AC(i), *Hi = HP(i);
+    double *Ho = HP(i - 1);
+    // T1[z, ph, k, be] = sum_ch H[z, ph, ch] x[k, be, ch]
+    WG_FOR((long long)s.Rr * s.rr * s.n * s.rl) {
+        long long t = e_; const int z = t % s.Rr; t /= s.Rr; const int ph = t % s.rr; t /= s.rr; const int k = t % s.n; const int be = (int)(t / s.n);
+        double a = 0.0;
+        for (int ch = 0; ch < s.rr; ++ch) a = fma(Hi[z + s.Rr * (ph + (long long)s.rr * ch)], x[k + s.n * (be + (long long)s.rl * ch)], a);
+        T1[e_] = a;
+    }
+    __syncthreads();
+    // T2[j, ph, a, be] = sum_{z, k} A[j, k, a, z] T1[z, ph, k, be]
+    WG_FOR((long long)s.n * s.rr * s.Rl * s.rl) {
+        long long t = e_; const int j = t % s.n; t /= s.n; const int ph = t % s.rr; t /= s.rr; const int a_ = t % s.Rl; const int be = (int)(t / s.Rl);
+        double a = 0.0;
+        for (int z = 0; z < s.Rr; ++z)
+            for (int k = 0; k < s.n; ++k)
+                a = fma(A[j + s.n * (k + s.n * (a_ + (long long)s.Rl * z))], T1[z + s.Rr * (ph + (long long)s.rr * (k + (long long)s.n * be))], a);
+        T2[e_] = a;
+    }
+    __syncthreads();
+    // H_{i-1}[a, al, be] = sum_{j, ph} x[j, al, ph] T2[j, ph, a, be]
+    WG_FOR((long long)s.Rl * s.rl * s.rl) {
+        long long t = e_; const int a_ = t % s.Rl; t /= s.Rl; const int al = t % s.rl; const int be = (int)(t / s.rl);
+        double a = 0.0;
+        for (int ph = 0; ph < s.rr; ++ph)
+            for (int j = 0; j < s.n; ++j)
+                a = fma(x[j + s.n * (al + (long long)s.rl * ph)], T2[j + s.n * (ph + (long long)s.rr * (a_ + (long long)s.Rl * be))], a);
+        Ho[e_] = a;
+    }
+    __syncthreads();
+}
+
+// The QR core moves of the one-site sweeps, on the local solution V (n, r_{i-1}, r_i column-major, ranks E.xr).  Tm, Qb, Rb: the
+// QR's tall matrix, its Q and R; W: its panel workspace.  Shared by k_als_linsolve and the one-site eigensolvers.
+struct AlsMove { OrthoWork W; double *Tm, *Qb, *Rb; };
+// right_core_move (als.jl:122-135): x_i <- Q of V (n r_{i-1} x r_i), x_{i+1}[a, b, c] <- sum_z R[b, z] x_{i+1}[a, z, c]
+__device__ __noinline__ void als_right_core_move(const AlsEnv& E, const AlsMove& M, const double* V, int i, double* lds) {
+    double* T1 = E.T1; double* Tm = M.Tm; double* Qb = M.Qb; double* Rb = M.Rb;
+    const AlsSite s = SITE(i);
+    const int mm = s.n * s.rl;
+    WG_FOR((long long)mm * s.rr) Tm[e_] = V[e_];
+    __syncthreads();
+    wg_qr_explicit(mm, s.rr, Tm, Qb, Rb, M.W, lds);
+    double* xi = XC(i);
+    WG_FOR((long long)mm * s.rr) xi[e_] = Qb[e_];
+    const AlsSite s2 = SITE(i + 1);
+    double* xn = XC(i + 1);
+    WG_FOR((long long)s2.n * s2.rl * s2.rr) {
+        long long t = e_; const int a_ = t % s2.n; t /= s2.n; const int bq = t % s2.rl; const int c = (int)(t / s2.rl);
+        double a = 0.0;
+        for (int z = 0; z < s2.rl; ++z) a = fma(Rb[bq + (long long)s.rr * z], xn[a_ + s2.n * (z + (long long)s2.rl * c)], a);
+        T1[e_] = a;
+    }
+    __syncthreads();
+    WG_FOR((long long)s2.n * s2.rl * s2.rr) xn[e_] = T1[e_];
+    __syncthreads();
+}
+// left_core_move (als.jl:102-120): M[(x + n a2), a1] = V[x, a1, a2] = Q R, x_i <- Q back in (n, r_{i-1}, r_i),
+// x_{i-1}[a, b, c] <- sum_z x_{i-1}[a, b, z] R[c, z]
+__device__ __noinline__ void als_left_core_move(const AlsEnv& E, const AlsMove& M, const double* V, int i, double* lds) {
+    double* T1 = E.T1; double* Tm = M.Tm; double* Qb = M.Qb; double* Rb = M.Rb;
+    const AlsSite s = SITE(i);
+    const int mm = s.n * s.rr;
+    WG_FOR((long long)mm * s.rl) {
+        const int row = (int)(e_ % mm), a1 = (int)(e_ / mm);
+        const int xx = row % s.n, a2 = row / s.n;
+        Tm[e_] = V[xx + s.n * (a1 + (long long)s.rl * a2)];
+    }
+    __syncthreads();
+    wg_qr_explicit(mm, s.rl, Tm, Qb, Rb, M.W, lds);
+    double* xi = XC(i);
+    WG_FOR((long long)mm * s.rl) {
+        const int row = (int)(e_ % mm), a1 = (int)(e_ / mm);
+        const int xx = row % s.n, a2 = row / s.n;
+        xi[xx + s.n * (a1 + (long long)s.rl * a2)] = Qb[e_];
+    }
+    const AlsSite s0 = SITE(i - 1);
+    double* xp = XC(i - 1);
+    WG_FOR((long long)s0.n * s0.rl * s0.rr) {
+        const long long ab = e_ % ((long long)s0.n * s0.rl);
+        const int c = (int)(e_ / ((long long)s0.n * s0.rl));
+        double a = 0.0;
+        for (int z = 0; z < s0.rr; ++z) a = fma(xp[ab + (long long)s0.n * s0.rl * z], Rb[c + (long long)s.rl * z], a);
+        T1[e_] = a;
+    }
+    __syncthreads();
+    WG_FOR((long long)s0.n * s0.rl * s0.rr) xp[e_] = T1[e_];
+    __syncthreads();
+}
+
 __global__ void __launch_bounds__(TTN_WG) k_als_linsolve(AlsArgs P) {
     extern __shared__ double lds[];
     const int tid = threadIdx.x, b = blockIdx.x + P.train0;
@@ -406,37 +501,10 @@ __global__ void __launch_bounds__(TTN_WG) k_als_linsolve(AlsArgs P) {
     E.A = P.A; E.b = P.b; E.x = P.x; E.tb = b; E.scr = scr; E.off = P.off; E.xr = P.rfix; E.br = br_; E.T1 = T1; E.T2 = T2; E.d = d;
     // H_{i-1} from site i (als.jl:23-26) and Hb_{i-1} (als.jl:42-45)
     auto update_H = [&](int i) {
+        als_update_H_op(E, i);
         const AlsSite s = SITE(i);
-        const double *x = XC(i), *A = AC(i), *Hi = HP(i), *Hbi = HBP(i), *bb = BC(i);
-        double *Ho = HP(i - 1), *Hbo = HBP(i - 1);
-        // T1[z, ph, k, be] = sum_ch H[z, ph, ch] x[k, be, ch]
-        WG_FOR((long long)s.Rr * s.rr * s.n * s.rl) {
-            long long t = e_; const int z = t % s.Rr; t /= s.Rr; const int ph = t % s.rr; t /= s.rr; const int k = t % s.n; const int be = (int)(t / s.n);
-            double a = 0.0;
-            for (int ch = 0; ch < s.rr; ++ch) a = fma(Hi[z + s.Rr * (ph + (long long)s.rr * ch)], x[k + s.n * (be + (long long)s.rl * ch)], a);
-            T1[e_] = a;
-        }
-        __syncthreads();
-        // T2[j, ph, a, be] = sum_{z, k} A[j, k, a, z] T1[z, ph, k, be]
-        WG_FOR((long long)s.n * s.rr * s.Rl * s.rl) {
-            long long t = e_; const int j = t % s.n; t /= s.n; const int ph = t % s.rr; t /= s.rr; const int a_ = t % s.Rl; const int be = (int)(t / s.Rl);
-            double a = 0.0;
-            for (int z = 0; z < s.Rr; ++z)
-                for (int k = 0; k < s.n; ++k)
-                    a = fma(A[j + s.n * (k + s.n * (a_ + (long long)s.Rl * z))], T1[z + s.Rr * (ph + (long long)s.rr * (k + (long long)s.n * be))], a);
-            T2[e_] = a;
-        }
-        __syncthreads();
-        // H_{i-1}[a, al, be] = sum_{j, ph} x[j, al, ph] T2[j, ph, a, be]
-        WG_FOR((long long)s.Rl * s.rl * s.rl) {
-            long long t = e_; const int a_ = t % s.Rl; t /= s.Rl; const int al = t % s.rl; const int be = (int)(t / s.rl);
-            double a = 0.0;
-            for (int ph = 0; ph < s.rr; ++ph)
-                for (int j = 0; j < s.n; ++j)
-                    a = fma(x[j + s.n * (al + (long long)s.rl * ph)], T2[j + s.n * (ph + (long long)s.rr * (a_ + (long long)s.Rl * be))], a);
-            Ho[e_] = a;
-        }
-        __syncthreads();
+        const double *x = XC(i), *Hbi = HBP(i), *bb = BC(i);
+        double *Hbo = HBP(i - 1);
         // Hb: T1[ph, i, be] = sum_ch Hb[ph, ch] b[i, be, ch] ; Hb_{i-1}[al, be] = sum_{i, ph} x[i, al, ph] T1[ph, i, be]
         WG_FOR((long long)s.rr * s.n * s.bl) {
             long long t = e_; const int ph = t % s.rr; t /= s.rr; const int ii = t % s.n; const int be = (int)(t / s.n);
@@ -478,59 +546,15 @@ __global__ void __launch_bounds__(TTN_WG) k_als_linsolve(AlsArgs P) {
     };
 
     // the core move and environment update that follow the local solve of site i (V in Pb): forward half sweep (als.jl:122-135) ...
+    AlsMove Mv;
+    Mv.W = W; Mv.Tm = Tm; Mv.Qb = Qb; Mv.Rb = Rb;
     auto fwd_move = [&](int i) {
-        const AlsSite s = SITE(i);
-        const int mm = s.n * s.rl;
-        WG_FOR((long long)mm * s.rr) Tm[e_] = Pb[e_];
-        __syncthreads();
-        wg_qr_explicit(mm, s.rr, Tm, Qb, Rb, W, lds);                           // right_core_move (als.jl:122-135)
-        double* xi = XC(i);
-        WG_FOR((long long)mm * s.rr) xi[e_] = Qb[e_];
-        // x_{i+1}[a, b, c] = sum_z R[b, z] x_{i+1}[a, z, c]
-        const AlsSite s2 = SITE(i + 1);
-        double* xn = XC(i + 1);
-        WG_FOR((long long)s2.n * s2.rl * s2.rr) {
-            long long t = e_; const int a_ = t % s2.n; t /= s2.n; const int bq = t % s2.rl; const int c = (int)(t / s2.rl);
-            double a = 0.0;
-            for (int z = 0; z < s2.rl; ++z) a = fma(Rb[bq + (long long)s.rr * z], xn[a_ + s2.n * (z + (long long)s2.rl * c)], a);
-            T1[e_] = a;
-        }
-        __syncthreads();
-        WG_FOR((long long)s2.n * s2.rl * s2.rr) xn[e_] = T1[e_];
-        __syncthreads();
+        als_right_core_move(E, Mv, Pb, i, lds);
         als_update_G(E, i);
     };
     // ... and backward half sweep (als.jl:102-120)
     auto bwd_move = [&](int i) {
-        const AlsSite s = SITE(i);
-        const int mm = s.n * s.rr;
-        // M[(x + n*a2), a1] = V[x, a1, a2]                                      left_core_move (als.jl:102-120)
-        WG_FOR((long long)mm * s.rl) {
-            const int row = (int)(e_ % mm), a1 = (int)(e_ / mm);
-            const int xx = row % s.n, a2 = row / s.n;
-            Tm[e_] = Pb[xx + s.n * (a1 + (long long)s.rl * a2)];
-        }
-        __syncthreads();
-        wg_qr_explicit(mm, s.rl, Tm, Qb, Rb, W, lds);
-        double* xi = XC(i);
-        WG_FOR((long long)mm * s.rl) {
-            const int row = (int)(e_ % mm), a1 = (int)(e_ / mm);
-            const int xx = row % s.n, a2 = row / s.n;
-            xi[xx + s.n * (a1 + (long long)s.rl * a2)] = Qb[e_];
-        }
-        // x_{i-1}[a, b, c] = sum_z x_{i-1}[a, b, z] R[c, z]
-        const AlsSite s0 = SITE(i - 1);
-        double* xp = XC(i - 1);
-        WG_FOR((long long)s0.n * s0.rl * s0.rr) {
-            const long long ab = e_ % ((long long)s0.n * s0.rl);
-            const int c = (int)(e_ / ((long long)s0.n * s0.rl));
-            double a = 0.0;
-            for (int z = 0; z < s0.rr; ++z) a = fma(xp[ab + (long long)s0.n * s0.rl * z], Rb[c + (long long)s.rl * z], a);
-            T1[e_] = a;
-        }
-        __syncthreads();
-        WG_FOR((long long)s0.n * s0.rl * s0.rr) xp[e_] = T1[e_];
-        __syncthreads();
+        als_left_core_move(E, Mv, Pb, i, lds);
         update_H(i);
     };
 

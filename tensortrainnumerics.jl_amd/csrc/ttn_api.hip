@@ -11,6 +11,7 @@
 #include "ttn_als_kernels.h"
 #include "ttn_als_grid.h"
 #include "ttn_eigsolve_kernels.h"
+#include "ttn_als_eig_kernels.h"
 #include "ttn_eig_kernels.h"
 #include "ttn_tdvp_kernels.h"
 #include "ttn_densefact_kernels.h"
@@ -91,8 +92,9 @@ DevBuf g_lu_flag;          // singular-pivot word of the grid form of als_linsol
 DevBuf g_cg_iters;         // [batch] CG iterations of the last two-site linear solve
 DevBuf g_hist_E, g_hist_r; // [batch][hist_len] energy / rank history of the last two-site eigensolve
 DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-site eigensolve
+DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
 DevBuf* const g_bufs[] = {&g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
-                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res};
+                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -175,6 +177,8 @@ int ttn_init(int device) {
         {(const void*)k_mals_linsolve, COMPRESS_LDS_BYTES},
         {(const void*)k_als_linsolve, COMPRESS_LDS_BYTES},
         {(const void*)k_two_site_eig, COMPRESS_LDS_BYTES},
+        {(const void*)k_als_eig, COMPRESS_LDS_BYTES},
+        {(const void*)k_increase_ranks, COMPRESS_LDS_BYTES},
         {(const void*)k_ttv_decomp, COMPRESS_LDS_BYTES},
         {(const void*)k_swap_chain, COMPRESS_LDS_BYTES},
         {(const void*)k_orthogonalize, ORTHO_LDS_BYTES},
@@ -1290,7 +1294,7 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
 const struct { int code, err; const char* msg; } status_table[] = {
     {TTN_ST_LANCZOS, TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol"},
     {TTN_ST_NONFINITE, TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)"},
-    {TTN_ST_SINGULAR, TTN_ERR_SINGULAR, "als_linsolve: a local system K is singular"},
+    {TTN_ST_SINGULAR, TTN_ERR_SINGULAR, "a local system K is singular (als_linsolve), or a local metric S_s is not positive definite (als_gen_eigsolv)"},
     {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "als_linsolve: a train's ranks differ from the ranks of the start handle"},
     {TTN_ST_RANK_OVERFLOW, TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)"},
     {TTN_ST_JACOBI, TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit"},
@@ -1547,11 +1551,12 @@ int ttn_dmrg_cg_iterations(int64_t batch, int64_t* iters) {
 static std::vector<int> g_lz_iters_host;       // Lanczos operator applications per train of the last eigensolve (ttn_eigsolve_stats)
 static std::vector<double> g_lz_res_host;      // largest final Lanczos residual per train of the last eigensolve
 
+// mode 0 MALS, 1 DMRG (N = 2), 2 ALS (als_eigsolve / als_gen_eigsolv: 2 (d - 1) micro-steps per full sweep, like MALS)
 static int64_t eig_hist_len(int mode, int64_t d, int64_t nsweeps) { return mode == 1 ? 2 * (d - 2) * nsweeps + 1 : 2 * (d - 1) * nsweeps; }
 
 int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_t* sweep_schedule, int64_t* len) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!len || (mode != 0 && mode != 1) || d < 2) return fail(TTN_ERR_ARG, "ttn_eigsolve_history_len: bad mode / d / len");
+    if (!len || mode < 0 || mode > 2 || d < 2) return fail(TTN_ERR_ARG, "ttn_eigsolve_history_len: bad mode / d / len");
     std::vector<int64_t> plan;
     const int rc = sweep_plan("ttn_eigsolve_history_len", TTN_ERR_ARG, n_stages, sweep_schedule, nullptr, plan);
     if (rc) return rc;
@@ -2242,5 +2247,194 @@ int ttn_bond_truncate_f64(int64_t d, const int64_t* dims, double* const* cores, 
     if (k < 1 || k >= d) return fail(TTN_ERR_BOND_INDEX, "k must be in 1:(N-1)");
     return compress_host(d, dims, cores, rks, k, max_bond, truncerr, 1);
 }
+
+// ---- als_eigsolve / als_gen_eigsolv (csrc/ttn_als_eig_kernels.h) ---------------------------------------------------------------
+// The host walks the stages of the schedule (als.jl:284-300, :370-397): k_als_eig runs a stage's full sweeps at fixed ranks, writing
+// its part of the history; between stages k_increase_ranks pads x into a temporary handle of x's capacity at the ranks
+// r_and_d_to_rks(fill(rmax)) and ttn_orthogonalize brings it back into x (it does not allow aliasing).  The environments of every
+// stage are rebuilt from the re-orthogonalised train — for als_gen_eigsolv too, where the reference zero-pads the stale right
+// environments instead (als.jl:379-396), which leaves the first solves of a new stage with a singular metric.
+static int als_eig_impl(int gen, ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, const int64_t* sweep_schedule,
+                        const int64_t* rmax_schedule, const double* noise_schedule, int64_t seed, int it_solver, int64_t maxiter,
+                        double linsolv_tol, int64_t itslv_thresh, int64_t hist_len, double* E_out) {
+    const char* who = gen ? "als_gen_eigsolv" : "als_eigsolve";
+    auto err = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
+    NEED_INIT();
+    if (!A || !x0 || !x || (gen && !S)) return err(TTN_ERR_ARG, "null handle");
+    if (!rmax_schedule || (hist_len > 0 && !E_out)) return err(TTN_ERR_ARG, "null schedule / history buffer");
+    if (!same_dims(A->dims, x0->dims) || !same_dims(x0->dims, x->dims) || (gen && !same_dims(S->dims, x0->dims)))
+        return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->batch != x0->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    const int d = x0->d;
+    if (d < 2) return err(TTN_ERR_UNSUPPORTED, "needs at least two sites");
+    if (maxiter < 1 || !(linsolv_tol >= 0.0) || itslv_thresh < 0) return err(TTN_ERR_ARG, "bad maxiter / linsolv_tol / itslv_thresh");
+    std::vector<int64_t> plan;
+    int rc = sweep_plan(who, TTN_ERR_ARG, n_stages, sweep_schedule, rmax_schedule, plan);
+    if (rc) return rc;
+    const int64_t per = 2 * (int64_t)(d - 1);
+    if (hist_len != per * (int64_t)plan.size()) return err(TTN_ERR_ARG, "hist_len differs from ttn_eigsolve_history_len");
+    if (noise_schedule)
+        for (int64_t j = 0; j < n_stages; ++j) if (!(noise_schedule[j] >= 0.0 || noise_schedule[j] < 0.0)) return err(TTN_ERR_ARG, "noise_schedule is not finite");
+    // ---- every check before anything is launched ----
+    const std::vector<int64_t>& r0 = x0->bound;
+    {
+        std::vector<int64_t> capped(d + 1);
+        ttn_r_and_d_to_rks(d, x0->dims.data(), d + 1, r0.data(), 1024, capped.data());
+        for (int k = 0; k <= d; ++k) if (capped[k] != r0[k]) return err(TTN_ERR_UNSUPPORTED, "the start ranks exceed what orthogonalize keeps");
+        for (int i = 0; i < d; ++i)
+            if (x0->dims[i] * r0[i] < r0[i + 1] || x0->dims[i] * r0[i + 1] < r0[i]) return err(TTN_ERR_UNSUPPORTED, "a core is too flat for the QR core moves");
+    }
+    std::vector<std::vector<int64_t>> stage_rks(n_stages);            // ranks of every stage after its rank increase (stage 0: the start)
+    stage_rks[0] = r0;
+    for (int64_t j = 1; j < n_stages; ++j) {
+        const int64_t top = *std::max_element(stage_rks[j - 1].begin(), stage_rks[j - 1].end());
+        if (rmax_schedule[j] <= top) return err(TTN_ERR_ARG, "New bond dimension too low (a stage's rmax must exceed the current maximum rank)");
+        std::vector<int64_t> fill(d + 1, rmax_schedule[j]);
+        fill[0] = 1; fill[d] = 1;
+        stage_rks[j].assign(d + 1, 1);
+        ttn_r_and_d_to_rks(d, x0->dims.data(), d + 1, fill.data(), rmax_schedule[j], stage_rks[j].data());
+    }
+    std::vector<int64_t> rl(d + 1, 1);                                 // the largest rank any stage holds: the slot sizes
+    for (const auto& v : stage_rks) for (int k = 0; k <= d; ++k) rl[k] = std::max(rl[k], v[k]);
+    for (int k = 0; k <= d; ++k) if (x->cap[k] < rl[k]) return err(TTN_ERR_CAPACITY, "the rank capacity of x is below the ranks of a stage");
+    const std::vector<int64_t>& RA = A->rks;
+    const std::vector<int64_t>& RS = gen ? S->rks : A->rks;
+    long long cur = 0, Nmax = 1, mmax = 1, cmax = 1, t1 = 1, t2 = 1, Rzmax = 1;
+    std::vector<long long> off(4 * d, 0);
+    for (int i = 0; i < d; ++i) {
+        const long long n = x0->dims[i], a = rl[i], c = rl[i + 1];
+        off[i] = cur; cur += n * a * n * a * RA[i + 1];
+        if (gen) { off[d + i] = cur; cur += n * a * n * a * RS[i + 1]; }
+        off[2 * d + i] = cur; cur += RA[i + 1] * c * c;
+        if (gen) { off[3 * d + i] = cur; cur += RS[i + 1] * c * c; }
+        Nmax = std::max(Nmax, n * a * c);
+        mmax = std::max(mmax, std::max(n * a, n * c));
+        cmax = std::max(cmax, std::max(a, c));
+        for (const std::vector<int64_t>* R : {&RA, &RS}) {
+            const long long Rl = (*R)[i], Rr = (*R)[i + 1];
+            t1 = std::max(t1, n * a * c * std::max<long long>(Rr, 1));
+            t2 = std::max(t2, std::max(c * c * Rr, n * c * Rl * a));
+            Rzmax = std::max(Rzmax, Rr);
+        }
+    }
+    if (Nmax > 65536) return err(TTN_ERR_UNSUPPORTED, "local problems above 65 536 unknowns (n_i r_{i-1} r_i) are not supported");
+    // branch rule: standard dense unless N > 2048 or (it_solver and N > itslv_thresh) (als.jl:74); generalized dense only when !it_solver
+    // and N <= min(itslv_thresh, 2048) (als.jl:95)
+    const long long dense_cap = TTN_DENSE_LOCAL_MAX_ALS;
+    const long long it_above = gen ? (it_solver ? 0 : std::min<long long>(itslv_thresh, dense_cap))
+                                   : (it_solver ? std::min<long long>(itslv_thresh, dense_cap) : dense_cap);
+    const bool need_it = Nmax > it_above;
+    const long long Kdim = std::min<long long>(Nmax, it_above);
+    AlsEigArgs Rg;
+    memset(&Rg, 0, sizeof(Rg));
+    Rg.offK = cur; cur += Kdim * Kdim;
+    Rg.offK2 = cur; if (gen) cur += Kdim * Kdim;
+    Rg.offEig = cur; cur += 8 + 8 * Kdim;
+    Rg.offPb = cur; cur += Nmax;
+    Rg.offIt = cur;
+    if (need_it) { Rg.it_nmax = Nmax; cur += gen ? (9 + Rzmax) * Nmax + 64 : (TTN_LZ_M + 1 + TTN_LZ_KEEP + Rzmax) * Nmax + 5000; }
+    Rg.offT1 = cur; cur += t1;
+    Rg.offT2 = cur; cur += t2;
+    Rg.offTm = cur; cur += mmax * cmax;
+    Rg.offQb = cur; cur += mmax * cmax;
+    Rg.offRb = cur; cur += cmax * cmax;
+    Rg.offVb = cur; cur += QR_NB * mmax;
+    Rg.offWb = cur; cur += QR_NB * mmax;
+    Rg.offTst = cur; cur += ((cmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64;
+    const long long per_train = cur;
+    const int batch = x->batch;
+    const size_t need = sizeof(double) * (size_t)per_train * batch;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        if (need > g_scratch.bytes && need - g_scratch.bytes > free_b)
+            return err(TTN_ERR_CAPACITY, "the workspace of this capacity and batch (environments, dense local matrices, iterative basis) does not fit in device memory");
+    }
+    // ---- the solve ----
+    rc = ttn_orthogonalize(x0, 1, x);                                  // als.jl:264, :350
+    if (rc) return rc;
+    const size_t hn = (size_t)batch * (size_t)std::max<int64_t>(hist_len, 1);
+    if ((rc = g_hist_E.ensure(sizeof(double) * hn)) || (rc = g_lz_iters.ensure(sizeof(int) * batch)) || (rc = g_lz_res.ensure(sizeof(double) * batch)) ||
+        (rc = g_als_tab.ensure(sizeof(long long) * (4 * (size_t)d + d + 1))))
+        return rc;
+    HIPCHK(hipMemsetAsync(g_lz_iters.p, 0, sizeof(int) * batch, g_stream));
+    HIPCHK(hipMemsetAsync(g_lz_res.p, 0, sizeof(double) * batch, g_stream));
+    HIPCHK(hipMemsetAsync(x->d_status, 0, sizeof(int) * batch, g_stream));
+    long long* d_off = g_als_tab.as<long long>();
+    long long* d_rn = d_off + 4 * d;
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));                            // off is a local
+    Rg.A = A->dev(); Rg.S = gen ? S->dev() : A->dev();
+    Rg.gen = gen;
+    Rg.off = d_off;
+    Rg.it_above = (int)it_above;
+    Rg.lz_maxrestart = (int)std::min<int64_t>(maxiter, 1 << 30);
+    Rg.lz_tol = linsolv_tol;
+    Rg.status = x->d_status;
+    Rg.hist_E = g_hist_E.as<double>(); Rg.hist_len = (int)hist_len;
+    Rg.it_count = g_lz_iters.as<int>(); Rg.it_res = g_lz_res.as<double>();
+    TmpTT tmp;
+    if (n_stages > 1 && (rc = ttn_tt_create(d, x->dims.data(), x->cap.data(), batch, &tmp.h))) return rc;
+    int64_t hoff = 0;
+    for (int64_t j = 0; j < n_stages; ++j) {
+        if (j > 0) {                                                   // increase_ranks -> orthogonalize (als.jl:291-292, :377-378)
+            if ((rc = g_scratch.ensure(need))) return rc;
+            HIPCHK(hipMemcpyAsync(d_rn, stage_rks[j].data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
+            IncArgs Ia;
+            memset(&Ia, 0, sizeof(Ia));
+            Ia.x = x->dev(); Ia.y = tmp.h->dev(); Ia.rn = d_rn;
+            Ia.noise = noise_schedule ? noise_schedule[j] : 0.0;
+            Ia.seed = seed;
+            Ia.scratch = g_scratch.as<double>(); Ia.scratch_stride = per_train;
+            Ia.offTm = Rg.offTm; Ia.offQb = Rg.offQb; Ia.offRb = Rg.offRb; Ia.offVb = Rg.offVb; Ia.offWb = Rg.offWb; Ia.offTst = Rg.offTst;
+            hipLaunchKernelGGL(k_increase_ranks, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Ia);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(g_stream));                    // stage_rks is the host's until the copy is done
+            tmp.h->bound = stage_rks[j];
+            std::fill(tmp.h->ot.begin(), tmp.h->ot.end(), 0);
+            if ((rc = ttn_orthogonalize(tmp.h, 1, x))) return rc;
+        }
+        const int64_t nsw = sweep_schedule[j] - (j ? sweep_schedule[j - 1] : 1);
+        if (nsw > 0) {
+            if ((rc = g_scratch.ensure(need))) return rc;              // ttn_orthogonalize shares the workspace: taken again every stage
+            Rg.x = x->dev();
+            Rg.scratch = g_scratch.as<double>(); Rg.scratch_stride = per_train;
+            Rg.nsweeps = (int)nsw;
+            Rg.hist_off = (int)hoff;
+            hipLaunchKernelGGL(k_als_eig, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Rg);
+            HIPCHK(hipGetLastError());
+            hoff += nsw * per;
+        }
+    }
+    g_lz_iters_host.assign(batch, 0);
+    g_lz_res_host.assign(batch, 0.0);
+    if (hist_len > 0) HIPCHK(hipMemcpyAsync(E_out, g_hist_E.p, sizeof(double) * (size_t)batch * hist_len, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(g_lz_iters_host.data(), g_lz_iters.p, sizeof(int) * batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(g_lz_res_host.data(), g_lz_res.p, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
+    unsigned seen = 0;
+    rc = take_status(x, seen);                                         // synchronises the copies above too
+    if (rc) return rc;
+    // gauge flags: after a backward half sweep x_1 carries the norm, the others are right-orthogonal (als.jl:112-118)
+    if (!plan.empty())
+        for (int bb = 0; bb < batch; ++bb)
+            for (int k = 0; k < d; ++k) x->ot[(size_t)bb * d + k] = (k == 0) ? 0 : 1;
+    return status_error(seen, who);
+}
+
+int ttn_als_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, const int64_t* sweep_schedule, const int64_t* rmax_schedule,
+                     const double* noise_schedule, int64_t seed, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                     int64_t hist_len, double* E) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return als_eig_impl(0, A, nullptr, x0, x, n_stages, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter, linsolv_tol,
+                        itslv_thresh, hist_len, E);
+}
+
+int ttn_als_gen_eigsolve(ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, const int64_t* sweep_schedule,
+                         const int64_t* rmax_schedule, int it_solver, int64_t itslv_thresh, int64_t hist_len, double* E) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return als_eig_impl(1, A, S, x0, x, n_stages, sweep_schedule, rmax_schedule, nullptr, 0, it_solver, 1, TTN_LOBPCG_TOL, itslv_thresh,
+                        hist_len, E);
+}
+
 
 }  // extern "C"

@@ -635,3 +635,122 @@ def mals_eigsolve(A: TToperator, tt_start: TTvector, tol: float = 1.0e-12, sweep
                   linsolv_tol: float | None = None, itslv_thresh: int = 256):
     """(E, x, r_hist) = mals_eigsolve(A, tt_start; ...) (src/solvers/mals.jl:335-425); rmax_schedule defaults to round(sqrt(prod(dims)))."""
     return _eig_host(0, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# als_eigsolve (src/solvers/als.jl:251-326) and als_gen_eigsolv (src/solvers/als.jl:344-426) — csrc/ttn_als_eig_kernels.h
+# ---------------------------------------------------------------------------------------------------------------------
+def _rd_rks(rks, dims, rmax: int = 1024):
+    """r_and_d_to_rks (src/tt_tools.jl) on the host: rank k is capped by prod(dims[:k]), prod(dims[k:]) and rmax."""
+    return [min(int(r), math.prod(dims[:k]), math.prod(dims[k:]), int(rmax)) if 0 < k < len(dims) else 1 for k, r in enumerate(rks)]
+
+
+def _als_stages(who, dims, start_rks, sweep_schedule, rmax_schedule, noise_schedule=None):
+    """Every refusal of the schedule and the start train, on the host: (ss, rs, ns, ranks of every stage)."""
+    ss = [int(v) for v in sweep_schedule]
+    rs = [int(min(v, 2 ** 30)) for v in rmax_schedule]
+    ns = [float(v) for v in noise_schedule] if noise_schedule is not None else [0.0] * len(rs)
+    if not (len(rs) == len(ss) == len(ns)):
+        raise _lib.TTNError(f"{who}: Sweep schedule error (the schedules differ in length)")            # als.jl:263
+    if not ss or any(v < 1 for v in ss) or any(b <= a for a, b in zip(ss, ss[1:])) or any(v < 1 for v in rs):
+        raise _lib.TTNError(f"{who}: sweep_schedule must be positive and strictly increasing, rmax_schedule positive")
+    if not all(math.isfinite(v) for v in ns):
+        raise _lib.TTNError(f"{who}: noise_schedule is not finite")
+    if ss[-1] - 1 > 32:
+        raise _lib.TTNError(f"{who}: more than 32 sweeps in one call")
+    d = len(dims)
+    if d < 2:
+        raise _lib.TTNError(f"{who}: needs at least two sites")
+    r0 = [int(v) for v in start_rks]
+    if _rd_rks(r0, dims) != r0:
+        raise _lib.TTNError(f"{who}: the start ranks exceed what orthogonalize keeps")
+    if any(dims[i] * r0[i] < r0[i + 1] or dims[i] * r0[i + 1] < r0[i] for i in range(d)):
+        raise _lib.TTNError(f"{who}: a core is too flat for the QR core moves")
+    stages = [r0]
+    for j in range(1, len(ss)):
+        if rs[j] <= max(stages[-1]):
+            raise _lib.TTNError(f"{who}: New bond dimension too low (a stage's rmax must exceed the current maximum rank)")   # tt_tools.jl:478
+        stages.append(_rd_rks([1] + [rs[j]] * (d - 1) + [1], dims, rs[j]))
+    return ss, rs, ns, stages
+
+
+def als_capacity(dims, start_rks, sweep_schedule=(2,), rmax_schedule=None):
+    """Rank capacity x needs for a schedule: the largest rank of any stage at every bond."""
+    if rmax_schedule is None:
+        rmax_schedule = (max(start_rks),)
+    _, _, _, stages = _als_stages("als_capacity", list(dims), start_rks, sweep_schedule, rmax_schedule)
+    return [max(s[k] for s in stages) for k in range(len(dims) + 1)]
+
+
+def _als_eig_run(gen, A: DeviceTTO, S, x0: DeviceTT, x: DeviceTT, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter,
+                 linsolv_tol, itslv_thresh):
+    who = "als_gen_eigsolv" if gen else "als_eigsolve"
+    if rmax_schedule is None:
+        rmax_schedule = (max(x0.max_ranks()),)
+    ss = [int(v) for v in sweep_schedule]
+    rs = [int(min(v, 2 ** 30)) for v in rmax_schedule]
+    ns = [float(v) for v in noise_schedule] if noise_schedule is not None else [0.0] * len(rs)
+    if not (len(rs) == len(ss) == len(ns)):
+        raise _lib.TTNError(f"{who}: Sweep schedule error (the schedules differ in length)")
+    hl = eigsolve_history_len(2, len(x0.dims), ss) if ss else 0
+    B = x0.batch
+    E = np.zeros((B, max(hl, 1)))
+    n = len(ss)
+    arr = C.c_int64 * max(n, 1)
+    nrr = C.c_double * max(n, 1)
+    if gen:
+        _lib.check(_lib.lib().ttn_als_gen_eigsolve(A.h, S.h, x0.h, x.h, n, arr(*ss), arr(*rs), 1 if it_solver else 0, int(itslv_thresh), hl,
+                                                   E.ctypes.data_as(_lib.p_f64)))
+    else:
+        _lib.check(_lib.lib().ttn_als_eigsolve(A.h, x0.h, x.h, n, arr(*ss), arr(*rs), nrr(*ns), int(seed), 1 if it_solver else 0, int(maxiter),
+                                               float(linsolv_tol), int(itslv_thresh), hl, E.ctypes.data_as(_lib.p_f64)))
+    return [list(map(float, E[b, :hl])) for b in range(B)]
+
+
+def als_eigsolve_(A: DeviceTTO, x0: DeviceTT, x: DeviceTT, sweep_schedule: Sequence[int] = (2,), rmax_schedule: Sequence[int] | None = None,
+                  noise_schedule: Sequence[float] | None = None, it_solver: bool = False, itslv_thresh: int = 1024, maxiter: int = 200,
+                  linsolv_tol: float = 1.0e-8, seed: int = 0):
+    """E_b of als_eigsolve(A, x0_b; ...) for every train of the batch; x receives the eigenvectors (its capacity must hold the ranks of
+    every stage: als_capacity).  rmax_schedule defaults to [max rank of x0], noise_schedule to zeros."""
+    return _als_eig_run(0, A, None, x0, x, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter, linsolv_tol, itslv_thresh)
+
+
+def als_gen_eigsolv_(A: DeviceTTO, S: DeviceTTO, x0: DeviceTT, x: DeviceTT, sweep_schedule: Sequence[int] = (2,),
+                     rmax_schedule: Sequence[int] | None = None, tol: float = 1.0e-10, it_solver: bool = False, itslv_thresh: int = 2500):
+    """E_b of als_gen_eigsolv(A, S, x0_b; ...) for every train of the batch.  `tol` is accepted and unused, as in the reference."""
+    return _als_eig_run(1, A, S, x0, x, sweep_schedule, rmax_schedule, None, 0, it_solver, 1, 1.0e-8, itslv_thresh)
+
+
+def _als_host(gen, A: TToperator, S, tt_start: TTvector, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter, linsolv_tol,
+              itslv_thresh):
+    who = "als_gen_eigsolv" if gen else "als_eigsolve"
+    dims = tuple(tt_start.ttv_dims)
+    if rmax_schedule is None:
+        rmax_schedule = (max(tt_start.ttv_rks),)                                  # als.jl:254, :344
+    if noise_schedule is None:
+        noise_schedule = (0.0,) * len(rmax_schedule)                              # als.jl:255
+    ss, rs, ns, stages = _als_stages(who, dims, tt_start.ttv_rks, sweep_schedule, rmax_schedule, noise_schedule)
+    cap = [max(s[k] for s in stages) for k in range(len(dims) + 1)]
+    dA = DeviceTTO(A)
+    dS = DeviceTTO(S) if gen else None
+    dx0 = DeviceTT.from_host(tt_start)
+    dx = DeviceTT(dims, cap)
+    E = _als_eig_run(gen, dA, dS, dx0, dx, ss, rs, ns, seed, it_solver, maxiter, linsolv_tol, itslv_thresh)
+    dx.max_ranks()
+    return E[0], dx.download(0)
+
+
+def als_eigsolve(A: TToperator, tt_start: TTvector, sweep_schedule: Sequence[int] = (2,), rmax_schedule: Sequence[int] | None = None,
+                 noise_schedule: Sequence[float] | None = None, it_solver: bool = False, itslv_thresh: int = 1024, maxiter: int = 200,
+                 linsolv_tol: float = 1.0e-8, seed: int = 0):
+    """(E, x) = als_eigsolve(A, tt_start; ...) (src/solvers/als.jl:251-326) with the reference's keywords and defaults: E the eigenvalue of
+    every micro-step, x the normalised eigenvector train.  The noise of a rank increase is seeded (`seed`) instead of drawn from the
+    global random stream."""
+    return _als_host(0, A, None, tt_start, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter, linsolv_tol, itslv_thresh)
+
+
+def als_gen_eigsolv(A: TToperator, S: TToperator, tt_start: TTvector, sweep_schedule: Sequence[int] = (2,),
+                    rmax_schedule: Sequence[int] | None = None, tol: float = 1.0e-10, it_solver: bool = False, itslv_thresh: int = 2500):
+    """(E, x) = als_gen_eigsolv(A, S, tt_start; ...) (src/solvers/als.jl:344-426): the smallest eigenpair of A x = lambda S x, x
+    S-normalised.  `tol` is accepted and unused, as in the reference (als.jl:344)."""
+    return _als_host(1, A, S, tt_start, sweep_schedule, rmax_schedule, None, 0, it_solver, 1, 1.0e-8, itslv_thresh)
