@@ -282,6 +282,28 @@ int ttn_tdvp_contract_f64(int op, int cplx, int64_t batch, const int64_t* dims7,
 int ttn_dense_qr(int cplx, int64_t m, int64_t n, double* A, double* Q, double* R);
 int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* s, double* Vh);
 
+/* --- TT-cross interpolation (src/tt_cross_interpolation.jl: tt_cross, tt_integrate), csrc/ttn_cross_kernels.h.  DEVICE pointers, the
+ * library's stream, Float64 (cplx = 0) or ComplexF64 (cplx = 1, interleaved), column-major matrices, int64 indices 1-based.
+ * ttn_cross_maxvol: maxvol!(A, tol, maxiter) on one m x r matrix, r <= m: initial rows by LU with partial pivoting (getrf's choice),
+ *   then swaps at the largest |C_ij| (ties: the smallest column-major index) while it exceeds tol, at most maxiter of them, C kept by
+ *   Sherman-Morrison updates.  piv (r): the pivot rows in column order; C (m x r) = A / A[piv,:] computed again from scratch (LU solve
+ *   with the r x r block).  dinfo (device, 2 words; may be null: library memory) receives {0 or TTN_ERR_SINGULAR, swaps}; with a
+ *   HOST hinfo the call synchronises, copies them there and returns TTN_ERR_SINGULAR on a zero pivot; without it the call is
+ *   asynchronous.  piv always holds rows of A.  Limits: r <= 1024, m <= 2^20 (TTN_ERR_UNSUPPORTED before any launch).
+ * ttn_cross_points: the P x N index matrix of a fibre (mode 0: _build_fiber_indices of site `site`, i fastest, then r_left, then
+ *   r_right; L rl x (site-1), R rr x (N-site)), of a superblock (mode 1: _sample_superblock of sites site, site+1, r_l fastest, then
+ *   i1, i2, r_g; L rl x (site-1), R rr x (N-site-1)) or a given one (mode 2: idx_in); into idx_out and / or the coordinates X (P x N)
+ *   gathered from the domain arrays concatenated in dom at offsets doff (N + 1, device); asynchronous.
+ * ttn_cross_eval: _evaluate_tt (idx, P x N) or _contract_with_weights (w: the weight vectors concatenated, P = 1) of the train whose
+ *   cores (n_k x r_{k-1} x r_k, device pointers in a HOST array) and dims / ranks (HOST) are given, ranks <= 1024; out (P).  With
+ *   yref, err[0] (device) = ||yref - out|| / max(||yref||, tol).  Synchronises (its core table is uploaded from the host). */
+int ttn_cross_maxvol(int cplx, int64_t m, int64_t r, const double* A, double tol, int64_t maxiter, int64_t* piv, double* C, int64_t* dinfo,
+                     int64_t* hinfo);
+int ttn_cross_points(int cplx, int mode, int64_t N, int64_t site, int64_t n1, int64_t n2, int64_t rl, int64_t rr, const int64_t* L,
+                     const int64_t* R, const int64_t* idx_in, int64_t P, const int64_t* doff, const double* dom, int64_t* idx_out, double* X);
+int ttn_cross_eval(int cplx, int64_t N, int64_t P, const double* const* cores, const int64_t* dims, const int64_t* rks, const int64_t* idx,
+                   const double* w, double* out, const double* yref, double tol, double* err);
+
 /* fused convenience for the benchmark op  tt_compress!(A*x, max_bond)  (src/solvers/euler.jl:55) */
 int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, double truncerr, int64_t sweeps);
 

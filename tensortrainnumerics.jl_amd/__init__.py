@@ -4,10 +4,11 @@ Host-side mirror of the reference interface (tt.py), input generators (construct
 device-resident batched handles (device.py) and the ctypes binding of the C ABI (_lib.py).
 The arithmetic lives in csrc/*.h, csrc/ttn_api.hip -> libttn_hip.so (hand-written HIP, gfx950).
 """
-from . import _lib, constructors, device, pipeline, qtt, shard, solvers, tdvp, tt
+from . import _lib, constructors, cross, device, pipeline, qtt, shard, solvers, tdvp, tt
 from ._lib import TTNError, build, ensure_init, finalize
 from .constructors import (Delta, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn, qtt_cos, qtt_exp, qtt_sin, qtt_to_vector, rand_tt,
                            shift, toeplitz_to_qtto, xxx_tto, xxz_tto, zeros_tt, zeros_tto)
+from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_integrate
 from .device import DeviceTT, DeviceTTO, StreamTimer
 from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, ttv_decomp

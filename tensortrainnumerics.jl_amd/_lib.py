@@ -93,6 +93,11 @@ SIGNATURES = {
     "ttn_tdvp_apply_h2": (C.c_int, [C.c_int, i64, i64, i64, i64, i64, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ttn_dense_qr": (C.c_int, [C.c_int, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ttn_dense_svd": (C.c_int, [C.c_int, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ttn_cross_maxvol": (C.c_int, [C.c_int, i64, i64, C.c_void_p, C.c_double, i64, C.c_void_p, C.c_void_p, C.c_void_p, p_i64]),
+    "ttn_cross_points": (C.c_int, [C.c_int, C.c_int, i64, i64, i64, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ttn_cross_eval": (C.c_int, [C.c_int, i64, i64, pp_f64, p_i64, p_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                 C.c_void_p]),
     "ttn_tdvp_contract_f64": (C.c_int, [C.c_int, C.c_int, i64, p_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ttn_selftest_eig128": (C.c_int, [C.c_void_p, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ttn_selftest_sym_eig": (C.c_int, [i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),

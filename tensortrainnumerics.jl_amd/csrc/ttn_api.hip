@@ -15,6 +15,7 @@
 #include "ttn_eig_kernels.h"
 #include "ttn_tdvp_kernels.h"
 #include "ttn_densefact_kernels.h"
+#include "ttn_cross_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -93,8 +94,10 @@ DevBuf g_cg_iters;         // [batch] CG iterations of the last two-site linear 
 DevBuf g_hist_E, g_hist_r; // [batch][hist_len] energy / rank history of the last two-site eigensolve
 DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-site eigensolve
 DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
+DevBuf g_cross_tab;        // core table of ttn_cross_eval
+DevBuf g_cross_info;       // status words of a ttn_cross_maxvol called without a device info
 DevBuf* const g_bufs[] = {&g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
-                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab};
+                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab, &g_cross_tab, &g_cross_info};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -188,6 +191,8 @@ int ttn_init(int device) {
         {(const void*)k_tdvp, TDVP_LDS_BYTES},
         {(const void*)k_lu_panel, LU_PANEL_LDS_BYTES},
         {(const void*)k_lu_trail, sizeof(double) * GEMM_LDS_TOTAL},
+        {(const void*)k_cross_maxvol<false>, TTN_XV_LDS_BYTES},
+        {(const void*)k_cross_maxvol<true>, TTN_XV_LDS_BYTES},
     };
     for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
@@ -2058,6 +2063,105 @@ int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* 
     HIPCHK(hipMemcpyAsync(&flag, iw + n, sizeof(int), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     if (flag) return fail(TTN_ERR_NO_CONVERGENCE, "ttn_dense_svd: the Jacobi sweeps did not converge");
+    return TTN_OK;
+}
+
+// ---- TT-cross (csrc/ttn_cross_kernels.h) --------------------------------------------------------------------------------------
+int ttn_cross_maxvol(int cplx, int64_t m, int64_t r, const double* A, double tol, int64_t maxiter, int64_t* piv, double* C, int64_t* dinfo,
+                     int64_t* hinfo) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !piv || !C || m < 1 || r < 1 || maxiter < 0) return fail(TTN_ERR_ARG, "ttn_cross_maxvol: bad argument");
+    if (m < r) return fail(TTN_ERR_ARG, "ttn_cross_maxvol: need m >= r");
+    if (r > TTN_XV_MAX_R || m > TTN_XV_MAX_M) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_maxvol: need r <= 1024 and m <= 2^20");
+    const size_t w = cplx ? 2 : 1, cbytes = sizeof(double) * w * (size_t)m * (size_t)r;
+    const int use_lds = cbytes <= TTN_XV_LDS_C ? 1 : 0;
+    const size_t wbytes = use_lds ? 0 : cbytes;
+    int rc = g_scratch.ensure(wbytes + sizeof(int) * (size_t)m + 64);
+    if (rc) return rc;
+    if (!dinfo) {
+        if ((rc = g_cross_info.ensure(sizeof(int64_t) * 2))) return rc;
+        dinfo = g_cross_info.as<int64_t>();
+    }
+    double* Cw = g_scratch.as<double>();
+    int* perm = reinterpret_cast<int*>(reinterpret_cast<char*>(g_scratch.p) + wbytes);
+    const size_t lds = (use_lds ? cbytes : 0) + sizeof(double) * w * (size_t)r + sizeof(int) * (size_t)r;
+    const int mi = (int)std::min<int64_t>(maxiter, 1 << 30);
+    if (cplx)
+        hipLaunchKernelGGL(k_cross_maxvol<true>, dim3(1), dim3(TTN_XV_WG), lds, g_stream, (int)m, (int)r, A, tol, mi, (long long*)piv, C, Cw, perm,
+                           (long long*)dinfo, use_lds);
+    else
+        hipLaunchKernelGGL(k_cross_maxvol<false>, dim3(1), dim3(TTN_XV_WG), lds, g_stream, (int)m, (int)r, A, tol, mi, (long long*)piv, C, Cw, perm,
+                           (long long*)dinfo, use_lds);
+    HIPCHK(hipGetLastError());
+    if (!hinfo) return TTN_OK;
+    HIPCHK(hipMemcpyAsync(hinfo, dinfo, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    if (hinfo[0]) return fail(TTN_ERR_SINGULAR, "ttn_cross_maxvol: zero pivot (the matrix has rank < r)");
+    return TTN_OK;
+}
+
+int ttn_cross_points(int cplx, int mode, int64_t N, int64_t site, int64_t n1, int64_t n2, int64_t rl, int64_t rr, const int64_t* L,
+                     const int64_t* R, const int64_t* idx_in, int64_t P, const int64_t* doff, const double* dom, int64_t* idx_out, double* X) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!doff || N < 1 || P < 0 || mode < 0 || mode > 2 || (!idx_out && !X) || (X && !dom)) return fail(TTN_ERR_ARG, "ttn_cross_points: bad argument");
+    if (mode == 2 && !idx_in) return fail(TTN_ERR_ARG, "ttn_cross_points: mode 2 needs an index matrix");
+    if (mode != 2) {
+        const int64_t last = mode == 0 ? N : N - 1;
+        if (site < 1 || site > last || n1 < 1 || rl < 1 || rr < 1 || (mode == 1 && n2 < 1))
+            return fail(TTN_ERR_ARG, "ttn_cross_points: bad site, size or rank");
+        if ((site > 1 && !L) || (site < last && !R)) return fail(TTN_ERR_ARG, "ttn_cross_points: missing index set");
+        const int64_t want = mode == 0 ? rl * n1 * rr : rl * n1 * n2 * rr;
+        if (P != want) return fail(TTN_ERR_ARG, "ttn_cross_points: P differs from the size of the fibre / superblock");
+    }
+    if (P == 0) return TTN_OK;
+    const long long total = (long long)P * N, blocks = (total + 255) / 256;
+    if (cplx)
+        hipLaunchKernelGGL(k_cross_points<true>, dim3((unsigned)blocks), dim3(256), 0, g_stream, mode, (long long)P, (int)N, (int)site, (long long)n1,
+                           (long long)n2, (long long)rl, (long long)rr, (const long long*)L, (const long long*)R, (const long long*)idx_in,
+                           (const long long*)doff, dom, (long long*)idx_out, X);
+    else
+        hipLaunchKernelGGL(k_cross_points<false>, dim3((unsigned)blocks), dim3(256), 0, g_stream, mode, (long long)P, (int)N, (int)site, (long long)n1,
+                           (long long)n2, (long long)rl, (long long)rr, (const long long*)L, (const long long*)R, (const long long*)idx_in,
+                           (const long long*)doff, dom, (long long*)idx_out, X);
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+int ttn_cross_eval(int cplx, int64_t N, int64_t P, const double* const* cores, const int64_t* dims, const int64_t* rks, const int64_t* idx,
+                   const double* w, double* out, const double* yref, double tol, double* err) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!cores || !dims || !rks || !out || N < 1 || P < 1 || (!idx && !w) || (idx && w) || (w && P != 1) || (yref && !err))
+        return fail(TTN_ERR_ARG, "ttn_cross_eval: bad argument (give idx, or w with P = 1)");
+    if (rks[0] != 1 || rks[N] != 1) return fail(TTN_ERR_DIMS, "ttn_cross_eval: the end ranks must be 1");
+    std::vector<long long> tab(4 * (size_t)N + 1);
+    long long woff = 0;
+    for (int64_t k = 0; k < N; ++k) {
+        if (!cores[k] || dims[k] < 1 || rks[k] < 1) return fail(TTN_ERR_ARG, "ttn_cross_eval: bad core");
+        tab[k] = (long long)reinterpret_cast<uintptr_t>(cores[k]);
+        tab[N + k] = dims[k];
+        tab[3 * N + 1 + k] = woff;
+        woff += dims[k];
+    }
+    for (int64_t k = 0; k <= N; ++k) {
+        if (rks[k] < 1 || rks[k] > TTN_XE_MAX_R) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_eval: ranks up to 1024");
+        tab[2 * N + k] = rks[k];
+    }
+    int rc = g_cross_tab.ensure(sizeof(long long) * tab.size());
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(g_cross_tab.p, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, g_stream));
+    const long long* dtab = g_cross_tab.as<long long>();
+    if (cplx) hipLaunchKernelGGL(k_cross_eval<true>, dim3((unsigned)P), dim3(64), 0, g_stream, (int)N, (long long)P, dtab, (const long long*)idx, w, w ? 1 : 0, out);
+    else hipLaunchKernelGGL(k_cross_eval<false>, dim3((unsigned)P), dim3(64), 0, g_stream, (int)N, (long long)P, dtab, (const long long*)idx, w, w ? 1 : 0, out);
+    HIPCHK(hipGetLastError());
+    if (yref) {
+        if (cplx) hipLaunchKernelGGL(k_cross_relerr<true>, dim3(1), dim3(TTN_XV_WG), 0, g_stream, (long long)P, yref, out, tol, err);
+        else hipLaunchKernelGGL(k_cross_relerr<false>, dim3(1), dim3(TTN_XV_WG), 0, g_stream, (long long)P, yref, out, tol, err);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(g_stream));             // the table is a host local
     return TTN_OK;
 }
 
