@@ -304,12 +304,48 @@ int ttn_cross_points(int cplx, int mode, int64_t N, int64_t site, int64_t n1, in
 int ttn_cross_eval(int cplx, int64_t N, int64_t P, const double* const* cores, const int64_t* dims, const int64_t* rks, const int64_t* idx,
                    const double* w, double* out, const double* yref, double tol, double* err);
 
+/* ---- TT operator algebra (csrc/ttn_opalg_kernels.h), Float64.  A ttn_tto is immutable and its ranks are known on the host, so
+ * every operation returns a NEW handle in *out (release it with ttn_tto_free); *out is written only on success.  Refused before
+ * any launch: null pointers (TTN_ERR_ARG), an output core with 2^31 or more fibres r_{k-1} r_k (TTN_ERR_UNSUPPORTED: 32-bit element
+ * indices), a result that does not fit in device memory (TTN_ERR_CAPACITY).  Asynchronous on the library stream unless stated.
+ *   ttn_tto_mul      A * B (src/tt_operations.jl:162-172): ranks A.rks .* B.rks, A's bond index fastest; dims must agree (TTN_ERR_DIMS).
+ *   ttn_tto_inner    the inner core product (:198-216): dims and ranks multiply, A major and B minor on every axis; d must agree.
+ *   ttn_tto_add      A + B (:71-95), d >= 2 (d = 1: TTN_ERR_UNSUPPORTED, as ttn_add); ttn_tto_scale  a * A (:271-281: the first core
+ *                    with ot == 0, else core 1; a == 0: zeros_tto with A's ranks, ot reset).  Both run the kernels of ttn_add /
+ *                    ttn_scale on the operator seen as a vector (an operator core (n, n, r, r') is the vector core (n^2, r, r')).
+ *   ttn_tto_kron     kron(A, B) (:427-433) and concatenate(A, B) (src/tt_tools.jl:723-735): needs A.rks[end] == B.rks[0] (TTN_ERR_DIMS).
+ *   ttn_tt_outer     outer_product(x_b, y_b) (:297-304; real: no conjugate); ttn_tt_diag_tto  ttv_to_diag_tto(x_b) (:310-338).  Both
+ *                    synchronise to read the current ranks of train b.
+ *   ttn_tt_kron      z_t = kron(x_t, y_t) (:440-448) for every train t; z has d_x + d_y sites; the joint ranks must be 1.
+ *   ttn_tto_to_tt    tto_to_ttv(A) (src/tt_tools.jl:296-304) into every train of y (dims n_k^2, capacity >= A's ranks).
+ *   ttn_tto_from_tt  ttv_to_tto(x_b) (:323-333) with the current ranks (synchronises); a non-square dimension is TTN_ERR_DIMS.
+ *   ttn_tto_compress tt_compress!(tto_to_ttv(A), max_bond; truncerr, sweeps) as an operator: to_tt, ttn_compress, from_tt, all on the
+ *                    device; a condition ttn_compress_status would report for the working train is this call's return value.
+ *                    Synchronises.
+ *   ttn_tto_ranks    d, dims (d), ranks (d + 1), ot (d) of a handle: any output may be null.  ttn_tto_set_ot: the gauge flags
+ *                    (tto_ot) that ttn_tto_scale, ttn_tto_kron and ttn_tto_to_tt carry along; ttn_tto_create sets zeros.
+ *   ttn_tto_download cores[k] receives n_k n_k rks[k] rks[k+1] doubles, column-major (synchronises). */
+int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out);
+int ttn_tto_inner(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out);
+int ttn_tto_add(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out);
+int ttn_tto_scale(double a, ttn_tto_t A, ttn_tto_t* out);
+int ttn_tto_kron(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out);
+int ttn_tt_outer(ttn_tt_t x, ttn_tt_t y, int64_t b, ttn_tto_t* out);
+int ttn_tt_diag_tto(ttn_tt_t x, int64_t b, ttn_tto_t* out);
+int ttn_tt_kron(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z);
+int ttn_tto_to_tt(ttn_tto_t A, ttn_tt_t y);
+int ttn_tto_from_tt(ttn_tt_t x, int64_t b, ttn_tto_t* out);
+int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t sweeps, ttn_tto_t* out);
+int ttn_tto_ranks(ttn_tto_t A, int64_t* d, int64_t* dims, int64_t* rks, int64_t* ot);
+int ttn_tto_set_ot(ttn_tto_t A, const int64_t* ot);
+int ttn_tto_download(ttn_tto_t A, double* const* cores);
+
 /* fused convenience for the benchmark op  tt_compress!(A*x, max_bond)  (src/solvers/euler.jl:55) */
 int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, double truncerr, int64_t sweeps);
 
 /* out[b] = dot(a_b, b_b)      src/tt_operations.jl:239-250 ; out is HOST memory, length batch (synchronises) */
 int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out);
-/* HIP-event time of the KERNEL of the last ttn_dot / ttn_norm / ttn_orthogonalize call alone (ttn_dot itself goes on to copy the
+/* HIP-event time of the KERNEL of the last ttn_dot / ttn_norm / ttn_orthogonalize / ttn_tto_mul call alone (ttn_dot itself goes on to copy the
  * results to the host and synchronises, which an event pair around the call would include) — what bench.py --op reports.  Its
  * events are its own: such a call inside a ttn_timer_begin / ttn_timer_end region does not move the timer's start. */
 int ttn_last_launch_ms(float* ms);

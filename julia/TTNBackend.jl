@@ -381,4 +381,131 @@ function _applyH2_lsr(AAC::Array{T, 4}, FL::Array{T, 3}, FR::Array{T, 3}, M1::Ar
     return _tdvp_contract(4, T, (Dl, d1, Dr, a, b, c, d2), FL, FR, AAC, M1, M2, Array{T}(undef, Dl, d1, d2, Dr))
 end
 
+# ---- TT operator algebra (src/tt_operations.jl:71-95, :162-216, :271-338, :427-435; src/tt_tools.jl:296-333, :723-735) -------------
+# Written against include/ttn.h and not executed (no Julia on the build machines).  A device operator is immutable, so every entry
+# point returns a new handle: the stateless forms below upload their operands, run one operation and download the result.  A chain
+# (assemble a generator, then round it) should keep the handles and call `_tto_op` / `ttn_tto_compress` on them instead.
+function _tto_up(A::TToperator{Float64, N}) where {N}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    pa = _ptrs(A.tto_vec)
+    GC.@preserve A pa _chk(ccall((:ttn_tto_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}),
+        N, _dims(A.tto_dims), A.tto_rks, pa, h))
+    any(!=(0), A.tto_ot) && _chk(ccall((:ttn_tto_set_ot, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], Int64[A.tto_ot...]))
+    return h[]
+end
+
+function _ttv_up(x::TTvector{Float64, N}) where {N}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    px = _ptrs(x.ttv_vec)
+    GC.@preserve x px begin
+        _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, _dims(x.ttv_dims), x.ttv_rks, 1, h))
+        _chk(ccall((:ttn_tt_upload, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Int64}), h[], 0, px, x.ttv_rks, x.ttv_ot))
+    end
+    return h[]
+end
+
+_tto_free(h) = ccall((:ttn_tto_free, LIB), Cint, (Ptr{Cvoid},), h)
+_ttv_free(h) = ccall((:ttn_tt_free, LIB), Cint, (Ptr{Cvoid},), h)
+
+# download a result handle as a TToperator and release it
+function _tto_down(h::Ptr{Cvoid})
+    d = Ref{Int64}(0)
+    _chk(ccall((:ttn_tto_ranks, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h, d, C_NULL, C_NULL, C_NULL))
+    N = Int(d[])
+    dims, rks, ot = zeros(Int64, N), zeros(Int64, N + 1), zeros(Int64, N)
+    _chk(ccall((:ttn_tto_ranks, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h, C_NULL, dims, rks, ot))
+    vec = [zeros(Float64, dims[k], dims[k], rks[k], rks[k + 1]) for k in 1:N]
+    pv = _ptrs(vec)
+    GC.@preserve vec pv _chk(ccall((:ttn_tto_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), h, pv))
+    _tto_free(h)
+    return TToperator{Float64, N}(N, vec, Tuple(dims), rks, ot)
+end
+
+# sym in (:ttn_tto_mul, :ttn_tto_inner, :ttn_tto_add, :ttn_tto_kron) on two operator handles
+function _tto_op(sym::Symbol, hA::Ptr{Cvoid}, hB::Ptr{Cvoid})
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _chk(ccall((sym, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), hA, hB, out))
+    return out[]
+end
+
+function _tto_binary(sym::Symbol, A::TToperator{Float64}, B::TToperator{Float64})
+    hA, hB = _tto_up(A), _tto_up(B)
+    try
+        return _tto_down(_tto_op(sym, hA, hB))
+    finally
+        _tto_free(hA); _tto_free(hB)
+    end
+end
+
+function *(A::TToperator{Float64, N}, B::TToperator{Float64, N}) where {N}
+    @assert A.tto_dims == B.tto_dims "Incompatible dimensions"
+    return _tto_binary(:ttn_tto_mul, A, B)
+end
+
+function +(A::TToperator{Float64, N}, B::TToperator{Float64, N}) where {N}
+    @assert A.tto_dims == B.tto_dims "Incompatible dimensions"
+    return _tto_binary(:ttn_tto_add, A, B)
+end
+
+function TensorTrainNumerics.:⨝(A::TToperator{Float64, N}, B::TToperator{Float64, N}) where {N}
+    return _tto_binary(:ttn_tto_inner, A, B)
+end
+
+# kron / ⊗ and concatenate only regroup cores: the reference's vcat stays the host form; on handles it is ttn_tto_kron / ttn_tt_kron.
+
+function *(a::Float64, A::TToperator{Float64, N}) where {N}
+    hA = _tto_up(A)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    try
+        _chk(ccall((:ttn_tto_scale, LIB), Cint, (Float64, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), a, hA, out))
+        return _tto_down(out[])
+    finally
+        _tto_free(hA)
+    end
+end
+
+function TensorTrainNumerics.outer_product(x::TTvector{Float64, N}, y::TTvector{Float64, N}) where {N}
+    hx, hy = _ttv_up(x), _ttv_up(y)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    try
+        _chk(ccall((:ttn_tt_outer, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), hx, hy, 0, out))
+        return _tto_down(out[])
+    finally
+        _ttv_free(hx); _ttv_free(hy)
+    end
+end
+
+function TensorTrainNumerics.ttv_to_diag_tto(x::TTvector{Float64, N}) where {N}
+    hx = _ttv_up(x)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    try
+        _chk(ccall((:ttn_tt_diag_tto, LIB), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), hx, 0, out))
+        return _tto_down(out[])
+    finally
+        _ttv_free(hx)
+    end
+end
+
+# ttv_to_tto(tt_compress!(tto_to_ttv(A), max_bond; truncerr, sweeps)) without leaving the device (no reference method of this name:
+# the examples round operators through tto_to_ttv by hand)
+function tto_compress(A::TToperator{Float64, N}, max_bond::Integer = typemax(Int64) >> 1; truncerr::Float64 = 0.0, sweeps::Integer = 1) where {N}
+    hA = _tto_up(A)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    try
+        _chk(ccall((:ttn_tto_compress, LIB), Cint, (Ptr{Cvoid}, Int64, Float64, Int64, Ref{Ptr{Cvoid}}), hA, max_bond, truncerr, sweeps, out))
+        return _tto_down(out[])
+    finally
+        _tto_free(hA)
+    end
+end
+
+# handle-level conversions and the vector kron, for chains that stay on the device
+_tto_to_tt(hA::Ptr{Cvoid}, hy::Ptr{Cvoid}) = _chk(ccall((:ttn_tto_to_tt, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), hA, hy))
+_tt_kron(hx::Ptr{Cvoid}, hy::Ptr{Cvoid}, hz::Ptr{Cvoid}) = _chk(ccall((:ttn_tt_kron, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), hx, hy, hz))
+function _tto_from_tt(hx::Ptr{Cvoid}, b::Integer = 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _chk(ccall((:ttn_tto_from_tt, LIB), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), hx, b, out))
+    return out[]
+end
+
 end # module

@@ -53,6 +53,20 @@ SIGNATURES = {
     "ttn_tt_copy": (C.c_int, [handle, handle]),
     "ttn_tto_create": (C.c_int, [i64, p_i64, p_i64, pp_f64, p_handle]),
     "ttn_tto_free": (C.c_int, [handle]),
+    "ttn_tto_mul": (C.c_int, [handle, handle, p_handle]),
+    "ttn_tto_inner": (C.c_int, [handle, handle, p_handle]),
+    "ttn_tto_add": (C.c_int, [handle, handle, p_handle]),
+    "ttn_tto_scale": (C.c_int, [C.c_double, handle, p_handle]),
+    "ttn_tto_kron": (C.c_int, [handle, handle, p_handle]),
+    "ttn_tt_outer": (C.c_int, [handle, handle, i64, p_handle]),
+    "ttn_tt_diag_tto": (C.c_int, [handle, i64, p_handle]),
+    "ttn_tt_kron": (C.c_int, [handle, handle, handle]),
+    "ttn_tto_to_tt": (C.c_int, [handle, handle]),
+    "ttn_tto_from_tt": (C.c_int, [handle, i64, p_handle]),
+    "ttn_tto_compress": (C.c_int, [handle, i64, C.c_double, i64, p_handle]),
+    "ttn_tto_ranks": (C.c_int, [handle, p_i64, p_i64, p_i64, p_i64]),
+    "ttn_tto_set_ot": (C.c_int, [handle, p_i64]),
+    "ttn_tto_download": (C.c_int, [handle, pp_f64]),
     "ttn_apply": (C.c_int, [handle, handle, handle]),
     "ttn_compress": (C.c_int, [handle, i64, C.c_double, i64]),
     "ttn_compress_status": (C.c_int, [handle, p_i64]),

@@ -3,9 +3,10 @@ vector cores the reference builds once on the host, plus the portable seeded gen
 benchmark uses for "rank-r random TTvector" inputs.
 
     zeros_tt / zeros_tto            src/tt_operators.jl:548-573, :601-616
-    toeplitz_to_qtto, Δ, shift      src/tt_operators.jl:4-19, :24, :283-285
+    toeplitz_to_qtto, Δ, shift, ∇   src/tt_operators.jl:4-19, :24, :276-285
     id_tto                          src/tt_operators.jl:519-532
     qtt_sin / qtt_cos / qtt_exp     src/qtt_tools.jl:116-175
+    qtt_polynom                     src/qtt_tools.jl:88-110
     rand_tt                         src/tt_tools.jl:100-139 (randn replaced by a portable stream)
     qtt_to_vector                   src/qtt_tools.jl:57-71 (densifier used by small tests)
 
@@ -68,6 +69,11 @@ def shift(d: int) -> TToperator:
     return toeplitz_to_qtto(0, 1, 0, d)
 
 
+def Nabla(d: int) -> TToperator:
+    """∇(d): the backward-difference matrix tridiag(-1, 1, 0) — src/tt_operators.jl:276-278."""
+    return toeplitz_to_qtto(1, 0, -1, d)
+
+
 def id_tto(d: int, n_dim: int = 2) -> TToperator:
     vec = [np.asfortranarray(np.eye(2).reshape(2, 2, 1, 1)) for _ in range(d)]
     return TToperator(d, vec, (n_dim,) * d, [1] * (d + 1), [0] * d)
@@ -104,6 +110,32 @@ def qtt_exp(d: int, a: float = 0.0, b: float = 1.0, alpha: float = 1.0, beta: fl
     for k in range(2, d):
         out.ttv_vec[k - 1][:, 0, 0] = [1.0, math.exp(alpha * (h * 2 ** (d - k)))]
     out.ttv_vec[d - 1][:, 0, 0] = [1.0, math.exp(alpha * h)]
+    return out
+
+
+def qtt_polynom(coef: Sequence[float], d: int, a: float = 0.0, b: float = 1.0) -> TTvector:
+    """QTT of the polynomial sum_k coef[k] x^k on the 2^d uniform points of [a, b], all bonds of rank p = len(coef)
+    (zeros_tt(2, d, p; r_and_d = false)) — src/qtt_tools.jl:88-110.  d >= 2."""
+    assert d >= 2, "qtt_polynom needs d >= 2"
+    coef = [float(c) for c in coef]
+    p = len(coef)
+    h = (b - a) / (2 ** d - 1)
+    out = zeros_tt((2,) * d, [1] + [p] * (d - 1) + [1])
+
+    def phi(x, s):                        # the s-th Taylor coefficient of the polynomial at x
+        return sum(coef[k] * x ** (k - s) * math.comb(k, s) for k in range(s, p))
+
+    for row, t in ((0, a), (1, a + h * 2 ** (d - 1))):                 # coarsest bit first
+        out.ttv_vec[0][row, 0, :] = [phi(t, s) for s in range(p)]
+    for k in range(2, d):
+        tk = h * 2 ** (d - k)
+        core = out.ttv_vec[k - 1]
+        core[0] = np.eye(p)
+        for i in range(p):
+            for j in range(i + 1):
+                core[1, i, j] = math.comb(i, j) * tk ** (i - j)
+    out.ttv_vec[d - 1][0, 0, 0] = 1.0
+    out.ttv_vec[d - 1][1, :, 0] = [h ** s for s in range(p)]
     return out
 
 

@@ -16,6 +16,7 @@
 #include "ttn_tdvp_kernels.h"
 #include "ttn_densefact_kernels.h"
 #include "ttn_cross_kernels.h"
+#include "ttn_opalg_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -135,9 +136,19 @@ struct ttn_tto_s {
     long long* d_off = nullptr;
     long long* d_rks = nullptr;
     int* d_dims = nullptr;
+    int* d_dims2 = nullptr;                   // [d] n_k^2: the dims of the operator seen as a vector (tto_to_ttv)
+    std::vector<int64_t> ot;                  // [d] gauge flags (tto_ot; zeros unless ttn_tto_set_ot or an operation sets them)
     TTODev dev() const {
         TTODev t;
         t.data = d_data; t.off = d_off; t.rks = d_rks; t.dims = d_dims; t.d = d;
+        return t;
+    }
+    // The operator as ONE train of physical dimensions n_k^2 whose capacity is its ranks: an operator core (n, n, r_l, r_r) is byte for
+    // byte the vector core (n^2, r_l, r_r), and the 16-byte slot rounding of both handle kinds gives the same offsets.
+    TTDev vdev() const {
+        TTDev t;
+        t.data = d_data; t.stride = off.empty() ? 0 : off.back(); t.off = d_off; t.rks = d_rks; t.dims = d_dims2; t.cap = d_rks;
+        t.d = d; t.batch = 1;
         return t;
     }
 };
@@ -490,21 +501,23 @@ int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const dou
         if (!cores[k]) { delete h; return fail(TTN_ERR_ARG, "ttn_tto_create: null core"); }
         std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)dims[k] * dims[k] * rks[k] * rks[k + 1]);
     }
-    std::vector<int> idims(d);
-    for (int64_t k = 0; k < d; ++k) idims[k] = (int)dims[k];
+    std::vector<int> idims(2 * d);
+    for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(dims[k] * dims[k]); }
     std::vector<long long> r64(rks, rks + d + 1);
+    h->ot.assign(d, 0);
     hipError_t e;
     if ((e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1))) != hipSuccess ||
         (e = hipMalloc((void**)&h->d_off, sizeof(long long) * (d + 1))) != hipSuccess ||
         (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * d)) != hipSuccess) {
+        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * d)) != hipSuccess) {
         ttn_tto_free(h);
         return hipfail(e, "hipMalloc(ttn_tto)");
     }
+    h->d_dims2 = h->d_dims + d;
     HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * (size_t)o, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * d, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * d, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     *out = h;
     return TTN_OK;
@@ -2540,5 +2553,350 @@ int ttn_als_gen_eigsolve(ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int6
                         hist_len, E);
 }
 
+// ---- TT operator algebra (csrc/ttn_opalg_kernels.h) ----------------------------------------------------------------------------
+// A ttn_tto is immutable and its ranks are host-known, so every operation allocates its result.  tto_alloc: the handle and its
+// tables, cores uninitialised; an allocation the device cannot satisfy is TTN_ERR_CAPACITY (nothing is launched).
+namespace {
+struct NewTTO {                       // frees the handle unless release() hands it to the caller
+    ttn_tto_t h = nullptr;
+    ~NewTTO() { if (h) ttn_tto_free(h); }
+    ttn_tto_t release() { ttn_tto_t t = h; h = nullptr; return t; }
+};
+int tto_alloc(const char* who, int64_t d, const int64_t* dims, const int64_t* rks, const int64_t* ot, NewTTO& out) {
+    for (int64_t k = 0; k < d; ++k)
+        if (stream_fibres_too_many((long long)rks[k] * rks[k + 1]))
+            return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": 2^31 or more fibres in one output core (32-bit element indices)").c_str());
+    ttn_tto_s* h = new ttn_tto_s();
+    out.h = h;
+    h->d = (int)d;
+    h->dims.assign(dims, dims + d);
+    h->rks.assign(rks, rks + d + 1);
+    h->ot.assign(d, 0);
+    if (ot) h->ot.assign(ot, ot + d);
+    h->off.resize(d + 1);
+    long long o = 0;
+    for (int64_t k = 0; k < d; ++k) {
+        h->off[k] = o;
+        const long long sz = (long long)dims[k] * dims[k] * rks[k] * rks[k + 1];
+        o += (sz + 1) & ~1LL;
+    }
+    h->off[d] = o;
+    std::vector<int> idims(2 * d);
+    for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(dims[k] * dims[k]); }
+    std::vector<long long> r64(rks, rks + d + 1);
+    if (hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_data = nullptr;
+        return fail(TTN_ERR_CAPACITY, (std::string(who) + ": the result does not fit in device memory").c_str());
+    }
+    hipError_t e;
+    if ((e = hipMalloc((void**)&h->d_off, sizeof(long long) * (d + 1))) != hipSuccess ||
+        (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (d + 1))) != hipSuccess ||
+        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * d)) != hipSuccess)
+        return hipfail(e, "hipMalloc(ttn_tto)");
+    h->d_dims2 = h->d_dims + d;
+    HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * d, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));          // the tables above are locals
+    return TTN_OK;
+}
+}  // namespace
+
+int ttn_tto_set_ot(ttn_tto_t A, const int64_t* ot) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!A || !ot) return fail(TTN_ERR_ARG, "null pointer");
+    A->ot.assign(ot, ot + A->d);
+    return TTN_OK;
+}
+
+int ttn_tto_ranks(ttn_tto_t A, int64_t* d, int64_t* dims, int64_t* rks, int64_t* ot) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!A) return fail(TTN_ERR_ARG, "null handle");
+    if (d) *d = A->d;
+    if (dims) for (int k = 0; k < A->d; ++k) dims[k] = A->dims[k];
+    if (rks) for (int m = 0; m <= A->d; ++m) rks[m] = A->rks[m];
+    if (ot) for (int k = 0; k < A->d; ++k) ot[k] = A->ot[k];
+    return TTN_OK;
+}
+
+int ttn_tto_download(ttn_tto_t A, double* const* cores) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !cores) return fail(TTN_ERR_ARG, "null pointer");
+    for (int k = 0; k < A->d; ++k) {
+        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_download: null core");
+        const size_t sz = (size_t)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1];
+        HIPCHK(hipMemcpyAsync(cores[k], A->d_data + A->off[k], sizeof(double) * sz, hipMemcpyDeviceToHost, g_stream));
+    }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return TTN_OK;
+}
+
+// *(A::TToperator, B::TToperator)   src/tt_operations.jl:162-172
+int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (!same_dims(A->dims, B->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    const int d = A->d;
+    std::vector<int64_t> rks(d + 1);
+    for (int m = 0; m <= d; ++m) rks[m] = A->rks[m] * B->rks[m];
+    NewTTO Y;
+    int rc = tto_alloc("ttn_tto_mul", d, A->dims.data(), rks.data(), nullptr, Y);
+    if (rc) return rc;
+    // LDS: the largest binary-site A core that fits; grid: rows x column groups on binary sites, fibres elsewhere
+    long long lds_a = 0, items = 1;
+    for (int k = 0; k < d; ++k) {
+        const long long P = rks[k], Q = rks[k + 1];
+        if (A->dims[k] == 2) {
+            const long long asz = 4LL * A->rks[k] * A->rks[k + 1];
+            if (asz <= TTN_TTOMUL_LDS_DOUBLES) lds_a = std::max(lds_a, asz);
+            items = std::max(items, P * ((Q + TTN_TTOMUL_K - 1) / TTN_TTOMUL_K));
+        } else items = std::max(items, P * Q);
+    }
+    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
+    hipLaunchKernelGGL(k_tto_mul, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), sizeof(double) * (size_t)lds_a, g_stream, A->dev(), B->dev(), Y.h->d_data,
+                       (const long long*)Y.h->d_off, (int)lds_a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));       // ttn_last_launch_ms: the kernel alone, without this call's allocation
+    g_have_launch_ms = true;
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// A ⨝ B   src/tt_operations.jl:198-216
+int ttn_tto_inner(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (A->d != B->d) return fail(TTN_ERR_DIMS, "Inner core product requires operators with the same number of cores");
+    const int d = A->d;
+    std::vector<int64_t> rks(d + 1), dims(d);
+    for (int m = 0; m <= d; ++m) rks[m] = A->rks[m] * B->rks[m];
+    long long items = 1;
+    for (int k = 0; k < d; ++k) {
+        dims[k] = A->dims[k] * B->dims[k];
+        if (dims[k] > 46340) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_inner: physical dimension above 46340");
+        items = std::max<long long>(items, std::min<long long>((long long)dims[k] * dims[k] * std::min<long long>(rks[k] * rks[k + 1], 1LL << 31), 1LL << 40));
+    }
+    NewTTO Y;
+    int rc = tto_alloc("ttn_tto_inner", d, dims.data(), rks.data(), nullptr, Y);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_tto_inner, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, A->dev(), B->dev(), Y.h->d_data, (const long long*)Y.h->d_off);
+    HIPCHK(hipGetLastError());
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// +(x::TToperator, y::TToperator)   src/tt_operations.jl:71-95: k_add on the operators seen as vectors
+int ttn_tto_add(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (!same_dims(A->dims, B->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    const int d = A->d;
+    if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_add: the reference's + is only defined for d >= 2");
+    std::vector<int64_t> rks(d + 1);
+    for (int m = 0; m <= d; ++m) rks[m] = (m == 0 || m == d) ? 1 : A->rks[m] + B->rks[m];
+    NewTTO Z;
+    int rc = tto_alloc("ttn_tto_add", d, A->dims.data(), rks.data(), nullptr, Z);
+    if (rc) return rc;
+    long long maxpq = 0;
+    bool qtt = true;                                   // k_add's n = 2 mapping is for vector dims 2: an operator has n^2 >= 4 unless n = 1
+    for (int k = 0; k < d; ++k) { maxpq = std::max<long long>(maxpq, (long long)rks[k] * rks[k + 1]); qtt = qtt && A->dims[k] * A->dims[k] == 2; }
+    hipLaunchKernelGGL(k_add, stream_grid(qtt ? (maxpq + TTN_ADD_K - 1) / TTN_ADD_K : maxpq, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, A->vdev(), B->vdev(), Z.h->vdev());
+    HIPCHK(hipGetLastError());
+    *out = Z.release();
+    return TTN_OK;
+}
+
+// *(a::Number, A::TToperator)   src/tt_operations.jl:271-281: k_scale on the operator seen as a vector
+int ttn_tto_scale(double a, ttn_tto_t A, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
+    const int d = A->d;
+    std::vector<int64_t> ot(A->ot);
+    if (a == 0.0) std::fill(ot.begin(), ot.end(), 0);       // zeros_tto(dims, rks)
+    NewTTO Y;
+    int rc = tto_alloc("ttn_tto_scale", d, A->dims.data(), A->rks.data(), ot.data(), Y);
+    if (rc) return rc;
+    int which = 0;
+    for (int k = 0; k < d; ++k) if (A->ot[k] == 0) { which = k; break; }
+    long long maxsz = 0;
+    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]);
+    hipLaunchKernelGGL(k_scale, stream_grid((maxsz + 7) / 8, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, A->vdev(), Y.h->vdev(), a, which, a == 0.0 ? 1 : 0, (const int*)nullptr);
+    HIPCHK(hipGetLastError());
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// kron(A, B) (src/tt_operations.jl:427-433) and concatenate(A, B) (src/tt_tools.jl:723-735): B's cores behind A's, two device copies
+int ttn_tto_kron(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (A->rks[A->d] != B->rks[0]) return fail(TTN_ERR_DIMS, "The final rank of the first TToperator must equal the initial rank of the second TToperator.");
+    const int d = A->d + B->d;
+    std::vector<int64_t> dims(A->dims), rks(A->rks.begin(), A->rks.end() - 1), ot(A->ot);
+    dims.insert(dims.end(), B->dims.begin(), B->dims.end());
+    rks.insert(rks.end(), B->rks.begin(), B->rks.end());
+    ot.insert(ot.end(), B->ot.begin(), B->ot.end());
+    NewTTO Y;
+    int rc = tto_alloc("ttn_tto_kron", d, dims.data(), rks.data(), ot.data(), Y);
+    if (rc) return rc;
+    // the slot offsets of a handle are running sums of its 16-byte rounded core sizes: the arena of A, then the arena of B
+    if (A->off[A->d]) HIPCHK(hipMemcpyAsync(Y.h->d_data, A->d_data, sizeof(double) * (size_t)A->off[A->d], hipMemcpyDeviceToDevice, g_stream));
+    if (B->off[B->d]) HIPCHK(hipMemcpyAsync(Y.h->d_data + A->off[A->d], B->d_data, sizeof(double) * (size_t)B->off[B->d], hipMemcpyDeviceToDevice, g_stream));
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// Current ranks of train b of x on the host (synchronises), as the ranks of a new operator
+static int train_ranks(ttn_tt_t x, int64_t b, std::vector<int64_t>& rks) {
+    rks.resize(x->d + 1);
+    return ttn_tt_ranks(x, b, rks.data(), nullptr);
+}
+
+// outer_product(x, y)   src/tt_operations.jl:297-304 (real)
+int ttn_tt_outer(ttn_tt_t x, ttn_tt_t y, int64_t b, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !y || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (b < 0 || b >= x->batch || b >= y->batch) return fail(TTN_ERR_ARG, "ttn_tt_outer: train index outside the batch");
+    if (!same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    const int d = x->d;
+    std::vector<int64_t> xr, yr, rks(d + 1);
+    int rc;
+    if ((rc = train_ranks(x, b, xr)) || (rc = train_ranks(y, b, yr))) return rc;
+    long long items = 1;
+    for (int m = 0; m <= d; ++m) rks[m] = xr[m] * yr[m];
+    for (int k = 0; k < d; ++k) items = std::max<long long>(items, std::min<long long>((long long)x->dims[k] * x->dims[k] * std::min<long long>(rks[k] * rks[k + 1], 1LL << 31), 1LL << 40));
+    NewTTO Y;
+    if ((rc = tto_alloc("ttn_tt_outer", d, x->dims.data(), rks.data(), nullptr, Y))) return rc;
+    hipLaunchKernelGGL(k_tt_outer, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), (int)b, Y.h->d_data, (const long long*)Y.h->d_off);
+    HIPCHK(hipGetLastError());
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// ttv_to_diag_tto(x)   src/tt_operations.jl:310-338
+int ttn_tt_diag_tto(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (b < 0 || b >= x->batch) return fail(TTN_ERR_ARG, "ttn_tt_diag_tto: train index outside the batch");
+    const int d = x->d;
+    std::vector<int64_t> rks;
+    int rc;
+    if ((rc = train_ranks(x, b, rks))) return rc;
+    long long items = 1;
+    for (int k = 0; k < d; ++k) items = std::max<long long>(items, std::min<long long>((long long)x->dims[k] * x->dims[k] * std::min<long long>(rks[k] * rks[k + 1], 1LL << 31), 1LL << 40));
+    NewTTO Y;
+    if ((rc = tto_alloc("ttn_tt_diag_tto", d, x->dims.data(), rks.data(), nullptr, Y))) return rc;
+    hipLaunchKernelGGL(k_tt_diag, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), (int)b, Y.h->d_data, (const long long*)Y.h->d_off);
+    HIPCHK(hipGetLastError());
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// kron(a::TTvector, b::TTvector)   src/tt_operations.jl:440-448, train by train: z_b = x_b (x) y_b.  Strided device copies of the slots
+// (a slot holds its core compactly at its start: copying the host-side bound of the ranks covers it) and of the rank tables.
+int ttn_tt_kron(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
+    if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_tt_kron: output must not alias an input");
+    const int dx = x->d, dy = y->d, d = dx + dy;
+    std::vector<int64_t> dims(x->dims);
+    dims.insert(dims.end(), y->dims.begin(), y->dims.end());
+    if (z->d != d || !same_dims(z->dims, dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    if (x->bound[dx] != 1 || y->bound[0] != 1) return fail(TTN_ERR_DIMS, "ttn_tt_kron: the ranks at the joint must be 1");
+    std::vector<int64_t> zb(x->bound.begin(), x->bound.end() - 1);
+    zb.insert(zb.end(), y->bound.begin(), y->bound.end());
+    for (int m = 0; m <= d; ++m) if (z->cap[m] < zb[m]) return fail(TTN_ERR_CAPACITY, "ttn_tt_kron: destination capacity too small");
+    const size_t B = (size_t)x->batch;
+    for (int k = 0; k < d; ++k) {
+        ttn_tt_t s = k < dx ? x : y;
+        const int ks = k < dx ? k : k - dx;
+        const size_t w = sizeof(double) * (size_t)s->dims[ks] * s->bound[ks] * s->bound[ks + 1];
+        HIPCHK(hipMemcpy2DAsync(z->d_data + z->off[k], sizeof(double) * (size_t)z->stride, s->d_data + s->off[ks], sizeof(double) * (size_t)s->stride, w, B,
+                                hipMemcpyDeviceToDevice, g_stream));
+    }
+    HIPCHK(hipMemcpy2DAsync(z->d_rks, sizeof(long long) * (d + 1), x->d_rks, sizeof(long long) * (dx + 1), sizeof(long long) * dx, B, hipMemcpyDeviceToDevice, g_stream));
+    HIPCHK(hipMemcpy2DAsync(z->d_rks + dx, sizeof(long long) * (d + 1), y->d_rks, sizeof(long long) * (dy + 1), sizeof(long long) * (dy + 1), B, hipMemcpyDeviceToDevice, g_stream));
+    z->bound = zb;
+    for (size_t b = 0; b < B; ++b)
+        for (int k = 0; k < d; ++k) z->ot[b * d + k] = k < dx ? x->ot[b * dx + k] : y->ot[b * dy + (k - dx)];
+    return TTN_OK;
+}
+
+// tto_to_ttv(A) (src/tt_tools.jl:296-304) into every train of y: one device copy per core into train 0, then ttn_tt_replicate
+int ttn_tto_to_tt(ttn_tto_t A, ttn_tt_t y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !y) return fail(TTN_ERR_ARG, "null handle");
+    const int d = A->d;
+    if (y->d != d) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    for (int k = 0; k < d; ++k) if (y->dims[k] != A->dims[k] * A->dims[k]) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m]) return fail(TTN_ERR_CAPACITY, "ttn_tto_to_tt: destination capacity too small");
+    for (int k = 0; k < d; ++k) {
+        const size_t sz = (size_t)y->dims[k] * A->rks[k] * A->rks[k + 1];
+        HIPCHK(hipMemcpyAsync(y->d_data + y->off[k], A->d_data + A->off[k], sizeof(double) * sz, hipMemcpyDeviceToDevice, g_stream));
+    }
+    HIPCHK(hipMemcpyAsync(y->d_rks, A->d_rks, sizeof(long long) * (d + 1), hipMemcpyDeviceToDevice, g_stream));
+    for (int k = 0; k < d; ++k) y->ot[k] = A->ot[k];
+    y->bound = A->rks;
+    return ttn_tt_replicate(y, 0);
+}
+
+// ttv_to_tto(x_b) (src/tt_tools.jl:323-333) with the train's current ranks (synchronises to read them)
+int ttn_tto_from_tt(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (b < 0 || b >= x->batch) return fail(TTN_ERR_ARG, "ttn_tto_from_tt: train index outside the batch");
+    const int d = x->d;
+    std::vector<int64_t> dims(d), rks;
+    for (int k = 0; k < d; ++k) {
+        dims[k] = (int64_t)std::llround(std::sqrt((double)x->dims[k]));
+        if (dims[k] * dims[k] != x->dims[k]) return fail(TTN_ERR_DIMS, "DimensionMismatch: the dimensions of the train are not perfect squares");
+    }
+    int rc;
+    if ((rc = train_ranks(x, b, rks))) return rc;
+    NewTTO Y;
+    if ((rc = tto_alloc("ttn_tto_from_tt", d, dims.data(), rks.data(), x->ot.data() + (size_t)b * d, Y))) return rc;
+    for (int k = 0; k < d; ++k) {
+        const size_t sz = (size_t)x->dims[k] * rks[k] * rks[k + 1];
+        HIPCHK(hipMemcpyAsync(Y.h->d_data + Y.h->off[k], x->d_data + (size_t)b * x->stride + x->off[k], sizeof(double) * sz, hipMemcpyDeviceToDevice, g_stream));
+    }
+    *out = Y.release();
+    return TTN_OK;
+}
+
+// tt_compress!(tto_to_ttv(A), max_bond; truncerr, sweeps) as an operator again: to_tt -> ttn_compress -> from_tt on the device.  The
+// working train is read and cleared of its status here (a failure is this call's return value), so its release folds nothing into
+// the library-level word of ttn_status_all.
+int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t sweeps, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
+    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    const int d = A->d;
+    std::vector<int64_t> dims2(d), need, fin;
+    for (int k = 0; k < d; ++k) dims2[k] = A->dims[k] * A->dims[k];
+    long long pm, qm;
+    rank_bounds(d, dims2.data(), A->rks.data(), max_bond, sweeps, 0, need, fin, pm, qm);
+    TmpTT t;
+    int rc;
+    if ((rc = ttn_tt_create(d, dims2.data(), need.data(), 1, &t.h))) return rc;
+    if ((rc = ttn_tto_to_tt(A, t.h))) return rc;
+    if ((rc = ttn_compress(t.h, max_bond, truncerr, sweeps))) return rc;
+    if ((rc = ttn_compress_status(t.h, nullptr))) return rc;
+    return ttn_tto_from_tt(t.h, 0, out);
+}
 
 }  // extern "C"

@@ -17,15 +17,101 @@ from .tt import TToperator, TTvector, _f, _i64, _ptrs
 
 
 class DeviceTTO:
+    """One TT operator in HBM (``ttn_tto``): immutable, ranks known on the host.  The algebra below (csrc/ttn_opalg_kernels.h) returns a
+    NEW ``DeviceTTO`` from every call and never crosses PCIe; ``download()`` brings the cores back."""
+
     def __init__(self, A: TToperator):
         _lib.ensure_init()
         self.dims = tuple(A.tto_dims)
         self.rks = list(A.tto_rks)
+        self.ot = [int(o) for o in A.tto_ot]
         self.N = A.N
         cores = [_f(c) for c in A.tto_vec]
         h = C.c_void_p()
         _lib.check(_lib.lib().ttn_tto_create(A.N, _i64(A.tto_dims), _i64(A.tto_rks), _ptrs(cores), C.byref(h)))
         self.h = h
+        if any(self.ot):
+            _lib.check(_lib.lib().ttn_tto_set_ot(self.h, _i64(self.ot)))
+
+    @classmethod
+    def _adopt(cls, h: C.c_void_p) -> "DeviceTTO":
+        """Wrap a handle an operation of the library returned (dims, ranks and gauge flags are read from it)."""
+        if not h:
+            raise _lib.TTNError("the library returned no operator handle")
+        self = cls.__new__(cls)
+        self.h = h
+        L = _lib.lib()
+        d = C.c_int64(0)
+        _lib.check(L.ttn_tto_ranks(h, C.byref(d), None, None, None))
+        self.N = int(d.value)
+        dims, rks, ot = (C.c_int64 * self.N)(), (C.c_int64 * (self.N + 1))(), (C.c_int64 * self.N)()
+        _lib.check(L.ttn_tto_ranks(h, None, dims, rks, ot))
+        self.dims, self.rks, self.ot = tuple(int(v) for v in dims), [int(v) for v in rks], [int(v) for v in ot]
+        return self
+
+    def _binary(self, name: str, other: "DeviceTTO") -> "DeviceTTO":
+        if not isinstance(other, DeviceTTO):
+            raise TypeError(f"{name}: expected a DeviceTTO, got {type(other).__name__}")
+        h = C.c_void_p()
+        _lib.check(getattr(_lib.lib(), name)(self.h, other.h, C.byref(h)))
+        return DeviceTTO._adopt(h)
+
+    def mul(self, B: "DeviceTTO") -> "DeviceTTO":
+        """A * B — src/tt_operations.jl:162-172 (ranks multiply)."""
+        return self._binary("ttn_tto_mul", B)
+
+    def inner(self, B: "DeviceTTO") -> "DeviceTTO":
+        """A ⨝ B, the inner core product — src/tt_operations.jl:198-216 (dims and ranks multiply)."""
+        return self._binary("ttn_tto_inner", B)
+
+    def add(self, B: "DeviceTTO") -> "DeviceTTO":
+        """A + B — src/tt_operations.jl:71-95 (ranks add, d >= 2)."""
+        return self._binary("ttn_tto_add", B)
+
+    def scale(self, a: float) -> "DeviceTTO":
+        """a * A — src/tt_operations.jl:271-281."""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tto_scale(float(a), self.h, C.byref(h)))
+        return DeviceTTO._adopt(h)
+
+    def sub(self, B: "DeviceTTO") -> "DeviceTTO":
+        """A - B = (-1.0 * B) + A, in that order — src/tt_operations.jl:289-291."""
+        if not isinstance(B, DeviceTTO):
+            raise TypeError(f"sub: expected a DeviceTTO, got {type(B).__name__}")
+        return B.scale(-1.0).add(self)
+
+    def kron(self, B: "DeviceTTO") -> "DeviceTTO":
+        """kron(A, B) / A ⊗ B — src/tt_operations.jl:427-435; with equal ranks at the joint also concatenate(A, B),
+        src/tt_tools.jl:723-735."""
+        return self._binary("ttn_tto_kron", B)
+
+    def to_tt(self, batch: int = 1, cap_rks: Sequence[int] | None = None) -> "DeviceTT":
+        """tto_to_ttv(A) in every train of a new batch — src/tt_tools.jl:296-304."""
+        y = DeviceTT([n * n for n in self.dims], cap_rks if cap_rks is not None else self.rks, batch)
+        _lib.check(_lib.lib().ttn_tto_to_tt(self.h, y.h))
+        return y
+
+    @classmethod
+    def from_tt(cls, x: "DeviceTT", b: int = 0) -> "DeviceTTO":
+        """ttv_to_tto of train b with its current ranks — src/tt_tools.jl:323-333."""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tto_from_tt(x.h, int(b), C.byref(h)))
+        return cls._adopt(h)
+
+    def compress(self, max_bond: int = 2 ** 62, truncerr: float = 0.0, sweeps: int = 1) -> "DeviceTTO":
+        """ttv_to_tto(tt_compress!(tto_to_ttv(A), max_bond; truncerr, sweeps)) without leaving the device."""
+        assert sweeps >= 1, "sweeps must be >= 1"
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tto_compress(self.h, int(min(max_bond, 2 ** 62)), float(truncerr), int(sweeps), C.byref(h)))
+        return DeviceTTO._adopt(h)
+
+    def ranks(self) -> List[int]:
+        return list(self.rks)
+
+    def download(self) -> TToperator:
+        cores = [np.zeros((self.dims[k], self.dims[k], self.rks[k], self.rks[k + 1]), order="F") for k in range(self.N)]
+        _lib.check(_lib.lib().ttn_tto_download(self.h, _ptrs(cores)))
+        return TToperator(self.N, cores, self.dims, list(self.rks), list(self.ot))
 
     def free(self):
         if self.h:
@@ -84,6 +170,29 @@ class DeviceTT:
         cores = [np.zeros((self.dims[k], rks[k], rks[k + 1]), order="F") for k in range(self.N)]
         _lib.check(_lib.lib().ttn_tt_download(self.h, int(b), _ptrs(cores)))
         return TTvector(self.N, cores, self.dims, rks, ot)
+
+    # operator algebra (csrc/ttn_opalg_kernels.h)
+    def kron(self, y: "DeviceTT", cap_rks: Sequence[int] | None = None) -> "DeviceTT":
+        """kron(x, y) / x ⊗ y train by train — src/tt_operations.jl:440-450."""
+        if not isinstance(y, DeviceTT):
+            raise TypeError(f"kron: expected a DeviceTT, got {type(y).__name__}")
+        z = DeviceTT(self.dims + y.dims, cap_rks if cap_rks is not None else self.cap[:-1] + y.cap, self.batch)
+        _lib.check(_lib.lib().ttn_tt_kron(self.h, y.h, z.h))
+        return z
+
+    def outer(self, y: "DeviceTT", b: int = 0) -> DeviceTTO:
+        """outer_product(x_b, y_b) — src/tt_operations.jl:297-304."""
+        if not isinstance(y, DeviceTT):
+            raise TypeError(f"outer: expected a DeviceTT, got {type(y).__name__}")
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tt_outer(self.h, y.h, int(b), C.byref(h)))
+        return DeviceTTO._adopt(h)
+
+    def diag_tto(self, b: int = 0) -> DeviceTTO:
+        """ttv_to_diag_tto(x_b) — src/tt_operations.jl:310-338."""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tt_diag_tto(self.h, int(b), C.byref(h)))
+        return DeviceTTO._adopt(h)
 
     def free(self):
         if self.h:

@@ -12,6 +12,7 @@ meaning and error behaviour:
     orthogonalize(x; i=1)                    src/tt_tools.jl:511-543
     _tt_bond_truncate!, tt_compress!         src/tt_tools.jl:743-789   (``!`` -> trailing ``_``)
     r_and_d_to_rks                           src/tt_tools.jl:407-425
+    TToperator * TToperator, +, -, scalar *  src/tt_operations.jl:71-95, :162-172, :271-291   (opalg.py)
 
 Every arithmetic function calls libttn_hip.so; nothing here computes on the CPU.
 Site numbers (``i``, ``k``) are 1-based like the reference.  Cores are numpy arrays of shape
@@ -92,6 +93,29 @@ class TToperator:
     def __mul__(self, v):
         if isinstance(v, TTvector):
             return apply(self, v)
+        from . import opalg
+        if isinstance(v, TToperator):
+            return opalg.tto_mul(self, v)
+        if isinstance(v, (int, float, np.integer, np.floating)):
+            return opalg.tto_scale(v, self)
+        return NotImplemented
+
+    def __rmul__(self, a):
+        from . import opalg
+        if isinstance(a, (int, float, np.integer, np.floating)):
+            return opalg.tto_scale(a, self)
+        return NotImplemented
+
+    def __add__(self, other):
+        from . import opalg
+        if isinstance(other, TToperator):
+            return opalg.tto_add(self, other)
+        return NotImplemented
+
+    def __sub__(self, other):
+        from . import opalg
+        if isinstance(other, TToperator):
+            return opalg.tto_sub(self, other)
         return NotImplemented
 
     def __call__(self, v: TTvector, *_):       # (A::TToperator)(x), src/tt_operations.jl:151-157
