@@ -8,7 +8,8 @@
  * would add is shown in INTEGRATION.md and julia/TTNBackend.jl.
  *
  * Conventions
- *   - plain C, no C++/torch types; all integers are int64_t, all payload is double (fp64);
+ *   - plain C, no C++/torch types; all integers are int64_t, all payload is double (fp64; ComplexF64 handles: interleaved
+ *     (re, im) pairs of doubles, see "ComplexF64 trains and operators" below);
  *   - arrays are COLUMN-MAJOR exactly as the reference stores them:
  *       vector core  k : (n_k, r_{k-1}, r_k)            offset i + n*(a + r_{k-1}*b)
  *       operator core k: (n_k, n_k, R_{k-1}, R_k)       offset i + n*(j + n*(a + R_{k-1}*b))
@@ -448,6 +449,57 @@ int ttn_apply_compress_rank_bound(int64_t d, const int64_t* dims, const int64_t*
 int ttn_apply_compress_f64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks,
                            const double* const* X_cores, const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks,
                            int64_t max_bond, double truncerr, int64_t sweeps);
+
+/* ---- ComplexF64 trains and operators (csrc/ttn_cplx_kernels.h) ------------------------------------------------
+ * The element type of a handle is fixed at creation: ttn_tt_create / ttn_tto_create make Float64 handles, the two creators below
+ * ComplexF64 ones.  A complex core is the reference's Array{ComplexF64,3} as it lies: column-major (n, r_l, r_r) (operator:
+ * (n, n, R_l, R_r)), interleaved (re, im); every `double*` that points at cores of a complex handle points at such pairs, so a core
+ * of n r_l r_r numbers is 2 n r_l r_r doubles.  ttn_tt_upload / download / ranks / max_ranks / replicate / copy (same type on both
+ * sides) / batch / free, ttn_tto_free / ranks / set_ot / download, ttn_compress_status and ttn_status_all work on either kind.
+ * On ComplexF64 handles:
+ *   ttn_apply           complex operator x complex train, REAL operator x complex train, complex operator x REAL train; y must be a
+ *                       complex handle (k_zapply).  A complex y with a real operator and a real train is refused.
+ *   ttn_add             all three complex (k_add on the (2n, r, r') real view of the cores: + only copies)
+ *   ttn_hadamard        all three complex, no conjugation (tt_operations.jl:343-361)
+ *   ttn_scale           real factor; ttn_scale_c64 a complex one (re, im); ttn_scale_batch_c64 one complex factor per train
+ *                       (a: HOST, `batch` interleaved pairs).  The reference's rule: the first core with ot == 0, else core 1; a == 0
+ *                       gives the zero train with ot reset.
+ *   ttn_dot             both complex; the FIRST argument is conjugated (tt_operations.jl:243-248); `out` receives `batch` interleaved
+ *                       (re, im) pairs, i.e. 2 * batch doubles.  ttn_norm: `batch` doubles, sqrt(max(real(dot(a, a)), 0)).
+ *   ttn_compress, ttn_bond_truncate, ttn_sweep   the contract of the Float64 calls (one workgroup per train, device-resident ranks, the
+ *                       same rank rule, sqrt(s) on both sides, no gauge step): Householder QR of the long side, then one-sided
+ *                       complex Jacobi on the square factor of the short side.  Limits: merged matrices with short side <= 512 and
+ *                       long side <= 8192 complex numbers (TTN_ERR_UNSUPPORTED before any launch).
+ *   ttn_apply_compress  ttn_apply, then ttn_compress (no fused complex merge); every check runs before y is touched.
+ * Refused with TTN_ERR_UNSUPPORTED before any launch, with a message that names the call: a call above whose vector operands differ
+ * in element type, and a ComplexF64 handle given to any Float64-only entry point: the linear solvers and eigensolvers,
+ * ttn_orthogonalize, ttn_hadamard_ttm, ttn_swap_sites, ttn_ttv_decomp, ttn_scale_batch, the operator algebra (ttn_tto_mul / inner /
+ * add / scale / kron / compress / to_tt / from_tt, ttn_tt_outer / diag_tto / kron), ttn_apply_begin / _sweep, ttn_tt_core_extent /
+ * _export / _import, ttn_sv_capture. */
+int ttn_tt_create_c64(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out);
+int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out);
+int ttn_tt_dtype(ttn_tt_t h, int* cplx);      /* *cplx = 0 Float64, 1 ComplexF64 */
+int ttn_tto_dtype(ttn_tto_t h, int* cplx);
+int ttn_scale_c64(double re, double im, ttn_tt_t x, ttn_tt_t y);
+int ttn_scale_batch_c64(const double* a, ttn_tt_t x, ttn_tt_t y);
+/* Stateless ComplexF64 drop-ins for one train: the argument lists of the _f64 calls, every core buffer interleaved.  apply and
+ * apply_compress take the two mixed forms too: a_cplx / x_cplx say whether the operator / the train is complex (at least one must
+ * be); Y is always complex.  ttn_dot_c64: out[0], out[1] = re, im.  ttn_scale_host_c64: the factor is (re, im). */
+int ttn_apply_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                  const int64_t* X_rks, double* const* Y_cores, int a_cplx, int x_cplx);
+int ttn_dot_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* B_cores,
+                const int64_t* B_rks, double* out);
+int ttn_hadamard_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                     const int64_t* Y_rks, double* const* Z_cores);
+int ttn_add_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                const int64_t* Y_rks, double* const* Z_cores);
+int ttn_scale_host_c64(int64_t d, const int64_t* dims, double re, double im, const double* const* X_cores, const int64_t* X_rks,
+                       const int64_t* X_ot, double* const* Y_cores, int64_t* Y_ot);
+int ttn_compress_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t max_bond, double truncerr, int64_t sweeps);
+int ttn_bond_truncate_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond, double truncerr);
+int ttn_apply_compress_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                           const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks, int64_t max_bond, double truncerr, int64_t sweeps,
+                           int a_cplx, int x_cplx);
 
 /* r_and_d_to_rks(rks, dims; rmax)   src/tt_tools.jl:407-425 (host-side integer helper, bit-exact) */
 int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int64_t* rks, int64_t rmax, int64_t* out);

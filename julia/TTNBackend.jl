@@ -3,8 +3,9 @@
 # image has no Julia runtime (see DESIGN.md §2); the same C ABI is exercised through ctypes by
 # tensortrainnumerics.jl_amd/tt.py, which mirrors this file function for function.
 #
-# Only `TTvector{Float64}` / `TToperator{Float64}` methods are overloaded; every other eltype
-# (ComplexF64, Float32, Int — test/test_tt_tools.jl:576-596) falls through to the generic Julia methods.
+# `TTvector{Float64}` / `TToperator{Float64}` methods are overloaded, and for ComplexF64 `*` (with the two mixed forms), `+`, `dot`
+# and `tt_compress!`; every other eltype (Float32, Int — test/test_tt_tools.jl:576-596) and every other ComplexF64 method falls
+# through to the generic Julia methods.
 module TTNBackend
 
 using TensorTrainNumerics
@@ -159,6 +160,79 @@ function tt_compress!(ψ::TTvector{Float64, N}, max_bond::Int; truncerr::Real = 
     GC.@preserve bufs pb _chk(ccall((:ttn_compress_f64, LIB), Cint,
         (Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Int64, Float64, Int64),
         N, _dims(ψ.ttv_dims), pb, rks, min(max_bond, typemax(Int64) >> 1), Float64(truncerr), sweeps))
+    for k in 1:N
+        n = ψ.ttv_dims[k]
+        ψ.ttv_vec[k] = reshape(bufs[k][1:(n * rks[k] * rks[k + 1])], n, rks[k], rks[k + 1])
+    end
+    ψ.ttv_rks .= rks
+    return ψ
+end
+
+# ---- ComplexF64 (include/ttn.h, "ComplexF64 trains and operators"): `*` (complex x complex and the two mixed forms), `+`, `dot`,
+# `tt_compress!` bound to the stateless _c64 entry points.  A Julia Array{ComplexF64} is interleaved (re, im) in memory, which is what
+# the library reads, so the pointers are passed as they are.  Like the rest of this file these lines have NEVER been executed.
+const _CF = ComplexF64
+_cptrs(v::Vector{<:Array{_CF}}) = Ptr{Float64}[Ptr{Float64}(pointer(c)) for c in v]
+_anyptrs(v::Vector{<:Array{Float64}}) = _ptrs(v)
+_anyptrs(v::Vector{<:Array{_CF}}) = _cptrs(v)
+
+function _apply_c64(A::TToperator{TA, N}, v::TTvector{TV, N}) where {TA, TV, N}
+    @assert A.tto_dims == v.ttv_dims "Incompatible dimensions"
+    y = zeros_tt(_CF, A.tto_dims, A.tto_rks .* v.ttv_rks)
+    pa, px, py = _anyptrs(A.tto_vec), _anyptrs(v.ttv_vec), _cptrs(y.ttv_vec)
+    GC.@preserve A v y pa px py _chk(ccall((:ttn_apply_c64, LIB), Cint,
+        (Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}, Cint, Cint),
+        N, _dims(A.tto_dims), pa, A.tto_rks, px, v.ttv_rks, py, Cint(TA == _CF), Cint(TV == _CF)))
+    return y
+end
+*(A::TToperator{_CF, N}, v::TTvector{_CF, N}) where {N} = _apply_c64(A, v)
+*(A::TToperator{Float64, N}, v::TTvector{_CF, N}) where {N} = _apply_c64(A, v)      # Δ * ψ, ψ from real-time TDVP
+*(A::TToperator{_CF, N}, v::TTvector{Float64, N}) where {N} = _apply_c64(A, v)      # fourier_qtto * qtt_sin
+
+function +(x::TTvector{_CF, N}, y::TTvector{_CF, N}) where {N}
+    @assert x.ttv_dims == y.ttv_dims "Incompatible dimensions"
+    rks = x.ttv_rks + y.ttv_rks; rks[1] = 1; rks[end] = 1
+    z = zeros_tt(_CF, x.ttv_dims, rks)
+    px, py, pz = _cptrs(x.ttv_vec), _cptrs(y.ttv_vec), _cptrs(z.ttv_vec)
+    GC.@preserve x y z px py pz _chk(ccall((:ttn_add_c64, LIB), Cint,
+        (Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}),
+        N, _dims(x.ttv_dims), px, x.ttv_rks, py, y.ttv_rks, pz))
+    return z
+end
+
+# dot(A, B) conjugates its FIRST argument (src/tt_operations.jl:243-248)
+function TensorTrainNumerics.dot(A::TTvector{_CF, N}, B::TTvector{_CF, N}) where {N}
+    @assert A.ttv_dims == B.ttv_dims "TT dimensions are not compatible"
+    out = zeros(Float64, 2)
+    pa, pb = _cptrs(A.ttv_vec), _cptrs(B.ttv_vec)
+    GC.@preserve A B pa pb out _chk(ccall((:ttn_dot_c64, LIB), Cint,
+        (Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Float64}),
+        N, _dims(A.ttv_dims), pa, A.ttv_rks, pb, B.ttv_rks, out))
+    return complex(out[1], out[2])
+end
+
+function tt_compress!(ψ::TTvector{_CF, N}, max_bond::Int; truncerr::Real = 0.0, sweeps::Int = 1, verbose::Bool = false) where {N}
+    @assert(sweeps ≥ 1, "sweeps must be >= 1")
+    if verbose
+        for sw in 1:sweeps
+            @info "TT compress: sweep $sw (L→R)"
+            @info "TT compress: sweep $sw (R→L)"
+        end
+    end
+    mb = min(max_bond, typemax(Int64) >> 1)
+    need = zeros(Int64, N + 1)
+    _chk(ccall((:ttn_compress_rank_bound, LIB), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}),
+        N, _dims(ψ.ttv_dims), ψ.ttv_rks, mb, sweeps, 0, need, C_NULL))
+    bufs = [zeros(_CF, ψ.ttv_dims[k] * need[k] * need[k + 1]) for k in 1:N]
+    for k in 1:N
+        copyto!(bufs[k], vec(ψ.ttv_vec[k]))
+    end
+    rks = copy(ψ.ttv_rks)
+    pb = Ptr{Float64}[Ptr{Float64}(pointer(c)) for c in bufs]
+    GC.@preserve bufs pb _chk(ccall((:ttn_compress_c64, LIB), Cint,
+        (Int64, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Int64, Float64, Int64),
+        N, _dims(ψ.ttv_dims), pb, rks, mb, Float64(truncerr), sweeps))
     for k in 1:N
         n = ψ.ttv_dims[k]
         ψ.ttv_vec[k] = reshape(bufs[k][1:(n * rks[k] * rks[k + 1])], n, rks[k], rks[k + 1])

@@ -6,8 +6,9 @@ The arithmetic lives in csrc/*.h, csrc/ttn_api.hip -> libttn_hip.so (hand-writte
 """
 from . import _lib, constructors, cross, device, opalg, pipeline, qtt, shard, solvers, tdvp, tt
 from ._lib import TTNError, build, ensure_init, finalize
-from .constructors import (Delta, Nabla, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn, qtt_cos, qtt_exp, qtt_polynom, qtt_sin,
-                           qtt_to_vector, rand_tt, shift, toeplitz_to_qtto, xxx_tto, xxz_tto, zeros_tt, zeros_tto)
+from .constructors import (Delta, Nabla, fourier_qtto, function_to_qtt_uniform, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn,
+                           qtt_cos, qtt_exp, qtt_polynom, qtt_sin, qtt_to_vector, rand_tt, reverse_qtt_bits, shift, toeplitz_to_qtto,
+                           xxx_tto, xxz_tto, zeros_tt, zeros_tto)
 from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_integrate
 from .device import DeviceTT, DeviceTTO, StreamTimer
 from .opalg import (concatenate, kron, outer_product, tto_add, tto_compress_, tto_inner, tto_mul, tto_scale, tto_sub, tto_to_ttv,

@@ -137,6 +137,21 @@ SIGNATURES = {
     "ttn_apply_compress_f64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64, p_i64, i64, C.c_double, i64]),
     "ttn_bond_truncate_f64": (C.c_int, [i64, p_i64, pp_f64, p_i64, i64, i64, C.c_double]),
     "ttn_r_and_d_to_rks": (C.c_int, [i64, p_i64, i64, p_i64, i64, p_i64]),
+    # ComplexF64 handles and stateless entry points (interleaved re / im doubles)
+    "ttn_tt_create_c64": (C.c_int, [i64, p_i64, p_i64, i64, p_handle]),
+    "ttn_tto_create_c64": (C.c_int, [i64, p_i64, p_i64, pp_f64, p_handle]),
+    "ttn_tt_dtype": (C.c_int, [handle, C.POINTER(C.c_int)]),
+    "ttn_tto_dtype": (C.c_int, [handle, C.POINTER(C.c_int)]),
+    "ttn_scale_c64": (C.c_int, [C.c_double, C.c_double, handle, handle]),
+    "ttn_scale_batch_c64": (C.c_int, [p_f64, handle, handle]),
+    "ttn_apply_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64, C.c_int, C.c_int]),
+    "ttn_dot_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, p_f64]),
+    "ttn_hadamard_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64]),
+    "ttn_add_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64]),
+    "ttn_scale_host_c64": (C.c_int, [i64, p_i64, C.c_double, C.c_double, pp_f64, p_i64, p_i64, pp_f64, p_i64]),
+    "ttn_compress_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, i64, C.c_double, i64]),
+    "ttn_bond_truncate_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, i64, i64, C.c_double]),
+    "ttn_apply_compress_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64, p_i64, i64, C.c_double, i64, C.c_int, C.c_int]),
 }
 
 _lib = None

@@ -8,7 +8,9 @@ benchmark uses for "rank-r random TTvector" inputs.
     qtt_sin / qtt_cos / qtt_exp     src/qtt_tools.jl:116-175
     qtt_polynom                     src/qtt_tools.jl:88-110
     rand_tt                         src/tt_tools.jl:100-139 (randn replaced by a portable stream)
-    qtt_to_vector                   src/qtt_tools.jl:57-71 (densifier used by small tests)
+    qtt_to_vector                   src/qtt_tools.jl:57-71 (densifier used by small tests; real or complex trains)
+    fourier_qtto, reverse_qtt_bits  src/tt_transformations.jl (the QFT as a complex TToperator of rank K + 1)
+    function_to_qtt_uniform         src/qtt_tools.jl:73-82
 
 These are rank-<=5 closed forms evaluated once per problem: host code, not GPU work.
 """
@@ -259,3 +261,110 @@ def xxz_tto(d: int, J: float = 1.0, Delta: float = 1.0, h: float = 0.0, field="z
 def xxx_tto(d: int, J: float = 1.0, h: float = 0.0, field="z") -> TToperator:
     """J (H_xx + H_yy + H_zz) + h H_field (src/tt_operators.jl:250-259)."""
     return heisenberg_xyz_tto(d, jx=J, jy=J, jz=J, lam=h, field=field)
+
+
+# ---------------------------------------------------------------------------------------------
+# QTT Fourier transform — src/tt_transformations.jl (arXiv:2404.03182): Chebyshev-Lobatto interpolation of the phase in every core.
+# ---------------------------------------------------------------------------------------------
+def _sincospi(x: float):
+    """(sin(pi x), cos(pi x)) with the argument reduced exactly first, so that integers and half-integers give exact zeros and ones
+    as Julia's sinpi / cospi / cispi do."""
+    r = math.remainder(x, 2.0)                      # exact, in [-1, 1]
+    if abs(r) <= 0.5:
+        return math.sin(math.pi * r), math.cos(math.pi * r)
+    t = math.copysign(1.0, r) - r                   # exact (Sterbenz): sin(pi r) = sin(pi t), cos(pi r) = -cos(pi t)
+    return math.sin(math.pi * t), -math.cos(math.pi * t)
+
+
+def _cheb_lobatto_grid(K: int):
+    """cheb_lobatto_grid(K) (:6-11): nodes c_j = (1 - cos(pi j / K)) / 2 in [0, 1] and barycentric weights."""
+    c = np.array([0.5 * (1.0 - _sincospi(j / K)[1]) for j in range(K + 1)])
+    w = np.array([(0.5 if j in (0, K) else 1.0) * (-1.0) ** j for j in range(K + 1)])
+    return c, w
+
+
+def _lagrange_eval(c: np.ndarray, w: np.ndarray, alpha: int, x: float) -> float:
+    """lagrange_eval (:13-24): the barycentric form; 1 within 1e-14 of the node itself."""
+    xa = float(c[alpha])
+    if abs(x - xa) <= 1.0e-14:
+        return 1.0
+    with np.errstate(divide="ignore"):
+        num = w[alpha] / np.float64(x - xa)
+        denom = np.float64(0.0)
+        for j in range(len(c)):
+            denom = denom + w[j] / np.float64(x - c[j])
+    return float(num / denom)
+
+
+def fourier_qtto(d: int, sign: float = -1.0, K: int = 25, normalize: bool = True) -> TToperator:
+    """fourier_qtto(d; sign = -1.0, K = 25, normalize = true) — src/tt_transformations.jl:38-77: the discrete Fourier transform of 2^d
+    points as a ComplexF64 TToperator of ranks [1, K + 1, ..., K + 1, 1]; the output comes in bit-reversed order (reverse_qtt_bits).
+    Core entries A[s, t, a, b] = L_a((s + c_b) / 2) cispi(sign (s + c_b) t); the first core sums over a, the last keeps b = 1;
+    ``normalize`` scales the first core by 1 / sqrt(2^d).  Host code (NumPy), evaluated once per problem.  d = 1 reproduces the
+    reference literally: its single core is the LAST core (2, 2, K + 1, 1) while tto_rks says [1, 1]."""
+    assert d >= 1
+    c, w = _cheb_lobatto_grid(K)
+    r = K + 1
+    A = np.zeros((2, 2, r, r), dtype=np.complex128, order="F")
+    for al in range(r):
+        for be in range(r):
+            for sg in range(2):
+                L = _lagrange_eval(c, w, al, 0.5 * (sg + c[be]))
+                for ta in range(2):
+                    sn, cs = _sincospi(sign * (sg + c[be]) * ta)
+                    A[sg, ta, al, be] = complex(L * cs, L * sn)          # real * cispi(...)
+    AL = np.zeros((2, 2, 1, r), dtype=np.complex128, order="F")
+    for be in range(r):
+        for sg in range(2):
+            for ta in range(2):
+                acc = complex(0.0, 0.0)
+                for al in range(r):
+                    acc = acc + complex(A[sg, ta, al, be])
+                AL[sg, ta, 0, be] = acc
+    AR = np.array(A[:, :, :, :1], order="F")
+    cores = [AL] + [A.copy(order="F") for _ in range(max(d - 2, 0))] + [AR]
+    if d == 1:
+        cores = [AR]
+    if normalize:
+        cores[0] = np.asfortranarray(cores[0] * (1.0 / math.sqrt(2.0 ** d)))
+    return TToperator(d, cores, (2,) * d, [1] + [r] * (d - 1) + [1], [0] * d)
+
+
+def reverse_qtt_bits(x: TTvector) -> TTvector:
+    """reverse_qtt_bits(x) — src/tt_transformations.jl:79-86: the sites in reverse order, each core with its two bond indices exchanged."""
+    vec = [np.asfortranarray(np.transpose(cr, (0, 2, 1))) for cr in reversed(x.ttv_vec)]
+    rks = [1] + list(reversed(x.ttv_rks[1:-1])) + [1]
+    return TTvector(x.N, vec, tuple(reversed(x.ttv_dims)), rks, list(reversed(x.ttv_ot)))
+
+
+def _ttv_decomp_host(tensor: np.ndarray, tol: float = 1.0e-12) -> TTvector:
+    """ttv_decomp(tensor; index = 1, tol) (src/tt_tools.jl:186-252) with LAPACK on the host, for complex tensors: the right-to-left
+    hierarchical SVD, singular values below tol (absolute) dropped, gauge flags [0, 1, ..., 1]."""
+    dims = tuple(int(v) for v in tensor.shape)
+    d = len(dims)
+    rks = [1] * (d + 1)
+    vec: list = [None] * d
+    cur = np.asarray(tensor)
+    for i in range(d, 1, -1):
+        cur = np.reshape(cur, (-1, dims[i - 1] * rks[i]), order="F")
+        u, sv, vt = np.linalg.svd(cur, full_matrices=False)
+        r = int(np.count_nonzero(sv >= tol))
+        rks[i - 1] = r
+        vec[i - 1] = np.asfortranarray(np.transpose(np.reshape(vt[:r, :], (r, dims[i - 1], rks[i]), order="F"), (1, 0, 2)))
+        cur = u[:, :r] * sv[None, :r]
+    vec[0] = np.asfortranarray(np.reshape(cur, (dims[0], 1, rks[1]), order="F"))
+    return TTvector(d, vec, dims, rks, [0] + [1] * (d - 1))
+
+
+def function_to_qtt_uniform(f, d: int) -> TTvector:
+    """function_to_qtt_uniform(f, d) — src/qtt_tools.jl:73-82: the samples f(n / 2^d), n = 0 .. 2^d - 1, as a QTT whose site 1 carries
+    the LEAST significant bit of n, by ttv_decomp of the 2 x ... x 2 tensor (tol 1e-12).  Real samples are decomposed on the device
+    (qtt.ttv_decomp, Float64).  Complex samples are decomposed on the HOST (NumPy's LAPACK SVD): the device decomposition is Float64
+    only, and a real-part + i imaginary-part sum would double the ranks."""
+    N = 2 ** d
+    y = np.array([f(n / N) for n in range(N)])
+    A = np.reshape(y, (2,) * d, order="F")          # A[b_1, ..., b_d] with n = sum b_k 2^(k-1): Julia's digits(n, base = 2) as a CartesianIndex
+    if np.iscomplexobj(A):
+        return _ttv_decomp_host(A.astype(np.complex128))
+    from .qtt import ttv_decomp
+    return ttv_decomp(A.astype(np.float64))

@@ -17,6 +17,7 @@
 #include "ttn_densefact_kernels.h"
 #include "ttn_cross_kernels.h"
 #include "ttn_opalg_kernels.h"
+#include "ttn_cplx_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -106,6 +107,7 @@ DevBuf* const g_bufs[] = {&g_scratch, &g_dout, &g_next_train, &g_pending_status,
 // ------------------------------------------------------------------------------------------------
 struct ttn_tt_s {
     int d = 0, batch = 0;
+    int el = 1;                               // doubles per element: 1 Float64, 2 ComplexF64 (interleaved; d_dims then holds 2 n_k, see ttn_cplx_kernels.h)
     std::vector<int64_t> dims, cap, bound;   // bound[m]: host upper bound on the current rank of any train
     std::vector<long long> off;               // d+1 slot offsets
     long long stride = 0;
@@ -130,6 +132,7 @@ struct ttn_tt_s {
 };
 struct ttn_tto_s {
     int d = 0;
+    int el = 1;                               // 1 Float64, 2 ComplexF64 (slots of twice the doubles; d_dims keeps n_k, d_dims2 holds 2 n_k^2)
     std::vector<int64_t> dims, rks;
     std::vector<long long> off;
     double* d_data = nullptr;
@@ -154,6 +157,22 @@ struct ttn_tto_s {
 };
 
 static bool same_dims(const std::vector<int64_t>& a, const std::vector<int64_t>& b) { return a == b; }
+
+// A Float64-only entry point that receives a ComplexF64 handle is refused before any launch: it would read half a slot as a whole one.
+static bool any_c64(std::initializer_list<const ttn_tt_s*> tts, std::initializer_list<const ttn_tto_s*> ops = {}) {
+    for (const ttn_tt_s* h : tts) if (h && h->el == 2) return true;
+    for (const ttn_tto_s* h : ops) if (h && h->el == 2) return true;
+    return false;
+}
+static int refuse_c64(const char* who) {
+    g_err = std::string(who) + ": Float64 only, a ComplexF64 handle is not supported";
+    return TTN_ERR_UNSUPPORTED;
+}
+#define F64_ONLY(who, ...) do { if (any_c64(__VA_ARGS__)) return refuse_c64(who); } while (0)
+static int refuse_mixed(const char* who) {
+    g_err = std::string(who) + ": the element types (Float64 / ComplexF64) of the handles do not fit this call";
+    return TTN_ERR_UNSUPPORTED;
+}
 
 // ttn_tt_free / ttn_status_all: bit `code` of the library-level word for every failure code recorded on the handle (which one is
 // reported is decided on the host, by the order of status_table)
@@ -204,6 +223,7 @@ int ttn_init(int device) {
         {(const void*)k_lu_trail, sizeof(double) * GEMM_LDS_TOTAL},
         {(const void*)k_cross_maxvol<false>, TTN_XV_LDS_BYTES},
         {(const void*)k_cross_maxvol<true>, TTN_XV_LDS_BYTES},
+        {(const void*)k_zcompress, TTN_ZC_LDS_BYTES},
     };
     for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
@@ -298,14 +318,27 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
 }
 
 // ---- ttn_tt ---------------------------------------------------------------------------------------
-int ttn_tt_create(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out) {
+static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out, int el);
+int ttn_tt_create(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out) { return tt_create_impl(d, dims, cap_rks, batch, out, 1); }
+int ttn_tt_create_c64(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out) { return tt_create_impl(d, dims, cap_rks, batch, out, 2); }
+int ttn_tt_dtype(ttn_tt_t h, int* cplx) {
+    if (!h || !cplx) return fail(TTN_ERR_ARG, "null pointer");
+    *cplx = h->el == 2 ? 1 : 0;
+    return TTN_OK;
+}
+int ttn_tto_dtype(ttn_tto_t h, int* cplx) {
+    if (!h || !cplx) return fail(TTN_ERR_ARG, "null pointer");
+    *cplx = h->el == 2 ? 1 : 0;
+    return TTN_OK;
+}
+static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out, int el) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!dims || !cap_rks || !out || d < 1 || batch < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: bad argument");
     for (int64_t k = 0; k < d; ++k) if (dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: dims must be >= 1");
     for (int64_t k = 0; k <= d; ++k) if (cap_rks[k] < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: ranks must be >= 1");
     ttn_tt_s* h = new ttn_tt_s();
-    h->d = (int)d; h->batch = (int)batch;
+    h->d = (int)d; h->batch = (int)batch; h->el = el;
     h->dims.assign(dims, dims + d);
     h->cap.assign(cap_rks, cap_rks + d + 1);
     h->bound.assign(d + 1, 1);          // every train starts as the rank-1 zero train
@@ -313,7 +346,7 @@ int ttn_tt_create(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_
     long long o = 0;
     for (int64_t k = 0; k < d; ++k) {
         h->off[k] = o;
-        long long sz = (long long)dims[k] * cap_rks[k] * cap_rks[k + 1];
+        long long sz = (long long)el * dims[k] * cap_rks[k] * cap_rks[k + 1];
         sz = (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
         o += sz;
     }
@@ -321,7 +354,7 @@ int ttn_tt_create(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_
     h->stride = o;
     h->ot.assign((size_t)batch * d, 0);
     std::vector<int> idims(d);
-    for (int64_t k = 0; k < d; ++k) idims[k] = (int)dims[k];
+    for (int64_t k = 0; k < d; ++k) idims[k] = (int)(el * dims[k]);
     std::vector<long long> cap64(cap_rks, cap_rks + d + 1);
     std::vector<long long> rk0((size_t)batch * (d + 1));
     for (int64_t b = 0; b < batch; ++b) for (int64_t m = 0; m <= d; ++m) rk0[b * (d + 1) + m] = 1;
@@ -386,7 +419,7 @@ int ttn_tt_upload(ttn_tt_t h, int64_t b, const double* const* cores, const int64
     HIPCHK(hipMemcpyAsync(h->d_rks + (size_t)b * (d + 1), r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     for (int k = 0; k < d; ++k) {
         if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tt_upload: null core");
-        const size_t sz = (size_t)h->dims[k] * rks[k] * rks[k + 1];
+        const size_t sz = (size_t)h->el * h->dims[k] * rks[k] * rks[k + 1];
         HIPCHK(hipMemcpyAsync(h->d_data + (size_t)b * h->stride + h->off[k], cores[k], sizeof(double) * sz, hipMemcpyHostToDevice, g_stream));
     }
     HIPCHK(hipStreamSynchronize(g_stream));   // host buffers may be released by the caller
@@ -452,7 +485,7 @@ int ttn_tt_download(ttn_tt_t h, int64_t b, double* const* cores) {
     HIPCHK(hipStreamSynchronize(g_stream));
     for (int k = 0; k < d; ++k) {
         if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tt_download: null core");
-        const size_t sz = (size_t)h->dims[k] * r64[k] * r64[k + 1];
+        const size_t sz = (size_t)h->el * h->dims[k] * r64[k] * r64[k + 1];
         HIPCHK(hipMemcpyAsync(cores[k], h->d_data + (size_t)b * h->stride + h->off[k], sizeof(double) * sz, hipMemcpyDeviceToHost, g_stream));
     }
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -464,11 +497,12 @@ int ttn_tt_copy(ttn_tt_t dst, ttn_tt_t src) {
     NEED_INIT();
     if (!dst || !src) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(dst->dims, src->dims) || dst->batch != src->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (dst->el != src->el) return refuse_mixed("ttn_tt_copy");
     for (int m = 0; m <= src->d; ++m) if (dst->cap[m] < src->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_tt_copy: destination capacity too small");
     // scale kernel with a = 1 on core -1 is a plain per-core copy that honours the two slot layouts
     const int d = src->d;
     long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)src->dims[k] * src->bound[k] * src->bound[k + 1]);
+    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)src->el * src->dims[k] * src->bound[k] * src->bound[k + 1]);
     hipLaunchKernelGGL(k_ranks_copy, dim3(src->batch), dim3(64), 0, g_stream, dst->dev(), src->dev());
     dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((maxsz + TTN_STREAM_TB - 1) / TTN_STREAM_TB, 2048)), (unsigned)d, (unsigned)src->batch);
     hipLaunchKernelGGL(k_scale, grid, dim3(TTN_STREAM_TB), 0, g_stream, src->dev(), dst->dev(), 1.0, -1, 0, (const int*)nullptr);
@@ -479,19 +513,22 @@ int ttn_tt_copy(ttn_tt_t dst, ttn_tt_t src) {
 }
 
 // ---- ttn_tto --------------------------------------------------------------------------------------
-int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) {
+static int tto_create_impl(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out, int el);
+int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 1); }
+int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 2); }
+static int tto_create_impl(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out, int el) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!dims || !rks || !cores || !out || d < 1) return fail(TTN_ERR_ARG, "ttn_tto_create: bad argument");
     ttn_tto_s* h = new ttn_tto_s();
-    h->d = (int)d;
+    h->d = (int)d; h->el = el;
     h->dims.assign(dims, dims + d);
     h->rks.assign(rks, rks + d + 1);
     h->off.resize(d + 1);
     long long o = 0;
     for (int64_t k = 0; k < d; ++k) {
         h->off[k] = o;
-        long long sz = (long long)dims[k] * dims[k] * rks[k] * rks[k + 1];
+        long long sz = (long long)el * dims[k] * dims[k] * rks[k] * rks[k + 1];
         sz = (sz + 1) & ~1LL;
         o += sz;
     }
@@ -499,10 +536,10 @@ int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const dou
     std::vector<double> flat((size_t)o, 0.0);
     for (int64_t k = 0; k < d; ++k) {
         if (!cores[k]) { delete h; return fail(TTN_ERR_ARG, "ttn_tto_create: null core"); }
-        std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)dims[k] * dims[k] * rks[k] * rks[k + 1]);
+        std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);
     }
     std::vector<int> idims(2 * d);
-    for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(dims[k] * dims[k]); }
+    for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(el * dims[k] * dims[k]); }
     std::vector<long long> r64(rks, rks + d + 1);
     h->ot.assign(d, 0);
     hipError_t e;
@@ -545,6 +582,29 @@ static dim3 stream_grid(long long max_items, int d, int batch) {
 // k_apply / k_hadamard / k_add count the fibres (p, q) of a core with 32-bit indices (ttn_stream_kernels.h): refuse larger cores here
 static bool stream_fibres_too_many(long long fibres) { return fibres >= (1LL << 31); }
 
+// ComplexF64 apply (k_zapply): complex operator and / or complex train into a complex y; the checks ran in ttn_apply
+static int zapply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
+    if (y->el != 2) return refuse_mixed("ttn_apply (a complex operand needs a ComplexF64 output handle)");
+    if (A->el != 2 && x->el != 2) return refuse_mixed("ttn_apply (a ComplexF64 output needs a complex operator or train)");
+    const int d = x->d;
+    long long items = 1;
+    for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
+    for (int k = 0; k < d; ++k) {
+        const long long P = (long long)A->rks[k] * x->bound[k], Q = (long long)A->rks[k + 1] * x->bound[k + 1];
+        if (stream_fibres_too_many(P * Q)) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
+        items = std::max(items, P * ((Q + TTN_ZAPPLY_K - 1) / TTN_ZAPPLY_K));
+    }
+    hipLaunchKernelGGL(k_ranks_mul_op, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
+    const dim3 grid = stream_grid(items, d, x->batch), tb(TTN_STREAM_TB);
+    if (A->el == 2 && x->el == 2) hipLaunchKernelGGL((k_zapply<true, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
+    else if (A->el == 2) hipLaunchKernelGGL((k_zapply<true, false>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
+    else hipLaunchKernelGGL((k_zapply<false, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
+    HIPCHK(hipGetLastError());
+    for (int m = 0; m <= d; ++m) y->bound[m] = A->rks[m] * x->bound[m];
+    std::fill(y->ot.begin(), y->ot.end(), 0);
+    return TTN_OK;
+}
+
 int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
@@ -552,6 +612,7 @@ int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (x == y) return fail(TTN_ERR_ARG, "ttn_apply: output must not alias the input");
+    if (A->el == 2 || x->el == 2 || y->el == 2) return zapply(A, x, y);
     const int d = x->d;
     long long maxfib = 0;
     for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
@@ -591,6 +652,7 @@ int ttn_hadamard(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     if (!same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible TT dimensions");
     if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_hadamard: output must not alias an input");
+    if (x->el != y->el || x->el != z->el) return refuse_mixed("ttn_hadamard");
     const int d = x->d;
     long long maxpq = 0;
     for (int m = 0; m <= d; ++m) if (z->cap[m] < x->bound[m] * y->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_hadamard: destination capacity too small");
@@ -599,6 +661,8 @@ int ttn_hadamard(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     hipLaunchKernelGGL(k_ranks_mul, dim3(x->batch), dim3(64), 0, g_stream, z->dev(), x->dev(), y->dev());
     bool qtt = true;
     for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
+    if (x->el == 2) hipLaunchKernelGGL(k_zhadamard, stream_grid((maxpq + TTN_ZHAD_K - 1) / TTN_ZHAD_K, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), z->dev());
+    else
     hipLaunchKernelGGL(k_hadamard, stream_grid(qtt ? (maxpq + TTN_HAD_K - 1) / TTN_HAD_K : maxpq, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), z->dev());
     HIPCHK(hipGetLastError());
     for (int m = 0; m <= d; ++m) z->bound[m] = x->bound[m] * y->bound[m];
@@ -613,6 +677,7 @@ int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     if (!same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_add: output must not alias an input");
+    if (x->el != y->el || x->el != z->el) return refuse_mixed("ttn_add");
     const int d = x->d;
     if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: the reference's + is only defined for d >= 2");
     std::vector<int64_t> zb(d + 1);
@@ -622,7 +687,8 @@ int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     for (int k = 0; k < d; ++k) maxpq = std::max<long long>(maxpq, (long long)zb[k] * zb[k + 1]);
     if (stream_fibres_too_many(maxpq)) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: 2^31 or more fibres in one core (32-bit element indices)");
     hipLaunchKernelGGL(k_ranks_add, dim3(x->batch), dim3(64), 0, g_stream, z->dev(), x->dev(), y->dev());
-    bool qtt = true;
+    // (a complex core (n, r, r') is byte for byte the real core (2n, r, r') and + only copies: k_add runs on that view)
+    bool qtt = x->el == 1;
     for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
     hipLaunchKernelGGL(k_add, stream_grid(qtt ? (maxpq + TTN_ADD_K - 1) / TTN_ADD_K : maxpq, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), z->dev());
     HIPCHK(hipGetLastError());
@@ -652,11 +718,58 @@ static int scaled_core(ttn_tt_t x, int& which, const int*& which_b) {
     return TTN_OK;
 }
 
+// a * x on ComplexF64 handles (k_zscale): one complex factor (ab null) or one per train (ab: device, interleaved; zero_b: which are 0)
+static int zscale(const char* who, double ar, double ai, const double* ab, const std::vector<char>* zero_b, ttn_tt_t x, ttn_tt_t y) {
+    const int d = x->d;
+    for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, (std::string(who) + ": destination capacity too small").c_str());
+    int which = 0;
+    const int* which_b = nullptr;
+    { int rc_ = scaled_core(x, which, which_b); if (rc_) return rc_; }
+    long long maxsz = 0;
+    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)x->dims[k] * x->bound[k] * x->bound[k + 1]);
+    const bool zero = !ab && ar == 0.0 && ai == 0.0;
+    if (x != y) hipLaunchKernelGGL(k_ranks_copy, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), x->dev());
+    hipLaunchKernelGGL(k_zscale, stream_grid((maxsz + 3) / 4, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), ar, ai, which, zero ? 1 : 0, which_b, ab);
+    HIPCHK(hipGetLastError());
+    y->bound = x->bound;
+    if (zero) std::fill(y->ot.begin(), y->ot.end(), 0); else y->ot = x->ot;
+    if (zero_b) for (int b = 0; b < x->batch; ++b) if ((*zero_b)[b]) for (int k = 0; k < d; ++k) y->ot[(size_t)b * d + k] = 0;
+    return TTN_OK;
+}
+
+int ttn_scale_c64(double re, double im, ttn_tt_t x, ttn_tt_t y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
+    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->el != 2 || y->el != 2) return refuse_mixed("ttn_scale_c64 (both handles must be ComplexF64)");
+    return zscale("ttn_scale_c64", re, im, nullptr, nullptr, x, y);
+}
+
+int ttn_scale_batch_c64(const double* a, ttn_tt_t x, ttn_tt_t y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!a || !x || !y) return fail(TTN_ERR_ARG, "null pointer");
+    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->el != 2 || y->el != 2) return refuse_mixed("ttn_scale_batch_c64 (both handles must be ComplexF64)");
+    int rc = g_dout.ensure(sizeof(double) * 2 * x->batch);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(g_dout.p, a, sizeof(double) * 2 * x->batch, hipMemcpyHostToDevice, g_stream));
+    std::vector<char> zb(x->batch);
+    for (int b = 0; b < x->batch; ++b) zb[b] = (a[2 * b] == 0.0 && a[2 * b + 1] == 0.0) ? 1 : 0;
+    rc = zscale("ttn_scale_batch_c64", 0.0, 0.0, g_dout.as<const double>(), &zb, x, y);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g_stream));      // `a` is caller memory and g_dout is reused by ttn_dot
+    return TTN_OK;
+}
+
 int ttn_scale(double a, ttn_tt_t x, ttn_tt_t y) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->el != y->el) return refuse_mixed("ttn_scale");
+    if (x->el == 2) return zscale("ttn_scale", a, 0.0, nullptr, nullptr, x, y);
     const int d = x->d;
     for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_scale: destination capacity too small");
     // i = findfirst(==(0), ot), else 1  (tt_operations.jl:262), per train
@@ -678,6 +791,7 @@ int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
     NEED_INIT();
     if (!a || !x || !y) return fail(TTN_ERR_ARG, "null pointer");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    F64_ONLY("ttn_scale_batch (ComplexF64 handles: ttn_scale_batch_c64)", {x, y});
     const int d = x->d;
     for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_scale_batch: destination capacity too small");
     int rc = g_dout.ensure(sizeof(double) * x->batch);
@@ -768,8 +882,44 @@ static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, in
     return g_dout.ensure(sizeof(double) * psi->batch);
 }
 
+// Limits of k_zcompress (include/ttn.h): short side <= 512, long side <= 8192 complex
+#define TTN_ZC_PMAX 512
+#define TTN_ZC_QMAX 8192
+static int zcompress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, int64_t k_single, int64_t max_bond, int64_t sweeps, int64_t k_first,
+                              int64_t k_last, std::vector<int64_t>& fin, long long& pmax, long long& qmax) {
+    std::vector<int64_t> need;
+    pmax = 1; qmax = 1;
+    rank_bounds(psi->d, psi->dims.data(), bound.data(), max_bond, sweeps, k_single, need, fin, pmax, qmax, k_first, k_last);
+    for (int m = 0; m <= psi->d; ++m)
+        if (need[m] > psi->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_compress: a bond rank can grow beyond the handle's capacity (see ttn_compress_rank_bound)");
+    if (pmax > TTN_ZC_PMAX || qmax > TTN_ZC_QMAX) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress (ComplexF64): merged matrix larger than 512 x 8192");
+    return g_scratch.ensure(sizeof(double) * (size_t)zcompress_scratch(pmax, qmax) * psi->batch);
+}
+static int launch_zcompress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, double truncerr, int64_t sweeps, int64_t k_first, int64_t k_last) {
+    const int d = psi->d;
+    if (d < 2 && k_single == 0) return TTN_OK;
+    std::vector<int64_t> fin;
+    long long pmax = 1, qmax = 1;
+    int rc = zcompress_precheck(psi, psi->bound, k_single, max_bond, sweeps, k_first, k_last, fin, pmax, qmax);
+    if (rc) return rc;
+    ZCompressArgs P;
+    P.tt = psi->dev();
+    P.max_bond = max_bond; P.truncerr = truncerr; P.sweeps = (int)sweeps;
+    P.k_single = (int)k_single; P.k_first = (int)k_first; P.k_last = (int)k_last;
+    P.scratch = g_scratch.as<double>();
+    P.scratch_stride = zcompress_scratch(pmax, qmax);
+    P.pmax = (int)pmax; P.qmax = (int)qmax;
+    P.status = psi->d_status;
+    P.sweep_stats = psi->d_status + psi->batch;
+    hipLaunchKernelGGL(k_zcompress, dim3(psi->batch), dim3(TTN_ZC_WG), TTN_ZC_LDS_BYTES, g_stream, P);
+    HIPCHK(hipGetLastError());
+    psi->bound = fin;
+    return TTN_OK;
+}
+
 static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, double truncerr, int64_t sweeps,
                            int64_t k_first = 0, int64_t k_last = 0, ttn_tto_t fuseA = nullptr, ttn_tt_t fusex = nullptr, int fused_first_real = 0) {
+    if (psi->el == 2) return launch_zcompress(psi, k_single, max_bond, truncerr, sweeps, k_first, k_last);
     const int d = psi->d;
     if (d < 2 && k_single == 0) return TTN_OK;
     std::vector<int64_t> fin;
@@ -851,6 +1001,7 @@ int ttn_sweep(ttn_tt_t psi, int64_t k_first, int64_t k_last, int64_t max_bond, d
 // of every train's slot carry it; they move to / from a dense [batch][that many] device buffer with one 2-D copy.
 int ttn_tt_core_extent(ttn_tt_t h, int64_t k, int64_t* doubles_per_train, int64_t* bound_left, int64_t* bound_right) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    F64_ONLY("ttn_tt_core_extent", {h});
     if (!h || k < 1 || k > h->d) return fail(TTN_ERR_ARG, "bad core index");
     const int64_t bl = h->bound[k - 1], br = h->bound[k];
     if (doubles_per_train) *doubles_per_train = h->dims[k - 1] * bl * br;
@@ -862,6 +1013,7 @@ int ttn_tt_core_extent(ttn_tt_t h, int64_t k, int64_t* doubles_per_train, int64_
 int ttn_tt_core_export(ttn_tt_t h, int64_t k, double* dev_buf, int64_t* dev_rks2) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tt_core_export", {h});
     if (!h || !dev_buf || !dev_rks2 || k < 1 || k > h->d) return fail(TTN_ERR_ARG, "bad argument");
     const size_t w = sizeof(double) * (size_t)(h->dims[k - 1] * h->bound[k - 1] * h->bound[k]);
     HIPCHK(hipMemcpy2DAsync(dev_buf, w, h->d_data + h->off[k - 1], sizeof(double) * (size_t)h->stride, w, h->batch,
@@ -874,6 +1026,7 @@ int ttn_tt_core_export(ttn_tt_t h, int64_t k, double* dev_buf, int64_t* dev_rks2
 int ttn_tt_core_import(ttn_tt_t h, int64_t k, const double* dev_buf, const int64_t* dev_rks2, int64_t bound_left, int64_t bound_right) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tt_core_import", {h});
     if (!h || !dev_buf || !dev_rks2 || k < 1 || k > h->d || bound_left < 1 || bound_right < 1) return fail(TTN_ERR_ARG, "bad argument");
     if (bound_left > h->cap[k - 1] || bound_right > h->cap[k]) return fail(TTN_ERR_CAPACITY, "ttn_tt_core_import: core does not fit the slot");
     const size_t w = sizeof(double) * (size_t)(h->dims[k - 1] * bound_left * bound_right);
@@ -892,6 +1045,18 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    if (A->el == 2 || x->el == 2 || y->el == 2) {             // ComplexF64: apply, then round (no fused complex merge)
+        if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+        if (y->el != 2 || (A->el != 2 && x->el != 2)) return refuse_mixed("ttn_apply_compress");
+        // what can refuse the rounding is checked on the product's ranks before y is touched
+        std::vector<int64_t> yb(x->d + 1), fin_;
+        for (int m = 0; m <= x->d; ++m) yb[m] = A->rks[m] * x->bound[m];
+        for (int m = 0; m <= x->d; ++m) if (y->cap[m] < yb[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
+        if (x->d >= 2) { long long pm_, qm_; int rc = zcompress_precheck(y, yb, 0, max_bond, sweeps, 0, 0, fin_, pm_, qm_); if (rc) return rc; }
+        int rc = ttn_apply(A, x, y);
+        if (rc) return rc;
+        return ttn_compress(y, max_bond, truncerr, sweeps);
+    }
     const char* nf = getenv("TTN_NOFUSE");
     if (x->d < 2 || (nf && atoi(nf))) {                     // nothing to fuse into / diagnostic switch
         int rc = ttn_apply(A, x, y);
@@ -922,6 +1087,7 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
 int ttn_apply_begin(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_apply_begin", {x, y}, {A});
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
@@ -938,6 +1104,7 @@ int ttn_apply_begin(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
 int ttn_apply_sweep(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t k_first, int64_t k_last, int64_t max_bond, double truncerr, int first_core_real) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_apply_sweep", {x, y}, {A});
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (k_first < 1 || k_first >= y->d || k_last < k_first || k_last >= y->d) return fail(TTN_ERR_BOND_INDEX, "ttn_apply_sweep: need 1 <= k_first <= k_last <= N-1 (one L->R pass)");
@@ -1014,6 +1181,7 @@ static int launch_chain(int kind, ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, int n, int
 int ttn_hadamard_ttm(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, double tol, int64_t rmax, int64_t work_cap) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_hadamard_ttm", {x, y, z});
     if (!x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible TT dimensions");
     if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
@@ -1046,6 +1214,7 @@ int ttn_hadamard_ttm(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, double tol, int64_t rma
 int ttn_swap_sites(ttn_tt_t x, int64_t nswaps, const int64_t* swaps, double threshold) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_swap_sites", {x});
     if (!x || nswaps < 0 || (nswaps > 0 && !swaps) || threshold < 0.0) return fail(TTN_ERR_ARG, "bad argument");
     const int d = x->d;
     const int64_t n = x->dims[0];
@@ -1075,6 +1244,7 @@ int ttn_swap_sites(ttn_tt_t x, int64_t nswaps, const int64_t* swaps, double thre
 int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_ttv_decomp", {z});
     if (!z || !tensors) return fail(TTN_ERR_ARG, "null argument");
     const int d = z->d;
     if (index < 1 || index > d) return fail(TTN_ERR_ARG, "index must be in 1:d");
@@ -1215,6 +1385,7 @@ static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std
 int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t sweep_count) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_als_linsolve", {b, x0, x}, {A});
     if (!A || !b || !x0 || !x) return fail(TTN_ERR_ARG, "null handle");
     if (sweep_count < 1) return fail(TTN_ERR_SWEEPS, "sweep_count must be >= 1");
     if (!same_dims(A->dims, b->dims) || !same_dims(b->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -1472,6 +1643,7 @@ static std::vector<int> g_cg_iters_host;       // total CG iterations per train 
 static int two_site_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t rmax, int mode, const std::vector<int64_t>& plan,
                              const LocalSolver& ls = LocalSolver()) {
     NEED_INIT();
+    F64_ONLY("two-site linear solver", {b, x0, x}, {A});
     if (!A || !b || !x0 || !x) return fail(TTN_ERR_ARG, "null handle");
     if (tol < 0.0 || rmax < 1) return fail(TTN_ERR_ARG, "bad tol / rmax");
     if (!same_dims(A->dims, b->dims) || !same_dims(b->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -1532,6 +1704,7 @@ int ttn_mals_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double t
 
 static int dmrg_linsolve_impl(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
                               const int64_t* rmax_schedule, const LocalSolver& ls) {
+    F64_ONLY("ttn_dmrg_linsolve", {b, x0, x}, {A});
     if (!rmax_schedule) return fail(TTN_ERR_ARG, "dmrg_linsolve: empty schedule");
     std::vector<int64_t> plan;
     const int rc = sweep_plan("dmrg_linsolve", TTN_ERR_UNSUPPORTED, n_stages, sweep_schedule, rmax_schedule, plan);
@@ -1588,6 +1761,7 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     const char* who = mode == 1 ? "dmrg_eigsolve" : "mals_eigsolve";
     auto err = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
     NEED_INIT();
+    F64_ONLY("two-site eigensolver", {x0, x}, {A});
     if (!A || !x0 || !x) return err(TTN_ERR_ARG, "null handle");
     if (!rmax_schedule || !E_out || !r_out) return err(TTN_ERR_ARG, "null schedule / history buffer");
     if (!same_dims(A->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -1719,12 +1893,41 @@ int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps) {
     return rc ? rc : status_error(seen);
 }
 
+// dot on ComplexF64 handles (k_zdot): out receives `batch` interleaved (re, im) pairs
+static int zdot(ttn_tt_t a, ttn_tt_t b, double* out) {
+    const int d = a->d;
+    long long wmax = 1, tmax = 1;
+    for (int m = 0; m <= d; ++m) wmax = std::max<long long>(wmax, a->bound[m] * b->bound[m]);
+    for (int k = 0; k < d; ++k) tmax = std::max<long long>(tmax, a->dims[k] * a->bound[k] * b->bound[k + 1]);
+    const long long per_train = 2 * (wmax + tmax);
+    const int in_lds = per_train <= TTN_ZDOT_LDS_DOUBLES ? 1 : 0;
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * a->batch);
+    if (rc) return rc;
+    rc = g_dout.ensure(sizeof(double) * 2 * a->batch);
+    if (rc) return rc;
+    ZDotArgs P;
+    P.a = a->dev(); P.b = b->dev();
+    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
+    P.wmax = wmax; P.tmax = tmax; P.in_lds = in_lds;
+    P.out = g_dout.as<double>();
+    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
+    hipLaunchKernelGGL(k_zdot, dim3(a->batch), dim3(TTN_ZC_WG), in_lds ? sizeof(double) * (size_t)per_train : 0, g_stream, P);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
+    g_have_launch_ms = true;
+    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * 2 * a->batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return TTN_OK;
+}
+
 int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!a || !b || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (!same_dims(a->dims, b->dims)) return fail(TTN_ERR_DIMS, "TT dimensions are not compatible");
     if (a->batch != b->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    if (a->el != b->el) return refuse_mixed("ttn_dot");
+    if (a->el == 2) return zdot(a, b, out);
     const int d = a->d;
     if (d > DOT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot: chains longer than 480 sites are not supported");
     if (a->stride >= (1LL << 31) || b->stride >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot: a train of 2^31 doubles or more");
@@ -1776,6 +1979,13 @@ int ttn_last_launch_ms(float* ms) {
 
 int ttn_norm(ttn_tt_t a, double* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (a && out && a->el == 2) {               // norm = sqrt(max(real(dot(a, a)), 0))
+        std::vector<double> z(2 * (size_t)a->batch);
+        const int rcz = ttn_dot(a, a, z.data());
+        if (rcz) return rcz;
+        for (int b = 0; b < a->batch; ++b) out[b] = std::sqrt(std::max(z[2 * b], 0.0));
+        return TTN_OK;
+    }
     int rc = ttn_dot(a, a, out);
     if (rc) return rc;
     for (int b = 0; b < a->batch; ++b) { double v = out[b]; v = v < 0 ? 0.0 : v; out[b] = std::sqrt(v); }
@@ -1785,6 +1995,7 @@ int ttn_norm(ttn_tt_t a, double* out) {
 int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_orthogonalize", {x, y});
     if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x == y) return fail(TTN_ERR_ARG, "ttn_orthogonalize: output must not alias the input");
@@ -1940,6 +2151,7 @@ int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, dou
 // ---- singular-value capture -----------------------------------------------------------------------
 int ttn_sv_capture(ttn_tt_t h, int enable) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    F64_ONLY("ttn_sv_capture", {h});
     if (!h) return fail(TTN_ERR_ARG, "null handle");
     h->sv_on = enable != 0;
     return TTN_OK;
@@ -2365,6 +2577,137 @@ int ttn_bond_truncate_f64(int64_t d, const int64_t* dims, double* const* cores, 
     return compress_host(d, dims, cores, rks, k, max_bond, truncerr, 1);
 }
 
+// ---- ComplexF64 stateless entry points: the _f64 calls above with interleaved (re, im) buffers -------------------------------------
+namespace {
+int up_tt(TmpTT& t, int64_t d, const int64_t* dims, const int64_t* cap, const double* const* cores, const int64_t* rks, const int64_t* ot, int cplx) {
+    int rc = cplx ? ttn_tt_create_c64(d, dims, cap, 1, &t.h) : ttn_tt_create(d, dims, cap, 1, &t.h);
+    if (rc) return rc;
+    return ttn_tt_upload(t.h, 0, cores, rks, ot);
+}
+}  // namespace
+
+int ttn_apply_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                  const int64_t* X_rks, double* const* Y_cores, int a_cplx, int x_cplx) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    TmpTTO A; TmpTT x, y;
+    if ((rc = a_cplx ? ttn_tto_create_c64(d, dims, A_rks, A_cores, &A.h) : ttn_tto_create(d, dims, A_rks, A_cores, &A.h))) return rc;
+    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, x_cplx))) return rc;
+    std::vector<int64_t> yr(d + 1);
+    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
+    if ((rc = ttn_tt_create_c64(d, dims, yr.data(), 1, &y.h))) return rc;
+    if ((rc = ttn_apply(A.h, x.h, y.h))) return rc;
+    return ttn_tt_download(y.h, 0, Y_cores);
+}
+
+int ttn_dot_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* B_cores,
+                const int64_t* B_rks, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !A_cores || !A_rks || !B_cores || !B_rks || !out || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    TmpTT a, b;
+    if ((rc = up_tt(a, d, dims, A_rks, A_cores, A_rks, nullptr, 1))) return rc;
+    if ((rc = up_tt(b, d, dims, B_rks, B_cores, B_rks, nullptr, 1))) return rc;
+    return ttn_dot(a.h, b.h, out);
+}
+
+int ttn_hadamard_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                     const int64_t* Y_rks, double* const* Z_cores) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    TmpTT x, y, z;
+    std::vector<int64_t> zr(d + 1);
+    for (int64_t m = 0; m <= d; ++m) zr[m] = X_rks[m] * Y_rks[m];
+    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, 1))) return rc;
+    if ((rc = up_tt(y, d, dims, Y_rks, Y_cores, Y_rks, nullptr, 1))) return rc;
+    if ((rc = ttn_tt_create_c64(d, dims, zr.data(), 1, &z.h))) return rc;
+    if ((rc = ttn_hadamard(x.h, y.h, z.h))) return rc;
+    return ttn_tt_download(z.h, 0, Z_cores);
+}
+
+int ttn_add_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                const int64_t* Y_rks, double* const* Z_cores) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    TmpTT x, y, z;
+    std::vector<int64_t> zr(d + 1);
+    for (int64_t m = 0; m <= d; ++m) zr[m] = (m == 0 || m == d) ? 1 : X_rks[m] + Y_rks[m];
+    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, 1))) return rc;
+    if ((rc = up_tt(y, d, dims, Y_rks, Y_cores, Y_rks, nullptr, 1))) return rc;
+    if ((rc = ttn_tt_create_c64(d, dims, zr.data(), 1, &z.h))) return rc;
+    if ((rc = ttn_add(x.h, y.h, z.h))) return rc;
+    return ttn_tt_download(z.h, 0, Z_cores);
+}
+
+int ttn_scale_host_c64(int64_t d, const int64_t* dims, double re, double im, const double* const* X_cores, const int64_t* X_rks,
+                       const int64_t* X_ot, double* const* Y_cores, int64_t* Y_ot) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    TmpTT x, y;
+    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, X_ot, 1))) return rc;
+    if ((rc = ttn_tt_create_c64(d, dims, X_rks, 1, &y.h))) return rc;
+    if ((rc = ttn_scale_c64(re, im, x.h, y.h))) return rc;
+    if (Y_ot) ttn_tt_ranks(y.h, 0, nullptr, Y_ot);
+    return ttn_tt_download(y.h, 0, Y_cores);
+}
+
+static int zcompress_host(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond, double truncerr,
+                          int64_t sweeps) {
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !cores || !rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    TmpTT x;
+    std::vector<int64_t> need, fin;
+    long long pm, qm;
+    rank_bounds((int)d, dims, rks, max_bond, sweeps, k, need, fin, pm, qm);
+    if ((rc = up_tt(x, d, dims, need.data(), cores, rks, nullptr, 1))) return rc;
+    if (k > 0) rc = ttn_bond_truncate(x.h, k, max_bond, truncerr);
+    else rc = ttn_compress(x.h, max_bond, truncerr, sweeps);
+    if (rc) return rc;
+    if ((rc = ttn_compress_status(x.h, nullptr))) return rc;
+    if ((rc = ttn_tt_ranks(x.h, 0, rks, nullptr))) return rc;
+    return ttn_tt_download(x.h, 0, cores);
+}
+
+int ttn_compress_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t max_bond, double truncerr, int64_t sweeps) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
+    return zcompress_host(d, dims, cores, rks, 0, max_bond, truncerr, sweeps);
+}
+
+int ttn_bond_truncate_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond, double truncerr) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (k < 1 || k >= d) return fail(TTN_ERR_BOND_INDEX, "k must be in 1:(N-1)");
+    return zcompress_host(d, dims, cores, rks, k, max_bond, truncerr, 1);
+}
+
+int ttn_apply_compress_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                           const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks, int64_t max_bond, double truncerr, int64_t sweeps,
+                           int a_cplx, int x_cplx) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || !Y_rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
+    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    TmpTTO A; TmpTT x, y;
+    if ((rc = a_cplx ? ttn_tto_create_c64(d, dims, A_rks, A_cores, &A.h) : ttn_tto_create(d, dims, A_rks, A_cores, &A.h))) return rc;
+    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, x_cplx))) return rc;
+    std::vector<int64_t> yr(d + 1), need, fin;
+    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
+    long long pm, qm;
+    rank_bounds((int)d, dims, yr.data(), max_bond, sweeps, 0, need, fin, pm, qm);
+    for (int64_t m = 0; m <= d; ++m) need[m] = std::max<int64_t>(need[m], yr[m]);
+    if ((rc = ttn_tt_create_c64(d, dims, need.data(), 1, &y.h))) return rc;
+    if ((rc = ttn_apply_compress(A.h, x.h, y.h, max_bond, truncerr, sweeps))) return rc;
+    if ((rc = ttn_compress_status(y.h, nullptr))) return rc;
+    if ((rc = ttn_tt_ranks(y.h, 0, Y_rks, nullptr))) return rc;
+    return ttn_tt_download(y.h, 0, Y_cores);
+}
+
 // ---- als_eigsolve / als_gen_eigsolv (csrc/ttn_als_eig_kernels.h) ---------------------------------------------------------------
 // The host walks the stages of the schedule (als.jl:284-300, :370-397): k_als_eig runs a stage's full sweeps at fixed ranks, writing
 // its part of the history; between stages k_increase_ranks pads x into a temporary handle of x's capacity at the ranks
@@ -2377,6 +2720,7 @@ static int als_eig_impl(int gen, ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t
     const char* who = gen ? "als_gen_eigsolv" : "als_eigsolve";
     auto err = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
     NEED_INIT();
+    F64_ONLY("one-site eigensolver", {x0, x}, {A, S});
     if (!A || !x0 || !x || (gen && !S)) return err(TTN_ERR_ARG, "null handle");
     if (!rmax_schedule || (hist_len > 0 && !E_out)) return err(TTN_ERR_ARG, "null schedule / history buffer");
     if (!same_dims(A->dims, x0->dims) || !same_dims(x0->dims, x->dims) || (gen && !same_dims(S->dims, x0->dims)))
@@ -2626,7 +2970,7 @@ int ttn_tto_download(ttn_tto_t A, double* const* cores) {
     if (!A || !cores) return fail(TTN_ERR_ARG, "null pointer");
     for (int k = 0; k < A->d; ++k) {
         if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_download: null core");
-        const size_t sz = (size_t)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1];
+        const size_t sz = (size_t)A->el * A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1];
         HIPCHK(hipMemcpyAsync(cores[k], A->d_data + A->off[k], sizeof(double) * sz, hipMemcpyDeviceToHost, g_stream));
     }
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -2637,6 +2981,7 @@ int ttn_tto_download(ttn_tto_t A, double* const* cores) {
 int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_mul", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (!same_dims(A->dims, B->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     const int d = A->d;
@@ -2669,6 +3014,7 @@ int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
 int ttn_tto_inner(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_inner", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (A->d != B->d) return fail(TTN_ERR_DIMS, "Inner core product requires operators with the same number of cores");
     const int d = A->d;
@@ -2693,6 +3039,7 @@ int ttn_tto_inner(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
 int ttn_tto_add(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_add", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (!same_dims(A->dims, B->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     const int d = A->d;
@@ -2715,6 +3062,7 @@ int ttn_tto_add(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
 int ttn_tto_scale(double a, ttn_tto_t A, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_scale", {}, {A});
     if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
     const int d = A->d;
     std::vector<int64_t> ot(A->ot);
@@ -2736,6 +3084,7 @@ int ttn_tto_scale(double a, ttn_tto_t A, ttn_tto_t* out) {
 int ttn_tto_kron(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_kron", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (A->rks[A->d] != B->rks[0]) return fail(TTN_ERR_DIMS, "The final rank of the first TToperator must equal the initial rank of the second TToperator.");
     const int d = A->d + B->d;
@@ -2763,6 +3112,7 @@ static int train_ranks(ttn_tt_t x, int64_t b, std::vector<int64_t>& rks) {
 int ttn_tt_outer(ttn_tt_t x, ttn_tt_t y, int64_t b, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tt_outer", {x, y});
     if (!x || !y || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (b < 0 || b >= x->batch || b >= y->batch) return fail(TTN_ERR_ARG, "ttn_tt_outer: train index outside the batch");
     if (!same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -2785,6 +3135,7 @@ int ttn_tt_outer(ttn_tt_t x, ttn_tt_t y, int64_t b, ttn_tto_t* out) {
 int ttn_tt_diag_tto(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tt_diag_tto", {x});
     if (!x || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (b < 0 || b >= x->batch) return fail(TTN_ERR_ARG, "ttn_tt_diag_tto: train index outside the batch");
     const int d = x->d;
@@ -2806,6 +3157,7 @@ int ttn_tt_diag_tto(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
 int ttn_tt_kron(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tt_kron", {x, y, z});
     if (!x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
     if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_tt_kron: output must not alias an input");
     const int dx = x->d, dy = y->d, d = dx + dy;
@@ -2837,6 +3189,7 @@ int ttn_tt_kron(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
 int ttn_tto_to_tt(ttn_tto_t A, ttn_tt_t y) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_to_tt", {y}, {A});
     if (!A || !y) return fail(TTN_ERR_ARG, "null handle");
     const int d = A->d;
     if (y->d != d) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -2856,6 +3209,7 @@ int ttn_tto_to_tt(ttn_tto_t A, ttn_tt_t y) {
 int ttn_tto_from_tt(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_from_tt", {x});
     if (!x || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (b < 0 || b >= x->batch) return fail(TTN_ERR_ARG, "ttn_tto_from_tt: train index outside the batch");
     const int d = x->d;
@@ -2882,6 +3236,7 @@ int ttn_tto_from_tt(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
 int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t sweeps, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
+    F64_ONLY("ttn_tto_compress", {}, {A});
     if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
     if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");

@@ -13,7 +13,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
-from .tt import TToperator, TTvector, _f, _i64, _ptrs
+from .tt import TToperator, TTvector, _f, _i64, _is_cplx, _ptrs, _z
 
 
 class DeviceTTO:
@@ -26,9 +26,14 @@ class DeviceTTO:
         self.rks = list(A.tto_rks)
         self.ot = [int(o) for o in A.tto_ot]
         self.N = A.N
-        cores = [_f(c) for c in A.tto_vec]
+        self.dtype = np.complex128 if _is_cplx(A.tto_vec) else np.float64          # the element type comes from the cores
         h = C.c_void_p()
-        _lib.check(_lib.lib().ttn_tto_create(A.N, _i64(A.tto_dims), _i64(A.tto_rks), _ptrs(cores), C.byref(h)))
+        if self.dtype is np.complex128:
+            cores = [_z(c) for c in A.tto_vec]
+            _lib.check(_lib.lib().ttn_tto_create_c64(A.N, _i64(A.tto_dims), _i64(A.tto_rks), _ptrs(cores), C.byref(h)))
+        else:
+            cores = [_f(c) for c in A.tto_vec]
+            _lib.check(_lib.lib().ttn_tto_create(A.N, _i64(A.tto_dims), _i64(A.tto_rks), _ptrs(cores), C.byref(h)))
         self.h = h
         if any(self.ot):
             _lib.check(_lib.lib().ttn_tto_set_ot(self.h, _i64(self.ot)))
@@ -47,6 +52,9 @@ class DeviceTTO:
         dims, rks, ot = (C.c_int64 * self.N)(), (C.c_int64 * (self.N + 1))(), (C.c_int64 * self.N)()
         _lib.check(L.ttn_tto_ranks(h, None, dims, rks, ot))
         self.dims, self.rks, self.ot = tuple(int(v) for v in dims), [int(v) for v in rks], [int(v) for v in ot]
+        cplx = C.c_int(0)
+        _lib.check(L.ttn_tto_dtype(h, C.byref(cplx)))
+        self.dtype = np.complex128 if cplx.value else np.float64
         return self
 
     def _binary(self, name: str, other: "DeviceTTO") -> "DeviceTTO":
@@ -109,7 +117,7 @@ class DeviceTTO:
         return list(self.rks)
 
     def download(self) -> TToperator:
-        cores = [np.zeros((self.dims[k], self.dims[k], self.rks[k], self.rks[k + 1]), order="F") for k in range(self.N)]
+        cores = [np.zeros((self.dims[k], self.dims[k], self.rks[k], self.rks[k + 1]), order="F", dtype=self.dtype) for k in range(self.N)]
         _lib.check(_lib.lib().ttn_tto_download(self.h, _ptrs(cores)))
         return TToperator(self.N, cores, self.dims, list(self.rks), list(self.ot))
 
@@ -126,27 +134,35 @@ class DeviceTTO:
 
 
 class DeviceTT:
-    def __init__(self, dims: Sequence[int], cap_rks: Sequence[int], batch: int = 1):
+    """``batch`` trains in HBM (``ttn_tt``).  ``dtype``: ``np.float64`` or ``np.complex128`` — fixed at creation; a complex handle holds
+    the cores interleaved (re, im), as Julia's ``Array{ComplexF64,3}`` lies in memory."""
+
+    def __init__(self, dims: Sequence[int], cap_rks: Sequence[int], batch: int = 1, dtype=np.float64):
         _lib.ensure_init()
+        if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.complex128)):
+            raise TypeError(f"DeviceTT: dtype must be float64 or complex128, got {np.dtype(dtype)}")
+        self.dtype = np.complex128 if np.dtype(dtype) == np.dtype(np.complex128) else np.float64
         self.dims = tuple(int(v) for v in dims)
         self.cap = [int(r) for r in cap_rks]
         self.N = len(self.dims)
         self.batch = int(batch)
         h = C.c_void_p()
-        _lib.check(_lib.lib().ttn_tt_create(self.N, _i64(self.dims), _i64(self.cap), self.batch, C.byref(h)))
+        create = _lib.lib().ttn_tt_create_c64 if self.dtype is np.complex128 else _lib.lib().ttn_tt_create
+        _lib.check(create(self.N, _i64(self.dims), _i64(self.cap), self.batch, C.byref(h)))
         self.h = h
 
     @classmethod
     def from_host(cls, x: TTvector, batch: int = 1, cap_rks: Sequence[int] | None = None) -> "DeviceTT":
-        """Upload x as train 0 and replicate it over the batch."""
-        t = cls(x.ttv_dims, cap_rks if cap_rks is not None else x.ttv_rks, batch)
+        """Upload x as train 0 and replicate it over the batch.  The element type is that of x's cores."""
+        t = cls(x.ttv_dims, cap_rks if cap_rks is not None else x.ttv_rks, batch, dtype=np.complex128 if _is_cplx(x.ttv_vec) else np.float64)
         t.upload(0, x)
         if batch > 1:
             t.replicate(0)
         return t
 
     def upload(self, b: int, x: TTvector) -> None:
-        cores = [_f(c) for c in x.ttv_vec]
+        # (a real train into a complex handle is promoted on the host; a complex train into a real handle is refused by _f)
+        cores = [(_z if self.dtype is np.complex128 else _f)(c) for c in x.ttv_vec]
         _lib.check(_lib.lib().ttn_tt_upload(self.h, int(b), _ptrs(cores), _i64(x.ttv_rks), _i64(x.ttv_ot)))
 
     def replicate(self, src: int = 0) -> None:
@@ -167,7 +183,7 @@ class DeviceTT:
 
     def download(self, b: int = 0) -> TTvector:
         rks, ot = self.ranks(b)
-        cores = [np.zeros((self.dims[k], rks[k], rks[k + 1]), order="F") for k in range(self.N)]
+        cores = [np.zeros((self.dims[k], rks[k], rks[k + 1]), order="F", dtype=self.dtype) for k in range(self.N)]
         _lib.check(_lib.lib().ttn_tt_download(self.h, int(b), _ptrs(cores)))
         return TTvector(self.N, cores, self.dims, rks, ot)
 
@@ -255,6 +271,11 @@ def status_all() -> None:
 
 
 def dot(a: DeviceTT, b: DeviceTT) -> np.ndarray:
+    """dot(a_b, b_b) per train; complex handles: the first argument conjugated, a complex128 array."""
+    if a.dtype is np.complex128:
+        out = (C.c_double * (2 * a.batch))()
+        _lib.check(_lib.lib().ttn_dot(a.h, b.h, out))
+        return np.array(out[:]).view(np.complex128)
     out = (C.c_double * a.batch)()
     _lib.check(_lib.lib().ttn_dot(a.h, b.h, out))
     return np.array(out[:])
@@ -276,13 +297,21 @@ def add(x: DeviceTT, y: DeviceTT, z: DeviceTT) -> DeviceTT:
     return z
 
 
-def scale(a: float, x: DeviceTT, y: DeviceTT) -> DeviceTT:
+def scale(a, x: DeviceTT, y: DeviceTT) -> DeviceTT:
+    if x.dtype is np.complex128 or isinstance(a, (complex, np.complexfloating)):       # (a complex factor on real handles is refused by the library)
+        a = complex(a)
+        _lib.check(_lib.lib().ttn_scale_c64(a.real, a.imag, x.h, y.h))
+        return y
     _lib.check(_lib.lib().ttn_scale(float(a), x.h, y.h))
     return y
 
 
 def scale_batch(a, x: DeviceTT, y: DeviceTT) -> DeviceTT:
-    """y_b = a[b] * x_b (one scalar per train)."""
+    """y_b = a[b] * x_b (one scalar per train; complex handles take complex factors)."""
+    if x.dtype is np.complex128:
+        flat = np.ascontiguousarray(np.asarray(a, dtype=np.complex128).reshape(x.batch)).view(np.float64)
+        _lib.check(_lib.lib().ttn_scale_batch_c64((C.c_double * (2 * x.batch))(*flat.tolist()), x.h, y.h))
+        return y
     arr = (C.c_double * x.batch)(*[float(v) for v in a])
     _lib.check(_lib.lib().ttn_scale_batch(arr, x.h, y.h))
     return y

@@ -111,6 +111,8 @@ def reorder_op(A: TToperator, n_dims: int, bits_per_dim: int, new_ordering: str,
 def ttv_decomp_(z: DeviceTT, tensors, index: int = 1, tol: float = 1.0e-12) -> DeviceTT:
     """z_b = ttv_decomp(tensors[b]; index, tol) (src/tt_tools.jl:186-252) for a batch of dense tensors of shape z.dims."""
     import numpy as np
+    if np.iscomplexobj(tensors):
+        raise TypeError("ttv_decomp_: the device decomposition is Float64 only, a complex tensor was passed")
     arr = np.asarray(tensors, dtype=np.float64)
     assert arr.shape == (z.batch,) + tuple(z.dims), "tensors must have shape (batch, *dims)"
     flat = np.ascontiguousarray(np.stack([np.ravel(arr[b], order="F") for b in range(z.batch)]))
@@ -121,6 +123,8 @@ def ttv_decomp_(z: DeviceTT, tensors, index: int = 1, tol: float = 1.0e-12) -> D
 def ttv_decomp(tensor, index: int = 1, tol: float = 1.0e-12, rank_cap: int = 1024) -> TTvector:
     """Host-level form for one tensor: capacity = the exact-rank bounds min(prod(dims[:k]), prod(dims[k:]), rank_cap)."""
     import numpy as np
+    if np.iscomplexobj(tensor):
+        raise TypeError("ttv_decomp: the device decomposition is Float64 only, a complex tensor was passed")
     t = np.asarray(tensor, dtype=np.float64)
     dims = tuple(int(v) for v in t.shape)
     d = len(dims)

@@ -39,15 +39,28 @@ def _i64(seq) -> "C.Array":
 
 
 def _f(core: np.ndarray) -> np.ndarray:
+    """A core as the Float64 entry points read it.  A complex core is refused: the conversion would drop its imaginary part."""
+    if np.iscomplexobj(core):
+        raise TypeError("this operation is Float64 only: a complex core was passed (ComplexF64 is supported by *, +, -, scalar *, /, "
+                        "dot, norm, euclidean_distance, hadamard, _tt_bond_truncate_, tt_compress_ and apply_compress)")
     return np.asfortranarray(core, dtype=np.float64)
+
+
+def _z(core: np.ndarray) -> np.ndarray:
+    """A core as the ComplexF64 entry points read it: column-major, interleaved (re, im)."""
+    return np.asfortranarray(core, dtype=np.complex128)
+
+
+def _is_cplx(*cores_lists) -> bool:
+    return any(np.iscomplexobj(c) for cores in cores_lists for c in cores)
 
 
 def _ptrs(arrs: Sequence[np.ndarray]):
     return (C.POINTER(C.c_double) * len(arrs))(*[a.ctypes.data_as(C.POINTER(C.c_double)) for a in arrs])
 
 
-def _empty_cores(dims, rks) -> List[np.ndarray]:
-    return [np.zeros((int(dims[k]), int(rks[k]), int(rks[k + 1])), order="F") for k in range(len(dims))]
+def _empty_cores(dims, rks, dtype=np.float64) -> List[np.ndarray]:
+    return [np.zeros((int(dims[k]), int(rks[k]), int(rks[k + 1])), order="F", dtype=dtype) for k in range(len(dims))]
 
 
 class TTvector:
@@ -134,6 +147,13 @@ def apply(A: TToperator, v: TTvector) -> TTvector:
     assert tuple(A.tto_dims) == tuple(v.ttv_dims), "Incompatible dimensions"
     d = v.N
     yr = [a * b for a, b in zip(A.tto_rks, v.ttv_rks)]
+    ca, cx = _is_cplx(A.tto_vec), _is_cplx(v.ttv_vec)
+    if ca or cx:          # complex x complex and the two mixed forms: the real side stays real on the device, the result is complex
+        Y = _empty_cores(v.ttv_dims, yr, np.complex128)
+        Ac = [(_z if ca else _f)(c) for c in A.tto_vec]
+        Xc = [(_z if cx else _f)(c) for c in v.ttv_vec]
+        _lib.check(_lib.lib().ttn_apply_c64(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(Y), int(ca), int(cx)))
+        return TTvector(d, Y, v.ttv_dims, yr, [0] * d)
     Y = _empty_cores(v.ttv_dims, yr)
     Ac = [_f(c) for c in A.tto_vec]
     Xc = [_f(c) for c in v.ttv_vec]
@@ -152,6 +172,17 @@ def apply_compress(A: TToperator, v: TTvector, max_bond: int, truncerr: float = 
     L = _lib.lib()
     cap = (C.c_int64 * (d + 1))()
     _lib.check(L.ttn_apply_compress_rank_bound(d, _i64(v.ttv_dims), _i64(A.tto_rks), _i64(v.ttv_rks), max_bond, int(sweeps), cap))
+    ca, cx = _is_cplx(A.tto_vec), _is_cplx(v.ttv_vec)
+    if ca or cx:          # ComplexF64: apply, then round, on the device (no fused complex merge)
+        need = [max(int(c), a * b) for c, a, b in zip(cap, A.tto_rks, v.ttv_rks)]
+        bufs = [np.zeros(v.ttv_dims[j] * need[j] * need[j + 1], dtype=np.complex128) for j in range(d)]
+        rks = (C.c_int64 * (d + 1))()
+        Ac = [(_z if ca else _f)(c) for c in A.tto_vec]
+        Xc = [(_z if cx else _f)(c) for c in v.ttv_vec]
+        _lib.check(L.ttn_apply_compress_c64(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(bufs), rks,
+                                            max_bond, float(truncerr), int(sweeps), int(ca), int(cx)))
+        rk = [int(r) for r in rks]
+        return TTvector(d, _rewrap(bufs, v.ttv_dims, rk), v.ttv_dims, rk, [0] * d)
     bufs = [np.zeros(v.ttv_dims[j] * int(cap[j]) * int(cap[j + 1])) for j in range(d)]
     rks = (C.c_int64 * (d + 1))()
     Ac = [_f(c) for c in A.tto_vec]
@@ -163,9 +194,16 @@ def apply_compress(A: TToperator, v: TTvector, max_bond: int, truncerr: float = 
     return TTvector(d, cores, v.ttv_dims, rk, [0] * d)
 
 
-def dot(A: TTvector, B: TTvector) -> float:
-    """dot(A, B) — src/tt_operations.jl:239-250."""
+def dot(A: TTvector, B: TTvector):
+    """dot(A, B) — src/tt_operations.jl:239-250.  With a complex argument the FIRST one is conjugated (:243-248) and the result is a
+    ``complex``; a real argument next to a complex one is promoted on the host."""
     assert tuple(A.ttv_dims) == tuple(B.ttv_dims), "TT dimensions are not compatible"
+    if _is_cplx(A.ttv_vec, B.ttv_vec):
+        out2 = (C.c_double * 2)()
+        Ac = [_z(c) for c in A.ttv_vec]
+        Bc = [_z(c) for c in B.ttv_vec]
+        _lib.check(_lib.lib().ttn_dot_c64(A.N, _i64(A.ttv_dims), _ptrs(Ac), _i64(A.ttv_rks), _ptrs(Bc), _i64(B.ttv_rks), out2))
+        return complex(out2[0], out2[1])
     out = C.c_double(0.0)
     Ac = [_f(c) for c in A.ttv_vec]
     Bc = [_f(c) for c in B.ttv_vec]
@@ -175,7 +213,7 @@ def dot(A: TTvector, B: TTvector) -> float:
 
 def norm(a: TTvector) -> float:
     """norm(a) — src/tt_operations.jl:465-470."""
-    v = dot(a, a)
+    v = dot(a, a).real          # norm = sqrt(max(real(dot(a, a)), 0))
     v = 0.0 if v < 0 else v
     return math.sqrt(v)
 
@@ -183,7 +221,7 @@ def norm(a: TTvector) -> float:
 def euclidean_distance(a: TTvector, b: TTvector) -> float:
     """src/tt_operations.jl:452-455."""
     assert tuple(a.ttv_dims) == tuple(b.ttv_dims), "TT dimensions must match"
-    return math.sqrt(max(dot(a, a) - 2 * dot(b, a) + dot(b, b), 0.0))
+    return math.sqrt(max((dot(a, a) - 2 * dot(b, a).real + dot(b, b)).real, 0.0))
 
 
 def hadamard(x: TTvector, y: TTvector) -> TTvector:
@@ -191,6 +229,12 @@ def hadamard(x: TTvector, y: TTvector) -> TTvector:
     assert tuple(x.ttv_dims) == tuple(y.ttv_dims), "Incompatible TT dimensions"
     d = x.N
     zr = [a * b for a, b in zip(x.ttv_rks, y.ttv_rks)]
+    if _is_cplx(x.ttv_vec, y.ttv_vec):          # no conjugation (:343-361); a real factor is promoted on the host
+        Z = _empty_cores(x.ttv_dims, zr, np.complex128)
+        Xc = [_z(c) for c in x.ttv_vec]
+        Yc = [_z(c) for c in y.ttv_vec]
+        _lib.check(_lib.lib().ttn_hadamard_c64(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
+        return TTvector(d, Z, x.ttv_dims, zr, [0] * d)
     Z = _empty_cores(x.ttv_dims, zr)
     Xc = [_f(c) for c in x.ttv_vec]
     Yc = [_f(c) for c in y.ttv_vec]
@@ -205,6 +249,12 @@ def add(x: TTvector, y: TTvector) -> TTvector:
     zr = [a + b for a, b in zip(x.ttv_rks, y.ttv_rks)]
     zr[0] = 1
     zr[d] = 1
+    if _is_cplx(x.ttv_vec, y.ttv_vec):          # a real summand is promoted on the host
+        Z = _empty_cores(x.ttv_dims, zr, np.complex128)
+        Xc = [_z(c) for c in x.ttv_vec]
+        Yc = [_z(c) for c in y.ttv_vec]
+        _lib.check(_lib.lib().ttn_add_c64(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
+        return TTvector(d, Z, x.ttv_dims, zr, [0] * d)
     Z = _empty_cores(x.ttv_dims, zr)
     Xc = [_f(c) for c in x.ttv_vec]
     Yc = [_f(c) for c in y.ttv_vec]
@@ -222,6 +272,13 @@ def add_(x: TTvector, y: TTvector) -> TTvector:
 def scale(a: float, A: TTvector) -> TTvector:
     """*(a::Number, A::TTvector) — src/tt_operations.jl:256-266."""
     d = A.N
+    if _is_cplx(A.ttv_vec) or isinstance(a, (complex, np.complexfloating)):
+        a = complex(a)
+        Y = _empty_cores(A.ttv_dims, A.ttv_rks, np.complex128)
+        Xc = [_z(c) for c in A.ttv_vec]
+        yot = (C.c_int64 * d)()
+        _lib.check(_lib.lib().ttn_scale_host_c64(d, _i64(A.ttv_dims), a.real, a.imag, _ptrs(Xc), _i64(A.ttv_rks), _i64(A.ttv_ot), _ptrs(Y), yot))
+        return TTvector(d, Y, A.ttv_dims, list(A.ttv_rks), [int(v) for v in yot])
     Y = _empty_cores(A.ttv_dims, A.ttv_rks)
     Xc = [_f(c) for c in A.ttv_vec]
     yot = (C.c_int64 * d)()
@@ -243,6 +300,8 @@ def orthogonalize(x_tt: TTvector, i: int = 1) -> TTvector:
     """orthogonalize(x_tt; i=1) — src/tt_tools.jl:511-543 (non-mutating)."""
     d = x_tt.N
     assert 1 <= i <= d, "Impossible orthogonalization"
+    if _is_cplx(x_tt.ttv_vec):
+        raise TypeError("orthogonalize: complex trains are not supported (Float64 only)")
     Y = _empty_cores(x_tt.ttv_dims, x_tt.ttv_rks)      # max-size buffers: output ranks never exceed the input's
     Xc = [_f(c) for c in x_tt.ttv_vec]
     yr = (C.c_int64 * (d + 1))()
@@ -269,6 +328,8 @@ def _tt_bond_truncate_(psi: TTvector, k: int, max_bond: int = 2 ** 62, truncerr:
     and ttv_rks[k+1]; ttv_ot untouched.  Returns orthogonalize(psi; i=k) like the reference (:769)."""
     assert 1 <= k < psi.N, "k must be in 1:(N-1)"
     _compress_call(psi, k, max_bond, truncerr, 1)
+    if _is_cplx(psi.ttv_vec):
+        return psi                 # (orthogonalize is Float64 only: the value the reference returns here is not formed for complex trains)
     return orthogonalize(psi, i=k)
 
 
@@ -294,13 +355,18 @@ def _compress_call(psi: TTvector, k: int, max_bond: int, truncerr: float, sweeps
     # min(length(s), max_bond) singular values): size the in/out buffers for that
     need = (C.c_int64 * (d + 1))()
     _lib.check(L.ttn_compress_rank_bound(d, _i64(psi.ttv_dims), _i64(psi.ttv_rks), max_bond, int(sweeps), int(k), need, None))
+    cplx = _is_cplx(psi.ttv_vec)
     bufs = []
     for j in range(d):
-        buf = np.zeros(psi.ttv_dims[j] * int(need[j]) * int(need[j + 1]))
-        buf[: psi.ttv_vec[j].size] = _f(psi.ttv_vec[j]).reshape(-1, order="F")
+        buf = np.zeros(psi.ttv_dims[j] * int(need[j]) * int(need[j + 1]), dtype=np.complex128 if cplx else np.float64)
+        buf[: psi.ttv_vec[j].size] = (_z if cplx else _f)(psi.ttv_vec[j]).reshape(-1, order="F")
         bufs.append(buf)
     rks = _i64(psi.ttv_rks)
-    if k > 0:
+    if cplx and k > 0:
+        rc = L.ttn_bond_truncate_c64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, int(k), max_bond, float(truncerr))
+    elif cplx:
+        rc = L.ttn_compress_c64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, max_bond, float(truncerr), int(sweeps))
+    elif k > 0:
         rc = L.ttn_bond_truncate_f64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, int(k), max_bond, float(truncerr))
     else:
         rc = L.ttn_compress_f64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, max_bond, float(truncerr), int(sweeps))
