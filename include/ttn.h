@@ -152,6 +152,27 @@ int ttn_swap_sites(ttn_tt_t x, int64_t nswaps, const int64_t* swaps, double thre
  * below `tol` discarded (absolute).  Ranks are bounded by the handle's capacity: a larger rank is reported by
  * ttn_compress_status as TTN_ERR_CAPACITY.  Sets the orthogonality flags -1 / 0 / +1 like the reference.  Synchronises. */
 int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol);
+/* ttn_ttv_decomp with the tensors already in DEVICE memory ([batch][prod(dims)], on the library's stream): the same kernel on the
+ * same data, without the host -> device copy.  The input buffer is only read.  Limits, status reporting and the orthogonality flags are
+ * those of ttn_ttv_decomp.  Synchronises. */
+int ttn_ttv_decomp_dev(ttn_tt_t z, const double* d_tensors, int64_t index, double tol);
+
+/* --- trains -> dense tensors and QTT grids on the device (csrc/ttn_grid_kernels.h), Float64 only (a ComplexF64 handle:
+ * TTN_ERR_UNSUPPORTED before any launch).
+ * ttn_tt_to_dense: for every train b of the batch d_out[b * total + sum_k (i_k - 1) strides[k]] = x_b(i_1..i_N); d_out is DEVICE
+ *   memory of batch * total doubles, total = prod(dims).  strides == NULL: Julia column-major, i.e. ttv_to_tensor
+ *   (src/tt_tools.jl).  The (stride, n) pairs sorted by stride must form a mixed-radix system (the smallest stride is 1, each next
+ *   one is the previous stride times that site's n; sites with n = 1 are ignored), which makes the map a bijection onto [0, total):
+ *   otherwise TTN_ERR_ARG before any launch.  Limits: total <= 2^27 per train, at most 64 sites, every n <= 4096, end ranks 1 (TTN_ERR_UNSUPPORTED).
+ *   The train is cut where both partial products are about sqrt(total) wide; out = L R by fp64 MFMA, stored in output-address
+ *   order.  Asynchronous on the library's stream.
+ * ttn_qtt_grid_points: coordinates of the entries first .. first + count - 1 of the (2, ..., 2) tensor of a QTT with n_dims * bits
+ *   sites (linear index, site 1 fastest), d_X (DEVICE) laid out (n_dims, count).  Bit -> (dim, level): src/qtt_tools.jl:820-829
+ *   (interleaved != 0: site = level * n_dims + dim; serial: site = dim * bits + level); grid index g = sum bit * 2^(bits-1-level),
+ *   coord = a + g * h, h = (b - a) / (2^bits - 1) computed on the host, one rounded multiply and one rounded add on the device (no
+ *   FMA).  Limits: bits <= 52, n_dims * bits <= 62 (TTN_ERR_ARG).  Asynchronous. */
+int ttn_tt_to_dense(ttn_tt_t x, const int64_t* strides, double* d_out);
+int ttn_qtt_grid_points(int64_t n_dims, int64_t bits, int interleaved, double a, double b, int64_t first, int64_t count, double* d_X);
 
 /* --- als_linsolve(A, b, tt_start; sweep_count) (src/solvers/als.jl:161-222): x = the ALS iterate after
  * sweep_count half sweeps, for every train of the batch (one operator, `batch` right-hand sides b and start trains x0).
@@ -475,7 +496,7 @@ int ttn_apply_compress_f64(int64_t d, const int64_t* dims, const double* const* 
  * in element type, and a ComplexF64 handle given to any Float64-only entry point: the linear solvers and eigensolvers,
  * ttn_orthogonalize, ttn_hadamard_ttm, ttn_swap_sites, ttn_ttv_decomp, ttn_scale_batch, the operator algebra (ttn_tto_mul / inner /
  * add / scale / kron / compress / to_tt / from_tt, ttn_tt_outer / diag_tto / kron), ttn_apply_begin / _sweep, ttn_tt_core_extent /
- * _export / _import, ttn_sv_capture. */
+ * _export / _import, ttn_sv_capture, ttn_tt_to_dense, ttn_ttv_decomp_dev. */
 int ttn_tt_create_c64(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out);
 int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out);
 int ttn_tt_dtype(ttn_tt_t h, int* cplx);      /* *cplx = 0 Float64, 1 ComplexF64 */

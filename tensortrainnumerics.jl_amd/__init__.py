@@ -1,12 +1,12 @@
 """MI355X-native TT/QTT core-arithmetic backend for TensorTrainNumerics.jl's hot path.
 
 Host-side mirror of the reference interface (tt.py), input generators (constructors.py),
-device-resident batched handles (device.py), TT operator algebra (opalg.py) and the ctypes binding of the C ABI (_lib.py).
+device-resident batched handles (device.py), TT operator algebra (opalg.py), the multi-dimensional QTT layer (qttnd.py) and the ctypes binding of the C ABI (_lib.py).
 The arithmetic lives in csrc/*.h, csrc/ttn_api.hip -> libttn_hip.so (hand-written HIP, gfx950).
 """
-from . import _lib, constructors, cross, device, opalg, pipeline, qtt, shard, solvers, tdvp, tt
+from . import _lib, constructors, cross, device, opalg, pipeline, qtt, qttnd, shard, solvers, tdvp, tt
 from ._lib import TTNError, build, ensure_init, finalize
-from .constructors import (Delta, Nabla, fourier_qtto, function_to_qtt_uniform, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn,
+from .constructors import (Delta, Delta_DN, Delta_ND, Delta_NN, Nabla, fourier_qtto, function_to_qtt_uniform, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn,
                            qtt_cos, qtt_exp, qtt_polynom, qtt_sin, qtt_to_vector, rand_tt, reverse_qtt_bits, shift, toeplitz_to_qtto,
                            xxx_tto, xxz_tto, zeros_tt, zeros_tto)
 from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_integrate
@@ -14,8 +14,9 @@ from .device import DeviceTT, DeviceTTO, StreamTimer
 from .opalg import (concatenate, kron, outer_product, tto_add, tto_compress_, tto_inner, tto_mul, tto_scale, tto_sub, tto_to_ttv,
                     ttv_to_diag_tto, ttv_to_tto)
 from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve
+from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_to_array
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, ttv_decomp
 from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, div, dot, euclidean_distance, hadamard, norm,
-                 orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_)
+                 orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_, ttv_to_tensor)
 
 __all__ = [n for n in dir() if not n.startswith("__")]

@@ -67,6 +67,57 @@ def Delta(d: int) -> TToperator:
     return toeplitz_to_qtto(2, -1, -1, d)
 
 
+def _bc_laplacian(d: int, corner: np.ndarray) -> TToperator:
+    """Δ_DN / Δ_ND (src/tt_operators.jl:290-327): the Toeplitz cores of Δ with a fourth channel that carries `corner` through every
+    site and is subtracted at the last one, i.e. tridiag(-1, 2, -1) minus 1 at the diagonal entry whose bits all select `corner`."""
+    assert d >= 4, "Dimension must be at least 4"
+    out = zeros_tto((2,) * d, [1] + [4] * (d - 1) + [1])
+    Id = np.eye(2)
+    J = np.array([[0.0, 1.0], [0.0, 0.0]])
+    out.tto_vec[0][:, :, 0, :] = np.stack([Id, J.T, J, corner], axis=-1)
+    mid = np.zeros((2, 2, 4, 4))
+    mid[:, :, 0, 0], mid[:, :, 0, 1], mid[:, :, 0, 2] = Id, J.T, J
+    mid[:, :, 1, 1] = J
+    mid[:, :, 2, 2] = J.T
+    mid[:, :, 3, 3] = corner
+    for k in range(1, d - 1):
+        out.tto_vec[k][...] = mid
+    out.tto_vec[d - 1][:, :, :, 0] = np.stack([2 * Id - J - J.T, -J, -J.T, -corner], axis=-1)
+    return out
+
+
+def Delta_DN(d: int) -> TToperator:
+    """Δ_DN(d): Dirichlet–Neumann Laplacian, tridiag(-1, 2, -1) with the LAST diagonal entry 1 — src/tt_operators.jl:290-306."""
+    return _bc_laplacian(d, np.array([[0.0, 0.0], [0.0, 1.0]]))
+
+
+def Delta_ND(d: int) -> TToperator:
+    """Δ_ND(d): Neumann–Dirichlet Laplacian, tridiag(-1, 2, -1) with the FIRST diagonal entry 1 — src/tt_operators.jl:311-327."""
+    return _bc_laplacian(d, np.array([[1.0, 0.0], [0.0, 0.0]]))
+
+
+def Delta_NN(d: int) -> TToperator:
+    """Δ_NN(d) — src/tt_operators.jl:332-349, cores as the reference writes them: ranks [4, 5, ..., 5, 4], i.e. end ranks that are not
+    1 (the first and the last core only fill row 1 / column 1 of their rank-4 ends)."""
+    assert d >= 4, "Dimension must be at least 4"
+    out = zeros_tto((2,) * d, [4] + [5] * (d - 1) + [4])
+    Id = np.eye(2)
+    J = np.array([[0.0, 1.0], [0.0, 0.0]])
+    I1 = np.array([[1.0, 0.0], [0.0, 0.0]])
+    I2 = np.array([[0.0, 0.0], [0.0, 1.0]])
+    out.tto_vec[0][:, :, 0, :] = np.stack([Id, J.T, J, I2, I1], axis=-1)
+    mid = np.zeros((2, 2, 5, 5))
+    mid[:, :, 0, 0], mid[:, :, 0, 1], mid[:, :, 0, 2] = Id, J.T, J
+    mid[:, :, 1, 1] = J
+    mid[:, :, 2, 2] = J.T
+    mid[:, :, 3, 3] = I2
+    mid[:, :, 4, 4] = -I1
+    for k in range(1, d - 1):
+        out.tto_vec[k][...] = mid
+    out.tto_vec[d - 1][:, :, :, 0] = np.stack([2 * Id - J - J.T, -J, -J.T, -I2, -I1], axis=-1)
+    return out
+
+
 def shift(d: int) -> TToperator:
     return toeplitz_to_qtto(0, 1, 0, d)
 

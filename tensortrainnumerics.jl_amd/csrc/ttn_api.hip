@@ -18,6 +18,7 @@
 #include "ttn_cross_kernels.h"
 #include "ttn_opalg_kernels.h"
 #include "ttn_cplx_kernels.h"
+#include "ttn_grid_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1241,10 +1242,12 @@ int ttn_swap_sites(ttn_tt_t x, int64_t nswaps, const int64_t* swaps, double thre
 }
 
 // ---- ttv_decomp: dense tensors -> trains ----------------------------------------------------------------
-int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol) {
+// One body for both entry points: `on_device` says where `tensors` lives.  HOST tensors are copied behind the working buffers; DEVICE
+// tensors are read in place (k_ttv_decomp only reads them: its first step copies train b's tensor into its own working buffer).
+static int ttv_decomp_impl(ttn_tt_t z, const double* tensors, int64_t index, double tol, bool on_device) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    F64_ONLY("ttn_ttv_decomp", {z});
+    F64_ONLY(on_device ? "ttn_ttv_decomp_dev" : "ttn_ttv_decomp", {z});
     if (!z || !tensors) return fail(TTN_ERR_ARG, "null argument");
     const int d = z->d;
     if (index < 1 || index > d) return fail(TTN_ERR_ARG, "index must be in 1:d");
@@ -1278,13 +1281,17 @@ int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol)
     const long long per_scr = QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64;
     const long long per_train = 3 * total + per_scr;
     const int batch = z->batch;
-    int rc = g_scratch.ensure(sizeof(double) * ((size_t)per_train * batch + (size_t)total * batch));
+    int rc = g_scratch.ensure(sizeof(double) * ((size_t)per_train * batch + (on_device ? 0 : (size_t)total * batch)));
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
     double* base = g_scratch.as<double>();
-    double* d_in = base + (size_t)per_train * batch;
-    HIPCHK(hipMemcpyAsync(d_in, tensors, sizeof(double) * (size_t)total * batch, hipMemcpyHostToDevice, g_stream));
+    const double* d_in = tensors;
+    if (!on_device) {
+        double* stage = base + (size_t)per_train * batch;
+        HIPCHK(hipMemcpyAsync(stage, tensors, sizeof(double) * (size_t)total * batch, hipMemcpyHostToDevice, g_stream));
+        d_in = stage;
+    }
     HsvdArgs H;
     memset(&H, 0, sizeof(H));
     CompressArgs& P = H.C;
@@ -1308,6 +1315,147 @@ int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol)
     z->bound = bnd;
     for (int b = 0; b < batch; ++b)
         for (int k = 0; k < d; ++k) z->ot[(size_t)b * d + k] = (k < index - 1) ? -1 : (k == index - 1 ? 0 : 1);     // tt_tools.jl:191-198
+    return TTN_OK;
+}
+int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol) { return ttv_decomp_impl(z, tensors, index, tol, false); }
+int ttn_ttv_decomp_dev(ttn_tt_t z, const double* d_tensors, int64_t index, double tol) { return ttv_decomp_impl(z, d_tensors, index, tol, true); }
+
+// ---- train -> dense tensor (csrc/ttn_grid_kernels.h) --------------------------------------------------------------------------------
+// One side's partial products, enqueued step by step: the small steps share single-workgroup launches, a large step gets the grid.
+// Returns the buffer (0 / 1) that holds the last step's result.
+static int dense_chain(ttn_tt_t x, int side, int k_first, int nsteps, double* buf0, double* buf1, long long buf_stride) {
+    DenseChainArgs C;
+    C.tt = x->dev(); C.side = side; C.buf[0] = buf0; C.buf[1] = buf1; C.buf_stride = buf_stride;
+    long long P = 1;
+    int g = 0;
+    auto site = [&](int s) { return side == 0 ? k_first + s : k_first - s; };
+    auto outputs = [&](int s, long long rows_in) {
+        const int k = site(s);
+        return rows_in * x->dims[k] * dense_ld(side == 0 ? x->bound[k + 1] : x->bound[k]);
+    };
+    while (g < nsteps) {
+        const long long big = outputs(g, P);
+        long long Pg = P * x->dims[site(g)];
+        int cnt = 1;
+        if (big <= TTN_DENSE_CHAIN_SMALL)
+            while (g + cnt < nsteps && outputs(g + cnt, Pg) <= TTN_DENSE_CHAIN_SMALL) { Pg *= x->dims[site(g + cnt)]; ++cnt; }
+        C.k0 = site(g); C.nsteps = cnt; C.par = g & 1;
+        const unsigned blocks = big <= TTN_DENSE_CHAIN_SMALL ? 1u : (unsigned)std::min<long long>((big + TTN_DENSE_TB - 1) / TTN_DENSE_TB, 4096);
+        hipLaunchKernelGGL(k_dense_chain, dim3(blocks, (unsigned)x->batch), dim3(TTN_DENSE_TB), 0, g_stream, C);
+        P = Pg;
+        g += cnt;
+    }
+    return (nsteps - 1) & 1;
+}
+
+int ttn_tt_to_dense(ttn_tt_t x, const int64_t* strides, double* d_out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    F64_ONLY("ttn_tt_to_dense", {x});
+    if (!x || !d_out) return fail(TTN_ERR_ARG, "null argument");
+    const int d = x->d, batch = x->batch;
+    if (d > TTN_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: more than 64 sites");
+    if (x->bound[0] != 1 || x->bound[d] != 1) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: the end ranks must be 1");
+    long long total = 1;
+    for (int k = 0; k < d; ++k) {
+        total *= x->dims[k];
+        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: more than 2^27 entries per train");
+        // a tile is made of whole sites: a dimension above the tile size would leave one workgroup per output element
+        if (x->dims[k] > TTN_DENSE_TILE) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: a physical dimension above 4096");
+    }
+    // output strides: Julia column-major unless given; they must form a mixed-radix system (a bijection onto [0, total))
+    std::vector<long long> st(d);
+    if (strides) for (int k = 0; k < d; ++k) st[k] = strides[k];
+    else { long long s = 1; for (int k = 0; k < d; ++k) { st[k] = s; s *= x->dims[k]; } }
+    std::vector<int> order;                                  // the sites with n > 1 by ascending stride (a site with n = 1 has no digit)
+    for (int k = 0; k < d; ++k) if (x->dims[k] > 1) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return st[a] < st[b]; });
+    {
+        long long expect = 1;
+        for (int k : order) {
+            if (st[k] != expect) return fail(TTN_ERR_ARG, "ttn_tt_to_dense: the strides are not a mixed-radix system (smallest 1, each next = previous * its n)");
+            expect *= x->dims[k];
+        }
+    }
+    // the cut m in 0..d-1 (sites 0..m-1 left, m..d-1 right): both partial products about sqrt(total) wide, the first minimiser.  m = 0
+    // happens only when no cut inside the train is better, i.e. for one site (or leading sites of dimension 1): the left side is
+    // then empty and L is the 1 x 1 unit.
+    int m = 0;
+    long long PL = 1;
+    {
+        long long p = 1, best = -1;
+        for (int c = 0; c < d; ++c) {
+            const long long wide = std::max(p, total / p);
+            if (best < 0 || wide < best) { best = wide; m = c; PL = p; }
+            p *= x->dims[c];
+        }
+    }
+    const long long PR = total / PL;
+    // the tile: the lowest-stride sites while their dimensions multiply to at most TTN_DENSE_TILE
+    DenseTabArgs TL, TR;
+    memset(&TL, 0, sizeof(TL)); memset(&TR, 0, sizeof(TR));
+    int TM = 1, TN = 1;
+    {
+        bool open = true;
+        std::vector<long long> rs(d);                        // stride of site k in the row index of L / the column index of R
+        { long long s = 1; for (int k = 0; k < m; ++k) { rs[k] = s; s *= x->dims[k]; } s = 1; for (int k = m; k < d; ++k) { rs[k] = s; s *= x->dims[k]; } }
+        for (int k : order) {
+            const int n = (int)x->dims[k];
+            if (open && (long long)TM * TN * n <= TTN_DENSE_TILE) { if (k < m) TM *= n; else TN *= n; }
+            else open = false;
+            DenseTabArgs& T = k < m ? TL : TR;
+            T.n[T.ns] = n; T.stride[T.ns] = st[k]; T.rstride[T.ns] = rs[k]; ++T.ns;
+        }
+    }
+    // scratch: [unit | offL | offR | rowL | colR | L ping-pong | R ping-pong]
+    long long szL = 4, szR = 4;
+    { long long p = 1; for (int k = 0; k < m; ++k) { p *= x->dims[k]; szL = std::max(szL, p * dense_ld(x->bound[k + 1])); } }
+    { long long p = 1; for (int k = d - 1; k >= m; --k) { p *= x->dims[k]; szR = std::max(szR, p * dense_ld(x->bound[k])); } }
+    auto pad4 = [](long long v) { return (v + 3) & ~3LL; };
+    const long long o_unit = 0, o_offL = 4, o_offR = o_offL + pad4(PL), o_rowL = o_offR + pad4(PR), o_colR = o_rowL + pad4((PL + 1) / 2),
+                    o_L = o_colR + pad4((PR + 1) / 2), o_R = o_L + 2 * szL * batch, o_end = o_R + 2 * szR * batch;
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)o_end);
+    if (rc) return rc;
+    double* base = g_scratch.as<double>();
+    if (m == 0) {
+        static const double unit[4] = {1.0, 0.0, 0.0, 0.0};
+        HIPCHK(hipMemcpyAsync(base + o_unit, unit, sizeof(unit), hipMemcpyHostToDevice, g_stream));
+    }
+    TL.count = PL; TL.off = reinterpret_cast<long long*>(base + o_offL); TL.idx = reinterpret_cast<int*>(base + o_rowL);
+    TR.count = PR; TR.off = reinterpret_cast<long long*>(base + o_offR); TR.idx = reinterpret_cast<int*>(base + o_colR);
+    for (DenseTabArgs* T : {&TL, &TR}) {
+        const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((T->count + TTN_DENSE_TB - 1) / TTN_DENSE_TB, 1024));
+        hipLaunchKernelGGL(k_dense_tables, dim3(blocks), dim3(TTN_DENSE_TB), 0, g_stream, *T);
+    }
+    double* Lb = base + o_L;
+    double* Rb = base + o_R;
+    DenseArgs A;
+    memset(&A, 0, sizeof(A));
+    if (m > 0) { const int w = dense_chain(x, 0, 0, m, Lb, Lb + szL * batch, szL); A.L = w ? Lb + szL * batch : Lb; A.strideL = szL; }
+    else { A.L = base + o_unit; A.strideL = 0; }
+    { const int w = dense_chain(x, 1, d - 1, d - m, Rb, Rb + szR * batch, szR); A.R = w ? Rb + szR * batch : Rb; A.strideR = szR; }
+    A.rks = x->d_rks; A.d = d; A.m = m;
+    A.offL = TL.off; A.offR = TR.off; A.rowL = TL.idx; A.colR = TR.idx;
+    A.tilesL = PL / TM; A.TM = TM; A.TN = TN; A.total = total; A.out = d_out;
+    const long long seg = (long long)TM * TN;
+    A.vec2 = (seg % 2 == 0 && (total % 2 == 0 || batch == 1) && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_dense_product, dim3((unsigned)(total / seg), (unsigned)batch), dim3(TTN_DENSE_TB), 0, g_stream, A);
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+int ttn_qtt_grid_points(int64_t n_dims, int64_t bits, int interleaved, double a, double b, int64_t first, int64_t count, double* d_X) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!d_X) return fail(TTN_ERR_ARG, "null argument");
+    if (n_dims < 1 || bits < 1 || bits > 52 || n_dims * bits > 62) return fail(TTN_ERR_ARG, "ttn_qtt_grid_points: need n_dims >= 1, 1 <= bits <= 52, n_dims * bits <= 62");
+    if (first < 0 || count < 0 || count > ((int64_t)1 << (n_dims * bits)) - first) return fail(TTN_ERR_ARG, "ttn_qtt_grid_points: first .. first + count - 1 leaves the tensor");
+    if (count == 0) return TTN_OK;
+    const double h = (b - a) / (double)(((int64_t)1 << bits) - 1);
+    const unsigned blocks = (unsigned)std::min<long long>((count + TTN_DENSE_TB - 1) / TTN_DENSE_TB, 4096);
+    hipLaunchKernelGGL(k_qtt_grid_points, dim3(blocks), dim3(TTN_DENSE_TB), 0, g_stream, (int)n_dims, (int)bits, interleaved ? 1 : 0, a, h,
+                       (long long)first, (long long)count, d_X);
+    HIPCHK(hipGetLastError());
     return TTN_OK;
 }
 

@@ -210,6 +210,28 @@ class DeviceTT:
         _lib.check(_lib.lib().ttn_tt_diag_tto(self.h, int(b), C.byref(h)))
         return DeviceTTO._adopt(h)
 
+    # train -> dense tensor (csrc/ttn_grid_kernels.h)
+    def to_dense(self, strides: Sequence[int] | None = None):
+        """Every train of the batch as a dense tensor, on the device: a float64 torch tensor (batch, total) with
+        out[b, sum_k (i_k - 1) strides[k]] = x_b(i_1..i_N).  ``strides=None`` is Julia column-major (``ttv_to_tensor``); any other table
+        must be a mixed-radix system of the dims (ttn_tt_to_dense refuses the rest).  Asynchronous: the kernels run on the library's
+        stream, and torch's current stream is made to wait for them, so the tensor can be used there right away."""
+        from .tdvp import _dev
+        torch, stream = _dev()
+        if strides is not None and len(strides) != self.N:
+            raise _lib.TTNError(f"to_dense: {len(strides)} strides for {self.N} sites")
+        total = 1
+        for n in self.dims:
+            total *= n
+        caller = torch.cuda.current_stream()
+        with torch.cuda.stream(stream):
+            out = torch.empty((self.batch, total), dtype=torch.float64, device="cuda")
+            _lib.check(_lib.lib().ttn_tt_to_dense(self.h, None if strides is None else _i64(strides), C.c_void_p(out.data_ptr())))
+        if caller != stream:
+            caller.wait_stream(stream)
+            out.record_stream(caller)
+        return out
+
     def free(self):
         if self.h:
             _lib.lib().ttn_tt_free(self.h)

@@ -58,6 +58,11 @@ def hadamard_ttm_(x: DeviceTT, y: DeviceTT, z: DeviceTT, tol: float = 1.0e-14, r
 
 
 # ---- host level (one train: upload, run, download) ----------------------------------------------------------------------
+def swap_rank_capacity(n_phys: int) -> int:
+    """Largest rank the swap kernel holds for sites of physical dimension n_phys (an operator site counts n²): n · rank <= 256."""
+    return 256 // int(n_phys)
+
+
 def _swap_capacity(d: int, cap: int) -> List[int]:
     """Uniform rank capacity: a swap SVD keeps min(n r_left, n r_right) directions (all of them when threshold == 0), which
     can exceed the minimal-TT bound prod(dims[:k]) of the bond — the chain is not in minimal form in between."""
@@ -81,7 +86,7 @@ def reorder(x: TTvector, n_dims: int, bits_per_dim: int, new_ordering: str, thre
     metadata (currently in the OTHER ordering).  Returns the reordered TTvector."""
     assert x.N == n_dims * bits_per_dim
     n = int(x.ttv_dims[0])
-    dx = DeviceTT.from_host(x, cap_rks=_swap_capacity(x.N, 256 // n))
+    dx = DeviceTT.from_host(x, cap_rks=_swap_capacity(x.N, swap_rank_capacity(n)))
     swap_sites_(dx, bubble_sort_swaps(reorder_perm(n_dims, bits_per_dim, new_ordering)), threshold)
     compress_status(dx)
     dx.max_ranks()
@@ -98,7 +103,7 @@ def reorder_op(A: TToperator, n_dims: int, bits_per_dim: int, new_ordering: str,
     dims = tuple(n * n for _ in range(A.N))
     vec = TTvector(A.N, [np.reshape(np.asfortranarray(c), (n * n, c.shape[2], c.shape[3]), order="F") for c in A.tto_vec],
                    dims, list(A.tto_rks), [0] * A.N)
-    dx = DeviceTT.from_host(vec, cap_rks=_swap_capacity(A.N, 256 // (n * n)))
+    dx = DeviceTT.from_host(vec, cap_rks=_swap_capacity(A.N, swap_rank_capacity(n * n)))
     swap_sites_(dx, bubble_sort_swaps(reorder_perm(n_dims, bits_per_dim, new_ordering)), threshold)
     compress_status(dx)
     dx.max_ranks()
@@ -117,6 +122,21 @@ def ttv_decomp_(z: DeviceTT, tensors, index: int = 1, tol: float = 1.0e-12) -> D
     assert arr.shape == (z.batch,) + tuple(z.dims), "tensors must have shape (batch, *dims)"
     flat = np.ascontiguousarray(np.stack([np.ravel(arr[b], order="F") for b in range(z.batch)]))
     _lib.check(_lib.lib().ttn_ttv_decomp(z.h, flat.ctypes.data_as(C.c_void_p), int(index), float(tol)))
+    return z
+
+
+def ttv_decomp_dev_(z: DeviceTT, d_tensors, index: int = 1, tol: float = 1.0e-12) -> DeviceTT:
+    """ttv_decomp_ with the tensors already on the device: a contiguous float64 torch tensor of batch * prod(dims) entries, each
+    tensor column-major like the reference's Array, on the library's stream.  It is only read."""
+    from .tdvp import _operands, _p
+    if _operands(d_tensors):
+        raise TypeError("ttv_decomp_dev_: the device decomposition is Float64 only, a complex tensor was passed")
+    total = 1
+    for n in z.dims:
+        total *= n
+    if d_tensors.numel() != z.batch * total:
+        raise _lib.TTNError(f"ttv_decomp_dev_: {d_tensors.numel()} entries for {z.batch} tensors of {total}")
+    _lib.check(_lib.lib().ttn_ttv_decomp_dev(z.h, _p(d_tensors), int(index), float(tol)))
     return z
 
 

@@ -10,6 +10,7 @@ meaning and error behaviour:
     hadamard (⊕)                             src/tt_operations.jl:343-363
     +, add!, scalar *, -, /                  src/tt_operations.jl:10-66, :256-295
     orthogonalize(x; i=1)                    src/tt_tools.jl:511-543
+    ttv_to_tensor                            src/tt_tools.jl (dense tensor of a train)
     _tt_bond_truncate!, tt_compress!         src/tt_tools.jl:743-789   (``!`` -> trailing ``_``)
     r_and_d_to_rks                           src/tt_tools.jl:407-425
     TToperator * TToperator, +, -, scalar *  src/tt_operations.jl:71-95, :162-172, :271-291   (opalg.py)
@@ -310,6 +311,19 @@ def orthogonalize(x_tt: TTvector, i: int = 1) -> TTvector:
     yr = [int(v) for v in yr]
     cores = _rewrap(Y, x_tt.ttv_dims, yr)
     return TTvector(d, cores, x_tt.ttv_dims, yr, [int(v) for v in yot])
+
+
+def ttv_to_tensor(x: TTvector) -> np.ndarray:
+    """ttv_to_tensor(x) — src/tt_tools.jl: the dense tensor of shape ``x.ttv_dims``, contracted on the device (ttn_tt_to_dense)."""
+    from .device import DeviceTT
+    if _is_cplx(x.ttv_vec):
+        raise TypeError("ttv_to_tensor: complex trains are not supported (Float64 only)")
+    h = DeviceTT.from_host(x)
+    try:
+        flat = h.to_dense().cpu().numpy()
+    finally:
+        h.free()
+    return np.reshape(flat[0], x.ttv_dims, order="F")
 
 
 def _rewrap(bufs: List[np.ndarray], dims, rks) -> List[np.ndarray]:
