@@ -183,6 +183,20 @@ __global__ void k_fold_status(const int* status, int batch, unsigned* pending) {
     if (m) atomicOr(pending, m);
 }
 
+// Owner of a handle that a call builds or only needs until it returns: the destructor frees the handle, with whatever device memory it
+// holds by then, on every return path, unless release() has handed it to the caller.
+template <class H, int (*Free)(H*)>
+struct Owned {
+    H* h = nullptr;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { if (h) Free(h); }
+    H* release() { H* t = h; h = nullptr; return t; }
+};
+using OwnedTT = Owned<ttn_tt_s, ttn_tt_free>;
+using OwnedTTO = Owned<ttn_tto_s, ttn_tto_free>;
+
 extern "C" {
 
 const char* ttn_version(void) { return "ttn-mi355x 0.1.0 (gfx950, fp64)"; }
@@ -338,7 +352,8 @@ static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks
     if (!dims || !cap_rks || !out || d < 1 || batch < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: bad argument");
     for (int64_t k = 0; k < d; ++k) if (dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: dims must be >= 1");
     for (int64_t k = 0; k <= d; ++k) if (cap_rks[k] < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: ranks must be >= 1");
-    ttn_tt_s* h = new ttn_tt_s();
+    OwnedTT own;
+    ttn_tt_s* h = own.h = new ttn_tt_s();
     h->d = (int)d; h->batch = (int)batch; h->el = el;
     h->dims.assign(dims, dims + d);
     h->cap.assign(cap_rks, cap_rks + d + 1);
@@ -365,10 +380,8 @@ static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks
         (e = hipMalloc((void**)&h->d_cap, sizeof(long long) * (d + 1))) != hipSuccess ||
         (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (size_t)batch * (d + 1))) != hipSuccess ||
         (e = hipMalloc((void**)&h->d_dims, sizeof(int) * d)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_status, sizeof(int) * 2 * (size_t)batch)) != hipSuccess) {
-        ttn_tt_free(h);
+        (e = hipMalloc((void**)&h->d_status, sizeof(int) * 2 * (size_t)batch)) != hipSuccess)
         return hipfail(e, "hipMalloc(ttn_tt)");
-    }
     HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_cap, cap64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_rks, rk0.data(), sizeof(long long) * rk0.size(), hipMemcpyHostToDevice, g_stream));
@@ -377,7 +390,7 @@ static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks
     HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int) * 2 * (size_t)batch, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     g_live.insert(h);
-    *out = h;
+    *out = own.release();
     return TTN_OK;
 }
 
@@ -514,52 +527,74 @@ int ttn_tt_copy(ttn_tt_t dst, ttn_tt_t src) {
 }
 
 // ---- ttn_tto --------------------------------------------------------------------------------------
-static int tto_create_impl(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out, int el);
-int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 1); }
-int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 2); }
-static int tto_create_impl(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out, int el) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!dims || !rks || !cores || !out || d < 1) return fail(TTN_ERR_ARG, "ttn_tto_create: bad argument");
-    ttn_tto_s* h = new ttn_tto_s();
+// k_apply / k_hadamard / k_add count the fibres (p, q) of a core with 32-bit indices (ttn_stream_kernels.h): refuse larger cores here
+static bool stream_fibres_too_many(long long fibres) { return fibres >= (1LL << 31); }
+
+// The one place that lays out and allocates an operator handle: slots, device tables and, with `cores`, their upload.  A ttn_tto is
+// immutable and its ranks are host-known, so every operation of the operator algebra allocates its result here (`who`: its name) with
+// the cores left uninitialised: an output core beyond the 32-bit fibre indices of the streaming kernels is refused, and a result the
+// device cannot hold is TTN_ERR_CAPACITY (nothing is launched).  ttn_tto_create passes no `who` and reports the HIP error itself.
+static int tto_alloc(const char* who, int el, int64_t d, const int64_t* dims, const int64_t* rks, const int64_t* ot, const double* const* cores,
+                     OwnedTTO& out) {
+    if (who)
+        for (int64_t k = 0; k < d; ++k)
+            if (stream_fibres_too_many((long long)rks[k] * rks[k + 1]))
+                return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": 2^31 or more fibres in one output core (32-bit element indices)").c_str());
+    ttn_tto_s* h = out.h = new ttn_tto_s();
     h->d = (int)d; h->el = el;
     h->dims.assign(dims, dims + d);
     h->rks.assign(rks, rks + d + 1);
+    h->ot.assign(d, 0);
+    if (ot) h->ot.assign(ot, ot + d);
     h->off.resize(d + 1);
     long long o = 0;
     for (int64_t k = 0; k < d; ++k) {
         h->off[k] = o;
-        long long sz = (long long)el * dims[k] * dims[k] * rks[k] * rks[k + 1];
-        sz = (sz + 1) & ~1LL;
-        o += sz;
+        const long long sz = (long long)el * dims[k] * dims[k] * rks[k] * rks[k + 1];
+        o += (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
     }
     h->off[d] = o;
-    std::vector<double> flat((size_t)o, 0.0);
-    for (int64_t k = 0; k < d; ++k) {
-        if (!cores[k]) { delete h; return fail(TTN_ERR_ARG, "ttn_tto_create: null core"); }
-        std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);
-    }
     std::vector<int> idims(2 * d);
     for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(el * dims[k] * dims[k]); }
     std::vector<long long> r64(rks, rks + d + 1);
-    h->ot.assign(d, 0);
-    hipError_t e;
-    if ((e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1))) != hipSuccess ||
+    hipError_t e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1));
+    if (e != hipSuccess && who) {
+        (void)hipGetLastError();
+        h->d_data = nullptr;
+        return fail(TTN_ERR_CAPACITY, (std::string(who) + ": the result does not fit in device memory").c_str());
+    }
+    if (e != hipSuccess ||
         (e = hipMalloc((void**)&h->d_off, sizeof(long long) * (d + 1))) != hipSuccess ||
         (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * d)) != hipSuccess) {
-        ttn_tto_free(h);
+        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * d)) != hipSuccess)
         return hipfail(e, "hipMalloc(ttn_tto)");
-    }
     h->d_dims2 = h->d_dims + d;
-    HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * (size_t)o, hipMemcpyHostToDevice, g_stream));
+    std::vector<double> flat;                           // the cores at their slots, the rounding gaps zero
+    if (cores) {
+        flat.assign((size_t)o, 0.0);
+        for (int64_t k = 0; k < d; ++k) std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);
+        HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * (size_t)o, hipMemcpyHostToDevice, g_stream));
+    }
     HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * d, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    *out = h;
+    HIPCHK(hipStreamSynchronize(g_stream));          // the tables and `flat` are locals, `cores` is caller memory
     return TTN_OK;
 }
+
+static int tto_create_impl(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out, int el) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!dims || !rks || !cores || !out || d < 1) return fail(TTN_ERR_ARG, "ttn_tto_create: bad argument");
+    for (int64_t k = 0; k < d; ++k) if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_create: null core");
+    OwnedTTO A;
+    const int rc = tto_alloc(nullptr, el, d, dims, rks, nullptr, cores, A);
+    if (rc) return rc;
+    *out = A.release();
+    return TTN_OK;
+}
+int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 1); }
+int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 2); }
 
 int ttn_tto_free(ttn_tto_t h) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
@@ -580,32 +615,22 @@ static dim3 stream_grid(long long max_items, int d, int batch) {
     return dim3((unsigned)gx, (unsigned)d, (unsigned)batch);
 }
 
-// k_apply / k_hadamard / k_add count the fibres (p, q) of a core with 32-bit indices (ttn_stream_kernels.h): refuse larger cores here
-static bool stream_fibres_too_many(long long fibres) { return fibres >= (1LL << 31); }
-
-// ComplexF64 apply (k_zapply): complex operator and / or complex train into a complex y; the checks ran in ttn_apply
-static int zapply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
-    if (y->el != 2) return refuse_mixed("ttn_apply (a complex operand needs a ComplexF64 output handle)");
-    if (A->el != 2 && x->el != 2) return refuse_mixed("ttn_apply (a ComplexF64 output needs a complex operator or train)");
-    const int d = x->d;
-    long long items = 1;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
-    for (int k = 0; k < d; ++k) {
-        const long long P = (long long)A->rks[k] * x->bound[k], Q = (long long)A->rks[k + 1] * x->bound[k + 1];
-        if (stream_fibres_too_many(P * Q)) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
-        items = std::max(items, P * ((Q + TTN_ZAPPLY_K - 1) / TTN_ZAPPLY_K));
-    }
+// The two steps every form of A * x shares (ttn_apply, ttn_apply_compress, ttn_apply_begin).  apply_capacity: y can hold the product's
+// ranks A.rks .* x.rks.  apply_ranks: y receives them, on the device and as host bounds, with the gauge flags of zeros_tt
+// (tt_operations.jl:103).
+static int apply_capacity(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
+    for (int m = 0; m <= x->d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
+    return TTN_OK;
+}
+static int apply_ranks(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     hipLaunchKernelGGL(k_ranks_mul_op, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
-    const dim3 grid = stream_grid(items, d, x->batch), tb(TTN_STREAM_TB);
-    if (A->el == 2 && x->el == 2) hipLaunchKernelGGL((k_zapply<true, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
-    else if (A->el == 2) hipLaunchKernelGGL((k_zapply<true, false>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
-    else hipLaunchKernelGGL((k_zapply<false, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
     HIPCHK(hipGetLastError());
-    for (int m = 0; m <= d; ++m) y->bound[m] = A->rks[m] * x->bound[m];
+    for (int m = 0; m <= x->d; ++m) y->bound[m] = A->rks[m] * x->bound[m];
     std::fill(y->ot.begin(), y->ot.end(), 0);
     return TTN_OK;
 }
 
+// Float64 operator and trains: k_apply.  A complex operator and / or a complex train into a complex y: k_zapply.
 int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
@@ -613,36 +638,52 @@ int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (x == y) return fail(TTN_ERR_ARG, "ttn_apply: output must not alias the input");
-    if (A->el == 2 || x->el == 2 || y->el == 2) return zapply(A, x, y);
+    const bool cplx = A->el == 2 || x->el == 2 || y->el == 2;
+    if (cplx && y->el != 2) return refuse_mixed("ttn_apply (a complex operand needs a ComplexF64 output handle)");
+    if (cplx && A->el != 2 && x->el != 2) return refuse_mixed("ttn_apply (a ComplexF64 output needs a complex operator or train)");
     const int d = x->d;
-    long long maxfib = 0;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
-    for (int k = 0; k < d; ++k) maxfib = std::max<long long>(maxfib, (long long)x->bound[k] * x->bound[k + 1]);
-    if (stream_fibres_too_many(maxfib * std::max<long long>(1, A->rks[0]))) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one core (32-bit element indices)");
-    for (int k = 0; k < d; ++k) if (stream_fibres_too_many((long long)y->cap[k] * y->cap[k + 1])) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
-    hipLaunchKernelGGL(k_ranks_mul_op, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
-    // LDS of k_apply: the largest operator core (if it fits TTN_APPLY_LDS_DOUBLES) + the store-transpose buffer for the largest left rank
-    long long amax_ = 0, rlmax_ = 1;
-    for (int k = 0; k < d; ++k) { amax_ = std::max<long long>(amax_, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]); rlmax_ = std::max<long long>(rlmax_, A->rks[k]); }
-    const int lds_a = amax_ <= TTN_APPLY_LDS_DOUBLES ? (int)amax_ : 0;
-    const int lds_rl = rlmax_ <= TTN_APPLY_MAX_RL ? (int)rlmax_ : 0;
-    const size_t apply_lds = sizeof(double) * (size_t)((lds_a + 1) & ~1) + sizeof(double) * 2 * (size_t)(TTN_STREAM_TB / 64) * lds_rl * 64;
-    // grid: output rows x groups of TTN_APPLY_K output columns when every site has n = 2 and the operator cores fit the LDS (the mapping
-    // of k_apply's fast path), input fibres otherwise
-    long long apply_items = maxfib;
-    {
-        bool qtt = lds_a > 0;
-        for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
-        if (qtt) {
-            apply_items = 0;
-            for (int k = 0; k < d; ++k)
-                apply_items = std::max<long long>(apply_items, (long long)A->rks[k] * x->bound[k] * (((long long)A->rks[k + 1] * x->bound[k + 1] + TTN_APPLY_K - 1) / TTN_APPLY_K));
+    int rc = apply_capacity(A, x, y);
+    if (rc) return rc;
+    const dim3 tb(TTN_STREAM_TB);
+    if (cplx) {
+        long long items = 1;
+        for (int k = 0; k < d; ++k) {
+            const long long P = (long long)A->rks[k] * x->bound[k], Q = (long long)A->rks[k + 1] * x->bound[k + 1];
+            if (stream_fibres_too_many(P * Q)) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
+            items = std::max(items, P * ((Q + TTN_ZAPPLY_K - 1) / TTN_ZAPPLY_K));
         }
+        if ((rc = apply_ranks(A, x, y))) return rc;
+        const dim3 grid = stream_grid(items, d, x->batch);
+        if (A->el == 2 && x->el == 2) hipLaunchKernelGGL((k_zapply<true, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
+        else if (A->el == 2) hipLaunchKernelGGL((k_zapply<true, false>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
+        else hipLaunchKernelGGL((k_zapply<false, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
+    } else {
+        long long maxfib = 0;
+        for (int k = 0; k < d; ++k) maxfib = std::max<long long>(maxfib, (long long)x->bound[k] * x->bound[k + 1]);
+        if (stream_fibres_too_many(maxfib * std::max<long long>(1, A->rks[0]))) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one core (32-bit element indices)");
+        for (int k = 0; k < d; ++k) if (stream_fibres_too_many((long long)y->cap[k] * y->cap[k + 1])) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
+        if ((rc = apply_ranks(A, x, y))) return rc;
+        // LDS of k_apply: the largest operator core (if it fits TTN_APPLY_LDS_DOUBLES) + the store-transpose buffer for the largest left rank
+        long long amax_ = 0, rlmax_ = 1;
+        for (int k = 0; k < d; ++k) { amax_ = std::max<long long>(amax_, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]); rlmax_ = std::max<long long>(rlmax_, A->rks[k]); }
+        const int lds_a = amax_ <= TTN_APPLY_LDS_DOUBLES ? (int)amax_ : 0;
+        const int lds_rl = rlmax_ <= TTN_APPLY_MAX_RL ? (int)rlmax_ : 0;
+        const size_t apply_lds = sizeof(double) * (size_t)((lds_a + 1) & ~1) + sizeof(double) * 2 * (size_t)(TTN_STREAM_TB / 64) * lds_rl * 64;
+        // grid: output rows x groups of TTN_APPLY_K output columns when every site has n = 2 and the operator cores fit the LDS (the mapping
+        // of k_apply's fast path), input fibres otherwise
+        long long apply_items = maxfib;
+        {
+            bool qtt = lds_a > 0;
+            for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
+            if (qtt) {
+                apply_items = 0;
+                for (int k = 0; k < d; ++k)
+                    apply_items = std::max<long long>(apply_items, (long long)A->rks[k] * x->bound[k] * (((long long)A->rks[k + 1] * x->bound[k + 1] + TTN_APPLY_K - 1) / TTN_APPLY_K));
+            }
+        }
+        hipLaunchKernelGGL(k_apply, stream_grid(apply_items, d, x->batch), tb, apply_lds, g_stream, A->dev(), x->dev(), y->dev(), lds_a, lds_rl);
     }
-    hipLaunchKernelGGL(k_apply, stream_grid(apply_items, d, x->batch), dim3(TTN_STREAM_TB), apply_lds, g_stream, A->dev(), x->dev(), y->dev(), lds_a, lds_rl);
     HIPCHK(hipGetLastError());
-    for (int m = 0; m <= d; ++m) y->bound[m] = A->rks[m] * x->bound[m];
-    std::fill(y->ot.begin(), y->ot.end(), 0);     // zeros_tt (tt_operations.jl:103)
     return TTN_OK;
 }
 
@@ -671,6 +712,18 @@ int ttn_hadamard(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     return TTN_OK;
 }
 
+// The largest number of fibres r_k r_{k+1} of a core with ranks r, and the k_add launch z = x + y for result ranks zr.  n2: every
+// physical dimension of the trains as k_add reads them is 2 (its mapping of TTN_ADD_K fibres per thread), one fibre per thread otherwise.
+static long long max_fibres(const std::vector<int64_t>& r) {
+    long long m = 0;
+    for (size_t k = 0; k + 1 < r.size(); ++k) m = std::max<long long>(m, (long long)r[k] * r[k + 1]);
+    return m;
+}
+static void launch_add(const TTDev& x, const TTDev& y, const TTDev& z, const std::vector<int64_t>& zr, bool n2, int batch) {
+    const long long maxpq = max_fibres(zr);
+    hipLaunchKernelGGL(k_add, stream_grid(n2 ? (maxpq + TTN_ADD_K - 1) / TTN_ADD_K : maxpq, (int)zr.size() - 1, batch), dim3(TTN_STREAM_TB), 0, g_stream, x, y, z);
+}
+
 int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
@@ -683,15 +736,13 @@ int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: the reference's + is only defined for d >= 2");
     std::vector<int64_t> zb(d + 1);
     for (int m = 0; m <= d; ++m) zb[m] = (m == 0 || m == d) ? 1 : x->bound[m] + y->bound[m];
-    long long maxpq = 0;
     for (int m = 0; m <= d; ++m) if (z->cap[m] < zb[m]) return fail(TTN_ERR_CAPACITY, "ttn_add: destination capacity too small");
-    for (int k = 0; k < d; ++k) maxpq = std::max<long long>(maxpq, (long long)zb[k] * zb[k + 1]);
-    if (stream_fibres_too_many(maxpq)) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: 2^31 or more fibres in one core (32-bit element indices)");
+    if (stream_fibres_too_many(max_fibres(zb))) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: 2^31 or more fibres in one core (32-bit element indices)");
     hipLaunchKernelGGL(k_ranks_add, dim3(x->batch), dim3(64), 0, g_stream, z->dev(), x->dev(), y->dev());
     // (a complex core (n, r, r') is byte for byte the real core (2n, r, r') and + only copies: k_add runs on that view)
     bool qtt = x->el == 1;
     for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
-    hipLaunchKernelGGL(k_add, stream_grid(qtt ? (maxpq + TTN_ADD_K - 1) / TTN_ADD_K : maxpq, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), z->dev());
+    launch_add(x->dev(), y->dev(), z->dev(), zb, qtt, x->batch);
     HIPCHK(hipGetLastError());
     z->bound = zb;
     std::fill(z->ot.begin(), z->ot.end(), 0);
@@ -700,41 +751,65 @@ int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
 
 // The core scalar multiplication scales: the first one with ot == 0, else the first (tt_operations.jl:262).  Uniform over the batch
 // -> `which`; trains with different gauge flags (uploaded one by one, or zeroed by ttn_scale_batch) -> a per-train device table.
-static int scaled_core(ttn_tt_t x, int& which, const int*& which_b) {
-    const int d = x->d;
-    std::vector<int> h_which(x->batch, 0);
+// ot: [batch][d] gauge flags.
+static int scaled_core(const int64_t* ot, int d, int batch, int& which, const int*& which_b) {
+    std::vector<int> h_which(batch, 0);
     bool uniform = true;
-    for (int b = 0; b < x->batch; ++b) {
-        for (int k = 0; k < d; ++k) if (x->ot[(size_t)b * d + k] == 0) { h_which[b] = k; break; }
+    for (int b = 0; b < batch; ++b) {
+        for (int k = 0; k < d; ++k) if (ot[(size_t)b * d + k] == 0) { h_which[b] = k; break; }
         uniform = uniform && h_which[b] == h_which[0];
     }
     which = h_which[0];
     which_b = nullptr;
     if (uniform) return TTN_OK;
-    const int rc = g_which.ensure(sizeof(int) * x->batch);
+    const int rc = g_which.ensure(sizeof(int) * batch);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g_which.p, h_which.data(), sizeof(int) * x->batch, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(g_which.p, h_which.data(), sizeof(int) * batch, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));              // h_which is a local
     which_b = g_which.as<int>();
     return TTN_OK;
 }
 
-// a * x on ComplexF64 handles (k_zscale): one complex factor (ab null) or one per train (ab: device, interleaved; zero_b: which are 0)
-static int zscale(const char* who, double ar, double ai, const double* ab, const std::vector<char>* zero_b, ttn_tt_t x, ttn_tt_t y) {
-    const int d = x->d;
+// The launch of y = a * x on trains of element type `el` (an operator passes its vector view): k_scale with the factor ar, k_scale_batch
+// with one factor per train (ab: device), k_zscale with the complex factor (ar, ai) or one per train (ab: device, interleaved).
+// dims / rks: physical dimensions (in elements) and rank bounds of x; zero: the one factor is 0.
+static void launch_scale(int el, int d, int batch, const int64_t* dims, const int64_t* rks, const TTDev& x, const TTDev& y, double ar, double ai,
+                         const double* ab, int which, const int* which_b, bool zero) {
+    long long maxsz = 0;
+    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)dims[k] * rks[k] * rks[k + 1]);
+    const dim3 tb(TTN_STREAM_TB);
+    if (el == 2) hipLaunchKernelGGL(k_zscale, stream_grid((maxsz + 3) / 4, d, batch), tb, 0, g_stream, x, y, ar, ai, which, zero ? 1 : 0, which_b, ab);
+    else if (ab) hipLaunchKernelGGL(k_scale_batch, stream_grid((maxsz + 7) / 8, d, batch), tb, 0, g_stream, x, y, ab, which, which_b);
+    else hipLaunchKernelGGL(k_scale, stream_grid((maxsz + 7) / 8, d, batch), tb, 0, g_stream, x, y, ar, which, zero ? 1 : 0, which_b);
+}
+
+// y = a * x on handles of one element type, behind every exported scale of a train.  The factor is (ar, ai) (ai: ComplexF64 only), or,
+// with a_b, one per train: `batch` host values of x's element type.
+static int scale_impl(const char* who, double ar, double ai, const double* a_b, ttn_tt_t x, ttn_tt_t y) {
+    const int d = x->d, el = x->el;
     for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, (std::string(who) + ": destination capacity too small").c_str());
+    if (a_b) {
+        const int rc = g_dout.ensure(sizeof(double) * el * x->batch);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(g_dout.p, a_b, sizeof(double) * el * x->batch, hipMemcpyHostToDevice, g_stream));
+    }
+    // i = findfirst(==(0), ot), else 1  (tt_operations.jl:262), per train
     int which = 0;
     const int* which_b = nullptr;
-    { int rc_ = scaled_core(x, which, which_b); if (rc_) return rc_; }
-    long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)x->dims[k] * x->bound[k] * x->bound[k + 1]);
-    const bool zero = !ab && ar == 0.0 && ai == 0.0;
+    { int rc_ = scaled_core(x->ot.data(), d, x->batch, which, which_b); if (rc_) return rc_; }
+    const bool zero = !a_b && ar == 0.0 && ai == 0.0;
     if (x != y) hipLaunchKernelGGL(k_ranks_copy, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), x->dev());
-    hipLaunchKernelGGL(k_zscale, stream_grid((maxsz + 3) / 4, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), ar, ai, which, zero ? 1 : 0, which_b, ab);
+    launch_scale(el, d, x->batch, x->dims.data(), x->bound.data(), x->dev(), y->dev(), ar, ai, a_b ? g_dout.as<const double>() : nullptr, which, which_b, zero);
     HIPCHK(hipGetLastError());
+    if (a_b) HIPCHK(hipStreamSynchronize(g_stream));      // `a_b` is caller memory and g_dout is reused by ttn_dot
     y->bound = x->bound;
     if (zero) std::fill(y->ot.begin(), y->ot.end(), 0); else y->ot = x->ot;
-    if (zero_b) for (int b = 0; b < x->batch; ++b) if ((*zero_b)[b]) for (int k = 0; k < d; ++k) y->ot[(size_t)b * d + k] = 0;
+    if (a_b)
+        for (int b = 0; b < x->batch; ++b) {
+            bool zero_b = true;
+            for (int c = 0; c < el; ++c) zero_b = zero_b && a_b[(size_t)el * b + c] == 0.0;
+            if (zero_b) for (int k = 0; k < d; ++k) y->ot[(size_t)b * d + k] = 0;
+        }
     return TTN_OK;
 }
 
@@ -744,7 +819,7 @@ int ttn_scale_c64(double re, double im, ttn_tt_t x, ttn_tt_t y) {
     if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->el != 2 || y->el != 2) return refuse_mixed("ttn_scale_c64 (both handles must be ComplexF64)");
-    return zscale("ttn_scale_c64", re, im, nullptr, nullptr, x, y);
+    return scale_impl("ttn_scale_c64", re, im, nullptr, x, y);
 }
 
 int ttn_scale_batch_c64(const double* a, ttn_tt_t x, ttn_tt_t y) {
@@ -753,15 +828,7 @@ int ttn_scale_batch_c64(const double* a, ttn_tt_t x, ttn_tt_t y) {
     if (!a || !x || !y) return fail(TTN_ERR_ARG, "null pointer");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->el != 2 || y->el != 2) return refuse_mixed("ttn_scale_batch_c64 (both handles must be ComplexF64)");
-    int rc = g_dout.ensure(sizeof(double) * 2 * x->batch);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g_dout.p, a, sizeof(double) * 2 * x->batch, hipMemcpyHostToDevice, g_stream));
-    std::vector<char> zb(x->batch);
-    for (int b = 0; b < x->batch; ++b) zb[b] = (a[2 * b] == 0.0 && a[2 * b + 1] == 0.0) ? 1 : 0;
-    rc = zscale("ttn_scale_batch_c64", 0.0, 0.0, g_dout.as<const double>(), &zb, x, y);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g_stream));      // `a` is caller memory and g_dout is reused by ttn_dot
-    return TTN_OK;
+    return scale_impl("ttn_scale_batch_c64", 0.0, 0.0, a, x, y);
 }
 
 int ttn_scale(double a, ttn_tt_t x, ttn_tt_t y) {
@@ -770,21 +837,7 @@ int ttn_scale(double a, ttn_tt_t x, ttn_tt_t y) {
     if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->el != y->el) return refuse_mixed("ttn_scale");
-    if (x->el == 2) return zscale("ttn_scale", a, 0.0, nullptr, nullptr, x, y);
-    const int d = x->d;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_scale: destination capacity too small");
-    // i = findfirst(==(0), ot), else 1  (tt_operations.jl:262), per train
-    int which = 0;
-    const int* which_b = nullptr;
-    { int rc_ = scaled_core(x, which, which_b); if (rc_) return rc_; }
-    long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)x->dims[k] * x->bound[k] * x->bound[k + 1]);
-    if (x != y) hipLaunchKernelGGL(k_ranks_copy, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), x->dev());
-    hipLaunchKernelGGL(k_scale, stream_grid((maxsz + 7) / 8, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), a, which, a == 0.0 ? 1 : 0, which_b);
-    HIPCHK(hipGetLastError());
-    y->bound = x->bound;
-    if (a == 0.0) std::fill(y->ot.begin(), y->ot.end(), 0); else y->ot = x->ot;
-    return TTN_OK;
+    return scale_impl("ttn_scale", a, 0.0, nullptr, x, y);
 }
 
 int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
@@ -793,24 +846,7 @@ int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
     if (!a || !x || !y) return fail(TTN_ERR_ARG, "null pointer");
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     F64_ONLY("ttn_scale_batch (ComplexF64 handles: ttn_scale_batch_c64)", {x, y});
-    const int d = x->d;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_scale_batch: destination capacity too small");
-    int rc = g_dout.ensure(sizeof(double) * x->batch);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g_dout.p, a, sizeof(double) * x->batch, hipMemcpyHostToDevice, g_stream));
-    int which = 0;
-    const int* which_b = nullptr;
-    { int rc_ = scaled_core(x, which, which_b); if (rc_) return rc_; }
-    long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)x->dims[k] * x->bound[k] * x->bound[k + 1]);
-    if (x != y) hipLaunchKernelGGL(k_ranks_copy, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), x->dev());
-    hipLaunchKernelGGL(k_scale_batch, stream_grid((maxsz + 7) / 8, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), g_dout.as<const double>(), which, which_b);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(g_stream));      // `a` is caller memory and g_dout is reused by ttn_dot
-    y->bound = x->bound;
-    y->ot = x->ot;
-    for (int b = 0; b < x->batch; ++b) if (a[b] == 0.0) for (int k = 0; k < d; ++k) y->ot[(size_t)b * d + k] = 0;
-    return TTN_OK;
+    return scale_impl("ttn_scale_batch", 0.0, 0.0, a, x, y);
 }
 
 // ---- dense ops ------------------------------------------------------------------------------------
@@ -854,9 +890,6 @@ int ttn_compress_rank_bound(int64_t d, const int64_t* dims, const int64_t* rks, 
     return TTN_OK;
 }
 
-// Everything that can refuse a compress launch — capacity of the handle for the ranks the sweep can reach from `bound`, the size
-// limits of the merged matrices, the scratch allocation — checked WITHOUT touching the handle (ttn_apply_compress runs this on the
-// product's ranks before it overwrites y's).
 // Which build runs a compress launch, and on how many workgroup slots.  More trains than CUs: the 512-thread build on a PERSISTENT
 // grid of two workgroups per CU that pull trains from a counter (scratch per slot); otherwise one 1024-thread workgroup per train
 // (lowest latency for a single train).  TTN_WG512=1 / 0 forces / forbids the 512-thread build (diagnostics, parity tests).
@@ -868,6 +901,13 @@ static bool compress_use_wg512(int batch) {
 }
 static int compress_slots(int batch) { return compress_use_wg512(batch) ? std::min(batch, 2 * TTN_NUM_CUS) : batch; }
 
+// Limits of k_zcompress (include/ttn.h): short side <= 512, long side <= 8192 complex
+#define TTN_ZC_PMAX 512
+#define TTN_ZC_QMAX 8192
+// Everything that can refuse a compress launch — capacity of the handle for the ranks the sweep can reach from `bound`, the size
+// limits of the merged matrices, the scratch allocation — checked WITHOUT touching the handle (ttn_apply_compress runs this on the
+// product's ranks before it overwrites y's).
+// The two element types differ in those limits and in the scratch of a train (per_train, in doubles).
 static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, int64_t k_single, int64_t max_bond, int64_t sweeps,
                              int64_t k_first, int64_t k_last, std::vector<int64_t>& fin, long long& pmax, long long& qmax, long long& per_train) {
     const int d = psi->d;
@@ -876,6 +916,11 @@ static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, in
     rank_bounds(d, psi->dims.data(), bound.data(), max_bond, sweeps, k_single, need, fin, pmax, qmax, k_first, k_last);
     for (int m = 0; m <= d; ++m)
         if (need[m] > psi->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_compress: a bond rank can grow beyond the handle's capacity (see ttn_compress_rank_bound)");
+    if (psi->el == 2) {                        // k_zcompress: one workgroup per train
+        if (pmax > TTN_ZC_PMAX || qmax > TTN_ZC_QMAX) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress (ComplexF64): merged matrix larger than 512 x 8192");
+        per_train = zcompress_scratch(pmax, qmax);
+        return g_scratch.ensure(sizeof(double) * (size_t)per_train * psi->batch);
+    }
     if (pmax > 4096 || qmax > 16384) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress: merged matrix larger than 4096 x 16384");
     per_train = 2 * pmax * qmax + QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64 + 6 * 128 * 128;
     int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * compress_slots(psi->batch));
@@ -883,50 +928,29 @@ static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, in
     return g_dout.ensure(sizeof(double) * psi->batch);
 }
 
-// Limits of k_zcompress (include/ttn.h): short side <= 512, long side <= 8192 complex
-#define TTN_ZC_PMAX 512
-#define TTN_ZC_QMAX 8192
-static int zcompress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, int64_t k_single, int64_t max_bond, int64_t sweeps, int64_t k_first,
-                              int64_t k_last, std::vector<int64_t>& fin, long long& pmax, long long& qmax) {
-    std::vector<int64_t> need;
-    pmax = 1; qmax = 1;
-    rank_bounds(psi->d, psi->dims.data(), bound.data(), max_bond, sweeps, k_single, need, fin, pmax, qmax, k_first, k_last);
-    for (int m = 0; m <= psi->d; ++m)
-        if (need[m] > psi->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_compress: a bond rank can grow beyond the handle's capacity (see ttn_compress_rank_bound)");
-    if (pmax > TTN_ZC_PMAX || qmax > TTN_ZC_QMAX) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress (ComplexF64): merged matrix larger than 512 x 8192");
-    return g_scratch.ensure(sizeof(double) * (size_t)zcompress_scratch(pmax, qmax) * psi->batch);
-}
-static int launch_zcompress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, double truncerr, int64_t sweeps, int64_t k_first, int64_t k_last) {
-    const int d = psi->d;
-    if (d < 2 && k_single == 0) return TTN_OK;
-    std::vector<int64_t> fin;
-    long long pmax = 1, qmax = 1;
-    int rc = zcompress_precheck(psi, psi->bound, k_single, max_bond, sweeps, k_first, k_last, fin, pmax, qmax);
-    if (rc) return rc;
-    ZCompressArgs P;
-    P.tt = psi->dev();
-    P.max_bond = max_bond; P.truncerr = truncerr; P.sweeps = (int)sweeps;
-    P.k_single = (int)k_single; P.k_first = (int)k_first; P.k_last = (int)k_last;
-    P.scratch = g_scratch.as<double>();
-    P.scratch_stride = zcompress_scratch(pmax, qmax);
-    P.pmax = (int)pmax; P.qmax = (int)qmax;
-    P.status = psi->d_status;
-    P.sweep_stats = psi->d_status + psi->batch;
-    hipLaunchKernelGGL(k_zcompress, dim3(psi->batch), dim3(TTN_ZC_WG), TTN_ZC_LDS_BYTES, g_stream, P);
-    HIPCHK(hipGetLastError());
-    psi->bound = fin;
-    return TTN_OK;
-}
-
 static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, double truncerr, int64_t sweeps,
                            int64_t k_first = 0, int64_t k_last = 0, ttn_tto_t fuseA = nullptr, ttn_tt_t fusex = nullptr, int fused_first_real = 0) {
-    if (psi->el == 2) return launch_zcompress(psi, k_single, max_bond, truncerr, sweeps, k_first, k_last);
     const int d = psi->d;
     if (d < 2 && k_single == 0) return TTN_OK;
     std::vector<int64_t> fin;
     long long pmax = 1, qmax = 1, per_train = 0;
     int rc = compress_precheck(psi, psi->bound, k_single, max_bond, sweeps, k_first, k_last, fin, pmax, qmax, per_train);
     if (rc) return rc;
+    if (psi->el == 2) {                        // ComplexF64: k_zcompress (no fused merge, no singular-value capture, no 512-thread build)
+        ZCompressArgs P;
+        P.tt = psi->dev();
+        P.max_bond = max_bond; P.truncerr = truncerr; P.sweeps = (int)sweeps;
+        P.k_single = (int)k_single; P.k_first = (int)k_first; P.k_last = (int)k_last;
+        P.scratch = g_scratch.as<double>();
+        P.scratch_stride = per_train;
+        P.pmax = (int)pmax; P.qmax = (int)qmax;
+        P.status = psi->d_status;
+        P.sweep_stats = psi->d_status + psi->batch;
+        hipLaunchKernelGGL(k_zcompress, dim3(psi->batch), dim3(TTN_ZC_WG), TTN_ZC_LDS_BYTES, g_stream, P);
+        HIPCHK(hipGetLastError());
+        psi->bound = fin;
+        return TTN_OK;
+    }
     const int steps = k_single > 0 ? 1 : (k_single < 0 ? (int)(std::llabs(k_last - k_first) + 1) : (int)(2 * (d - 1) * sweeps));
     if (psi->sv_on) {
         if (psi->sv_steps < steps || psi->sv_pmax < pmax) {
@@ -1046,40 +1070,35 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    if (A->el == 2 || x->el == 2 || y->el == 2) {             // ComplexF64: apply, then round (no fused complex merge)
-        if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-        if (y->el != 2 || (A->el != 2 && x->el != 2)) return refuse_mixed("ttn_apply_compress");
-        // what can refuse the rounding is checked on the product's ranks before y is touched
-        std::vector<int64_t> yb(x->d + 1), fin_;
-        for (int m = 0; m <= x->d; ++m) yb[m] = A->rks[m] * x->bound[m];
-        for (int m = 0; m <= x->d; ++m) if (y->cap[m] < yb[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
-        if (x->d >= 2) { long long pm_, qm_; int rc = zcompress_precheck(y, yb, 0, max_bond, sweeps, 0, 0, fin_, pm_, qm_); if (rc) return rc; }
+    const bool cplx = A->el == 2 || x->el == 2 || y->el == 2;     // ComplexF64: apply, then round (no fused complex merge)
+    const char* nf = getenv("TTN_NOFUSE");
+    if (!cplx && (x->d < 2 || (nf && atoi(nf)))) {          // nothing to fuse into / diagnostic switch
         int rc = ttn_apply(A, x, y);
         if (rc) return rc;
         return ttn_compress(y, max_bond, truncerr, sweeps);
     }
-    const char* nf = getenv("TTN_NOFUSE");
-    if (x->d < 2 || (nf && atoi(nf))) {                     // nothing to fuse into / diagnostic switch
-        int rc = ttn_apply(A, x, y);
-        if (rc) return rc;
+    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (cplx) {
+        if (y->el != 2 || (A->el != 2 && x->el != 2)) return refuse_mixed("ttn_apply_compress");
+    } else {
+        if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+        if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_compress: output must not alias the input");
+    }
+    const int d = x->d;
+    int rc = apply_capacity(A, x, y);
+    if (rc) return rc;
+    // every check that can refuse the rounding runs on the product's ranks BEFORE y is touched: on an error return y still holds
+    // what it held (ranks, bounds, gauge flags and cores)
+    std::vector<int64_t> yb(d + 1), fin_;
+    for (int m = 0; m <= d; ++m) yb[m] = A->rks[m] * x->bound[m];
+    if (d >= 2) { long long pm_, qm_, pt_; if ((rc = compress_precheck(y, yb, 0, max_bond, sweeps, 0, 0, fin_, pm_, qm_, pt_))) return rc; }
+    if (cplx) {
+        if ((rc = ttn_apply(A, x, y))) return rc;
         return ttn_compress(y, max_bond, truncerr, sweeps);
     }
     // FUSED: y = A*x is never written to HBM.  y only receives its ranks (A.rks .* x.rks, tt_operations.jl:103); the first
     // L->R sweep of k_compress builds each merged matrix straight from core k of y, x_{k+1} and A_{k+1}.
-    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_compress: output must not alias the input");
-    const int d = x->d;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
-    // every check that can refuse the launch runs on the product's ranks BEFORE y is touched: on an error return y still holds
-    // what it held (ranks, bounds, gauge flags and cores)
-    std::vector<int64_t> yb(d + 1), fin_;
-    for (int m = 0; m <= d; ++m) yb[m] = A->rks[m] * x->bound[m];
-    { long long pm_, qm_, pt_; int rc = compress_precheck(y, yb, 0, max_bond, sweeps, 0, 0, fin_, pm_, qm_, pt_); if (rc) return rc; }
-    hipLaunchKernelGGL(k_ranks_mul_op, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
-    HIPCHK(hipGetLastError());
-    y->bound = yb;
-    std::fill(y->ot.begin(), y->ot.end(), 0);
+    if ((rc = apply_ranks(A, x, y))) return rc;
     return launch_compress(y, 0, max_bond, truncerr, sweeps, 0, 0, A, x);
 }
 
@@ -1093,13 +1112,8 @@ int ttn_apply_begin(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_begin: output must not alias the input");
-    const int d = x->d;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
-    hipLaunchKernelGGL(k_ranks_mul_op, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
-    HIPCHK(hipGetLastError());
-    for (int m = 0; m <= d; ++m) y->bound[m] = A->rks[m] * x->bound[m];
-    std::fill(y->ot.begin(), y->ot.end(), 0);
-    return TTN_OK;
+    const int rc = apply_capacity(A, x, y);
+    return rc ? rc : apply_ranks(A, x, y);
 }
 
 int ttn_apply_sweep(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t k_first, int64_t k_last, int64_t max_bond, double truncerr, int first_core_real) {
@@ -2547,96 +2561,180 @@ int ttn_tdvp_contract_f64(int op, int cplx, int64_t batch, const int64_t* dims7,
     return tdvp_launch(op, cplx, batch, dims7[0], dims7[1], dims7[2], dims7[3], dims7[4], dims7[5], dims7[6], FL, FR, X, M1, M2, out, m_shared, true);
 }
 
+// ---- stateless entry points on host arrays ----------------------------------------------------------------------------------------
+// Each one is: operands onto the device (host_tt / host_tto), the handle call, the result back (host_result).  The _f64 and _c64
+// exports of an operation share one body that takes the element type of every operand (el: 1 Float64, 2 ComplexF64 as interleaved
+// (re, im) doubles).
 namespace {
-struct TmpTT {
-    ttn_tt_t h = nullptr;
-    ~TmpTT() { if (h) ttn_tt_free(h); }
-};
-struct TmpTTO {
-    ttn_tto_t h = nullptr;
-    ~TmpTTO() { if (h) ttn_tto_free(h); }
-};
 int auto_init() {
     if (g_init) return TTN_OK;
     return ttn_init(0);
+}
+// a one-train handle of capacity `cap`; with `cores` it holds that train (ranks rks, gauge flags ot or zeros)
+int host_tt(OwnedTT& t, int el, int64_t d, const int64_t* dims, const int64_t* cap, const double* const* cores = nullptr, const int64_t* rks = nullptr,
+            const int64_t* ot = nullptr) {
+    const int rc = tt_create_impl(d, dims, cap, 1, &t.h, el);
+    if (rc || !cores) return rc;
+    return ttn_tt_upload(t.h, 0, cores, rks, ot);
+}
+int host_tto(OwnedTTO& A, int el, int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores) {
+    return tto_create_impl(d, dims, rks, cores, &A.h, el);
+}
+// the result of a stateless call: with `status`, a failure the dense kernels recorded on h is the call's error; then the ranks and
+// gauge flags that are asked for, and the cores
+int host_result(ttn_tt_t h, bool status, int64_t* rks, int64_t* ot, double* const* cores) {
+    int rc;
+    if (status && (rc = ttn_compress_status(h, nullptr))) return rc;
+    if ((rks || ot) && (rc = ttn_tt_ranks(h, 0, rks, ot))) return rc;
+    return ttn_tt_download(h, 0, cores);
+}
+
+int apply_host(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+               const int64_t* X_rks, double* const* Y_cores, int a_el, int x_el, int y_el) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    OwnedTTO A; OwnedTT x, y;
+    if ((rc = host_tto(A, a_el, d, dims, A_rks, A_cores))) return rc;
+    if ((rc = host_tt(x, x_el, d, dims, X_rks, X_cores, X_rks))) return rc;
+    std::vector<int64_t> yr(d + 1);
+    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
+    if ((rc = host_tt(y, y_el, d, dims, yr.data()))) return rc;
+    if ((rc = ttn_apply(A.h, x.h, y.h))) return rc;
+    return host_result(y.h, false, nullptr, nullptr, Y_cores);
+}
+
+int dot_host(int el, int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* B_cores,
+             const int64_t* B_rks, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !A_cores || !A_rks || !B_cores || !B_rks || !out || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    OwnedTT a, b;
+    if ((rc = host_tt(a, el, d, dims, A_rks, A_cores, A_rks))) return rc;
+    if ((rc = host_tt(b, el, d, dims, B_rks, B_cores, B_rks))) return rc;
+    return ttn_dot(a.h, b.h, out);
+}
+
+// z = x + y (sum) or the Hadamard product: the two differ in the ranks of z and in the handle call
+int binary_host(bool sum, int el, int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                const int64_t* Y_rks, double* const* Z_cores) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    OwnedTT x, y, z;
+    std::vector<int64_t> zr(d + 1);
+    for (int64_t m = 0; m <= d; ++m) zr[m] = !sum ? X_rks[m] * Y_rks[m] : (m == 0 || m == d) ? 1 : X_rks[m] + Y_rks[m];
+    if ((rc = host_tt(x, el, d, dims, X_rks, X_cores, X_rks))) return rc;
+    if ((rc = host_tt(y, el, d, dims, Y_rks, Y_cores, Y_rks))) return rc;
+    if ((rc = host_tt(z, el, d, dims, zr.data()))) return rc;
+    if ((rc = sum ? ttn_add(x.h, y.h, z.h) : ttn_hadamard(x.h, y.h, z.h))) return rc;
+    return host_result(z.h, false, nullptr, nullptr, Z_cores);
+}
+
+int scale_host(int el, int64_t d, const int64_t* dims, double re, double im, const double* const* X_cores, const int64_t* X_rks,
+               const int64_t* X_ot, double* const* Y_cores, int64_t* Y_ot) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    OwnedTT x, y;
+    if ((rc = host_tt(x, el, d, dims, X_rks, X_cores, X_rks, X_ot))) return rc;
+    if ((rc = host_tt(y, el, d, dims, X_rks))) return rc;
+    if ((rc = el == 2 ? ttn_scale_c64(re, im, x.h, y.h) : ttn_scale(re, x.h, y.h))) return rc;
+    return host_result(y.h, false, nullptr, Y_ot, Y_cores);
+}
+
+// tt_compress! (k = 0) or one _tt_bond_truncate! (k > 0) in place on the caller's buffers; the caller has held the lock and checked
+// sweeps / k, which need no device
+int compress_host(int el, int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond, double truncerr,
+                  int64_t sweeps) {
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !cores || !rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    OwnedTT x;
+    std::vector<int64_t> need, fin;
+    long long pm, qm;
+    rank_bounds((int)d, dims, rks, max_bond, sweeps, k, need, fin, pm, qm);
+    if ((rc = host_tt(x, el, d, dims, need.data(), cores, rks))) return rc;
+    if (k > 0) rc = ttn_bond_truncate(x.h, k, max_bond, truncerr);
+    else rc = ttn_compress(x.h, max_bond, truncerr, sweeps);
+    if (rc) return rc;
+    return host_result(x.h, true, rks, nullptr, cores);
+}
+
+// The ranks yr = A_rks .* X_rks of A * x and what rounding it can reach: need[m] >= yr[m] covers every rank bond m takes during
+// tt_compress!(A * x, max_bond; sweeps), fin[m] bounds it afterwards.
+void product_rank_bounds(int64_t d, const int64_t* dims, const int64_t* A_rks, const int64_t* X_rks, int64_t max_bond, int64_t sweeps,
+                         std::vector<int64_t>& need, std::vector<int64_t>& fin) {
+    std::vector<int64_t> yr(d + 1);
+    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
+    long long pm, qm;
+    rank_bounds((int)d, dims, yr.data(), max_bond, sweeps, 0, need, fin, pm, qm);
+    for (int64_t m = 0; m <= d; ++m) need[m] = std::max<int64_t>(need[m], yr[m]);
+}
+
+int apply_compress_host(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                        const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks, int64_t max_bond, double truncerr, int64_t sweeps,
+                        int a_el, int x_el, int y_el) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || !Y_rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
+    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
+    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    OwnedTTO A; OwnedTT x, y;
+    if ((rc = host_tto(A, a_el, d, dims, A_rks, A_cores))) return rc;
+    if ((rc = host_tt(x, x_el, d, dims, X_rks, X_cores, X_rks))) return rc;
+    std::vector<int64_t> need, fin;
+    product_rank_bounds(d, dims, A_rks, X_rks, max_bond, sweeps, need, fin);
+    if ((rc = host_tt(y, y_el, d, dims, need.data()))) return rc;
+    if ((rc = ttn_apply_compress(A.h, x.h, y.h, max_bond, truncerr, sweeps))) return rc;
+    return host_result(y.h, true, Y_rks, nullptr, Y_cores);
 }
 }  // namespace
 
 int ttn_apply_f64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks,
                   const double* const* X_cores, const int64_t* X_rks, double* const* Y_cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTTO A; TmpTT x, y;
-    if ((rc = ttn_tto_create(d, dims, A_rks, A_cores, &A.h))) return rc;
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, X_cores, X_rks, nullptr))) return rc;
-    std::vector<int64_t> yr(d + 1);
-    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
-    if ((rc = ttn_tt_create(d, dims, yr.data(), 1, &y.h))) return rc;
-    if ((rc = ttn_apply(A.h, x.h, y.h))) return rc;
-    return ttn_tt_download(y.h, 0, Y_cores);
+    return apply_host(d, dims, A_cores, A_rks, X_cores, X_rks, Y_cores, 1, 1, 1);
+}
+// a real operator or train stays real on the device; the result is complex
+int ttn_apply_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                  const int64_t* X_rks, double* const* Y_cores, int a_cplx, int x_cplx) {
+    return apply_host(d, dims, A_cores, A_rks, X_cores, X_rks, Y_cores, a_cplx ? 2 : 1, x_cplx ? 2 : 1, 2);
 }
 
 int ttn_dot_f64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks,
                 const double* const* B_cores, const int64_t* B_rks, double* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !A_cores || !A_rks || !B_cores || !B_rks || !out || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT a, b;
-    if ((rc = ttn_tt_create(d, dims, A_rks, 1, &a.h))) return rc;
-    if ((rc = ttn_tt_upload(a.h, 0, A_cores, A_rks, nullptr))) return rc;
-    if ((rc = ttn_tt_create(d, dims, B_rks, 1, &b.h))) return rc;
-    if ((rc = ttn_tt_upload(b.h, 0, B_cores, B_rks, nullptr))) return rc;
-    return ttn_dot(a.h, b.h, out);
+    return dot_host(1, d, dims, A_cores, A_rks, B_cores, B_rks, out);
+}
+int ttn_dot_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* B_cores,
+                const int64_t* B_rks, double* out) {
+    return dot_host(2, d, dims, A_cores, A_rks, B_cores, B_rks, out);
 }
 
 int ttn_hadamard_f64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks,
                      const double* const* Y_cores, const int64_t* Y_rks, double* const* Z_cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x, y, z;
-    std::vector<int64_t> zr(d + 1);
-    for (int64_t m = 0; m <= d; ++m) zr[m] = X_rks[m] * Y_rks[m];
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, X_cores, X_rks, nullptr))) return rc;
-    if ((rc = ttn_tt_create(d, dims, Y_rks, 1, &y.h))) return rc;
-    if ((rc = ttn_tt_upload(y.h, 0, Y_cores, Y_rks, nullptr))) return rc;
-    if ((rc = ttn_tt_create(d, dims, zr.data(), 1, &z.h))) return rc;
-    if ((rc = ttn_hadamard(x.h, y.h, z.h))) return rc;
-    return ttn_tt_download(z.h, 0, Z_cores);
+    return binary_host(false, 1, d, dims, X_cores, X_rks, Y_cores, Y_rks, Z_cores);
+}
+int ttn_hadamard_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                     const int64_t* Y_rks, double* const* Z_cores) {
+    return binary_host(false, 2, d, dims, X_cores, X_rks, Y_cores, Y_rks, Z_cores);
 }
 
 int ttn_add_f64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks,
                 const double* const* Y_cores, const int64_t* Y_rks, double* const* Z_cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x, y, z;
-    std::vector<int64_t> zr(d + 1);
-    for (int64_t m = 0; m <= d; ++m) zr[m] = (m == 0 || m == d) ? 1 : X_rks[m] + Y_rks[m];
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, X_cores, X_rks, nullptr))) return rc;
-    if ((rc = ttn_tt_create(d, dims, Y_rks, 1, &y.h))) return rc;
-    if ((rc = ttn_tt_upload(y.h, 0, Y_cores, Y_rks, nullptr))) return rc;
-    if ((rc = ttn_tt_create(d, dims, zr.data(), 1, &z.h))) return rc;
-    if ((rc = ttn_add(x.h, y.h, z.h))) return rc;
-    return ttn_tt_download(z.h, 0, Z_cores);
+    return binary_host(true, 1, d, dims, X_cores, X_rks, Y_cores, Y_rks, Z_cores);
+}
+int ttn_add_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
+                const int64_t* Y_rks, double* const* Z_cores) {
+    return binary_host(true, 2, d, dims, X_cores, X_rks, Y_cores, Y_rks, Z_cores);
 }
 
 int ttn_scale_f64(int64_t d, const int64_t* dims, double a, const double* const* X_cores, const int64_t* X_rks,
                   const int64_t* X_ot, double* const* Y_cores, int64_t* Y_ot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x, y;
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, X_cores, X_rks, X_ot))) return rc;
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &y.h))) return rc;
-    if ((rc = ttn_scale(a, x.h, y.h))) return rc;
-    if (Y_ot) ttn_tt_ranks(y.h, 0, nullptr, Y_ot);
-    return ttn_tt_download(y.h, 0, Y_cores);
+    return scale_host(1, d, dims, a, 0.0, X_cores, X_rks, X_ot, Y_cores, Y_ot);
+}
+int ttn_scale_host_c64(int64_t d, const int64_t* dims, double re, double im, const double* const* X_cores, const int64_t* X_rks,
+                       const int64_t* X_ot, double* const* Y_cores, int64_t* Y_ot) {
+    return scale_host(2, d, dims, re, im, X_cores, X_rks, X_ot, Y_cores, Y_ot);
 }
 
 int ttn_orthogonalize_f64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, int64_t center,
@@ -2645,215 +2743,58 @@ int ttn_orthogonalize_f64(int64_t d, const int64_t* dims, const double* const* X
     int rc = auto_init(); if (rc) return rc;
     if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Y_ot || d < 1) return fail(TTN_ERR_ARG, "bad argument");
     if (center < 1 || center > d) return fail(TTN_ERR_CENTER, "Impossible orthogonalization");
-    TmpTT x, y;
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, X_cores, X_rks, nullptr))) return rc;
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &y.h))) return rc;
+    OwnedTT x, y;
+    if ((rc = host_tt(x, 1, d, dims, X_rks, X_cores, X_rks))) return rc;
+    if ((rc = host_tt(y, 1, d, dims, X_rks))) return rc;
     if ((rc = ttn_orthogonalize(x.h, center, y.h))) return rc;
-    if ((rc = ttn_tt_ranks(y.h, 0, Y_rks, Y_ot))) return rc;
-    return ttn_tt_download(y.h, 0, Y_cores);
-}
-
-static int compress_host(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond,
-                         double truncerr, int64_t sweeps) {
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !cores || !rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x;
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    std::vector<int64_t> need, fin;
-    long long pm, qm;
-    rank_bounds((int)d, dims, rks, max_bond, sweeps, k, need, fin, pm, qm);
-    if ((rc = ttn_tt_create(d, dims, need.data(), 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, cores, rks, nullptr))) return rc;
-    if (k > 0) rc = ttn_bond_truncate(x.h, k, max_bond, truncerr);
-    else rc = ttn_compress(x.h, max_bond, truncerr, sweeps);
-    if (rc) return rc;
-    if ((rc = ttn_compress_status(x.h, nullptr))) return rc;
-    if ((rc = ttn_tt_ranks(x.h, 0, rks, nullptr))) return rc;
-    return ttn_tt_download(x.h, 0, cores);
+    return host_result(y.h, false, Y_rks, Y_ot, Y_cores);
 }
 
 int ttn_compress_f64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t max_bond, double truncerr,
                      int64_t sweeps) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
-    return compress_host(d, dims, cores, rks, 0, max_bond, truncerr, sweeps);
+    return compress_host(1, d, dims, cores, rks, 0, max_bond, truncerr, sweeps);
 }
-
-// The Krylov operator of the reference in ONE stateless call: op = x -> tt_compress!(A * x, max_bond) (src/solvers/euler.jl:55).  A * x
-// is never materialised (fused apply, k_compress builds the merged matrices from x and A) — neither in HBM nor over PCIe: the host
-// hands over A and x, and receives the compressed train.  Y_cores[k] sized n_k * cap_k * cap_{k+1} with cap = min(A_rks .* X_rks,
-// max_bond-capped bounds) as ttn_apply_compress_rank_bound returns them; Y_rks receives the ranks.
-int ttn_apply_compress_rank_bound(int64_t d, const int64_t* dims, const int64_t* A_rks, const int64_t* X_rks, int64_t max_bond, int64_t sweeps,
-                                  int64_t* cap) {
+int ttn_compress_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t max_bond, double truncerr, int64_t sweeps) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!dims || !A_rks || !X_rks || !cap || d < 1 || max_bond < 1 || sweeps < 1) return fail(TTN_ERR_ARG, "bad argument");
-    std::vector<int64_t> yr(d + 1), need, fin;
-    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
-    long long pm, qm;
-    rank_bounds((int)d, dims, yr.data(), max_bond, sweeps, 0, need, fin, pm, qm);
-    for (int64_t m = 0; m <= d; ++m) cap[m] = fin[m];
-    return TTN_OK;
-}
-int ttn_apply_compress_f64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
-                           const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks, int64_t max_bond, double truncerr, int64_t sweeps) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || !Y_rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    TmpTTO A; TmpTT x, y;
-    if ((rc = ttn_tto_create(d, dims, A_rks, A_cores, &A.h))) return rc;
-    if ((rc = ttn_tt_create(d, dims, X_rks, 1, &x.h))) return rc;
-    if ((rc = ttn_tt_upload(x.h, 0, X_cores, X_rks, nullptr))) return rc;
-    std::vector<int64_t> yr(d + 1), need, fin;
-    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
-    long long pm, qm;
-    rank_bounds((int)d, dims, yr.data(), max_bond, sweeps, 0, need, fin, pm, qm);
-    for (int64_t m = 0; m <= d; ++m) need[m] = std::max<int64_t>(need[m], yr[m]);
-    if ((rc = ttn_tt_create(d, dims, need.data(), 1, &y.h))) return rc;
-    if ((rc = ttn_apply_compress(A.h, x.h, y.h, max_bond, truncerr, sweeps))) return rc;
-    if ((rc = ttn_compress_status(y.h, nullptr))) return rc;
-    if ((rc = ttn_tt_ranks(y.h, 0, Y_rks, nullptr))) return rc;
-    return ttn_tt_download(y.h, 0, Y_cores);
+    return compress_host(2, d, dims, cores, rks, 0, max_bond, truncerr, sweeps);
 }
 
 int ttn_bond_truncate_f64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond,
                           double truncerr) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (k < 1 || k >= d) return fail(TTN_ERR_BOND_INDEX, "k must be in 1:(N-1)");
-    return compress_host(d, dims, cores, rks, k, max_bond, truncerr, 1);
+    return compress_host(1, d, dims, cores, rks, k, max_bond, truncerr, 1);
 }
-
-// ---- ComplexF64 stateless entry points: the _f64 calls above with interleaved (re, im) buffers -------------------------------------
-namespace {
-int up_tt(TmpTT& t, int64_t d, const int64_t* dims, const int64_t* cap, const double* const* cores, const int64_t* rks, const int64_t* ot, int cplx) {
-    int rc = cplx ? ttn_tt_create_c64(d, dims, cap, 1, &t.h) : ttn_tt_create(d, dims, cap, 1, &t.h);
-    if (rc) return rc;
-    return ttn_tt_upload(t.h, 0, cores, rks, ot);
-}
-}  // namespace
-
-int ttn_apply_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
-                  const int64_t* X_rks, double* const* Y_cores, int a_cplx, int x_cplx) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTTO A; TmpTT x, y;
-    if ((rc = a_cplx ? ttn_tto_create_c64(d, dims, A_rks, A_cores, &A.h) : ttn_tto_create(d, dims, A_rks, A_cores, &A.h))) return rc;
-    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, x_cplx))) return rc;
-    std::vector<int64_t> yr(d + 1);
-    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
-    if ((rc = ttn_tt_create_c64(d, dims, yr.data(), 1, &y.h))) return rc;
-    if ((rc = ttn_apply(A.h, x.h, y.h))) return rc;
-    return ttn_tt_download(y.h, 0, Y_cores);
-}
-
-int ttn_dot_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* B_cores,
-                const int64_t* B_rks, double* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !A_cores || !A_rks || !B_cores || !B_rks || !out || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT a, b;
-    if ((rc = up_tt(a, d, dims, A_rks, A_cores, A_rks, nullptr, 1))) return rc;
-    if ((rc = up_tt(b, d, dims, B_rks, B_cores, B_rks, nullptr, 1))) return rc;
-    return ttn_dot(a.h, b.h, out);
-}
-
-int ttn_hadamard_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
-                     const int64_t* Y_rks, double* const* Z_cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x, y, z;
-    std::vector<int64_t> zr(d + 1);
-    for (int64_t m = 0; m <= d; ++m) zr[m] = X_rks[m] * Y_rks[m];
-    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, 1))) return rc;
-    if ((rc = up_tt(y, d, dims, Y_rks, Y_cores, Y_rks, nullptr, 1))) return rc;
-    if ((rc = ttn_tt_create_c64(d, dims, zr.data(), 1, &z.h))) return rc;
-    if ((rc = ttn_hadamard(x.h, y.h, z.h))) return rc;
-    return ttn_tt_download(z.h, 0, Z_cores);
-}
-
-int ttn_add_c64(int64_t d, const int64_t* dims, const double* const* X_cores, const int64_t* X_rks, const double* const* Y_cores,
-                const int64_t* Y_rks, double* const* Z_cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !X_cores || !X_rks || !Y_cores || !Y_rks || !Z_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x, y, z;
-    std::vector<int64_t> zr(d + 1);
-    for (int64_t m = 0; m <= d; ++m) zr[m] = (m == 0 || m == d) ? 1 : X_rks[m] + Y_rks[m];
-    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, 1))) return rc;
-    if ((rc = up_tt(y, d, dims, Y_rks, Y_cores, Y_rks, nullptr, 1))) return rc;
-    if ((rc = ttn_tt_create_c64(d, dims, zr.data(), 1, &z.h))) return rc;
-    if ((rc = ttn_add(x.h, y.h, z.h))) return rc;
-    return ttn_tt_download(z.h, 0, Z_cores);
-}
-
-int ttn_scale_host_c64(int64_t d, const int64_t* dims, double re, double im, const double* const* X_cores, const int64_t* X_rks,
-                       const int64_t* X_ot, double* const* Y_cores, int64_t* Y_ot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !X_cores || !X_rks || !Y_cores || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    TmpTT x, y;
-    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, X_ot, 1))) return rc;
-    if ((rc = ttn_tt_create_c64(d, dims, X_rks, 1, &y.h))) return rc;
-    if ((rc = ttn_scale_c64(re, im, x.h, y.h))) return rc;
-    if (Y_ot) ttn_tt_ranks(y.h, 0, nullptr, Y_ot);
-    return ttn_tt_download(y.h, 0, Y_cores);
-}
-
-static int zcompress_host(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond, double truncerr,
-                          int64_t sweeps) {
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !cores || !rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    TmpTT x;
-    std::vector<int64_t> need, fin;
-    long long pm, qm;
-    rank_bounds((int)d, dims, rks, max_bond, sweeps, k, need, fin, pm, qm);
-    if ((rc = up_tt(x, d, dims, need.data(), cores, rks, nullptr, 1))) return rc;
-    if (k > 0) rc = ttn_bond_truncate(x.h, k, max_bond, truncerr);
-    else rc = ttn_compress(x.h, max_bond, truncerr, sweeps);
-    if (rc) return rc;
-    if ((rc = ttn_compress_status(x.h, nullptr))) return rc;
-    if ((rc = ttn_tt_ranks(x.h, 0, rks, nullptr))) return rc;
-    return ttn_tt_download(x.h, 0, cores);
-}
-
-int ttn_compress_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t max_bond, double truncerr, int64_t sweeps) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
-    return zcompress_host(d, dims, cores, rks, 0, max_bond, truncerr, sweeps);
-}
-
 int ttn_bond_truncate_c64(int64_t d, const int64_t* dims, double* const* cores, int64_t* rks, int64_t k, int64_t max_bond, double truncerr) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (k < 1 || k >= d) return fail(TTN_ERR_BOND_INDEX, "k must be in 1:(N-1)");
-    return zcompress_host(d, dims, cores, rks, k, max_bond, truncerr, 1);
+    return compress_host(2, d, dims, cores, rks, k, max_bond, truncerr, 1);
 }
 
+// The Krylov operator of the reference in ONE stateless call: op = x -> tt_compress!(A * x, max_bond) (src/solvers/euler.jl:55).  A * x
+// is never materialised (fused apply, k_compress builds the merged matrices from x and A) — neither in HBM nor over PCIe: the host
+// hands over A and x, and receives the compressed train.  Y_cores[k] sized n_k * cap_k * cap_{k+1} with cap = min(A_rks .* X_rks,
+// max_bond-capped bounds) as ttn_apply_compress_rank_bound returns them; Y_rks receives the ranks.  (ComplexF64: apply, then round.)
+int ttn_apply_compress_rank_bound(int64_t d, const int64_t* dims, const int64_t* A_rks, const int64_t* X_rks, int64_t max_bond, int64_t sweeps,
+                                  int64_t* cap) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!dims || !A_rks || !X_rks || !cap || d < 1 || max_bond < 1 || sweeps < 1) return fail(TTN_ERR_ARG, "bad argument");
+    std::vector<int64_t> need, fin;
+    product_rank_bounds(d, dims, A_rks, X_rks, max_bond, sweeps, need, fin);
+    for (int64_t m = 0; m <= d; ++m) cap[m] = fin[m];
+    return TTN_OK;
+}
+int ttn_apply_compress_f64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
+                           const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks, int64_t max_bond, double truncerr, int64_t sweeps) {
+    return apply_compress_host(d, dims, A_cores, A_rks, X_cores, X_rks, Y_cores, Y_rks, max_bond, truncerr, sweeps, 1, 1, 1);
+}
 int ttn_apply_compress_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,
                            const int64_t* X_rks, double* const* Y_cores, int64_t* Y_rks, int64_t max_bond, double truncerr, int64_t sweeps,
                            int a_cplx, int x_cplx) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    int rc = auto_init(); if (rc) return rc;
-    if (!dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || !Y_rks || d < 1) return fail(TTN_ERR_ARG, "bad argument");
-    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    TmpTTO A; TmpTT x, y;
-    if ((rc = a_cplx ? ttn_tto_create_c64(d, dims, A_rks, A_cores, &A.h) : ttn_tto_create(d, dims, A_rks, A_cores, &A.h))) return rc;
-    if ((rc = up_tt(x, d, dims, X_rks, X_cores, X_rks, nullptr, x_cplx))) return rc;
-    std::vector<int64_t> yr(d + 1), need, fin;
-    for (int64_t m = 0; m <= d; ++m) yr[m] = A_rks[m] * X_rks[m];
-    long long pm, qm;
-    rank_bounds((int)d, dims, yr.data(), max_bond, sweeps, 0, need, fin, pm, qm);
-    for (int64_t m = 0; m <= d; ++m) need[m] = std::max<int64_t>(need[m], yr[m]);
-    if ((rc = ttn_tt_create_c64(d, dims, need.data(), 1, &y.h))) return rc;
-    if ((rc = ttn_apply_compress(A.h, x.h, y.h, max_bond, truncerr, sweeps))) return rc;
-    if ((rc = ttn_compress_status(y.h, nullptr))) return rc;
-    if ((rc = ttn_tt_ranks(y.h, 0, Y_rks, nullptr))) return rc;
-    return ttn_tt_download(y.h, 0, Y_cores);
+    return apply_compress_host(d, dims, A_cores, A_rks, X_cores, X_rks, Y_cores, Y_rks, max_bond, truncerr, sweeps, a_cplx ? 2 : 1, x_cplx ? 2 : 1, 2);
 }
 
 // ---- als_eigsolve / als_gen_eigsolv (csrc/ttn_als_eig_kernels.h) ---------------------------------------------------------------
@@ -2982,7 +2923,7 @@ static int als_eig_impl(int gen, ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t
     Rg.status = x->d_status;
     Rg.hist_E = g_hist_E.as<double>(); Rg.hist_len = (int)hist_len;
     Rg.it_count = g_lz_iters.as<int>(); Rg.it_res = g_lz_res.as<double>();
-    TmpTT tmp;
+    OwnedTT tmp;
     if (n_stages > 1 && (rc = ttn_tt_create(d, x->dims.data(), x->cap.data(), batch, &tmp.h))) return rc;
     int64_t hoff = 0;
     for (int64_t j = 0; j < n_stages; ++j) {
@@ -3046,55 +2987,7 @@ int ttn_als_gen_eigsolve(ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int6
 }
 
 // ---- TT operator algebra (csrc/ttn_opalg_kernels.h) ----------------------------------------------------------------------------
-// A ttn_tto is immutable and its ranks are host-known, so every operation allocates its result.  tto_alloc: the handle and its
-// tables, cores uninitialised; an allocation the device cannot satisfy is TTN_ERR_CAPACITY (nothing is launched).
-namespace {
-struct NewTTO {                       // frees the handle unless release() hands it to the caller
-    ttn_tto_t h = nullptr;
-    ~NewTTO() { if (h) ttn_tto_free(h); }
-    ttn_tto_t release() { ttn_tto_t t = h; h = nullptr; return t; }
-};
-int tto_alloc(const char* who, int64_t d, const int64_t* dims, const int64_t* rks, const int64_t* ot, NewTTO& out) {
-    for (int64_t k = 0; k < d; ++k)
-        if (stream_fibres_too_many((long long)rks[k] * rks[k + 1]))
-            return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": 2^31 or more fibres in one output core (32-bit element indices)").c_str());
-    ttn_tto_s* h = new ttn_tto_s();
-    out.h = h;
-    h->d = (int)d;
-    h->dims.assign(dims, dims + d);
-    h->rks.assign(rks, rks + d + 1);
-    h->ot.assign(d, 0);
-    if (ot) h->ot.assign(ot, ot + d);
-    h->off.resize(d + 1);
-    long long o = 0;
-    for (int64_t k = 0; k < d; ++k) {
-        h->off[k] = o;
-        const long long sz = (long long)dims[k] * dims[k] * rks[k] * rks[k + 1];
-        o += (sz + 1) & ~1LL;
-    }
-    h->off[d] = o;
-    std::vector<int> idims(2 * d);
-    for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(dims[k] * dims[k]); }
-    std::vector<long long> r64(rks, rks + d + 1);
-    if (hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_data = nullptr;
-        return fail(TTN_ERR_CAPACITY, (std::string(who) + ": the result does not fit in device memory").c_str());
-    }
-    hipError_t e;
-    if ((e = hipMalloc((void**)&h->d_off, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * d)) != hipSuccess)
-        return hipfail(e, "hipMalloc(ttn_tto)");
-    h->d_dims2 = h->d_dims + d;
-    HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * d, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));          // the tables above are locals
-    return TTN_OK;
-}
-}  // namespace
-
+// Every operation allocates its result with tto_alloc (an operator handle is immutable).
 int ttn_tto_set_ot(ttn_tto_t A, const int64_t* ot) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!A || !ot) return fail(TTN_ERR_ARG, "null pointer");
@@ -3135,8 +3028,8 @@ int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     const int d = A->d;
     std::vector<int64_t> rks(d + 1);
     for (int m = 0; m <= d; ++m) rks[m] = A->rks[m] * B->rks[m];
-    NewTTO Y;
-    int rc = tto_alloc("ttn_tto_mul", d, A->dims.data(), rks.data(), nullptr, Y);
+    OwnedTTO Y;
+    int rc = tto_alloc("ttn_tto_mul", 1, d, A->dims.data(), rks.data(), nullptr, nullptr, Y);
     if (rc) return rc;
     // LDS: the largest binary-site A core that fits; grid: rows x column groups on binary sites, fibres elsewhere
     long long lds_a = 0, items = 1;
@@ -3174,8 +3067,8 @@ int ttn_tto_inner(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
         if (dims[k] > 46340) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_inner: physical dimension above 46340");
         items = std::max<long long>(items, std::min<long long>((long long)dims[k] * dims[k] * std::min<long long>(rks[k] * rks[k + 1], 1LL << 31), 1LL << 40));
     }
-    NewTTO Y;
-    int rc = tto_alloc("ttn_tto_inner", d, dims.data(), rks.data(), nullptr, Y);
+    OwnedTTO Y;
+    int rc = tto_alloc("ttn_tto_inner", 1, d, dims.data(), rks.data(), nullptr, nullptr, Y);
     if (rc) return rc;
     hipLaunchKernelGGL(k_tto_inner, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, A->dev(), B->dev(), Y.h->d_data, (const long long*)Y.h->d_off);
     HIPCHK(hipGetLastError());
@@ -3194,13 +3087,10 @@ int ttn_tto_add(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_add: the reference's + is only defined for d >= 2");
     std::vector<int64_t> rks(d + 1);
     for (int m = 0; m <= d; ++m) rks[m] = (m == 0 || m == d) ? 1 : A->rks[m] + B->rks[m];
-    NewTTO Z;
-    int rc = tto_alloc("ttn_tto_add", d, A->dims.data(), rks.data(), nullptr, Z);
+    OwnedTTO Z;
+    int rc = tto_alloc("ttn_tto_add", 1, d, A->dims.data(), rks.data(), nullptr, nullptr, Z);
     if (rc) return rc;
-    long long maxpq = 0;
-    bool qtt = true;                                   // k_add's n = 2 mapping is for vector dims 2: an operator has n^2 >= 4 unless n = 1
-    for (int k = 0; k < d; ++k) { maxpq = std::max<long long>(maxpq, (long long)rks[k] * rks[k + 1]); qtt = qtt && A->dims[k] * A->dims[k] == 2; }
-    hipLaunchKernelGGL(k_add, stream_grid(qtt ? (maxpq + TTN_ADD_K - 1) / TTN_ADD_K : maxpq, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, A->vdev(), B->vdev(), Z.h->vdev());
+    launch_add(A->vdev(), B->vdev(), Z.h->vdev(), rks, false, 1);     // k_add's n = 2 mapping is for vector dims 2: the n^2 of an operator is never 2
     HIPCHK(hipGetLastError());
     *out = Z.release();
     return TTN_OK;
@@ -3215,14 +3105,15 @@ int ttn_tto_scale(double a, ttn_tto_t A, ttn_tto_t* out) {
     const int d = A->d;
     std::vector<int64_t> ot(A->ot);
     if (a == 0.0) std::fill(ot.begin(), ot.end(), 0);       // zeros_tto(dims, rks)
-    NewTTO Y;
-    int rc = tto_alloc("ttn_tto_scale", d, A->dims.data(), A->rks.data(), ot.data(), Y);
+    OwnedTTO Y;
+    int rc = tto_alloc("ttn_tto_scale", 1, d, A->dims.data(), A->rks.data(), ot.data(), nullptr, Y);
     if (rc) return rc;
     int which = 0;
-    for (int k = 0; k < d; ++k) if (A->ot[k] == 0) { which = k; break; }
-    long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]);
-    hipLaunchKernelGGL(k_scale, stream_grid((maxsz + 7) / 8, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, A->vdev(), Y.h->vdev(), a, which, a == 0.0 ? 1 : 0, (const int*)nullptr);
+    const int* which_b = nullptr;                           // one train: stays null
+    if ((rc = scaled_core(A->ot.data(), d, 1, which, which_b))) return rc;
+    std::vector<int64_t> dims2(d);
+    for (int k = 0; k < d; ++k) dims2[k] = A->dims[k] * A->dims[k];
+    launch_scale(1, d, 1, dims2.data(), A->rks.data(), A->vdev(), Y.h->vdev(), a, 0.0, nullptr, which, which_b, a == 0.0);
     HIPCHK(hipGetLastError());
     *out = Y.release();
     return TTN_OK;
@@ -3240,8 +3131,8 @@ int ttn_tto_kron(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     dims.insert(dims.end(), B->dims.begin(), B->dims.end());
     rks.insert(rks.end(), B->rks.begin(), B->rks.end());
     ot.insert(ot.end(), B->ot.begin(), B->ot.end());
-    NewTTO Y;
-    int rc = tto_alloc("ttn_tto_kron", d, dims.data(), rks.data(), ot.data(), Y);
+    OwnedTTO Y;
+    int rc = tto_alloc("ttn_tto_kron", 1, d, dims.data(), rks.data(), ot.data(), nullptr, Y);
     if (rc) return rc;
     // the slot offsets of a handle are running sums of its 16-byte rounded core sizes: the arena of A, then the arena of B
     if (A->off[A->d]) HIPCHK(hipMemcpyAsync(Y.h->d_data, A->d_data, sizeof(double) * (size_t)A->off[A->d], hipMemcpyDeviceToDevice, g_stream));
@@ -3271,8 +3162,8 @@ int ttn_tt_outer(ttn_tt_t x, ttn_tt_t y, int64_t b, ttn_tto_t* out) {
     long long items = 1;
     for (int m = 0; m <= d; ++m) rks[m] = xr[m] * yr[m];
     for (int k = 0; k < d; ++k) items = std::max<long long>(items, std::min<long long>((long long)x->dims[k] * x->dims[k] * std::min<long long>(rks[k] * rks[k + 1], 1LL << 31), 1LL << 40));
-    NewTTO Y;
-    if ((rc = tto_alloc("ttn_tt_outer", d, x->dims.data(), rks.data(), nullptr, Y))) return rc;
+    OwnedTTO Y;
+    if ((rc = tto_alloc("ttn_tt_outer", 1, d, x->dims.data(), rks.data(), nullptr, nullptr, Y))) return rc;
     hipLaunchKernelGGL(k_tt_outer, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), (int)b, Y.h->d_data, (const long long*)Y.h->d_off);
     HIPCHK(hipGetLastError());
     *out = Y.release();
@@ -3292,8 +3183,8 @@ int ttn_tt_diag_tto(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
     if ((rc = train_ranks(x, b, rks))) return rc;
     long long items = 1;
     for (int k = 0; k < d; ++k) items = std::max<long long>(items, std::min<long long>((long long)x->dims[k] * x->dims[k] * std::min<long long>(rks[k] * rks[k + 1], 1LL << 31), 1LL << 40));
-    NewTTO Y;
-    if ((rc = tto_alloc("ttn_tt_diag_tto", d, x->dims.data(), rks.data(), nullptr, Y))) return rc;
+    OwnedTTO Y;
+    if ((rc = tto_alloc("ttn_tt_diag_tto", 1, d, x->dims.data(), rks.data(), nullptr, nullptr, Y))) return rc;
     hipLaunchKernelGGL(k_tt_diag, stream_grid(items, d, 1), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), (int)b, Y.h->d_data, (const long long*)Y.h->d_off);
     HIPCHK(hipGetLastError());
     *out = Y.release();
@@ -3368,8 +3259,8 @@ int ttn_tto_from_tt(ttn_tt_t x, int64_t b, ttn_tto_t* out) {
     }
     int rc;
     if ((rc = train_ranks(x, b, rks))) return rc;
-    NewTTO Y;
-    if ((rc = tto_alloc("ttn_tto_from_tt", d, dims.data(), rks.data(), x->ot.data() + (size_t)b * d, Y))) return rc;
+    OwnedTTO Y;
+    if ((rc = tto_alloc("ttn_tto_from_tt", 1, d, dims.data(), rks.data(), x->ot.data() + (size_t)b * d, nullptr, Y))) return rc;
     for (int k = 0; k < d; ++k) {
         const size_t sz = (size_t)x->dims[k] * rks[k] * rks[k + 1];
         HIPCHK(hipMemcpyAsync(Y.h->d_data + Y.h->off[k], x->d_data + (size_t)b * x->stride + x->off[k], sizeof(double) * sz, hipMemcpyDeviceToDevice, g_stream));
@@ -3393,7 +3284,7 @@ int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t swe
     for (int k = 0; k < d; ++k) dims2[k] = A->dims[k] * A->dims[k];
     long long pm, qm;
     rank_bounds(d, dims2.data(), A->rks.data(), max_bond, sweeps, 0, need, fin, pm, qm);
-    TmpTT t;
+    OwnedTT t;
     int rc;
     if ((rc = ttn_tt_create(d, dims2.data(), need.data(), 1, &t.h))) return rc;
     if ((rc = ttn_tto_to_tt(A, t.h))) return rc;

@@ -56,6 +56,20 @@ def _is_cplx(*cores_lists) -> bool:
     return any(np.iscomplexobj(c) for cores in cores_lists for c in cores)
 
 
+def _conv(cores, cplx: bool) -> List[np.ndarray]:
+    """The cores of one operand as the entry points read them: ComplexF64 or Float64."""
+    return [(_z if cplx else _f)(c) for c in cores]
+
+
+def _entry(name: str, cplx: bool, c64_name: str = None):
+    """What differs between the two element types of a stateless call: the symbol (``ttn_<name>_c64`` / ``ttn_<name>_f64``) and the
+    dtype of its result buffers."""
+    L = _lib.lib()
+    if cplx:
+        return getattr(L, c64_name or "ttn_%s_c64" % name), np.complex128
+    return getattr(L, "ttn_%s_f64" % name), np.float64
+
+
 def _ptrs(arrs: Sequence[np.ndarray]):
     return (C.POINTER(C.c_double) * len(arrs))(*[a.ctypes.data_as(C.POINTER(C.c_double)) for a in arrs])
 
@@ -144,72 +158,52 @@ def r_and_d_to_rks(rks: Sequence[int], dims: Sequence[int], rmax: int = 1024) ->
 
 
 def apply(A: TToperator, v: TTvector) -> TTvector:
-    """*(A::TToperator, v::TTvector) — src/tt_operations.jl:101-111."""
+    """*(A::TToperator, v::TTvector) — src/tt_operations.jl:101-111.  Complex x complex and the two mixed forms: the real side stays
+    real on the device, the result is complex."""
     assert tuple(A.tto_dims) == tuple(v.ttv_dims), "Incompatible dimensions"
     d = v.N
     yr = [a * b for a, b in zip(A.tto_rks, v.ttv_rks)]
     ca, cx = _is_cplx(A.tto_vec), _is_cplx(v.ttv_vec)
-    if ca or cx:          # complex x complex and the two mixed forms: the real side stays real on the device, the result is complex
-        Y = _empty_cores(v.ttv_dims, yr, np.complex128)
-        Ac = [(_z if ca else _f)(c) for c in A.tto_vec]
-        Xc = [(_z if cx else _f)(c) for c in v.ttv_vec]
-        _lib.check(_lib.lib().ttn_apply_c64(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(Y), int(ca), int(cx)))
-        return TTvector(d, Y, v.ttv_dims, yr, [0] * d)
-    Y = _empty_cores(v.ttv_dims, yr)
-    Ac = [_f(c) for c in A.tto_vec]
-    Xc = [_f(c) for c in v.ttv_vec]
-    _lib.check(_lib.lib().ttn_apply_f64(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(Y)))
+    fn, dtype = _entry("apply", ca or cx)
+    Y = _empty_cores(v.ttv_dims, yr, dtype)
+    Ac, Xc = _conv(A.tto_vec, ca), _conv(v.ttv_vec, cx)
+    flags = (int(ca), int(cx)) if ca or cx else ()
+    _lib.check(fn(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(Y), *flags))
     return TTvector(d, Y, v.ttv_dims, yr, [0] * d)
 
 
 def apply_compress(A: TToperator, v: TTvector, max_bond: int, truncerr: float = 0.0, sweeps: int = 1) -> TTvector:
     """tt_compress!(A * v, max_bond; truncerr, sweeps) — the operator krylov_linsolve and the time steppers iterate
     (src/solvers/euler.jl:55) — as ONE stateless call (ttn_apply_compress_f64): A * v is never materialised, neither in HBM nor over
-    PCIe.  Same result as tt_compress_(apply(A, v), max_bond)."""
+    PCIe.  Same result as tt_compress_(apply(A, v), max_bond).  ComplexF64: apply, then round, on the device (no fused complex merge)."""
     assert tuple(A.tto_dims) == tuple(v.ttv_dims), "Incompatible dimensions"
     assert sweeps >= 1, "sweeps must be >= 1"
     d = v.N
     max_bond = int(min(max_bond, 2 ** 62))
-    L = _lib.lib()
     cap = (C.c_int64 * (d + 1))()
-    _lib.check(L.ttn_apply_compress_rank_bound(d, _i64(v.ttv_dims), _i64(A.tto_rks), _i64(v.ttv_rks), max_bond, int(sweeps), cap))
+    _lib.check(_lib.lib().ttn_apply_compress_rank_bound(d, _i64(v.ttv_dims), _i64(A.tto_rks), _i64(v.ttv_rks), max_bond, int(sweeps), cap))
     ca, cx = _is_cplx(A.tto_vec), _is_cplx(v.ttv_vec)
-    if ca or cx:          # ComplexF64: apply, then round, on the device (no fused complex merge)
-        need = [max(int(c), a * b) for c, a, b in zip(cap, A.tto_rks, v.ttv_rks)]
-        bufs = [np.zeros(v.ttv_dims[j] * need[j] * need[j + 1], dtype=np.complex128) for j in range(d)]
-        rks = (C.c_int64 * (d + 1))()
-        Ac = [(_z if ca else _f)(c) for c in A.tto_vec]
-        Xc = [(_z if cx else _f)(c) for c in v.ttv_vec]
-        _lib.check(L.ttn_apply_compress_c64(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(bufs), rks,
-                                            max_bond, float(truncerr), int(sweeps), int(ca), int(cx)))
-        rk = [int(r) for r in rks]
-        return TTvector(d, _rewrap(bufs, v.ttv_dims, rk), v.ttv_dims, rk, [0] * d)
-    bufs = [np.zeros(v.ttv_dims[j] * int(cap[j]) * int(cap[j + 1])) for j in range(d)]
+    fn, dtype = _entry("apply_compress", ca or cx)
+    bufs = [np.zeros(v.ttv_dims[j] * int(cap[j]) * int(cap[j + 1]), dtype=dtype) for j in range(d)]
     rks = (C.c_int64 * (d + 1))()
-    Ac = [_f(c) for c in A.tto_vec]
-    Xc = [_f(c) for c in v.ttv_vec]
-    _lib.check(L.ttn_apply_compress_f64(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(bufs), rks,
-                                        max_bond, float(truncerr), int(sweeps)))
+    Ac, Xc = _conv(A.tto_vec, ca), _conv(v.ttv_vec, cx)
+    flags = (int(ca), int(cx)) if ca or cx else ()
+    _lib.check(fn(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(bufs), rks,
+                  max_bond, float(truncerr), int(sweeps), *flags))
     rk = [int(r) for r in rks]
-    cores = [np.reshape(bufs[j][: v.ttv_dims[j] * rk[j] * rk[j + 1]], (v.ttv_dims[j], rk[j], rk[j + 1]), order="F").copy(order="F") for j in range(d)]
-    return TTvector(d, cores, v.ttv_dims, rk, [0] * d)
+    return TTvector(d, _rewrap(bufs, v.ttv_dims, rk), v.ttv_dims, rk, [0] * d)
 
 
 def dot(A: TTvector, B: TTvector):
     """dot(A, B) — src/tt_operations.jl:239-250.  With a complex argument the FIRST one is conjugated (:243-248) and the result is a
     ``complex``; a real argument next to a complex one is promoted on the host."""
     assert tuple(A.ttv_dims) == tuple(B.ttv_dims), "TT dimensions are not compatible"
-    if _is_cplx(A.ttv_vec, B.ttv_vec):
-        out2 = (C.c_double * 2)()
-        Ac = [_z(c) for c in A.ttv_vec]
-        Bc = [_z(c) for c in B.ttv_vec]
-        _lib.check(_lib.lib().ttn_dot_c64(A.N, _i64(A.ttv_dims), _ptrs(Ac), _i64(A.ttv_rks), _ptrs(Bc), _i64(B.ttv_rks), out2))
-        return complex(out2[0], out2[1])
-    out = C.c_double(0.0)
-    Ac = [_f(c) for c in A.ttv_vec]
-    Bc = [_f(c) for c in B.ttv_vec]
-    _lib.check(_lib.lib().ttn_dot_f64(A.N, _i64(A.ttv_dims), _ptrs(Ac), _i64(A.ttv_rks), _ptrs(Bc), _i64(B.ttv_rks), C.byref(out)))
-    return float(out.value)
+    cplx = _is_cplx(A.ttv_vec, B.ttv_vec)
+    fn, _ = _entry("dot", cplx)
+    out = (C.c_double * 2)()
+    Ac, Bc = _conv(A.ttv_vec, cplx), _conv(B.ttv_vec, cplx)
+    _lib.check(fn(A.N, _i64(A.ttv_dims), _ptrs(Ac), _i64(A.ttv_rks), _ptrs(Bc), _i64(B.ttv_rks), out))
+    return complex(out[0], out[1]) if cplx else float(out[0])
 
 
 def norm(a: TTvector) -> float:
@@ -225,42 +219,30 @@ def euclidean_distance(a: TTvector, b: TTvector) -> float:
     return math.sqrt(max((dot(a, a) - 2 * dot(b, a).real + dot(b, b)).real, 0.0))
 
 
-def hadamard(x: TTvector, y: TTvector) -> TTvector:
-    """hadamard(x, y) / ⊕ — src/tt_operations.jl:343-363."""
-    assert tuple(x.ttv_dims) == tuple(y.ttv_dims), "Incompatible TT dimensions"
+def _binary(name: str, x: TTvector, y: TTvector, zr: List[int]) -> TTvector:
+    """z = x (op) y with result ranks zr through ttn_<name>_f64 / _c64; a real operand next to a complex one is promoted on the host."""
     d = x.N
-    zr = [a * b for a, b in zip(x.ttv_rks, y.ttv_rks)]
-    if _is_cplx(x.ttv_vec, y.ttv_vec):          # no conjugation (:343-361); a real factor is promoted on the host
-        Z = _empty_cores(x.ttv_dims, zr, np.complex128)
-        Xc = [_z(c) for c in x.ttv_vec]
-        Yc = [_z(c) for c in y.ttv_vec]
-        _lib.check(_lib.lib().ttn_hadamard_c64(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
-        return TTvector(d, Z, x.ttv_dims, zr, [0] * d)
-    Z = _empty_cores(x.ttv_dims, zr)
-    Xc = [_f(c) for c in x.ttv_vec]
-    Yc = [_f(c) for c in y.ttv_vec]
-    _lib.check(_lib.lib().ttn_hadamard_f64(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
+    cplx = _is_cplx(x.ttv_vec, y.ttv_vec)
+    fn, dtype = _entry(name, cplx)
+    Z = _empty_cores(x.ttv_dims, zr, dtype)
+    Xc, Yc = _conv(x.ttv_vec, cplx), _conv(y.ttv_vec, cplx)
+    _lib.check(fn(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
     return TTvector(d, Z, x.ttv_dims, zr, [0] * d)
+
+
+def hadamard(x: TTvector, y: TTvector) -> TTvector:
+    """hadamard(x, y) / ⊕ — src/tt_operations.jl:343-363 (no conjugation, :343-361)."""
+    assert tuple(x.ttv_dims) == tuple(y.ttv_dims), "Incompatible TT dimensions"
+    return _binary("hadamard", x, y, [a * b for a, b in zip(x.ttv_rks, y.ttv_rks)])
 
 
 def add(x: TTvector, y: TTvector) -> TTvector:
     """+(x, y) — src/tt_operations.jl:10-35."""
     assert tuple(x.ttv_dims) == tuple(y.ttv_dims), "Incompatible dimensions"
-    d = x.N
     zr = [a + b for a, b in zip(x.ttv_rks, y.ttv_rks)]
     zr[0] = 1
-    zr[d] = 1
-    if _is_cplx(x.ttv_vec, y.ttv_vec):          # a real summand is promoted on the host
-        Z = _empty_cores(x.ttv_dims, zr, np.complex128)
-        Xc = [_z(c) for c in x.ttv_vec]
-        Yc = [_z(c) for c in y.ttv_vec]
-        _lib.check(_lib.lib().ttn_add_c64(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
-        return TTvector(d, Z, x.ttv_dims, zr, [0] * d)
-    Z = _empty_cores(x.ttv_dims, zr)
-    Xc = [_f(c) for c in x.ttv_vec]
-    Yc = [_f(c) for c in y.ttv_vec]
-    _lib.check(_lib.lib().ttn_add_f64(d, _i64(x.ttv_dims), _ptrs(Xc), _i64(x.ttv_rks), _ptrs(Yc), _i64(y.ttv_rks), _ptrs(Z)))
-    return TTvector(d, Z, x.ttv_dims, zr, [0] * d)
+    zr[x.N] = 1
+    return _binary("add", x, y, zr)
 
 
 def add_(x: TTvector, y: TTvector) -> TTvector:
@@ -273,17 +255,13 @@ def add_(x: TTvector, y: TTvector) -> TTvector:
 def scale(a: float, A: TTvector) -> TTvector:
     """*(a::Number, A::TTvector) — src/tt_operations.jl:256-266."""
     d = A.N
-    if _is_cplx(A.ttv_vec) or isinstance(a, (complex, np.complexfloating)):
-        a = complex(a)
-        Y = _empty_cores(A.ttv_dims, A.ttv_rks, np.complex128)
-        Xc = [_z(c) for c in A.ttv_vec]
-        yot = (C.c_int64 * d)()
-        _lib.check(_lib.lib().ttn_scale_host_c64(d, _i64(A.ttv_dims), a.real, a.imag, _ptrs(Xc), _i64(A.ttv_rks), _i64(A.ttv_ot), _ptrs(Y), yot))
-        return TTvector(d, Y, A.ttv_dims, list(A.ttv_rks), [int(v) for v in yot])
-    Y = _empty_cores(A.ttv_dims, A.ttv_rks)
-    Xc = [_f(c) for c in A.ttv_vec]
+    cplx = _is_cplx(A.ttv_vec) or isinstance(a, (complex, np.complexfloating))
+    fn, dtype = _entry("scale", cplx, "ttn_scale_host_c64")
+    factor = (complex(a).real, complex(a).imag) if cplx else (float(a),)
+    Y = _empty_cores(A.ttv_dims, A.ttv_rks, dtype)
+    Xc = _conv(A.ttv_vec, cplx)
     yot = (C.c_int64 * d)()
-    _lib.check(_lib.lib().ttn_scale_f64(d, _i64(A.ttv_dims), float(a), _ptrs(Xc), _i64(A.ttv_rks), _i64(A.ttv_ot), _ptrs(Y), yot))
+    _lib.check(fn(d, _i64(A.ttv_dims), *factor, _ptrs(Xc), _i64(A.ttv_rks), _i64(A.ttv_ot), _ptrs(Y), yot))
     return TTvector(d, Y, A.ttv_dims, list(A.ttv_rks), [int(v) for v in yot])
 
 
@@ -370,20 +348,15 @@ def _compress_call(psi: TTvector, k: int, max_bond: int, truncerr: float, sweeps
     need = (C.c_int64 * (d + 1))()
     _lib.check(L.ttn_compress_rank_bound(d, _i64(psi.ttv_dims), _i64(psi.ttv_rks), max_bond, int(sweeps), int(k), need, None))
     cplx = _is_cplx(psi.ttv_vec)
+    fn, dtype = _entry("bond_truncate" if k > 0 else "compress", cplx)
     bufs = []
     for j in range(d):
-        buf = np.zeros(psi.ttv_dims[j] * int(need[j]) * int(need[j + 1]), dtype=np.complex128 if cplx else np.float64)
+        buf = np.zeros(psi.ttv_dims[j] * int(need[j]) * int(need[j + 1]), dtype=dtype)
         buf[: psi.ttv_vec[j].size] = (_z if cplx else _f)(psi.ttv_vec[j]).reshape(-1, order="F")
         bufs.append(buf)
     rks = _i64(psi.ttv_rks)
-    if cplx and k > 0:
-        rc = L.ttn_bond_truncate_c64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, int(k), max_bond, float(truncerr))
-    elif cplx:
-        rc = L.ttn_compress_c64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, max_bond, float(truncerr), int(sweeps))
-    elif k > 0:
-        rc = L.ttn_bond_truncate_f64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, int(k), max_bond, float(truncerr))
-    else:
-        rc = L.ttn_compress_f64(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, max_bond, float(truncerr), int(sweeps))
+    tail = (int(k), max_bond, float(truncerr)) if k > 0 else (max_bond, float(truncerr), int(sweeps))
+    rc = fn(d, _i64(psi.ttv_dims), _ptrs(bufs), rks, *tail)
     _lib.check(rc)
     new_rks = [int(v) for v in rks]
     cores = _rewrap(bufs, psi.ttv_dims, new_rks)

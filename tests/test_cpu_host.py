@@ -202,6 +202,19 @@ def test_c_abi_argument_errors_without_gpu(T):
     out = (ctypes.c_int64 * 3)()
     assert L.ttn_r_and_d_to_rks(2, None, 3, None, 4, out) == T._lib.TTN_ERR_ARG
     assert b"bad argument" in L.ttn_last_error_string()
+    # the Float64 / ComplexF64 twins of a stateless call refuse alike, before anything needs a device or reads a pointer
+    d = 3
+
+    def refusal(fn, *args):
+        return fn(d, None, None, None, *args), L.ttn_last_error_string()
+
+    got = refusal(L.ttn_compress_f64, 4, 0.0, 0)                        # sweeps = 0
+    assert got == (T._lib.TTN_ERR_SWEEPS, b"sweeps must be >= 1")
+    assert refusal(L.ttn_compress_c64, 4, 0.0, 0) == got
+    for k in (0, d):
+        got = refusal(L.ttn_bond_truncate_f64, k, 4, 0.0)
+        assert got == (T._lib.TTN_ERR_BOND_INDEX, b"k must be in 1:(N-1)")
+        assert refusal(L.ttn_bond_truncate_c64, k, 4, 0.0) == got
 
 
 def test_tdvp_drivers_and_dense_kernels_fail_loudly_without_gpu(T):
