@@ -374,6 +374,37 @@ int ttn_last_launch_ms(float* ms);
 /* out[b] = norm(a_b) = sqrt(max(dot(a,a),0))   src/tt_operations.jl:465-470 */
 int ttn_norm(ttn_tt_t a, double* out);
 
+/* ---- core gradients (csrc/ttn_grad_kernels.h): the two reverse-mode rules of the reference's ChainRulesCore extension
+ * (ext/TensorTrainNumericsChainRulesCoreExt) and the core-wise linear algebra of their tangents.  Float64 only.  A TANGENT (Abar, Bbar,
+ * xbar, a gradient, a search direction) lives in an ordinary ttn_tt handle used as a bag of cores with the primal's current ranks per
+ * train; its `ot` flags are 0 and it is never contracted as a train.
+ *   ttn_dot_pullback    the rrule of dot(A, B) (ChainRulesCoreExt.jl:36-65): with the environments L_1 = [1], L_{k+1}[a,b] = sum A_k[z,al,a]
+ *                       B_k[z,be,b] L_k[al,be] and G_{N+1} = [1], G_k[al,be] = sum A_k[z,al,a] B_k[z,be,b] G_{k+1}[a,b] (:8-34),
+ *                       Abar_k[z,al,a] = Delta_b sum L_k[al,be] B_k[z,be,b] G_{k+1}[a,b] and Bbar_k with A and B exchanged.  delta: HOST,
+ *                       `batch` doubles, NULL = 1.  abar / bbar may each be NULL, not both; abar receives a's current ranks (copied on
+ *                       the device), bbar b's.  out: HOST or NULL; non-NULL: receives dot(a_b, b_b) = L_{N+1}[1,1] and the call
+ *                       synchronises like ttn_dot; NULL (and delta NULL: a non-NULL delta is copied from caller memory first, which
+ *                       waits for the stream) the call is asynchronous.  a and b may be the same handle; their ranks are independent.
+ *                       Each environment is computed once per call (O(N) chain steps) and stays in library workspace:
+ *                       2 (N + 1) W + 2 n_max rA_max rB_max doubles per train, W = max_m rA_m rB_m over the host-side rank bounds; a
+ *                       workspace that cannot be allocated returns the allocator's error before any launch.
+ *   ttn_apply_pullback  the rrule of H * psi with respect to psi (:67-88): xbar_k[j,vl,vr] = sum H_k[i,j,al,ar] ybar_k[i, al + R_{k-1} vl,
+ *                       ar + R_k vr] (the operator index fastest in the merged rank, as ttn_apply writes it).  x is the primal: it gives
+ *                       xbar its ranks, its cores are not read.  ybar must hold, per train, the ranks R .* (ranks of x).  Asynchronous.
+ *   ttn_tt_cores_axpby  y_k <- alpha_b x_k + beta_b y_k on every core; alpha, beta: HOST, `batch` doubles each, NULL = 1 (a non-NULL one
+ *                       is copied first, which waits for the stream; otherwise asynchronous).  x may be y.  Needs equal current ranks.
+ *   ttn_tt_cores_dot    out[b] = sum_k <x_k, y_k>, the Frobenius pairing of two tangents (test_ad.jl: ladot); out: HOST; synchronises;
+ *                       summed in a fixed order: a repeated call returns the same bits.
+ * Before any launch: NULL pointer, bad handle, aliased output TTN_ERR_ARG; dims or batch differ TTN_ERR_DIMS; destination capacity below
+ * the source's host-side rank bounds TTN_ERR_CAPACITY; a ComplexF64 handle or a train of 2^31 doubles or more TTN_ERR_UNSUPPORTED with a
+ * message naming the call.  Ranks are device-resident, so the kernels check each train's own ranks themselves (ybar against R .* x; x
+ * against y): a mismatch records a per-train code on the DESTINATION that ttn_compress_status reports as TTN_ERR_DIMS, that train's
+ * destination cores are not written (ttn_tt_cores_dot: out[b] = NaN), every other train is computed.  Operands are only read. */
+int ttn_dot_pullback(ttn_tt_t a, ttn_tt_t b, const double* delta, ttn_tt_t abar, ttn_tt_t bbar, double* out);
+int ttn_apply_pullback(ttn_tto_t A, ttn_tt_t x, ttn_tt_t ybar, ttn_tt_t xbar);
+int ttn_tt_cores_axpby(const double* alpha, ttn_tt_t x, const double* beta, ttn_tt_t y);
+int ttn_tt_cores_dot(ttn_tt_t x, ttn_tt_t y, double* out);
+
 /* z = hadamard(x, y)   src/tt_operations.jl:343-361 */
 int ttn_hadamard(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z);
 /* z = x + y            src/tt_operations.jl:10-35 (also the body of add!, :37-66) */

@@ -1,16 +1,17 @@
 """MI355X-native TT/QTT core-arithmetic backend for TensorTrainNumerics.jl's hot path.
 
 Host-side mirror of the reference interface (tt.py), input generators (constructors.py),
-device-resident batched handles (device.py), TT operator algebra (opalg.py), the multi-dimensional QTT layer (qttnd.py) and the ctypes binding of the C ABI (_lib.py).
+device-resident batched handles (device.py), core gradients (grad.py), TT operator algebra (opalg.py), the multi-dimensional QTT layer (qttnd.py) and the ctypes binding of the C ABI (_lib.py).
 The arithmetic lives in csrc/*.h, csrc/ttn_api.hip -> libttn_hip.so (hand-written HIP, gfx950).
 """
-from . import _lib, constructors, cross, device, opalg, pipeline, qtt, qttnd, shard, solvers, tdvp, tt
+from . import _lib, constructors, cross, device, grad, opalg, pipeline, qtt, qttnd, shard, solvers, tdvp, tt
 from ._lib import TTNError, build, ensure_init, finalize
 from .constructors import (Delta, Delta_DN, Delta_ND, Delta_NN, Nabla, fourier_qtto, function_to_qtt_uniform, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn,
                            qtt_cos, qtt_exp, qtt_polynom, qtt_sin, qtt_to_vector, rand_tt, reverse_qtt_bits, shift, toeplitz_to_qtto,
                            xxx_tto, xxz_tto, zeros_tt, zeros_tto)
 from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_integrate
 from .device import DeviceTT, DeviceTTO, StreamTimer
+from .grad import apply_pullback, apply_rrule, cores_axpby, cores_dot, dot_pullback, dot_rrule, rayleigh_gradient, rayleigh_value_and_grad
 from .opalg import (concatenate, kron, outer_product, tto_add, tto_compress_, tto_inner, tto_mul, tto_scale, tto_sub, tto_to_ttv,
                     ttv_to_diag_tto, ttv_to_tto)
 from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve

@@ -19,6 +19,7 @@
 #include "ttn_opalg_kernels.h"
 #include "ttn_cplx_kernels.h"
 #include "ttn_grid_kernels.h"
+#include "ttn_grad_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -99,8 +100,9 @@ DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-sit
 DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
 DevBuf g_cross_tab;        // core table of ttn_cross_eval
 DevBuf g_cross_info;       // status words of a ttn_cross_maxvol called without a device info
+DevBuf g_grad_coef;        // [2][batch] doubles: Delta of ttn_dot_pullback, alpha and beta of ttn_tt_cores_axpby
 DevBuf* const g_bufs[] = {&g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
-                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab, &g_cross_tab, &g_cross_info};
+                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab, &g_cross_tab, &g_cross_info, &g_grad_coef};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -232,6 +234,7 @@ int ttn_init(int device) {
         {(const void*)k_orthogonalize, ORTHO_LDS_BYTES},
         {(const void*)k_ortho512, O5_LDS_BYTES(TTN_MAX_D * 8)},
         {(const void*)k_dot_fused, DOT_LDS_BYTES(DOT_MAX_D)},
+        {(const void*)k_grad_chain, DOT_LDS_BYTES(DOT_MAX_D)},
         {(const void*)k_selftest_gemm, sizeof(double) * GEMM_LDS_TOTAL},
         {(const void*)k_tdvp, TDVP_LDS_BYTES},
         {(const void*)k_lu_panel, LU_PANEL_LDS_BYTES},
@@ -1646,7 +1649,7 @@ const struct { int code, err; const char* msg; } status_table[] = {
     {TTN_ST_LANCZOS, TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol"},
     {TTN_ST_NONFINITE, TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)"},
     {TTN_ST_SINGULAR, TTN_ERR_SINGULAR, "a local system K is singular (als_linsolve), or a local metric S_s is not positive definite (als_gen_eigsolv)"},
-    {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "als_linsolve: a train's ranks differ from the ranks of the start handle"},
+    {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "a train's ranks differ from the ranks the call needs (als_linsolve: the start handle; ttn_apply_pullback: R .* x; ttn_tt_cores_axpby: x)"},
     {TTN_ST_RANK_OVERFLOW, TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)"},
     {TTN_ST_JACOBI, TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit"},
 };
@@ -2151,6 +2154,157 @@ int ttn_norm(ttn_tt_t a, double* out) {
     int rc = ttn_dot(a, a, out);
     if (rc) return rc;
     for (int b = 0; b < a->batch; ++b) { double v = out[b]; v = v < 0 ? 0.0 : v; out[b] = std::sqrt(v); }
+    return TTN_OK;
+}
+
+// ---- core gradients (csrc/ttn_grad_kernels.h) ------------------------------------------------------------------------------------
+// What the four calls check alike before anything is launched: Float64 handles of equal dims and batch, trains below 2^31 doubles.
+static int grad_common(const char* who, std::initializer_list<const ttn_tt_s*> tts) {
+    const ttn_tt_s* first = nullptr;
+    for (const ttn_tt_s* h : tts) {
+        if (!h) continue;
+        if (!first) first = h;
+        if (!same_dims(first->dims, h->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+        if (first->batch != h->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    }
+    if (any_c64(tts)) return refuse_c64(who);
+    for (const ttn_tt_s* h : tts)
+        if (h && h->stride >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": a train of 2^31 doubles or more").c_str());
+    return TTN_OK;
+}
+// dst becomes a tangent of src: src's ranks (copied on the device), its host-side bounds, gauge flags 0
+static void grad_tangent_of(ttn_tt_t dst, ttn_tt_t src) {
+    hipLaunchKernelGGL(k_ranks_copy, dim3(src->batch), dim3(64), 0, g_stream, dst->dev(), src->dev());
+    dst->bound = src->bound;
+    std::fill(dst->ot.begin(), dst->ot.end(), 0);
+}
+// `batch` host doubles into half `slot` of g_grad_coef (null: no copy, the kernel takes 1).  Synchronises: `v` is caller memory.
+static int grad_coef(const double* v, int batch, int slot, const double*& dev) {
+    dev = nullptr;
+    if (!v) return TTN_OK;
+    const int rc = g_grad_coef.ensure(sizeof(double) * 2 * (size_t)batch);
+    if (rc) return rc;
+    double* p = g_grad_coef.as<double>() + (size_t)slot * batch;
+    HIPCHK(hipMemcpyAsync(p, v, sizeof(double) * batch, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    dev = p;
+    return TTN_OK;
+}
+
+int ttn_dot_pullback(ttn_tt_t a, ttn_tt_t b, const double* delta, ttn_tt_t abar, ttn_tt_t bbar, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!a || !b) return fail(TTN_ERR_ARG, "ttn_dot_pullback: null handle");
+    if (!abar && !bbar) return fail(TTN_ERR_ARG, "ttn_dot_pullback: neither abar nor bbar is given");
+    if ((abar && (abar == a || abar == b || abar == bbar)) || (bbar && (bbar == a || bbar == b)))
+        return fail(TTN_ERR_ARG, "ttn_dot_pullback: an output must not alias an operand or the other output");
+    int rc = grad_common("ttn_dot_pullback", {a, b, abar, bbar});
+    if (rc) return rc;
+    const int d = a->d, batch = a->batch;
+    if (d > DOT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot_pullback: chains longer than 480 sites are not supported");
+    for (int m = 0; m <= d; ++m)
+        if ((abar && abar->cap[m] < a->bound[m]) || (bbar && bbar->cap[m] < b->bound[m]))
+            return fail(TTN_ERR_CAPACITY, "ttn_dot_pullback: destination capacity too small");
+    // workspace per train: both chains with every state, 2 (d + 1) W doubles, W = max_m r^A_m r^B_m, and one GEMM intermediate per chain
+    long long W = 1, ramax = 1, rbmax = 1, nmax = 1, tiles = 1;
+    for (int m = 0; m <= d; ++m) {
+        W = std::max<long long>(W, a->bound[m] * b->bound[m]);
+        ramax = std::max<long long>(ramax, a->bound[m]); rbmax = std::max<long long>(rbmax, b->bound[m]);
+    }
+    for (int k = 0; k < d; ++k) nmax = std::max<long long>(nmax, a->dims[k]);
+    W = (W + 1) & ~1LL;
+    const long long tsz = (nmax * ramax * rbmax + 1) & ~1LL;
+    for (int k = 0; k < d; ++k) {
+        if (abar) tiles = std::max<long long>(tiles, ((a->bound[k] + 15) / 16) * ((a->bound[k + 1] + 63) / 64));
+        if (bbar) tiles = std::max<long long>(tiles, ((b->bound[k] + 15) / 16) * ((b->bound[k + 1] + 63) / 64));
+    }
+    if (tiles >= (1LL << 31) || batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot_pullback: more than 2^31 output tiles in one core, or more than 65535 trains");
+    const size_t per_train = (size_t)(2 * (d + 1) * W + 2 * tsz);
+    if ((rc = g_scratch.ensure(sizeof(double) * per_train * batch))) return rc;
+    if ((rc = g_dout.ensure(sizeof(double) * batch))) return rc;
+    const double* d_delta = nullptr;
+    if ((rc = grad_coef(delta, batch, 0, d_delta))) return rc;
+    if (abar) grad_tangent_of(abar, a);
+    if (bbar) grad_tangent_of(bbar, b);
+    GradChainArgs C_;
+    C_.a = a->dev(); C_.b = b->dev();
+    C_.env = g_scratch.as<double>();
+    C_.tbuf = C_.env + (size_t)2 * (d + 1) * W * batch;
+    C_.W = W; C_.tsz = tsz;
+    C_.out = out ? g_dout.as<double>() : nullptr;
+    hipLaunchKernelGGL(k_grad_chain, dim3(batch, 2), dim3(TTN_WG), DOT_LDS_BYTES(d), g_stream, C_);
+    HIPCHK(hipGetLastError());
+    GradSandArgs S_;
+    S_.a = a->dev(); S_.b = b->dev();
+    S_.abar = abar ? abar->dev() : TTDev{}; S_.bbar = bbar ? bbar->dev() : TTDev{};
+    S_.env = C_.env; S_.W = W; S_.delta = d_delta;
+    hipLaunchKernelGGL(k_grad_sandwich, dim3((unsigned)tiles, 2 * d, batch), dim3(GRAD_SW_TB), 0, g_stream, S_);
+    HIPCHK(hipGetLastError());
+    if (out) {
+        HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+    }
+    return TTN_OK;
+}
+
+int ttn_apply_pullback(ttn_tto_t A, ttn_tt_t x, ttn_tt_t ybar, ttn_tt_t xbar) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !x || !ybar || !xbar) return fail(TTN_ERR_ARG, "ttn_apply_pullback: null handle");
+    if (xbar == x || xbar == ybar) return fail(TTN_ERR_ARG, "ttn_apply_pullback: the output must not alias an operand");
+    if (!same_dims(A->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    int rc = grad_common("ttn_apply_pullback", {x, ybar, xbar});
+    if (rc) return rc;
+    if (A->el == 2) return refuse_c64("ttn_apply_pullback");
+    const int d = x->d, batch = x->batch;
+    for (int m = 0; m <= d; ++m) if (xbar->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply_pullback: destination capacity too small");
+    for (int m = 0; m <= d; ++m) if (ybar->cap[m] < A->rks[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply_pullback: ybar cannot hold the ranks R .* x");
+    long long items = 1, amax_ = 0;
+    for (int k = 0; k < d; ++k) {
+        if (stream_fibres_too_many((long long)x->dims[k] * x->bound[k] * x->bound[k + 1]) || stream_fibres_too_many((long long)ybar->cap[k] * ybar->cap[k + 1]))
+            return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_pullback: 2^31 or more fibres in one core (32-bit element indices)");
+        items = std::max<long long>(items, x->dims[k] == 2 ? x->bound[k] * ((x->bound[k + 1] + TTN_APB_K - 1) / TTN_APB_K) : x->dims[k] * x->bound[k] * x->bound[k + 1]);
+        amax_ = std::max<long long>(amax_, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]);
+    }
+    if (batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_pullback: more than 65535 trains");
+    const int lds_a = amax_ <= TTN_APPLY_LDS_DOUBLES ? (int)amax_ : 0;
+    grad_tangent_of(xbar, x);
+    hipLaunchKernelGGL(k_apply_pullback, stream_grid(items, d, batch), dim3(TTN_STREAM_TB), sizeof(double) * (size_t)lds_a, g_stream, A->dev(), x->dev(),
+                       ybar->dev(), xbar->dev(), lds_a, xbar->d_status);
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+int ttn_tt_cores_axpby(const double* alpha, ttn_tt_t x, const double* beta, ttn_tt_t y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !y) return fail(TTN_ERR_ARG, "ttn_tt_cores_axpby: null handle");
+    int rc = grad_common("ttn_tt_cores_axpby", {x, y});
+    if (rc) return rc;
+    const int d = x->d, batch = x->batch;
+    for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_tt_cores_axpby: destination capacity too small");
+    if (batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_cores_axpby: more than 65535 trains");
+    const double* d_alpha = nullptr; const double* d_beta = nullptr;
+    if ((rc = grad_coef(alpha, batch, 0, d_alpha))) return rc;
+    if ((rc = grad_coef(beta, batch, 1, d_beta))) return rc;
+    long long maxsz = 1;
+    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)x->dims[k] * x->bound[k] * x->bound[k + 1]);
+    hipLaunchKernelGGL(k_cores_axpby, stream_grid((maxsz + 3) / 4, d, batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), d_alpha, d_beta, y->d_status);
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+int ttn_tt_cores_dot(ttn_tt_t x, ttn_tt_t y, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !y || !out) return fail(TTN_ERR_ARG, "ttn_tt_cores_dot: null pointer");
+    int rc = grad_common("ttn_tt_cores_dot", {x, y});
+    if (rc) return rc;
+    if ((rc = g_dout.ensure(sizeof(double) * x->batch))) return rc;
+    hipLaunchKernelGGL(k_cores_dot, dim3(x->batch), dim3(TTN_WG), 0, g_stream, x->dev(), y->dev(), g_dout.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * x->batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
     return TTN_OK;
 }
 
