@@ -91,9 +91,10 @@ int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y);
 int ttn_compress(ttn_tt_t psi, int64_t max_bond, double truncerr, int64_t sweeps);
 
 /* Device-side status of the handle (synchronises).  Every call that runs bond steps or local solves on psi — ttn_compress,
- * ttn_apply_compress, ttn_bond_truncate, ttn_sweep, ttn_apply_sweep, ttn_swap_sites, ttn_hadamard_ttm, ttn_ttv_decomp, the linear
- * solvers — records per train the FIRST condition its kernels meet: TTN_ERR_CAPACITY (a rank outgrew its slot),
- * TTN_ERR_NO_CONVERGENCE (a Jacobi SVD / eigensolver hit its sweep limit), TTN_ERR_SINGULAR (singular local system).  The record is
+ * ttn_apply_compress, ttn_bond_truncate, ttn_sweep, ttn_apply_sweep, ttn_swap_sites, ttn_hadamard_ttm, ttn_ttv_decomp,
+ * ttn_tt_split_sites, ttn_tt_merge_sites, the linear solvers — records per train the FIRST condition its kernels meet:
+ * TTN_ERR_CAPACITY (a rank outgrew its slot), TTN_ERR_NO_CONVERGENCE (a Jacobi SVD / eigensolver hit its sweep limit),
+ * TTN_ERR_SINGULAR (singular local system).  The record is
  * STICKY per handle: it survives later calls and is returned — and cleared — by this query, so a chain of asynchronous calls needs
  * one query at its end.  If non-null, total_jacobi_sweeps[b] receives the number of Jacobi sweeps train b used in the last call
  * (diagnostics). */
@@ -156,6 +157,29 @@ int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol)
  * same data, without the host -> device copy.  The input buffer is only read.  Limits, status reporting and the orthogonality flags are
  * those of ttn_ttv_decomp.  Synchronises. */
 int ttn_ttv_decomp_dev(ttn_tt_t z, const double* d_tensors, int64_t index, double tol);
+
+/* --- split and merge sites (csrc/ttn_resite_kernels.h; to_qtt / to_ttv, src/qtt_tools.jl:254-360), Float64 only.  z is
+ * created by the caller with the new dims and a rank capacity (the ttn_tt_kron convention), has x's batch and must not be x.
+ * Both calls are asynchronous on the library's stream, read x's device-resident per-train ranks, write z's ranks per train
+ * and clear z's orthogonality flags; a rank above z's capacity is that train's TTN_ERR_CAPACITY through
+ * ttn_compress_status(z).
+ * ttn_tt_split_sites: z_b = to_qtt(x_b, split_dims; threshold).  nsplit[i] factors for site i of x, the factors of all sites
+ *   one after the other in split_dims (sum(nsplit) entries, the FIRST factor of a site its most significant digit); z.dims
+ *   must be exactly split_dims.  Every factor but a site's last costs one SVD of the (r_prev s) x (rest r_next) unfolding:
+ *   the new core is U, S V' is carried on.  Rank rule of ttn_swap_sites: every singular value when threshold == 0, else
+ *   count(s > threshold * s[1]), at least 1 (an all-zero unfolding keeps one zero direction where the reference would keep
+ *   none).
+ * ttn_tt_merge_sites: z_b = to_ttv(x_b, merge_numbers).  Site g of z is the product of merge_numbers[g] consecutive cores of
+ *   x with the physical indices merged big-endian (i1 n2 + i2); no SVD, the ranks are x's at the kept bonds.
+ * Refused before any launch, with a message that names the call.  TTN_ERR_ARG: a null pointer, x == z, sum(nsplit) != z's
+ * sites, sum(merge_numbers) != x's sites, ngroups != z's sites, a factor list whose product differs from the site's
+ * dimension, z.dims that differ from the flattened split lists / the merged products, differing batches, threshold < 0.
+ * TTN_ERR_CAPACITY: z's capacity at a bond kept from x below x's rank bound.  TTN_ERR_UNSUPPORTED: a ComplexF64 handle; a
+ * split unfolding with a short side above 4096 or more than 2^27 entries (ranks bounded by x's rank bound and z's capacity,
+ * as in ttn_ttv_decomp); more than 64 sites in x for a split; for a merge a batch above 65535, a merged dimension of 2^31 or
+ * more, or 2^31 output tiles in one core. */
+int ttn_tt_split_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* nsplit, const int64_t* split_dims, double threshold);
+int ttn_tt_merge_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* merge_numbers, int64_t ngroups);
 
 /* --- trains -> dense tensors and QTT grids on the device (csrc/ttn_grid_kernels.h), Float64 only (a ComplexF64 handle:
  * TTN_ERR_UNSUPPORTED before any launch).
@@ -527,7 +551,7 @@ int ttn_apply_compress_f64(int64_t d, const int64_t* dims, const double* const* 
  * in element type, and a ComplexF64 handle given to any Float64-only entry point: the linear solvers and eigensolvers,
  * ttn_orthogonalize, ttn_hadamard_ttm, ttn_swap_sites, ttn_ttv_decomp, ttn_scale_batch, the operator algebra (ttn_tto_mul / inner /
  * add / scale / kron / compress / to_tt / from_tt, ttn_tt_outer / diag_tto / kron), ttn_apply_begin / _sweep, ttn_tt_core_extent /
- * _export / _import, ttn_sv_capture, ttn_tt_to_dense, ttn_ttv_decomp_dev. */
+ * _export / _import, ttn_sv_capture, ttn_tt_to_dense, ttn_ttv_decomp_dev, ttn_tt_split_sites, ttn_tt_merge_sites. */
 int ttn_tt_create_c64(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out);
 int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out);
 int ttn_tt_dtype(ttn_tt_t h, int* cplx);      /* *cplx = 0 Float64, 1 ComplexF64 */

@@ -16,7 +16,7 @@ from .opalg import (concatenate, kron, outer_product, tto_add, tto_compress_, tt
                     ttv_to_diag_tto, ttv_to_tto)
 from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve
 from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_to_array
-from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, ttv_decomp
+from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
 from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, div, dot, euclidean_distance, hadamard, norm,
                  orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_, ttv_to_tensor)
 

@@ -94,6 +94,8 @@ SIGNATURES = {
     "ttn_swap_sites": (C.c_int, [handle, i64, p_i64, C.c_double]),
     "ttn_ttv_decomp": (C.c_int, [handle, C.c_void_p, i64, C.c_double]),
     "ttn_ttv_decomp_dev": (C.c_int, [handle, C.c_void_p, i64, C.c_double]),
+    "ttn_tt_split_sites": (C.c_int, [handle, handle, p_i64, p_i64, C.c_double]),
+    "ttn_tt_merge_sites": (C.c_int, [handle, handle, p_i64, i64]),
     "ttn_tt_to_dense": (C.c_int, [handle, p_i64, C.c_void_p]),
     "ttn_qtt_grid_points": (C.c_int, [i64, i64, C.c_int, C.c_double, C.c_double, i64, i64, C.c_void_p]),
     "ttn_als_linsolve": (C.c_int, [handle, handle, handle, handle, i64]),

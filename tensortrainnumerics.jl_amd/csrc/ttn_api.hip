@@ -8,6 +8,7 @@
 #include "ttn_ortho512.h"
 #include "ttn_ortho_ramp.h"
 #include "ttn_hsvd_kernels.h"
+#include "ttn_resite_kernels.h"
 #include "ttn_als_kernels.h"
 #include "ttn_als_grid.h"
 #include "ttn_eigsolve_kernels.h"
@@ -230,6 +231,7 @@ int ttn_init(int device) {
         {(const void*)k_als_eig, COMPRESS_LDS_BYTES},
         {(const void*)k_increase_ranks, COMPRESS_LDS_BYTES},
         {(const void*)k_ttv_decomp, COMPRESS_LDS_BYTES},
+        {(const void*)k_split_sites, COMPRESS_LDS_BYTES},
         {(const void*)k_swap_chain, COMPRESS_LDS_BYTES},
         {(const void*)k_orthogonalize, ORTHO_LDS_BYTES},
         {(const void*)k_ortho512, O5_LDS_BYTES(TTN_MAX_D * 8)},
@@ -1336,6 +1338,183 @@ static int ttv_decomp_impl(ttn_tt_t z, const double* tensors, int64_t index, dou
 }
 int ttn_ttv_decomp(ttn_tt_t z, const double* tensors, int64_t index, double tol) { return ttv_decomp_impl(z, tensors, index, tol, false); }
 int ttn_ttv_decomp_dev(ttn_tt_t z, const double* d_tensors, int64_t index, double tol) { return ttv_decomp_impl(z, d_tensors, index, tol, true); }
+
+// ---- to_qtt / to_ttv: split and merge sites (csrc/ttn_resite_kernels.h) ----------------------------------------------------------
+// to_qtt(tt, split_dims; threshold)   src/qtt_tools.jl:254-310.  z carries the flattened split lists as its dims; its ranks are written per
+// train, a rank above z's capacity is that train's TTN_ST_RANK_OVERFLOW.  Asynchronous.
+int ttn_tt_split_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* nsplit, const int64_t* split_dims, double threshold) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    F64_ONLY("ttn_tt_split_sites", {x, z});
+    if (!x || !z || !nsplit || !split_dims) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: null argument");
+    if (x == z) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: output must not alias the input");
+    if (!(threshold >= 0.0)) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: threshold must be >= 0");
+    const int dx = x->d, dz = z->d, batch = x->batch;
+    if (dx > TTN_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_split_sites: more than 64 input sites");
+    int64_t nz = 0;
+    for (int i = 0; i < dx; ++i) {
+        if (nsplit[i] < 1) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: every site needs at least one factor");
+        nz += nsplit[i];
+    }
+    if (nz != dz) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: sum(nsplit) differs from the number of sites of the output handle");
+    for (int i = 0, m = 0; i < dx; ++i) {
+        int64_t prod = 1;
+        for (int64_t j = 0; j < nsplit[i]; ++j, ++m) {
+            if (split_dims[m] < 1) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: factors must be >= 1");
+            prod *= split_dims[m];
+            if (prod > x->dims[i]) break;
+        }
+        if (prod != x->dims[i]) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: the product of a site's factors differs from its dimension");
+    }
+    for (int m = 0; m < dz; ++m)
+        if (z->dims[m] != split_dims[m]) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: the output handle's dims differ from the flattened split lists");
+    if (z->batch != batch) return fail(TTN_ERR_ARG, "ttn_tt_split_sites: batch sizes differ");
+    // worst-case unfoldings and carried remainders: input ranks bounded by x's host bound, new ranks by z's capacity (cf. ttn_ttv_decomp)
+    std::vector<int64_t> bnd(dz + 1, 1);
+    long long pmax = 1, qmax = 1, m2max = 1, carry = 2;
+    bnd[0] = x->bound[0];
+    if (z->cap[0] < x->bound[0]) return fail(TTN_ERR_CAPACITY, "ttn_tt_split_sites: destination capacity too small at a kept bond");
+    for (int i = 0, zi = 0; i < dx; ++i) {
+        const long long rnext = x->bound[i + 1];
+        long long rprev = x->bound[i], remaining = x->dims[i];
+        if (z->cap[zi + nsplit[i]] < rnext) return fail(TTN_ERR_CAPACITY, "ttn_tt_split_sites: destination capacity too small at a kept bond");
+        for (int64_t j = 0; j + 1 < nsplit[i]; ++j, ++zi) {
+            const long long s = z->dims[zi], fine = remaining / s, a = rprev * s, bc = fine * rnext;
+            pmax = std::max(pmax, std::min(a, bc)); qmax = std::max(qmax, std::max(a, bc));
+            if (std::min(a, bc) > 4096)
+                return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_split_sites: an unfolding has a short side above 4096 (lower the ranks or the rank capacity of the output)");
+            if (a * bc > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_split_sites: an unfolding has more than 2^27 entries");
+            m2max = std::max(m2max, a * bc);
+            rprev = std::min<long long>(std::min(a, bc), z->cap[zi + 1]);
+            bnd[zi + 1] = rprev;
+            carry = std::max(carry, rprev * bc);
+            remaining = fine;
+        }
+        ++zi;
+        bnd[zi] = rnext;
+    }
+    carry = (carry + 1) & ~1LL; m2max = (m2max + 1) & ~1LL;
+    const long long per_scr = QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64;
+    const long long per_train = 2 * carry + m2max + per_scr;
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * batch);
+    if (rc) return rc;
+    double* base = g_scratch.as<double>();
+    SplitArgs H;
+    memset(&H, 0, sizeof(H));
+    CompressArgs& P = H.C;
+    P.tt = z->dev();
+    P.max_bond = (int64_t)1 << 62;
+    P.sweeps = 1;
+    P.scratch = base + 2 * carry + m2max;                  // per train: [cur0 | cur1 | M2 | LQ / Jacobi scratch]
+    P.scratch_stride = per_train;
+    P.pmax = (int)pmax; P.qmax = (int)qmax;
+    P.status = z->d_status;
+    P.sweep_stats = z->d_status + batch;
+    H.x = x->dev();
+    for (int i = 0; i < dx; ++i) H.nsplit[i] = (int)nsplit[i];
+    H.threshold = threshold;
+    H.work = base;
+    H.work_stride = per_train;
+    H.carry_len = carry;
+    hipLaunchKernelGGL(k_split_sites, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, H);
+    HIPCHK(hipGetLastError());
+    z->bound = bnd;
+    std::fill(z->ot.begin(), z->ot.end(), 0);              // qtt_tools.jl:309
+    return TTN_OK;
+}
+
+// to_ttv(qtt, merge_numbers)   src/qtt_tools.jl:323-360: group g of z is the product of merge_numbers[g] consecutive cores of x, physical
+// indices merged big-endian (the earlier core is the more significant digit).  Asynchronous; no SVD, ranks are the kept bonds of x.
+int ttn_tt_merge_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* merge_numbers, int64_t ngroups) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    F64_ONLY("ttn_tt_merge_sites", {x, z});
+    if (!x || !z || !merge_numbers) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: null argument");
+    if (x == z) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: output must not alias the input");
+    const int dx = x->d, batch = x->batch;
+    int64_t total = 0;
+    for (int64_t g = 0; g < ngroups; ++g) {
+        if (merge_numbers[g] < 1) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: every group needs at least one core");
+        total += merge_numbers[g];
+    }
+    if (ngroups < 1 || total != dx) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: sum(merge_numbers) differs from the number of sites of the input handle");
+    if (ngroups != z->d) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: the number of groups differs from the number of sites of the output handle");
+    std::vector<int> first((size_t)ngroups);
+    for (int g = 0, k = 0; g < (int)ngroups; k += (int)merge_numbers[g], ++g) {
+        first[g] = k;
+        int64_t prod = 1;
+        for (int s = 0; s < merge_numbers[g]; ++s) { prod *= x->dims[k + s]; if (prod > z->dims[g]) break; }
+        if (prod != z->dims[g]) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: the output handle's dims differ from the products of the merged dims");
+    }
+    if (z->batch != batch) return fail(TTN_ERR_ARG, "ttn_tt_merge_sites: batch sizes differ");
+    std::vector<int64_t> bnd((size_t)ngroups + 1);
+    for (int g = 0; g <= (int)ngroups; ++g) {
+        bnd[g] = x->bound[g < ngroups ? first[g] : dx];
+        if (z->cap[g] < bnd[g]) return fail(TTN_ERR_CAPACITY, "ttn_tt_merge_sites: destination capacity too small");
+    }
+    // workspace: two buffers per group of >= 3 cores, each as large as its largest intermediate product
+    std::vector<long long> woff((size_t)ngroups, 0), whalf((size_t)ngroups, 0);
+    long long wtot = 0;
+    for (int g = 0; g < (int)ngroups; ++g) {
+        const int k0 = first[g], cnt = (int)merge_numbers[g];
+        long long n = x->dims[k0], half = 0;
+        for (int s = 1; s + 1 < cnt; ++s) { n *= x->dims[k0 + s]; half = std::max(half, n * x->bound[k0] * x->bound[k0 + s + 1]); }
+        half = (half + 1) & ~1LL;
+        woff[g] = wtot; whalf[g] = half; wtot += 2 * half;
+    }
+    // grid sizes of every launch, checked before the first one: tiles of step `step` over the groups g0 .. g0 + ng - 1 (by x's rank bounds)
+    auto step_tiles = [&](int g0, int ng, int step) {
+        long long tiles = 1;
+        for (int g = g0; g < g0 + ng; ++g) {
+            if (merge_numbers[g] <= step) continue;
+            const int k0 = first[g];
+            long long nA = 1;
+            for (int s = 0; s < step; ++s) nA *= x->dims[k0 + s];
+            const long long n2 = x->dims[k0 + step];
+            const long long CJ = std::min<long long>(n2, TTN_MERGE_NX), CI = std::min<long long>(nA, TTN_MERGE_NX / CJ);
+            tiles = std::max(tiles, ((nA + CI - 1) / CI) * ((n2 + CJ - 1) / CJ) * ((x->bound[k0] + 15) / 16) * ((x->bound[k0 + step + 1] + 15) / 16));
+        }
+        return tiles;
+    };
+    if (batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_merge_sites: more than 65535 trains in one handle");
+    for (int g = 0; g < (int)ngroups; ++g)
+        if (z->dims[g] >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_merge_sites: a merged physical dimension of 2^31 or more");
+    for (int g0 = 0; g0 < (int)ngroups; g0 += TTN_MERGE_GROUPS) {
+        const int ng = std::min<int>(TTN_MERGE_GROUPS, (int)ngroups - g0);
+        int maxcnt = 1;
+        for (int g = g0; g < g0 + ng; ++g) maxcnt = std::max(maxcnt, (int)merge_numbers[g]);
+        for (int step = 1; step < maxcnt; ++step)
+            if (step_tiles(g0, ng, step) >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_merge_sites: more than 2^31 output tiles in one core");
+    }
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)std::max<long long>(2, wtot) * batch);
+    if (rc) return rc;
+    for (int g0 = 0; g0 < (int)ngroups; g0 += TTN_MERGE_GROUPS) {
+        const int ng = std::min<int>(TTN_MERGE_GROUPS, (int)ngroups - g0);
+        MergeArgs M;
+        memset(&M, 0, sizeof(M));
+        M.x = x->dev(); M.z = z->dev(); M.status = z->d_status; M.ngroups = ng; M.g0 = g0;
+        M.work = g_scratch.as<double>(); M.work_stride = wtot;
+        int maxcnt = 1;
+        long long copy_len = 1;
+        for (int g = 0; g < ng; ++g) {
+            const int k0 = first[g0 + g], cnt = (int)merge_numbers[g0 + g];
+            M.k0[g] = k0; M.count[g] = cnt; M.work_off[g] = woff[g0 + g]; M.work_half[g] = whalf[g0 + g];
+            maxcnt = std::max(maxcnt, cnt);
+            if (cnt == 1) copy_len = std::max<long long>(copy_len, x->dims[k0] * x->bound[k0] * x->bound[k0 + 1]);
+        }
+        const unsigned cblocks = (unsigned)std::min<long long>((copy_len + TTN_MERGE_TB - 1) / TTN_MERGE_TB, 1024);
+        hipLaunchKernelGGL(k_merge_copy, dim3(cblocks, (unsigned)ng, (unsigned)batch), dim3(TTN_MERGE_TB), 0, g_stream, M);
+        HIPCHK(hipGetLastError());
+        for (int step = 1; step < maxcnt; ++step) {
+            M.step = step;
+            hipLaunchKernelGGL(k_merge_step, dim3((unsigned)step_tiles(g0, ng, step), (unsigned)ng, (unsigned)batch), dim3(TTN_MERGE_TB), 0, g_stream, M);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    z->bound = bnd;
+    std::fill(z->ot.begin(), z->ot.end(), 0);              // qtt_tools.jl:359
+    return TTN_OK;
+}
 
 // ---- train -> dense tensor (csrc/ttn_grid_kernels.h) --------------------------------------------------------------------------------
 // One side's partial products, enqueued step by step: the small steps share single-workgroup launches, a large step gets the grid.

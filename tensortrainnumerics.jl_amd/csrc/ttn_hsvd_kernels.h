@@ -26,7 +26,8 @@ struct HsvdArgs {
 //   3 (left move, called on the TRANSPOSED view): core = x_{i+1}[x, j, c] <- V'[j, x + n c]; remainder (U S) -> x_i, contiguous
 // `rule` 0: r = count(s >= tol) (absolute); 1: sv_trunc (mals.jl:42-56: drop the tail while its weight stays below
 // tol * ||s||^2, keep the value that crossed the line) clamped to `rclamp`; 2: cut_off_index (dmrg.jl:179-185: count(s > ||s|| tol),
-// extended over values within 1e-10 (relative and absolute) of the last kept one) clamped to `rclamp`.
+// extended over values within 1e-10 (relative and absolute) of the last kept one) clamped to `rclamp`; 3: to_qtt
+// (src/qtt_tools.jl:285-291: every value when tol == 0, else count(s > tol * s[1]), at least 1 — the rule of ttn_swap_sites).
 // Returns r (>= 1), or -1 if r exceeds `cap` (nothing written).
 __device__ __noinline__ int wg_hsvd_step(const CompressArgs& P, int b, const BondCtx& S, View Av, int a, int bcols, double* M2,
                                          int layout, int n, int rfix, double* core, double* rem, double tol, int cap, double* lds,
@@ -78,6 +79,13 @@ __device__ __noinline__ int wg_hsvd_step(const CompressArgs& P, int b, const Bon
                 if (fabs(u - v) <= fmax(1.0e-10, 1.0e-10 * fmax(fabs(u), fabs(v)))) ++r; else break;
             }
             if (r > rclamp) r = rclamp;
+        } else if (rule == 3) {
+            r = p;
+            if (tol > 0.0) {
+                const double thr = tol * (S.sigs[0] * s0);
+                r = 0;
+                for (int i = 0; i < p; ++i) r += (S.sigs[i] * s0 > thr) ? 1 : 0;
+            }
         } else {
             r = p;
             if (tol != 0.0) {

@@ -210,6 +210,40 @@ class DeviceTT:
         _lib.check(_lib.lib().ttn_tt_diag_tto(self.h, int(b), C.byref(h)))
         return DeviceTTO._adopt(h)
 
+    # split / merge sites (csrc/ttn_resite_kernels.h)
+    def split_sites(self, split_dims: Sequence[Sequence[int]], threshold: float = 0.0, cap_rks: Sequence[int] | None = None) -> "DeviceTT":
+        """to_qtt(x, split_dims; threshold) train by train — src/qtt_tools.jl:254-310: site i becomes len(split_dims[i]) sites, the first
+        factor the most significant digit.  Default capacity: the exact bound min(rows, cols) of every SVD, propagated from ``self.cap``.
+        Asynchronous; a rank above ``cap_rks`` shows in ``compress_status`` of the result."""
+        sd = [[int(v) for v in s] for s in split_dims]
+        if len(sd) != self.N or any(len(s) < 1 for s in sd):
+            raise _lib.TTNError(f"split_sites: {len(sd)} factor lists for {self.N} sites (every site needs a non-empty list)")
+        flat = [v for s in sd for v in s]
+        if cap_rks is None:
+            cap_rks = split_rank_capacity(self.dims, self.cap, sd)
+        z = DeviceTT(flat, cap_rks, self.batch, dtype=self.dtype)
+        _lib.check(_lib.lib().ttn_tt_split_sites(self.h, z.h, _i64([len(s) for s in sd]), _i64(flat), float(threshold)))
+        return z
+
+    def merge_sites(self, merge_numbers: Sequence[int], cap_rks: Sequence[int] | None = None) -> "DeviceTT":
+        """to_ttv(x, merge_numbers) train by train — src/qtt_tools.jl:323-360: every run of merge_numbers[g] consecutive cores becomes one
+        core, physical indices merged big-endian.  Default capacity: ``self.cap`` at the kept bonds.  Asynchronous."""
+        mn = [int(c) for c in merge_numbers]
+        if not mn or any(c < 1 for c in mn) or sum(mn) != self.N:
+            raise _lib.TTNError(f"merge_sites: merge_numbers {mn} must be positive and sum to {self.N} (the number of sites)")
+        first = [sum(mn[:g]) for g in range(len(mn) + 1)]
+        dims = []
+        for g, c in enumerate(mn):
+            n = 1
+            for k in range(first[g], first[g] + c):
+                n *= self.dims[k]
+            dims.append(n)
+        if cap_rks is None:
+            cap_rks = [self.cap[k] for k in first]
+        z = DeviceTT(dims, cap_rks, self.batch, dtype=self.dtype)
+        _lib.check(_lib.lib().ttn_tt_merge_sites(self.h, z.h, _i64(mn), len(mn)))
+        return z
+
     # train -> dense tensor (csrc/ttn_grid_kernels.h)
     def to_dense(self, strides: Sequence[int] | None = None):
         """Every train of the batch as a dense tensor, on the device: a float64 torch tensor (batch, total) with
@@ -252,6 +286,19 @@ class DeviceTT:
         n = C.c_int64(0)
         _lib.check(_lib.lib().ttn_sv_get(self.h, int(b), int(step), out, cap, C.byref(n)))
         return np.array(out[: n.value])
+
+
+def split_rank_capacity(dims: Sequence[int], rks: Sequence[int], split_dims: Sequence[Sequence[int]]) -> List[int]:
+    """Rank bounds of to_qtt at threshold 0 for input ranks (or capacities) ``rks``: every SVD keeps min(rows, cols) directions."""
+    cap = [int(rks[0])]
+    for i, s in enumerate(split_dims):
+        r_prev, r_next, remaining = int(rks[i]), int(rks[i + 1]), int(dims[i])
+        for f in s[:-1]:
+            remaining //= max(int(f), 1)
+            r_prev = max(1, min(r_prev * int(f), remaining * r_next))
+            cap.append(r_prev)
+        cap.append(r_next)
+    return cap
 
 
 def apply(A: DeviceTTO, x: DeviceTT, y: DeviceTT) -> DeviceTT:

@@ -158,3 +158,44 @@ def ttv_decomp(tensor, index: int = 1, tol: float = 1.0e-12, rank_cap: int = 102
     compress_status(z)
     z.max_ranks()
     return z.download(0)
+
+
+# ---- to_qtt / to_ttv ----------------------------------------------------------------------------------------------------
+def _plain_real_train(x, who: str) -> TTvector:
+    """A QTTvector counts as its TTvector (the reference's methods forward the same way); complex cores are refused."""
+    import numpy as np
+    from .qttnd import QTTvector
+    if isinstance(x, QTTvector):
+        x = x.ttvector()
+    if not isinstance(x, TTvector):
+        raise TypeError(f"{who}: expected a TTvector or a QTTvector, got {type(x).__name__}")
+    if any(np.iscomplexobj(c) for c in x.ttv_vec):
+        raise TypeError(f"{who}: the device kernels are Float64 only, a complex train was passed")
+    return x
+
+
+def to_qtt(tt, split_dims: Sequence[Sequence[int]], threshold: float = 0.0) -> TTvector:
+    """to_qtt(tt, split_dims; threshold) (src/qtt_tools.jl:254-310): split the physical index of core i into the factors split_dims[i]
+    (first factor = most significant digit) by successive SVDs; ``threshold`` > 0 keeps the singular values above threshold * s[1]
+    (at least one: an all-zero unfolding keeps a zero direction where the reference would keep none).  Returns a plain TTvector."""
+    tt = _plain_real_train(tt, "to_qtt")
+    assert len(split_dims) == tt.N, "split_dims must have one entry per TT core"
+    for i in range(tt.N):
+        prod = 1
+        for f in split_dims[i]:
+            prod *= int(f)
+        assert len(split_dims[i]) >= 1 and prod == tt.ttv_dims[i], f"prod(split_dims[{i + 1}]) must equal {tt.ttv_dims[i]}"
+    dz = DeviceTT.from_host(tt).split_sites(split_dims, threshold)
+    compress_status(dz)
+    return dz.download(0)
+
+
+def to_ttv(qtt, merge_numbers: Sequence[int]) -> TTvector:
+    """to_ttv(qtt, merge_numbers) (src/qtt_tools.jl:323-360): contract every run of merge_numbers[i] consecutive cores into one, the
+    earlier core the more significant digit of the merged physical index.  Returns a plain TTvector."""
+    qtt = _plain_real_train(qtt, "to_ttv")
+    mn = [int(c) for c in merge_numbers]
+    assert sum(mn) == qtt.N and all(c >= 1 for c in mn), f"merge_numbers must sum to {qtt.N} (the number of QTT cores)"
+    dz = DeviceTT.from_host(qtt).merge_sites(mn)
+    compress_status(dz)
+    return dz.download(0)
