@@ -580,6 +580,14 @@ int ttn_apply_compress_c64(int64_t d, const int64_t* dims, const double* const* 
 /* r_and_d_to_rks(rks, dims; rmax)   src/tt_tools.jl:407-425 (host-side integer helper, bit-exact) */
 int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int64_t* rks, int64_t rmax, int64_t* out);
 
+/* ---- rectangular operators: grid transfer (csrc/ttn_rect_kernels.h) ----------------------------------------------
+ * The reference's second method of `*` (src/tt_operations.jl:116-148): an operator of M = N + 1 sites with cores
+ * (n_out, n_in, R_l, R_r), exactly one of them with n_in == 1, applied to trains of N sites: qtto_constant_prolongation and
+ * qtto_linear_prolongation (src/tt_operators.jl:441-504).  Such an operator lives in a handle type of its own, ttn_rtto_t, so that no
+ * entry point above can be handed one; the type and its five entry points (ttn_rtto_create / free / ranks, ttn_apply_rect,
+ * ttn_apply_rect_f64) are declared in ttn_rect.h, which this header includes. */
+#include "ttn_rect.h"
+
 #ifdef __cplusplus
 }
 #endif

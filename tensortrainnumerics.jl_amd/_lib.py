@@ -163,6 +163,15 @@ SIGNATURES = {
     "ttn_apply_compress_c64": (C.c_int, [i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64, p_i64, i64, C.c_double, i64, C.c_int, C.c_int]),
 }
 
+# the rectangular operators of include/ttn_rect.h (a handle type of their own, ttn_rtto_t)
+RECT_SIGNATURES = {
+    "ttn_rtto_create": (C.c_int, [i64, p_i64, p_i64, p_i64, pp_f64, p_handle]),
+    "ttn_rtto_free": (C.c_int, [handle]),
+    "ttn_rtto_ranks": (C.c_int, [handle, p_i64, p_i64, p_i64, p_i64]),
+    "ttn_apply_rect": (C.c_int, [handle, handle, handle]),
+    "ttn_apply_rect_f64": (C.c_int, [i64, p_i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64]),
+}
+
 _lib = None
 
 
@@ -170,7 +179,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile csrc/ttn_api.hip for gfx950 into libttn_hip.so (in-tree).  hipcc cross-compiles
     without a GPU."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
-    srcs.append(os.path.join(INCLUDE, "ttn.h"))
+    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -193,7 +202,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,9 @@ benchmark uses for "rank-r random TTvector" inputs.
     qtt_to_vector                   src/qtt_tools.jl:57-71 (densifier used by small tests; real or complex trains)
     fourier_qtto, reverse_qtt_bits  src/tt_transformations.jl (the QFT as a complex TToperator of rank K + 1)
     function_to_qtt_uniform         src/qtt_tools.jl:73-82
+    qtto_prolongation, qtto_constant_prolongation, qtto_linear_prolongation   src/tt_operators.jl:418-504 (grid transfer; the last two
+                                    are RECTANGULAR: d + 1 sites, the extra one with a singleton input index)
+    qtt_basis_vector, function_to_tensor, function_to_qtt, qtt_to_function    src/qtt_tools.jl:190-199, :15-55
 
 These are rank-<=5 closed forms evaluated once per problem: host code, not GPU work.
 """
@@ -132,6 +135,108 @@ def id_tto(d: int, n_dim: int = 2) -> TToperator:
     return TToperator(d, vec, (n_dim,) * d, [1] * (d + 1), [0] * d)
 
 
+# ---------------------------------------------------------------------------------------------
+# Grid transfer — src/tt_operators.jl:418-504.  The constant and the linear prolongation take a train of d binary sites to d + 1: their
+# cores have shape (n_out, n_in, R_l, R_r) and the last one is (2, 1, r, 1), a site that consumes no input site (tt.apply's
+# rectangular form, src/tt_operations.jl:116-148).
+# ---------------------------------------------------------------------------------------------
+def qtto_prolongation(d: int) -> TToperator:
+    """qtto_prolongation(d) — src/tt_operators.jl:418-436: the multigrid prolongation as a SQUARE operator of ranks 2."""
+    assert d >= 2, "Dimension must be at least 2"
+    out = zeros_tto((2,) * d, [1] + [2] * (d - 1) + [1])
+    Id = np.eye(2)
+    J = np.array([[0.0, 1.0], [0.0, 0.0]])
+    out.tto_vec[0][:, :, 0, :] = 0.5 * np.stack([Id, J.T], axis=-1)
+    mid = np.zeros((2, 2, 2, 2))
+    mid[:, :, 0, 0], mid[:, :, 0, 1], mid[:, :, 1, 1] = Id, J.T, J
+    for k in range(1, d - 1):
+        out.tto_vec[k][...] = mid
+    out.tto_vec[d - 1][:, :, 0, 0] = [[1.0, 1.0], [2.0, 0.0]]
+    return out
+
+
+def qtto_constant_prolongation(d: int) -> TToperator:
+    """qtto_constant_prolongation(d) — src/tt_operators.jl:441-458: every coarse value copied to its two fine points.  d + 1 sites: the
+    cores of id_tto(d), then ones(2, 1, 1, 1)."""
+    assert d >= 1, "Dimension must be at least 1"
+    vec = id_tto(d).tto_vec + [np.ones((2, 1, 1, 1), order="F")]
+    return TToperator(d + 1, vec, (2,) * (d + 1), [1] * (d + 2), [0] * (d + 1))
+
+
+def _average_branch(d: int) -> TToperator:
+    """0.5 * (id_tto(d) + shift(d)) restated on the host (the sum of src/tt_operations.jl:71-95: first core [I S], middle cores block
+    diagonal, last core [I; S]; the scalar of :271-281 on the first core), so that building an operator needs no device.  d == 1 is the
+    reference's special case (src/tt_operators.jl:467-470)."""
+    if d == 1:
+        return TToperator(1, [np.asfortranarray((0.5 * np.array([[1.0, 1.0], [0.0, 1.0]])).reshape(2, 2, 1, 1))], (2,), [1, 1], [0])
+    I, S = id_tto(d), shift(d)
+    out = zeros_tto((2,) * d, [1] + [a + b for a, b in zip(I.tto_rks[1:-1], S.tto_rks[1:-1])] + [1])
+    for k in range(d):
+        li, ri = I.tto_rks[k], I.tto_rks[k + 1]
+        if k == 0:
+            out.tto_vec[k][:, :, :, :ri], out.tto_vec[k][:, :, :, ri:] = I.tto_vec[k], S.tto_vec[k]
+        elif k == d - 1:
+            out.tto_vec[k][:, :, :li, :], out.tto_vec[k][:, :, li:, :] = I.tto_vec[k], S.tto_vec[k]
+        else:
+            out.tto_vec[k][:, :, :li, :ri], out.tto_vec[k][:, :, li:, ri:] = I.tto_vec[k], S.tto_vec[k]
+    out.tto_vec[0] = np.asfortranarray(0.5 * out.tto_vec[0])
+    return out
+
+
+def qtto_linear_prolongation(d: int) -> TToperator:
+    """qtto_linear_prolongation(d) — src/tt_operators.jl:463-504: fine point 2a takes coarse value a, fine point 2a + 1 the mean of a and
+    a + 1 (the last one: half of the last value).  d + 1 sites, interior ranks 5: the block-diagonal join of id_tto(d) and
+    0.5 (id_tto(d) + shift(d)); the last core (2, 1, r, 1) selects the identity branch for output bit 0, the average for bit 1."""
+    assert d >= 1, "Dimension must be at least 1"
+    I, Av = id_tto(d), _average_branch(d)
+    rks = [1] + [a + b for a, b in zip(I.tto_rks[1:], Av.tto_rks[1:])] + [1]
+    vec = []
+    for k in range(d):
+        li, ri = I.tto_rks[k], I.tto_rks[k + 1]
+        core = np.zeros((2, 2, rks[k], rks[k + 1]), order="F")
+        if k == 0:
+            core[:, :, :, :ri], core[:, :, :, ri:] = I.tto_vec[0], Av.tto_vec[0]
+        else:
+            core[:, :, :li, :ri], core[:, :, li:, ri:] = I.tto_vec[k], Av.tto_vec[k]
+        vec.append(core)
+    last = np.zeros((2, 1, rks[d], 1), order="F")
+    last[0, 0, :I.tto_rks[d], 0] = 1.0
+    last[1, 0, I.tto_rks[d]:, 0] = 1.0
+    vec.append(last)
+    return TToperator(d + 1, vec, (2,) * (d + 1), rks, [0] * (d + 1))
+
+
+def qtt_basis_vector(d: int, pos: int, val: float = 1.0) -> TTvector:
+    """qtt_basis_vector(d, pos, val = 1.0) — src/qtt_tools.jl:190-199: val times the pos-th (1-based) unit vector of 2^d entries, rank 1,
+    site 1 the most significant bit, val on the first core."""
+    out = zeros_tt((2,) * d, [1] * (d + 1))
+    for k in range(d):
+        out.ttv_vec[k][((pos - 1) >> (d - 1 - k)) & 1, 0, 0] = val if k == 0 else 1.0
+    return out
+
+
+def function_to_tensor(f, d: int, a: float = 0.0, b: float = 1.0) -> np.ndarray:
+    """function_to_tensor(f, d; a, b) — src/qtt_tools.jl:15-31: out[t_1, ..., t_d] = f(sum_i 2^(d - i) t_i / (2^d - 1)), t_i in {0, 1},
+    site 1 the most significant bit.  As in the reference, the interval is accepted and NOT used (index_to_point takes L = b - a and
+    never reads it): the points are k / (2^d - 1) in [0, 1] whatever a and b are."""
+    out = np.zeros((2,) * d, order="F")
+    scale = 2 ** d - 1
+    for t in np.ndindex(*(2,) * d):
+        x = 2.0 ** (d - 1) * t[0] / scale
+        for i in range(2, d + 1):
+            x = x + 2.0 ** (d - i) * t[i - 1] / scale
+        out[t] = f(x)
+    return out
+
+
+def function_to_qtt(f, d: int, a: float = 0.0, b: float = 1.0) -> TTvector:
+    """function_to_qtt(f, d; a = 0.0, b = 1.0) — src/qtt_tools.jl:45-48: ttv_decomp (on the device, tol 1e-12) of the samples of f at
+    k / (2^d - 1), k = 0 .. 2^d - 1, site 1 the most significant bit.  a and b do not move the points (see function_to_tensor): the
+    reference's behaviour, restated."""
+    from .qtt import ttv_decomp
+    return ttv_decomp(function_to_tensor(f, d, a, b))
+
+
 def _trig_train(d, a, b, lam, first_of):
     out = zeros_tt((2,) * d, _qtt_ranks(d, 2))
     h = (b - a) / (2 ** d - 1)
@@ -199,6 +304,11 @@ def qtt_to_vector(qtt: TTvector) -> np.ndarray:
         G = qtt.ttv_vec[k]
         P = np.stack([P @ G[0], P @ G[1]], axis=1).reshape(2 * P.shape[0], G.shape[2])
     return P[:, 0].copy() if P.shape[1] == 1 else P.reshape(-1)
+
+
+def qtt_to_function(qtt: TTvector) -> np.ndarray:
+    """qtt_to_function(qtt) — src/qtt_tools.jl:53-55: qtt_to_vector."""
+    return qtt_to_vector(qtt)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 #include "ttn_cplx_kernels.h"
 #include "ttn_grid_kernels.h"
 #include "ttn_grad_kernels.h"
+#include "ttn_rect_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -160,6 +161,25 @@ struct ttn_tto_s {
     }
 };
 
+// A rectangular TT operator (include/ttn_rect.h): cores (n_out, n_in, R_l, R_r), Float64, immutable, ranks known on the host.  A type
+// of its own: no entry point written for square operators can be handed one.
+struct ttn_rtto_s {
+    int d = 0;                                // M, the number of sites
+    std::vector<int64_t> odims, idims, rks;
+    std::vector<int> singles;                 // 0-based sites with n_in == 1 (ttn_apply_rect needs exactly one)
+    std::vector<long long> off;
+    double* d_data = nullptr;
+    long long* d_off = nullptr;
+    long long* d_rks = nullptr;
+    int* d_dims = nullptr;                    // [2 M]: n_out, then n_in
+    RTTODev dev() const {
+        RTTODev t;
+        t.data = d_data; t.off = d_off; t.rks = d_rks; t.odims = d_dims; t.idims = d_dims + d; t.d = d;
+        t.s = singles.empty() ? -1 : singles[0];
+        return t;
+    }
+};
+
 static bool same_dims(const std::vector<int64_t>& a, const std::vector<int64_t>& b) { return a == b; }
 
 // A Float64-only entry point that receives a ComplexF64 handle is refused before any launch: it would read half a slot as a whole one.
@@ -199,6 +219,7 @@ struct Owned {
 };
 using OwnedTT = Owned<ttn_tt_s, ttn_tt_free>;
 using OwnedTTO = Owned<ttn_tto_s, ttn_tto_free>;
+using OwnedRTTO = Owned<ttn_rtto_s, ttn_rtto_free>;
 
 extern "C" {
 
@@ -688,6 +709,109 @@ int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
         }
         hipLaunchKernelGGL(k_apply, stream_grid(apply_items, d, x->batch), tb, apply_lds, g_stream, A->dev(), x->dev(), y->dev(), lds_a, lds_rl);
     }
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+// ---- rectangular operators (csrc/ttn_rect_kernels.h) ------------------------------------------------------------------------------
+int ttn_rtto_create(int64_t M, const int64_t* out_dims, const int64_t* in_dims, const int64_t* rks, const double* const* cores, ttn_rtto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!out_dims || !in_dims || !rks || !cores || !out || M < 1 || M > TTN_MAX_D) return fail(TTN_ERR_ARG, "ttn_rtto_create: bad argument");
+    for (int64_t k = 0; k < M; ++k) {
+        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_rtto_create: null core");
+        if (out_dims[k] < 1 || in_dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_rtto_create: dims must be >= 1");
+    }
+    for (int64_t k = 0; k <= M; ++k) if (rks[k] < 1) return fail(TTN_ERR_ARG, "ttn_rtto_create: ranks must be >= 1");
+    OwnedRTTO own;
+    ttn_rtto_s* h = own.h = new ttn_rtto_s();
+    h->d = (int)M;
+    h->odims.assign(out_dims, out_dims + M);
+    h->idims.assign(in_dims, in_dims + M);
+    h->rks.assign(rks, rks + M + 1);
+    h->off.resize(M + 1);
+    long long o = 0;
+    for (int64_t k = 0; k < M; ++k) {
+        h->off[k] = o;
+        if (in_dims[k] == 1) h->singles.push_back((int)k);
+        const long long sz = (long long)out_dims[k] * in_dims[k] * rks[k] * rks[k + 1];
+        o += (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
+    }
+    h->off[M] = o;
+    std::vector<int> idims(2 * M);
+    for (int64_t k = 0; k < M; ++k) { idims[k] = (int)out_dims[k]; idims[M + k] = (int)in_dims[k]; }
+    std::vector<long long> r64(rks, rks + M + 1);
+    std::vector<double> flat((size_t)o, 0.0);                           // the cores at their slots, the rounding gaps zero
+    for (int64_t k = 0; k < M; ++k) std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)out_dims[k] * in_dims[k] * rks[k] * rks[k + 1]);
+    hipError_t e;
+    if ((e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)o)) != hipSuccess ||
+        (e = hipMalloc((void**)&h->d_off, sizeof(long long) * (M + 1))) != hipSuccess ||
+        (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (M + 1))) != hipSuccess ||
+        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * M)) != hipSuccess)
+        return hipfail(e, "hipMalloc(ttn_rtto)");
+    HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * (size_t)o, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * M, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));          // the tables and `flat` are locals, `cores` is caller memory
+    *out = own.release();
+    return TTN_OK;
+}
+
+int ttn_rtto_free(ttn_rtto_t h) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!h) return TTN_OK;
+    if (g_init) hipStreamSynchronize(g_stream);
+    if (h->d_data) hipFree(h->d_data);
+    if (h->d_off) hipFree(h->d_off);
+    if (h->d_rks) hipFree(h->d_rks);
+    if (h->d_dims) hipFree(h->d_dims);
+    delete h;
+    return TTN_OK;
+}
+
+int ttn_rtto_ranks(ttn_rtto_t h, int64_t* M, int64_t* out_dims, int64_t* in_dims, int64_t* rks) {
+    if (!h) return fail(TTN_ERR_ARG, "null handle");
+    if (M) *M = h->d;
+    for (int k = 0; k < h->d; ++k) { if (out_dims) out_dims[k] = h->odims[k]; if (in_dims) in_dims[k] = h->idims[k]; }
+    if (rks) for (int m = 0; m <= h->d; ++m) rks[m] = h->rks[m];
+    return TTN_OK;
+}
+
+// y = A * x for a rectangular A (src/tt_operations.jl:116-148).  Every check runs before y is touched.
+int ttn_apply_rect(ttn_rtto_t A, ttn_tt_t x, ttn_tt_t y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
+    if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_rect: output must not alias the input");
+    F64_ONLY("ttn_apply_rect", {x, y});
+    const int M = A->d, N = x->d;
+    if (M != N + 1) return fail(TTN_ERR_DIMS, "Rectangular TToperator must have one additional output site");
+    if (A->singles.size() != 1) return fail(TTN_ERR_DIMS, "Rectangular TToperator must have exactly one singleton input site");
+    const int s = A->singles[0];
+    for (int k = 0; k < N; ++k) if (A->idims[k < s ? k : k + 1] != x->dims[k]) return fail(TTN_ERR_DIMS, "Incompatible input dimensions");
+    if (x->bound[N] != 1) return fail(TTN_ERR_DIMS, "Input TTvector must have a closed right boundary rank");
+    if (y->d != M || !same_dims(A->odims, y->dims)) return fail(TTN_ERR_DIMS, "ttn_apply_rect: the destination's dimensions are not the operator's output dimensions");
+    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    std::vector<int64_t> yb(M + 1);
+    for (int m = 0; m <= M; ++m) yb[m] = A->rks[m] * x->bound[m > s ? m - 1 : m];
+    for (int m = 0; m <= M; ++m) if (y->cap[m] < yb[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply_rect: destination capacity too small");
+    for (int k = 0; k < M; ++k)
+        if (stream_fibres_too_many((long long)y->cap[k] * y->cap[k + 1])) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_rect: 2^31 or more fibres in one output core (32-bit element indices)");
+    // LDS: the largest operator core that takes the n_out = 2 mapping and fits TTN_APPLY_LDS_DOUBLES; grid: the most items of any site
+    long long lds_a = 0, items = 1;
+    for (int k = 0; k < M; ++k) {
+        const long long asz = (long long)A->odims[k] * A->idims[k] * A->rks[k] * A->rks[k + 1];
+        const bool fast = A->odims[k] == 2 && A->idims[k] == (k == s ? 1 : 2) && asz <= TTN_APPLY_LDS_DOUBLES;
+        if (fast) lds_a = std::max<long long>(lds_a, asz);
+        items = std::max<long long>(items, fast ? yb[k] * ((yb[k + 1] + TTN_RECT_K - 1) / TTN_RECT_K) : yb[k] * yb[k + 1]);
+    }
+    hipLaunchKernelGGL(k_ranks_mul_rect, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
+    HIPCHK(hipGetLastError());
+    y->bound = yb;
+    std::fill(y->ot.begin(), y->ot.end(), 0);
+    hipLaunchKernelGGL(k_apply_rect, stream_grid(items, M, x->batch), dim3(TTN_STREAM_TB), sizeof(double) * (size_t)((lds_a + 1) & ~1LL), g_stream,
+                       A->dev(), x->dev(), y->dev(), (int)lds_a);
     HIPCHK(hipGetLastError());
     return TTN_OK;
 }
@@ -3027,6 +3151,24 @@ int apply_compress_host(int64_t d, const int64_t* dims, const double* const* A_c
 int ttn_apply_f64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks,
                   const double* const* X_cores, const int64_t* X_rks, double* const* Y_cores) {
     return apply_host(d, dims, A_cores, A_rks, X_cores, X_rks, Y_cores, 1, 1, 1);
+}
+// the rectangular form for one train: Y_cores[k] sized out_dims[k] * yr[k] * yr[k + 1], yr[b] = A_rks[b] * X_rks[c(b)]
+int ttn_apply_rect_f64(int64_t M, const int64_t* out_dims, const int64_t* in_dims, const double* const* A_cores, const int64_t* A_rks,
+                       const double* const* X_cores, const int64_t* X_rks, double* const* Y_cores) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    int rc = auto_init(); if (rc) return rc;
+    if (!out_dims || !in_dims || !A_cores || !A_rks || !X_cores || !X_rks || !Y_cores || M < 2) return fail(TTN_ERR_ARG, "bad argument");
+    OwnedRTTO A; OwnedTT x, y;
+    if ((rc = ttn_rtto_create(M, out_dims, in_dims, A_rks, A_cores, &A.h))) return rc;
+    if (A.h->singles.size() != 1) return fail(TTN_ERR_DIMS, "Rectangular TToperator must have exactly one singleton input site");
+    const int s = A.h->singles[0];
+    std::vector<int64_t> xd(M - 1), yr(M + 1);
+    for (int64_t k = 0; k + 1 < M; ++k) xd[k] = in_dims[k < s ? k : k + 1];
+    for (int64_t m = 0; m <= M; ++m) yr[m] = A_rks[m] * X_rks[m > s ? m - 1 : m];
+    if ((rc = host_tt(x, 1, M - 1, xd.data(), X_rks, X_cores, X_rks))) return rc;
+    if ((rc = host_tt(y, 1, M, out_dims, yr.data()))) return rc;
+    if ((rc = ttn_apply_rect(A.h, x.h, y.h))) return rc;
+    return host_result(y.h, false, nullptr, nullptr, Y_cores);
 }
 // a real operator or train stays real on the device; the result is complex
 int ttn_apply_c64(int64_t d, const int64_t* dims, const double* const* A_cores, const int64_t* A_rks, const double* const* X_cores,

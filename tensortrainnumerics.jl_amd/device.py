@@ -1,7 +1,8 @@
 """Device-resident batches of trains (the handle half of include/ttn.h).
 
 ``DeviceTT`` wraps a ``ttn_tt`` handle: ``batch`` independent TT vectors with common dims and a
-per-bond rank capacity, resident in HBM.  ``DeviceTTO`` wraps one TT operator.  Chains such as
+per-bond rank capacity, resident in HBM.  ``DeviceTTO`` wraps one TT operator, ``DeviceRectTTO`` one
+rectangular operator (grid transfer: one more site than the trains it is applied to).  Chains such as
 ``tt_compress!(A*x, r)`` then never cross PCIe.  All ops are asynchronous on the
 library's HIP stream.
 """
@@ -124,6 +125,47 @@ class DeviceTTO:
     def free(self):
         if self.h:
             _lib.lib().ttn_tto_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceRectTTO:
+    """One rectangular TT operator in HBM (``ttn_rtto``, include/ttn_rect.h): cores (n_out, n_in, R_l, R_r), exactly one site with
+    n_in == 1 when it is applied (``apply_rect``).  Float64 only, immutable.  A handle type of its own: ``apply`` and the operator
+    algebra do not take it."""
+
+    def __init__(self, A: TToperator):
+        _lib.ensure_init()
+        cores = [_f(c) for c in A.tto_vec]                    # (a complex core: TypeError)
+        for k, c in enumerate(cores):
+            if c.ndim != 4 or c.shape[2:] != (A.tto_rks[k], A.tto_rks[k + 1]):
+                raise _lib.TTNError(f"DeviceRectTTO: core {k + 1} has shape {c.shape}, its ranks are {A.tto_rks[k]}, {A.tto_rks[k + 1]}")
+        self.N = A.N
+        self.dims = tuple(int(c.shape[0]) for c in cores)      # output dimensions (tto_dims)
+        self.in_dims = tuple(int(c.shape[1]) for c in cores)
+        self.rks = list(A.tto_rks)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_rtto_create(A.N, _i64(self.dims), _i64(self.in_dims), _i64(self.rks), _ptrs(cores), C.byref(h)))
+        self.h = h
+
+    def ranks(self) -> List[int]:
+        """The operator's ranks as the library holds them (ttn_rtto_ranks)."""
+        rks = (C.c_int64 * (self.N + 1))()
+        _lib.check(_lib.lib().ttn_rtto_ranks(self.h, None, None, None, rks))
+        return [int(v) for v in rks]
+
+    def singleton_sites(self) -> List[int]:
+        """1-based sites with a singleton input index; ``apply_rect`` needs exactly one."""
+        return [k + 1 for k, n in enumerate(self.in_dims) if n == 1]
+
+    def free(self):
+        if self.h:
+            _lib.lib().ttn_rtto_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -304,6 +346,29 @@ def split_rank_capacity(dims: Sequence[int], rks: Sequence[int], split_dims: Seq
 def apply(A: DeviceTTO, x: DeviceTT, y: DeviceTT) -> DeviceTT:
     _lib.check(_lib.lib().ttn_apply(A.h, x.h, y.h))
     return y
+
+
+def rect_rank_capacity(A_rks: Sequence[int], singleton_site: int, x_cap: Sequence[int]) -> List[int]:
+    """Rank capacity of y = A * x for a rectangular A: A_rks[b] * x_cap[c(b)] with c(b) = b - [b >= singleton_site] (1-based site) —
+    src/tt_operations.jl:127-130 on capacities."""
+    s = int(singleton_site)
+    return [int(A_rks[b]) * int(x_cap[b - (1 if b >= s else 0)]) for b in range(len(A_rks))]
+
+
+def apply_rect(A: DeviceRectTTO, x: DeviceTT, y: DeviceTT) -> DeviceTT:
+    """y = A * x for a rectangular A on every train of the batch (ttn_apply_rect); y has A.N = x.N + 1 sites and A's output dims."""
+    if not isinstance(A, DeviceRectTTO):
+        raise TypeError(f"apply_rect: expected a DeviceRectTTO, got {type(A).__name__}")
+    _lib.check(_lib.lib().ttn_apply_rect(A.h, x.h, y.h))
+    return y
+
+
+def prolong_compress_(A: DeviceRectTTO, x: DeviceTT, y: DeviceTT, max_bond: int, truncerr: float = 0.0, sweeps: int = 1) -> DeviceTT:
+    """tt_compress!(A * x, max_bond; truncerr, sweeps) for a rectangular A, the coarse-to-fine step of the reference's prolongation
+    examples: apply_rect into y, then the existing rounding in place on y, within its limits (y's capacity must hold what
+    compress_rank_bound says a sweep can reach).  Two launches, no transfer."""
+    apply_rect(A, x, y)
+    return tt_compress_(y, max_bond, truncerr, sweeps)
 
 
 def compress_rank_bound(dims, rks, max_bond: int, sweeps: int = 1, k: int = 0):

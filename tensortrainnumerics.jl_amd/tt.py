@@ -6,6 +6,7 @@ meaning and error behaviour:
 
     TTvector / TToperator                    src/tt_tools.jl:23-29, :48-54
     A * v, A(v)                              src/tt_operations.jl:101-111, :151-157
+    A * v, A rectangular (one more site)     src/tt_operations.jl:116-148
     dot, norm, euclidean_distance            src/tt_operations.jl:239-250, :452-470
     hadamard (⊕)                             src/tt_operations.jl:343-363
     +, add!, scalar *, -, /                  src/tt_operations.jl:10-66, :256-295
@@ -17,8 +18,8 @@ meaning and error behaviour:
 
 Every arithmetic function calls libttn_hip.so; nothing here computes on the CPU.
 Site numbers (``i``, ``k``) are 1-based like the reference.  Cores are numpy arrays of shape
-``(n, r_left, r_right)`` (operator: ``(n, n, R_left, R_right)``) and are handed to the ABI in
-column-major order, exactly the reference's memory layout.
+``(n, r_left, r_right)`` (operator: ``(n, n, R_left, R_right)``; a rectangular operator: ``(n_out, n_in, R_left, R_right)`` with
+``tto_dims`` the output dimensions) and are handed to the ABI in column-major order, exactly the reference's memory layout.
 """
 from __future__ import annotations
 
@@ -109,7 +110,8 @@ class TTvector:
 
 
 class TToperator:
-    """struct TToperator{T,M} — src/tt_tools.jl:48-54."""
+    """struct TToperator{T,M} — src/tt_tools.jl:48-54.  A core may be rectangular, (n_out, n_in, R_l, R_r): ``tto_dims`` are the
+    output dimensions, as in the reference (qtto_constant_prolongation, qtto_linear_prolongation)."""
 
     def __init__(self, N: int, tto_vec: List[np.ndarray], tto_dims: Tuple[int, ...], tto_rks: List[int], tto_ot: List[int]):
         self.N = int(N)
@@ -159,8 +161,11 @@ def r_and_d_to_rks(rks: Sequence[int], dims: Sequence[int], rmax: int = 1024) ->
 
 def apply(A: TToperator, v: TTvector) -> TTvector:
     """*(A::TToperator, v::TTvector) — src/tt_operations.jl:101-111.  Complex x complex and the two mixed forms: the real side stays
-    real on the device, the result is complex."""
-    assert tuple(A.tto_dims) == tuple(v.ttv_dims), "Incompatible dimensions"
+    real on the device, the result is complex.  An operator with another number of sites than v takes the reference's second method
+    (apply_rect)."""
+    if A.N != v.N:
+        return apply_rect(A, v)
+    assert tuple(A.tto_dims) == tuple(v.ttv_dims) and all(c.shape[0] == c.shape[1] for c in A.tto_vec), "Incompatible dimensions"
     d = v.N
     yr = [a * b for a, b in zip(A.tto_rks, v.ttv_rks)]
     ca, cx = _is_cplx(A.tto_vec), _is_cplx(v.ttv_vec)
@@ -170,6 +175,33 @@ def apply(A: TToperator, v: TTvector) -> TTvector:
     flags = (int(ca), int(cx)) if ca or cx else ()
     _lib.check(fn(d, _i64(v.ttv_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(Y), *flags))
     return TTvector(d, Y, v.ttv_dims, yr, [0] * d)
+
+
+def rect_singleton_sites(A: TToperator) -> List[int]:
+    """The 1-based sites of A whose input index has a single value (src/tt_operations.jl:118)."""
+    return [k + 1 for k, c in enumerate(A.tto_vec) if c.shape[1] == 1]
+
+
+def apply_rect(A: TToperator, v: TTvector) -> TTvector:
+    """*(A::TToperator{T,M}, v::TTvector{T,N}), M == N + 1 — src/tt_operations.jl:116-148: A has one more site than v and exactly one
+    site s whose input index is a singleton; that site consumes no input site and the others meet v's sites in order.  With c(b) =
+    b - [b >= s] the input sites left of boundary b: ranks y.rks[b] = A.rks[b] * v.rks[c(b)], regular cores as in apply, the singleton
+    core Y_s[i, a' + R_l nu', a + R_r nu] = A_s[i, 1, a', a] delta(nu', nu); ttv_ot zeros.  One stateless call (ttn_apply_rect_f64).
+    Float64 only."""
+    M, N = A.N, v.N
+    assert M == N + 1, "Rectangular TToperator must have one additional output site"
+    sing = rect_singleton_sites(A)
+    assert len(sing) == 1, "Rectangular TToperator must have exactly one singleton input site"
+    s = sing[0]
+    in_dims = [int(c.shape[1]) for c in A.tto_vec]
+    assert tuple(in_dims[:s - 1] + in_dims[s:]) == tuple(v.ttv_dims), "Incompatible input dimensions"
+    assert v.ttv_rks[-1] == 1, "Input TTvector must have a closed right boundary rank"
+    out_dims = tuple(int(c.shape[0]) for c in A.tto_vec)
+    yr = [A.tto_rks[b] * v.ttv_rks[b - (1 if b >= s else 0)] for b in range(M + 1)]
+    Ac, Xc = [_f(c) for c in A.tto_vec], [_f(c) for c in v.ttv_vec]
+    Y = _empty_cores(out_dims, yr)
+    _lib.check(_lib.lib().ttn_apply_rect_f64(M, _i64(out_dims), _i64(in_dims), _ptrs(Ac), _i64(A.tto_rks), _ptrs(Xc), _i64(v.ttv_rks), _ptrs(Y)))
+    return TTvector(M, Y, out_dims, yr, [0] * M)
 
 
 def apply_compress(A: TToperator, v: TTvector, max_bond: int, truncerr: float = 0.0, sweeps: int = 1) -> TTvector:
