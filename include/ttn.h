@@ -391,7 +391,8 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
 
 /* out[b] = dot(a_b, b_b)      src/tt_operations.jl:239-250 ; out is HOST memory, length batch (synchronises) */
 int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out);
-/* HIP-event time of the KERNEL of the last ttn_dot / ttn_norm / ttn_orthogonalize / ttn_tto_mul call alone (ttn_dot itself goes on to copy the
+/* HIP-event time of the KERNEL of the last ttn_dot / ttn_norm / ttn_orthogonalize / ttn_tto_mul call alone, or of the gather of the last
+ * ttn_tto_decomp_dev (its three table launches and k_dense_gather, without the decomposition) (ttn_dot itself goes on to copy the
  * results to the host and synchronises, which an event pair around the call would include) — what bench.py --op reports.  Its
  * events are its own: such a call inside a ttn_timer_begin / ttn_timer_end region does not move the timer's start. */
 int ttn_last_launch_ms(float* ms);
@@ -551,7 +552,7 @@ int ttn_apply_compress_f64(int64_t d, const int64_t* dims, const double* const* 
  * in element type, and a ComplexF64 handle given to any Float64-only entry point: the linear solvers and eigensolvers,
  * ttn_orthogonalize, ttn_hadamard_ttm, ttn_swap_sites, ttn_ttv_decomp, ttn_scale_batch, the operator algebra (ttn_tto_mul / inner /
  * add / scale / kron / compress / to_tt / from_tt, ttn_tt_outer / diag_tto / kron), ttn_apply_begin / _sweep, ttn_tt_core_extent /
- * _export / _import, ttn_sv_capture, ttn_tt_to_dense, ttn_ttv_decomp_dev, ttn_tt_split_sites, ttn_tt_merge_sites. */
+ * _export / _import, ttn_sv_capture, ttn_tt_to_dense, ttn_tto_to_dense, ttn_ttv_decomp_dev, ttn_tt_split_sites, ttn_tt_merge_sites. */
 int ttn_tt_create_c64(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out);
 int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out);
 int ttn_tt_dtype(ttn_tt_t h, int* cplx);      /* *cplx = 0 Float64, 1 ComplexF64 */
@@ -587,6 +588,12 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * entry point above can be handed one; the type and its five entry points (ttn_rtto_create / free / ranks, ttn_apply_rect,
  * ttn_apply_rect_f64) are declared in ttn_rect.h, which this header includes. */
 #include "ttn_rect.h"
+
+/* ---- the dense bridge for operators (csrc/ttn_grid_kernels.h) -----------------------------------------------------
+ * tto_to_tensor / qtto_to_matrix and tto_decomp on the device: ttn_tto_to_dense writes an operator into a dense array addressed by
+ * two stride tables, ttn_tto_decomp_dev turns such an array into an operator (gather kernel + the hierarchical SVD of
+ * ttn_ttv_decomp_dev).  Both are declared in ttn_dense.h, which this header includes. */
+#include "ttn_dense.h"
 
 #ifdef __cplusplus
 }

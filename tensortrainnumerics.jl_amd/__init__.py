@@ -13,8 +13,8 @@ from .constructors import (Delta, Delta_DN, Delta_ND, Delta_NN, Nabla, fourier_q
 from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_integrate
 from .device import DeviceRectTTO, DeviceTT, DeviceTTO, StreamTimer
 from .grad import apply_pullback, apply_rrule, cores_axpby, cores_dot, dot_pullback, dot_rrule, rayleigh_gradient, rayleigh_value_and_grad
-from .opalg import (concatenate, kron, outer_product, tto_add, tto_compress_, tto_inner, tto_mul, tto_scale, tto_sub, tto_to_ttv,
-                    ttv_to_diag_tto, ttv_to_tto)
+from .opalg import (concatenate, kron, operator_strides, outer_product, qtto_to_matrix, tto_add, tto_compress_, tto_decomp, tto_inner, tto_mul,
+                    tto_scale, tto_sub, tto_to_tensor, tto_to_ttv, ttv_to_diag_tto, ttv_to_tto)
 from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve
 from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_to_array
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp

@@ -172,6 +172,14 @@ RECT_SIGNATURES = {
     "ttn_apply_rect_f64": (C.c_int, [i64, p_i64, p_i64, pp_f64, p_i64, pp_f64, p_i64, pp_f64]),
 }
 
+# the dense bridge for operators of include/ttn_dense.h
+DENSE_SIGNATURES = {
+    "ttn_tto_to_dense": (C.c_int, [handle, p_i64, p_i64, C.c_void_p]),
+    "ttn_tto_decomp_dev": (C.c_int, [i64, p_i64, C.c_void_p, p_i64, p_i64, i64, C.c_double, i64, p_handle]),
+    "ttn_debug_dense_plan": (C.c_int, [p_i64]),
+    "ttn_debug_gather_plan": (C.c_int, [p_i64]),
+}
+
 _lib = None
 
 
@@ -179,7 +187,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile csrc/ttn_api.hip for gfx950 into libttn_hip.so (in-tree).  hipcc cross-compiles
     without a GPU."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
-    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h")]
+    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -202,7 +210,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -56,6 +56,8 @@ hipEvent_t g_launch_ev0 = nullptr, g_launch_ev1 = nullptr;   // the kernels of t
 bool g_have_launch_ms = false;
 size_t g_ortho_state_off = 0;     // byte offset in g_scratch of the state words of the last ttn_orthogonalize (ttn_debug_ortho_state)
 int g_ortho_state_batch = 0;      // its batch; 0: none
+long long g_dense_plan[3] = {-1, 0, 0};   // cut m, TM, TN of the last ttn_tt_to_dense / ttn_tto_to_dense (ttn_debug_dense_plan); m < 0: none
+long long g_gather_plan[4] = {0, 0, 0, 0};   // TI, TO, ld, RO of the gather of the last ttn_tto_decomp_dev (ttn_debug_gather_plan); TI == 0: none
 std::string g_err = "";
 std::vector<hipEvent_t> g_slots;   // ttn_event_record slots
 
@@ -1385,6 +1387,40 @@ int ttn_swap_sites(ttn_tt_t x, int64_t nswaps, const int64_t* swaps, double thre
 }
 
 // ---- ttv_decomp: dense tensors -> trains ----------------------------------------------------------------
+// The size checks of a decomposition into d sites `dims` with rank capacities `cap`, rooted at `index` (1-based), and what they compute:
+// the host-side rank bounds and the worst-case short / long sides of the unfoldings.  The messages name `who`; `hint` says how the caller
+// lowers the capacities.
+static int ttv_decomp_plan(const char* who, const char* hint, int d, const int64_t* dims, const int64_t* cap, int64_t index, std::vector<int64_t>& bnd,
+                           long long& total, long long& pmax, long long& qmax) {
+    if (index < 1 || index > d) return fail(TTN_ERR_ARG, "index must be in 1:d");
+    total = 1;
+    for (int k = 0; k < d; ++k) {
+        total *= dims[k];
+        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": more than 2^27 entries per tensor").c_str());
+    }
+    // worst-case short / long sides of the unfoldings, with the ranks bounded by the handle's capacity
+    bnd.assign(d + 1, 1);
+    pmax = 1; qmax = 1;
+    {
+        long long len = total, rl = 1;
+        for (int i = 0; i < index - 1; ++i) {
+            const long long a = rl * dims[i], bc = len / a;
+            pmax = std::max(pmax, std::min(a, bc)); qmax = std::max(qmax, std::max(a, bc));
+            rl = std::min<long long>(std::min(a, bc), cap[i + 1]);
+            bnd[i + 1] = rl; len = rl * bc;
+        }
+        long long rr = 1;
+        for (int i = d - 1; i > index - 1; --i) {
+            const long long a = dims[i] * rr, rows = len / a;
+            pmax = std::max(pmax, std::min(a, rows)); qmax = std::max(qmax, std::max(a, rows));
+            rr = std::min<long long>(std::min(a, rows), cap[i]);
+            bnd[i] = rr; len = rows * rr;
+        }
+    }
+    if (pmax > 4096) return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": an unfolding has a short side above 4096 (" + hint + ")").c_str());
+    return TTN_OK;
+}
+
 // One body for both entry points: `on_device` says where `tensors` lives.  HOST tensors are copied behind the working buffers; DEVICE
 // tensors are read in place (k_ttv_decomp only reads them: its first step copies train b's tensor into its own working buffer).
 static int ttv_decomp_impl(ttn_tt_t z, const double* tensors, int64_t index, double tol, bool on_device) {
@@ -1393,34 +1429,9 @@ static int ttv_decomp_impl(ttn_tt_t z, const double* tensors, int64_t index, dou
     F64_ONLY(on_device ? "ttn_ttv_decomp_dev" : "ttn_ttv_decomp", {z});
     if (!z || !tensors) return fail(TTN_ERR_ARG, "null argument");
     const int d = z->d;
-    if (index < 1 || index > d) return fail(TTN_ERR_ARG, "index must be in 1:d");
-    long long total = 1, nmax = 1, nmin = 1LL << 40;
-    for (int k = 0; k < d; ++k) {
-        total *= z->dims[k];
-        nmax = std::max<long long>(nmax, z->dims[k]);
-        nmin = std::min<long long>(nmin, z->dims[k]);
-        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_ttv_decomp: more than 2^27 entries per tensor");
-    }
-    // worst-case short / long sides of the unfoldings, with the ranks bounded by the handle's capacity
-    std::vector<int64_t> bnd(d + 1, 1);
-    long long pmax = 1, qmax = 1;
-    {
-        long long len = total, rl = 1;
-        for (int i = 0; i < index - 1; ++i) {
-            const long long a = rl * z->dims[i], bc = len / a;
-            pmax = std::max(pmax, std::min(a, bc)); qmax = std::max(qmax, std::max(a, bc));
-            rl = std::min<long long>(std::min(a, bc), z->cap[i + 1]);
-            bnd[i + 1] = rl; len = rl * bc;
-        }
-        long long rr = 1;
-        for (int i = d - 1; i > index - 1; --i) {
-            const long long a = z->dims[i] * rr, rows = len / a;
-            pmax = std::max(pmax, std::min(a, rows)); qmax = std::max(qmax, std::max(a, rows));
-            rr = std::min<long long>(std::min(a, rows), z->cap[i]);
-            bnd[i] = rr; len = rows * rr;
-        }
-    }
-    if (pmax > 4096) return fail(TTN_ERR_UNSUPPORTED, "ttn_ttv_decomp: an unfolding has a short side above 4096 (lower the handle's rank capacity)");
+    std::vector<int64_t> bnd;
+    long long total, pmax, qmax;
+    { const int rc = ttv_decomp_plan("ttn_ttv_decomp", "lower the handle's rank capacity", d, z->dims.data(), z->cap.data(), index, bnd, total, pmax, qmax); if (rc) return rc; }
     const long long per_scr = QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64;
     const long long per_train = 3 * total + per_scr;
     const int batch = z->batch;
@@ -1642,60 +1653,69 @@ int ttn_tt_merge_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* merge_numbers, int
 
 // ---- train -> dense tensor (csrc/ttn_grid_kernels.h) --------------------------------------------------------------------------------
 // One side's partial products, enqueued step by step: the small steps share single-workgroup launches, a large step gets the grid.
-// Returns the buffer (0 / 1) that holds the last step's result.
-static int dense_chain(ttn_tt_t x, int side, int k_first, int nsteps, double* buf0, double* buf1, long long buf_stride) {
+// Returns the buffer (0 / 1) that holds the last step's result.  `dims` / `bound`: the host copies of the view's dimensions and rank bounds.
+static int dense_chain(const TTDev& tt, const int64_t* dims, const int64_t* bound, int batch, int side, int k_first, int nsteps, double* buf0,
+                       double* buf1, long long buf_stride) {
     DenseChainArgs C;
-    C.tt = x->dev(); C.side = side; C.buf[0] = buf0; C.buf[1] = buf1; C.buf_stride = buf_stride;
+    C.tt = tt; C.side = side; C.buf[0] = buf0; C.buf[1] = buf1; C.buf_stride = buf_stride;
     long long P = 1;
     int g = 0;
     auto site = [&](int s) { return side == 0 ? k_first + s : k_first - s; };
     auto outputs = [&](int s, long long rows_in) {
         const int k = site(s);
-        return rows_in * x->dims[k] * dense_ld(side == 0 ? x->bound[k + 1] : x->bound[k]);
+        return rows_in * dims[k] * dense_ld(side == 0 ? bound[k + 1] : bound[k]);
     };
     while (g < nsteps) {
         const long long big = outputs(g, P);
-        long long Pg = P * x->dims[site(g)];
+        long long Pg = P * dims[site(g)];
         int cnt = 1;
         if (big <= TTN_DENSE_CHAIN_SMALL)
-            while (g + cnt < nsteps && outputs(g + cnt, Pg) <= TTN_DENSE_CHAIN_SMALL) { Pg *= x->dims[site(g + cnt)]; ++cnt; }
+            while (g + cnt < nsteps && outputs(g + cnt, Pg) <= TTN_DENSE_CHAIN_SMALL) { Pg *= dims[site(g + cnt)]; ++cnt; }
         C.k0 = site(g); C.nsteps = cnt; C.par = g & 1;
         const unsigned blocks = big <= TTN_DENSE_CHAIN_SMALL ? 1u : (unsigned)std::min<long long>((big + TTN_DENSE_TB - 1) / TTN_DENSE_TB, 4096);
-        hipLaunchKernelGGL(k_dense_chain, dim3(blocks, (unsigned)x->batch), dim3(TTN_DENSE_TB), 0, g_stream, C);
+        hipLaunchKernelGGL(k_dense_chain, dim3(blocks, (unsigned)batch), dim3(TTN_DENSE_TB), 0, g_stream, C);
         P = Pg;
         g += cnt;
     }
     return (nsteps - 1) & 1;
 }
 
-int ttn_tt_to_dense(ttn_tt_t x, const int64_t* strides, double* d_out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    F64_ONLY("ttn_tt_to_dense", {x});
-    if (!x || !d_out) return fail(TTN_ERR_ARG, "null argument");
-    const int d = x->d, batch = x->batch;
-    if (d > TTN_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: more than 64 sites");
-    if (x->bound[0] != 1 || x->bound[d] != 1) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: the end ranks must be 1");
-    long long total = 1;
-    for (int k = 0; k < d; ++k) {
-        total *= x->dims[k];
-        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: more than 2^27 entries per train");
-        // a tile is made of whole sites: a dimension above the tile size would leave one workgroup per output element
-        if (x->dims[k] > TTN_DENSE_TILE) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: a physical dimension above 4096");
+// A digit of the output address: a factor n of site `site`'s dimension with its output stride; `sub` is its stride inside the site's
+// own index.  A vector site is one digit (sub = 1); operator site k, seen as a site of dimension n_k^2 with merged index x + n_k y, is
+// two: x_k (sub = 1) and y_k (sub = n_k).
+struct DenseDigit {
+    int site, n;
+    long long ostride, sub;
+};
+
+// Digits with n > 1 by ascending stride (a digit with n = 1 has none), checked to be a mixed-radix system: a bijection onto [0, total).
+static bool mixed_radix_order(const std::vector<int>& n, const std::vector<long long>& stride, std::vector<int>& order) {
+    order.clear();
+    for (int j = 0; j < (int)n.size(); ++j) if (n[j] > 1) order.push_back(j);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return stride[a] < stride[b]; });
+    long long expect = 1;
+    for (int j : order) {
+        if (stride[j] != expect) return false;
+        expect *= n[j];
     }
-    // output strides: Julia column-major unless given; they must form a mixed-radix system (a bijection onto [0, total))
-    std::vector<long long> st(d);
-    if (strides) for (int k = 0; k < d; ++k) st[k] = strides[k];
-    else { long long s = 1; for (int k = 0; k < d; ++k) { st[k] = s; s *= x->dims[k]; } }
-    std::vector<int> order;                                  // the sites with n > 1 by ascending stride (a site with n = 1 has no digit)
-    for (int k = 0; k < d; ++k) if (x->dims[k] > 1) order.push_back(k);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return st[a] < st[b]; });
+    return true;
+}
+
+// The body of ttn_tt_to_dense and ttn_tto_to_dense: `tt` is a view of `batch` trains on d sites with host dimensions `dims` (every
+// one <= its digits' product), host rank bounds `bound` and end ranks 1; `digits` lists the digits of every site in train order.  The
+// callers have checked the sizes (total <= 2^27, every digit's n <= TTN_DENSE_TILE, d <= TTN_MAX_D).
+static int dense_export(const char* who, const TTDev& tt, const int64_t* dims, const int64_t* bound, int batch, const std::vector<DenseDigit>& digits,
+                        double* d_out) {
+    const int d = tt.d;
+    long long total = 1;
+    for (int k = 0; k < d; ++k) total *= dims[k];
+    std::vector<int> order;
     {
-        long long expect = 1;
-        for (int k : order) {
-            if (st[k] != expect) return fail(TTN_ERR_ARG, "ttn_tt_to_dense: the strides are not a mixed-radix system (smallest 1, each next = previous * its n)");
-            expect *= x->dims[k];
-        }
+        std::vector<int> dn(digits.size());
+        std::vector<long long> ds(digits.size());
+        for (size_t j = 0; j < digits.size(); ++j) { dn[j] = digits[j].n; ds[j] = digits[j].ostride; }
+        if (!mixed_radix_order(dn, ds, order))
+            return fail(TTN_ERR_ARG, (std::string(who) + ": the strides are not a mixed-radix system (smallest 1, each next = previous * its n)").c_str());
     }
     // the cut m in 0..d-1 (sites 0..m-1 left, m..d-1 right): both partial products about sqrt(total) wide, the first minimiser.  m = 0
     // happens only when no cut inside the train is better, i.e. for one site (or leading sites of dimension 1): the left side is
@@ -1707,30 +1727,30 @@ int ttn_tt_to_dense(ttn_tt_t x, const int64_t* strides, double* d_out) {
         for (int c = 0; c < d; ++c) {
             const long long wide = std::max(p, total / p);
             if (best < 0 || wide < best) { best = wide; m = c; PL = p; }
-            p *= x->dims[c];
+            p *= dims[c];
         }
     }
     const long long PR = total / PL;
-    // the tile: the lowest-stride sites while their dimensions multiply to at most TTN_DENSE_TILE
+    // the tile: the lowest-stride digits while their n multiply to at most TTN_DENSE_TILE
     DenseTabArgs TL, TR;
     memset(&TL, 0, sizeof(TL)); memset(&TR, 0, sizeof(TR));
     int TM = 1, TN = 1;
     {
         bool open = true;
         std::vector<long long> rs(d);                        // stride of site k in the row index of L / the column index of R
-        { long long s = 1; for (int k = 0; k < m; ++k) { rs[k] = s; s *= x->dims[k]; } s = 1; for (int k = m; k < d; ++k) { rs[k] = s; s *= x->dims[k]; } }
-        for (int k : order) {
-            const int n = (int)x->dims[k];
-            if (open && (long long)TM * TN * n <= TTN_DENSE_TILE) { if (k < m) TM *= n; else TN *= n; }
+        { long long s = 1; for (int k = 0; k < m; ++k) { rs[k] = s; s *= dims[k]; } s = 1; for (int k = m; k < d; ++k) { rs[k] = s; s *= dims[k]; } }
+        for (int j : order) {
+            const DenseDigit& g = digits[j];
+            if (open && (long long)TM * TN * g.n <= TTN_DENSE_TILE) { if (g.site < m) TM *= g.n; else TN *= g.n; }
             else open = false;
-            DenseTabArgs& T = k < m ? TL : TR;
-            T.n[T.ns] = n; T.stride[T.ns] = st[k]; T.rstride[T.ns] = rs[k]; ++T.ns;
+            DenseTabArgs& T = g.site < m ? TL : TR;
+            T.n[T.ns] = g.n; T.stride[T.ns] = g.ostride; T.rstride[T.ns] = rs[g.site] * g.sub; ++T.ns;
         }
     }
     // scratch: [unit | offL | offR | rowL | colR | L ping-pong | R ping-pong]
     long long szL = 4, szR = 4;
-    { long long p = 1; for (int k = 0; k < m; ++k) { p *= x->dims[k]; szL = std::max(szL, p * dense_ld(x->bound[k + 1])); } }
-    { long long p = 1; for (int k = d - 1; k >= m; --k) { p *= x->dims[k]; szR = std::max(szR, p * dense_ld(x->bound[k])); } }
+    { long long p = 1; for (int k = 0; k < m; ++k) { p *= dims[k]; szL = std::max(szL, p * dense_ld(bound[k + 1])); } }
+    { long long p = 1; for (int k = d - 1; k >= m; --k) { p *= dims[k]; szR = std::max(szR, p * dense_ld(bound[k])); } }
     auto pad4 = [](long long v) { return (v + 3) & ~3LL; };
     const long long o_unit = 0, o_offL = 4, o_offR = o_offL + pad4(PL), o_rowL = o_offR + pad4(PR), o_colR = o_rowL + pad4((PL + 1) / 2),
                     o_L = o_colR + pad4((PR + 1) / 2), o_R = o_L + 2 * szL * batch, o_end = o_R + 2 * szR * batch;
@@ -1751,17 +1771,95 @@ int ttn_tt_to_dense(ttn_tt_t x, const int64_t* strides, double* d_out) {
     double* Rb = base + o_R;
     DenseArgs A;
     memset(&A, 0, sizeof(A));
-    if (m > 0) { const int w = dense_chain(x, 0, 0, m, Lb, Lb + szL * batch, szL); A.L = w ? Lb + szL * batch : Lb; A.strideL = szL; }
+    if (m > 0) { const int w = dense_chain(tt, dims, bound, batch, 0, 0, m, Lb, Lb + szL * batch, szL); A.L = w ? Lb + szL * batch : Lb; A.strideL = szL; }
     else { A.L = base + o_unit; A.strideL = 0; }
-    { const int w = dense_chain(x, 1, d - 1, d - m, Rb, Rb + szR * batch, szR); A.R = w ? Rb + szR * batch : Rb; A.strideR = szR; }
-    A.rks = x->d_rks; A.d = d; A.m = m;
+    { const int w = dense_chain(tt, dims, bound, batch, 1, d - 1, d - m, Rb, Rb + szR * batch, szR); A.R = w ? Rb + szR * batch : Rb; A.strideR = szR; }
+    A.rks = tt.rks; A.d = d; A.m = m;
     A.offL = TL.off; A.offR = TR.off; A.rowL = TL.idx; A.colR = TR.idx;
     A.tilesL = PL / TM; A.TM = TM; A.TN = TN; A.total = total; A.out = d_out;
+    g_dense_plan[0] = m; g_dense_plan[1] = TM; g_dense_plan[2] = TN;
     const long long seg = (long long)TM * TN;
     A.vec2 = (seg % 2 == 0 && (total % 2 == 0 || batch == 1) && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) ? 1 : 0;
     hipLaunchKernelGGL(k_dense_product, dim3((unsigned)(total / seg), (unsigned)batch), dim3(TTN_DENSE_TB), 0, g_stream, A);
     HIPCHK(hipGetLastError());
     return TTN_OK;
+}
+
+int ttn_tt_to_dense(ttn_tt_t x, const int64_t* strides, double* d_out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    F64_ONLY("ttn_tt_to_dense", {x});
+    if (!x || !d_out) return fail(TTN_ERR_ARG, "null argument");
+    const int d = x->d;
+    if (d > TTN_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: more than 64 sites");
+    if (x->bound[0] != 1 || x->bound[d] != 1) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: the end ranks must be 1");
+    long long total = 1;
+    for (int k = 0; k < d; ++k) {
+        total *= x->dims[k];
+        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: more than 2^27 entries per train");
+        // a tile is made of whole digits: a dimension above the tile size would leave one workgroup per output element
+        if (x->dims[k] > TTN_DENSE_TILE) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_to_dense: a physical dimension above 4096");
+    }
+    // output strides: Julia column-major unless given; one digit per site
+    std::vector<DenseDigit> digits(d);
+    { long long s = 1; for (int k = 0; k < d; ++k) { digits[k] = DenseDigit{k, (int)x->dims[k], strides ? (long long)strides[k] : s, 1}; s *= x->dims[k]; } }
+    return dense_export("ttn_tt_to_dense", x->dev(), x->dims.data(), x->bound.data(), x->batch, digits, d_out);
+}
+
+// ---- operator <-> dense array (include/ttn_dense.h) -----------------------------------------------------------------------------------
+// The two stride tables of an operator's dense array, or the reference's [x_1..x_d, y_1..y_d] column-major array when both are null.
+static void operator_strides(int d, const int64_t* dims, const int64_t* xstrides, const int64_t* ystrides, std::vector<long long>& xs, std::vector<long long>& ys) {
+    xs.resize(d); ys.resize(d);
+    long long N = 1;
+    for (int k = 0; k < d; ++k) N *= dims[k];
+    long long s = 1;
+    for (int k = 0; k < d; ++k) {
+        xs[k] = xstrides ? (long long)xstrides[k] : s;
+        ys[k] = ystrides ? (long long)ystrides[k] : N * s;
+        s *= dims[k];
+    }
+}
+
+int ttn_debug_dense_plan(int64_t* out3) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!out3 || g_dense_plan[0] < 0) return fail(TTN_ERR_ARG, "ttn_debug_dense_plan: no ttn_tt_to_dense / ttn_tto_to_dense launch yet");
+    for (int i = 0; i < 3; ++i) out3[i] = g_dense_plan[i];
+    return TTN_OK;
+}
+
+int ttn_debug_gather_plan(int64_t* out4) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!out4 || g_gather_plan[0] == 0) return fail(TTN_ERR_ARG, "ttn_debug_gather_plan: no ttn_tto_decomp_dev launch yet");
+    for (int i = 0; i < 4; ++i) out4[i] = g_gather_plan[i];
+    return TTN_OK;
+}
+
+int ttn_tto_to_dense(ttn_tto_t A, const int64_t* xstrides, const int64_t* ystrides, double* d_out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    F64_ONLY("ttn_tto_to_dense", {}, {A});
+    if (!A || !d_out) return fail(TTN_ERR_ARG, "ttn_tto_to_dense: null argument");
+    if ((xstrides == nullptr) != (ystrides == nullptr)) return fail(TTN_ERR_ARG, "ttn_tto_to_dense: xstrides and ystrides must both be given or both be null");
+    const int d = A->d;
+    if (d > TTN_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_to_dense: more than 64 sites");
+    if (A->rks[0] != 1 || A->rks[d] != 1) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_to_dense: the end ranks must be 1");
+    std::vector<int64_t> dims2(d);
+    long long total = 1;
+    for (int k = 0; k < d; ++k) {
+        // the limit of a tile holds per digit: n_k^2 may exceed it, the tile then splits the site between x_k and y_k
+        if (A->dims[k] > TTN_DENSE_TILE) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_to_dense: a physical dimension above 4096");
+        dims2[k] = A->dims[k] * A->dims[k];
+        total *= dims2[k];
+        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_to_dense: more than 2^27 entries");
+    }
+    std::vector<long long> xs, ys;
+    operator_strides(d, A->dims.data(), xstrides, ystrides, xs, ys);
+    std::vector<DenseDigit> digits;
+    for (int k = 0; k < d; ++k) {
+        digits.push_back(DenseDigit{k, (int)A->dims[k], xs[k], 1});
+        digits.push_back(DenseDigit{k, (int)A->dims[k], ys[k], (long long)A->dims[k]});
+    }
+    return dense_export("ttn_tto_to_dense", A->vdev(), dims2.data(), A->rks.data(), 1, digits, d_out);
 }
 
 int ttn_qtt_grid_points(int64_t n_dims, int64_t bits, int interleaved, double a, double b, int64_t first, int64_t count, double* d_X) {
@@ -2439,7 +2537,7 @@ int ttn_last_launch_ms(float* ms) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!ms) return fail(TTN_ERR_ARG, "null pointer");
-    if (!g_have_launch_ms) return fail(TTN_ERR_ARG, "ttn_last_launch_ms: no ttn_dot / ttn_orthogonalize launch yet");
+    if (!g_have_launch_ms) return fail(TTN_ERR_ARG, "ttn_last_launch_ms: no ttn_dot / ttn_norm / ttn_orthogonalize / ttn_tto_mul / ttn_tto_decomp_dev launch yet");
     HIPCHK(hipEventSynchronize(g_launch_ev1));
     HIPCHK(hipEventElapsedTime(ms, g_launch_ev0, g_launch_ev1));
     return TTN_OK;
@@ -3765,6 +3863,153 @@ int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t swe
     if ((rc = ttn_tto_to_tt(A, t.h))) return rc;
     if ((rc = ttn_compress(t.h, max_bond, truncerr, sweeps))) return rc;
     if ((rc = ttn_compress_status(t.h, nullptr))) return rc;
+    return ttn_tto_from_tt(t.h, 0, out);
+}
+
+// tto_decomp(tensor; index) from a dense array on the device (include/ttn_dense.h): k_dense_gather permutes the array into the layout
+// (n_1^2, ..., n_d^2) of tto_decomp's reshape(permutedims(...)) in a temporary allocation, ttv_decomp runs on a working train that is
+// read and cleared of its status here (a failure is this call's return value, as in ttn_tto_compress), then from_tt.
+int ttn_tto_decomp_dev(int64_t d64, const int64_t* dims, const double* d_tensor, const int64_t* xstrides, const int64_t* ystrides, int64_t index,
+                       double tol, int64_t rank_cap, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    const char* who = "ttn_tto_decomp_dev";
+    if (!dims || !d_tensor || !out) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: null argument");
+    if (d64 < 1 || d64 > TTN_MAX_D) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: the number of sites must be in 1:64");
+    const int d = (int)d64;
+    if ((xstrides == nullptr) != (ystrides == nullptr)) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: xstrides and ystrides must both be given or both be null");
+    if (index < 1 || index > d) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: index must be in 1:d");
+    if (!(tol >= 0.0)) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: tol must be >= 0");
+    if (rank_cap < 1) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: rank_cap must be >= 1");
+    std::vector<int64_t> dims2(d);
+    long long total = 1;
+    for (int k = 0; k < d; ++k) {
+        if (dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: dims must be >= 1");
+        if (dims[k] > TTN_DENSE_TILE) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_decomp_dev: a physical dimension above 4096");
+        dims2[k] = dims[k] * dims[k];
+        total *= dims2[k];
+        if (total > (1LL << 27)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_decomp_dev: more than 2^27 entries");
+    }
+    // the digits x_1, y_1, x_2, y_2, ... with their strides in the caller's array and in the array the decomposition reads
+    std::vector<long long> xs, ys;
+    operator_strides(d, dims, xstrides, ystrides, xs, ys);
+    std::vector<int> dn(2 * d);
+    std::vector<long long> din(2 * d), dout(2 * d);
+    { long long s = 1; for (int k = 0; k < d; ++k) { dn[2 * k] = dn[2 * k + 1] = (int)dims[k]; din[2 * k] = xs[k]; din[2 * k + 1] = ys[k];
+                                                      dout[2 * k] = s; dout[2 * k + 1] = s * dims[k]; s *= dims2[k]; } }
+    std::vector<int> iord, oord;
+    if (!mixed_radix_order(dn, din, iord)) return fail(TTN_ERR_ARG, "ttn_tto_decomp_dev: the strides are not a mixed-radix system (smallest 1, each next = previous * its n)");
+    mixed_radix_order(dn, dout, oord);
+    // capacity of the working train, and the limits of the decomposition under it
+    std::vector<int64_t> cap(d + 1, 1), bnd;
+    { long long p = 1; for (int k = 1; k < d; ++k) { p *= dims2[k - 1]; cap[k] = std::min<long long>(std::min<long long>(p, total / p), rank_cap); } }
+    long long tot2, pmax, qmax;
+    int rc;
+    if ((rc = ttv_decomp_plan(who, "lower rank_cap", d, dims2.data(), cap.data(), index, bnd, tot2, pmax, qmax))) return rc;
+    if (iord.size() > TTN_GATHER_DIGITS) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_decomp_dev: too many digits");     // (2^27 entries leave at most 27)
+    // ---- the tile of the gather ----
+    std::vector<char> in_tile(2 * d, 0);
+    std::vector<int> SI, SO;
+    long long TI = 1, TO = 1;
+    size_t ip = 0;
+    while (ip < iord.size() && (TI < 64 || SI.empty()) && TI * dn[iord[ip]] <= TTN_DENSE_TILE) { TI *= dn[iord[ip]]; in_tile[iord[ip]] = 1; SI.push_back(iord[ip]); ++ip; }
+    for (int j : oord) {
+        if (in_tile[j]) continue;
+        if (TI * TO * dn[j] > TTN_DENSE_TILE) break;
+        TO *= dn[j]; in_tile[j] = 2; SO.push_back(j);
+    }
+    while (ip < iord.size() && !in_tile[iord[ip]] && TI * TO * dn[iord[ip]] <= TTN_DENSE_TILE) { TI *= dn[iord[ip]]; in_tile[iord[ip]] = 1; SI.push_back(iord[ip]); ++ip; }
+    // eh enumerates SO in output order (as collected): the digits that vary inside a half wave of the store phase then get the small
+    // weights, and the pad below can spread them over the banks
+    const int nt = (int)(TI * TO);
+    // LDS position strides for ld = TI + pad: an SI digit keeps its input stride, an SO digit gets ld times its weight in eh
+    auto lds_strides = [&](long long ld, std::vector<long long>& ls) {
+        ls.assign(2 * d, 0);
+        for (int j : SI) ls[j] = din[j];
+        long long w = 1;
+        for (int j : SO) { ls[j] = ld * w; w *= dn[j]; }
+    };
+    // the tile's digits in output order: the leading ones that follow each other without a gap span runs of RO contiguous outputs
+    std::vector<int> lo, hi;
+    long long RO = 1;
+    { bool run = true; for (int j : oord) { if (!in_tile[j]) { run = false; continue; } if (run) { lo.push_back(j); RO *= dn[j]; } else hi.push_back(j); } }
+    const long long FH = nt / RO;
+    // the pad: the fewest bank conflicts of the store phase's LDS reads (8-byte reads: 32 banks of doubles, lanes in halves of 32), over
+    // the first 256 elements; ties go to the smaller pad
+    long long ld = TI;
+    {
+        long long best = -1;
+        std::vector<long long> ls;
+        for (long long pad = 0; pad <= 32 && TO * (TI + pad) <= TTN_GATHER_LDS; ++pad) {
+            lds_strides(TI + pad, ls);
+            long long cost = 0;
+            for (int f0 = 0; f0 < std::min(nt, 256); f0 += 32) {
+                int cnt[32] = {0};
+                for (int f = f0; f < std::min(nt, f0 + 32); ++f) {
+                    long long rem = f, pos = 0;
+                    for (int j : lo) { pos += (rem % dn[j]) * ls[j]; rem /= dn[j]; }
+                    for (int j : hi) { pos += (rem % dn[j]) * ls[j]; rem /= dn[j]; }
+                    ++cnt[pos & 31];
+                }
+                int worst = 0;
+                for (int c : cnt) worst = std::max(worst, c);
+                cost += worst;
+            }
+            if (best < 0 || cost < best) { best = cost; ld = TI + pad; }
+            if (TO == 1) break;                                 // one row: the pad changes nothing
+        }
+        // diagnostic knob (tools/diag_dense_operator.py measures what the search is worth): TTN_GATHER_PAD = a fixed pad instead
+        if (const char* e = getenv("TTN_GATHER_PAD")) { const long long pad = atoll(e); if (pad >= 0 && pad <= 32 && TO * (TI + pad) <= TTN_GATHER_LDS) ld = TI + pad; }
+    }
+    std::vector<long long> ls;
+    lds_strides(ld, ls);
+    // ---- temporary device memory: [permuted array | inHi | outHi | posLo | posHi (+ the off / idx halves k_dense_tables also fills)] ----
+    struct Temp { void* p = nullptr; ~Temp() { if (p) { hipStreamSynchronize(g_stream); hipFree(p); } } } tmp;
+    auto pad2 = [](long long v) { return (v + 1) & ~1LL; };
+    const long long o_inHi = pad2(total), o_inIdx = o_inHi + TO, o_loOff = o_inIdx + pad2((TO + 1) / 2), o_loIdx = o_loOff + RO,
+                    o_hiOff = o_loIdx + pad2((RO + 1) / 2), o_hiIdx = o_hiOff + FH, o_end = o_hiIdx + pad2((FH + 1) / 2);
+    if (hipMalloc(&tmp.p, sizeof(double) * (size_t)o_end) != hipSuccess) {
+        (void)hipGetLastError();
+        tmp.p = nullptr;
+        return fail(TTN_ERR_CAPACITY, "ttn_tto_decomp_dev: the permuted array does not fit in device memory");
+    }
+    double* base = static_cast<double*>(tmp.p);
+    auto fill_table = [&](const std::vector<int>& dg, const std::vector<long long>& stride, long long count, long long o_off, long long o_idx) {
+        DenseTabArgs T;
+        memset(&T, 0, sizeof(T));
+        for (int j : dg) { T.n[T.ns] = dn[j]; T.stride[T.ns] = stride[j]; T.rstride[T.ns] = ls[j]; ++T.ns; }
+        T.count = count; T.off = reinterpret_cast<long long*>(base + o_off); T.idx = reinterpret_cast<int*>(base + o_idx);
+        const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((count + TTN_DENSE_TB - 1) / TTN_DENSE_TB, 1024));
+        hipLaunchKernelGGL(k_dense_tables, dim3(blocks), dim3(TTN_DENSE_TB), 0, g_stream, T);
+    };
+    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
+    fill_table(SO, din, TO, o_inHi, o_inIdx);
+    fill_table(lo, dout, RO, o_loOff, o_loIdx);
+    fill_table(hi, dout, FH, o_hiOff, o_hiIdx);
+    GatherArgs G;
+    memset(&G, 0, sizeof(G));
+    G.in = d_tensor; G.out = base;
+    G.TI = (int)TI; G.TO = (int)TO; G.ld = (int)ld; G.RO = (int)RO; G.nt = nt;
+    g_gather_plan[0] = TI; g_gather_plan[1] = TO; g_gather_plan[2] = ld; g_gather_plan[3] = RO;
+    G.inHi = reinterpret_cast<const long long*>(base + o_inHi);
+    G.posLo = reinterpret_cast<const int*>(base + o_loIdx);
+    G.outHi = reinterpret_cast<const long long*>(base + o_hiOff);
+    G.posHi = reinterpret_cast<const int*>(base + o_hiIdx);
+    for (int j : iord) {
+        if (in_tile[j]) continue;
+        G.on[G.nouter] = dn[j]; G.oin[G.nouter] = din[j]; G.oout[G.nouter] = dout[j]; ++G.nouter;
+    }
+    hipLaunchKernelGGL(k_dense_gather, dim3((unsigned)(total / nt)), dim3(TTN_DENSE_TB), 0, g_stream, G);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));       // ttn_last_launch_ms: the gather (its tables and the kernel) without the decomposition
+    g_have_launch_ms = true;
+    // ---- the decomposition on a working train, then the operator ----
+    OwnedTT t;
+    if ((rc = ttn_tt_create(d, dims2.data(), cap.data(), 1, &t.h))) return rc;
+    if ((rc = ttn_ttv_decomp_dev(t.h, base, index, tol))) return rc;
+    unsigned seen = 0;
+    if ((rc = take_status(t.h, seen))) return rc;
+    if ((rc = status_error(seen, who))) return rc;
     return ttn_tto_from_tt(t.h, 0, out);
 }
 

@@ -165,6 +165,59 @@ __global__ void __launch_bounds__(TTN_DENSE_TB) k_dense_product(DenseArgs A) {
     }
 }
 
+// ---- dense -> dense permutation of digits (ttn_tto_decomp_dev) ----------------------------------------------------------------------
+// out[sum_j v_j ostride_j] = in[sum_j v_j istride_j] over the digits (n_j, istride_j, ostride_j), both stride sets mixed-radix systems
+// of the same digits.  One workgroup moves one tile through LDS.  The tile is spanned by
+//   SI: the fastest INPUT digits (their product TI, a contiguous run of the input), and
+//   SO: the fastest OUTPUT digits not in SI (their product TO),
+// with TI * TO <= TTN_DENSE_TILE; every other digit is enumerated by blockIdx.x.  Element e = eh * TI + el of the tile in input order
+// (el over SI, eh over SO in output order) is loaded from in[baseI + el + inHi[eh]] — consecutive lanes, consecutive addresses — to
+// tile[el + ld * eh].  In output order the tile's leading digits (in SI or SO alike) form contiguous runs of RO outputs: element
+// f = fh * RO + fl is stored to out[baseO + fl + outHi[fh]] from tile[posLo[fl] + posHi[fh]], again consecutive lanes on consecutive
+// addresses, every output exactly once.  The tables are filled by k_dense_tables from the digit lists (off: global offset, idx: LDS
+// position); ld = TI + a pad the host picks so that the 32 lanes of a half wave read distinct banks (8-byte reads: 32 banks).
+#define TTN_GATHER_LDS 5120          // doubles: TTN_DENSE_TILE plus room for the padded leading dimension (40 KB)
+#define TTN_GATHER_DIGITS 32         // digits with n > 1: total <= 2^27 leaves at most 27
+
+struct GatherArgs {
+    const double* in;
+    double* out;
+    int TI, TO, ld, RO, nt;          // nt = TI * TO
+    const long long* inHi;           // [TO] input offset of eh
+    const int* posLo;                // [RO] LDS position of fl
+    const long long* outHi;          // [nt / RO] output offset of fh
+    const int* posHi;                // [nt / RO] LDS position of fh
+    int nouter;                      // the digits outside the tile
+    int on[TTN_GATHER_DIGITS];
+    long long oin[TTN_GATHER_DIGITS], oout[TTN_GATHER_DIGITS];
+};
+
+__global__ void __launch_bounds__(TTN_DENSE_TB) k_dense_gather(GatherArgs G) {
+    __shared__ double tile[TTN_GATHER_LDS];
+    const int tid = threadIdx.x;
+    long long baseI = 0, baseO = 0;
+    {
+        long long rem = blockIdx.x;
+        for (int j = 0; j < G.nouter; ++j) {
+            const long long dg = rem % G.on[j];
+            rem /= G.on[j];
+            baseI += dg * G.oin[j];
+            baseO += dg * G.oout[j];
+        }
+    }
+    const double* src = G.in + baseI;
+    for (int e = tid; e < G.nt; e += TTN_DENSE_TB) {
+        const int eh = e / G.TI, el = e - eh * G.TI;
+        tile[el + G.ld * eh] = src[el + G.inHi[eh]];
+    }
+    __syncthreads();
+    double* dst = G.out + baseO;
+    for (int f = tid; f < G.nt; f += TTN_DENSE_TB) {
+        const int fh = f / G.RO, fl = f - fh * G.RO;
+        dst[fl + G.outHi[fh]] = tile[G.posLo[fl] + G.posHi[fh]];
+    }
+}
+
 // ---- QTT grid coordinates ---------------------------------------------------------------------------------------------------------
 // Entry e of the (2, ..., 2) tensor (site 1 fastest) has bit (e >> s) & 1 at site s; the bit -> (dim, level) rule of
 // src/qtt_tools.jl:820-829 gives the grid index g per dimension.  coord = a + g * h with one rounded multiply and one rounded add

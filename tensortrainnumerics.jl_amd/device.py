@@ -114,6 +114,54 @@ class DeviceTTO:
         _lib.check(_lib.lib().ttn_tto_compress(self.h, int(min(max_bond, 2 ** 62)), float(truncerr), int(sweeps), C.byref(h)))
         return DeviceTTO._adopt(h)
 
+    # operator <-> dense array (include/ttn_dense.h)
+    def to_dense(self, layout="tensor"):
+        """The operator as a dense array on the device: a 1-D float64 torch tensor of prod(dims)^2 entries.  ``layout="tensor"`` is
+        tto_to_tensor's array (column-major over [x_1..x_d, y_1..y_d]), ``"matrix"`` is qtto_to_matrix's column-major matrix (site 1 most
+        significant), or a ``(xstrides, ystrides)`` pair (opalg.operator_strides).  Asynchronous like ``DeviceTT.to_dense``."""
+        from .opalg import operator_strides
+        from .tdvp import _dev
+        torch, stream = _dev()
+        xs, ys = operator_strides(self.dims, layout)
+        total = 1
+        for n in self.dims:
+            total *= n * n
+        caller = torch.cuda.current_stream()
+        with torch.cuda.stream(stream):
+            out = torch.empty((total,), dtype=torch.float64, device="cuda")
+            _lib.check(_lib.lib().ttn_tto_to_dense(self.h, _i64(xs), _i64(ys), C.c_void_p(out.data_ptr())))
+        if caller != stream:
+            caller.wait_stream(stream)
+            out.record_stream(caller)
+        return out
+
+    @classmethod
+    def from_dense(cls, d_tensor, dims: Sequence[int], index: int = 1, tol: float = 1.0e-12, layout="tensor", rank_cap: int = 1024) -> "DeviceTTO":
+        """tto_decomp of a dense array on the device — src/tt_tools.jl:338-362: ``d_tensor`` is a float64 CUDA tensor of prod(dims)^2
+        entries in ``layout`` (see ``to_dense``), only read; ranks above ``rank_cap`` raise (TTN_ERR_CAPACITY).  Synchronises."""
+        from .opalg import operator_strides
+        from .tdvp import _dev
+        _lib.ensure_init()
+        torch, stream = _dev()
+        dims = [int(n) for n in dims]
+        xs, ys = operator_strides(dims, layout)
+        total = 1
+        for n in dims:
+            total *= n * n
+        if not isinstance(d_tensor, torch.Tensor) or not d_tensor.is_cuda:
+            raise _lib.TTNError("from_dense: expected a CUDA tensor (upload a host array first)")
+        if d_tensor.is_complex():
+            raise TypeError("from_dense: complex tensors are not supported (Float64 only)")
+        if d_tensor.dtype != torch.float64 or not d_tensor.is_contiguous():
+            raise _lib.TTNError("from_dense: expected a contiguous float64 tensor")
+        if d_tensor.numel() != total:
+            raise _lib.TTNError(f"from_dense: {d_tensor.numel()} entries for dims {tuple(dims)} (need {total})")
+        stream.wait_stream(torch.cuda.current_stream())
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tto_decomp_dev(len(dims), _i64(dims), C.c_void_p(d_tensor.data_ptr()), _i64(xs), _i64(ys), int(index), float(tol),
+                                                 int(min(rank_cap, 2 ** 62)), C.byref(h)))
+        return cls._adopt(h)
+
     def ranks(self) -> List[int]:
         return list(self.rks)
 

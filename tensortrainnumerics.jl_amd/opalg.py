@@ -7,10 +7,14 @@
     concatenate                              src/tt_tools.jl:708-735
     outer_product, ttv_to_diag_tto           src/tt_operations.jl:297-338
     tto_to_ttv, ttv_to_tto                   src/tt_tools.jl:296-333
+    tto_to_tensor, tto_decomp                src/tt_tools.jl:338-392
+    qtto_to_matrix                           src/qtt_tools.jl:180-188
 
 Everything that computes uploads its operands, runs the device operation (device.DeviceTTO / DeviceTT, csrc/ttn_opalg_kernels.h) and
 downloads the result; a chain of several operations should stay on ``DeviceTTO`` handles instead.  kron, concatenate and the two
-conversions only regroup cores (the reference's are ``vcat`` and ``reshape``), so they are host code.  Float64 only.
+conversions only regroup cores (the reference's are ``vcat`` and ``reshape``), so they are host code.  The dense bridge
+(tto_to_tensor, qtto_to_matrix, tto_decomp) is one upload, one device call (ttn_tto_to_dense / ttn_tto_decomp_dev) and one download.
+Float64 only.
 """
 from __future__ import annotations
 
@@ -139,3 +143,93 @@ def ttv_to_tto(x: TTvector) -> TToperator:
     assert tuple(n * n for n in dims) == tuple(x.ttv_dims), "DimensionMismatch"
     vec = [np.reshape(np.asfortranarray(c), (dims[k], dims[k], x.ttv_rks[k], x.ttv_rks[k + 1]), order="F") for k, c in enumerate(x.ttv_vec)]
     return TToperator(x.N, vec, dims, list(x.ttv_rks), list(x.ttv_ot))
+
+
+# ---- the dense bridge: operator <-> dense array (include/ttn_dense.h) -------------------------------------------------------------------
+def operator_strides(dims, layout="tensor"):
+    """(xstrides, ystrides) of an operator's dense array: entry (x_1..x_d ; y_1..y_d), 0-based, lies at
+    sum_k x_k xstrides[k] + y_k ystrides[k].  ``"tensor"``: tto_to_tensor's array, column-major over [x_1..x_d, y_1..y_d].
+    ``"matrix"``: qtto_to_matrix's matrix, column-major N x N with row = sum_k x_k prod_{j>k} n_j (site 1 most significant) and the
+    same for the column.  A pair of tables is checked (the digits must form a mixed-radix system) and returned as lists."""
+    dims = [int(n) for n in dims]
+    d = len(dims)
+    N = math.prod(dims)
+    if isinstance(layout, str):
+        if layout == "tensor":
+            xs = [math.prod(dims[:k]) for k in range(d)]
+        elif layout == "matrix":
+            xs = [math.prod(dims[k + 1:]) for k in range(d)]
+        else:
+            raise ValueError(f"operator_strides: layout must be 'tensor', 'matrix' or a (xstrides, ystrides) pair, got {layout!r}")
+        return xs, [N * s for s in xs]
+    try:
+        xs, ys = layout
+        xs, ys = [int(v) for v in xs], [int(v) for v in ys]
+    except (TypeError, ValueError):
+        raise ValueError("operator_strides: layout must be 'tensor', 'matrix' or a (xstrides, ystrides) pair") from None
+    if len(xs) != d or len(ys) != d:
+        raise ValueError(f"operator_strides: {len(xs)} and {len(ys)} strides for {d} sites")
+    expect = 1
+    for stride, n in sorted((s, n) for s, n in zip(xs + ys, dims + dims) if n > 1):
+        if stride != expect:
+            raise ValueError("operator_strides: the strides are not a mixed-radix system (smallest 1, each next = previous * its n)")
+        expect *= n
+    return xs, ys
+
+
+def _need_square(A, who):
+    _need(A, TToperator, who)
+    for k, c in enumerate(A.tto_vec):
+        if np.ndim(c) != 4 or c.shape[0] != c.shape[1]:
+            raise TypeError(f"{who}: core {k + 1} has shape {np.shape(c)}; a rectangular operator has no dense form here (square cores only)")
+
+
+def tto_to_tensor(A: TToperator) -> np.ndarray:
+    """tto_to_tensor(A) — src/tt_tools.jl:375-392: the array of shape dims + dims, contracted on the device (ttn_tto_to_dense)."""
+    from .device import DeviceTTO
+    _need_square(A, "tto_to_tensor")
+    h = DeviceTTO(A)
+    try:
+        return np.reshape(h.to_dense("tensor").cpu().numpy(), tuple(A.tto_dims) * 2, order="F")
+    finally:
+        h.free()
+
+
+def qtto_to_matrix(A: TToperator, device: bool = False):
+    """qtto_to_matrix(A) — src/qtt_tools.jl:180-188: the (2^d, 2^d) matrix with site 1 the most significant bit of row and column.
+    One ttn_tto_to_dense in the matrix layout; ``device=True`` returns the torch tensor (a view with the same logical indexing)."""
+    from .device import DeviceTTO
+    _need_square(A, "qtto_to_matrix")
+    assert all(n == 2 for n in A.tto_dims), "qtto_to_matrix: all dimensions must be 2"
+    N = 2 ** A.N
+    h = DeviceTTO(A)
+    try:
+        flat = h.to_dense("matrix")
+        if device:
+            return flat.reshape(N, N).T                      # column-major in memory
+        return np.reshape(flat.cpu().numpy(), (N, N), order="F")
+    finally:
+        h.free()
+
+
+def tto_decomp(tensor, index: int = 1, tol: float = 1.0e-12, rank_cap: int = 1024) -> TToperator:
+    """tto_decomp(tensor; index) — src/tt_tools.jl:338-362, with ttv_decomp's absolute threshold ``tol`` exposed: the TT operator of the
+    array tensor[x_1..x_d, y_1..y_d], decomposed on the device (ttn_tto_decomp_dev) with the root at site ``index``."""
+    from .device import DeviceTTO
+    from .tdvp import _dev
+    t = np.asarray(tensor)
+    if np.iscomplexobj(t):
+        raise TypeError("tto_decomp: complex tensors are not supported (Float64 only)")
+    assert t.ndim >= 2 and t.ndim % 2 == 0, "tto_decomp: the tensor needs an even number of axes [x_1..x_d, y_1..y_d]"
+    d = t.ndim // 2
+    assert t.shape[:d] == t.shape[d:], "tto_decomp: the x and y dimensions differ"
+    assert 1 <= int(index) <= d, "tto_decomp: index must be in 1:d"
+    torch, stream = _dev()
+    flat = np.ascontiguousarray(np.ravel(np.asarray(t, dtype=np.float64), order="F"))
+    with torch.cuda.stream(stream):
+        dt = torch.from_numpy(flat).to("cuda")
+    h = DeviceTTO.from_dense(dt, t.shape[:d], index=index, tol=tol, layout="tensor", rank_cap=rank_cap)
+    try:
+        return h.download()
+    finally:
+        h.free()
