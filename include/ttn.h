@@ -595,6 +595,11 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * ttn_ttv_decomp_dev).  Both are declared in ttn_dense.h, which this header includes. */
 #include "ttn_dense.h"
 
+/* ---- time steps (csrc/ttn_step_kernels.h) --------------------------------------------------------------------------
+ * What the steppers of src/solvers/euler.jl do around their linear solve: ttn_apply_axpby, z = alpha x + beta (A y) in one streaming
+ * launch, and ttn_tt_increase_ranks, the public increase_ranks.  Both are declared in ttn_step.h, which this header includes. */
+#include "ttn_step.h"
+
 #ifdef __cplusplus
 }
 #endif

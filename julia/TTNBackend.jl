@@ -582,4 +582,52 @@ function _tto_from_tt(hx::Ptr{Cvoid}, b::Integer = 0)
     return out[]
 end
 
+# ---- time steps (include/ttn_step.h; DESIGN.md §4.23) ------------------------------------------------------------------------------
+# Written against include/ttn_step.h and not executed (no Julia on the build machines).
+# download train 0 of a result handle as a TTvector and release the handle
+function _ttv_down(h::Ptr{Cvoid}, dims::NTuple{N, Int64}) where {N}
+    rks, ot = zeros(Int64, N + 1), zeros(Int64, N)
+    _chk(ccall((:ttn_tt_ranks, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), h, 0, rks, ot))
+    x = zeros_tt(Float64, dims, rks)
+    px = _ptrs(x.ttv_vec)
+    GC.@preserve x px _chk(ccall((:ttn_tt_download, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Ptr{Float64}}), h, 0, px))
+    x.ttv_ot .= ot
+    _ttv_free(h)
+    return x
+end
+
+# alpha * x + beta * (A * y) in one launch: the Crank-Nicolson right-hand side (I + (h/2) A) u is apply_axpby(1.0, u, h / 2, A, u), a
+# residual M * sol - u_prev is apply_axpby(-1.0, u_prev, 1.0, M, sol).  Bit for bit alpha * x + beta * (A * y) as the reference's own
+# operators evaluate it (scalar * first, then +).
+function apply_axpby(alpha::Float64, x::TTvector{Float64, N}, beta::Float64, A::TToperator{Float64, N}, y::TTvector{Float64, N}) where {N}
+    hA, hx, hy = _tto_up(A), _ttv_up(x), _ttv_up(y)
+    cap = vcat(1, x.ttv_rks[2:N] .+ A.tto_rks[2:N] .* y.ttv_rks[2:N], 1)
+    hz = Ref{Ptr{Cvoid}}(C_NULL)
+    try
+        _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, _dims(x.ttv_dims), cap, 1, hz))
+        _chk(ccall((:ttn_apply_axpby, LIB), Cint, (Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            Float64[alpha], hx, Float64[beta], hA, hy, hz[]))
+        return _ttv_down(hz[], x.ttv_dims)
+    finally
+        _tto_free(hA); _ttv_free(hx); _ttv_free(hy)
+    end
+end
+
+# increase_ranks(x, max_bond; rks, noise) (src/tt_tools.jl:480-490) on the device; the noise blocks come from the library's seeded
+# splitmix64 stream (`seed`), not from Julia's RNG
+function increase_ranks_device(x::TTvector{Float64, N}, max_bond::Int; rks = vcat(1, max_bond * ones(Int, N - 1), 1), noise::Float64 = 0.0,
+        seed::Integer = 0) where {N}
+    @assert(max_bond > maximum(x.ttv_rks), "New bond dimension too low")
+    new = Int64.(r_and_d_to_rks(rks, x.ttv_dims; rmax = max_bond))
+    hx = _ttv_up(x)
+    hy = Ref{Ptr{Cvoid}}(C_NULL)
+    try
+        _chk(ccall((:ttn_tt_create, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}), N, _dims(x.ttv_dims), new, 1, hy))
+        _chk(ccall((:ttn_tt_increase_ranks, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Float64, UInt64, Ptr{Cvoid}), hx, new, noise, UInt64(seed), hy[]))
+        return _ttv_down(hy[], x.ttv_dims)
+    finally
+        _ttv_free(hx)
+    end
+end
+
 end # module

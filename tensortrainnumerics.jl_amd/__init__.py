@@ -15,10 +15,11 @@ from .device import DeviceRectTTO, DeviceTT, DeviceTTO, StreamTimer
 from .grad import apply_pullback, apply_rrule, cores_axpby, cores_dot, dot_pullback, dot_rrule, rayleigh_gradient, rayleigh_value_and_grad
 from .opalg import (concatenate, kron, operator_strides, outer_product, qtto_to_matrix, tto_add, tto_compress_, tto_decomp, tto_inner, tto_mul,
                     tto_scale, tto_sub, tto_to_tensor, tto_to_ttv, ttv_to_diag_tto, ttv_to_tto)
-from .solvers import als_eigsolve, als_gen_eigsolv, dmrg_eigsolve, mals_eigsolve
+from .solvers import (als_eigsolve, als_gen_eigsolv, crank_nicholson_method, dmrg_eigsolve, euler_method, implicit_euler_method, krylov_linsolve,
+                      mals_eigsolve, rk4_method)
 from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_to_array
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
-from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, div, dot, euclidean_distance, hadamard, norm,
-                 orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_, ttv_to_tensor)
+from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, div, dot, euclidean_distance, hadamard, increase_ranks,
+                 norm, orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_, tt_up_rks, ttv_to_tensor)
 
 __all__ = [n for n in dir() if not n.startswith("__")]

@@ -180,6 +180,12 @@ DENSE_SIGNATURES = {
     "ttn_debug_gather_plan": (C.c_int, [p_i64]),
 }
 
+# the time-step entry points of include/ttn_step.h
+STEP_SIGNATURES = {
+    "ttn_apply_axpby": (C.c_int, [p_f64, handle, p_f64, handle, handle, handle]),
+    "ttn_tt_increase_ranks": (C.c_int, [handle, p_i64, C.c_double, C.c_uint64, handle]),
+}
+
 _lib = None
 
 
@@ -187,7 +193,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile csrc/ttn_api.hip for gfx950 into libttn_hip.so (in-tree).  hipcc cross-compiles
     without a GPU."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
-    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h")]
+    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -210,7 +216,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

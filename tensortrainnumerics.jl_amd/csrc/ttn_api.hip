@@ -22,6 +22,7 @@
 #include "ttn_grid_kernels.h"
 #include "ttn_grad_kernels.h"
 #include "ttn_rect_kernels.h"
+#include "ttn_step_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -978,6 +979,57 @@ int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
     if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     F64_ONLY("ttn_scale_batch (ComplexF64 handles: ttn_scale_batch_c64)", {x, y});
     return scale_impl("ttn_scale_batch", 0.0, 0.0, a, x, y);
+}
+
+// z = alpha x + beta (A y) (include/ttn_step.h): k_apply_axpby, one launch for ttn_apply -> ttn_scale_batch x 2 -> ttn_add.  Factors that
+// are the same for every train travel as kernel arguments; only a pair that differs over the batch is uploaded (and waited for).
+int ttn_apply_axpby(const double* alpha, ttn_tt_t x, const double* beta, ttn_tto_t A, ttn_tt_t y, ttn_tt_t z) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
+    F64_ONLY("ttn_apply_axpby", {x, y, z}, {A});
+    if (!same_dims(A->dims, y->dims) || !same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_apply_axpby: output must not alias an input");
+    const int d = x->d, batch = x->batch;
+    if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_axpby: the reference's + is only defined for d >= 2");
+    std::vector<int64_t> zb(d + 1);
+    for (int m = 0; m <= d; ++m) zb[m] = (m == 0 || m == d) ? 1 : x->bound[m] + A->rks[m] * y->bound[m];
+    for (int m = 0; m <= d; ++m) if (z->cap[m] < zb[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply_axpby: destination capacity too small");
+    long long maxfib = 0;
+    for (int k = 0; k < d; ++k) maxfib = std::max<long long>(maxfib, (long long)y->bound[k] * y->bound[k + 1]);
+    if (stream_fibres_too_many(maxfib * std::max<long long>(1, A->rks[0])) || stream_fibres_too_many(max_fibres(zb)))
+        return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_axpby: 2^31 or more fibres in one core (32-bit element indices)");
+    bool uniform = true;
+    for (int b = 1; b < batch; ++b) uniform = uniform && (!alpha || alpha[b] == alpha[0]) && (!beta || beta[b] == beta[0]);
+    const double* d_ab = nullptr;
+    if (!uniform) {
+        std::vector<double> ab(2 * (size_t)batch, 1.0);
+        for (int b = 0; b < batch; ++b) { if (alpha) ab[b] = alpha[b]; if (beta) ab[(size_t)batch + b] = beta[b]; }
+        const int rc = g_grad_coef.ensure(sizeof(double) * 2 * batch);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(g_grad_coef.p, ab.data(), sizeof(double) * 2 * batch, hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));              // ab is a local
+        d_ab = g_grad_coef.as<const double>();
+    }
+    int which = 0;
+    const int* which_b = nullptr;
+    { const int rc = scaled_core(x->ot.data(), d, batch, which, which_b); if (rc) return rc; }
+    hipLaunchKernelGGL(k_ranks_axpby, dim3(batch), dim3(64), 0, g_stream, z->dev(), x->dev(), A->dev(), y->dev());
+    // LDS: the largest operator core, if it fits the bound of k_apply; grid: rows x groups of TTN_AXPBY_K columns on binary sites,
+    // fibres elsewhere
+    long long amax_ = 0, items = 1;
+    for (int k = 0; k < d; ++k) {
+        amax_ = std::max<long long>(amax_, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]);
+        items = std::max<long long>(items, x->dims[k] == 2 ? (long long)zb[k] * ((zb[k + 1] + TTN_AXPBY_K - 1) / TTN_AXPBY_K) : (long long)zb[k] * zb[k + 1]);
+    }
+    const int lds_a = amax_ <= TTN_APPLY_LDS_DOUBLES ? (int)amax_ : 0;
+    hipLaunchKernelGGL(k_apply_axpby, stream_grid(items, d, batch), dim3(TTN_STREAM_TB), sizeof(double) * (size_t)lds_a, g_stream, A->dev(), x->dev(), y->dev(),
+                       z->dev(), alpha ? alpha[0] : 1.0, beta ? beta[0] : 1.0, d_ab, which, which_b, lds_a);
+    HIPCHK(hipGetLastError());
+    z->bound = zb;
+    std::fill(z->ot.begin(), z->ot.end(), 0);
+    return TTN_OK;
 }
 
 // ---- dense ops ------------------------------------------------------------------------------------
@@ -3557,6 +3609,58 @@ int ttn_als_gen_eigsolve(ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int6
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     return als_eig_impl(1, A, S, x0, x, n_stages, sweep_schedule, rmax_schedule, nullptr, 0, it_solver, 1, TTN_LOBPCG_TOL, itslv_thresh,
                         hist_len, E);
+}
+
+// increase_ranks(x, max_bond; rks, noise) (src/tt_tools.jl:443-489; include/ttn_step.h): the stage transition of the one-site eigensolver
+// as a call of its own — k_increase_ranks unchanged, its scratch (Tm, Qb, Rb, Vb, Wb, Tst) sized as als_eig_impl sizes it for the new ranks.
+int ttn_tt_increase_ranks(ttn_tt_t x, const int64_t* new_rks, double noise, uint64_t seed, ttn_tt_t y) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !y || !new_rks) return fail(TTN_ERR_ARG, "null pointer");
+    F64_ONLY("ttn_tt_increase_ranks", {x, y});
+    if (!same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    if (x == y) return fail(TTN_ERR_ARG, "ttn_tt_increase_ranks: output must not alias the input");
+    if (!(noise >= 0.0 || noise < 0.0) || std::isinf(noise)) return fail(TTN_ERR_ARG, "ttn_tt_increase_ranks: noise is not finite");
+    const int d = x->d, batch = x->batch;
+    if (new_rks[0] != 1 || new_rks[d] != 1) return fail(TTN_ERR_ARG, "ttn_tt_increase_ranks: the end ranks must be 1");
+    int rc = ttn_tt_max_ranks(x, nullptr);                              // the current ranks, not their host-side bound (synchronises)
+    if (rc) return rc;
+    for (int m = 0; m <= d; ++m) {
+        if (new_rks[m] < x->bound[m]) return fail(TTN_ERR_ARG, "ttn_tt_increase_ranks: a new rank is below a current rank");
+        if (new_rks[m] > y->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_tt_increase_ranks: a new rank is above the destination's capacity");
+    }
+    long long mmax = 1, cmax = 1, Nmax = 1;
+    for (int i = 0; i < d; ++i) {
+        const long long n = x->dims[i], a = new_rks[i], c = new_rks[i + 1];
+        Nmax = std::max(Nmax, n * a * c);
+        mmax = std::max(mmax, std::max(n * a, n * c));
+        cmax = std::max(cmax, std::max(a, c));
+    }
+    if (noise != 0.0 && (cmax > 1024 || Nmax > 65536))
+        return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_increase_ranks: with noise, ranks above 1024 or cores above 65 536 entries are not supported");
+    IncArgs Ia;
+    memset(&Ia, 0, sizeof(Ia));
+    long long cur = 0;
+    Ia.offTm = cur; cur += mmax * cmax;
+    Ia.offQb = cur; cur += mmax * cmax;
+    Ia.offRb = cur; cur += cmax * cmax;
+    Ia.offVb = cur; cur += QR_NB * mmax;
+    Ia.offWb = cur; cur += QR_NB * mmax;
+    Ia.offTst = cur; cur += ((cmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64;
+    const long long per_train = noise != 0.0 ? cur : 1;                 // (zero padding alone touches no scratch)
+    if ((rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * batch)) || (rc = g_als_tab.ensure(sizeof(long long) * (d + 1)))) return rc;
+    std::vector<long long> rn(new_rks, new_rks + d + 1);
+    HIPCHK(hipMemcpyAsync(g_als_tab.p, rn.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
+    Ia.x = x->dev(); Ia.y = y->dev(); Ia.rn = g_als_tab.as<const long long>();
+    Ia.noise = noise; Ia.seed = seed;
+    Ia.scratch = g_scratch.as<double>(); Ia.scratch_stride = per_train;
+    hipLaunchKernelGGL(k_increase_ranks, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Ia);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(g_stream));                             // rn is a local
+    y->bound.assign(new_rks, new_rks + d + 1);
+    std::fill(y->ot.begin(), y->ot.end(), 0);
+    return TTN_OK;
 }
 
 // ---- TT operator algebra (csrc/ttn_opalg_kernels.h) ----------------------------------------------------------------------------

@@ -334,6 +334,20 @@ class DeviceTT:
         _lib.check(_lib.lib().ttn_tt_merge_sites(self.h, z.h, _i64(mn), len(mn)))
         return z
 
+    # increase_ranks (include/ttn_step.h)
+    def increase_ranks(self, max_bond: int, rks: Sequence[int] | None = None, noise: float = 0.0, seed: int = 0,
+                       cap_rks: Sequence[int] | None = None) -> "DeviceTT":
+        """increase_ranks(x, max_bond; rks, noise) train by train — src/tt_tools.jl:480-490: a NEW handle with every core zero-padded to
+        ``r_and_d_to_rks(rks, dims; rmax=max_bond)`` (``rks`` defaults to [1, max_bond, ..., 1]); with ``noise != 0`` the new blocks hold
+        noise * Q, Q orthonormal from the seeded splitmix64 stream of als_eigsolve (not Julia's RNG).  Gauge flags: zeros.  Synchronises."""
+        from .tt import r_and_d_to_rks
+        max_bond = int(max_bond)
+        assert max_bond > max(self.max_ranks()), "New bond dimension too low"                       # tt_tools.jl:484
+        new = r_and_d_to_rks(list(rks) if rks is not None else [1] + [max_bond] * (self.N - 1) + [1], self.dims, rmax=max_bond)
+        y = DeviceTT(self.dims, cap_rks if cap_rks is not None else new, self.batch, dtype=self.dtype)
+        _lib.check(_lib.lib().ttn_tt_increase_ranks(self.h, _i64(new), float(noise), int(seed) & (2 ** 64 - 1), y.h))
+        return y
+
     # train -> dense tensor (csrc/ttn_grid_kernels.h)
     def to_dense(self, strides: Sequence[int] | None = None):
         """Every train of the batch as a dense tensor, on the device: a float64 torch tensor (batch, total) with
@@ -394,6 +408,24 @@ def split_rank_capacity(dims: Sequence[int], rks: Sequence[int], split_dims: Seq
 def apply(A: DeviceTTO, x: DeviceTT, y: DeviceTT) -> DeviceTT:
     _lib.check(_lib.lib().ttn_apply(A.h, x.h, y.h))
     return y
+
+
+def _factors(a, batch: int):
+    """None (= 1), a scalar or one value per train as the `batch` doubles ttn_apply_axpby reads (None stays NULL)."""
+    if a is None:
+        return None
+    v = np.broadcast_to(np.asarray(a, dtype=np.float64), (batch,))
+    return (C.c_double * batch)(*[float(t) for t in v])
+
+
+def apply_axpby(alpha, x: DeviceTT, beta, A: DeviceTTO, y: DeviceTT, z: DeviceTT) -> DeviceTT:
+    """z_b = alpha_b x_b + beta_b (A y_b) in one streaming launch (ttn_apply_axpby): bit for bit ``apply`` -> ``scale_batch`` ->
+    ``scale_batch`` -> ``add``.  alpha / beta: None (= 1), a scalar, or one value per train.  z needs the capacity
+    x.rks + A.rks * y.rks; x may be y."""
+    if not isinstance(A, DeviceTTO):
+        raise TypeError(f"apply_axpby: expected a DeviceTTO, got {type(A).__name__}")
+    _lib.check(_lib.lib().ttn_apply_axpby(_factors(alpha, x.batch), x.h, _factors(beta, x.batch), A.h, y.h, z.h))
+    return z
 
 
 def rect_rank_capacity(A_rks: Sequence[int], singleton_site: int, x_cap: Sequence[int]) -> List[int]:

@@ -78,6 +78,10 @@ class QTTvector:
     def orthogonalize(self, i: int = 1) -> "QTTvector":
         return self._like(_tt.orthogonalize(self.ttvector(), i=i))
 
+    def increase_ranks(self, max_bond: int, rks=None, noise: float = 0.0, seed: int = 0) -> "QTTvector":
+        """increase_ranks(q, max_bond; rks, noise) — src/qtt_tools.jl:793: n_dims, bits_per_dim and ordering are kept."""
+        return self._like(_tt.increase_ranks(self.ttvector(), max_bond, rks=rks, noise=noise, seed=seed))
+
     def reorder(self, new_ordering: str, threshold: float = 0.0) -> "QTTvector":
         return reorder(self, new_ordering, threshold)
 

@@ -10,8 +10,11 @@ Mirrors of the explicit time steppers of the reference that are literally chains
     implicit_euler_method / crank_nicholson_method (tt_solver = "krylov")   src/solvers/euler.jl:98-190
 
 They run on ``DeviceTT`` batches (every train of the batch is an independent initial condition / linear system),
-never leave HBM between ops, and return a new ``DeviceTT``.  The ``return_error`` branches and the ALS/MALS/DMRG
-solvers of the implicit steppers are not built.
+never leave HBM between ops, and return a new ``DeviceTT``.  The implicit steppers take ``tt_solver`` in
+{"krylov", "als", "mals", "dmrg"}; everything a step does around its linear solve is ``alpha x + beta (A y)``, one launch of
+``device.apply_axpby`` (csrc/ttn_step_kernels.h).  ``return_error=True`` returns ``(solution, rel_error)`` with the reference's
+residual formulas, ``rel_error`` a float64 array of length ``batch``.  Handed ``TTvector`` s instead of handles, the four steppers
+upload, run with batch 1, download, and return a ``TTvector`` (and a float).
 """
 from __future__ import annotations
 
@@ -65,28 +68,68 @@ def _normalize(u: DeviceTT) -> None:
     D.scale_batch([1.0 / math.sqrt(v) for v in nrm2], u, u)
 
 
-def rk4_method(A: DeviceTTO, u0: DeviceTT, steps: Sequence[float], max_bond: int, normalize: bool = True) -> DeviceTT:
-    """src/solvers/euler.jl:193-209 on a device-resident batch."""
+def _axpby(alpha, x: DeviceTT, xr, beta, A: DeviceTTO, y: DeviceTT, yr):
+    """alpha x + beta (A y) in one launch (device.apply_axpby): bit for bit _apply -> scale -> scale -> add."""
+    zr = [p + a * q for p, a, q in zip(xr, A.rks, yr)]
+    zr[0] = zr[-1] = 1
+    z = DeviceTT(x.dims, zr, x.batch)
+    D.apply_axpby(alpha, x, beta, A, y, z)
+    return z, zr
+
+
+def _is_host(u) -> bool:
+    return hasattr(u, "ttv_vec")
+
+
+def _dev_op(A) -> DeviceTTO:
+    return A if isinstance(A, DeviceTTO) else DeviceTTO(A)
+
+
+def _host_level(run, A, *trains):
+    """A stepper called with TTvectors: upload, run with batch 1, download; (TTvector, float) when the run returns an error too."""
+    if not all(_is_host(t) for t in trains):
+        raise TypeError("the trains of one call must be all TTvectors or all DeviceTT handles")
+    dA = _dev_op(A)
+    hs = [DeviceTT.from_host(t.ttvector() if hasattr(t, "ttvector") else t) for t in trains]
+    out = run(dA, *hs)
+    sol, err = out if isinstance(out, tuple) else (out, None)
+    res = sol.download(0)
+    for h in hs + [sol]:
+        h.free()
+    return res if err is None else (res, float(err[0]))
+
+
+def _rk4_increment(A: DeviceTTO, u: DeviceTT, ur, h: float, max_bond: int):
+    """(h/6) * tt_compress!(k1 + 2k2 + 2k3 + k4, max_bond) of one step (euler.jl:199-203, :212-216) before the scalar: (handle, ranks)."""
+    k1, k1r = _apply(A, u, ur)
+    t, tr = _axpy(u, ur, h / 2, k1, k1r)
+    t, tr = _compress(t, tr, max_bond)
+    k2, k2r = _apply(A, t, tr); t.free()
+    t, tr = _axpy(u, ur, h / 2, k2, k2r)
+    t, tr = _compress(t, tr, max_bond)
+    k3, k3r = _apply(A, t, tr); t.free()
+    t, tr = _axpy(u, ur, h, k3, k3r)
+    t, tr = _compress(t, tr, max_bond)
+    k4, k4r = _apply(A, t, tr); t.free()
+    # k1 + 2k2 + 2k3 + k4, left to right like the reference
+    s, sr = _axpy(k1, k1r, 2.0, k2, k2r)
+    s2, s2r = _axpy(s, sr, 2.0, k3, k3r); s.free()
+    s3, s3r = _axpy(s2, s2r, 1.0, k4, k4r); s2.free()
+    for k in (k1, k2, k3, k4):
+        k.free()
+    return _compress(s3, s3r, max_bond)
+
+
+def rk4_method(A, u0, steps: Sequence[float], max_bond: int, normalize: bool = True, return_error: bool = False):
+    """src/solvers/euler.jl:193-222 on a device-resident batch (A: TToperator or DeviceTTO).  return_error: (u, rel_error) with
+    rel_error = norm(tt_compress!(u - (u - incr) - incr, max_bond)) / max(norm(u), eps) for one more increment of size steps[-1]."""
+    if _is_host(u0):
+        return _host_level(lambda dA, du: rk4_method(dA, du, steps, max_bond, normalize, return_error), A, u0)
+    A = _dev_op(A)
     u, ur = u0, _ranks_of(u0)
     own = False
     for h in steps:
-        k1, k1r = _apply(A, u, ur)
-        t, tr = _axpy(u, ur, h / 2, k1, k1r)
-        t, tr = _compress(t, tr, max_bond)
-        k2, k2r = _apply(A, t, tr); t.free()
-        t, tr = _axpy(u, ur, h / 2, k2, k2r)
-        t, tr = _compress(t, tr, max_bond)
-        k3, k3r = _apply(A, t, tr); t.free()
-        t, tr = _axpy(u, ur, h, k3, k3r)
-        t, tr = _compress(t, tr, max_bond)
-        k4, k4r = _apply(A, t, tr); t.free()
-        # k1 + 2k2 + 2k3 + k4, left to right like the reference
-        s, sr = _axpy(k1, k1r, 2.0, k2, k2r)
-        s2, s2r = _axpy(s, sr, 2.0, k3, k3r); s.free()
-        s3, s3r = _axpy(s2, s2r, 1.0, k4, k4r); s2.free()
-        for k in (k1, k2, k3, k4):
-            k.free()
-        s3, s3r = _compress(s3, s3r, max_bond)
+        s3, s3r = _rk4_increment(A, u, ur, h, max_bond)
         un, unr = _axpy(u, ur, h / 6, s3, s3r); s3.free()    # u + (h/6) * tt_compress!(...)
         un, unr = _compress(un, unr, max_bond)
         if normalize:
@@ -95,16 +138,33 @@ def rk4_method(A: DeviceTTO, u0: DeviceTT, steps: Sequence[float], max_bond: int
             u.free()
         u, ur, own = un, unr, True
         D.status_all()          # one check per time step: a non-converged SVD inside the step must not be committed silently
-    return u
+    if not return_error:
+        return u
+    h = steps[-1]
+    s3, s3r = _rk4_increment(A, u, ur, h, max_bond)
+    incr = DeviceTT(s3.dims, s3r, s3.batch)
+    D.scale(h / 6, s3, incr); s3.free()
+    uv, iv = _Vec(u, ur, own=False), _Vec(incr, s3r)
+    t1 = _lin(1.0, uv, -1.0, iv)                              # u - incr          = (-1 * incr) + u
+    t2 = _lin(1.0, uv, -1.0, t1); t1.free()                   # u - (u - incr)
+    t3 = _lin(1.0, t2, -1.0, iv); t2.free(); iv.free()        # ... - incr
+    res, _ = _compress(t3.h, t3.rks, max_bond)
+    rel = D.norm(res) / np.maximum(D.norm(u), np.finfo(np.float64).eps)
+    res.free()
+    D.status_all()
+    return u, rel
 
 
-def euler_method(A: DeviceTTO, u0: DeviceTT, steps: Sequence[float], normalize: bool = True) -> DeviceTT:
-    """src/solvers/euler.jl:76-97: solution = orthogonalize(solution + h * (A * solution)), optional normalisation."""
+def euler_method(A, u0, steps: Sequence[float], normalize: bool = True, return_error: bool = False):
+    """src/solvers/euler.jl:76-97: solution = orthogonalize(solution + h * (A * solution)), optional normalisation (A: TToperator or
+    DeviceTTO).  return_error: (solution, rel_error), rel_error = norm(solution - (I + h A) solution) / norm(solution), h = steps[-1]."""
+    if _is_host(u0):
+        return _host_level(lambda dA, du: euler_method(dA, du, steps, normalize, return_error), A, u0)
+    A = _dev_op(A)
     u, ur = u0, _ranks_of(u0)
     own = False
     for h in steps:
-        upd, updr = _apply(A, u, ur)
-        t, tr = _axpy(u, ur, h, upd, updr); upd.free()
+        t, tr = _axpby(None, u, ur, h, A, u, ur)              # solution + h * (A * solution): one launch
         un = DeviceTT(t.dims, tr, t.batch)
         D.orthogonalize(t, 1, un); t.free()
         unr = _ranks_of(un)
@@ -113,7 +173,14 @@ def euler_method(A: DeviceTTO, u0: DeviceTT, steps: Sequence[float], normalize: 
         if own:
             u.free()
         u, ur, own = un, unr, True
-    return u
+    if not return_error:
+        return u
+    w, wr = _axpby(None, u, ur, steps[-1], A, u, ur)          # (I + h A) * solution
+    res = _lin(1.0, _Vec(u, ur, own=False), -1.0, _Vec(w, wr, own=False)); w.free()      # solution - (...)
+    rel = D.norm(res.h) / D.norm(u)
+    res.free()
+    D.status_all()
+    return u, rel
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -361,45 +428,146 @@ def krylov_linsolve(A, b: DeviceTT, guess: DeviceTT, max_bond: int = 0, krylov_s
     return x.h
 
 
-def _implicit_stepper(A: TToperator, u0: DeviceTT, guess: DeviceTT, steps, normalize, tt_solver, max_bond, crank, kw) -> DeviceTT:
-    if tt_solver != "krylov":
-        if tt_solver in ("mals", "als", "dmrg"):
-            raise NotImplementedError(f"tt_solver={tt_solver!r}: ALS/MALS/DMRG local solves are outside this backend (SURVEY §8 f1)")
-        raise ValueError(f"Unknown TT solver: {tt_solver}")
+# ----------------------------------------------------------------------------------------------------------------------
+# The implicit steppers (src/solvers/euler.jl:99-191) on the Krylov, ALS, MALS and DMRG solvers.  Keywords are forwarded to the chosen
+# solver exactly as the reference forwards `kwargs...`; they are checked against that solver's own list before anything reaches the
+# device, so a misspelt one is a TypeError naming it.
+# ----------------------------------------------------------------------------------------------------------------------
+_TT_SOLVERS = ("krylov", "als", "mals", "dmrg")
+_SOLVER_KW = {
+    "krylov": ("krylov_solver", "krylovdim", "maxiter", "rtol", "atol", "tol", "issymmetric", "ishermitian", "isposdef"),     # euler.jl:34-46
+    "als": ("sweep_count", "it_solver", "r_itsolver"),                                                                           # als.jl:161
+    "mals": ("tol", "rmax"),                                                                                                     # mals.jl:239-244
+    "dmrg": ("N", "tol", "sweep_schedule", "rmax_schedule", "it_solver", "linsolv_maxiter", "linsolv_tol", "itslv_thresh"),     # dmrg.jl:388-396
+}
+
+
+def _check_solver(who: str, tt_solver: str, kw: dict) -> None:
+    if tt_solver not in _TT_SOLVERS:
+        raise ValueError(f"Unknown TT solver: {tt_solver}")                                                                      # euler.jl:122
+    for name in kw:
+        if name not in _SOLVER_KW[tt_solver]:
+            raise TypeError(f"{who}() got an unexpected keyword argument {name!r} for tt_solver={tt_solver!r}")
+    if tt_solver == "dmrg" and kw.get("N", 2) != 2:
+        raise _lib.TTNError("dmrg_linsolve: only the two-site scheme N = 2 is offered (single-site: als_linsolve)")
+
+
+def _solve(tt_solver: str, lhs: DeviceTTO, rhs: DeviceTT, guess: DeviceTT, max_bond: int, kw: dict) -> DeviceTT:
+    """One linear solve of a step into a fresh handle."""
+    dims, B = guess.dims, guess.batch
+    if tt_solver == "krylov":
+        return krylov_linsolve(lhs, rhs, guess, max_bond=max_bond, **kw)
+    gr = guess.max_ranks()
+    if tt_solver == "als":                                     # it_solver / r_itsolver: accepted and ignored, as in als.jl:161
+        return als_linsolve_(lhs, rhs, guess, DeviceTT(dims, gr, B), kw.get("sweep_count", 2))
+    if tt_solver == "mals":
+        rmax = kw.get("rmax")
+        if rmax is None:
+            rmax = int(round(math.sqrt(math.prod(dims))))                                                                        # mals.jl:244
+        x = DeviceTT(dims, mals_capacity(dims, gr, rmax), B)
+        return mals_linsolve_(lhs, rhs, guess, x, kw.get("tol", 1.0e-12), rmax)
+    k = {n: v for n, v in kw.items() if n != "N"}
+    rs = k.get("rmax_schedule")
+    if rs is None:
+        rs = k["rmax_schedule"] = (math.isqrt(math.prod(dims)),)                                                                 # dmrg.jl:391
+    rtop = max(int(v) for v in rs)
+    cap = dmrg_capacity(dims, gr, rtop)                        # the capacity the host dmrg_linsolve chooses
+    if not k.get("it_solver", False) and max(dims[i] * cap[i] * dims[i + 1] * cap[i + 2] for i in range(len(cap) - 2)) <= 2048:
+        cap = mals_capacity(dims, gr, rtop)
+    return dmrg_linsolve_(lhs, rhs, guess, DeviceTT(dims, cap, B), **k)
+
+
+def _implicit_stepper(who, A, u0, guess, steps, normalize, return_error, tt_solver, max_bond, crank, kw):
+    _check_solver(who, tt_solver, kw)
+    if _is_host(u0) or _is_host(guess):
+        return _host_level(lambda dA, du, dg: _implicit_stepper(who, dA, du, dg, steps, normalize, return_error, tt_solver, max_bond, crank, kw),
+                           A, u0, guess)
     from .constructors import id_tto
-    I = id_tto(A.N)
-    sol, own = u0, False
+    half = 0.5 if crank else 1.0
+    lhs_of, rhs_of = {}, {}                                    # step size -> operator, built once per distinct h
+    if tt_solver == "krylov":                                  # (this path keeps its host-built operators: block order [I, -cA])
+        hostA = A.download() if isinstance(A, DeviceTTO) else A
+        I = id_tto(hostA.N)
+        dA = _dev_op(A) if (crank and return_error) else None
+
+        def lhs(h):
+            if h not in lhs_of:
+                lhs_of[h] = DeviceTTO(_tto_add(I, _tto_scale(-h * half, hostA)))                     # I - h A (:115), I - (h/2) A (:161)
+            return lhs_of[h]
+
+        def rhs_op(h):
+            if h not in rhs_of:
+                rhs_of[h] = DeviceTTO(_tto_add(I, _tto_scale(h / 2, hostA)))                         # I + (h/2) A   (:162)
+            return rhs_of[h]
+    else:
+        dA = _dev_op(A)
+        dI = DeviceTTO(id_tto(dA.N))
+
+        def lhs(h):
+            if h not in lhs_of:
+                cA = dA.scale(h * half)
+                lhs_of[h] = dI.sub(cA)                          # tto_sub(I, tto_scale(c, A)) = (-1 * (c A)) + I, on the device
+                cA.free()
+            return lhs_of[h]
+    sol, sol_own = u0, False
+    prev, prev_own = u0, False
     for h in steps:
-        if crank:
-            lhs = _tto_add(I, _tto_scale(-h / 2, A))                                  # I - (h/2) A      (:156)
-            rhs_op = DeviceTTO(_tto_add(I, _tto_scale(h / 2, A)))                     # (I + (h/2) A) * solution
-            rhs, _ = _apply(rhs_op, sol, _ranks_of(sol))
+        M = lhs(h)
+        if crank and tt_solver == "krylov":
+            rhs, _ = _apply(rhs_op(h), sol, _ranks_of(sol))                                          # (I + (h/2) A) * solution
+        elif crank:
+            sr = _ranks_of(sol)
+            rhs, _ = _axpby(None, sol, sr, h / 2, dA, sol, sr)                                       # solution + (h/2) (A solution), one launch
         else:
-            lhs = _tto_add(I, _tto_scale(-h, A))                                      # M = I - h A      (:113)
             rhs = sol
-        nxt = krylov_linsolve(lhs, rhs, guess, max_bond=max_bond, **kw)
+        nxt = _solve(tt_solver, M, rhs, guess, max_bond, kw)
         if crank:
             rhs.free()
         if normalize:
             D.scale_batch(1.0 / D.norm(nxt), nxt, nxt)                                 # next / norm(next)
         v = _round(_Vec(nxt, _ranks_of(nxt)), max_bond)                               # tt_compress!(next, max_bond) : orthogonalize(next)
         D.status_all()
-        if own:
-            sol.free()
-        sol, own, guess = v.h, True, v.h
-    return sol
+        if prev_own and prev is not sol:
+            prev.free()
+        prev, prev_own = sol, sol_own                                                  # u_prev = solution
+        sol, sol_own, guess = v.h, True, v.h
+    rel = None
+    if return_error:
+        h = steps[-1]
+        M = lhs(h)
+        sr, pr = _ranks_of(sol), _ranks_of(prev)
+        if crank:                                                                      # LHS * solution - (I + (h/2) A) * u_prev   (:182-186)
+            w, wr = _axpby(None, prev, pr, h / 2, dA, prev, pr)
+            res, _ = _axpby(-1.0, w, wr, None, M, sol, sr); w.free()
+        else:                                                                          # M * solution - u_prev                    (:135-138)
+            res, _ = _axpby(-1.0, prev, pr, None, M, sol, sr)
+        rel = D.norm(res) / D.norm(sol)
+        res.free()
+        D.status_all()
+    if prev_own and prev is not sol:
+        prev.free()
+    for M in list(lhs_of.values()) + list(rhs_of.values()):
+        M.free()
+    return sol if rel is None else (sol, rel)
 
 
-def implicit_euler_method(A: TToperator, u0: DeviceTT, guess: DeviceTT, steps, normalize: bool = True, tt_solver: str = "krylov",
-                          max_bond: int = 0, **kw) -> DeviceTT:
-    """src/solvers/euler.jl:98-140 (tt_solver = "krylov"; the return_error branch is not built)."""
-    return _implicit_stepper(A, u0, guess, steps, normalize, tt_solver, max_bond, False, kw)
+def implicit_euler_method(A, u0, guess, steps, normalize: bool = True, tt_solver: str = "krylov", max_bond: int = 0,
+                          return_error: bool = False, **kw):
+    """src/solvers/euler.jl:99-143 on a device-resident batch: per step M = I - h A, next = <tt_solver>_linsolve(M, solution, guess; kw...),
+    optional next / norm(next), solution = tt_compress!(next, max_bond) or orthogonalize(next), guess = solution.  A: TToperator or
+    DeviceTTO.  tt_solver: "krylov" (the default HERE; the reference defaults to "mals"), "als", "mals" or "dmrg"; the keywords go to
+    the chosen solver and an unknown one is a TypeError.  return_error: (solution, rel_error), rel_error = norm(M solution - u_prev) /
+    norm(solution) per train.  TTvector arguments: upload, batch 1, download."""
+    return _implicit_stepper("implicit_euler_method", A, u0, guess, steps, normalize, return_error, tt_solver, max_bond, False, kw)
 
 
-def crank_nicholson_method(A: TToperator, u0: DeviceTT, guess: DeviceTT, steps, normalize: bool = True, tt_solver: str = "krylov",
-                           max_bond: int = 0, **kw) -> DeviceTT:
-    """src/solvers/euler.jl:142-190 (tt_solver = "krylov"; the return_error branch is not built)."""
-    return _implicit_stepper(A, u0, guess, steps, normalize, tt_solver, max_bond, True, kw)
+def crank_nicholson_method(A, u0, guess, steps, normalize: bool = True, tt_solver: str = "krylov", max_bond: int = 0,
+                           return_error: bool = False, **kw):
+    """src/solvers/euler.jl:145-191: per step LHS = I - (h/2) A, RHS = (I + (h/2) A) solution — formed as solution + (h/2) (A solution)
+    by one launch of apply_axpby: the same tensor, another internal rank order than the reference's intermediate, which no caller sees —
+    then as implicit_euler_method.  tt_solver defaults to "krylov" HERE (the reference: "mals").  return_error: rel_error =
+    norm(LHS solution - RHS(u_prev)) / norm(solution) per train."""
+    return _implicit_stepper("crank_nicholson_method", A, u0, guess, steps, normalize, return_error, tt_solver, max_bond, True, kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

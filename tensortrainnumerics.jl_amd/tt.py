@@ -159,6 +159,41 @@ def r_and_d_to_rks(rks: Sequence[int], dims: Sequence[int], rmax: int = 1024) ->
     return [int(v) for v in out]
 
 
+def increase_ranks(x_tt, max_bond: int, rks: Sequence[int] | None = None, noise: float = 0.0, seed: int = 0):
+    """increase_ranks(x_tt, max_bond; rks, noise) — src/tt_tools.jl:480-490: every core zero-padded to
+    ``r_and_d_to_rks(rks, dims; rmax=max_bond)``, ``ttv_ot`` all zeros.  ``noise == 0`` is exact zero-padding on the host and needs no
+    device; ``noise != 0`` runs k_increase_ranks (``DeviceTT.increase_ranks``), whose orthonormal blocks come from the seeded splitmix64
+    stream of als_eigsolve (``seed``) instead of Julia's global RNG.  A QTTvector keeps its metadata."""
+    if hasattr(x_tt, "n_dims") and hasattr(x_tt, "ttvector"):                                       # qtt_tools.jl:793
+        return x_tt.increase_ranks(max_bond, rks=rks, noise=noise, seed=seed)
+    max_bond = int(max_bond)
+    assert max_bond > max(x_tt.ttv_rks), "New bond dimension too low"                               # tt_tools.jl:484
+    d = x_tt.N
+    new = r_and_d_to_rks(list(rks) if rks is not None else [1] + [max_bond] * (d - 1) + [1], x_tt.ttv_dims, rmax=max_bond)
+    if any(r < c for r, c in zip(new, x_tt.ttv_rks)):
+        raise _lib.TTNError(f"increase_ranks: the new ranks {new} are below the current ranks {list(x_tt.ttv_rks)}")
+    if noise != 0.0:
+        from .device import DeviceTT
+        dx = DeviceTT.from_host(x_tt)
+        dy = dx.increase_ranks(max_bond, rks=rks, noise=noise, seed=seed)
+        out = dy.download(0)
+        dx.free(); dy.free()
+        return out
+    cores = []
+    for k, c in enumerate(x_tt.ttv_vec):
+        p = np.zeros((c.shape[0], new[k], new[k + 1]), order="F", dtype=c.dtype)
+        p[:, : c.shape[1], : c.shape[2]] = c
+        cores.append(p)
+    return TTvector(d, cores, x_tt.ttv_dims, new, [0] * d)
+
+
+def tt_up_rks(x, max_bond: int, eps_wn: float = 0.0, **kw):
+    """Deprecated alias of ``increase_ranks`` (the ``eps_wn`` keyword is now ``noise``) — src/tt_tools.jl:493-496."""
+    import warnings
+    warnings.warn("`tt_up_rks` is deprecated, use `increase_ranks` (the `eps_wn` keyword is now `noise`).", DeprecationWarning, stacklevel=2)
+    return increase_ranks(x, max_bond, noise=eps_wn, **kw)
+
+
 def apply(A: TToperator, v: TTvector) -> TTvector:
     """*(A::TToperator, v::TTvector) — src/tt_operations.jl:101-111.  Complex x complex and the two mixed forms: the real side stays
     real on the device, the result is complex.  An operator with another number of sites than v takes the reference's second method
