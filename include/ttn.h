@@ -600,6 +600,13 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * launch, and ttn_tt_increase_ranks, the public increase_ranks.  Both are declared in ttn_step.h, which this header includes. */
 #include "ttn_step.h"
 
+/* ---- MaxVol cross for a batch of functions (csrc/ttn_cross_batch_kernels.h) ----------------------------------------
+ * The per-site work of tt_cross(f, domain, ::MaxVol) for many functions in one launch: ttn_cross_batch_points (fibre index matrices and
+ * coordinates from per-function sets), ttn_cross_batch_site (scale, QR, maxvol, core and next index set, one workgroup per function)
+ * and ttn_cross_batch_eval (validation error or weight contraction per function).  Declared in ttn_cross_batch.h, which this header
+ * includes. */
+#include "ttn_cross_batch.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ from .constructors import (Delta, Delta_DN, Delta_ND, Delta_NN, Nabla, fourier_q
                            qtt_basis_vector, qtt_cos, qtt_exp, qtt_polynom, qtt_sin, qtt_to_function, qtt_to_vector, qtto_constant_prolongation,
                            qtto_linear_prolongation, qtto_prolongation, rand_tt, reverse_qtt_bits, shift, toeplitz_to_qtto,
                            xxx_tto, xxz_tto, zeros_tt, zeros_tto)
-from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_integrate
+from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_cross_batch, tt_integrate, tt_integrate_batch
 from .device import DeviceRectTTO, DeviceTT, DeviceTTO, StreamTimer
 from .grad import apply_pullback, apply_rrule, cores_axpby, cores_dot, dot_pullback, dot_rrule, rayleigh_gradient, rayleigh_value_and_grad
 from .opalg import (concatenate, kron, operator_strides, outer_product, qtto_to_matrix, tto_add, tto_compress_, tto_decomp, tto_inner, tto_mul,

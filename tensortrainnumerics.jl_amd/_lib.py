@@ -186,6 +186,16 @@ STEP_SIGNATURES = {
     "ttn_tt_increase_ranks": (C.c_int, [handle, p_i64, C.c_double, C.c_uint64, handle]),
 }
 
+# MaxVol cross for a batch of functions, include/ttn_cross_batch.h (device pointers throughout; the core table of the evaluation is host)
+CROSS_BATCH_SIGNATURES = {
+    "ttn_cross_batch_points": (C.c_int, [C.c_int, i64, i64, i64, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "ttn_cross_batch_site": (C.c_int, [i64, C.c_int, i64, i64, i64, i64, i64, C.c_void_p, C.c_double, i64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "ttn_cross_batch_eval": (C.c_int, [i64, i64, i64, pp_f64, p_i64, p_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                       C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -193,7 +203,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile csrc/ttn_api.hip for gfx950 into libttn_hip.so (in-tree).  hipcc cross-compiles
     without a GPU."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
-    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h")]
+    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
+             os.path.join(INCLUDE, "ttn_cross_batch.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -216,7 +227,8 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
+            + list(CROSS_BATCH_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

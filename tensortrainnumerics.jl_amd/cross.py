@@ -10,6 +10,11 @@ SVD are ttn_dense_qr / ttn_dense_svd through the TDVP module's helpers; torch is
 MaxVol sweep reads the host once, at its validation (the error, the finiteness flag and the maxvol status words together); DMRG also
 reads each superblock's singular values to choose the rank.  No CPU fallback: without a GPU these functions raise TTNError.
 
+tt_cross_batch / tt_integrate_batch run MaxVol for many functions at once: f(X, which) receives the coordinates of
+every function still running, one workgroup per function does a whole site step (scale, QR, maxvol, core, next index set:
+csrc/ttn_cross_batch_kernels.h), a sweep still reads the host once, finished functions leave the active set, and the result is a list
+of host trains or one resident DeviceTT batch filled on the device.  Float64 on a real domain, MaxVol only.
+
 Deviations from the reference: the random draws come from a seeded portable stream (`draw_indices`), non-finite
 values of f raise TTNError, Greedy is not offered, and a MaxVol run that stops at maxiter after a kick returns the ranks of its cores.
 """
@@ -669,3 +674,326 @@ def tt_integrate(f, *args, alg=None, nquad: int = 20, lower=0.0, upper=1.0, **kw
         weights.append(w)
     tt = tt_cross(f, nodes, alg, **kw)
     return _contract_with_weights(tt.ttv_vec, weights)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# a batch of functions in one MaxVol cross (csrc/ttn_cross_batch_kernels.h, include/ttn_cross_batch.h)
+# ---------------------------------------------------------------------------------------------------------------------------------
+# MaxVol's ranks do not depend on the data (r = Rs[j+1] after every site, a kick adds a fixed amount), so every function still running
+# has the shapes of every other: a per-function array is one torch tensor with the function axis in front, a Julia (rows x cols) set
+# of A functions is (A, cols, rows), a core (n, r_left, r_right) is (A, r_right, r_left, n).
+class _BatchProblem:
+    """f(X, which), its domain on the device, the steps that called f and, per running function, the first step with a non-finite
+    value."""
+
+    def __init__(self, f, domain, batch):
+        torch, _ = _dev()
+        self.f = f
+        self.N = len(domain)
+        self.Is = [None] + [len(d) for d in domain]
+        self.dom = torch.from_numpy(np.concatenate([np.asarray(d, dtype=np.float64).reshape(-1) for d in domain])).to("cuda")
+        self.doff = torch.tensor([0] + list(np.cumsum([len(d) for d in domain])), dtype=torch.int64, device="cuda")
+        self.which = torch.arange(batch, dtype=torch.int64, device="cuda")
+        self.ids = list(range(batch))                       # the host copy of `which`
+        self.bad = torch.zeros((batch,), dtype=torch.int64, device="cuda")
+        self.steps = []
+
+    @property
+    def A(self):
+        return len(self.ids)
+
+    def keep(self, rows, rows_dev):
+        """compaction: only the functions at the positions `rows` go on"""
+        self.ids = [self.ids[a] for a in rows]
+        self.which = self.which[rows_dev].contiguous()
+        self.bad = self.bad[rows_dev].contiguous()
+
+    def fibre_points(self, j, n, rl, rr, L, R):
+        torch, _ = _dev()
+        P = rl * n * rr
+        X = torch.empty((self.A, self.N, P), dtype=torch.float64, device="cuda")
+        _lib.check(_lib.lib().ttn_cross_batch_points(0, self.A, self.N, j, n, rl, rr, None if L is None else _p(L), None if R is None else _p(R),
+                                                     None, P, _p(self.doff), _p(self.dom), None, _p(X)))
+        return X
+
+    def shared_points(self, idx):
+        """coordinates (A, N, P) of the index matrix idx, held as (N, P), for every running function"""
+        torch, _ = _dev()
+        P = int(idx.shape[1])
+        X = torch.empty((self.A, self.N, P), dtype=torch.float64, device="cuda")
+        _lib.check(_lib.lib().ttn_cross_batch_points(2, self.A, self.N, 1, 1, 1, 1, None, None, _p(idx), P, _p(self.doff), _p(self.dom), None, _p(X)))
+        return X
+
+    def call(self, X, step):
+        """f at the coordinate rows of X (A, N, P): (A, P) float64 values on the device"""
+        torch, _ = _dev()
+        A, _, P = X.shape
+        y = self.f(X.transpose(1, 2), self.which)
+        if isinstance(y, torch.Tensor):
+            y = y.to("cuda")
+        else:
+            y = torch.from_numpy(np.array(y)).to("cuda")
+        if y.numel() != A * P:
+            raise _lib.TTNError(f"tt_cross_batch: f returned {y.numel()} values for {A} functions x {P} points ({step})")
+        if y.is_complex():
+            raise _lib.TTNError(f"tt_cross_batch: f returned complex values; float64 values on a real domain only ({step})")
+        y = y.reshape(A, P).to(torch.float64).contiguous()
+        self.steps.append(step)
+        if P:
+            fin = torch.isfinite(y).all(dim=1)
+            self.bad.copy_(torch.where((self.bad == 0) & ~fin, torch.full_like(self.bad, len(self.steps)), self.bad))
+        return y
+
+    def probe(self):
+        torch, _ = _dev()
+        ones = torch.ones((self.N, 1), dtype=torch.int64, device="cuda")
+        self.call(self.shared_points(ones), "the value-type probe at index (1, ..., 1)")
+
+    def check(self, bad, status):
+        """the host read's words: bad (A), status (2(N-1) x A)"""
+        for a, w in enumerate(bad):
+            if int(w):
+                raise _lib.TTNError(f"tt_cross_batch: f returned a non-finite value for function {self.ids[a]} ({self.steps[int(w) - 1]})")
+        for row in status:
+            for a, w in enumerate(row):
+                if int(w):
+                    raise _lib.TTNError(f"tt_cross_batch: maxvol met a zero pivot for function {self.ids[a]} "
+                                        "(a fibre is zero, or a fibre matrix has rank below its size)")
+
+
+def _d_batch_site(direction, N, j, n, rl, rr, V, tol, maxiter, set_in, info):
+    """one site step of every running function: (core, next set, pivots).  V (A, rl n rr) as f returned it; set_in (A, cols, rows) or
+    None; info (A, 2) int64 receives {status, swaps}."""
+    torch, _ = _dev()
+    A = V.shape[0]
+    r = rr if direction == 0 else rl
+    nin = (j - 1) if direction == 0 else (N - j)
+    core = torch.empty((A, rr, rl, n), dtype=torch.float64, device="cuda")         # Julia (n, rl, rr) in both directions
+    nxt = torch.empty((A, nin + 1, r), dtype=torch.int64, device="cuda")
+    piv = torch.empty((A, r), dtype=torch.int64, device="cuda")
+    _lib.check(_lib.lib().ttn_cross_batch_site(A, direction, N, j, n, rl, rr, _p(V), float(tol), int(maxiter), None if set_in is None else _p(set_in),
+                                               _p(nxt), _p(core), _p(piv), _p(info)))
+    return core, nxt, piv
+
+
+def _d_batch_eval(cores, Rs_, Is_, idx=None, w=None, yref=None, tol=0.0):
+    """the A trains cores[k] (A, r_right, r_left, n) at the shared index matrix idx (N, P), or against the weights w: (out, err)"""
+    torch, _ = _dev()
+    N = len(cores)
+    A = int(cores[0].shape[0])
+    P = 1 if idx is None else int(idx.shape[1])
+    out = torch.empty((A, P), dtype=torch.float64, device="cuda")
+    err = torch.empty((A,), dtype=torch.float64, device="cuda") if yref is not None else None
+    ptrs = (C.POINTER(C.c_double) * N)(*[C.cast(C.c_void_p(c.data_ptr()), C.POINTER(C.c_double)) for c in cores])
+    dims = (C.c_int64 * N)(*[int(v) for v in Is_])
+    rks = (C.c_int64 * (N + 1))(*[int(v) for v in Rs_])
+    _lib.check(_lib.lib().ttn_cross_batch_eval(A, N, P, ptrs, dims, rks, None if idx is None else _p(idx), None if w is None else _p(w), _p(out),
+                                               None if yref is None else _p(yref), float(tol), None if err is None else _p(err)))
+    return out, err
+
+
+_LAST_BATCH = {}    # diagnostics of the last batched run: per function eps and sweeps; groups; the timing split; sets through last_batch_sets
+
+
+def last_batch_sets(b):
+    """(lsets, rsets) of function b after the last tt_cross_batch, as host matrices in the lists' 1-based layout of _LAST"""
+    for g in _LAST_BATCH["groups"]:
+        if b in g["ids"]:
+            a = g["ids"].index(b)
+            N = len(g["cores"])
+            return ([None, None] + [_host_set(g["lsets"][k][a]) for k in range(2, N + 1)],
+                    [None] + [_host_set(g["rsets"][k][a]) for k in range(1, N)] + [None])
+    raise KeyError(b)
+
+
+def _maxvol_cross_batch(pb, alg, ranks, val_size, seed):
+    """_maxvol_cross for every function of pb at once.  Returns the groups of functions that finished together: dicts with ids, Rs
+    (1-based list), cores (list of N device tensors (G, r_right, r_left, n)), lsets, rsets."""
+    torch, _ = _dev()
+    N, Is = pb.N, pb.Is
+    B = pb.A
+    Rs = [None, 1] + ([int(ranks)] * (N - 1) if isinstance(ranks, (int, np.integer)) else [int(r) for r in ranks]) + [1]
+    if len(Rs) != N + 2:
+        raise _lib.TTNError(f"tt_cross_batch: ranks needs N - 1 = {N - 1} entries")
+    _cap_ranks_(Rs, Is, alg.rmax)
+    if max(Rs[1:]) > 1024 or max(r * n for r, n in zip(Rs[1:], Is[1:])) > (1 << 20):
+        raise _lib.TTNError("tt_cross_batch: ranks up to 1024 and fibre matrices of up to 2^20 rows")
+    cores = [None] * (N + 1)
+    lsets, rsets = [None] * (N + 1), [None] * (N + 1)
+    randint = draw_indices(seed, DRAW_MAXVOL_RSETS, 0, 0, max(Rs[1:]), Is[1:])
+    for n in range(1, N):
+        rsets[n] = _dev_set(randint[: Rs[n + 1], n:]).unsqueeze(0).expand(B, -1, -1).contiguous()
+    Xs = draw_indices(seed, DRAW_VALIDATION, 0, 0, val_size, Is[1:])
+    it_val = torch.from_numpy(np.ascontiguousarray(Xs.T)).to("cuda")
+    ys_val = pb.call(pb.shared_points(it_val), "the validation points")
+    if alg.verbose:
+        log.info("MaxVol cross-interpolation of %d functions over %dD domain with %d grid points", B, N, int(np.prod(Is[1:], dtype=np.float64)))
+    hist = [[] for _ in range(B)]
+    groups = []
+    tm = _Timer()
+
+    def fibre(j, step):
+        tm.mark("gathers")
+        X = pb.fibre_points(j, Is[j], Rs[j], Rs[j + 1], None if j == 1 else lsets[j], None if j == N else rsets[j])
+        tm.mark("f")
+        return pb.call(X, step)
+
+    def finish(rows, rows_dev, core_Rs):
+        groups.append(dict(ids=[pb.ids[a] for a in rows], Rs=list(core_Rs), cores=[cores[k][rows_dev].contiguous() for k in range(1, N + 1)],
+                           lsets=[None, None] + [lsets[k][rows_dev] for k in range(2, N + 1)],
+                           rsets=[None] + [rsets[k][rows_dev] for k in range(1, N)] + [None]))
+
+    for it in range(1, alg.maxiter + 1):
+        A = pb.A
+        info = torch.zeros((2 * (N - 1), A, 2), dtype=torch.int64, device="cuda")
+        for j in range(1, N):
+            V = fibre(j, f"iteration {it}, left-to-right, site {j}")
+            tm.mark("site")
+            cores[j], lsets[j + 1], _ = _d_batch_site(0, N, j, Is[j], Rs[j], Rs[j + 1], V, alg.pivot.tol, alg.pivot.maxiter,
+                                                      None if j == 1 else lsets[j], info[j - 1])
+        for j in range(N, 1, -1):
+            V = fibre(j, f"iteration {it}, right-to-left, site {j}")
+            tm.mark("site")
+            cores[j], rsets[j - 1], _ = _d_batch_site(1, N, j, Is[j], Rs[j], Rs[j + 1], V, alg.pivot.tol, alg.pivot.maxiter,
+                                                      None if j == N else rsets[j], info[N - 2 + j - 1])
+        V = fibre(1, f"iteration {it}, site 1")
+        cores[1] = V.reshape(A, Rs[2], Rs[1], Is[1])
+        tm.mark("evaluation")
+        _, err = _d_batch_eval(cores[1:], Rs[1:], Is[1:], idx=it_val, yref=ys_val, tol=alg.tol)
+        words = torch.cat([err, pb.bad.to(torch.float64), info[:, :, 0].reshape(-1).to(torch.float64)]).tolist()   # the sweep's one host read
+        tm.mark("end")
+        pb.check(words[A: 2 * A], [words[2 * A + s * A: 2 * A + (s + 1) * A] for s in range(2 * (N - 1))])
+        eps = words[:A]
+        for a in range(A):
+            hist[pb.ids[a]].append(eps[a])
+        if alg.verbose:
+            log.info("Iteration %d: %d functions, max ε = %s, max rank = %d", it, A, max(eps), max(Rs[1:]))
+        done = [a for a in range(A) if eps[a] < alg.tol]
+        rest = [a for a in range(A) if not eps[a] < alg.tol]
+        if done:
+            finish(done, torch.tensor(done, dtype=torch.int64, device="cuda"), Rs)
+        if not rest:
+            break
+        if done:
+            rd = torch.tensor(rest, dtype=torch.int64, device="cuda")
+            pb.keep(rest, rd)
+            ys_val = ys_val[rd].contiguous()
+            for k in range(1, N):
+                rsets[k] = rsets[k][rd].contiguous()
+            if it == alg.maxiter:                           # (the next sweep would write these anew)
+                cores = [None] + [c[rd] for c in cores[1:]]
+                for k in range(2, N + 1):
+                    lsets[k] = lsets[k][rd]
+        core_Rs = list(Rs)
+        if alg.kickrank is not None:
+            newRs = list(Rs)
+            for n in range(2, N + 1):
+                newRs[n] = min(newRs[n] + alg.kickrank, alg.rmax)
+            _cap_ranks_(newRs, Is, alg.rmax)
+            for n in range(1, N):
+                if newRs[n + 1] > Rs[n + 1]:
+                    extra = _dev_set(draw_indices(seed, DRAW_KICK, it, n, newRs[n + 1] - Rs[n + 1], Is[n + 1:]))
+                    rsets[n] = torch.cat([rsets[n], extra.unsqueeze(0).expand(pb.A, -1, -1)], 2).contiguous()
+            Rs = newRs
+        if it == alg.maxiter:                               # stopped after the kick, as _maxvol_cross: the ranks are those of the cores
+            if alg.verbose:
+                log.warning("Max iterations reached: functions %s, max ε = %s", pb.ids, max(eps[a] for a in rest))
+            finish(list(range(pb.A)), torch.arange(pb.A, dtype=torch.int64, device="cuda"), core_Rs)
+    _LAST_BATCH.clear()
+    _LAST_BATCH.update(eps=hist, sweeps=[len(h) for h in hist], split=tm.split(), groups=groups)
+    return groups
+
+
+def _batch_checks(alg, domain, batch, who):
+    alg = MaxVol() if alg is None else alg
+    if isinstance(alg, (DMRG, Greedy)):
+        raise _lib.TTNError(f"{who}: MaxVol only; the ranks of {type(alg).__name__} depend on the data, so a batch has no common shapes")
+    if not isinstance(alg, MaxVol):
+        raise _lib.TTNError(f"{who}: unknown algorithm {type(alg).__name__}")
+    if not isinstance(alg.pivot, MaxVolPivot):
+        raise _lib.TTNError(f"{who}: MaxVol needs a MaxVolPivot (a {type(alg.pivot).__name__} has no tol)")
+    if not isinstance(batch, (int, np.integer)) or batch < 1:
+        raise _lib.TTNError(f"{who}: batch must be an integer >= 1, got {batch!r}")
+    if batch > 65535:
+        raise _lib.TTNError(f"{who}: at most 65535 functions in one call")
+    dom = _domain(domain)
+    if any(np.iscomplexobj(d) for d in dom):
+        raise _lib.TTNError(f"{who}: float64 values on a real domain only (the domain is complex)")
+    return alg, dom
+
+
+def _cross_batch_groups(f, dom, batch, alg, ranks, val_size, seed):
+    pb = _BatchProblem(f, dom, int(batch))
+    pb.probe()
+    return _maxvol_cross_batch(pb, alg, ranks, int(val_size), seed), pb
+
+
+def tt_cross_batch(f, domain, batch: int, alg=None, ranks=2, val_size: int = 1000, seed: int = 0, resident: bool = False):
+    """MaxVol tt_cross of `batch` functions at once.  f(X, which): X is a float64 device tensor (A, P, N), row X[a, p, :] the p-th point
+    of function which[a]; which is the int64 device tensor of the A <= batch functions still running; f returns (A, P) values.  One
+    `seed` names the draws of all functions: function b sees the draws of tt_cross(f_b, ..., seed=seed) and ends with the
+    index sets, ranks and sweep count of that call.  A function whose validation error falls below alg.tol is finished and is not asked of f again.  Returns
+    a list of `batch` host TTvectors, or with resident=True one device.DeviceTT of that batch (capacity: the per-bond maximum of the
+    final ranks, every train at its own ranks), filled on the device."""
+    alg, dom = _batch_checks(alg, domain, batch, "tt_cross_batch")
+    torch, stream = _dev()
+    with torch.cuda.stream(stream):
+        groups, pb = _cross_batch_groups(f, dom, batch, alg, ranks, val_size, seed)
+        N, Is = pb.N, pb.Is
+        if not resident:
+            out = [None] * int(batch)
+            for g in groups:
+                host = [c.cpu().numpy() for c in g["cores"]]                     # one copy per site and group
+                for a, b in enumerate(g["ids"]):
+                    cs = [np.asfortranarray(np.transpose(h[a])) for h in host]
+                    out[b] = TTvector(N, cs, tuple(Is[1:]), [1] + [int(c.shape[2]) for c in cs], [0] * N)
+            return out
+        from .device import DeviceTT
+        cap = [max(g["Rs"][k] for g in groups) for k in range(1, N + 2)]
+        tt = DeviceTT(Is[1:], cap, int(batch))
+        for k in range(1, N + 1):
+            buf = torch.zeros((int(batch), Is[k] * cap[k - 1] * cap[k]), dtype=torch.float64, device="cuda")
+            rk2 = torch.empty((int(batch), 2), dtype=torch.int64, device="cuda")
+            for g in groups:
+                ids = torch.tensor(g["ids"], dtype=torch.int64, device="cuda")
+                rl, rr = g["Rs"][k], g["Rs"][k + 1]
+                buf[ids, : Is[k] * rl * rr] = g["cores"][k - 1].reshape(len(g["ids"]), -1)
+                rk2[ids] = torch.tensor([rl, rr], dtype=torch.int64, device="cuda")
+            _lib.check(_lib.lib().ttn_tt_core_import(tt.h, k, _p(buf), _p(rk2), cap[k - 1], cap[k]))
+        return tt
+
+
+def tt_integrate_batch(f, *args, alg=None, nquad: int = 20, lower=0.0, upper=1.0, **kw):
+    """tt_integrate for `batch` functions at once — tt_integrate_batch(f, d, batch; lower, upper, ...) or tt_integrate_batch(f, lower,
+    upper, batch; ...), `batch` also as a keyword: Gauss-Legendre nodes per axis, tt_cross_batch on them (f as there; ranks, val_size,
+    seed pass through), every train contracted with the weights on the device.  Returns `batch` floats."""
+    args = list(args)
+    if "batch" in kw:
+        args.append(kw.pop("batch"))
+    if len(args) == 2 and isinstance(args[0], (int, np.integer)):
+        d, batch = int(args[0]), args[1]
+        lo, hi = [lower] * d, [upper] * d
+    elif len(args) == 3:
+        lo, hi, batch = list(args[0]), list(args[1]), args[2]
+        if len(lo) != len(hi):
+            raise AssertionError("lower and upper bounds must have the same length")
+    else:
+        raise TypeError("tt_integrate_batch(f, lower, upper, batch; ...) or tt_integrate_batch(f, d, batch; lower, upper, ...)")
+    ranks, val_size, seed = kw.pop("ranks", 2), kw.pop("val_size", 1000), kw.pop("seed", 0)
+    if kw:
+        raise TypeError(f"tt_integrate_batch: unknown keywords {sorted(kw)}")
+    nodes, weights = [], []
+    for a, b in zip(lo, hi):
+        x, w = _gauss_legendre(int(nquad), a, b)
+        nodes.append(x)
+        weights.append(w)
+    alg, dom = _batch_checks(alg, nodes, batch, "tt_integrate_batch")
+    torch, stream = _dev()
+    with torch.cuda.stream(stream):
+        groups, pb = _cross_batch_groups(f, dom, batch, alg, ranks, val_size, seed)
+        wt = torch.from_numpy(np.concatenate([np.asarray(w, dtype=np.float64) for w in weights])).to("cuda")
+        out = torch.empty((int(batch),), dtype=torch.float64, device="cuda")
+        for g in groups:
+            v, _ = _d_batch_eval(g["cores"], g["Rs"][1:], pb.Is[1:], w=wt)
+            out[torch.tensor(g["ids"], dtype=torch.int64, device="cuda")] = v.reshape(-1)
+        return out.cpu().numpy()

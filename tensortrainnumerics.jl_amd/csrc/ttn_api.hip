@@ -17,6 +17,7 @@
 #include "ttn_tdvp_kernels.h"
 #include "ttn_densefact_kernels.h"
 #include "ttn_cross_kernels.h"
+#include "ttn_cross_batch_kernels.h"
 #include "ttn_opalg_kernels.h"
 #include "ttn_cplx_kernels.h"
 #include "ttn_grid_kernels.h"
@@ -61,6 +62,8 @@ long long g_dense_plan[3] = {-1, 0, 0};   // cut m, TM, TN of the last ttn_tt_to
 long long g_gather_plan[4] = {0, 0, 0, 0};   // TI, TO, ld, RO of the gather of the last ttn_tto_decomp_dev (ttn_debug_gather_plan); TI == 0: none
 std::string g_err = "";
 std::vector<hipEvent_t> g_slots;   // ttn_event_record slots
+std::vector<long long> g_xb_tab_host;   // ttn_cross_batch_eval: the host copy of the core table, kept until its upload has completed
+hipEvent_t g_xb_tab_ev = nullptr;       // recorded after that upload; waited for before the host copy is written again
 
 int fail(int code, const char* what) {
     g_err = what;
@@ -105,9 +108,10 @@ DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-sit
 DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
 DevBuf g_cross_tab;        // core table of ttn_cross_eval
 DevBuf g_cross_info;       // status words of a ttn_cross_maxvol called without a device info
+DevBuf g_xb_tab;           // core table of ttn_cross_batch_eval
 DevBuf g_grad_coef;        // [2][batch] doubles: Delta of ttn_dot_pullback, alpha and beta of ttn_tt_cores_axpby
 DevBuf* const g_bufs[] = {&g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
-                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab, &g_cross_tab, &g_cross_info, &g_grad_coef};
+                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab, &g_cross_tab, &g_cross_info, &g_grad_coef, &g_xb_tab};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -268,6 +272,7 @@ int ttn_init(int device) {
         {(const void*)k_cross_maxvol<false>, TTN_XV_LDS_BYTES},
         {(const void*)k_cross_maxvol<true>, TTN_XV_LDS_BYTES},
         {(const void*)k_zcompress, TTN_ZC_LDS_BYTES},
+        {(const void*)k_cross_batch_site, TTN_XB_LDS_BYTES},
     };
     for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
@@ -290,6 +295,7 @@ int ttn_finalize(void) {
     g_ortho_state_batch = 0;
     for (auto e : g_slots) if (e) hipEventDestroy(e);
     g_slots.clear();
+    if (g_xb_tab_ev) { hipEventDestroy(g_xb_tab_ev); g_xb_tab_ev = nullptr; }
     hipStreamDestroy(g_stream);
     g_stream = nullptr; g_init = false; g_device = -1;
     return TTN_OK;
@@ -3156,6 +3162,98 @@ int ttn_cross_eval(int cplx, int64_t N, int64_t P, const double* const* cores, c
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(g_stream));             // the table is a host local
+    return TTN_OK;
+}
+
+// ---- MaxVol cross for a batch of functions (include/ttn_cross_batch.h, csrc/ttn_cross_batch_kernels.h) ----------------------------
+int ttn_cross_batch_points(int mode, int64_t A, int64_t N, int64_t site, int64_t n, int64_t rl, int64_t rr, const int64_t* L, const int64_t* R,
+                           const int64_t* idx_in, int64_t P, const int64_t* doff, const double* dom, int64_t* idx_out, double* X) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!doff || A < 1 || N < 1 || P < 0 || (mode != 0 && mode != 2) || (!idx_out && !X) || (X && !dom))
+        return fail(TTN_ERR_ARG, "ttn_cross_batch_points: bad argument");
+    if (mode == 2 && !idx_in) return fail(TTN_ERR_ARG, "ttn_cross_batch_points: mode 2 needs an index matrix");
+    if (mode == 0) {
+        if (site < 1 || site > N || n < 1 || rl < 1 || rr < 1) return fail(TTN_ERR_ARG, "ttn_cross_batch_points: bad site, size or rank");
+        if ((site > 1 && !L) || (site < N && !R)) return fail(TTN_ERR_ARG, "ttn_cross_batch_points: missing index set");
+        if (P != rl * n * rr) return fail(TTN_ERR_ARG, "ttn_cross_batch_points: P differs from the size of the fibre");
+    }
+    if (A > TTN_XB_MAX_A) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_points: at most 65535 functions");
+    if (P == 0) return TTN_OK;
+    const long long total = (long long)P * N, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_points: too many points");
+    hipLaunchKernelGGL(k_cross_batch_points, dim3((unsigned)blocks, (unsigned)A), dim3(256), 0, g_stream, mode, (long long)P, (int)N, (int)site,
+                       (long long)n, (long long)rl, (long long)rr, (const long long*)L, (const long long*)R, (const long long*)idx_in,
+                       (const long long*)doff, dom, (long long*)idx_out, X);
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+int ttn_cross_batch_site(int64_t A, int dir, int64_t N, int64_t site, int64_t n, int64_t rl, int64_t rr, const double* V, double tol,
+                         int64_t maxiter, const int64_t* set_in, int64_t* set_out, double* core, int64_t* piv, int64_t* info) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!V || !set_out || !core || !piv || !info || A < 1 || N < 2 || (dir != 0 && dir != 1) || n < 1 || rl < 1 || rr < 1 || maxiter < 0)
+        return fail(TTN_ERR_ARG, "ttn_cross_batch_site: bad argument");
+    if (dir == 0 ? (site < 1 || site > N - 1) : (site < 2 || site > N)) return fail(TTN_ERR_ARG, "ttn_cross_batch_site: bad site for this direction");
+    const int64_t nin = dir == 0 ? site - 1 : N - site;
+    if (nin > 0 && !set_in) return fail(TTN_ERR_ARG, "ttn_cross_batch_site: missing index set");
+    if (nin == 0 && (dir == 0 ? rl : rr) != 1) return fail(TTN_ERR_ARG, "ttn_cross_batch_site: the end rank must be 1");
+    if (rl > TTN_XV_MAX_M || rr > TTN_XV_MAX_M || n > TTN_XV_MAX_M) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_site: need r <= 1024 and m <= 2^20");
+    const int64_t m = dir == 0 ? rl * n : n * rr, r = dir == 0 ? rr : rl;
+    if (m < r) return fail(TTN_ERR_ARG, "ttn_cross_batch_site: need m >= r");
+    if (r > TTN_XV_MAX_R || m > TTN_XV_MAX_M) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_site: need r <= 1024 and m <= 2^20");
+    if (A > TTN_XB_MAX_A) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_site: at most 65535 functions");
+    const size_t sz = (size_t)m * (size_t)r;
+    const int use_lds = 2 * sizeof(double) * sz <= TTN_XB_LDS_MAT ? 1 : 0;
+    const size_t stride = (use_lds ? 0 : 2 * sz) + (dir == 0 ? 0 : sz) + ((size_t)m + 1) / 2;       // doubles per function
+    int rc = g_scratch.ensure(sizeof(double) * stride * (size_t)A + 64);
+    if (rc) return rc;
+    const size_t lds = (use_lds ? 2 * sizeof(double) * sz : 0) + TTN_XB_LDS_SMALL(r);
+    const int mi = (int)std::min<int64_t>(maxiter, 1 << 30);
+    hipLaunchKernelGGL(k_cross_batch_site, dim3((unsigned)A), dim3(TTN_XB_WG), lds, g_stream, dir, (int)n, (int)rl, (int)rr, (int)nin, V, tol, mi,
+                       (const long long*)set_in, (long long*)set_out, core, (long long*)piv, (long long*)info, g_scratch.as<double>(),
+                       (long long)stride, use_lds);
+    HIPCHK(hipGetLastError());
+    return TTN_OK;
+}
+
+int ttn_cross_batch_eval(int64_t A, int64_t N, int64_t P, const double* const* cores, const int64_t* dims, const int64_t* rks,
+                         const int64_t* idx, const double* w, double* out, const double* yref, double tol, double* err) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!cores || !dims || !rks || !out || A < 1 || N < 1 || P < 1 || (!idx && !w) || (idx && w) || (w && P != 1) || (yref && !err))
+        return fail(TTN_ERR_ARG, "ttn_cross_batch_eval: bad argument (give idx, or w with P = 1)");
+    if (rks[0] != 1 || rks[N] != 1) return fail(TTN_ERR_DIMS, "ttn_cross_batch_eval: the end ranks must be 1");
+    for (int64_t k = 0; k < N; ++k)
+        if (!cores[k] || dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_cross_batch_eval: bad core");
+    for (int64_t k = 0; k <= N; ++k)
+        if (rks[k] < 1 || rks[k] > TTN_XE_MAX_R) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_eval: ranks up to 1024");
+    if (A > TTN_XB_MAX_A || P > 0x7fffffffLL) return fail(TTN_ERR_UNSUPPORTED, "ttn_cross_batch_eval: at most 65535 functions");
+    // the table travels from a host copy that stays untouched until the upload has completed: no wait on the stream here
+    if (!g_xb_tab_ev) HIPCHK(hipEventCreateWithFlags(&g_xb_tab_ev, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(g_xb_tab_ev));
+    g_xb_tab_host.assign(4 * (size_t)N + 1, 0);
+    long long woff = 0;
+    for (int64_t k = 0; k < N; ++k) {
+        g_xb_tab_host[k] = (long long)reinterpret_cast<uintptr_t>(cores[k]);
+        g_xb_tab_host[N + k] = dims[k];
+        g_xb_tab_host[3 * N + 1 + k] = woff;
+        woff += dims[k];
+    }
+    for (int64_t k = 0; k <= N; ++k) g_xb_tab_host[2 * N + k] = rks[k];
+    const size_t tbytes = sizeof(long long) * g_xb_tab_host.size();
+    int rc = g_xb_tab.ensure(tbytes);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(g_xb_tab.p, g_xb_tab_host.data(), tbytes, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipEventRecord(g_xb_tab_ev, g_stream));
+    hipLaunchKernelGGL(k_cross_batch_eval, dim3((unsigned)P, (unsigned)A), dim3(64), 0, g_stream, (int)N, (long long)P, g_xb_tab.as<long long>(),
+                       (const long long*)idx, w, w ? 1 : 0, out);
+    HIPCHK(hipGetLastError());
+    if (yref) {
+        hipLaunchKernelGGL(k_cross_batch_relerr, dim3((unsigned)A), dim3(TTN_XB_WG), 0, g_stream, (long long)P, yref, out, tol, err);
+        HIPCHK(hipGetLastError());
+    }
     return TTN_OK;
 }
 
