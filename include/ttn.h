@@ -211,15 +211,20 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
 /* mals_linsolve(A, b, tt_start; tol, rmax) (src/solvers/mals.jl:240-312): one forward and one backward half sweep of
  * two-site solves, ranks adapted by the truncated SVD of every local solution (sv_trunc, clamped to rmax).  x receives
  * orthogonalize(x0) first; x's CAPACITY bounds the ranks (a larger rank: TTN_ERR_CAPACITY through ttn_compress_status) and
- * must keep every two-site system n_i cap_i n_{i+1} cap_{i+2} <= 2048. */
+ * must keep every two-site system n_i cap_i n_{i+1} cap_{i+2} <= 2048.  The local systems are solved as the reference's
+ * `Hermitian(K) \ b` (mals.jl:156,167): the matrix is K's UPPER TRIANGLE mirrored, in the reference's ordering of the unknowns, then LU
+ * with partial pivoting.  For a symmetric A that is K; for a non-symmetric A it is not, and the result is the reference's, not the
+ * Galerkin solution. */
 int ttn_mals_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t rmax);
 
 /* dmrg_linsolve(A, b, tt_start; N = 2, tol, sweep_schedule, rmax_schedule) (src/solvers/dmrg.jl:388-472): two-site sweeps
  * (windows 1..d-2 forward with right_core_move!, d-1..2 backward with left_core_move!, dmrg.jl:187-232) walked through the
  * reference's stage schedule — sweep s ends stage j when s == sweep_schedule[j], the sweep that would end the last stage is
  * the closing solve at window 1 — with the ranks cut by cut_off_index (dmrg.jl:179-185) clamped to the stage's rmax.
- * Local systems up to 2048 unknowns are assembled densely and solved by LU (the reference's `K_full` + `K \ Pb` branch,
- * dmrg.jl:57-62, :173-175), larger ones matrix-free by conjugate gradients (see ttn_dmrg_linsolve_it).  sweep_schedule must be positive and
+ * Local systems up to 2048 unknowns are assembled densely and solved by LU (the reference's `K_full` + `Hermitian(K) \ Pb` branch,
+ * dmrg.jl:53-62, :173-175: the upper triangle of K mirrored, in the reference's ordering (r_l, n_i n_{i+1}, r_r) of the unknowns), larger
+ * ones matrix-free by conjugate gradients on 1/2 (K + K^T) (see ttn_dmrg_linsolve_it).  For a non-symmetric A the two branches solve
+ * different systems, as in the reference.  sweep_schedule must be positive and
  * strictly increasing (anything else does not terminate in the reference); at most 32 full sweeps per call.  Capacity and
  * status as for ttn_mals_linsolve.  N = 1 is ttn_als_linsolve's territory and not offered here. */
 int ttn_dmrg_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
@@ -467,6 +472,17 @@ int ttn_event_elapsed(int64_t slot_a, int64_t slot_b, float* ms);
  * workgroup GEMM (fp64 MFMA) every dense kernel is built on; ta/tb: operand stored transposed */
 int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const double* B, double* C, double alpha, double beta,
                       int ta, int tb);
+
+/* kernel unit-test hook of the dense local solve of als / mals / dmrg_linsolve: K x = rhs by the blocked LU with partial pivoting (first
+ * maximal |entry| of the column, as LAPACK's idamax).  K host, N x N column-major; rhs, x_out N doubles; piv_out[j] = the 0-based row
+ * exchanged with row j at step j (LAPACK's ipiv - 1; -1 for a column the elimination did not reach).  form 0: wg_lu_solve, one
+ * workgroup, N <= 2048; form 1: the grid-form stages of csrc/ttn_als_grid.h, N <= 8192.  Returns 0, or 1 if a pivot column is exactly
+ * zero (x_out then holds the partly eliminated right-hand side: finite, not a solution), or a TTN_ERR_* code. */
+int ttn_selftest_lu_solve(int64_t N, const double* K, const double* rhs, double* x_out, int64_t* piv_out, int form);
+/* kernel unit-test hook of the matrix-free two-site operator (wg_two_site_apply, shared by the CG local solver and the two-site
+ * eigensolvers): out = 1/2 (K + K^T) v with K[(ab,cd),(ef,gh)] = sum_z G[ab,ef,z] H[z,cd,gh].  Host arrays: G (na, na, Rz)
+ * column-major, H (Rz, nb, nb) with z fastest, v and out na x nb column-major.  1 <= na, nb <= 256, 1 <= Rz <= 64. */
+int ttn_selftest_two_site_apply(int64_t na, int64_t nb, int64_t Rz, const double* G, const double* H, const double* v, double* out);
 
 /* self-test of the symmetric eigensolver used by the Gram routes (csrc/ttn_eig_kernels.h): G host, n x n (n = 64 or 128),
  * column-major, symmetric positive definite; sig[nev] = sqrt of the nev largest eigenvalues (descending), X[128*r] = sig_j * u_j (r <= 64);

@@ -593,10 +593,14 @@ __global__ void __launch_bounds__(TTN_WG) k_als_linsolve(AlsArgs P) {
 // -------------------------------------------------------------------------------------------------
 // mals_linsolve (src/solvers/mals.jl:240-312): one forward and one backward half sweep of TWO-site solves; the ranks adapt
 // through the truncated SVD of every local solution (sv_trunc, :42-56, clamped to rmax).  Same machinery as als_linsolve:
-// dense K[(a,b,c,d),(e,f,g,h)] = sum_z G_i[a,b,e,f,z] H_i[z,c,d,g,h] (:148-157) solved by the blocked LU (the reference's
-// Hermitian(K) \ b reads one triangle; K is symmetric to rounding), the split by the Householder-LQ + Jacobi SVD of the bond
-// step (wg_hsvd_step, layouts 2 / 1).  Ranks change per train, so the environments are stored compactly with the CURRENT
-// ranks inside slots sized by the handle's capacity.
+// dense K[(a,b,c,d),(e,f,g,h)] = sum_z G_i[a,b,e,f,z] H_i[z,c,d,g,h] (:148-157) solved by the blocked LU.  The reference solves
+// `Hermitian(K) \ b` (mals.jl:156,167; dmrg.jl:53,174), which reads ONLY THE UPPER TRIANGLE of K: for a non-symmetric operator that
+// is another matrix than K (and its solution another vector than K \ b).  The assembly below mirrors it — an entry below the
+// diagonal, in the reference's ordering of the unknowns, is taken from its transposed position (ksolve) — so the LU runs on
+// exactly the matrix LAPACK's symmetric solve sees.  The matrix-free path (wg_cg_two_site) runs on 1/2 (K + K^T) like the
+// reference's: for a non-symmetric A the two paths solve DIFFERENT systems, there as here.  The split is the Householder-LQ +
+// Jacobi SVD of the bond step (wg_hsvd_step, layouts 2 / 1).  Ranks change per train, so the environments are stored compactly
+// with the CURRENT ranks inside slots sized by the handle's capacity.
 //   H_i  (R_{i+1}, n_{i+1}, r_{i+2}, n_{i+1}, r_{i+2})   couples sites i, i+1          (:10-40)
 //   Hb_i (rb_{i+1}, n_{i+1}, r_{i+2})                                                  (:60-92)
 // -------------------------------------------------------------------------------------------------
@@ -703,14 +707,16 @@ __global__ void __launch_bounds__(TTN_WG) k_mals_linsolve(MalsArgs Q) {
             double* cg = scr + Q.offCg;
             double *xv = cg, *rv = cg + Q.cg_nmax, *pv = cg + 2 * Q.cg_nmax, *qv = cg + 3 * Q.cg_nmax, *Wv = cg + 4 * Q.cg_nmax;
             const int rm = uni32((int)xr[i + 1]);
-            if (v0_swapped && n1 == n2) {
+            if (v0_swapped) {
                 // after a LEFT move the reference builds the start vector with the two physical indices exchanged (update_left reshapes
-                // [alpha, J, i_k, gamma] with the index of site i+1 running faster than that of site i, dmrg.jl:331-334): restated as
-                // it is — V0[(j, al), (k, be)] = sum_ga x_i[k, al, ga] x_{i+1}[j, ga, be], one rl x rr x rm product per (j, k)
-                for (int j = 0; j < n1; ++j)
-                    for (int k = 0; k < n2; ++k)
-                        wg_gemm(rl, rr, rm, mkview(XC(i) + k, plain(n1), plain((long long)n1 * rl)), mkview(XC(i + 1) + j, plain(n2), plain((long long)n2 * rm)),
-                                mkview(xv + j + (long long)na * k, plain(n1), plain((long long)na * n2)), 1.0, 0.0, lds);
+                // [alpha, J, i_k, gamma] with J, the index of site i+1, running faster than i_k, that of site i, dmrg.jl:331-336) and
+                // reads the merged index m = J + n2 i_k back as i_1 + n1 i_2: restated as it is — per m one rl x rr x rm product
+                // sum_ga x_i[i_k, al, ga] x_{i+1}[J, ga, be] into V0[(m % n1, al), (m / n1, be)].  For n1 = n2 that is the plain exchange.
+                for (int m = 0; m < n1 * n2; ++m) {
+                    const int j = m % n2, k = m / n2;
+                    wg_gemm(rl, rr, rm, mkview(XC(i) + k, plain(n1), plain((long long)n1 * rl)), mkview(XC(i + 1) + j, plain(n2), plain((long long)n2 * rm)),
+                            mkview(xv + m % n1 + (long long)na * (m / n1), plain(n1), plain((long long)na * n2)), 1.0, 0.0, lds);
+                }
             } else {
                 // V0[(j, al), (k, be)] = sum_ga x_i[j, al, ga] x_{i+1}[k, ga, be]: the current two-site block (b_mid / update_right)
                 wg_gemm(na, nb, rm, mkview(XC(i), plain(1), plain(na)), mkview(XC(i + 1), plain(n2), Idx{n2, 1, (long long)n2 * rm}),
@@ -722,9 +728,16 @@ __global__ void __launch_bounds__(TTN_WG) k_mals_linsolve(MalsArgs Q) {
             __syncthreads();
             return true;
         }
+        // Hermitian(K): entry (row, col) is K's own if it lies in the upper triangle of the REFERENCE's matrix, K[col, row] otherwise.
+        // mals_linsolve orders the unknowns (n1, r_l, n2, r_r) column-major like this kernel: upper = row <= col.  dmrg_linsolve
+        // orders them (r_l, n1 n2 with site i fast, r_r): with ab = i1 + n1 al the position of an unknown there is
+        // pi = al + r_l i1 + na cd.
+        const bool dmrg_order = uni32(Q.mode) == 1;
+        auto ref_pos = [&](int ab, int cd) { return dmrg_order ? ab / n1 + rl * (ab % n1) + na * cd : ab + na * cd; };
         WG_FOR((long long)N * N) {
             const int row = (int)(e_ % N), col = (int)(e_ / N);
-            const int ab = row % na, cd = row / na, ef = col % na, gh = col / na;
+            int ab = row % na, cd = row / na, ef = col % na, gh = col / na;
+            if (ref_pos(ab, cd) > ref_pos(ef, gh)) { int t_ = ab; ab = ef; ef = t_; t_ = cd; cd = gh; gh = t_; }
             double a = 0.0;
             for (int z = 0; z < Rz; ++z) a = fma(Gi[ab + (long long)na * (ef + (long long)na * z)], Hi[z + Rz * (cd + (long long)nb * gh)], a);
             K[e_] = a;
@@ -794,3 +807,19 @@ __global__ void __launch_bounds__(TTN_WG) k_mals_linsolve(MalsArgs Q) {
 #undef HBP
 #undef SITE
 #undef WG_FOR
+
+// -------------------------------------------------------------------------------------------------
+// kernel unit-test hooks (tests/test_gpu_lu.py): wg_lu_solve and wg_two_site_apply alone in one workgroup, with the LDS layout
+// k_als_linsolve / k_mals_linsolve give them.  rc[0] = wg_lu_solve's return value.
+// -------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(TTN_WG) k_selftest_lu(int N, double* K, double* rhs, int* piv, int* rc) {
+    extern __shared__ double lds[];
+    double* red = lds + GEMM_LDS_TOTAL;
+    int* iflag = reinterpret_cast<int*>(red + 32 + 2 * QR_NB * QR_NB + QR_NB + 8);
+    const int r = wg_lu_solve(N, K, rhs, piv, red, iflag, lds);
+    if (threadIdx.x == 0) rc[0] = r;
+}
+__global__ void __launch_bounds__(TTN_WG) k_selftest_two_site_apply(int na, int nb, int Rz, double* G, double* H, double* v, double* out, double* W) {
+    extern __shared__ double lds[];
+    wg_two_site_apply(uni32(na), uni32(nb), uni32(Rz), unip(G), unip(H), unip(v), unip(out), unip(W), lds);
+}

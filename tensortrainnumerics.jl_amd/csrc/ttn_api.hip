@@ -269,6 +269,8 @@ int ttn_init(int device) {
         {(const void*)k_tdvp, TDVP_LDS_BYTES},
         {(const void*)k_lu_panel, LU_PANEL_LDS_BYTES},
         {(const void*)k_lu_trail, sizeof(double) * GEMM_LDS_TOTAL},
+        {(const void*)k_selftest_lu, COMPRESS_LDS_BYTES},
+        {(const void*)k_selftest_two_site_apply, COMPRESS_LDS_BYTES},
         {(const void*)k_cross_maxvol<false>, TTN_XV_LDS_BYTES},
         {(const void*)k_cross_maxvol<true>, TTN_XV_LDS_BYTES},
         {(const void*)k_zcompress, TTN_ZC_LDS_BYTES},
@@ -1941,6 +1943,27 @@ int ttn_qtt_grid_points(int64_t n_dims, int64_t bits, int interleaved, double a,
 // the host — per site the assembly of K (grid), the blocked LU with partial pivoting panel by panel (panel: one workgroup; row
 // interchanges + U12: grid; trailing MFMA update: grid), the back substitution, then the core move and environment update (phase 2 / 3
 // of k_als_linsolve, one workgroup).  Everything is enqueued on the library stream; one flag word carries a singular pivot column.
+// The blocked LU of the grid form, panel by panel, on K (N x N column-major, destroyed) and rhs (the solution on return); piv: N
+// ints, flag: the singular-pivot word (every stage returns at once while it is set).  Shared by als_grid_path and the kernel
+// unit-test hook ttn_selftest_lu_solve.  Enqueues only.
+static void lu_grid_solve(double* K, double* Pb, int N, int* piv, int* d_flag) {
+    for (int k0 = 0; k0 < N; k0 += LU_NB) {
+        const int w = std::min(LU_NB, N - k0);
+        hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(TTN_WG), LU_PANEL_LDS_BYTES, g_stream, K, N, k0, w, piv, d_flag);
+        hipLaunchKernelGGL(k_lu_rows, dim3((N + 1 + 255) / 256), dim3(256), 0, g_stream, K, Pb, N, k0, w, (const int*)piv, (const int*)d_flag);
+        const int m = N - k0 - w;
+        if (m > 0) {
+            const int nt = (m + LU_TILE - 1) / LU_TILE;
+            hipLaunchKernelGGL(k_lu_trail, dim3(nt, nt), dim3(TTN_WG), sizeof(double) * GEMM_LDS_TOTAL, g_stream, K, Pb, N, k0, w, (const int*)d_flag);
+        }
+    }
+    for (int kb = ((N - 1) / 32) * 32; kb >= 0; kb -= 32) {
+        const int wb = std::min(32, N - kb);
+        hipLaunchKernelGGL(k_lu_back_tri, dim3(1), dim3(64), 0, g_stream, (const double*)K, Pb, N, kb, wb, (const int*)d_flag);
+        if (kb > 0) hipLaunchKernelGGL(k_lu_back_rows, dim3((kb + 255) / 256), dim3(256), 0, g_stream, (const double*)K, Pb, N, kb, wb, (const int*)d_flag);
+    }
+}
+
 static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std::vector<int64_t>& r, ttn_tto_t A, ttn_tt_t b, ttn_tt_t x, int sweep_count) {
     const int d = x->d, batch = x->batch;
     double* scr = P.scratch;
@@ -1950,28 +1973,18 @@ static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std
     { const int rc = g_lu_flag.ensure(sizeof(int)); if (rc) return rc; }
     int* d_flag = g_lu_flag.as<int>();
     const std::vector<int64_t>& R = A->rks;
-    auto solve_site = [&](int i) -> int {
+    // the right-hand sides of a batch may differ in ranks: phases 1 - 3 lay Gb / Hb out with the train's own, so must the assembly
+    std::vector<long long> h_brks((size_t)batch * (d + 1));
+    HIPCHK(hipMemcpyAsync(h_brks.data(), b->d_rks, sizeof(long long) * h_brks.size(), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    auto solve_site = [&](int i, int tb) -> int {
         const int n = (int)x->dims[i], rl = (int)r[i], rr = (int)r[i + 1];
         const int nr = n * rl, N = nr * rr;
         AlsAssembleArgs Q;
         Q.G = scr + off[i]; Q.Gb = scr + off[d + i]; Q.H = scr + off[2 * d + i]; Q.Hb = scr + off[3 * d + i];
-        Q.K = K; Q.Pb = Pb; Q.nr = nr; Q.rr = rr; Q.Rr = (int)R[i + 1]; Q.br = (int)b->bound[i + 1];
+        Q.K = K; Q.Pb = Pb; Q.nr = nr; Q.rr = rr; Q.Rr = (int)R[i + 1]; Q.br = (int)h_brks[(size_t)tb * (d + 1) + i + 1];
         hipLaunchKernelGGL(k_als_assemble, dim3((N + ALS_ASM_ROWS - 1) / ALS_ASM_ROWS, (N + ALS_ASM_COLS - 1) / ALS_ASM_COLS), dim3(ALS_ASM_ROWS), 0, g_stream, Q);
-        for (int k0 = 0; k0 < N; k0 += LU_NB) {
-            const int w = std::min(LU_NB, N - k0);
-            hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(TTN_WG), LU_PANEL_LDS_BYTES, g_stream, K, N, k0, w, piv, d_flag);
-            hipLaunchKernelGGL(k_lu_rows, dim3((N + 1 + 255) / 256), dim3(256), 0, g_stream, K, Pb, N, k0, w, (const int*)piv, (const int*)d_flag);
-            const int m = N - k0 - w;
-            if (m > 0) {
-                const int nt = (m + LU_TILE - 1) / LU_TILE;
-                hipLaunchKernelGGL(k_lu_trail, dim3(nt, nt), dim3(TTN_WG), sizeof(double) * GEMM_LDS_TOTAL, g_stream, K, Pb, N, k0, w, (const int*)d_flag);
-            }
-        }
-        for (int kb = ((N - 1) / 32) * 32; kb >= 0; kb -= 32) {
-            const int wb = std::min(32, N - kb);
-            hipLaunchKernelGGL(k_lu_back_tri, dim3(1), dim3(64), 0, g_stream, (const double*)K, Pb, N, kb, wb, (const int*)d_flag);
-            if (kb > 0) hipLaunchKernelGGL(k_lu_back_rows, dim3((kb + 255) / 256), dim3(256), 0, g_stream, (const double*)K, Pb, N, kb, wb, (const int*)d_flag);
-        }
+        lu_grid_solve(K, Pb, N, piv, d_flag);
         HIPCHK(hipGetLastError());
         return TTN_OK;
     };
@@ -1989,10 +2002,10 @@ static int als_grid_path(AlsArgs P, const std::vector<long long>& off, const std
         int nsweeps = 0;
         while (nsweeps < sweep_count) {
             ++nsweeps;
-            for (int i = 0; i < d - 1; ++i) { if ((rc = solve_site(i))) return rc; if ((rc = phase(2, i, tb))) return rc; }
+            for (int i = 0; i < d - 1; ++i) { if ((rc = solve_site(i, tb))) return rc; if ((rc = phase(2, i, tb))) return rc; }
             if (nsweeps == sweep_count) break;
             ++nsweeps;
-            for (int i = d - 1; i >= 1; --i) { if ((rc = solve_site(i))) return rc; if ((rc = phase(3, i, tb))) return rc; }
+            for (int i = d - 1; i >= 1; --i) { if ((rc = solve_site(i, tb))) return rc; if ((rc = phase(3, i, tb))) return rc; }
         }
         int h_flag = 0;
         HIPCHK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
@@ -2865,6 +2878,65 @@ int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const do
     HIPCHK(hipMemcpyAsync(C, dC, sizeof(double) * m * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     hipFree(dA); hipFree(dB); hipFree(dC);
+    return TTN_OK;
+}
+
+// kernel unit-test hook of the dense local solve: K x = rhs by the blocked LU with partial pivoting.  form 0: wg_lu_solve in one
+// workgroup (what k_als_linsolve / k_mals_linsolve run); form 1: the stages of csrc/ttn_als_grid.h through lu_grid_solve (what
+// als_grid_path runs).  Returns 0, 1 for an exactly zero pivot column, or a TTN_ERR_* code.
+int ttn_selftest_lu_solve(int64_t N, const double* K, const double* rhs, double* x_out, int64_t* piv_out, int form) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!K || !rhs || !x_out || !piv_out || N < 1 || (form != 0 && form != 1) || N > (form == 0 ? TTN_DENSE_LOCAL_MAX_ALS : 8192))
+        return fail(TTN_ERR_ARG, "ttn_selftest_lu_solve: need 1 <= N <= 2048 (form 0) / 8192 (form 1) and form 0 or 1");
+    NEED_INIT();
+    { const int rc = g_lu_flag.ensure(sizeof(int)); if (rc) return rc; }
+    int* d_flag = g_lu_flag.as<int>();
+    double *dK = nullptr, *dR = nullptr;
+    int* dP = nullptr;
+    HIPCHK(hipMalloc((void**)&dK, sizeof(double) * N * N));
+    HIPCHK(hipMalloc((void**)&dR, sizeof(double) * N));
+    HIPCHK(hipMalloc((void**)&dP, sizeof(int) * N));
+    HIPCHK(hipMemcpyAsync(dK, K, sizeof(double) * N * N, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dR, rhs, sizeof(double) * N, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(dP, 0xff, sizeof(int) * N, g_stream));                     // -1: a column the elimination never reached
+    HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g_stream));
+    if (form == 0) hipLaunchKernelGGL(k_selftest_lu, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, (int)N, dK, dR, dP, d_flag);
+    else lu_grid_solve(dK, dR, (int)N, dP, d_flag);
+    HIPCHK(hipGetLastError());
+    std::vector<int> h_piv(N);
+    int h_flag = 0;
+    HIPCHK(hipMemcpyAsync(x_out, dR, sizeof(double) * N, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(h_piv.data(), dP, sizeof(int) * N, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    hipFree(dK); hipFree(dR); hipFree(dP);
+    for (int64_t j = 0; j < N; ++j) piv_out[j] = h_piv[j];
+    return h_flag ? 1 : 0;
+}
+
+// kernel unit-test hook of the matrix-free two-site operator: out = 1/2 (K + K^T) v through wg_two_site_apply, K[(ab,cd),(ef,gh)] =
+// sum_z G[ab,ef,z] H[z,cd,gh].  G (na, na, Rz) column-major, H (Rz, nb, nb) with z fastest, v and out na x nb column-major; all host.
+int ttn_selftest_two_site_apply(int64_t na, int64_t nb, int64_t Rz, const double* G, const double* H, const double* v, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!G || !H || !v || !out || na < 1 || nb < 1 || Rz < 1 || na > 256 || nb > 256 || Rz > 64)
+        return fail(TTN_ERR_ARG, "ttn_selftest_two_site_apply: need 1 <= na, nb <= 256 and 1 <= Rz <= 64");
+    NEED_INIT();
+    const size_t N = (size_t)na * nb;
+    double *dG = nullptr, *dH = nullptr, *dv = nullptr, *dout = nullptr, *dW = nullptr;
+    HIPCHK(hipMalloc((void**)&dG, sizeof(double) * na * na * Rz));
+    HIPCHK(hipMalloc((void**)&dH, sizeof(double) * nb * nb * Rz));
+    HIPCHK(hipMalloc((void**)&dv, sizeof(double) * N));
+    HIPCHK(hipMalloc((void**)&dout, sizeof(double) * N));
+    HIPCHK(hipMalloc((void**)&dW, sizeof(double) * N * Rz));
+    HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * na * na * Rz, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dH, H, sizeof(double) * nb * nb * Rz, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dv, v, sizeof(double) * N, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(dout, 0, sizeof(double) * N, g_stream));
+    hipLaunchKernelGGL(k_selftest_two_site_apply, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, (int)na, (int)nb, (int)Rz, dG, dH, dv, dout, dW);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * N, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    hipFree(dG); hipFree(dH); hipFree(dv); hipFree(dout); hipFree(dW);
     return TTN_OK;
 }
 

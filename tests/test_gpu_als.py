@@ -7,6 +7,7 @@ import pytest
 
 from oracle import tt_oracle as O
 from tests.helpers import to_oracle, to_product, tt_norm_stable, tt_rel_diff
+from tests.linsolve_reference import A_piv, id_general, pivot_spy
 
 pytestmark = pytest.mark.gpu
 
@@ -202,3 +203,117 @@ def test_als_rank40_beyond_the_one_workgroup_limit(T):
     assert list(got.ttv_rks) == list(ref.ttv_rks) and list(got.ttv_ot) == list(ref.ttv_ot)
     assert tt_rel_diff(to_oracle(got), ref) <= 1e-9
     assert abs(_resid(A, to_oracle(got), b) - _resid(A, ref, b)) <= 1e-9
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Local systems that make the LU exchange rows BEYOND its first panel of 32 columns.  Delta + sigma I never does (the CPU spy of
+# tests/linsolve_reference.py counts 0 exchanges on every parameter set above with N > 32), so a wrong interchange outside the panel
+# or on the right-hand side would pass everything above.  A_piv = 2 X + toeplitz(0.5, -0.7, 0.2), X the bit flip: the dominant entries
+# sit on the anti-diagonal.  Every test first asserts, on the oracle's own local systems, that its input really pivots out there.
+# ------------------------------------------------------------------------------------------------------------------------
+def _upload_batch(T, dims, trains):
+    cap = [max(t.ttv_rks[k] for t in trains) for k in range(len(dims) + 1)]
+    h = T.DeviceTT(dims, cap, batch=len(trains))
+    for k, t in enumerate(trains):
+        h.upload(k, to_product(t))
+    return h
+
+
+@pytest.mark.parametrize("sweeps", [2, 3])
+@pytest.mark.parametrize("grid", [0, 1])
+def test_als_pivoting_operator_vs_oracle(T, monkeypatch, sweeps, grid):
+    """d = 8, r = 8 on A_piv: 8 (12 with three half sweeps) local systems of 64 / 128 unknowns, every one of them exchanging rows at
+    steps >= 32 (local cond <= 1.5e3); the one-workgroup form and the grid form (TTN_ALS_GRID=1).  Bars as test_als_vs_oracle."""
+    d, r = 8, 8
+    rng = np.random.default_rng(40 + sweeps)
+    A = A_piv(d)
+    b, x0 = O.rand_tt((2,) * d, 3, rng), O.rand_tt((2,) * d, r, rng)
+    with pivot_spy() as log:
+        ref = O.als_linsolve(A, b, x0, sweep_count=sweeps)
+    big = log.beyond_first_panel()
+    assert len(big) >= 8 and max(e[2] for e in big) < 1e4
+    log.assert_pivots_beyond_first_panel(at_least=len(big))
+    if grid:
+        monkeypatch.setenv("TTN_ALS_GRID", "1")
+    got = T.solvers.als_linsolve(to_product(A), to_product(b), to_product(x0), sweep_count=sweeps)
+    assert list(got.ttv_rks) == list(ref.ttv_rks) == list(x0.ttv_rks)
+    assert list(got.ttv_ot) == list(ref.ttv_ot) == _ot_after(d, sweeps)
+    assert tt_rel_diff(to_oracle(got), ref) <= 1e-9
+    assert abs(_resid(A, to_oracle(got), b) - _resid(A, ref, b)) <= 1e-9
+
+
+def test_als_pivoting_mixed_dims_general_operator(T):
+    """dims (2,3,2,3,2,3), rand_tto(dims, 2) + I, ranks [1,2,6,8,6,3,1]: local systems of 36 / 96 / 144 unknowns, local cond <= 2.5e4
+    (asserted), at least 7 of the 8 with N > 32 exchanging rows at steps >= 32."""
+    dims = (2, 3, 2, 3, 2, 3)
+    rng = np.random.default_rng(54)
+    A = O.tto_add(O.rand_tto(dims, 2, rng), id_general(dims))
+    b, x0 = O.rand_tt(dims, 2, rng), O.rand_tt(dims, 8, rng)
+    with pivot_spy() as log:
+        ref = O.als_linsolve(A, b, x0, sweep_count=2)
+    assert len(log.beyond_first_panel()) == 8 and max(e[2] for e in log) <= 2.5e4
+    log.assert_pivots_beyond_first_panel(at_least=7)
+    got = T.solvers.als_linsolve(to_product(A), to_product(b), to_product(x0), sweep_count=2)
+    assert list(got.ttv_rks) == list(ref.ttv_rks) == list(x0.ttv_rks)
+    assert list(got.ttv_ot) == list(ref.ttv_ot) == _ot_after(len(dims), 2)
+    assert tt_rel_diff(to_oracle(got), ref) <= 1e-9
+    assert abs(_resid(A, to_oracle(got), b) - _resid(A, ref, b)) <= 1e-9
+
+
+def test_als_full_rank_on_pivoting_operator_is_exact(T):
+    """Full ranks on A_piv (d = 6): the last local problem is the whole, row-exchanging system, the answer A \\ b to 1e-10."""
+    rng = np.random.default_rng(3)
+    d = 6
+    A = A_piv(d)
+    b = O.rand_tt((2,) * d, 3, rng)
+    x0 = O.rand_tt((2,) * d, [1, 2, 4, 8, 4, 2, 1], rng)
+    with pivot_spy() as log:
+        O.als_linsolve(A, b, x0, sweep_count=2)
+    log.assert_pivots_beyond_first_panel(at_least=len(log.beyond_first_panel()))
+    assert len(log.beyond_first_panel()) >= 4
+    got = T.solvers.als_linsolve(to_product(A), to_product(b), to_product(x0), sweep_count=2)
+    dense = np.linalg.solve(O.qtto_to_matrix(A), O.qtt_to_vector(b))
+    assert np.max(np.abs(O.qtt_to_vector(to_oracle(got)) - dense)) <= 1e-10 * np.max(np.abs(dense))
+
+
+@pytest.mark.parametrize("grid", [0, 1])
+def test_als_batch_with_ragged_rhs_ranks(T, monkeypatch, grid):
+    """Three right-hand sides of ranks 1, 3, 2 in one handle: every train is projected with its OWN ranks (Gb / Hb are laid out per
+    train) in both forms; each train against its single-train oracle run."""
+    d, r = 7, 4
+    rng = np.random.default_rng(90)
+    A = A_piv(d)
+    bs = [O.rand_tt((2,) * d, rb, rng) for rb in (1, 3, 2)]
+    xs = [O.rand_tt((2,) * d, r, rng) for _ in bs]
+    assert len({tuple(b_.ttv_rks) for b_ in bs}) == 3
+    if grid:
+        monkeypatch.setenv("TTN_ALS_GRID", "1")
+    db, dx0 = _upload_batch(T, (2,) * d, bs), _upload_batch(T, (2,) * d, xs)
+    dx = T.DeviceTT((2,) * d, xs[0].ttv_rks, batch=3)
+    T.solvers.als_linsolve_(T.DeviceTTO(to_product(A)), db, dx0, dx, 3)
+    T.device.compress_status(dx)
+    for k in range(3):
+        assert tt_rel_diff(to_oracle(dx.download(k)), O.als_linsolve(A, bs[k], xs[k], sweep_count=3)) <= 1e-9, k
+
+
+def test_als_rank_mismatch_is_reported_for_that_train_only(T):
+    """als_linsolve keeps the start ranks (als.jl:177) and one launch serves one set of ranks: a start train whose ranks differ from
+    the handle's is refused through the handle's status (TTN_ST_RANKS_DIFFER -> 'ranks differ'), read by compress_status; the
+    other trains of the batch are solved as if it were not there, and the status is cleared by the read."""
+    d, r = 6, 4
+    rng = np.random.default_rng(91)
+    A = _spd(d, 2.0)
+    bs = [O.rand_tt((2,) * d, 2, rng) for _ in range(3)]
+    xs = [O.rand_tt((2,) * d, r, rng), O.rand_tt((2,) * d, 2, rng), O.rand_tt((2,) * d, r, rng)]
+    assert list(xs[1].ttv_rks) != list(xs[0].ttv_rks) == list(xs[2].ttv_rks)
+    db, dx0 = _upload_batch(T, (2,) * d, bs), _upload_batch(T, (2,) * d, xs)
+    dx = T.DeviceTT((2,) * d, xs[0].ttv_rks, batch=3)
+    T.solvers.als_linsolve_(T.DeviceTTO(to_product(A)), db, dx0, dx, 2)
+    with pytest.raises((AssertionError, T.TTNError), match="ranks differ"):
+        T.device.compress_status(dx)
+    T.device.compress_status(dx)                                 # cleared on read
+    for k in (0, 2):
+        assert tt_rel_diff(to_oracle(dx.download(k)), O.als_linsolve(A, bs[k], xs[k], sweep_count=2)) <= 1e-9, k
+    left = dx.download(1)                                        # the refused train: orthogonalize(x0) and nothing else
+    assert list(left.ttv_rks) == list(xs[1].ttv_rks)
+    assert tt_rel_diff(to_oracle(left), xs[1]) <= 1e-12

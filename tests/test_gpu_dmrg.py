@@ -9,6 +9,7 @@ import pytest
 
 from oracle import tt_oracle as O
 from tests.helpers import to_oracle, to_product, tt_norm_stable, tt_rel_diff
+from tests.linsolve_reference import A_cd, A_piv, mixed_dims_operator, oracle_solves_by_lu, pivot_spy
 
 pytestmark = pytest.mark.gpu
 
@@ -196,3 +197,104 @@ def test_dmrg_large_local_systems_beyond_the_dense_limit(T):
     assert list(got.ttv_rks) == list(ref.ttv_rks), (got.ttv_rks, ref.ttv_rks)
     assert tt_rel_diff(to_oracle(got), ref) <= 1e-7
     assert abs(_resid(A, to_oracle(got), b) - _resid(A, ref, b)) <= 1e-7
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Non-symmetric operators.  Dense branch: the reference solves `Hermitian(K) \\ Pb` (dmrg.jl:53,174) — the UPPER TRIANGLE of K in ITS
+# ordering (r_l, n_i n_{i+1}, r_r) of the unknowns, which the device mirrors (k_mals_linsolve, two-site assembly); the matrix-free
+# branch runs CG on 1/2 (K + K^T).  For a symmetric A all three are K; for A_cd they are three different systems and the two
+# branches differ at O(1) in the reference itself (asserted below on the oracle), so each device branch is held to ITS oracle twin.
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["A_piv", "A_cd"])
+def test_dmrg_nonsymmetric_operator_dense_vs_oracle(T, name):
+    d = 8
+    rng = np.random.default_rng(60)
+    A = {"A_piv": A_piv, "A_cd": A_cd}[name](d)
+    b, x0 = O.rand_tt((2,) * d, 2, rng), O.rand_tt((2,) * d, 4, rng)
+    kw = dict(tol=1e-10, sweep_schedule=[2], rmax_schedule=[8])
+    with pivot_spy() as log:
+        ref = O.dmrg_linsolve(A, b, x0, **kw)
+    assert list(ref.ttv_rks) == [1, 2, 4, 8, 8, 8, 4, 2, 1]
+    if name == "A_piv":
+        big = log.beyond_first_panel()
+        assert len(big) == 9 and max(e[0] for e in big) == 256 and max(e[2] for e in big) <= 1.5e3
+        log.assert_pivots_beyond_first_panel(at_least=9)
+    got = T.solvers.dmrg_linsolve(to_product(A), to_product(b), to_product(x0), **kw)
+    assert T.solvers.dmrg_cg_iterations(1)[0] == 0
+    assert list(got.ttv_rks) == list(ref.ttv_rks)
+    assert list(got.ttv_ot) == list(ref.ttv_ot) == [0] + [-1] * (d - 1)
+    assert tt_rel_diff(to_oracle(got), ref) <= 1e-8
+
+
+def test_dmrg_matrix_free_cg_on_nonsymmetric_operator_vs_oracle(T):
+    """it_solver on A_cd (symmetric part positive definite): CG on 1/2 (K + K^T) with K != K^T, so the K^T half of
+    wg_two_site_apply carries weight.  Against the oracle's CG run: ranks exact, tensor 1e-7, iteration count within 10 %."""
+    d = 8
+    rng = np.random.default_rng(62)
+    A = A_cd(d)
+    b, x0 = O.rand_tt((2,) * d, 2, rng), O.rand_tt((2,) * d, 3, rng)
+    kw = dict(tol=1e-10, sweep_schedule=[2], rmax_schedule=[8])
+    st = {}
+    ref = O.dmrg_linsolve(A, b, x0, it_solver=True, linsolv_tol=1e-12, stats=st, **kw)
+    dense = O.dmrg_linsolve(A, b, x0, **kw)
+    vd = O.qtt_to_vector(dense)
+    assert np.linalg.norm(O.qtt_to_vector(ref) - vd) > 1e-3 * np.linalg.norm(vd)       # the two branches solve different systems here
+    got = T.solvers.dmrg_linsolve(to_product(A), to_product(b), to_product(x0), it_solver=True, linsolv_tol=1e-12, **kw)
+    iters = T.solvers.dmrg_cg_iterations(1)[0]
+    assert iters > 0 and abs(iters - st["cg_iterations"]) <= max(4, st["cg_iterations"] // 10), (iters, st)
+    assert list(got.ttv_rks) == list(ref.ttv_rks)
+    assert list(got.ttv_ot) == list(ref.ttv_ot)
+    assert tt_rel_diff(to_oracle(got), ref) <= 1e-7
+
+
+@pytest.mark.parametrize("it_solver", [False, True])
+def test_dmrg_mixed_dims_vs_oracle(T, it_solver):
+    """dims (2,3,2,3,2), dense and CG.  With n_i != n_{i+1} the start vector update_left hands to CG is the two-site block with its
+    merged physical index read back in the other radix (dmrg.jl:331-336: J of site i+1 fast, then taken as i_1 + n_i i_2); the
+    oracle restates that and the device builds the same vector, so the iteration counts are held to the usual 10 %."""
+    dims = (2, 3, 2, 3, 2)
+    rng = np.random.default_rng(63)
+    A = mixed_dims_operator(dims, rng)
+    b, x0 = O.rand_tt(dims, 2, rng), O.rand_tt(dims, 2, rng)
+    kw = dict(tol=1e-10, sweep_schedule=[3], rmax_schedule=[6])
+    if it_solver:
+        kw.update(it_solver=True, linsolv_tol=1e-12)
+    st = {}
+    ref = O.dmrg_linsolve(A, b, x0, stats=st, **kw)
+    got = T.solvers.dmrg_linsolve(to_product(A), to_product(b), to_product(x0), **kw)
+    iters = T.solvers.dmrg_cg_iterations(1)[0]
+    if it_solver:
+        assert iters > 0 and abs(iters - st["cg_iterations"]) <= max(4, st["cg_iterations"] // 10), (iters, st)
+    else:
+        assert iters == 0
+    assert list(got.ttv_rks) == list(ref.ttv_rks) and max(ref.ttv_rks) == 6
+    assert tt_rel_diff(to_oracle(got), ref) <= (1e-7 if it_solver else 1e-8)
+
+
+def test_dmrg_ragged_batch(T):
+    """Three trains that differ in the ranks of b AND of the start train, in one handle: each against its single-train oracle run.
+    (An input on which the oracle itself moves by more than 1e-9 when its local solves take another rounding path — LU instead of the
+    symmetric-indefinite factorisation — cannot carry a 1e-8 bar; asserted not to be the case here.)"""
+    d = 7
+    sched, rmaxs = [2, 3], [4, 6]
+    rng = np.random.default_rng(66)
+    A = A_piv(d)
+    bs = [O.rand_tt((2,) * d, rb, rng) for rb in (1, 3, 2)]
+    x0s = [O.rand_tt((2,) * d, r0, rng) for r0 in (2, 1, 4)]
+    assert len({tuple(v.ttv_rks) for v in bs}) == 3 and len({tuple(v.ttv_rks) for v in x0s}) == 3
+    cap = lambda ts: [max(t.ttv_rks[k] for t in ts) for k in range(d + 1)]          # noqa: E731
+    db, dx0 = T.DeviceTT((2,) * d, cap(bs), batch=3), T.DeviceTT((2,) * d, cap(x0s), batch=3)
+    for i in range(3):
+        db.upload(i, to_product(bs[i]))
+        dx0.upload(i, to_product(x0s[i]))
+    dx = T.DeviceTT((2,) * d, T.solvers.mals_capacity((2,) * d, cap(x0s), max(rmaxs)), batch=3)
+    T.solvers.dmrg_linsolve_(T.DeviceTTO(to_product(A)), db, dx0, dx, 1e-9, sched, rmaxs)
+    T.device.compress_status(dx)
+    for i in range(3):
+        ref = O.dmrg_linsolve(A, bs[i], x0s[i], tol=1e-9, sweep_schedule=sched, rmax_schedule=rmaxs)
+        with oracle_solves_by_lu():                              # the reference's own sensitivity on this input: far below the bar
+            alt = O.dmrg_linsolve(A, bs[i], x0s[i], tol=1e-9, sweep_schedule=sched, rmax_schedule=rmaxs)
+        assert list(alt.ttv_rks) == list(ref.ttv_rks) and tt_rel_diff(alt, ref) <= 1e-9, i
+        got = dx.download(i)
+        assert list(got.ttv_rks) == list(ref.ttv_rks), i
+        assert tt_rel_diff(to_oracle(got), ref) <= 1e-8, i

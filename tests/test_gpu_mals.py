@@ -8,6 +8,7 @@ import pytest
 
 from oracle import tt_oracle as O
 from tests.helpers import to_oracle, to_product, tt_norm_stable, tt_rel_diff
+from tests.linsolve_reference import A_cd, A_piv, mixed_dims_operator, oracle_solves_by_lu, pivot_spy
 
 pytestmark = pytest.mark.gpu
 
@@ -108,3 +109,69 @@ def test_mals_errors(T):
     x12 = T.DeviceTT.from_host(to_product(O.rand_tt((2,) * 12, 2, rng)))
     with pytest.raises(T.TTNError):                            # two-site systems above the device limit
         T.solvers.mals_linsolve_(dA, x12, x12, big, 1e-10, 40)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Non-symmetric operators.  The reference solves `Hermitian(K) \\ b` (mals.jl:156,167): it reads the UPPER TRIANGLE of the local
+# matrix only, and so does the oracle.  For a symmetric A that is K; for A_piv / A_cd it is another matrix, whose solution is O(1)
+# away from K \\ b (tests/test_cpu_linsolve_inputs.py pins 0.1 < distance on A_cd) — a device that ran its LU on the full K would
+# fail the 1e-8 below by eight orders of magnitude.  A_piv also makes the LU exchange rows at steps >= 32 in all 9 systems with
+# N > 32 (up to N = 256), which Delta + sigma I never does.
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["A_piv", "A_cd"])
+def test_mals_nonsymmetric_operator_vs_oracle(T, name):
+    d = 8
+    rng = np.random.default_rng(60)
+    A = {"A_piv": A_piv, "A_cd": A_cd}[name](d)
+    b, x0 = O.rand_tt((2,) * d, 2, rng), O.rand_tt((2,) * d, 4, rng)
+    with pivot_spy() as log:
+        ref = O.mals_linsolve(A, b, x0, tol=1e-10, rmax=8)
+    assert list(ref.ttv_rks) == [1, 2, 4, 8, 8, 8, 4, 2, 1]
+    if name == "A_piv":
+        big = log.beyond_first_panel()
+        assert len(big) == 9 and max(e[0] for e in big) == 256 and max(e[2] for e in big) <= 1.5e3
+        log.assert_pivots_beyond_first_panel(at_least=9)
+    got = T.solvers.mals_linsolve(to_product(A), to_product(b), to_product(x0), tol=1e-10, rmax=8)
+    assert list(got.ttv_rks) == list(ref.ttv_rks)
+    assert list(got.ttv_ot) == list(ref.ttv_ot) == [0] + [1] * (d - 1)
+    assert tt_rel_diff(to_oracle(got), ref) <= 1e-8
+
+
+def test_mals_mixed_dims_vs_oracle(T):
+    """dims (2,3,2,3,2): n1 != n2 in every window (the environments and the two SVD layouts take every size from its own site)."""
+    dims = (2, 3, 2, 3, 2)
+    rng = np.random.default_rng(63)
+    A = mixed_dims_operator(dims, rng)
+    b, x0 = O.rand_tt(dims, 2, rng), O.rand_tt(dims, 2, rng)
+    ref = O.mals_linsolve(A, b, x0, tol=1e-10, rmax=6)
+    got = T.solvers.mals_linsolve(to_product(A), to_product(b), to_product(x0), tol=1e-10, rmax=6)
+    assert list(got.ttv_rks) == list(ref.ttv_rks) and max(ref.ttv_rks) == 6
+    assert tt_rel_diff(to_oracle(got), ref) <= 1e-8
+
+
+def test_mals_ragged_batch(T):
+    """Three trains that differ in the ranks of b AND of the start train, in one handle: each against its single-train oracle run.
+    (An input on which the oracle itself moves by more than 1e-9 when its local solves take another rounding path — LU instead of the
+    symmetric-indefinite factorisation — cannot carry a 1e-8 bar; asserted not to be the case here.)"""
+    d, rmax = 7, 6
+    rng = np.random.default_rng(64)
+    A = A_piv(d)
+    bs = [O.rand_tt((2,) * d, rb, rng) for rb in (1, 3, 2)]
+    x0s = [O.rand_tt((2,) * d, r0, rng) for r0 in (2, 1, 4)]
+    assert len({tuple(v.ttv_rks) for v in bs}) == 3 and len({tuple(v.ttv_rks) for v in x0s}) == 3
+    cap = lambda ts: [max(t.ttv_rks[k] for t in ts) for k in range(d + 1)]          # noqa: E731
+    db, dx0 = T.DeviceTT((2,) * d, cap(bs), batch=3), T.DeviceTT((2,) * d, cap(x0s), batch=3)
+    for i in range(3):
+        db.upload(i, to_product(bs[i]))
+        dx0.upload(i, to_product(x0s[i]))
+    dx = T.DeviceTT((2,) * d, T.solvers.mals_capacity((2,) * d, cap(x0s), rmax), batch=3)
+    T.solvers.mals_linsolve_(T.DeviceTTO(to_product(A)), db, dx0, dx, 1e-9, rmax)
+    T.device.compress_status(dx)
+    for i in range(3):
+        ref = O.mals_linsolve(A, bs[i], x0s[i], tol=1e-9, rmax=rmax)
+        with oracle_solves_by_lu():                              # the reference's own sensitivity on this input: far below the bar
+            alt = O.mals_linsolve(A, bs[i], x0s[i], tol=1e-9, rmax=rmax)
+        assert list(alt.ttv_rks) == list(ref.ttv_rks) and tt_rel_diff(alt, ref) <= 1e-9, i
+        got = dx.download(i)
+        assert list(got.ttv_rks) == list(ref.ttv_rks), i
+        assert tt_rel_diff(to_oracle(got), ref) <= 1e-8, i
