@@ -623,6 +623,11 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * includes. */
 #include "ttn_cross_batch.h"
 
+/* ---- expectation values (csrc/ttn_expect_kernels.h) ----------------------------------------------------------------
+ * <x, A y> per train without forming A y: ttn_sandwich (result on the host, synchronises as ttn_dot) and ttn_sandwich_dev (result in
+ * device memory, asynchronous).  Declared in ttn_expect.h, which this header includes. */
+#include "ttn_expect.h"
+
 #ifdef __cplusplus
 }
 #endif

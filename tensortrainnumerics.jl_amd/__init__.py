@@ -6,10 +6,10 @@ The arithmetic lives in csrc/*.h, csrc/ttn_api.hip -> libttn_hip.so (hand-writte
 """
 from . import _lib, constructors, cross, device, grad, opalg, pipeline, qtt, qttnd, shard, solvers, tdvp, tt
 from ._lib import TTNError, build, ensure_init, finalize
-from .constructors import (Delta, Delta_DN, Delta_ND, Delta_NN, Nabla, fourier_qtto, function_to_qtt, function_to_qtt_uniform, function_to_tensor, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn,
+from .constructors import (Delta, Delta_DN, Delta_ND, Delta_NN, H_mu, H_munu, Nabla, fourier_qtto, function_to_qtt, function_to_qtt_uniform, function_to_tensor, heisenberg_xyz_tto, id_tto, ising_tto, portable_randn,
                            qtt_basis_vector, qtt_cos, qtt_exp, qtt_polynom, qtt_sin, qtt_to_function, qtt_to_vector, qtto_constant_prolongation,
-                           qtto_linear_prolongation, qtto_prolongation, rand_tt, reverse_qtt_bits, shift, toeplitz_to_qtto,
-                           xxx_tto, xxz_tto, zeros_tt, zeros_tto)
+                           qtto_linear_prolongation, qtto_prolongation, pauli_matrix, pauli_pair_sum_tto, pauli_sum_tto, rand_tt, reverse_qtt_bits, shift,
+                           toeplitz_to_qtto, xxx_tto, xxz_tto, xy_tto, zeros_tt, zeros_tto)
 from .cross import DMRG, Greedy, MaxVol, MaxVolPivot, RandomPivot, tt_cross, tt_cross_batch, tt_integrate, tt_integrate_batch
 from .device import DeviceRectTTO, DeviceTT, DeviceTTO, StreamTimer
 from .grad import apply_pullback, apply_rrule, cores_axpby, cores_dot, dot_pullback, dot_rrule, rayleigh_gradient, rayleigh_value_and_grad
@@ -19,7 +19,7 @@ from .solvers import (als_eigsolve, als_gen_eigsolv, crank_nicholson_method, dmr
                       mals_eigsolve, rk4_method)
 from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_to_array
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
-from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, div, dot, euclidean_distance, hadamard, increase_ranks,
-                 norm, orthogonalize, r_and_d_to_rks, scale, sub, tt_compress_, tt_up_rks, ttv_to_tensor)
+from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, div, dot, euclidean_distance, expect, hadamard,
+                 increase_ranks, norm, orthogonalize, r_and_d_to_rks, rayleigh, sandwich, scale, sub, tt_compress_, tt_up_rks, ttv_to_tensor)
 
 __all__ = [n for n in dir() if not n.startswith("__")]

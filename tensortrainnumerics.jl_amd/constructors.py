@@ -424,6 +424,70 @@ def xxx_tto(d: int, J: float = 1.0, h: float = 0.0, field="z") -> TToperator:
     return heisenberg_xyz_tto(d, jx=J, jy=J, jz=J, lam=h, field=field)
 
 
+def xy_tto(d: int, jx: float = 1.0, jy: float = 1.0, h: float = 0.0, field="z") -> TToperator:
+    """jx H_xx + jy H_yy + h H_field (src/tt_operators.jl:262-271)."""
+    return heisenberg_xyz_tto(d, jx=jx, jy=jy, jz=0.0, lam=h, field=field)
+
+
+# Pauli sums (src/tt_operators.jl:45-151): the one- and two-site building blocks of the Hamiltonians above as operators of their own —
+# what a measurement such as the magnetisation sum_k Z_k contracts against a state (device.expect).
+def pauli_matrix(mu) -> np.ndarray:
+    """The Pauli matrix of axis x or z (src/tt_operators.jl:45-54).  sigma_y alone is complex: TTNError, as in _pauli_pair_factors."""
+    a = _pauli_axis(mu)
+    if a == "y":
+        from ._lib import TTNError
+        raise TTNError("a single sigma_y factor is complex: only real (Float64) operators are offered")
+    return (_PAULI_X if a == "x" else _PAULI_Z).copy()
+
+
+def pauli_sum_tto(mu, d: int) -> TToperator:
+    """H_mu = sum_k I (x) ... (x) P_mu (x) ... (x) I on d spin-1/2 sites, open boundaries, ranks [1, 2, ..., 2, 1]
+    (src/tt_operators.jl:75-107): bond state 1 = "P not placed yet", bond state 0 = "placed"; d == 1 is the single core P."""
+    assert d >= 1, "number of spin sites must be at least 1"
+    P, Id = pauli_matrix(mu), np.eye(2)
+    if d == 1:
+        out = zeros_tto((2,), [1, 1])
+        out.tto_vec[0][:, :, 0, 0] = P
+        return out
+    out = zeros_tto((2,) * d, [1] + [2] * (d - 1) + [1])
+    c = out.tto_vec[0]
+    c[:, :, 0, 0], c[:, :, 0, 1] = P, Id
+    for k in range(1, d - 1):
+        c = out.tto_vec[k]
+        c[:, :, 0, 0], c[:, :, 1, 0], c[:, :, 1, 1] = Id, P, Id
+    c = out.tto_vec[d - 1]
+    c[:, :, 0, 0], c[:, :, 1, 0] = Id, P
+    return out
+
+
+def pauli_pair_sum_tto(mu, nu, d: int) -> TToperator:
+    """H_{mu,nu} = sum_k I (x) ... (x) P_mu (x) P_nu (x) ... (x) I (sites k, k + 1), open boundaries, ranks [1, 3, ..., 3, 1]
+    (src/tt_operators.jl:118-148): bond state 2 = "nothing placed", 1 = "P_mu placed, P_nu is due", 0 = "both placed".  Mixed pairs
+    with one sigma_y are complex: TTNError; (y, y) is real."""
+    assert d >= 2, "nearest-neighbor Pauli pair sum needs at least 2 spin sites"
+    P1, P2 = _pauli_pair_factors(mu, nu)
+    Id = np.eye(2)
+    out = zeros_tto((2,) * d, [1] + [3] * (d - 1) + [1])
+    c = out.tto_vec[0]
+    c[:, :, 0, 1], c[:, :, 0, 2] = P1, Id
+    for k in range(1, d - 1):
+        c = out.tto_vec[k]
+        c[:, :, 0, 0], c[:, :, 1, 0], c[:, :, 2, 1], c[:, :, 2, 2] = Id, P2, P1, Id
+    c = out.tto_vec[d - 1]
+    c[:, :, 0, 0], c[:, :, 1, 0] = Id, P2
+    return out
+
+
+def H_mu(mu, d: int) -> TToperator:
+    """Alias of pauli_sum_tto (src/tt_operators.jl:150)."""
+    return pauli_sum_tto(mu, d)
+
+
+def H_munu(mu, nu, d: int) -> TToperator:
+    """Alias of pauli_pair_sum_tto (src/tt_operators.jl:151)."""
+    return pauli_pair_sum_tto(mu, nu, d)
+
+
 # ---------------------------------------------------------------------------------------------
 # QTT Fourier transform — src/tt_transformations.jl (arXiv:2404.03182): Chebyshev-Lobatto interpolation of the phase in every core.
 # ---------------------------------------------------------------------------------------------

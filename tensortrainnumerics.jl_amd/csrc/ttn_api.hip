@@ -24,6 +24,7 @@
 #include "ttn_grad_kernels.h"
 #include "ttn_rect_kernels.h"
 #include "ttn_step_kernels.h"
+#include "ttn_expect_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -275,6 +276,12 @@ int ttn_init(int device) {
         {(const void*)k_cross_maxvol<true>, TTN_XV_LDS_BYTES},
         {(const void*)k_zcompress, TTN_ZC_LDS_BYTES},
         {(const void*)k_cross_batch_site, TTN_XB_LDS_BYTES},
+        {(const void*)k_expect<0>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expect<1>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expect<2>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expect<3>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expect<4>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expect<5>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
     };
     for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
@@ -2587,6 +2594,71 @@ int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
     HIPCHK(hipEventRecord(g_launch_ev1, g_stream));       // ttn_last_launch_ms: the kernel alone (this call goes on to copy and synchronise)
     g_have_launch_ms = true;
     HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * a->batch, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return TTN_OK;
+}
+
+// <x, A y> (include/ttn_expect.h): k_expect, one workgroup per train; d_out is device memory
+static_assert(EXPECT_QTT_RMAX == TTN_EXPECT_QTT_MAX_RANK && EXPECT_QTT_OPR_MAX == TTN_EXPECT_QTT_MAX_OP_RANK, "ttn_expect.h and ttn_expect_kernels.h disagree");
+static int sandwich_launch(const char* who, ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, double* d_out) {
+    F64_ONLY(who, {x, y}, {A});
+    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    const int d = x->d;
+    if (d > EXPECT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: chains longer than 480 sites are not supported");
+    if (x->stride >= (1LL << 31) || y->stride >= (1LL << 31) || A->off.back() >= (1LL << 31))
+        return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: a train or an operator of 2^31 doubles or more");
+    long long rxmax = 1, rymax = 1, Rmax = 1, nmax = 1;
+    for (int m = 0; m <= d; ++m) {
+        rxmax = std::max<long long>(rxmax, x->bound[m]); rymax = std::max<long long>(rymax, y->bound[m]); Rmax = std::max<long long>(Rmax, A->rks[m]);
+    }
+    bool qtt = Rmax <= EXPECT_QTT_OPR_MAX;
+    for (int k = 0; k < d; ++k) { nmax = std::max<long long>(nmax, x->dims[k]); qtt = qtt && x->dims[k] == 2; }
+    // 32-bit element offsets in the workgroup GEMM: the workspace of one train stays below 2^31 doubles
+    if (rxmax >= (1LL << 31) || rymax >= (1LL << 31) || Rmax >= (1LL << 31) || rxmax * rymax >= (1LL << 31) || rxmax * rymax * Rmax >= (1LL << 31)
+        || (2 + 2 * nmax) * rxmax * rymax * Rmax >= (1LL << 31))
+        return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: ranks too large (the three-layer state of one train reaches 2^31 doubles)");
+    const long long general = (2 + 2 * nmax) * rxmax * rymax * Rmax;
+    const long long per_train = std::max<long long>(general, qtt ? Rmax * EXPECT_IMG_STATE : 0) + 16;
+    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch);
+    if (rc) return rc;
+    ExpectArgs P;
+    P.x = x->dev(); P.y = y->dev(); P.A = A->dev();
+    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
+    P.rxmax = (int)rxmax; P.rymax = (int)rymax; P.Rmax = (int)Rmax; P.nmax = (int)nmax;
+    P.out = d_out;
+    const dim3 grid(x->batch), block(TTN_WG);
+    const size_t lds = EXPECT_LDS_BYTES(d);
+    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
+    switch (qtt ? (int)Rmax : 0) {
+        case 1: hipLaunchKernelGGL(k_expect<1>, grid, block, lds, g_stream, P); break;
+        case 2: hipLaunchKernelGGL(k_expect<2>, grid, block, lds, g_stream, P); break;
+        case 3: hipLaunchKernelGGL(k_expect<3>, grid, block, lds, g_stream, P); break;
+        case 4: hipLaunchKernelGGL(k_expect<4>, grid, block, lds, g_stream, P); break;
+        case 5: hipLaunchKernelGGL(k_expect<5>, grid, block, lds, g_stream, P); break;
+        default: hipLaunchKernelGGL(k_expect<0>, grid, block, lds, g_stream, P); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
+    g_have_launch_ms = true;
+    return TTN_OK;
+}
+
+int ttn_sandwich_dev(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, double* d_out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !A || !y || !d_out) return fail(TTN_ERR_ARG, "null pointer");
+    return sandwich_launch("ttn_sandwich_dev", x, A, y, d_out);
+}
+
+int ttn_sandwich(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !A || !y || !out) return fail(TTN_ERR_ARG, "null pointer");
+    int rc = g_dout.ensure(sizeof(double) * x->batch);
+    if (rc) return rc;
+    if ((rc = sandwich_launch("ttn_sandwich", x, A, y, g_dout.as<double>()))) return rc;
+    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * x->batch, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return TTN_OK;
 }

@@ -495,6 +495,51 @@ def dot(a: DeviceTT, b: DeviceTT) -> np.ndarray:
     return np.array(out[:])
 
 
+# limits of the on-chip route of ttn_sandwich (TTN_EXPECT_QTT_MAX_RANK / TTN_EXPECT_QTT_MAX_OP_RANK of include/ttn_expect.h): every
+# n_k = 2, train ranks and operator ranks up to these; beyond them a train takes the general route — the same number
+EXPECT_QTT_MAX_RANK = 64
+EXPECT_QTT_MAX_OP_RANK = 5
+
+
+def _sandwich_args(x: DeviceTT, A: DeviceTTO, y: DeviceTT):
+    if not isinstance(A, DeviceTTO):
+        raise TypeError(f"sandwich: expected a DeviceTTO, got {type(A).__name__}")
+    if not isinstance(x, DeviceTT) or not isinstance(y, DeviceTT):
+        raise TypeError("sandwich: expected DeviceTT trains")
+
+
+def sandwich(x: DeviceTT, A: DeviceTTO, y: DeviceTT) -> np.ndarray:
+    """<x_b, A y_b> per train in one sweep over the three cores of every site (ttn_sandwich): what ``dot(x, apply(A, y))`` returns up
+    to rounding, without the train A y.  x may be y.  Float64 only.  Synchronises, as ``dot``."""
+    _sandwich_args(x, A, y)
+    out = (C.c_double * x.batch)()
+    _lib.check(_lib.lib().ttn_sandwich(x.h, A.h, y.h, out))
+    return np.array(out[:])
+
+
+def sandwich_dev(x: DeviceTT, A: DeviceTTO, y: DeviceTT, out=None):
+    """``sandwich`` into a float64 device tensor of ``batch`` entries (``out``, or a new one), asynchronously on the library stream:
+    no number crosses to the host.  The tensor must not be read on another stream before ``sync()``."""
+    import torch
+    _sandwich_args(x, A, y)
+    if out is None:
+        out = torch.empty(x.batch, dtype=torch.float64, device="cuda")
+    if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.numel() != x.batch:
+        raise TypeError("sandwich_dev: out must be a contiguous float64 device tensor with one entry per train")
+    _lib.check(_lib.lib().ttn_sandwich_dev(x.h, A.h, y.h, C.c_void_p(out.data_ptr())))
+    return out
+
+
+def expect(A: DeviceTTO, x: DeviceTT) -> np.ndarray:
+    """<x_b, A x_b> per train: ``sandwich(x, A, x)``."""
+    return sandwich(x, A, x)
+
+
+def rayleigh(A: DeviceTTO, x: DeviceTT) -> np.ndarray:
+    """<x_b, A x_b> / <x_b, x_b> per train — the reference's ``real(dot(psi, H * psi)) / real(dot(psi, psi))``."""
+    return expect(A, x) / dot(x, x)
+
+
 def norm(a: DeviceTT) -> np.ndarray:
     out = (C.c_double * a.batch)()
     _lib.check(_lib.lib().ttn_norm(a.h, out))

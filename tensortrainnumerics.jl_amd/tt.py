@@ -273,6 +273,33 @@ def dot(A: TTvector, B: TTvector):
     return complex(out[0], out[1]) if cplx else float(out[0])
 
 
+def sandwich(x: TTvector, A: TToperator, y: TTvector) -> float:
+    """<x, A y> = dot(x, A * y) in one sweep over the three cores of every site (ttn_sandwich): A * y is never formed.  The trains and
+    the operator are uploaded, the kernel runs, the handles are freed.  Float64 only."""
+    from .device import DeviceTT, DeviceTTO, sandwich as dev_sandwich
+    assert tuple(A.tto_dims) == tuple(x.ttv_dims) == tuple(y.ttv_dims), "Incompatible dimensions"
+    dx = dA = dy = None
+    try:
+        dx = DeviceTT.from_host(x)
+        dy = dx if y is x else DeviceTT.from_host(y)
+        dA = DeviceTTO(A)
+        return float(dev_sandwich(dx, dA, dy)[0])
+    finally:
+        for h in (dA, dy if dy is not dx else None, dx):
+            if h is not None:
+                h.free()
+
+
+def expect(A: TToperator, x: TTvector) -> float:
+    """<x, A x>: ``sandwich(x, A, x)``."""
+    return sandwich(x, A, x)
+
+
+def rayleigh(A: TToperator, x: TTvector) -> float:
+    """<x, A x> / <x, x> — the reference's ``real(dot(psi, H * psi)) / real(dot(psi, psi))`` without the train H * psi."""
+    return expect(A, x) / dot(x, x)
+
+
 def norm(a: TTvector) -> float:
     """norm(a) — src/tt_operations.jl:465-470."""
     v = dot(a, a).real          # norm = sqrt(max(real(dot(a, a)), 0))
