@@ -628,6 +628,11 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * device memory, asynchronous).  Declared in ttn_expect.h, which this header includes. */
 #include "ttn_expect.h"
 
+/* ---- the gradient of an expectation value (csrc/ttn_expect_grad_kernels.h) ------------------------------------------
+ * ttn_sandwich_pullback: the tangents of <x, A y> with respect to the cores of x and y on the three-layer environments, A y never
+ * formed.  Declared in ttn_expect_grad.h, which this header includes. */
+#include "ttn_expect_grad.h"
+
 #ifdef __cplusplus
 }
 #endif

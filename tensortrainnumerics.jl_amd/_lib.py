@@ -204,6 +204,11 @@ EXPECT_SIGNATURES = {
     "ttn_sandwich_dev": (C.c_int, [handle, handle, handle, C.c_void_p]),
 }
 
+# the pullback of <x, A y>, include/ttn_expect_grad.h
+EXPECT_GRAD_SIGNATURES = {
+    "ttn_sandwich_pullback": (C.c_int, [handle, handle, handle, p_f64, handle, handle, p_f64]),
+}
+
 _lib = None
 
 
@@ -212,7 +217,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     without a GPU."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
     srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
-             os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h")]
+             os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h"),
+             os.path.join(INCLUDE, "ttn_expect_grad.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -236,7 +242,7 @@ def lib() -> C.CDLL:
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
-            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()):
+            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -25,6 +25,7 @@
 #include "ttn_rect_kernels.h"
 #include "ttn_step_kernels.h"
 #include "ttn_expect_kernels.h"
+#include "ttn_expect_grad_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -282,6 +283,14 @@ int ttn_init(int device) {
         {(const void*)k_expect<3>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
         {(const void*)k_expect<4>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
         {(const void*)k_expect<5>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_chain<0>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_chain<1>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_chain<2>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_chain<3>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_chain<4>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_chain<5>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
+        {(const void*)k_expgrad_core_gen<false>, sizeof(double) * GEMM_LDS_TOTAL},
+        {(const void*)k_expgrad_core_gen<true>, sizeof(double) * GEMM_LDS_TOTAL},
     };
     for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
     { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
@@ -2784,6 +2793,92 @@ int ttn_dot_pullback(ttn_tt_t a, ttn_tt_t b, const double* delta, ttn_tt_t abar,
     S_.env = C_.env; S_.W = W; S_.delta = d_delta;
     hipLaunchKernelGGL(k_grad_sandwich, dim3((unsigned)tiles, 2 * d, batch), dim3(GRAD_SW_TB), 0, g_stream, S_);
     HIPCHK(hipGetLastError());
+    if (out) {
+        HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+    }
+    return TTN_OK;
+}
+
+// The pullback of <x, A y> on the three-layer environments (include/ttn_expect_grad.h, csrc/ttn_expect_grad_kernels.h): A y is never formed.
+int ttn_sandwich_pullback(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, const double* delta, ttn_tt_t xbar, ttn_tt_t ybar, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!x || !A || !y) return fail(TTN_ERR_ARG, "ttn_sandwich_pullback: null handle");
+    if (!xbar && !ybar) return fail(TTN_ERR_ARG, "ttn_sandwich_pullback: neither xbar nor ybar is given");
+    if ((xbar && (xbar == x || xbar == y || xbar == ybar)) || (ybar && (ybar == x || ybar == y)))
+        return fail(TTN_ERR_ARG, "ttn_sandwich_pullback: an output must not alias an operand or the other output");
+    if (!same_dims(A->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
+    int rc = grad_common("ttn_sandwich_pullback", {x, y, xbar, ybar});
+    if (rc) return rc;
+    if (A->el == 2) return refuse_c64("ttn_sandwich_pullback");
+    const int d = x->d, batch = x->batch;
+    if (d > EXPECT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: chains longer than 480 sites are not supported");
+    if (A->off.back() >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: an operator of 2^31 doubles or more");
+    if (batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: more than 65535 trains");
+    for (int m = 0; m <= d; ++m)
+        if ((xbar && xbar->cap[m] < x->bound[m]) || (ybar && ybar->cap[m] < y->bound[m]))
+            return fail(TTN_ERR_CAPACITY, "ttn_sandwich_pullback: destination capacity too small");
+    long long rxmax = 1, rymax = 1, Rmax = 1, nmax = 1, W = 1;
+    bool wbig = false;
+    for (int m = 0; m <= d; ++m) {
+        rxmax = std::max<long long>(rxmax, x->bound[m]); rymax = std::max<long long>(rymax, y->bound[m]); Rmax = std::max<long long>(Rmax, A->rks[m]);
+        if (x->bound[m] >= (1LL << 31) || y->bound[m] >= (1LL << 31) || A->rks[m] >= (1LL << 31) || x->bound[m] * y->bound[m] >= (1LL << 31)) wbig = true;
+        else W = std::max<long long>(W, x->bound[m] * y->bound[m] * A->rks[m]);
+    }
+    bool qtt = Rmax <= EXPECT_QTT_OPR_MAX;
+    for (int k = 0; k < d; ++k) { nmax = std::max<long long>(nmax, x->dims[k]); qtt = qtt && x->dims[k] == 2; }
+    // 32-bit element offsets in the workgroup GEMM, as in ttn_sandwich
+    if (wbig || rxmax * rymax >= (1LL << 31) || rxmax * rymax * Rmax >= (1LL << 31) || (2 + 2 * nmax) * rxmax * rymax * Rmax >= (1LL << 31))
+        return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: ranks too large (the three-layer state of one train reaches 2^31 doubles)");
+    // workspace per train (doubles): 2 (d + 1) W  both chains with every state, W = max_m rx_m R_m ry_m (even)
+    //                              + 2 wsz        per chain: U and V of a GEMM site, 2 nmax S with S = rxmax Rmax rymax, or the Rmax 64 x 64
+    //                                             images of the on-chip G chain
+    //                              + 4 d nmax S   T1 and T2 of the 2 d outputs of the general gradient route — absent when every train is
+    //                                             known on the host to be of the on-chip class
+    W = (W + 1) & ~1LL;
+    const long long S = rxmax * Rmax * rymax;
+    const long long wsz = (std::max<long long>(2 * nmax * S, qtt ? Rmax * EXPECT_IMG_STATE : 0) + 1) & ~1LL;
+    const bool all_chip = qtt && rxmax <= EXPECT_QTT_RMAX && rymax <= EXPECT_QTT_RMAX;
+    const long long gw = all_chip ? 0 : 4LL * d * nmax * S;
+    // and, behind it all, one 32-bit route word per train.
+    const size_t per_train = (size_t)(2LL * (d + 1) * W + 2 * wsz + gw);
+    if ((rc = g_scratch.ensure(sizeof(double) * per_train * batch + sizeof(int) * batch))) return rc;
+    if ((rc = g_dout.ensure(sizeof(double) * batch))) return rc;
+    const double* d_delta = nullptr;
+    if ((rc = grad_coef(delta, batch, 0, d_delta))) return rc;
+    if (xbar) grad_tangent_of(xbar, x);
+    if (ybar) grad_tangent_of(ybar, y);
+    ExpGradArgs P;
+    P.x = x->dev(); P.y = y->dev(); P.A = A->dev();
+    P.xbar = xbar ? xbar->dev() : TTDev{}; P.ybar = ybar ? ybar->dev() : TTDev{};
+    P.env = g_scratch.as<double>();
+    P.work = P.env + (size_t)2 * (d + 1) * W * batch;
+    P.gwork = all_chip ? nullptr : P.work + (size_t)2 * wsz * batch;
+    P.route = (int*)(P.env + per_train * batch);
+    P.W = W; P.wsz = wsz; P.S = S; P.nmax = (int)nmax;
+    P.delta = d_delta;
+    P.out = out ? g_dout.as<double>() : nullptr;
+    const int rm = qtt ? (int)Rmax : 0;
+    const dim3 cgrid(batch, 2), cblock(TTN_WG);
+    const size_t clds = EXPECT_LDS_BYTES(d);
+    const dim3 qgrid(EXPECT_QTT_RMAX / 16, 2 * d, batch), qblock(EXPGRAD_TB);
+    switch (rm) {
+        case 1: hipLaunchKernelGGL(k_expgrad_chain<1>, cgrid, cblock, clds, g_stream, P); hipLaunchKernelGGL(k_expgrad_core<1>, qgrid, qblock, 0, g_stream, P); break;
+        case 2: hipLaunchKernelGGL(k_expgrad_chain<2>, cgrid, cblock, clds, g_stream, P); hipLaunchKernelGGL(k_expgrad_core<2>, qgrid, qblock, 0, g_stream, P); break;
+        case 3: hipLaunchKernelGGL(k_expgrad_chain<3>, cgrid, cblock, clds, g_stream, P); hipLaunchKernelGGL(k_expgrad_core<3>, qgrid, qblock, 0, g_stream, P); break;
+        case 4: hipLaunchKernelGGL(k_expgrad_chain<4>, cgrid, cblock, clds, g_stream, P); hipLaunchKernelGGL(k_expgrad_core<4>, qgrid, qblock, 0, g_stream, P); break;
+        case 5: hipLaunchKernelGGL(k_expgrad_chain<5>, cgrid, cblock, clds, g_stream, P); hipLaunchKernelGGL(k_expgrad_core<5>, qgrid, qblock, 0, g_stream, P); break;
+        default: hipLaunchKernelGGL(k_expgrad_chain<0>, cgrid, cblock, clds, g_stream, P); break;
+    }
+    HIPCHK(hipGetLastError());
+    if (!all_chip) {
+        const dim3 ggrid(2 * d, batch);
+        const size_t glds = sizeof(double) * GEMM_LDS_TOTAL;
+        if (qtt) hipLaunchKernelGGL(k_expgrad_core_gen<true>, ggrid, cblock, glds, g_stream, P);
+        else hipLaunchKernelGGL(k_expgrad_core_gen<false>, ggrid, cblock, glds, g_stream, P);
+        HIPCHK(hipGetLastError());
+    }
     if (out) {
         HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * batch, hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));

@@ -8,10 +8,13 @@ On handles (a batch of resident trains; nothing but scalars crosses to the host)
     cores_axpby(alpha, x, beta, y)           y_k <- alpha_b x_k + beta_b y_k on every core
     cores_dot(x, y)                          sum_k <x_k, y_k>  (test_ad.jl: ladot)
     rayleigh_value_and_grad(A, psi, g)       E = <psi, A psi> / <psi, psi> and its gradient, composed from the calls above and ttn_apply
+    sandwich_pullback(x, A, y, delta, ...)   tangents of <x, A y> on the three-layer environments: A y is never formed
+    expect_value_and_grad(A, psi, g)         <psi, A psi> and its gradient xbar + ybar
+    rayleigh_value_and_grad(..., fused=True) the same E and gradient from sandwich_pullback: no A psi, no cotangent of its size
 
 A tangent is an ordinary ``DeviceTT`` used as a bag of cores with the primal's current ranks; it is never contracted as a train.
 
-On host trains, with the reference's shape: ``dot_rrule``, ``apply_rrule``, ``rayleigh_gradient``.  They run the same kernels on a batch
+On host trains, with the reference's shape: ``dot_rrule``, ``apply_rrule``, ``sandwich_rrule``, ``rayleigh_gradient``.  They run the same kernels on a batch
 of one; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -73,11 +76,50 @@ def cores_dot(x: DeviceTT, y: DeviceTT) -> np.ndarray:
     return np.array(out[:])
 
 
-def rayleigh_value_and_grad(A: DeviceTTO, psi: DeviceTT, g: Optional[DeviceTT] = None) -> Tuple[np.ndarray, DeviceTT]:
+def sandwich_pullback(x: DeviceTT, A: DeviceTTO, y: DeviceTT, delta=None, xbar: Optional[DeviceTT] = None, ybar: Optional[DeviceTT] = None,
+                      want_value: bool = True, want_xbar: bool = True, want_ybar: bool = True):
+    """(values or None, xbar, ybar): xbar_k = delta_b * d <x_b, A y_b> / d x_k, ybar likewise (ttn_sandwich_pullback): one three-layer
+    chain from each end, every gradient a contraction of the two environments with the operator core and the other train's core.  A y is
+    never formed.  Destinations are allocated as ``dot_pullback`` allocates them; the values are not scaled by delta."""
+    if not isinstance(A, DeviceTTO):
+        raise TypeError(f"sandwich_pullback: expected a DeviceTTO, got {type(A).__name__}")
+    if not isinstance(x, DeviceTT) or not isinstance(y, DeviceTT):
+        raise TypeError("sandwich_pullback: expected DeviceTT trains")
+    if want_xbar and xbar is None:
+        xbar = _like(x)
+    if want_ybar and ybar is None:
+        ybar = _like(y)
+    out = (C.c_double * x.batch)() if want_value else None
+    _lib.check(_lib.lib().ttn_sandwich_pullback(x.h, A.h, y.h, _coef(delta, x.batch), xbar.h if xbar is not None else None,
+                                                ybar.h if ybar is not None else None, out))
+    return (np.array(out[:]) if want_value else None), xbar, ybar
+
+
+def expect_value_and_grad(A: DeviceTTO, psi: DeviceTT, g: Optional[DeviceTT] = None) -> Tuple[np.ndarray, DeviceTT]:
+    """(<psi, A psi>, its gradient with respect to the cores of psi) per train: xbar + ybar of ``sandwich_pullback(psi, A, psi)``."""
+    val, g, yb = sandwich_pullback(psi, A, psi, xbar=g)
+    cores_axpby(None, yb, None, g)
+    yb.free()
+    return val, g
+
+
+def rayleigh_value_and_grad(A: DeviceTTO, psi: DeviceTT, g: Optional[DeviceTT] = None, fused: bool = False) -> Tuple[np.ndarray, DeviceTT]:
     """E_b = <psi, A psi> / <psi, psi> and g = dE / d(cores of psi), per train (test_ad.jl:104-113):
     Y = A psi; (psibar1, Ybar) = pullback of dot(psi, Y) at 1 / <psi, psi>; psibar2 = pullback of Y = A psi at Ybar;
-    (p3, p4) = pullback of dot(psi, psi) at -E / <psi, psi>; g = psibar1 + psibar2 + p3 + p4."""
+    (p3, p4) = pullback of dot(psi, psi) at -E / <psi, psi>; g = psibar1 + psibar2 + p3 + p4.
+    ``fused=True`` takes psibar1 and psibar2 from ``sandwich_pullback`` at 1 / <psi, psi> instead: neither Y nor Ybar exists."""
     from .device import dot as _dot
+    if fused:
+        nn = _dot(psi, psi)
+        num, g, t = sandwich_pullback(psi, A, psi, delta=1.0 / nn, xbar=g)
+        E = num / nn
+        cores_axpby(None, t, None, g)
+        _, p3, p4 = dot_pullback(psi, psi, delta=-E / nn, abar=t, want_value=False)
+        cores_axpby(None, p3, None, g)
+        cores_axpby(None, p4, None, g)
+        for h in (p3, p4):
+            h.free()
+        return E, g
     Y = DeviceTT(psi.dims, [R * c for R, c in zip(A.rks, psi.cap)], psi.batch)
     _dev_apply(A, psi, Y)
     nn = _dot(psi, psi)
@@ -116,6 +158,23 @@ def dot_rrule(A: TTvector, B: TTvector) -> Tuple[float, Callable]:
     return value, pullback
 
 
+def sandwich_rrule(X: TTvector, H: TToperator, Y: TTvector) -> Tuple[float, Callable]:
+    """(<X, H Y>, pullback) with pullback(delta) -> (Xbar cores, Ybar cores); H gets no tangent, as in the reference's rule of H * psi.
+    The value is one ``ttn_sandwich`` sweep; the chains and the tangents are computed only when the pullback is called."""
+    from .device import sandwich as _sandwich
+    x, y, Hd = DeviceTT.from_host(X), DeviceTT.from_host(Y), DeviceTTO(H)
+    value = float(_sandwich(x, Hd, y)[0])
+
+    def pullback(delta):
+        _, xb, yb = sandwich_pullback(x, Hd, y, delta=float(delta), want_value=False)
+        res = (_cores(xb), _cores(yb))
+        xb.free()
+        yb.free()
+        return res
+
+    return value, pullback
+
+
 def apply_rrule(H: TToperator, psi: TTvector) -> Tuple[TTvector, Callable]:
     """(H * psi, pullback) with pullback(Ybar cores or TTvector) -> psibar cores — ChainRulesCoreExt.jl:67-88 (H gets no tangent)."""
     Hd, x = DeviceTTO(H), DeviceTT.from_host(psi)
@@ -136,9 +195,9 @@ def apply_rrule(H: TToperator, psi: TTvector) -> Tuple[TTvector, Callable]:
     return Y, pullback
 
 
-def rayleigh_gradient(H: TToperator, psi: TTvector) -> Tuple[float, List[np.ndarray]]:
-    """(E, dE / d cores) of the Rayleigh quotient <psi, H psi> / <psi, psi> — test_ad.jl:104-113."""
-    E, g = rayleigh_value_and_grad(DeviceTTO(H), DeviceTT.from_host(psi))
+def rayleigh_gradient(H: TToperator, psi: TTvector, fused: bool = False) -> Tuple[float, List[np.ndarray]]:
+    """(E, dE / d cores) of the Rayleigh quotient <psi, H psi> / <psi, psi> — test_ad.jl:104-113 (``fused``: see rayleigh_value_and_grad)."""
+    E, g = rayleigh_value_and_grad(DeviceTTO(H), DeviceTT.from_host(psi), fused=fused)
     cores = _cores(g)
     g.free()
     return float(E[0]), cores
