@@ -10,6 +10,7 @@
 // each); at ALS sizes they are latency-, not flop-bound, and run on the VALU.  Local sizes n*r*r up to 2048 are supported.
 #pragma once
 #include "ttn_ortho_kernels.h"
+#include "ttn_hsvd_kernels.h"
 
 struct AlsArgs {
     TTODev A;

@@ -3,6 +3,8 @@
 #include "ttn_common.h"
 #include "ttn_stream_kernels.h"
 #include "ttn_dense_kernels.h"
+#include "ttn_swap_kernels.h"
+#include "ttn_selftest_kernels.h"
 #include "ttn_dot_kernels.h"
 #include "ttn_ortho_kernels.h"
 #include "ttn_ortho512.h"

@@ -17,7 +17,7 @@
 #else
 #define TTN_KERNEL_BOUNDS __launch_bounds__(TTN_WG)
 #endif
-// Wave priorities of the dense kernels (s_setprio; see ttn_dense_kernels.h): matrix-product routines 0, everything else
+// Wave priorities of the dense kernels (s_setprio; see ttn_wg_prims.h): matrix-product routines 0, everything else
 // TTN_PRIO_BASE, the symmetric eigensolver TTN_EIG_PRIO, the one wave that carries the tridiagonalisation's serial chain
 // TTN_TRIDIAG_PRIO.  Only the order matters (3/3/2 and 3/3/1 measure the same).  Without priorities the benchmark ran 556 k
 // instead of 583 k cores/s (same box); one train alone on a CU sees no difference.

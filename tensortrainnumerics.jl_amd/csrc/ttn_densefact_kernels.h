@@ -14,6 +14,7 @@
 //                rotations and orthonormal as it stands.
 #pragma once
 #include "ttn_common.h"
+#include "ttn_wg_prims.h"
 
 #define TTN_DF_WG 1024
 

@@ -32,7 +32,20 @@
 // reproducible to rounding (1e-16 relative), not bitwise.
 #pragma once
 #include "ttn_common.h"
-#include "ttn_dense_kernels.h"
+#include "ttn_wg_gemm.h"
+
+// -------------------------------------------------------------------------------------------------
+// dot: transfer-matrix recurrence (src/tt_operations.jl:239-250), one workgroup per train pair.
+//   T[al, (z,b)] = sum_be M[al,be] * B[z,be,b]        (ra x rb) * (rb x n*rb')
+//   M'[a, b]     = sum_{(z,al)} A[z,al,a] * T[(z,al), b]
+// -------------------------------------------------------------------------------------------------
+struct DotArgs {
+    TTDev a, b;
+    double* scratch;            // per train: 2 * ramax*rbmax + nmax*ramax*rbmax
+    long long scratch_stride;
+    int ramax, rbmax, nmax;
+    double* out;                // [batch] device
+};
 
 #define DOT_RMAX 64                      // largest rank of the LDS-resident form
 // Element (al, be) of a state image sits at DOT_AT(be, al) = 80 be + 4 (be >> 1) + al (k-major with a swizzled row pitch).  Two LDS access

@@ -10,7 +10,8 @@
 //      check (FAST_CHECK_TOL) and its Householder + Jacobi fallback cover the rest;
 //   4. back-transformation by the stored reflectors (lane = column, wave = 8 rows).
 #pragma once
-#include "ttn_dense_kernels.h"
+#include "ttn_wg_gemm.h"
+#include "ttn_wg_jacobi.h"
 
 #define EIG_N 128
 // a += (lane J of the caller's row of 16 lanes of w) * s : the DPP form of the fp64 multiply-add broadcasts a lane of each row for
@@ -40,7 +41,7 @@ __device__ __forceinline__ void fmac_bcast(double& a, double w, double s_) {
 // reflector rows written to Vst for the back-transformation), ~1 k clk per column of the tridiagonalisation for nothing.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // 64-lane sum, result in every lane: two v_mfma_f64_4x4x4 against ones reduce the 16 lanes that share a quad position (grp_sum,
-// ttn_dense_kernels.h), two DPP row rotations add the four quad positions.  Whole-wave control flow only.
+// ttn_wg_jacobi.h), two DPP row rotations add the four quad positions.  Whole-wave control flow only.
 __device__ __forceinline__ double wave64_sum_mfma(double v) {
     v = grp_sum(v);
     v += dpp_mov_f64<0x124>(v);      // row_ror:4

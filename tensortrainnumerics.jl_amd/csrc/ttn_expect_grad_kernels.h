@@ -29,7 +29,7 @@
 // e_1 over their whole slot, rx R ry entries, so the value and the tangents are those of the [1, 1, 1] boundary entry.
 #pragma once
 #include "ttn_common.h"
-#include "ttn_dense_kernels.h"
+#include "ttn_wg_gemm.h"
 #include "ttn_dot_kernels.h"
 #include "ttn_expect_kernels.h"
 

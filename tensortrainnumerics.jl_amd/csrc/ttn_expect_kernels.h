@@ -25,7 +25,7 @@
 // One train takes one route for the whole chain (decided per train from its rank words, as k_dot decides).
 #pragma once
 #include "ttn_common.h"
-#include "ttn_dense_kernels.h"
+#include "ttn_wg_gemm.h"
 #include "ttn_dot_kernels.h"
 
 #define EXPECT_QTT_RMAX DOT_RMAX                 // largest train rank of the QTT route (= TTN_EXPECT_QTT_MAX_RANK of the public header)

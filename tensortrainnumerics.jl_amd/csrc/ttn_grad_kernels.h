@@ -24,7 +24,7 @@
 // k_cores_axpby / k_cores_dot   one pass over the arena with the trains' current ranks; the dot reduces per train in a fixed order.
 #pragma once
 #include "ttn_common.h"
-#include "ttn_dense_kernels.h"
+#include "ttn_wg_gemm.h"
 #include "ttn_dot_kernels.h"
 #include "ttn_stream_kernels.h"
 

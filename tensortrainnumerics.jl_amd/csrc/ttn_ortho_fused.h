@@ -22,9 +22,9 @@
 //       Y_j from the accumulators;  P6  max |Q^T Q - I| by MFMA from the image;  P7  R = L^T to global memory for the next site.
 // Ten workgroup barriers per site, no global scratch.
 #pragma once
-#include "ttn_ortho_dpp_gen.h"
 #include "ttn_common.h"
-#include "ttn_dense_kernels.h"
+#include "ttn_ortho_dpp_gen.h"
+#include "ttn_wg_prims.h"
 #include "ttn_dot_kernels.h"
 
 #define ORTHO_FUSED_ACCEPT 2.0e-13       // max |Q^T Q - I| up to which the single Cholesky-QR pass is the result (parity bar: 1e-12)

@@ -14,6 +14,8 @@
 //     the identity) and written as the core Y_j.
 // Four waves per workgroup, one per SIMD: 1024 trains run in one round over the chip.
 #pragma once
+#include "ttn_common.h"
+#include "ttn_ortho_kernels.h"
 
 #define ORAMP_WG 256
 

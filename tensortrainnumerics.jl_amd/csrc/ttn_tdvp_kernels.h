@@ -16,7 +16,7 @@
 // operand are strided Views of the same memory (element stride 2), and a complex product is four real GEMM calls
 // (Cre = Are Bre - Aim Bim, Cim = Are Bim + Aim Bre; conj(A) flips the sign of Aim) — the MFMA GEMM itself is unchanged.
 #pragma once
-#include "ttn_dense_kernels.h"
+#include "ttn_wg_gemm.h"
 
 struct TdvpArgs {
     int op;                      // 0 applyH1, 1 applyH0, 2 update_left_env, 3 update_right_env, 4 applyH2

@@ -1,6 +1,6 @@
 // ttn_wg512.hip — the 512-THREAD build of the bond-step machinery (second translation unit of libttn_hip.so).
 //
-// The same sources as the 1024-thread kernels of ttn_api.hip (ttn_dense_kernels.h, ttn_eig_kernels.h), compiled with TTN_WG = 512
+// The same sources as the 1024-thread kernels of ttn_api.hip (ttn_dense_kernels.h and its layers, ttn_eig_kernels.h), compiled with TTN_WG = 512
 // inside their own namespace: 8 waves per workgroup, the LDS image halved (TTN_LDS_IMG = 64 x 128 doubles, < 80 KB in all) and at
 // most 128 VGPRs per lane, so that TWO workgroups — two trains — are resident on every CU.  A bond step is a chain of short
 // dependent phases (reflectors, pivots, bisection rounds, one barrier after another): one workgroup per CU leaves two thirds of
@@ -16,6 +16,10 @@
 namespace ttn_wg512 {
 #include "ttn_common.h"
 #include "ttn_dense_kernels.h"
+// Nothing launches k_swap_chain from this build, yet it is compiled into the code object (1144 bytes of scratch).  Dropping the
+// include is right, but it moves every later function of the code object: a change of its own that can be measured.
+#include "ttn_swap_kernels.h"
+#include "ttn_selftest_kernels.h"
 #include "ttn_eig_kernels.h"
 }  // namespace ttn_wg512
 

@@ -1,0 +1,621 @@
+// ttn_wg_gemm.h — the workgroup matrix products of the one-workgroup-per-train kernels (fp64 MFMA, operands through Views).
+//
+// Provides (top to bottom):
+//   GEMM_BK, GEMM_LD, GEMM_LDS_DOUBLES, GEMM_TAB_ENTRIES, GEMM_KSLAB, GEMM_SMALL_KMAX, GEMM_DESC_DOUBLES, GEMM_LDS_TOTAL
+//                                   the LDS budget every caller reserves for a product
+//   GemmDesc                        the descriptor in LDS through which the out-of-line bodies take their operands
+//   wg_gemm                         C = alpha A B + beta C: tiled (wg_gemm_impl: 2 LDS stages, offset tables) and one-shot small form
+//                                   (wg_gemm_small_impl)
+//   wg_syrk                         G = alpha A A^T, lower triangle computed, both triangles stored
+//   wg_gemm_ra                      C = alpha A B with A held in registers (short m, k; the 512-thread build)
+// Needs: ttn_wg_prims.h (reductions, the uniform pins, the address-space typedefs, TTN_LDS_IMG, TTN_SETPRIO_*).
+// Used by: ttn_wg_lq.h, ttn_dense_kernels.h (the bond step), ttn_selftest_kernels.h and every kernel header that only multiplies
+// matrices: ttn_dot, ttn_grad, ttn_expect, ttn_expect_grad, ttn_tdvp, ttn_eig.
+#pragma once
+#include "ttn_wg_prims.h"
+
+#define GEMM_BK 16
+// LDS leading dimension (doubles) of the staged chunks, 145 = 17 mod 32.  Two access patterns meet here:
+//  * a k-fast operand is staged by 16 lanes that walk k (coalesced global reads) and store to As[kk*LD + r]: an even LD
+//    puts all 16 stores on ONE bank pair (16-way conflict: measured 49 % of the MFMA peak with LD = 144, stores alone
+//    cost 13 points); with LD odd, 2*kk*LD mod 32 = 2*kk: conflict free;
+//  * the MFMA fragment reads take two k-rows per 32-lane half (ds_read_b64, 64 banks): LD*8 mod 256 = 136 puts the second
+//    row 2 banks short of the other half: one 2-way conflict per read instead of none.
+#define GEMM_LD 145
+#define GEMM_LDS_DOUBLES (TTN_LDS_IMG + 512)       // LDS region every GEMM may use (the one-shot small GEMM uses all of it): the
+                                                   // image + room for the odd leading dimensions of a 64x64x128 one-shot product
+
+// -------------------------------------------------------------------------------------------------
+// wg_gemm: C[m x n] = alpha * A[m x k] * B[k x n] + beta * C, all operands through Views.
+// fp64 MFMA (v_mfma_f64_16x16x4_f64): the 16 waves form a 4x4 grid, each wave owns a 32x32 block of a
+// 128x128 output tile (2x2 MFMA tiles, 16 accumulator doubles per lane).  K is consumed in chunks of
+// 16 staged through LDS (k-major, leading dimension GEMM_LD = 145 doubles: the bank arithmetic stands above, at
+// its definition); the next chunk's global loads are issued before the MFMAs of
+// the current one.  Fragment maps (one f64 per lane): A[i = lane&15][k = lane>>4],
+// B[k = lane>>4][j = lane&15], D[row = (lane>>4) + 4*reg][col = lane&15].
+// Every thread of the workgroup must call it (it contains barriers).
+// -------------------------------------------------------------------------------------------------
+
+struct GemmDesc {
+    int m, n, k, pad;
+    View A, B, C;
+    double alpha, beta;
+    unsigned long long* amax;   // null, or an LDS word that receives max |C_ij| over the stored values (bits of a non-negative double)
+};
+// Behind the LDS tiles: the descriptor (sizeof(GemmDesc) = 208 bytes, 32 doubles reserved) and the OFFSET TABLES.
+// Operands are 2-level strided Views, so an element address costs two integer divisions; a GEMM evaluates ix() once per
+// row / column / k index into these tables and the staging loops only add table entries.
+// (32-bit entries, two per double of the region: element offsets fit 32 bits, operands are at most 4096 x 16384 doubles)
+#if TTN_WG == 512
+#define GEMM_TAB_ENTRIES 704                     // doubles: tiled 2 x GEMM_KSLAB + BM + BN ints; one-shot 4 x 128 + 2 x 256 ints
+#define GEMM_KSLAB 512
+#define GEMM_SMALL_KMAX 256
+#else
+#define GEMM_TAB_ENTRIES 1536
+#define GEMM_KSLAB 768                           // k indices tabulated at a time by the tiled GEMM (A and B tables)
+#define GEMM_SMALL_KMAX 512                      // one-shot GEMM: k <= GEMM_LDS_DOUBLES / 34
+#endif
+#define GEMM_DESC_DOUBLES (32 + GEMM_TAB_ENTRIES)
+#define GEMM_LDS_TOTAL (GEMM_LDS_DOUBLES + GEMM_DESC_DOUBLES)
+
+// The body is deliberately NOT inlined (17 call sites) and takes its operands through a descriptor in LDS: only two
+// pointers cross the call boundary.
+// The descriptor lives in LDS: read it through an LDS-address-space pointer (ds_read, ~100 clk and batched) — through the generic
+// pointer the ~25 fields were FLAT loads, 3.5 k clk per GEMM call before the first useful instruction.
+typedef __attribute__((address_space(3))) GemmDesc lds_gdesc;
+__device__ inline Idx ldsIdx(const __attribute__((address_space(3))) Idx* d) { return Idx{uni32(d->q), uni64(d->lo), uni64(d->hi)}; }
+__device__ inline View ldsView(const __attribute__((address_space(3))) View* v) { return View{(double*)uni64((long long)v->p), ldsIdx(&v->r), ldsIdx(&v->c)}; }
+
+// max |C_ij| of the values a GEMM stored, for callers that rescale by it: saves a pass over C (wave max, then one LDS
+// atomic per wave; non-negative doubles order like their bit patterns)
+__device__ inline void gemm_publish_amax(const lds_gdesc* dsc, double cmax) {
+    unsigned long long* am = (unsigned long long*)uni64((long long)dsc->amax);
+    if (am) {
+        cmax = wave_max(cmax);
+        if ((threadIdx.x & 63) == 0) atomicMax(am, (unsigned long long)__double_as_longlong(cmax));
+    }
+}
+
+// WR = wave rows of the 16-wave grid (WR x 16/WR waves, 32x32 outputs per wave): 4 -> 128x128 output tiles, 2 -> 64x256
+// (for m <= 64 and wide n, where half the waves of the square grid would idle).
+template <int WR>
+__device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
+    const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
+    constexpr int WCN = TTN_NWAVES / WR;                 // wave columns
+    constexpr int BM = 32 * WR, BN = 32 * WCN;
+    constexpr int LDA = (BM <= 64) ? 81 : GEMM_LD, LDB = (BN <= 64) ? 81 : (BN <= 128) ? GEMM_LD : 273;     // all == 17 mod 32 (see GEMM_LD)
+    constexpr int STAGE = GEMM_BK * (LDA + LDB);
+    static_assert(2 * STAGE <= GEMM_LDS_DOUBLES, "two LDS stages must fit");
+    const int m = uni32(dsc->m), n = uni32(dsc->n), k = uni32(dsc->k);
+    const View A = ldsView(&dsc->A), B = ldsView(&dsc->B), C = ldsView(&dsc->C);
+    const double alpha = unif64(dsc->alpha), beta = unif64(dsc->beta);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave / WCN, wc = wave % WCN;
+    const int li = lane & 15, lk = lane >> 4;
+    gmem_f64* Ag = (gmem_f64*)A.p;
+    gmem_f64* Bg = (gmem_f64*)B.p;
+    // element offsets fit 32 bits (operands are at most 4096 x 16384 doubles): half the registers of 64-bit ones
+    lds_i32* tabA = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32);      // ix(A.c, slab0 + j), j < GEMM_KSLAB
+    lds_i32* tabB = tabA + GEMM_KSLAB;                            // ix(B.r, slab0 + j)
+    const bool a_kfast = minstride(A.c) < minstride(A.r);
+    const bool b_kfast = minstride(B.r) < minstride(B.c);
+    // staging assignment: element e = tid + TTN_WG*u of the BM x BK (A) and BK x BN (B) chunk
+    constexpr int NUA = BM * GEMM_BK / TTN_WG, NUB = BN * GEMM_BK / TTN_WG;
+    int ar[NUA], akk[NUA], bc[NUB], bkk[NUB];
+#pragma unroll
+    for (int u = 0; u < NUA; ++u) {
+        const int e = tid + TTN_WG * u;
+        if (a_kfast) { akk[u] = e & (GEMM_BK - 1); ar[u] = e / GEMM_BK; } else { ar[u] = e & (BM - 1); akk[u] = e / BM; }
+    }
+#pragma unroll
+    for (int u = 0; u < NUB; ++u) {
+        const int e = tid + TTN_WG * u;
+        if (b_kfast) { bkk[u] = e & (GEMM_BK - 1); bc[u] = e / GEMM_BK; } else { bc[u] = e & (BN - 1); bkk[u] = e / BN; }
+    }
+    double cmax = 0.0;
+    const int nch = (k + GEMM_BK - 1) / GEMM_BK;
+    int slab0 = -1;                                               // first k index the tables currently hold
+    for (int m0 = 0; m0 < m; m0 += BM) {
+        for (int n0 = 0; n0 < n; n0 += BN) {
+            int aoff[NUA], boff[NUB];
+            bool aok[NUA], bok[NUB];
+#pragma unroll
+            for (int u = 0; u < NUA; ++u) { aok[u] = (m0 + ar[u]) < m; aoff[u] = aok[u] ? (int)ix(A.r, m0 + ar[u]) : 0; }
+#pragma unroll
+            for (int u = 0; u < NUB; ++u) { bok[u] = (n0 + bc[u]) < n; boff[u] = bok[u] ? (int)ix(B.c, n0 + bc[u]) : 0; }
+            const bool live = (m0 + wr * 32 < m) && (n0 + wc * 32 < n);      // wave-uniform
+            mfma_acc_t acc[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+            double av[NUA], bv[NUB];
+            // Software pipeline over the K chunks, two LDS stages, ONE barrier per chunk:
+            //   iteration c:  MFMAs of chunk c (stage c&1) | registers (chunk c+1) -> stage (c+1)&1 | global loads of chunk c+2
+#define GEMM_FILL_TAB(K0)                                                                                       \
+            {                                                                                                   \
+                __syncthreads();                                                                                \
+                slab0 = (K0);                                                                                   \
+                for (int j = tid; j < GEMM_KSLAB; j += TTN_WG) {                                                \
+                    const int kk = slab0 + j;                                                                   \
+                    tabA[j] = (kk < k) ? (int)ix(A.c, kk) : 0;                                                     \
+                    tabB[j] = (kk < k) ? (int)ix(B.r, kk) : 0;                                                     \
+                }                                                                                               \
+                __syncthreads();                                                                                \
+            }
+#define GEMM_LOAD(K0)  /* branch-free: out-of-range elements read element 0 of the operand and are then zeroed */        \
+            {                                                                                                   \
+                int oa_[NUA], ob_[NUB];                                                                         \
+                bool va_[NUA], vb_[NUB];                                                                        \
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) {                                               \
+                    const int ga = (K0) + akk[u];                                                               \
+                    va_[u] = aok[u] && ga < k;                                                                  \
+                    oa_[u] = va_[u] ? aoff[u] + tabA[ga - slab0] : 0;                                           \
+                }                                                                                               \
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) {                                               \
+                    const int gb = (K0) + bkk[u];                                                               \
+                    vb_[u] = bok[u] && gb < k;                                                                  \
+                    ob_[u] = vb_[u] ? boff[u] + tabB[gb - slab0] : 0;                                           \
+                }                                                                                               \
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) av[u] = Ag[oa_[u]];                             \
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) bv[u] = Bg[ob_[u]];                             \
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) av[u] = va_[u] ? av[u] : 0.0;                   \
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) bv[u] = vb_[u] ? bv[u] : 0.0;                   \
+            }
+#define GEMM_STORE(STG)                                                                                         \
+            {                                                                                                   \
+                lds_f64* As_ = (lds_f64*)lds + (STG) * STAGE;                                                    \
+                lds_f64* Bs_ = As_ + GEMM_BK * LDA;                                                             \
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) As_[akk[u] * LDA + ar[u]] = av[u];              \
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs_[bkk[u] * LDB + bc[u]] = bv[u];              \
+            }
+            if (slab0 != 0) GEMM_FILL_TAB(0)
+            else __syncthreads();                      // the previous tile's MFMAs have consumed both stages
+            {   // prologue: the loads of chunk 0 AND chunk 1 are in flight together (one exposed global latency, not two)
+                GEMM_LOAD(0)
+                double av0[NUA], bv0[NUB];
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) av0[u] = av[u];
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) bv0[u] = bv[u];
+                if (nch > 1) GEMM_LOAD(GEMM_BK)
+                lds_f64* As0 = (lds_f64*)lds;
+                lds_f64* Bs0 = As0 + GEMM_BK * LDA;
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) As0[akk[u] * LDA + ar[u]] = av0[u];
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs0[bkk[u] * LDB + bc[u]] = bv0[u];
+            }
+            __syncthreads();
+            for (int c = 0; c < nch; ++c) {
+                // The staging work of the other chunks is placed BETWEEN this wave's MFMA groups: an MFMA occupies the
+                // matrix pipe for 64 clk, so the VALU/LDS/global instructions issued behind it run under the MFMAs of
+                // the SIMD's other waves instead of after them (the waves run in lockstep from barrier to barrier).
+                lds_f64* As = (lds_f64*)lds + (c & 1) * STAGE;
+                lds_f64* Bs = As + GEMM_BK * LDA;
+#define GEMM_MFMA_STEP(T)                                                                                       \
+                if (live) {                                                                                     \
+                    const int kra = (4 * (T) + lk) * LDA, krb = (4 * (T) + lk) * LDB;                                                 \
+                    const double a0 = As[kra + wr * 32 + li], a1 = As[kra + wr * 32 + 16 + li];                 \
+                    const double b0 = Bs[krb + wc * 32 + li], b1 = Bs[krb + wc * 32 + 16 + li];                 \
+                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);               \
+                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);               \
+                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);               \
+                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);               \
+                }
+                GEMM_MFMA_STEP(0)
+                if (c + 1 < nch) GEMM_STORE((c + 1) & 1)
+                GEMM_MFMA_STEP(1)
+                if (c + 2 < nch) {
+                    const int k2 = (c + 2) * GEMM_BK;
+                    if (k2 >= slab0 + GEMM_KSLAB) GEMM_FILL_TAB(k2)       // workgroup-uniform; rare (k > GEMM_KSLAB)
+                    GEMM_LOAD(k2)
+                }
+                GEMM_MFMA_STEP(2)
+                GEMM_MFMA_STEP(3)
+#undef GEMM_MFMA_STEP
+                __syncthreads();
+            }
+#undef GEMM_FILL_TAB
+#undef GEMM_LOAD
+#undef GEMM_STORE
+            // C offsets of this tile through tables too (ten ix() per thread otherwise: two integer divisions each)
+            lds_i32* rowC = tabB + GEMM_KSLAB;                            // BM entries
+            lds_i32* colC = rowC + BM;                                    // BN entries
+            for (int i = tid; i < BM + BN; i += TTN_WG) {
+                if (i < BM) rowC[i] = (m0 + i < m) ? (int)ix(C.r, m0 + i) : 0;
+                else colC[i - BM] = (n0 + i - BM < n) ? (int)ix(C.c, n0 + i - BM) : 0;
+            }
+            __syncthreads();
+            if (live) {
+#pragma unroll
+                for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        const int li_ = wr * 32 + ti * 16 + lk + 4 * reg;
+                        if (m0 + li_ >= m) continue;
+                        const int ro = rowC[li_];
+#pragma unroll
+                        for (int tj = 0; tj < 2; ++tj) {
+                            const int lj_ = wc * 32 + tj * 16 + li;
+                            if (n0 + lj_ >= n) continue;
+                            gmem_wf64* cp = (gmem_wf64*)C.p + ((long long)ro + colC[lj_]);      // C is always global memory: global_store, not flat
+                            double v = alpha * acc[ti][tj][reg];
+                            if (beta != 0.0) v += beta * (*cp);
+                            *cp = v;
+                            cmax = fmax(cmax, fabs(v));
+                        }
+                    }
+            }
+        }
+    }
+    gemm_publish_amax(dsc, cmax);
+    __syncthreads();
+}
+
+// -------------------------------------------------------------------------------------------------
+// One-shot small GEMM: m, n <= 128, m*n <= 8192 (at most 2 MFMA tiles per wave) and the WHOLE K extent of both
+// operands fits the LDS region: k*(lda+ldb) <= GEMM_LDS_DOUBLES.  All global loads are issued at once (these GEMMs
+// are latency bound: a 64x64x128 product is 1 Mflop), one barrier, k/4 MFMAs per tile, store.  Small register
+// footprint on purpose (8 accumulator doubles per tile): the factored route issues ten of these per bond step.
+// -------------------------------------------------------------------------------------------------
+__device__ inline int small_ld(int x) { const int t = (x + 15) & ~15; return (((t & 31) == 16) ? t : t + 16) + 1; }   // == 17 mod 32 (see GEMM_LD)
+__device__ inline int tight_ld(int x) { return ((x + 15) & ~15) + 1; }                                             // odd: conflict-free k-fast stores
+
+__device__ __noinline__ void wg_gemm_small_impl(const GemmDesc* dsc_, double* lds) {
+    const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
+    const int m = uni32(dsc->m), n = uni32(dsc->n), k = uni32(dsc->k);
+    const View A = ldsView(&dsc->A), B = ldsView(&dsc->B), C = ldsView(&dsc->C);
+    const double alpha = unif64(dsc->alpha), beta = unif64(dsc->beta);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    // dsc->pad = 1: leading dimensions == 17 mod 32 (fragment reads nearly conflict free); 0: tight (2-way read conflicts, fits more)
+    const int lda = uni32(dsc->pad) ? small_ld(m) : tight_ld(m), ldb = uni32(dsc->pad) ? small_ld(n) : tight_ld(n);
+    lds_f64* As = (lds_f64*)lds;                       // As[kk*lda + row]
+    lds_f64* Bs = As + k * lda;                        // Bs[kk*ldb + col]
+    const bool a_kfast = minstride(A.c) < minstride(A.r);
+    const bool b_kfast = minstride(B.r) < minstride(B.c);
+    const int mp = (m + 15) & ~15, np = (n + 15) & ~15;
+    // ---- offset tables (m, n <= 128; k <= 512 because k*(lda+ldb) <= GEMM_LDS_DOUBLES and lda, ldb >= 16) ----
+    gmem_f64* Ag = (gmem_f64*)A.p;
+    gmem_f64* Bg = (gmem_f64*)B.p;
+    lds_i32* rowA = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32);
+    lds_i32* colB = rowA + 128;
+    lds_i32* rowC = colB + 128;
+    lds_i32* colC = rowC + 128;
+    lds_i32* kA = colC + 128;
+    lds_i32* kB = kA + GEMM_SMALL_KMAX;
+    for (int i = tid; i < 128; i += TTN_WG) {
+        rowA[i] = (i < m) ? (int)ix(A.r, i) : 0;
+        rowC[i] = (i < m) ? (int)ix(C.r, i) : 0;
+        colB[i] = (i < n) ? (int)ix(B.c, i) : 0;
+        colC[i] = (i < n) ? (int)ix(C.c, i) : 0;
+    }
+    for (int i = tid; i < k; i += TTN_WG) { kA[i] = (int)ix(A.c, i); kB[i] = (int)ix(B.r, i); }
+    __syncthreads();
+    // ---- stage all of A (m x k) and B (k x n), zero padding rows/cols up to the tile edge; 16 lanes walk the
+    //      operand's fast (small-stride) index, the 64 lane groups its slow index: no divisions in the loops ----
+    const int fx = tid & 15, sy = tid >> 4;
+    // The loads of a thread are issued in batches of GS_U before the first of them is awaited (written naively — load, wait, store
+    // per element — every element of a thread paid its own global-memory round trip: 16 of them in a row for a 64 x 64 x 128
+    // product, most of the time of these latency-bound GEMMs).  Out-of-range elements read element 0 and are zeroed.
+#define GS_U 8
+#define GEMM_SMALL_STAGE(DST, LDD, SRC, SLOWTAB, FASTTAB, NSLOW, NSLOW_VALID, NFAST, NFAST_VALID, SLOW_IS_K)                      \
+    for (int s_ = sy; s_ < (NSLOW); s_ += TTN_WG / 16) {                                                                        \
+        const int so_ = (s_ < (NSLOW_VALID)) ? SLOWTAB[s_] : 0;                                                                 \
+        for (int f0_ = fx; f0_ < (NFAST); f0_ += 16 * GS_U) {                                                                   \
+            double v_[GS_U];                                                                                                    \
+            _Pragma("unroll") for (int u_ = 0; u_ < GS_U; ++u_) {                                                               \
+                const int f_ = f0_ + 16 * u_;                                                                                   \
+                const bool ok_ = (s_ < (NSLOW_VALID)) && (f_ < (NFAST_VALID));                                                  \
+                v_[u_] = SRC[ok_ ? so_ + FASTTAB[f_] : 0];                                                                      \
+            }                                                                                                                   \
+            _Pragma("unroll") for (int u_ = 0; u_ < GS_U; ++u_) {                                                               \
+                const int f_ = f0_ + 16 * u_;                                                                                   \
+                const bool ok_ = (s_ < (NSLOW_VALID)) && (f_ < (NFAST_VALID));                                                  \
+                if (f_ < (NFAST)) DST[(SLOW_IS_K) ? s_ * (LDD) + f_ : f_ * (LDD) + s_] = ok_ ? v_[u_] : 0.0;                    \
+            }                                                                                                                   \
+        }                                                                                                                       \
+    }
+    if (a_kfast) { GEMM_SMALL_STAGE(As, lda, Ag, rowA, kA, mp, m, k, k, 0) }          // slow = row, fast = k
+    else { GEMM_SMALL_STAGE(As, lda, Ag, kA, rowA, k, k, mp, m, 1) }                  // slow = k, fast = row
+    if (b_kfast) { GEMM_SMALL_STAGE(Bs, ldb, Bg, colB, kB, np, n, k, k, 0) }          // slow = column, fast = k
+    else { GEMM_SMALL_STAGE(Bs, ldb, Bg, kB, colB, k, k, np, n, 1) }                  // slow = k, fast = column
+#undef GEMM_SMALL_STAGE
+#undef GS_U
+    __syncthreads();
+    const int tm = mp >> 4, tn = np >> 4, ntile = tm * tn;
+    const int k4 = k >> 2, krem = k & 3;
+    double cmax = 0.0;
+    for (int tile = wave; tile < ntile; tile += (TTN_WG >> 6)) {
+        const int r0 = (tile % tm) << 4, c0 = (tile / tm) << 4;
+        mfma_acc_t acc = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+        const lds_f64* ap = As + lk * lda + r0 + li;
+        const lds_f64* bp = Bs + lk * ldb + c0 + li;
+        int t = 0;
+        for (; t + 4 <= k4; t += 4) {                   // four k-steps per trip: the eight LDS reads go out before the MFMAs
+            double a_[4], b_[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { a_[q] = ap[(4 * (t + q)) * lda]; b_[q] = bp[(4 * (t + q)) * ldb]; }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a_[q], b_[q], acc, 0, 0, 0);
+        }
+        for (; t < k4; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[(4 * t) * lda], bp[(4 * t) * ldb], acc, 0, 0, 0);
+        if (krem) {                                     // k not a multiple of 4: pad the last step with zeros
+            const double a = (lk < krem) ? ap[(4 * k4) * lda] : 0.0;
+            const double b = (lk < krem) ? bp[(4 * k4) * ldb] : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int gi = r0 + lk + 4 * reg, gj = c0 + li;
+            if (gi < m && gj < n) {
+                gmem_wf64* cp = (gmem_wf64*)C.p + ((long long)rowC[gi] + colC[gj]);
+                double v = alpha * acc[reg];
+                if (beta != 0.0) v += beta * (*cp);
+                *cp = v;
+                cmax = fmax(cmax, fabs(v));
+            }
+        }
+    }
+    gemm_publish_amax(dsc, cmax);
+    __syncthreads();
+}
+
+__device__ inline void wg_gemm(int m, int n, int k, View A, View B, View C, double alpha, double beta, double* lds,
+                               double* amax_lds = nullptr /* LDS word: receives max |C_ij| */) {
+    GemmDesc* dsc = reinterpret_cast<GemmDesc*>(lds + GEMM_LDS_DOUBLES);
+    __syncthreads();                         // nobody still reads what the tiles / descriptor alias
+    if (threadIdx.x == 0) {
+        dsc->m = m; dsc->n = n; dsc->k = k; dsc->pad = 0;
+        dsc->A = A; dsc->B = B; dsc->C = C;
+        dsc->alpha = alpha; dsc->beta = beta;
+        dsc->amax = (unsigned long long*)amax_lds;
+        if (amax_lds) *amax_lds = 0.0;
+    }
+    __syncthreads();
+    TTN_SETPRIO_GEMM();
+    const bool shape_ok = (m <= 128) && (n <= 128) && (((m + 15) >> 4) * ((n + 15) >> 4) <= 32);
+    const int wpad = small_ld(m) + small_ld(n), wtight = tight_ld(m) + tight_ld(n);
+    if (shape_ok && (long long)k * wpad <= GEMM_LDS_DOUBLES) {
+        if (threadIdx.x == 0) dsc->pad = 1;
+        __syncthreads();
+        wg_gemm_small_impl(dsc, lds);
+    } else if (shape_ok && (long long)k * wtight <= GEMM_LDS_DOUBLES) {
+        wg_gemm_small_impl(dsc, lds);                    // pad = 0: tight leading dimensions
+    } else if (shape_ok && A.c.q == 0 && B.r.q == 0 && k <= 8 * (GEMM_LDS_DOUBLES / wtight)) {
+        // few output tiles but a long K: the tiled GEMM would keep most waves idle; run the one-shot kernel over
+        // K chunks, accumulating into C.  Plain-stride k indices only: a chunk is addressed by shifting the operands' base pointers,
+        // which a two-level k index (the stacked H of the matrix-free two-site operator) does not allow — that takes the tiled form
+        const int kcmax = (GEMM_LDS_DOUBLES / wtight) & ~3;
+        const int nck = (k + kcmax - 1) / kcmax;
+        const int kc = (((k + nck - 1) / nck) + 3) & ~3;                  // balanced chunks, multiples of 4
+        for (int k0 = 0; k0 < k; k0 += kc) {
+            if (k0 > 0) __syncthreads();
+            if (threadIdx.x == 0) {
+                dsc->k = (k - k0 < kc) ? k - k0 : kc;
+                dsc->A.p = A.p + ix(A.c, k0);
+                dsc->B.p = B.p + ix(B.r, k0);
+                dsc->beta = (k0 == 0) ? beta : 1.0;
+                dsc->amax = (k0 + kc >= k) ? (unsigned long long*)amax_lds : nullptr;     // the last chunk stores the final values
+            }
+            __syncthreads();
+            wg_gemm_small_impl(dsc, lds);
+        }
+    } else if (m <= 64 && n > 128) {
+        wg_gemm_impl<2>(dsc, lds);                       // 64 x 256 output tiles: all 16 waves busy on a short, wide product
+    } else {
+        wg_gemm_impl<4>(dsc, lds);
+    }
+    TTN_SETPRIO_BASE();
+}
+
+// -------------------------------------------------------------------------------------------------
+// wg_syrk: G = alpha * A A^T, A (p x q, p <= 128) and G (p x p, both triangles written) through Views in global memory.
+// The Gram products of a bond step (M M^T, the a-posteriori checks Rf Rf^T / Lf^T Lf, route F's A'^T A' and B' B'^T) are
+// 64..128 rows x a long K: as general GEMMs they ran the tiled form at 25 % of the matrix pipe (128 x 128 x 384: both operands staged
+// although they are the same matrix, a barrier per 16 k) or the chunked one-shot form (64 x 64 x 384: seven K chunks, each read-modify-
+// writing C in memory).  Here A is staged ONCE per K chunk (k-major, leading dimension == 17 mod 32 like the GEMM's) and serves both
+// fragment operands — frag(tb) = A[16 tb + lane&15][k + lane>>4] is the A fragment of tile row tb and the B fragment of tile column
+// tb alike —, only the tiles on and below the diagonal are computed (36 of 64 for p = 128) with the accumulators in registers over all
+// of K, and the global loads of chunk c + 1 are in flight (registers) while chunk c is multiplied.
+//   KC16 x 16 = k per chunk, JMAX = rows per thread of a chunk, MAXT = tiles per wave (all sized per build by the wrapper below).
+// -------------------------------------------------------------------------------------------------
+#define SYRK_QMAX (2 * GEMM_TAB_ENTRIES - 128)           // k offsets tabulated once (32-bit entries behind the descriptor)
+template <int KC16, int JMAX, int MAXT>
+__device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
+    const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
+    constexpr int KC = 16 * KC16, RG = TTN_WG / 16;                 // k per chunk; row groups (16 lanes walk k)
+    const int p = uni32(dsc->m), q = uni32(dsc->k);
+    const View A = ldsView(&dsc->A), C = ldsView(&dsc->C);
+    const double alpha = unif64(dsc->alpha);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int pp = (p + 15) & ~15, LD = small_ld(p);
+    lds_f64* Cs = (lds_f64*)lds;                                    // Cs[kk * LD + row]
+    lds_i32* rowT = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32);       // 128 entries
+    lds_i32* colT = rowT + 128;                                     // q entries
+    gmem_f64* Ag = (gmem_f64*)A.p;
+    for (int i = tid; i < 128; i += TTN_WG) rowT[i] = (i < p) ? (int)ix(A.r, i) : 0;
+    for (int i = tid; i < q; i += TTN_WG) colT[i] = (int)ix(A.c, i);
+    // tiles of this wave: t = wave, wave + NWAVES, ... over the lower triangle, t = tr (tr + 1) / 2 + tc
+    const int nt = pp >> 4, ntile = nt * (nt + 1) / 2;
+    int t_r[MAXT], t_c[MAXT];
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) {
+        const int t = wave + u * TTN_NWAVES;
+        int tr = 0, base = 0;
+        while (base + tr + 1 <= t) { base += tr + 1; ++tr; }
+        t_r[u] = uni32((t < ntile) ? tr : -1); t_c[u] = uni32(t - base);
+    }
+    mfma_acc_t acc[MAXT];
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) acc[u] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+    const int fx = tid & 15, sy = tid >> 4;
+    double v[JMAX][KC16];
+    __syncthreads();
+#define SYRK_LOAD(K0)                                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < JMAX; ++j) {                                                                   \
+        const int row = sy + RG * j;                                                                                    \
+        const int ro = (row < p) ? rowT[row] : 0;                                                                       \
+        _Pragma("unroll") for (int u = 0; u < KC16; ++u) {                                                               \
+            const int kk = (K0) + fx + 16 * u;                                                                          \
+            v[j][u] = Ag[(row < p && kk < q) ? ro + colT[kk] : 0];                                                      \
+        }                                                                                                               \
+    }
+    SYRK_LOAD(0)
+    for (int k0 = 0; k0 < q; k0 += KC) {
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) {
+            const int row = sy + RG * j;
+#pragma unroll
+            for (int u = 0; u < KC16; ++u) {
+                const int kl = fx + 16 * u;
+                if (row < pp) Cs[kl * LD + row] = (row < p && k0 + kl < q) ? v[j][u] : 0.0;
+            }
+        }
+        __syncthreads();
+        if (k0 + KC < q) { SYRK_LOAD(k0 + KC) }
+        const int ksteps = (q - k0 < KC) ? (q - k0 + 3) >> 2 : KC / 4;
+        for (int ks = 0; ks < ksteps; ++ks) {
+            const lds_f64* rowp = Cs + (4 * ks + lk) * LD + li;
+#pragma unroll
+            for (int u = 0; u < MAXT; ++u) {
+                if (t_r[u] >= 0) {                                   // wave-uniform
+                    const double a = rowp[16 * t_r[u]], b = rowp[16 * t_c[u]];
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[u], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+#undef SYRK_LOAD
+    gmem_wf64* Cg = (gmem_wf64*)C.p;
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) {
+        if (t_r[u] < 0) continue;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int gi = 16 * t_r[u] + lk + 4 * reg, gj = 16 * t_c[u] + li;
+            if (gi < p && gj < p) {
+                const double val = alpha * acc[u][reg];
+                Cg[ix(C.r, gi) + ix(C.c, gj)] = val;
+                if (t_r[u] != t_c[u]) Cg[ix(C.r, gj) + ix(C.c, gi)] = val;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+__device__ inline void wg_syrk(int p, int q, View A, View G, double alpha, double* lds) {
+    if (p > 128 || q > SYRK_QMAX) { wg_gemm(p, p, q, A, tview(A), G, alpha, 0.0, lds); return; }
+    GemmDesc* dsc = reinterpret_cast<GemmDesc*>(lds + GEMM_LDS_DOUBLES);
+    __syncthreads();                         // nobody still reads what the tiles / descriptor alias
+    if (threadIdx.x == 0) { dsc->m = p; dsc->n = p; dsc->k = q; dsc->pad = 0; dsc->A = A; dsc->C = G; dsc->alpha = alpha; dsc->beta = 0.0; dsc->amax = nullptr; }
+    __syncthreads();
+    TTN_SETPRIO_GEMM();
+#if TTN_WG == 512
+    if (p > 64) wg_syrk_impl<3, 4, 5>(dsc, lds);         // 128 rows: chunks of 48 k (145 x 48 doubles), 36 tiles on 8 waves
+    else wg_syrk_impl<6, 2, 2>(dsc, lds);                // <= 64 rows: chunks of 96 k (81 x 96), 10 tiles
+#else
+    if (p > 64) wg_syrk_impl<6, 2, 3>(dsc, lds);         // 145 x 96 doubles, 36 tiles on 16 waves
+    else wg_syrk_impl<6, 1, 1>(dsc, lds);
+#endif
+    TTN_SETPRIO_BASE();
+}
+
+// -------------------------------------------------------------------------------------------------
+// wg_gemm_ra: C = alpha * A B for a SHORT, SHALLOW A (m <= 64 rows, k <= 128) and any n — the right factor of a bond step
+// (sqrt(S) V^T = X^T M: 64 x 384 x 128), route F's two output products (64 x 128 x 64; the left one is passed transposed).
+// Every wave keeps the A fragments of its 16-row tile for ALL of k in registers (k/4 doubles per lane, read once), B streams through
+// LDS in chunks of 16 x (NWAVES / 4) columns — all of k at once, so one barrier pair per chunk of k/4 MFMAs per wave instead of
+// one per 16 k, no A staging at all, and the loads of the next chunk are in flight (registers) during the MFMAs.  The general
+// tiled GEMM ran these shapes at 21 % of the matrix pipe with two workgroups per CU.
+// -------------------------------------------------------------------------------------------------
+#define GEMM_RA_NMAX (2 * GEMM_TAB_ENTRIES - 320)           // column offsets of B tabulated once
+__device__ __noinline__ void wg_gemm_ra_impl(const GemmDesc* dsc_, double* lds) {
+    const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
+    constexpr int CG = TTN_NWAVES / 4, NC = 16 * CG;                // column groups of waves; columns per chunk (32 / 64)
+    constexpr int LD = (NC == 32) ? 49 : 81;                       // == 17 mod 32
+    constexpr int KR = 128 / (TTN_WG / NC);                         // k rows per thread of a chunk (8)
+    static_assert(128 * LD <= GEMM_LDS_DOUBLES, "a chunk holds all of k");
+    const int m = uni32(dsc->m), n = uni32(dsc->n), k = uni32(dsc->k);
+    const View A = ldsView(&dsc->A), B = ldsView(&dsc->B), C = ldsView(&dsc->C);
+    const double alpha = unif64(dsc->alpha);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int rt = uni32(wave & 3), cg = uni32(wave >> 2);
+    lds_f64* Bs = (lds_f64*)lds;                                    // Bs[kk * LD + j]
+    lds_i32* rowA = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32);       // 64
+    lds_i32* kA = rowA + 64;                                        // 128
+    lds_i32* kB = kA + 128;                                         // 128
+    lds_i32* colB = kB + 128;                                       // n
+    for (int i = tid; i < 64; i += TTN_WG) rowA[i] = (i < m) ? (int)ix(A.r, i) : 0;
+    for (int i = tid; i < 128; i += TTN_WG) { kA[i] = (i < k) ? (int)ix(A.c, i) : 0; kB[i] = (i < k) ? (int)ix(B.r, i) : 0; }
+    for (int i = tid; i < n; i += TTN_WG) colB[i] = (int)ix(B.c, i);
+    __syncthreads();
+    gmem_f64* Ag = (gmem_f64*)A.p;
+    gmem_f64* Bg = (gmem_f64*)B.p;
+    gmem_wf64* Cg = (gmem_wf64*)C.p;
+    const int ksteps = (k + 3) >> 2;
+    double areg[32];
+    {
+        const int row = rt * 16 + li, ro = rowA[row < 64 ? row : 0];
+#pragma unroll
+        for (int ks = 0; ks < 32; ++ks) {
+            const int kk = 4 * ks + lk;
+            areg[ks] = Ag[(row < m && kk < k) ? ro + kA[kk] : 0];
+        }
+#pragma unroll
+        for (int ks = 0; ks < 32; ++ks) { const int kk = 4 * ks + lk; if (!(row < m && kk < k)) areg[ks] = 0.0; }
+    }
+    const int fx = tid % NC, sy = tid / NC;                         // column of the chunk; first k row (rows sy + (TTN_WG / NC) u)
+    double v[KR];
+#define RA_LOAD(C0)                                                                                                     \
+    {                                                                                                                   \
+        const int col = (C0) + fx;                                                                                      \
+        const int co = (col < n) ? colB[col] : 0;                                                                       \
+        _Pragma("unroll") for (int u = 0; u < KR; ++u) {                                                                 \
+            const int kk = sy + (TTN_WG / NC) * u;                                                                      \
+            v[u] = Bg[(col < n && kk < k) ? co + kB[kk] : 0];                                                           \
+        }                                                                                                               \
+    }
+    RA_LOAD(0)
+    const bool live = rt * 16 < m;                                  // wave-uniform
+    for (int c0 = 0; c0 < n; c0 += NC) {
+#pragma unroll
+        for (int u = 0; u < KR; ++u) {
+            const int kk = sy + (TTN_WG / NC) * u;
+            Bs[kk * LD + fx] = (c0 + fx < n && kk < k) ? v[u] : 0.0;
+        }
+        __syncthreads();
+        if (c0 + NC < n) RA_LOAD(c0 + NC)
+        if (live && c0 + cg * 16 < n) {
+            mfma_acc_t acc = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+            const lds_f64* bp = Bs + lk * LD + cg * 16 + li;
+#pragma unroll
+            for (int ks = 0; ks < 32; ++ks)
+                if (ks < ksteps) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ks], bp[4 * ks * LD], acc, 0, 0, 0);
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int gi = rt * 16 + lk + 4 * reg, gj = c0 + cg * 16 + li;
+                if (gi < m && gj < n) Cg[ix(C.r, gi) + ix(C.c, gj)] = alpha * acc[reg];
+            }
+        }
+        __syncthreads();
+    }
+#undef RA_LOAD
+}
+
+// C = alpha A B; takes the register-A form when the shape allows (m <= 64, k <= 128), else the general GEMM
+__device__ inline void wg_gemm_ra(int m, int n, int k, View A, View B, View C, double alpha, double* lds) {
+#if TTN_WG != 512
+    // (measured: inside the 1024-thread kernel — one workgroup per CU, 16 waves — the general forms are as fast or faster)
+    wg_gemm(m, n, k, A, B, C, alpha, 0.0, lds);
+#else
+    if (m > 64 || k > 128 || n > GEMM_RA_NMAX || n < 64) { wg_gemm(m, n, k, A, B, C, alpha, 0.0, lds); return; }
+    GemmDesc* dsc = reinterpret_cast<GemmDesc*>(lds + GEMM_LDS_DOUBLES);
+    __syncthreads();
+    if (threadIdx.x == 0) { dsc->m = m; dsc->n = n; dsc->k = k; dsc->pad = 0; dsc->A = A; dsc->B = B; dsc->C = C; dsc->alpha = alpha; dsc->beta = 0.0; dsc->amax = nullptr; }
+    __syncthreads();
+    TTN_SETPRIO_GEMM();
+    wg_gemm_ra_impl(dsc, lds);
+    TTN_SETPRIO_BASE();
+#endif
+}

@@ -1,6 +1,6 @@
 """Site-swap chains on the device: hadamard_ttm and QTT reorder.
 
-Both are sequences of the two-site swap SVD (csrc/ttn_dense_kernels.h: wg_bond_step_io<1>, k_swap_chain) — the same Jacobi
+Both are sequences of the two-site swap SVD (csrc/ttn_dense_kernels.h: wg_bond_step_io<1>; csrc/ttn_swap_kernels.h: k_swap_chain) — the same Jacobi
 SVD step as tt_compress!, with the physical indices of the two cores exchanged and factors U, S*Vt.  The index work (bubble
 sort network of reorder, the op list of hadamard_ttm) is integer work and bit-exact with the reference.
 """
