@@ -4,25 +4,27 @@
 #  2. one --pmc pass per counter set (never combined with the trace domains)   -> gpurun_out/<tag>_pmc.json
 #  3. gpurun_out/k_compress_traffic.json = the UNTAGGED file bench.py reads `roofline.traffic` from (copy it, and the tagged
 #     summaries, to profiles/ and commit them; nothing here is ever edited by hand)
+#  TTN_LIB=<path> profiles another build of the library (the parent of a change, for a before / after pair on one box).
 #  OPS=1: also a --kernel-trace --stats pass + FETCH/WRITE passes for each `bench.py --op X` line -> gpurun_out/<tag>_op_<X>.json
 set -e
 TAG=${1:-r02x}
+STEP_LIMIT=${STEP_LIMIT:-240}     # seconds per profiled run: a run that faults or hangs ends the script (set -e), nothing starts after it
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 CMD="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu --no-single --no-verify --no-c2 --no-ops"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $CMD > $OUT/line.json 2> $OUT/stats.err
+timeout -k 10 $STEP_LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $CMD > $OUT/line.json 2> $OUT/stats.err
 for C in FETCH_SIZE WRITE_SIZE "SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES" "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_MOPS_F64"; do
   N=$(echo $C | tr ' ' '_')
-  rocprofv3 --kernel-trace --output-format csv --pmc $C -d $OUT/pmc_$N -o p -- $CMD > $OUT/pmc_$N.line 2> $OUT/pmc_$N.err
+  timeout -k 10 $STEP_LIMIT rocprofv3 --kernel-trace --output-format csv --pmc $C -d $OUT/pmc_$N -o p -- $CMD > $OUT/pmc_$N.line 2> $OUT/pmc_$N.err
 done
 if [ -n "$OPS" ]; then
   for OP in apply hadamard add scale dot orthogonalize; do
     OCMD="python3 $ROOT/bench.py --op $OP --steps 5 --warmup 2 --batch ${OPBATCH:-256}"
-    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/op_$OP/stats -o s -- $OCMD > $OUT/op_$OP.line 2> $OUT/op_$OP.err
+    timeout -k 10 $STEP_LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/op_$OP/stats -o s -- $OCMD > $OUT/op_$OP.line 2> $OUT/op_$OP.err
     for C in FETCH_SIZE WRITE_SIZE; do
-      rocprofv3 --kernel-trace --output-format csv --pmc $C -d $OUT/op_$OP/pmc_$C -o p -- $OCMD > /dev/null 2>> $OUT/op_$OP.err
+      timeout -k 10 $STEP_LIMIT rocprofv3 --kernel-trace --output-format csv --pmc $C -d $OUT/op_$OP/pmc_$C -o p -- $OCMD > /dev/null 2>> $OUT/op_$OP.err
     done
   done
 fi

@@ -538,13 +538,177 @@ __device__ __noinline__ bool wg_fused_merge_mfma(double* ck, const double* xc, c
 // A fragments — lane (li, lk) needs C_k[row 16 rt + li, a' + Rl (4 ks + lk)] — are loaded from global memory (L2) straight into the
 // MFMA operand registers, four k-steps ahead of their use: no LDS staging of C_k, no barrier between the staging of x and the epilogue.
 // Same tiling (a wave = one 16-row tile x two 16-column tiles x Rl accumulators), same epilogue.
+//
+// What keeps those loads in flight (the first version compiled to one memory round trip per LOAD: 4 Rl of them in a row per group):
+//  * the operator rank Rl is a template parameter of the tile loops (fmd_tiles<RL>, RL = 1, 2, 3; the __noinline__ entry below picks
+//    one).  As a run-time value every `a' < Rl` guard was a branch around one load or one MFMA pair, and a wait in front of each;
+//  * an A fragment is addressed through a buffer descriptor of C_k (scalar registers) as ONE 32-bit byte offset per lane plus the
+//    uniform displacement of its (group, k-step, a') in a scalar register (fmd_ld: buffer_load ... offen).  As 4 Rl 64-bit per-lane
+//    addresses they did not fit the 128-VGPR budget next to the accumulators, and each was reloaded from the stack — behind a
+//    vmcnt(0) that also drained the global load issued just before.  The displacement is ONE running scalar, advanced by an add
+//    per load: left to itself the compiler precomputes all 4 Rl of every group, this leaf then uses every scalar register up to
+//    s99, and k_compress — whose register allocation sees which registers its callees use — spills 180 VGPRs instead of 116;
+//  * two fragment sets (fa, fb) alternate, the group loop is unrolled by two: no register copies between groups, so the only
+//    wait in front of a group's MFMAs is the counted one for its own loads, with the next group's still outstanding.
+// The order of the MFMAs and of the epilogue's FMAs is that of the first version: results are bit-identical.
+typedef unsigned int fmd_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ double fmd_ld(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {   // bytes: voff per lane, soff uniform
+    return __builtin_bit_cast(double, (fmd_u32x2)__builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, (int)soff, 0));
+}
+template <int RL>
+__device__ __forceinline__ double fmd_tiles(gmem_f64* Cg, gmem_wf64* Mg, const lds_f64* Bs, const lds_f64* opl, int p, int q, int n1,
+                                            int Dl, int rhl, int rhr, int Rr, int LDB) {
+    constexpr int n2 = 2, nin = RL * n2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int RT = p >> 4;
+    const int WR = RT < 8 ? RT : 8;
+    const int WC = TTN_NWAVES / WR;
+    const int CP = 32 * WC;
+    const int ncol = n2 * rhr, nout = n2 * Rr;
+    const int ldk = n1 * Dl;                                         // column stride of C_k as a (n1 Dl) x (Rl rho_l) matrix
+    const int wr = uni32(wave % WR), wc = uni32(wave / WR);          // wave-uniform: scalar registers
+    const int ngrp = rhl >> 4;                                       // groups of four k-steps
+    const int kstride = ldk * RL;                                    // address advance per nu'
+    const unsigned a_step = 8u * (unsigned)ldk, t_step = 8u * (unsigned)(4 * kstride - (RL - 1) * ldk);   // bytes: a' -> a' + 1; (k-step, Rl - 1) -> (k-step + 1, 0)
+    double cmax = 0.0;
+    // C_k as a buffer: base and size (n1 Dl Rl rho_l doubles, <= 2^26) in scalar registers; a read past the end would return 0
+    const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc((void*)Cg, 0, 8 * kstride * rhl, 0x00020000);
+    for (int rb = 0; rb < RT; rb += WR) {
+        const int arow = 16 * (rb + wr) + li;
+        // C_k[(al, s1), ga] at s1 + n1 (al + Dl ga), row = al + Dl s1, ga = a' + Rl nu'
+        const unsigned aoff = 8u * (unsigned)((arow % Dl) * n1 + arow / Dl + lk * kstride);
+        for (int c0 = 0; c0 < ncol; c0 += CP) {
+            mfma_acc_t acc[RL][2];
+#pragma unroll
+            for (int a1 = 0; a1 < RL; ++a1) { acc[a1][0] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0}; acc[a1][1] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0}; }
+            double fa[4][RL], fb[4][RL];
+            const lds_f64* bp = Bs + lk * LDB + c0 + wc * 32 + li;   // B fragments of k-step ks: bp[0], bp[16] at bp = ... + 4 ks LDB
+#define FMD_LOAD(DST, G)   /* the uniform displacement runs along in ONE scalar register (opaque to the compiler: see above) */   \
+            {                                                                                                           \
+                unsigned so_ = 8u * (unsigned)(16 * (G) * kstride);                                                     \
+                _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                            \
+                    _Pragma("unroll") for (int a1 = 0; a1 < RL; ++a1) {                                                  \
+                        DST[t][a1] = fmd_ld(crs, aoff, so_);                                                            \
+                        so_ += (a1 + 1 < RL) ? a_step : t_step;                                                         \
+                        asm volatile("" : "+s"(so_));                                                                   \
+                    }                                                                                                   \
+            }
+#define FMD_MFMA(SRC, G)                                                                                                \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                              \
+                const double b0 = bp[0], b1 = bp[16];                                                                   \
+                bp += 4 * LDB;                                                                                          \
+                asm volatile("" : "+v"(bp));         /* ONE running LDS address, not one induction variable per k-step */ \
+                _Pragma("unroll") for (int a1 = 0; a1 < RL; ++a1) {                                                      \
+                    acc[a1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(SRC[t][a1], b0, acc[a1][0], 0, 0, 0);             \
+                    acc[a1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(SRC[t][a1], b1, acc[a1][1], 0, 0, 0);             \
+                }                                                                                                       \
+            }
+            FMD_LOAD(fa, 0)
+            // Group g + 1's loads go out before group g's MFMAs.  Loop body and tail are straight-line code: a load under a
+            // condition makes the wait in front of the MFMAs behind it a full drain (the compiler merges both paths' counts).
+            int g = 0;
+            for (; g + 2 < ngrp; g += 2) {
+                FMD_LOAD(fb, g + 1)
+                FMD_MFMA(fa, g)
+                FMD_LOAD(fa, g + 2)
+                FMD_MFMA(fb, g + 1)
+            }
+            {   // one or two groups are left; an odd count loads its last group twice (in bounds, unused) instead of branching
+                const bool two = g + 1 < ngrp;
+                FMD_LOAD(fb, two ? g + 1 : g)
+                FMD_MFMA(fa, g)
+                if (two) { FMD_MFMA(fb, g + 1) }
+            }
+#undef FMD_LOAD
+#undef FMD_MFMA
+            // ---- epilogue: lane (li, lk) holds T_a'[row = lk + 4 reg][column li] of its two column tiles; column = j + n2 nu.
+            // Both lanes of a (j = 0, 1) pair end up with all nout sums of their (row, nu); the pair then writes the nout consecutive
+            // doubles M[row, nout nu ...] as two contiguous halves (lane j = 0 the first nout / 2, lane j = 1 the rest), 16 bytes at a
+            // time where the address allows: the 16 lanes of a row of lanes cover 8 nu = 8 nout contiguous doubles of one row of M —
+            // whole cache lines per store instruction.  (Stored one output at a time, lanes 6 doubles apart and half of them idle,
+            // these stores, not the MFMAs, set the time of the merge.) ----
+            // What the epilogue needs per lane (LDS addresses of the weights, row offsets into M) is derived HERE from an opaque copy
+            // of the thread index — a handful of integer instructions per pass.  Derived from `li` / `lk` it is loop invariant: the
+            // compiler computes it once, above the K loop, where it does not fit next to the accumulators and the two fragment sets,
+            // and every pass reloads it from the stack.
+            int te = tid;
+            asm volatile("" : "+v"(te));
+            const int lie = te & 15, lke = (te >> 4) & 3, jl = lie & 1;
+            const int half = nout >> 1;
+            const bool vec_ok = (half == 3) && ((((unsigned long long)Mg) & 15ull) == 0) && ((q & 1) == 0);
+            if (RL == 3 && vec_ok) {
+                // Operator ranks 3 x 3 (the Laplacian's interior cores): the pair first swaps its raw T values (one DPP move per a'), then
+                // each lane forms ITS three outputs from all six inputs — weights w[oo][a'][own / other j] read from LDS once per pass —
+                // and stores them as 16 + 8 bytes.
+                constexpr int R3 = RL == 3 ? 3 : 1;                  // (this branch is compiled for RL < 3 too, and dropped)
+                double w[3][R3][2];
+#pragma unroll
+                for (int oo = 0; oo < 3; ++oo)
+#pragma unroll
+                    for (int a1 = 0; a1 < R3; ++a1) {
+                        const int o = 3 * jl + oo;
+                        w[oo][a1][0] = opl[o * nin + jl + n2 * a1];          // own j
+                        w[oo][a1][1] = opl[o * nin + (1 - jl) + n2 * a1];    // the neighbour's j
+                    }
+                typedef double dbl2 __attribute__((ext_vector_type(2)));
+                typedef __attribute__((address_space(1))) dbl2 gmem_wd2;
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const int nu = (c0 + wc * 32 + ct * 16 + lie) >> 1;
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        const int row = 16 * (rb + wr) + lke + 4 * reg;
+                        gmem_wf64* mrow = Mg + ((long long)row * q + (long long)nout * nu);
+                        const double t0 = acc[0][ct][reg], t1 = acc[R3 > 1 ? 1 : 0][ct][reg], t2 = acc[R3 > 2 ? 2 : 0][ct][reg];
+                        const double u0 = dpp_mov_f64<0xB1>(t0), u1 = dpp_mov_f64<0xB1>(t1), u2 = dpp_mov_f64<0xB1>(t2);      // quad_perm [1,0,3,2]
+                        double v[3];
+#pragma unroll
+                        for (int oo = 0; oo < 3; ++oo) {
+                            double x_ = t0 * w[oo][0][0];
+                            x_ = fma(u0, w[oo][0][1], x_);
+                            x_ = fma(t1, w[oo][R3 > 1 ? 1 : 0][0], x_); x_ = fma(u1, w[oo][R3 > 1 ? 1 : 0][1], x_);
+                            x_ = fma(t2, w[oo][R3 > 2 ? 2 : 0][0], x_); x_ = fma(u2, w[oo][R3 > 2 ? 2 : 0][1], x_);
+                            v[oo] = x_;
+                            cmax = fmax(cmax, fabs(x_));
+                        }
+                        // j = 0: (o0, o1) as 16 bytes at +0, o2 at +2;  j = 1: o3 at +3, (o4, o5) as 16 bytes at +4
+                        *(gmem_wd2*)(mrow + (jl ? 4 : 0)) = jl ? (dbl2){v[1], v[2]} : (dbl2){v[0], v[1]};
+                        mrow[jl ? 3 : 2] = jl ? v[0] : v[2];
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const int nu = (c0 + wc * 32 + ct * 16 + lie) >> 1;
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        const int row = 16 * (rb + wr) + lke + 4 * reg;
+                        gmem_wf64* mrow = Mg + ((long long)row * q + (long long)nout * nu);
+                        for (int o = 0; o < nout; ++o) {
+                            double v = 0.0;
+#pragma unroll
+                            for (int a1 = 0; a1 < RL; ++a1) v = fma(acc[a1][ct][reg], opl[o * nin + jl + n2 * a1], v);
+                            v += dpp_mov_f64<0xB1>(v);                   // + the other j (quad_perm [1,0,3,2]): both lanes of the pair hold the sum
+                            if ((o >= half) == (jl == 1)) mrow[o] = v;   // the pair shares the stores: each lane a contiguous half
+                            cmax = fmax(cmax, fabs(v));
+                        }
+                    }
+                }
+            }
+        }
+    }
+    return cmax;
+}
+
+// The ONE out-of-line entry (wg_fused_merge, inlined into the bond step, keeps a single call site): checks the shapes, stages the
+// operator core and x, and runs the tile loops of its operator rank.
 __device__ __noinline__ bool wg_fused_merge_direct(double* ck, const double* xc, const double* ac, double* M, int p, int q, int n1, int Dl,
                                                    int rhl, int rhr, int Rl, int Rr, double* lds, double* amax_lds, double* red) {
     ck = unip(ck); xc = unip(xc); ac = unip(ac); M = unip(M); lds = unip(lds); amax_lds = unip(amax_lds); red = unip(red);
     p = uni32(p); q = uni32(q); n1 = uni32(n1); Dl = uni32(Dl); rhl = uni32(rhl); rhr = uni32(rhr); Rl = uni32(Rl); Rr = uni32(Rr);
     constexpr int n2 = 2;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lk = lane >> 4;
+    const int tid = threadIdx.x;
     const int RT = p >> 4;
     const int WR = RT < 8 ? RT : 8;
     const int WC = TTN_NWAVES / WR;
@@ -579,116 +743,10 @@ __device__ __noinline__ bool wg_fused_merge_direct(double* ck, const double* xc,
         }
     }
     __syncthreads();
-    const long long ldk = (long long)n1 * Dl;                        // column stride of C_k as a (n1 Dl) x (Rl rho_l) matrix
-    const int wr = wave % WR, wc = wave / WR;
-    const int ksteps = rhl >> 2, ngrp = ksteps >> 2;                 // groups of four k-steps
-    const int kstride = (int)(ldk * Rl);                             // address advance per nu'
-    double cmax = 0.0;
-    const int jl = li & 1;
-    for (int rb = 0; rb < RT; rb += WR) {
-        const int arow = 16 * (rb + wr) + li;
-        // C_k[(al, s1), ga] at s1 + n1 (al + Dl ga), row = al + Dl s1, ga = a' + Rl nu'
-        const int abase = (arow % Dl) * n1 + arow / Dl + lk * kstride;
-        for (int c0 = 0; c0 < ncol; c0 += CP) {
-            mfma_acc_t acc[3][2];
-#pragma unroll
-            for (int a1 = 0; a1 < 3; ++a1) { acc[a1][0] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0}; acc[a1][1] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0}; }
-            double cur[4][3], nxt[4][3];
-#define FMD_LOAD(DST, G)                                                                                                \
-            _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                                \
-                _Pragma("unroll") for (int a1 = 0; a1 < 3; ++a1)                                                         \
-                    DST[t][a1] = (a1 < Rl) ? Cg[abase + (4 * (4 * (G) + t)) * kstride + a1 * (int)ldk] : 0.0;
-            FMD_LOAD(cur, 0)
-            const lds_f64* bcol = Bs + lk * LDB + c0 + wc * 32 + li;
-            for (int g = 0; g < ngrp; ++g) {
-                if (g + 1 < ngrp) { FMD_LOAD(nxt, g + 1) }
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int kr = 4 * (4 * g + t);
-                    const double b0 = bcol[kr * LDB], b1 = bcol[kr * LDB + 16];
-#pragma unroll
-                    for (int a1 = 0; a1 < 3; ++a1) {
-                        if (a1 < Rl) {
-                            acc[a1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[t][a1], b0, acc[a1][0], 0, 0, 0);
-                            acc[a1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[t][a1], b1, acc[a1][1], 0, 0, 0);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int a1 = 0; a1 < 3; ++a1) cur[t][a1] = nxt[t][a1];
-            }
-#undef FMD_LOAD
-            // ---- epilogue: lane (li, lk) holds T_a'[row = lk + 4 reg][column li] of its two column tiles; column = j + n2 nu.
-            // Both lanes of a (j = 0, 1) pair end up with all nout sums of their (row, nu); the pair then writes the nout consecutive
-            // doubles M[row, nout nu ...] as two contiguous halves (lane j = 0 the first nout / 2, lane j = 1 the rest), 16 bytes at a
-            // time where the address allows: the 16 lanes of a row of lanes cover 8 nu = 8 nout contiguous doubles of one row of M —
-            // whole cache lines per store instruction.  (Stored one output at a time, lanes 6 doubles apart and half of them idle,
-            // these stores, not the MFMAs, set the time of the merge.) ----
-            const int half = nout >> 1;
-            const bool vec_ok = (half == 3) && ((((unsigned long long)Mg) & 15ull) == 0) && ((q & 1) == 0);
-            if (vec_ok && Rl == 3) {
-                // Operator ranks 3 x 3 (the Laplacian's interior cores): the pair first swaps its raw T values (one DPP move per a'), then
-                // each lane forms ITS three outputs from all six inputs — weights w[oo][a'][own / other j] read from LDS once per pass —
-                // and stores them as 16 + 8 bytes.
-                double w[3][3][2];
-#pragma unroll
-                for (int oo = 0; oo < 3; ++oo)
-#pragma unroll
-                    for (int a1 = 0; a1 < 3; ++a1) {
-                        const int o = 3 * jl + oo;
-                        w[oo][a1][0] = opl[o * nin + jl + n2 * a1];          // own j
-                        w[oo][a1][1] = opl[o * nin + (1 - jl) + n2 * a1];    // the neighbour's j
-                    }
-                typedef double dbl2 __attribute__((ext_vector_type(2)));
-                typedef __attribute__((address_space(1))) dbl2 gmem_wd2;
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    const int nu = (c0 + wc * 32 + ct * 16 + li) >> 1;
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int row = 16 * (rb + wr) + lk + 4 * reg;
-                        gmem_wf64* mrow = Mg + ((long long)row * q + (long long)nout * nu);
-                        const double t0 = acc[0][ct][reg], t1 = acc[1][ct][reg], t2 = acc[2][ct][reg];
-                        const double u0 = dpp_mov_f64<0xB1>(t0), u1 = dpp_mov_f64<0xB1>(t1), u2 = dpp_mov_f64<0xB1>(t2);      // quad_perm [1,0,3,2]
-                        double v[3];
-#pragma unroll
-                        for (int oo = 0; oo < 3; ++oo) {
-                            double x_ = t0 * w[oo][0][0];
-                            x_ = fma(u0, w[oo][0][1], x_);
-                            x_ = fma(t1, w[oo][1][0], x_); x_ = fma(u1, w[oo][1][1], x_);
-                            x_ = fma(t2, w[oo][2][0], x_); x_ = fma(u2, w[oo][2][1], x_);
-                            v[oo] = x_;
-                            cmax = fmax(cmax, fabs(x_));
-                        }
-                        // j = 0: (o0, o1) as 16 bytes at +0, o2 at +2;  j = 1: o3 at +3, (o4, o5) as 16 bytes at +4
-                        *(gmem_wd2*)(mrow + (jl ? 4 : 0)) = jl ? (dbl2){v[1], v[2]} : (dbl2){v[0], v[1]};
-                        mrow[jl ? 3 : 2] = jl ? v[0] : v[2];
-                    }
-                }
-            } else {
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                const int nu = (c0 + wc * 32 + ct * 16 + li) >> 1;
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int row = 16 * (rb + wr) + lk + 4 * reg;
-                    gmem_wf64* mrow = Mg + ((long long)row * q + (long long)nout * nu);
-                    for (int o = 0; o < nout; ++o) {
-                        double v = 0.0;
-#pragma unroll
-                        for (int a1 = 0; a1 < 3; ++a1)
-                            if (a1 < Rl) v = fma(acc[a1][ct][reg], opl[o * nin + jl + n2 * a1], v);
-                        v += dpp_mov_f64<0xB1>(v);                   // + the other j (quad_perm [1,0,3,2]): both lanes of the pair hold the sum
-                        if ((o >= half) == (jl == 1)) mrow[o] = v;   // the pair shares the stores: each lane a contiguous half
-                        cmax = fmax(cmax, fabs(v));
-                    }
-                }
-            }
-            }
-        }
-    }
+    double cmax;
+    if (Rl == 3) cmax = fmd_tiles<3>(Cg, Mg, Bs, opl, p, q, n1, Dl, rhl, rhr, Rr, LDB);
+    else if (Rl == 2) cmax = fmd_tiles<2>(Cg, Mg, Bs, opl, p, q, n1, Dl, rhl, rhr, Rr, LDB);
+    else cmax = fmd_tiles<1>(Cg, Mg, Bs, opl, p, q, n1, Dl, rhl, rhr, Rr, LDB);
     cmax = wg_max(cmax, red);
     if (tid == 0) *amax_lds = cmax;
     __syncthreads();

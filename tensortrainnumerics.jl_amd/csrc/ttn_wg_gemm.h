@@ -99,30 +99,42 @@ __device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
     lds_i32* tabB = tabA + GEMM_KSLAB;                            // ix(B.r, slab0 + j)
     const bool a_kfast = minstride(A.c) < minstride(A.r);
     const bool b_kfast = minstride(B.r) < minstride(B.c);
-    // staging assignment: element e = tid + TTN_WG*u of the BM x BK (A) and BK x BN (B) chunk
+    // staging assignment: element e = tid + TTN_WG*u of the BM x BK (A) and BK x BN (B) chunk; (row, kk) = (e / BK, e % BK) for a k-fast
+    // operand, (e % BM, e / BM) otherwise.  TTN_WG is a multiple of BK, BM and BN, so element u of a thread is its element 0 plus
+    // u times a uniform step: the indices are DERIVED where they are used (GEMM_IDX: a shift, a mask and a multiply-add on an opaque
+    // copy of the thread index) instead of living in 2 (NUA + NUB) registers across the tile loops — there the compiler kept them,
+    // the offsets and the masks made from them on the stack and reloaded them tile after tile.
     constexpr int NUA = BM * GEMM_BK / TTN_WG, NUB = BN * GEMM_BK / TTN_WG;
-    int ar[NUA], akk[NUA], bc[NUB], bkk[NUB];
-#pragma unroll
-    for (int u = 0; u < NUA; ++u) {
-        const int e = tid + TTN_WG * u;
-        if (a_kfast) { akk[u] = e & (GEMM_BK - 1); ar[u] = e / GEMM_BK; } else { ar[u] = e & (BM - 1); akk[u] = e / BM; }
-    }
-#pragma unroll
-    for (int u = 0; u < NUB; ++u) {
-        const int e = tid + TTN_WG * u;
-        if (b_kfast) { bkk[u] = e & (GEMM_BK - 1); bc[u] = e / GEMM_BK; } else { bc[u] = e & (BN - 1); bkk[u] = e / BN; }
-    }
+    static_assert(TTN_WG % BM == 0 && TTN_WG % BN == 0 && TTN_WG % GEMM_BK == 0, "the staging steps are uniform");
+    const int ars = a_kfast ? TTN_WG / GEMM_BK : 0, aks = a_kfast ? 0 : TTN_WG / BM;      // row / kk step per element of a thread
+    const int bcs = b_kfast ? TTN_WG / GEMM_BK : 0, bks = b_kfast ? 0 : TTN_WG / BN;
+    // (shift, mask) pairs of element 0, uniform: the k-fast / row-fast choice costs no branch where the indices are derived
+    constexpr int LBK = 4, LBM = BM == 64 ? 6 : 7, LBN = BN == 64 ? 6 : BN == 128 ? 7 : 8;
+    static_assert((1 << LBK) == GEMM_BK && (1 << LBM) == BM && (1 << LBN) == BN, "powers of two");
+    const int arsh = a_kfast ? LBK : 0, armk = a_kfast ? -1 : BM - 1, aksh = a_kfast ? 0 : LBM, akmk = a_kfast ? GEMM_BK - 1 : -1;
+    const int bcsh = b_kfast ? LBK : 0, bcmk = b_kfast ? -1 : BN - 1, bksh = b_kfast ? 0 : LBN, bkmk = b_kfast ? GEMM_BK - 1 : -1;
+#define GEMM_IDX                                                                                                \
+    int t_ = tid;                                                                                               \
+    asm volatile("" : "+v"(t_));                                                                                \
+    const int ar0 = (t_ >> arsh) & armk, akk0 = (t_ >> aksh) & akmk;                                            \
+    const int bc0 = (t_ >> bcsh) & bcmk, bkk0 = (t_ >> bksh) & bkmk;
+#define AR(u) (ar0 + ars * (u))
+#define AKK(u) (akk0 + aks * (u))
+#define BC(u) (bc0 + bcs * (u))
+#define BKK(u) (bkk0 + bks * (u))
     double cmax = 0.0;
     const int nch = (k + GEMM_BK - 1) / GEMM_BK;
     int slab0 = -1;                                               // first k index the tables currently hold
     for (int m0 = 0; m0 < m; m0 += BM) {
         for (int n0 = 0; n0 < n; n0 += BN) {
             int aoff[NUA], boff[NUB];
-            bool aok[NUA], bok[NUB];
+            {
+                GEMM_IDX
 #pragma unroll
-            for (int u = 0; u < NUA; ++u) { aok[u] = (m0 + ar[u]) < m; aoff[u] = aok[u] ? (int)ix(A.r, m0 + ar[u]) : 0; }
+                for (int u = 0; u < NUA; ++u) aoff[u] = (m0 + AR(u)) < m ? (int)ix(A.r, m0 + AR(u)) : 0;
 #pragma unroll
-            for (int u = 0; u < NUB; ++u) { bok[u] = (n0 + bc[u]) < n; boff[u] = bok[u] ? (int)ix(B.c, n0 + bc[u]) : 0; }
+                for (int u = 0; u < NUB; ++u) boff[u] = (n0 + BC(u)) < n ? (int)ix(B.c, n0 + BC(u)) : 0;
+            }
             const bool live = (m0 + wr * 32 < m) && (n0 + wc * 32 < n);      // wave-uniform
             mfma_acc_t acc[2][2];
 #pragma unroll
@@ -145,16 +157,17 @@ __device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
             }
 #define GEMM_LOAD(K0)  /* branch-free: out-of-range elements read element 0 of the operand and are then zeroed */        \
             {                                                                                                   \
+                GEMM_IDX                                                                                        \
                 int oa_[NUA], ob_[NUB];                                                                         \
                 bool va_[NUA], vb_[NUB];                                                                        \
                 _Pragma("unroll") for (int u = 0; u < NUA; ++u) {                                               \
-                    const int ga = (K0) + akk[u];                                                               \
-                    va_[u] = aok[u] && ga < k;                                                                  \
+                    const int ga = (K0) + AKK(u);                                                               \
+                    va_[u] = (m0 + AR(u)) < m && ga < k;                                                        \
                     oa_[u] = va_[u] ? aoff[u] + tabA[ga - slab0] : 0;                                           \
                 }                                                                                               \
                 _Pragma("unroll") for (int u = 0; u < NUB; ++u) {                                               \
-                    const int gb = (K0) + bkk[u];                                                               \
-                    vb_[u] = bok[u] && gb < k;                                                                  \
+                    const int gb = (K0) + BKK(u);                                                               \
+                    vb_[u] = (n0 + BC(u)) < n && gb < k;                                                        \
                     ob_[u] = vb_[u] ? boff[u] + tabB[gb - slab0] : 0;                                           \
                 }                                                                                               \
                 _Pragma("unroll") for (int u = 0; u < NUA; ++u) av[u] = Ag[oa_[u]];                             \
@@ -164,10 +177,11 @@ __device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
             }
 #define GEMM_STORE(STG)                                                                                         \
             {                                                                                                   \
+                GEMM_IDX                                                                                        \
                 lds_f64* As_ = (lds_f64*)lds + (STG) * STAGE;                                                    \
                 lds_f64* Bs_ = As_ + GEMM_BK * LDA;                                                             \
-                _Pragma("unroll") for (int u = 0; u < NUA; ++u) As_[akk[u] * LDA + ar[u]] = av[u];              \
-                _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs_[bkk[u] * LDB + bc[u]] = bv[u];              \
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) As_[AKK(u) * LDA + AR(u)] = av[u];              \
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs_[BKK(u) * LDB + BC(u)] = bv[u];              \
             }
             if (slab0 != 0) GEMM_FILL_TAB(0)
             else __syncthreads();                      // the previous tile's MFMAs have consumed both stages
@@ -177,10 +191,11 @@ __device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
                 _Pragma("unroll") for (int u = 0; u < NUA; ++u) av0[u] = av[u];
                 _Pragma("unroll") for (int u = 0; u < NUB; ++u) bv0[u] = bv[u];
                 if (nch > 1) GEMM_LOAD(GEMM_BK)
+                GEMM_IDX
                 lds_f64* As0 = (lds_f64*)lds;
                 lds_f64* Bs0 = As0 + GEMM_BK * LDA;
-                _Pragma("unroll") for (int u = 0; u < NUA; ++u) As0[akk[u] * LDA + ar[u]] = av0[u];
-                _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs0[bkk[u] * LDB + bc[u]] = bv0[u];
+                _Pragma("unroll") for (int u = 0; u < NUA; ++u) As0[AKK(u) * LDA + AR(u)] = av0[u];
+                _Pragma("unroll") for (int u = 0; u < NUB; ++u) Bs0[BKK(u) * LDB + BC(u)] = bv0[u];
             }
             __syncthreads();
             for (int c = 0; c < nch; ++c) {
@@ -245,6 +260,11 @@ __device__ __noinline__ void wg_gemm_impl(const GemmDesc* dsc_, double* lds) {
             }
         }
     }
+#undef GEMM_IDX
+#undef AR
+#undef AKK
+#undef BC
+#undef BKK
     gemm_publish_amax(dsc, cmax);
     __syncthreads();
 }
