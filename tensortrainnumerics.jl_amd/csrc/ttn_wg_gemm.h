@@ -438,6 +438,47 @@ __device__ inline void wg_gemm(int m, int n, int k, View A, View B, View C, doub
 //   KC16 x 16 = k per chunk, JMAX = rows per thread of a chunk, MAXT = tiles per wave (all sized per build by the wrapper below).
 // -------------------------------------------------------------------------------------------------
 #define SYRK_QMAX (2 * GEMM_TAB_ENTRIES - 128)           // k offsets tabulated once (32-bit entries behind the descriptor)
+// The k-steps of one staged chunk for a wave that owns NT tiles (NT is wave-uniform: wg_syrk_impl dispatches on it once per call, so
+// no test of "does tile u exist" stands between a fragment read and its MFMA).  The fragments live in a RING of D k-steps x NT tiles
+// register pairs: an MFMA reads its operands when it issues, so the pair of (step s + D, tile u) is read into the registers of
+// (step s, tile u) right behind that tile's MFMA and has the D NT - 1 MFMAs in between (64 clk each) to arrive.  All reads are
+// unconditional, so the waits in front of the MFMAs are counted ones.  (With one register pair per operand, reused by every tile,
+// each MFMA sat behind its own two reads and a full lgkmcnt(0) drain.)  D NT fragment pairs, not two whole sets: the 128-row form
+// has 40 accumulator and 24 staging registers next to them, and k_compress's own allocation depends on what its callees clobber.
+//  * LD is a compile-time constant and rp ONE running address: a fragment's address is rp + its uniform tile offset (ta / tb = 16 tr,
+//    16 tc) + an immediate.
+//  * ksteps is rounded up to a multiple of D (D divides the steps of a chunk, KS).  The rows of a chunk behind the operand's last k
+//    are staged as +0.0, so a step past the end adds +0.0 to accumulators that started at +0.0 and therefore never hold -0.0: the same
+//    bits as skipping it.  For every accumulator the order of its MFMAs is that of the plain loop: results are unchanged bit for bit.
+template <int NT, int LD, int KS>
+__device__ __forceinline__ void syrk_ksteps(mfma_acc_t* acc, const lds_f64* rp, int ksteps, const int* ta, const int* tb) {
+    constexpr int D = NT >= 4 ? 1 : NT == 3 ? 2 : NT == 2 ? 3 : 6;
+    static_assert(KS % D == 0, "a rounded-up step count stays inside the chunk");
+    double a[D][NT], b[D][NT];
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+#pragma unroll
+        for (int u = 0; u < NT; ++u) { a[j][u] = rp[4 * j * LD + ta[u]]; b[j][u] = rp[4 * j * LD + tb[u]]; }
+    __builtin_amdgcn_sched_barrier(0);
+    const int rounds = (ksteps + D - 1) / D;
+    for (int r = 1; r < rounds; ++r) {
+        rp += 4 * D * LD;
+        asm volatile("" : "+v"(rp));         // ONE running LDS address, not one induction variable per fragment
+#pragma unroll
+        for (int j = 0; j < D; ++j)
+#pragma unroll
+            for (int u = 0; u < NT; ++u) {
+                acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[j][u], b[j][u], acc[u], 0, 0, 0);
+                a[j][u] = rp[4 * j * LD + ta[u]]; b[j][u] = rp[4 * j * LD + tb[u]];
+                __builtin_amdgcn_sched_barrier(0);       // keep each refill right behind its MFMA
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+#pragma unroll
+        for (int u = 0; u < NT; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[j][u], b[j][u], acc[u], 0, 0, 0);
+}
+template <int N> struct syrk_nt { static constexpr int value = N; };
 template <int KC16, int JMAX, int MAXT>
 __device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
     const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
@@ -447,7 +488,9 @@ __device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
     const double alpha = unif64(dsc->alpha);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
-    const int pp = (p + 15) & ~15, LD = small_ld(p);
+    constexpr int LD = (JMAX * RG > 64) ? GEMM_LD : 81;             // == 17 mod 32 (see GEMM_LD); a constant: syrk_ksteps
+    static_assert(LD >= JMAX * RG + 16 && KC * LD <= GEMM_LDS_DOUBLES, "a chunk fits the region");
+    const int pp = (p + 15) & ~15;
     lds_f64* Cs = (lds_f64*)lds;                                    // Cs[kk * LD + row]
     lds_i32* rowT = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32);       // 128 entries
     lds_i32* colT = rowT + 128;                                     // q entries
@@ -456,65 +499,90 @@ __device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
     for (int i = tid; i < q; i += TTN_WG) colT[i] = (int)ix(A.c, i);
     // tiles of this wave: t = wave, wave + NWAVES, ... over the lower triangle, t = tr (tr + 1) / 2 + tc
     const int nt = pp >> 4, ntile = nt * (nt + 1) / 2;
-    int t_r[MAXT], t_c[MAXT];
+    int t_r[MAXT], t_c[MAXT], ta[MAXT], tb[MAXT], nlive = 0;        // the live tiles of a wave are u < nlive
 #pragma unroll
     for (int u = 0; u < MAXT; ++u) {
         const int t = wave + u * TTN_NWAVES;
         int tr = 0, base = 0;
         while (base + tr + 1 <= t) { base += tr + 1; ++tr; }
-        t_r[u] = uni32((t < ntile) ? tr : -1); t_c[u] = uni32(t - base);
+        t_r[u] = uni32(tr); t_c[u] = uni32(t - base);
+        ta[u] = uni32(16 * tr); tb[u] = uni32(16 * (t - base));
+        nlive += (t < ntile) ? 1 : 0;
     }
-    mfma_acc_t acc[MAXT];
-#pragma unroll
-    for (int u = 0; u < MAXT; ++u) acc[u] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+    nlive = uni32(nlive);
     const int fx = tid & 15, sy = tid >> 4;
-    double v[JMAX][KC16];
+    gmem_wf64* Cg = (gmem_wf64*)C.p;
     __syncthreads();
+    // Everything from here on is compiled once per number of live tiles NT and the wave picks its copy ONCE (all copies run the same
+    // barriers): a wave with fewer tiles than MAXT then has neither the accumulators of the absent ones nor a test per tile and
+    // k-step in its loops.
+    mfma_acc_t res[MAXT];                                           // the finished tiles: ONE copy of the store loop below
+#pragma unroll
+    for (int u = 0; u < MAXT; ++u) res[u] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+    auto body = [&](auto ntc) {
+        constexpr int NT = decltype(ntc)::value, NA = NT ? NT : 1;
+        mfma_acc_t acc[NA];
+#pragma unroll
+        for (int u = 0; u < NA; ++u) acc[u] = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+        double v[JMAX][KC16];
+        // The prefetch of a chunk: the row offsets of a thread do not change from chunk to chunk (registers, read once), the k
+        // offsets are ONE batch of table reads per chunk, and the loads are unconditional — an out-of-range position reads element 0
+        // of the operand (the LDS store below writes its zero).  (Each load once sat behind its own table read and drain, under a
+        // branch.)
+        int ro[JMAX];
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) ro[j] = rowT[sy + RG * j];   // sy + RG j < 128; entries of rows >= p are 0
 #define SYRK_LOAD(K0)                                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < JMAX; ++j) {                                                                   \
-        const int row = sy + RG * j;                                                                                    \
-        const int ro = (row < p) ? rowT[row] : 0;                                                                       \
-        _Pragma("unroll") for (int u = 0; u < KC16; ++u) {                                                               \
-            const int kk = (K0) + fx + 16 * u;                                                                          \
-            v[j][u] = Ag[(row < p && kk < q) ? ro + colT[kk] : 0];                                                      \
-        }                                                                                                               \
-    }
-    SYRK_LOAD(0)
-    for (int k0 = 0; k0 < q; k0 += KC) {
-#pragma unroll
-        for (int j = 0; j < JMAX; ++j) {
-            const int row = sy + RG * j;
-#pragma unroll
-            for (int u = 0; u < KC16; ++u) {
-                const int kl = fx + 16 * u;
-                if (row < pp) Cs[kl * LD + row] = (row < p && k0 + kl < q) ? v[j][u] : 0.0;
-            }
+        {                                                                                                               \
+            int co_[KC16];                                                                                              \
+            _Pragma("unroll") for (int u = 0; u < KC16; ++u) {                                                           \
+                const int kk = (K0) + fx + 16 * u;                                                                      \
+                co_[u] = colT[kk < q ? kk : 0];                                                                         \
+            }                                                                                                           \
+            _Pragma("unroll") for (int j = 0; j < JMAX; ++j) {                                                           \
+                const int row = sy + RG * j;                                                                            \
+                _Pragma("unroll") for (int u = 0; u < KC16; ++u) {                                                       \
+                    const int kk = (K0) + fx + 16 * u;                                                                  \
+                    v[j][u] = Ag[(row < p && kk < q) ? ro[j] + co_[u] : 0];                                             \
+                }                                                                                                       \
+            }                                                                                                           \
         }
-        __syncthreads();
-        if (k0 + KC < q) { SYRK_LOAD(k0 + KC) }
-        const int ksteps = (q - k0 < KC) ? (q - k0 + 3) >> 2 : KC / 4;
-        for (int ks = 0; ks < ksteps; ++ks) {
-            const lds_f64* rowp = Cs + (4 * ks + lk) * LD + li;
+        SYRK_LOAD(0)
+        for (int k0 = 0; k0 < q; k0 += KC) {
 #pragma unroll
-            for (int u = 0; u < MAXT; ++u) {
-                if (t_r[u] >= 0) {                                   // wave-uniform
-                    const double a = rowp[16 * t_r[u]], b = rowp[16 * t_c[u]];
-                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[u], 0, 0, 0);
+            for (int j = 0; j < JMAX; ++j) {
+                const int row = sy + RG * j;
+#pragma unroll
+                for (int u = 0; u < KC16; ++u) {
+                    const int kl = fx + 16 * u;
+                    if (row < pp) Cs[kl * LD + row] = (row < p && k0 + kl < q) ? v[j][u] : 0.0;
                 }
             }
+            __syncthreads();
+            if (k0 + KC < q) { SYRK_LOAD(k0 + KC) }
+            const int ksteps = (q - k0 < KC) ? (q - k0 + 3) >> 2 : KC / 4;
+            if constexpr (NT > 0) syrk_ksteps<NT, LD, KC / 4>(acc, Cs + lk * LD + li, ksteps, ta, tb);
+            __syncthreads();
         }
-        __syncthreads();
-    }
 #undef SYRK_LOAD
-    gmem_wf64* Cg = (gmem_wf64*)C.p;
+#pragma unroll
+        for (int u = 0; u < NT; ++u) res[u] = acc[u];
+    };
+    if (nlive == MAXT) body(syrk_nt<MAXT>{});
+    else if (MAXT > 1 && nlive == MAXT - 1) body(syrk_nt<(MAXT > 1 ? MAXT - 1 : 0)>{});
+    else if (MAXT > 2 && nlive == MAXT - 2) body(syrk_nt<(MAXT > 2 ? MAXT - 2 : 0)>{});
+    else if (MAXT > 3 && nlive == MAXT - 3) body(syrk_nt<(MAXT > 3 ? MAXT - 3 : 0)>{});
+    else if (MAXT > 4 && nlive == MAXT - 4) body(syrk_nt<(MAXT > 4 ? MAXT - 4 : 0)>{});
+    else body(syrk_nt<0>{});
+    static_assert(MAXT <= 5, "one copy of the body per number of live tiles");
 #pragma unroll
     for (int u = 0; u < MAXT; ++u) {
-        if (t_r[u] < 0) continue;
+        if (u >= nlive) continue;                                   // wave-uniform
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int gi = 16 * t_r[u] + lk + 4 * reg, gj = 16 * t_c[u] + li;
             if (gi < p && gj < p) {
-                const double val = alpha * acc[u][reg];
+                const double val = alpha * res[u][reg];
                 Cg[ix(C.r, gi) + ix(C.c, gj)] = val;
                 if (t_r[u] != t_c[u]) Cg[ix(C.r, gj) + ix(C.c, gi)] = val;
             }
@@ -549,6 +617,30 @@ __device__ inline void wg_syrk(int p, int q, View A, View G, double alpha, doubl
 // tiled GEMM ran these shapes at 21 % of the matrix pipe with two workgroups per CU.
 // -------------------------------------------------------------------------------------------------
 #define GEMM_RA_NMAX (2 * GEMM_TAB_ENTRIES - 320)           // column offsets of B tabulated once
+// The MFMAs of one chunk for 8 NB k-steps, straight-line.  The B fragments live in a ring of RA_RING registers: an MFMA reads its
+// operands when it issues, so the fragment of k-step ks + RA_RING is read into the register of k-step ks right behind that MFMA and
+// has RA_RING - 1 MFMAs (64 clk each) to arrive; the waits in front of the MFMAs are counted ones and no branch stands between
+// them.  (Written as 32 steps each under `if (ks < ksteps)`, every MFMA sat behind one ds_read into the same register pair and a
+// full drain, with a branch per k-step.)  One accumulator, its MFMAs in k order: results are unchanged.
+// RA_RING = 3 is what fits: next to the 64 A registers and the 16 of the prefetch, a ring of 4 or more has the compiler keep A
+// fragments on the stack and reload them between the MFMAs (each reload behind a vmcnt(0) that drains the prefetch), or leaves
+// k_compress with 60 to 70 more spilled registers of its own (its allocation depends on its callees': DESIGN 4.2).
+#define RA_RING 3
+template <int NB, int LD>
+__device__ __forceinline__ mfma_acc_t ra_ksteps(const double* areg, const lds_f64* bp) {
+    mfma_acc_t acc = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
+    double b[RA_RING];
+#pragma unroll
+    for (int t = 0; t < RA_RING; ++t) b[t] = bp[4 * t * LD];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < 8 * NB; ++ks) {
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ks], b[ks % RA_RING], acc, 0, 0, 0);
+        if (ks + RA_RING < 8 * NB) b[ks % RA_RING] = bp[4 * (ks + RA_RING) * LD];
+        __builtin_amdgcn_sched_barrier(0);               // keep each refill right behind its MFMA
+    }
+    return acc;
+}
 __device__ __noinline__ void wg_gemm_ra_impl(const GemmDesc* dsc_, double* lds) {
     const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
     constexpr int CG = TTN_NWAVES / 4, NC = 16 * CG;                // column groups of waves; columns per chunk (32 / 64)
@@ -579,25 +671,35 @@ __device__ __noinline__ void wg_gemm_ra_impl(const GemmDesc* dsc_, double* lds) 
         const int row = rt * 16 + li, ro = rowA[row < 64 ? row : 0];
 #pragma unroll
         for (int ks = 0; ks < 32; ++ks) {
-            const int kk = 4 * ks + lk;
-            areg[ks] = Ag[(row < m && kk < k) ? ro + kA[kk] : 0];
+            const int kk = 4 * ks + lk, ka = kA[kk];                // read unconditionally (entries of rows >= k are 0): one batch
+            areg[ks] = Ag[(row < m && kk < k) ? ro + ka : 0];
         }
 #pragma unroll
         for (int ks = 0; ks < 32; ++ks) { const int kk = 4 * ks + lk; if (!(row < m && kk < k)) areg[ks] = 0.0; }
     }
     const int fx = tid % NC, sy = tid / NC;                         // column of the chunk; first k row (rows sy + (TTN_WG / NC) u)
     double v[KR];
+    // The prefetch of a chunk: ONE batch of table reads (the column offset and the KR k offsets: entries of rows >= k are 0), then
+    // the loads, unconditional — an out-of-range position reads element 0 of B (the LDS store below writes its zero).  (Each load
+    // once sat behind its own table read and drain, under a branch.)  The k offsets are the same for every chunk, but kept in
+    // registers across the chunk loop they take this leaf to the last of the 128 VGPRs, and k_compress then spills 50 more of its own.
 #define RA_LOAD(C0)                                                                                                     \
     {                                                                                                                   \
         const int col = (C0) + fx;                                                                                      \
-        const int co = (col < n) ? colB[col] : 0;                                                                       \
+        const int co = colB[col < n ? col : 0];                                                                         \
+        int kb_[KR];                                                                                                    \
+        _Pragma("unroll") for (int u = 0; u < KR; ++u) kb_[u] = kB[sy + (TTN_WG / NC) * u];                             \
         _Pragma("unroll") for (int u = 0; u < KR; ++u) {                                                                 \
             const int kk = sy + (TTN_WG / NC) * u;                                                                      \
-            v[u] = Bg[(col < n && kk < k) ? co + kB[kk] : 0];                                                           \
+            v[u] = Bg[(col < n && kk < k) ? co + kb_[u] : 0];                                                           \
         }                                                                                                               \
     }
     RA_LOAD(0)
     const bool live = rt * 16 < m;                                  // wave-uniform
+    // Dispatched ONCE per chunk on the number of eight-step groups (64 and 128 deep are the bond step's), not per k-step.  A k that
+    // is no multiple of 32 runs the rest of its last group on the zero padding of areg and Bs (rows k .. 127 of both are +0.0): that
+    // adds +0.0 to an accumulator that started at +0.0 and therefore never holds -0.0 — the same bits as skipping those steps.
+    const int nb = uni32((ksteps + 7) >> 3);
     for (int c0 = 0; c0 < n; c0 += NC) {
 #pragma unroll
         for (int u = 0; u < KR; ++u) {
@@ -607,11 +709,12 @@ __device__ __noinline__ void wg_gemm_ra_impl(const GemmDesc* dsc_, double* lds) 
         __syncthreads();
         if (c0 + NC < n) RA_LOAD(c0 + NC)
         if (live && c0 + cg * 16 < n) {
-            mfma_acc_t acc = (mfma_acc_t){0.0, 0.0, 0.0, 0.0};
             const lds_f64* bp = Bs + lk * LD + cg * 16 + li;
-#pragma unroll
-            for (int ks = 0; ks < 32; ++ks)
-                if (ks < ksteps) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ks], bp[4 * ks * LD], acc, 0, 0, 0);
+            mfma_acc_t acc;
+            if (nb == 4) acc = ra_ksteps<4, LD>(areg, bp);
+            else if (nb == 2) acc = ra_ksteps<2, LD>(areg, bp);
+            else if (nb == 3) acc = ra_ksteps<3, LD>(areg, bp);
+            else acc = ra_ksteps<1, LD>(areg, bp);
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int gi = rt * 16 + lk + 4 * reg, gj = c0 + cg * 16 + li;
