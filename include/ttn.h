@@ -473,6 +473,18 @@ int ttn_event_elapsed(int64_t slot_a, int64_t slot_b, float* ms);
 int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const double* B, double* C, double alpha, double beta,
                       int ta, int tb);
 
+/* kernel unit-test hook of the two-team Gram product of a bond step: G_i (p_i x p_i row-major, host, in/out) = alpha_i A_i A_i^T for
+ * i = 1, 2 in ONE single-workgroup launch; A_i stored p_i x q_i row-major, or q_i x p_i if ta_i.  pair = 1: one paired call;
+ * pair = 0: two single calls in the same launch (the reference the paired call must match bit for bit) */
+int ttn_selftest_syrk2(int64_t p1, int64_t q1, const double* A1, double* G1, double alpha1, int ta1,
+                       int64_t p2, int64_t q2, const double* A2, double* G2, double alpha2, int ta2, int pair);
+
+/* kernel unit-test hook of the two-team register-A product of a bond step: C_i (m_i x n_i, host, in/out) = alpha_i A_i B_i for i = 1, 2 in
+ * ONE single-workgroup launch; row-major operands, f_i & 1 / 2 / 4: A_i / B_i / C_i stored transposed.  pair = 1: one paired call;
+ * pair = 0: two single calls in the same launch (the reference the paired call must match bit for bit) */
+int ttn_selftest_gemm_ra2(int64_t m1, int64_t n1, int64_t k1, const double* A1, const double* B1, double* C1, double alpha1, int f1,
+                          int64_t m2, int64_t n2, int64_t k2, const double* A2, const double* B2, double* C2, double alpha2, int f2, int pair);
+
 /* kernel unit-test hook of the dense local solve of als / mals / dmrg_linsolve: K x = rhs by the blocked LU with partial pivoting (first
  * maximal |entry| of the column, as LAPACK's idamax).  K host, N x N column-major; rhs, x_out N doubles; piv_out[j] = the 0-based row
  * exchanged with row j at step j (LAPACK's ipiv - 1; -1 for a column the elimination did not reach).  form 0: wg_lu_solve, one

@@ -133,6 +133,8 @@ SIGNATURES = {
     "ttn_timer_begin": (C.c_int, []),
     "ttn_timer_end": (C.c_int, [C.POINTER(C.c_float)]),
     "ttn_selftest_gemm": (C.c_int, [i64, i64, i64, p_f64, p_f64, p_f64, C.c_double, C.c_double, C.c_int, C.c_int]),
+    "ttn_selftest_syrk2": (C.c_int, [i64, i64, p_f64, p_f64, C.c_double, C.c_int, i64, i64, p_f64, p_f64, C.c_double, C.c_int, C.c_int]),
+    "ttn_selftest_gemm_ra2": (C.c_int, [i64, i64, i64, p_f64, p_f64, p_f64, C.c_double, C.c_int, i64, i64, i64, p_f64, p_f64, p_f64, C.c_double, C.c_int, C.c_int]),
     "ttn_selftest_lu_solve": (C.c_int, [i64, p_f64, p_f64, p_f64, p_i64, C.c_int]),
     "ttn_selftest_two_site_apply": (C.c_int, [i64, i64, i64, p_f64, p_f64, p_f64, p_f64]),
     "ttn_event_record": (C.c_int, [i64]),

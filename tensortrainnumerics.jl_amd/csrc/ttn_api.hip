@@ -46,6 +46,10 @@ size_t ttn_wg512_compress_args_bytes(void);
 int ttn_wg512_launch_compress(const void* args, size_t nbytes, int grid, hipStream_t stream);
 int ttn_wg512_selftest_eig(const double* G, double* Vst, int n, int r, int nev, double* sig, double* Xout, long long* clk, hipStream_t stream);
 int ttn_wg512_selftest_gemm(int m, int n, int k, double* A, double* B, double* C, double alpha, double beta, int ta, int tb, hipStream_t stream);
+int ttn_wg512_selftest_syrk2(int p1, int q1, double* A1, double* G1, double alpha1, int ta1, int p2, int q2, double* A2, double* G2, double alpha2, int ta2,
+                             int pair, hipStream_t stream);
+int ttn_wg512_selftest_gemm_ra2(int m1, int n1, int k1, double* A1, double* B1, double* C1, double alpha1, int f1,
+                                int m2, int n2, int k2, double* A2, double* B2, double* C2, double alpha2, int f2, int pair, hipStream_t stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -270,6 +274,8 @@ int ttn_init(int device) {
         {(const void*)k_dot_fused, DOT_LDS_BYTES(DOT_MAX_D)},
         {(const void*)k_grad_chain, DOT_LDS_BYTES(DOT_MAX_D)},
         {(const void*)k_selftest_gemm, sizeof(double) * GEMM_LDS_TOTAL},
+        {(const void*)k_selftest_syrk2, sizeof(double) * GEMM_LDS_TOTAL},
+        {(const void*)k_selftest_gemm_ra2, sizeof(double) * GEMM_LDS_TOTAL},
         {(const void*)k_tdvp, TDVP_LDS_BYTES},
         {(const void*)k_lu_panel, LU_PANEL_LDS_BYTES},
         {(const void*)k_lu_trail, sizeof(double) * GEMM_LDS_TOTAL},
@@ -3047,6 +3053,74 @@ int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const do
     HIPCHK(hipMemcpyAsync(C, dC, sizeof(double) * m * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     hipFree(dA); hipFree(dB); hipFree(dC);
+    return TTN_OK;
+}
+
+// kernel unit-test hook of wg_syrk2: G_i (p_i x p_i, row-major, host, in/out) = alpha_i A_i A_i^T, both products in ONE single-workgroup
+// launch; pair = 0 computes them by two wg_syrk calls instead (the unpaired reference)
+int ttn_selftest_syrk2(int64_t p1, int64_t q1, const double* A1, double* G1, double alpha1, int ta1,
+                       int64_t p2, int64_t q2, const double* A2, double* G2, double alpha2, int ta2, int pair) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A1 || !G1 || !A2 || !G2 || p1 < 1 || q1 < 1 || p2 < 1 || q2 < 1 || p1 > 4096 || p2 > 4096 || q1 > 16384 || q2 > 16384)
+        return fail(TTN_ERR_ARG, "bad argument");
+    double *dA1 = nullptr, *dA2 = nullptr, *dG1 = nullptr, *dG2 = nullptr;
+    HIPCHK(hipMalloc((void**)&dA1, sizeof(double) * p1 * q1));
+    HIPCHK(hipMalloc((void**)&dA2, sizeof(double) * p2 * q2));
+    HIPCHK(hipMalloc((void**)&dG1, sizeof(double) * p1 * p1));
+    HIPCHK(hipMalloc((void**)&dG2, sizeof(double) * p2 * p2));
+    HIPCHK(hipMemcpyAsync(dA1, A1, sizeof(double) * p1 * q1, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dA2, A2, sizeof(double) * p2 * q2, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dG1, G1, sizeof(double) * p1 * p1, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dG2, G2, sizeof(double) * p2 * p2, hipMemcpyHostToDevice, g_stream));
+    if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {       // the same test against the 512-thread build
+        const int rc512 = ttn_wg512_selftest_syrk2((int)p1, (int)q1, dA1, dG1, alpha1, ta1, (int)p2, (int)q2, dA2, dG2, alpha2, ta2, pair, g_stream);
+        if (rc512) return hipfail((hipError_t)rc512, "k_selftest_syrk2 (512-thread build)");
+    } else {
+        hipLaunchKernelGGL(k_selftest_syrk2, dim3(1), dim3(TTN_WG), sizeof(double) * GEMM_LDS_TOTAL, g_stream, (int)p1, (int)q1, dA1, dG1, alpha1, ta1,
+                           (int)p2, (int)q2, dA2, dG2, alpha2, ta2, pair);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(G1, dG1, sizeof(double) * p1 * p1, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(G2, dG2, sizeof(double) * p2 * p2, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    hipFree(dA1); hipFree(dA2); hipFree(dG1); hipFree(dG2);
+    return TTN_OK;
+}
+
+// kernel unit-test hook of wg_gemm_ra2: C_i (m_i x n_i, host, in/out) = alpha_i A_i B_i, both products in ONE single-workgroup launch; f_i & 1 / 2 / 4:
+// A_i / B_i / C_i stored transposed; pair = 0 computes them by two wg_gemm_ra calls instead (the unpaired reference)
+int ttn_selftest_gemm_ra2(int64_t m1, int64_t n1, int64_t k1, const double* A1, const double* B1, double* C1, double alpha1, int f1,
+                          int64_t m2, int64_t n2, int64_t k2, const double* A2, const double* B2, double* C2, double alpha2, int f2, int pair) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    const int64_t dm[2] = {m1, m2}, dn[2] = {n1, n2}, dk[2] = {k1, k2};
+    const double* hA[2] = {A1, A2};
+    const double* hB[2] = {B1, B2};
+    double* hC[2] = {C1, C2};
+    for (int i = 0; i < 2; ++i)
+        if (!hA[i] || !hB[i] || !hC[i] || dm[i] < 1 || dn[i] < 1 || dk[i] < 1 || dm[i] > 4096 || dn[i] > 4096 || dk[i] > 4096) return fail(TTN_ERR_ARG, "bad argument");
+    double *dA[2] = {nullptr, nullptr}, *dB[2] = {nullptr, nullptr}, *dC[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(hipMalloc((void**)&dA[i], sizeof(double) * dm[i] * dk[i]));
+        HIPCHK(hipMalloc((void**)&dB[i], sizeof(double) * dk[i] * dn[i]));
+        HIPCHK(hipMalloc((void**)&dC[i], sizeof(double) * dm[i] * dn[i]));
+        HIPCHK(hipMemcpyAsync(dA[i], hA[i], sizeof(double) * dm[i] * dk[i], hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipMemcpyAsync(dB[i], hB[i], sizeof(double) * dk[i] * dn[i], hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipMemcpyAsync(dC[i], hC[i], sizeof(double) * dm[i] * dn[i], hipMemcpyHostToDevice, g_stream));
+    }
+    if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {       // the same test against the 512-thread build
+        const int rc512 = ttn_wg512_selftest_gemm_ra2((int)m1, (int)n1, (int)k1, dA[0], dB[0], dC[0], alpha1, f1, (int)m2, (int)n2, (int)k2, dA[1], dB[1], dC[1],
+                                                      alpha2, f2, pair, g_stream);
+        if (rc512) return hipfail((hipError_t)rc512, "k_selftest_gemm_ra2 (512-thread build)");
+    } else {
+        hipLaunchKernelGGL(k_selftest_gemm_ra2, dim3(1), dim3(TTN_WG), sizeof(double) * GEMM_LDS_TOTAL, g_stream, (int)m1, (int)n1, (int)k1, dA[0], dB[0], dC[0],
+                           alpha1, f1, (int)m2, (int)n2, (int)k2, dA[1], dB[1], dC[1], alpha2, f2, pair);
+        HIPCHK(hipGetLastError());
+    }
+    for (int i = 0; i < 2; ++i) HIPCHK(hipMemcpyAsync(hC[i], dC[i], sizeof(double) * dm[i] * dn[i], hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    for (int i = 0; i < 2; ++i) { hipFree(dA[i]); hipFree(dB[i]); hipFree(dC[i]); }
     return TTN_OK;
 }
 

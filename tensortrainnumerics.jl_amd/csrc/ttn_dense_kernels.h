@@ -13,7 +13,7 @@
 // ttn_swap_kernels.h (k_swap_chain).  ttn_selftest_kernels.h (k_selftest_gemm) needs ttn_wg_gemm.h only.
 // Map of this file (top to bottom):
 //   CompressArgs, COMPRESS_LDS_BYTES, the FAST_* tolerances, BondCtx
-//   wg_img_load, wg_trsm_lower_cols, wg_tril_mul_lds, wg_scale_image, wg_check_diag_tab, wg_diag_test_t3, wg_scale_t12_diag
+//   wg_img_load, wg_trsm_lower_cols, wg_tril_mul_lds, wg_scale_image, wg_check_diag_tab, wg_check_diag_tab2, wg_diag_test_t3, wg_scale_t12_diag
 //                                   out-of-line leaves of the routes (CholeskyQR2 helpers first)
 //   wg_svd_cols / wg_rank_rule / wg_check_diag, wg_materialize_core / wg_fused_merge, wg_bond_step, k_compress
 //                                   the bond step (routes F / G / H, fused apply) and the persistent sweep kernel
@@ -231,6 +231,27 @@ __device__ __noinline__ double wg_check_diag_tab(const double* sigs, const doubl
             const double dv = Dg[i + ldd * j];
             const double dev = fabs(dv - ((i == j) ? ref[i] : 0.0)) * (t[i] * tj);
             worst = fmax(worst, dev);
+        }
+    }
+    return unif64(wg_max(worst, red));
+}
+
+// The same check of TWO matrices D1, D2 against the same sigs in one pass: max of the two results (route F tests both against one
+// tolerance).  One table, one reduction, the loads of both matrices in flight together; a maximum does not depend on the order.
+__device__ __noinline__ double wg_check_diag_tab2(const double* sigs, const double* D1, const double* D2, int ldd, int r, double s0, double* tab, double* red) {
+    sigs = unip(sigs); D1 = unip(D1); D2 = unip(D2); ldd = uni32(ldd); r = uni32(r); s0 = unif64(s0); tab = unip(tab); red = unip(red);
+    lds_f64* t = (lds_f64*)tab; lds_f64* ref = t + 128;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < r; i += TTN_WG) { const double si = sigs[i]; t[i] = 1.0 / sqrt(s0 * si); ref[i] = si * s0; }
+    __syncthreads();
+    gmem_f64* D1g = (gmem_f64*)D1; gmem_f64* D2g = (gmem_f64*)D2;
+    double worst = 0.0;
+    for (int j = wave; j < r; j += TTN_NWAVES) {
+        const double tj = t[j];
+        for (int i = lane; i < r; i += 64) {
+            const double d1 = D1g[i + ldd * j], d2 = D2g[i + ldd * j];
+            const double rf = (i == j) ? ref[i] : 0.0, sc = t[i] * tj;
+            worst = fmax(worst, fmax(fabs(d1 - rf) * sc, fabs(d2 - rf) * sc));
         }
     }
     return unif64(wg_max(worst, red));
@@ -1087,8 +1108,8 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         const View Ccv = mkview(S.Cc, plain(1), plain(128));
         bool diagA = false;
         if (ok) {
-            wg_syrk(rm, p, tview(Ap), Gav, 1.0 / (sA * sA), lds);          // A'^T A'
-            wg_syrk(rm, q, Bp, Gbv, 1.0 / (sB * sB), lds);          // B' B'^T
+            // A'^T A' and B' B'^T: independent, one two-team call (two wg_syrk calls where rm > 64)
+            wg_syrk2(rm, p, tview(Ap), Gav, 1.0 / (sA * sA), rm, q, Bp, Gbv, 1.0 / (sB * sB), lds);
             // A' = U D^(1/2) with orthonormal U (the left core of a bond step is left as U sqrt(S) by the step before it, so every
             // R->L step of a sweep that follows an L->R sweep sees this): then M = U (D^(1/2) B') and the SVD of M is U times the SVD
             // of the rm x q matrix N = D^(1/2) B' — no Cholesky factors, no core matrix, two output GEMMs instead of five.
@@ -1176,8 +1197,8 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             const View Lft = mkview(LfT, plain(1), plain(p));
             const View Rft = mkview(RfT, plain(q), plain(1));
             if (diagA) {
-                wg_gemm_ra(rk, p, rm, tview(T1v), tview(Ap), tview(Lft), 1.0, lds);          // Lf^T = T1^T A'^T: the short operand in registers
-                wg_gemm_ra(rk, q, rm, tview(T2v), Bp, Rft, 1.0, lds);
+                // Lf^T = T1^T A'^T and Rf = T2^T B': the short operands in registers, both products in one two-team call
+                wg_gemm_ra2(rk, p, rm, tview(T1v), tview(Ap), tview(Lft), 1.0, rk, q, rm, tview(T2v), Bp, Rft, 1.0, lds);
             } else {
             // Lf = A' * (L_B * (C^T * X_s))     (ldsX is free again: use it as the second temporary)
             wg_gemm(rm, rk, rm, tview(Ccv), T1v, mkview(S.T3, plain(1), plain(128)), 1.0, 0.0, lds);
@@ -1188,11 +1209,8 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             wg_gemm(rk, q, rm, tview(mkview(S.T3, plain(1), plain(128))), Bp, Rft, 1.0, 0.0, lds);
             }
             // a-posteriori check: Lf^T Lf = Sigma, Rf Rf^T = Sigma
-            wg_syrk(rk, p, tview(Lft), mkview(S.T1, plain(1), plain(128)), 1.0, lds);
-            wg_syrk(rk, q, Rft, mkview(S.T2, plain(1), plain(128)), 1.0, lds);
-            const double e1 = wg_check_diag_tab(S.sigs, S.T1, 128, rk, s0, S.Ts, S.red);
-            const double e2 = wg_check_diag_tab(S.sigs, S.T2, 128, rk, s0, S.Ts, S.red);
-            ok = (e1 <= FAST_CHECK_TOL) && (e2 <= FAST_CHECK_TOL);
+            wg_syrk2(rk, p, tview(Lft), mkview(S.T1, plain(1), plain(128)), 1.0, rk, q, Rft, mkview(S.T2, plain(1), plain(128)), 1.0, lds);
+            ok = wg_check_diag_tab2(S.sigs, S.T1, S.T2, 128, rk, s0, S.Ts, S.red) <= FAST_CHECK_TOL;       // both checks, one pass
             if (ok) {
                 if (P.sv_out && step < P.sv_steps) {
                     double* so = P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax;

@@ -33,6 +33,8 @@ int ttn_wg512_init(void) {
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ttn_wg512::k_compress), hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMPRESS_LDS_BYTES)) != hipSuccess) return (int)e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ttn_wg512::k_selftest_eig128), hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMPRESS_LDS_BYTES)) != hipSuccess) return (int)e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ttn_wg512::k_selftest_gemm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMPRESS_LDS_BYTES)) != hipSuccess) return (int)e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ttn_wg512::k_selftest_syrk2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMPRESS_LDS_BYTES)) != hipSuccess) return (int)e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ttn_wg512::k_selftest_gemm_ra2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)COMPRESS_LDS_BYTES)) != hipSuccess) return (int)e;
     return 0;
 }
 
@@ -54,6 +56,17 @@ int ttn_wg512_selftest_eig(const double* G, double* Vst, int n, int r, int nev, 
 }
 int ttn_wg512_selftest_gemm(int m, int n, int k, double* A, double* B, double* C, double alpha, double beta, int ta, int tb, hipStream_t stream) {
     hipLaunchKernelGGL(ttn_wg512::k_selftest_gemm, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, stream, m, n, k, A, B, C, alpha, beta, ta, tb);
+    return (int)hipGetLastError();
+}
+int ttn_wg512_selftest_syrk2(int p1, int q1, double* A1, double* G1, double alpha1, int ta1, int p2, int q2, double* A2, double* G2, double alpha2, int ta2,
+                             int pair, hipStream_t stream) {
+    hipLaunchKernelGGL(ttn_wg512::k_selftest_syrk2, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, stream, p1, q1, A1, G1, alpha1, ta1, p2, q2, A2, G2, alpha2, ta2, pair);
+    return (int)hipGetLastError();
+}
+int ttn_wg512_selftest_gemm_ra2(int m1, int n1, int k1, double* A1, double* B1, double* C1, double alpha1, int f1,
+                                int m2, int n2, int k2, double* A2, double* B2, double* C2, double alpha2, int f2, int pair, hipStream_t stream) {
+    hipLaunchKernelGGL(ttn_wg512::k_selftest_gemm_ra2, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, stream, m1, n1, k1, A1, B1, C1, alpha1, f1,
+                       m2, n2, k2, A2, B2, C2, alpha2, f2, pair);
     return (int)hipGetLastError();
 }
 

@@ -7,7 +7,9 @@
 //   wg_gemm                         C = alpha A B + beta C: tiled (wg_gemm_impl: 2 LDS stages, offset tables) and one-shot small form
 //                                   (wg_gemm_small_impl)
 //   wg_syrk                         G = alpha A A^T, lower triangle computed, both triangles stored
+//   wg_syrk2                        two independent Gram products of <= 64 rows in one call, one per half of the workgroup's waves
 //   wg_gemm_ra                      C = alpha A B with A held in registers (short m, k; the 512-thread build)
+//   wg_gemm_ra2                     two independent register-A products with m, k <= 64 in one call, one per team of four waves
 // Needs: ttn_wg_prims.h (reductions, the uniform pins, the address-space typedefs, TTN_LDS_IMG, TTN_SETPRIO_*).
 // Used by: ttn_wg_lq.h, ttn_dense_kernels.h (the bond step), ttn_selftest_kernels.h and every kernel header that only multiplies
 // matrices: ttn_dot, ttn_grad, ttn_expect, ttn_expect_grad, ttn_tdvp, ttn_eig.
@@ -42,7 +44,8 @@ struct GemmDesc {
     double alpha, beta;
     unsigned long long* amax;   // null, or an LDS word that receives max |C_ij| over the stored values (bits of a non-negative double)
 };
-// Behind the LDS tiles: the descriptor (sizeof(GemmDesc) = 208 bytes, 32 doubles reserved) and the OFFSET TABLES.
+// Behind the LDS tiles: the descriptor (sizeof(GemmDesc) = 208 bytes, 32 doubles reserved; the two-team forms wg_syrk2 / wg_gemm_ra2 put
+// TWO descriptors there, 64 doubles, and start their tables behind them) and the OFFSET TABLES.
 // Operands are 2-level strided Views, so an element address costs two integer divisions; a GEMM evaluates ix() once per
 // row / column / k index into these tables and the staging loops only add table entries.
 // (32-bit entries, two per double of the region: element offsets fit 32 bits, operands are at most 4096 x 16384 doubles)
@@ -479,30 +482,42 @@ __device__ __forceinline__ void syrk_ksteps(mfma_acc_t* acc, const lds_f64* rp, 
         for (int u = 0; u < NT; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[j][u], b[j][u], acc[u], 0, 0, 0);
 }
 template <int N> struct syrk_nt { static constexpr int value = N; };
-template <int KC16, int JMAX, int MAXT>
-__device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
-    const lds_gdesc* dsc = (const lds_gdesc*)dsc_;
-    constexpr int KC = 16 * KC16, RG = TTN_WG / 16;                 // k per chunk; row groups (16 lanes walk k)
+// TEAMS = 1: the whole workgroup computes the product of descriptor 0.  TEAMS = 2 (wg_syrk2): the workgroup splits into two teams of
+// TTN_NWAVES / 2 waves, team t computes the product of descriptor t (p <= 64) in its own half of the LDS region and of the tables, and
+// both teams meet at the SAME workgroup barriers: the chunk loop runs the chunk count of the longer product, the team that is done
+// stages zeros and skips its MFMAs.  "tid", "wave" and the thread / wave counts below are those of the TEAM.
+#define SYRK2_TAB (GEMM_TAB_ENTRIES - 32)                // 32-bit table entries of one team: 64 row + SYRK2_QMAX k offsets
+#define SYRK2_QMAX (SYRK2_TAB - 64)
+template <int KC16, int JMAX, int MAXT, int TEAMS>
+__device__ __forceinline__ void syrk_body(const GemmDesc* dsc_, double* lds) {
+    constexpr int TWG = TTN_WG / TEAMS, TNW = TTN_NWAVES / TEAMS, NROW = 128 / TEAMS;      // threads, waves, tabulated rows of a team
+    const int team = (TEAMS == 1) ? 0 : uni32((int)threadIdx.x / TWG);
+    const lds_gdesc* dsc = (const lds_gdesc*)dsc_ + team;
+    constexpr int KC = 16 * KC16, RG = TWG / 16;                    // k per chunk; row groups (16 lanes walk k)
     const int p = uni32(dsc->m), q = uni32(dsc->k);
+    int qall = q;                                                   // the k extent the chunk loop (and its barriers) covers
+    if constexpr (TEAMS == 2) { const int qo = uni32(((const lds_gdesc*)dsc_ + (1 - team))->k); qall = q > qo ? q : qo; }
     const View A = ldsView(&dsc->A), C = ldsView(&dsc->C);
     const double alpha = unif64(dsc->alpha);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x - team * TWG, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     constexpr int LD = (JMAX * RG > 64) ? GEMM_LD : 81;             // == 17 mod 32 (see GEMM_LD); a constant: syrk_ksteps
-    static_assert(LD >= JMAX * RG + 16 && KC * LD <= GEMM_LDS_DOUBLES, "a chunk fits the region");
+    static_assert(LD >= JMAX * RG + 16 && TEAMS * KC * LD <= GEMM_LDS_DOUBLES, "a chunk fits the region");
+    static_assert(TEAMS == 1 || (TEAMS == 2 && JMAX * RG == NROW), "two teams: 64 rows each");
     const int pp = (p + 15) & ~15;
-    lds_f64* Cs = (lds_f64*)lds;                                    // Cs[kk * LD + row]
-    lds_i32* rowT = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32);       // 128 entries
-    lds_i32* colT = rowT + 128;                                     // q entries
+    lds_f64* Cs = (lds_f64*)lds + team * (KC * LD);                 // Cs[kk * LD + row]
+    // (two descriptors take 52 doubles: the tables of the two-team form start 64 doubles behind the region, not 32)
+    lds_i32* rowT = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 32 * TEAMS) + team * SYRK2_TAB;      // NROW entries
+    lds_i32* colT = rowT + NROW;                                    // q entries
     gmem_f64* Ag = (gmem_f64*)A.p;
-    for (int i = tid; i < 128; i += TTN_WG) rowT[i] = (i < p) ? (int)ix(A.r, i) : 0;
-    for (int i = tid; i < q; i += TTN_WG) colT[i] = (int)ix(A.c, i);
+    for (int i = tid; i < NROW; i += TWG) rowT[i] = (i < p) ? (int)ix(A.r, i) : 0;
+    for (int i = tid; i < q; i += TWG) colT[i] = (int)ix(A.c, i);
     // tiles of this wave: t = wave, wave + NWAVES, ... over the lower triangle, t = tr (tr + 1) / 2 + tc
     const int nt = pp >> 4, ntile = nt * (nt + 1) / 2;
     int t_r[MAXT], t_c[MAXT], ta[MAXT], tb[MAXT], nlive = 0;        // the live tiles of a wave are u < nlive
 #pragma unroll
     for (int u = 0; u < MAXT; ++u) {
-        const int t = wave + u * TTN_NWAVES;
+        const int t = wave + u * TNW;
         int tr = 0, base = 0;
         while (base + tr + 1 <= t) { base += tr + 1; ++tr; }
         t_r[u] = uni32(tr); t_c[u] = uni32(t - base);
@@ -548,7 +563,7 @@ __device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
             }                                                                                                           \
         }
         SYRK_LOAD(0)
-        for (int k0 = 0; k0 < q; k0 += KC) {
+        for (int k0 = 0; k0 < qall; k0 += KC) {
 #pragma unroll
             for (int j = 0; j < JMAX; ++j) {
                 const int row = sy + RG * j;
@@ -561,7 +576,9 @@ __device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
             __syncthreads();
             if (k0 + KC < q) { SYRK_LOAD(k0 + KC) }
             const int ksteps = (q - k0 < KC) ? (q - k0 + 3) >> 2 : KC / 4;
-            if constexpr (NT > 0) syrk_ksteps<NT, LD, KC / 4>(acc, Cs + lk * LD + li, ksteps, ta, tb);
+            if constexpr (NT > 0) {
+                if (TEAMS == 1 || ksteps > 0) syrk_ksteps<NT, LD, KC / 4>(acc, Cs + lk * LD + li, ksteps, ta, tb);      // (wave-uniform)
+            }
             __syncthreads();
         }
 #undef SYRK_LOAD
@@ -590,6 +607,16 @@ __device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) {
     }
     __syncthreads();
 }
+template <int KC16, int JMAX, int MAXT>
+__device__ __noinline__ void wg_syrk_impl(const GemmDesc* dsc_, double* lds) { syrk_body<KC16, JMAX, MAXT, 1>(dsc_, lds); }
+// the two-team form: descriptors dsc_[0] and dsc_[1], both products <= 64 rows (10 lower-triangle tiles on TTN_NWAVES / 2 waves)
+__device__ __noinline__ void wg_syrk2_impl(const GemmDesc* dsc_, double* lds) {
+#if TTN_WG == 512
+    syrk_body<3, 4, 3, 2>(dsc_, lds);                    // 4 waves: chunks of 48 k (81 x 48 doubles per team), up to 3 tiles per wave
+#else
+    syrk_body<3, 2, 2, 2>(dsc_, lds);                    // 8 waves: up to 2 tiles per wave
+#endif
+}
 
 __device__ inline void wg_syrk(int p, int q, View A, View G, double alpha, double* lds) {
     if (p > 128 || q > SYRK_QMAX) { wg_gemm(p, p, q, A, tview(A), G, alpha, 0.0, lds); return; }
@@ -605,6 +632,30 @@ __device__ inline void wg_syrk(int p, int q, View A, View G, double alpha, doubl
     if (p > 64) wg_syrk_impl<6, 2, 3>(dsc, lds);         // 145 x 96 doubles, 36 tiles on 16 waves
     else wg_syrk_impl<6, 1, 1>(dsc, lds);
 #endif
+    TTN_SETPRIO_BASE();
+}
+
+// wg_syrk2: G1 = alpha1 A1 A1^T and G2 = alpha2 A2 A2^T, two INDEPENDENT Gram products of at most 64 rows in one call.  Such a product
+// is a few microseconds of MFMAs behind its table setup, one global round trip per chunk, two barriers per chunk and the store: run
+// back to back, two of them pay that latency twice; here each runs on half of the workgroup's waves and both wait together.  Every
+// accumulator sees the MFMAs of its k-steps in ascending order with the operands wg_syrk gives it (the chunks are 48 k instead of 96,
+// the accumulators carry over), so the results are those of two wg_syrk calls bit for bit.  Other shapes take the two calls.
+__device__ inline void wg_syrk2(int p1, int q1, View A1, View G1, double alpha1, int p2, int q2, View A2, View G2, double alpha2, double* lds) {
+    if (p1 > 64 || p2 > 64 || q1 > SYRK2_QMAX || q2 > SYRK2_QMAX) {
+        wg_syrk(p1, q1, A1, G1, alpha1, lds);
+        wg_syrk(p2, q2, A2, G2, alpha2, lds);
+        return;
+    }
+    GemmDesc* dsc = reinterpret_cast<GemmDesc*>(lds + GEMM_LDS_DOUBLES);
+    static_assert(2 * sizeof(GemmDesc) <= 64 * sizeof(double), "two descriptors in front of the two-team tables");
+    __syncthreads();                         // nobody still reads what the tiles / descriptors alias
+    if (threadIdx.x == 0) {
+        dsc[0].m = p1; dsc[0].n = p1; dsc[0].k = q1; dsc[0].pad = 0; dsc[0].A = A1; dsc[0].C = G1; dsc[0].alpha = alpha1; dsc[0].beta = 0.0; dsc[0].amax = nullptr;
+        dsc[1].m = p2; dsc[1].n = p2; dsc[1].k = q2; dsc[1].pad = 0; dsc[1].A = A2; dsc[1].C = G2; dsc[1].alpha = alpha2; dsc[1].beta = 0.0; dsc[1].amax = nullptr;
+    }
+    __syncthreads();
+    TTN_SETPRIO_GEMM();
+    wg_syrk2_impl(dsc, lds);
     TTN_SETPRIO_BASE();
 }
 
@@ -741,4 +792,121 @@ __device__ inline void wg_gemm_ra(int m, int n, int k, View A, View B, View C, d
     wg_gemm_ra_impl(dsc, lds);
     TTN_SETPRIO_BASE();
 #endif
+}
+
+// -------------------------------------------------------------------------------------------------
+// wg_gemm_ra2: C1 = alpha1 A1 B1 and C2 = alpha2 A2 B2, two INDEPENDENT register-A products with m, k <= 64 in one call (route F's
+// two output products, 64 x 128 x 64 each), for the reason wg_syrk2 gives: the single call is table setup, one global round trip
+// and two barriers per chunk around 16 MFMAs per wave.  The workgroup's 8 waves split into two teams of 4; team t takes the product
+// of descriptor t: wave w of the team keeps the A fragments of row tile w (16 registers for k <= 64, not 32), B streams through the
+// team's half of the LDS region in the single form's chunks (all of k x 32 columns, LD 49) and the wave multiplies BOTH 16-column
+// groups of a chunk, one after the other, with the single form's straight-line k-step groups (ra_ksteps).  One accumulator per output
+// tile, its MFMAs in k order with the operands the single form gives it: the same bits.  Both teams run the chunk count of the wider
+// product (the same workgroup barriers); the team that is done stages zeros and skips its MFMAs.
+// -------------------------------------------------------------------------------------------------
+#if TTN_WG == 512
+#define GEMM_RA2_NMAX (SYRK2_TAB - 192)                     // a team's tables: 64 row, 2 x 64 k and n column offsets
+__device__ __noinline__ void wg_gemm_ra2_impl(const GemmDesc* dsc_, double* lds) {
+    constexpr int TWG = TTN_WG / 2, NC = 32, LD = 49, KMAX = 64;   // threads of a team; columns per chunk; == 17 mod 32; deepest k
+    constexpr int KR = KMAX / (TWG / NC);                           // k rows per thread of a chunk (8)
+    static_assert(TWG == 256 && 2 * KMAX * LD <= GEMM_LDS_DOUBLES, "one chunk per team holds all of k");
+    const int team = uni32((int)threadIdx.x / TWG);
+    const lds_gdesc* dsc = (const lds_gdesc*)dsc_ + team;
+    const int m = uni32(dsc->m), n = uni32(dsc->n), k = uni32(dsc->k);
+    const int no = uni32(((const lds_gdesc*)dsc_ + (1 - team))->n), nall = n > no ? n : no;     // the columns the chunk loop (and its barriers) covers
+    const View A = ldsView(&dsc->A), B = ldsView(&dsc->B), C = ldsView(&dsc->C);
+    const double alpha = unif64(dsc->alpha);
+    const int tid = threadIdx.x - team * TWG, lane = tid & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int rt = uni32(tid >> 6);                                 // row tile of this wave
+    lds_f64* Bs = (lds_f64*)lds + team * (KMAX * LD);               // Bs[kk * LD + j]
+    lds_i32* rowA = (lds_i32*)(lds + GEMM_LDS_DOUBLES + 64) + team * SYRK2_TAB;      // 64 (behind the two descriptors, as wg_syrk2's)
+    lds_i32* kA = rowA + 64;                                        // 64
+    lds_i32* kB = kA + KMAX;                                        // 64
+    lds_i32* colB = kB + KMAX;                                      // n
+    for (int i = tid; i < 64; i += TWG) {
+        rowA[i] = (i < m) ? (int)ix(A.r, i) : 0;
+        kA[i] = (i < k) ? (int)ix(A.c, i) : 0;
+        kB[i] = (i < k) ? (int)ix(B.r, i) : 0;
+    }
+    for (int i = tid; i < n; i += TWG) colB[i] = (int)ix(B.c, i);
+    __syncthreads();
+    gmem_f64* Ag = (gmem_f64*)A.p;
+    gmem_f64* Bg = (gmem_f64*)B.p;
+    gmem_wf64* Cg = (gmem_wf64*)C.p;
+    double areg[KMAX / 4];
+    {
+        const int row = rt * 16 + li, ro = rowA[row];               // row < 64
+#pragma unroll
+        for (int ks = 0; ks < KMAX / 4; ++ks) {
+            const int kk = 4 * ks + lk, ka = kA[kk];                // read unconditionally (entries of rows >= k are 0): one batch
+            areg[ks] = Ag[(row < m && kk < k) ? ro + ka : 0];
+        }
+#pragma unroll
+        for (int ks = 0; ks < KMAX / 4; ++ks) { const int kk = 4 * ks + lk; if (!(row < m && kk < k)) areg[ks] = 0.0; }
+    }
+    const int fx = tid % NC, sy = tid / NC;                         // column of the chunk; first k row (rows sy + (TWG / NC) u)
+    double v[KR];
+#define RA2_LOAD(C0)        /* as RA_LOAD of the single form: one batch of table reads, unconditional loads from clamped addresses */ \
+    {                                                                                                                   \
+        const int col = (C0) + fx;                                                                                      \
+        const int co = colB[col < n ? col : 0];                                                                         \
+        int kb_[KR];                                                                                                    \
+        _Pragma("unroll") for (int u = 0; u < KR; ++u) kb_[u] = kB[sy + (TWG / NC) * u];                                \
+        _Pragma("unroll") for (int u = 0; u < KR; ++u) {                                                                 \
+            const int kk = sy + (TWG / NC) * u;                                                                         \
+            v[u] = Bg[(col < n && kk < k) ? co + kb_[u] : 0];                                                           \
+        }                                                                                                               \
+    }
+    RA2_LOAD(0)
+    const bool live = rt * 16 < m;                                  // wave-uniform
+    const int nb = uni32((((k + 3) >> 2) + 7) >> 3);                // groups of eight k-steps: 1 or 2 (the rest of a group runs on zeros)
+    for (int c0 = 0; c0 < nall; c0 += NC) {
+#pragma unroll
+        for (int u = 0; u < KR; ++u) {
+            const int kk = sy + (TWG / NC) * u;
+            Bs[kk * LD + fx] = (c0 + fx < n && kk < k) ? v[u] : 0.0;
+        }
+        __syncthreads();
+        if (c0 + NC < n) RA2_LOAD(c0 + NC)
+#pragma unroll
+        for (int cg = 0; cg < 2; ++cg) {
+            if (live && c0 + cg * 16 < n) {                         // wave-uniform
+                const lds_f64* bp = Bs + lk * LD + cg * 16 + li;
+                mfma_acc_t acc;
+                if (nb == 2) acc = ra_ksteps<2, LD>(areg, bp);
+                else acc = ra_ksteps<1, LD>(areg, bp);
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int gi = rt * 16 + lk + 4 * reg, gj = c0 + cg * 16 + li;
+                    if (gi < m && gj < n) Cg[ix(C.r, gi) + ix(C.c, gj)] = alpha * acc[reg];
+                }
+            }
+        }
+        __syncthreads();
+    }
+#undef RA2_LOAD
+}
+#endif
+
+// two products C_i = alpha_i A_i B_i; the two-team form where both shapes allow it (the 512-thread build, m, k <= 64), else two wg_gemm_ra
+__device__ inline void wg_gemm_ra2(int m1, int n1, int k1, View A1, View B1, View C1, double alpha1,
+                                   int m2, int n2, int k2, View A2, View B2, View C2, double alpha2, double* lds) {
+#if TTN_WG == 512
+    if (m1 <= 64 && m2 <= 64 && k1 <= 64 && k2 <= 64 && n1 >= 64 && n2 >= 64 && n1 <= GEMM_RA2_NMAX && n2 <= GEMM_RA2_NMAX) {
+        GemmDesc* dsc = reinterpret_cast<GemmDesc*>(lds + GEMM_LDS_DOUBLES);
+        __syncthreads();                     // nobody still reads what the tiles / descriptors alias
+        if (threadIdx.x == 0) {
+            dsc[0].m = m1; dsc[0].n = n1; dsc[0].k = k1; dsc[0].pad = 0; dsc[0].A = A1; dsc[0].B = B1; dsc[0].C = C1; dsc[0].alpha = alpha1; dsc[0].beta = 0.0; dsc[0].amax = nullptr;
+            dsc[1].m = m2; dsc[1].n = n2; dsc[1].k = k2; dsc[1].pad = 0; dsc[1].A = A2; dsc[1].B = B2; dsc[1].C = C2; dsc[1].alpha = alpha2; dsc[1].beta = 0.0; dsc[1].amax = nullptr;
+        }
+        __syncthreads();
+        TTN_SETPRIO_GEMM();
+        wg_gemm_ra2_impl(dsc, lds);
+        TTN_SETPRIO_BASE();
+        return;
+    }
+#endif
+    wg_gemm_ra(m1, n1, k1, A1, B1, C1, alpha1, lds);
+    wg_gemm_ra(m2, n2, k2, A2, B2, C2, alpha2, lds);
 }
