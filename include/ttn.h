@@ -645,6 +645,12 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * formed.  Declared in ttn_expect_grad.h, which this header includes. */
 #include "ttn_expect_grad.h"
 
+/* ---- operator batches (csrc/ttn_opbatch_kernels.h) ------------------------------------------------------------------
+ * B operators of equal dims and ranks in one ttn_tto handle, operator b for train b: ttn_tto_create_batch, ttn_tto_from_tt_batch,
+ * ttn_tto_batch, ttn_tto_select, ttn_tto_download_b, and the list of the entry points above that take such a handle (every other one
+ * refuses it).  Declared in ttn_opbatch.h, which this header includes. */
+#include "ttn_opbatch.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,6 +211,15 @@ EXPECT_GRAD_SIGNATURES = {
     "ttn_sandwich_pullback": (C.c_int, [handle, handle, handle, p_f64, handle, handle, p_f64]),
 }
 
+# operator batches, include/ttn_opbatch.h
+OPBATCH_SIGNATURES = {
+    "ttn_tto_create_batch": (C.c_int, [i64, p_i64, p_i64, i64, pp_f64, p_handle]),
+    "ttn_tto_from_tt_batch": (C.c_int, [handle, p_handle]),
+    "ttn_tto_batch": (C.c_int, [handle, p_i64]),
+    "ttn_tto_select": (C.c_int, [handle, i64, p_handle]),
+    "ttn_tto_download_b": (C.c_int, [handle, i64, pp_f64]),
+}
+
 _lib = None
 
 
@@ -220,7 +229,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
     srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
              os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h"),
-             os.path.join(INCLUDE, "ttn_expect_grad.h")]
+             os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -244,7 +253,7 @@ def lib() -> C.CDLL:
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
-            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()):
+            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()) + list(OPBATCH_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -268,7 +268,7 @@ struct AlsEnv {
 };
 #define XC(i) (E.x.data + (long long)E.tb * E.x.stride + E.x.off[i])
 #define BC(i) (E.b.data + (long long)E.tb * E.b.stride + E.b.off[i])
-#define AC(i) (E.A.data + E.A.off[i])
+#define AC(i) (E.A.data + (long long)E.tb * E.A.stride + E.A.off[i])      // (stride 0: one operator for every train)
 #define GP(i) (E.scr + E.off[i])
 #define GBP(i) (E.scr + E.off[E.d + (i)])
 #define HP(i) (E.scr + E.off[2 * E.d + (i)])

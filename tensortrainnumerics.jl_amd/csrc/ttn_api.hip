@@ -28,6 +28,7 @@
 #include "ttn_step_kernels.h"
 #include "ttn_expect_kernels.h"
 #include "ttn_expect_grad_kernels.h"
+#include "ttn_opbatch_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -152,6 +153,8 @@ struct ttn_tt_s {
 };
 struct ttn_tto_s {
     int d = 0;
+    int batch = 1;                            // operators in the handle (include/ttn_opbatch.h): equal dims and ranks, operator b at d_data + b * stride
+    long long stride = 0;                     // doubles per operator: off[d]
     int el = 1;                               // 1 Float64, 2 ComplexF64 (slots of twice the doubles; d_dims keeps n_k, d_dims2 holds 2 n_k^2)
     std::vector<int64_t> dims, rks;
     std::vector<long long> off;
@@ -164,6 +167,7 @@ struct ttn_tto_s {
     TTODev dev() const {
         TTODev t;
         t.data = d_data; t.off = d_off; t.rks = d_rks; t.dims = d_dims; t.d = d;
+        t.stride = batch > 1 ? stride : 0;    // 0: every train reads the one operator
         return t;
     }
     // The operator as ONE train of physical dimensions n_k^2 whose capacity is its ranks: an operator core (n, n, r_l, r_r) is byte for
@@ -211,6 +215,19 @@ static int refuse_c64(const char* who) {
 static int refuse_mixed(const char* who) {
     g_err = std::string(who) + ": the element types (Float64 / ComplexF64) of the handles do not fit this call";
     return TTN_ERR_UNSUPPORTED;
+}
+
+// An operator batch (include/ttn_opbatch.h) is taken by the entry points listed there; every other one refuses it before any launch: it
+// would read operator 0 for every train, or 1 train's worth of a batch of slots.
+static int single_op(const ttn_tto_s* A, const char* who) {
+    if (!A || A->batch <= 1) return TTN_OK;
+    g_err = std::string(who) + ": an operator batch is not supported here (ttn_opbatch.h lists the calls that take one; ttn_tto_select gives one operator of it)";
+    return TTN_ERR_UNSUPPORTED;
+}
+// ... and the ones that take it need one operator per train
+static int op_batch_fits(const ttn_tto_s* A, int batch) {
+    if (A->batch > 1 && A->batch != batch) { g_err = "batch sizes differ (the operator batch and the trains)"; return TTN_ERR_DIMS; }
+    return TTN_OK;
 }
 
 // ttn_tt_free / ttn_status_all: bit `code` of the library-level word for every failure code recorded on the handle (which one is
@@ -596,13 +613,13 @@ static bool stream_fibres_too_many(long long fibres) { return fibres >= (1LL << 
 // the cores left uninitialised: an output core beyond the 32-bit fibre indices of the streaming kernels is refused, and a result the
 // device cannot hold is TTN_ERR_CAPACITY (nothing is launched).  ttn_tto_create passes no `who` and reports the HIP error itself.
 static int tto_alloc(const char* who, int el, int64_t d, const int64_t* dims, const int64_t* rks, const int64_t* ot, const double* const* cores,
-                     OwnedTTO& out) {
+                     OwnedTTO& out, int64_t batch = 1 /* operators of these dims and ranks; cores: [batch * d] */) {
     if (who)
         for (int64_t k = 0; k < d; ++k)
             if (stream_fibres_too_many((long long)rks[k] * rks[k + 1]))
                 return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": 2^31 or more fibres in one output core (32-bit element indices)").c_str());
     ttn_tto_s* h = out.h = new ttn_tto_s();
-    h->d = (int)d; h->el = el;
+    h->d = (int)d; h->el = el; h->batch = (int)batch;
     h->dims.assign(dims, dims + d);
     h->rks.assign(rks, rks + d + 1);
     h->ot.assign(d, 0);
@@ -615,10 +632,11 @@ static int tto_alloc(const char* who, int el, int64_t d, const int64_t* dims, co
         o += (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
     }
     h->off[d] = o;
+    h->stride = o;
     std::vector<int> idims(2 * d);
     for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(el * dims[k] * dims[k]); }
     std::vector<long long> r64(rks, rks + d + 1);
-    hipError_t e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1));
+    hipError_t e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1) * (size_t)batch);
     if (e != hipSuccess && who) {
         (void)hipGetLastError();
         h->d_data = nullptr;
@@ -632,9 +650,11 @@ static int tto_alloc(const char* who, int el, int64_t d, const int64_t* dims, co
     h->d_dims2 = h->d_dims + d;
     std::vector<double> flat;                           // the cores at their slots, the rounding gaps zero
     if (cores) {
-        flat.assign((size_t)o, 0.0);
-        for (int64_t k = 0; k < d; ++k) std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);
-        HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * (size_t)o, hipMemcpyHostToDevice, g_stream));
+        flat.assign((size_t)o * (size_t)batch, 0.0);
+        for (int64_t b = 0; b < batch; ++b)
+            for (int64_t k = 0; k < d; ++k)
+                std::memcpy(flat.data() + (size_t)b * (size_t)o + h->off[k], cores[b * d + k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);
+        HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * flat.size(), hipMemcpyHostToDevice, g_stream));
     }
     HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
@@ -699,7 +719,9 @@ int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (x == y) return fail(TTN_ERR_ARG, "ttn_apply: output must not alias the input");
+    if (int rb = op_batch_fits(A, x->batch)) return rb;
     const bool cplx = A->el == 2 || x->el == 2 || y->el == 2;
+    if (cplx) { if (int rb = single_op(A, "ttn_apply (ComplexF64)")) return rb; }
     if (cplx && y->el != 2) return refuse_mixed("ttn_apply (a complex operand needs a ComplexF64 output handle)");
     if (cplx && A->el != 2 && x->el != 2) return refuse_mixed("ttn_apply (a ComplexF64 output needs a complex operator or train)");
     const int d = x->d;
@@ -1023,6 +1045,7 @@ int ttn_apply_axpby(const double* alpha, ttn_tt_t x, const double* beta, ttn_tto
     if (!same_dims(A->dims, y->dims) || !same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_apply_axpby: output must not alias an input");
+    if (int rb = op_batch_fits(A, x->batch)) return rb;
     const int d = x->d, batch = x->batch;
     if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_axpby: the reference's + is only defined for d >= 2");
     std::vector<int64_t> zb(d + 1);
@@ -1285,6 +1308,7 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
     if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
+    if (int rb = single_op(A, "ttn_apply_compress")) return rb;
     const bool cplx = A->el == 2 || x->el == 2 || y->el == 2;     // ComplexF64: apply, then round (no fused complex merge)
     const char* nf = getenv("TTN_NOFUSE");
     if (!cplx && (x->d < 2 || (nf && atoi(nf)))) {          // nothing to fuse into / diagnostic switch
@@ -1324,6 +1348,7 @@ int ttn_apply_begin(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
     NEED_INIT();
     F64_ONLY("ttn_apply_begin", {x, y}, {A});
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
+    if (int rb = single_op(A, "ttn_apply_begin")) return rb;
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
     if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_begin: output must not alias the input");
@@ -1336,6 +1361,7 @@ int ttn_apply_sweep(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t k_first, int64_
     NEED_INIT();
     F64_ONLY("ttn_apply_sweep", {x, y}, {A});
     if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
+    if (int rb = single_op(A, "ttn_apply_sweep")) return rb;
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (k_first < 1 || k_first >= y->d || k_last < k_first || k_last >= y->d) return fail(TTN_ERR_BOND_INDEX, "ttn_apply_sweep: need 1 <= k_first <= k_last <= N-1 (one L->R pass)");
     if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
@@ -1923,6 +1949,7 @@ int ttn_tto_to_dense(ttn_tto_t A, const int64_t* xstrides, const int64_t* ystrid
     NEED_INIT();
     F64_ONLY("ttn_tto_to_dense", {}, {A});
     if (!A || !d_out) return fail(TTN_ERR_ARG, "ttn_tto_to_dense: null argument");
+    if (int rb = single_op(A, "ttn_tto_to_dense")) return rb;
     if ((xstrides == nullptr) != (ystrides == nullptr)) return fail(TTN_ERR_ARG, "ttn_tto_to_dense: xstrides and ystrides must both be given or both be null");
     const int d = A->d;
     if (d > TTN_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_to_dense: more than 64 sites");
@@ -2048,6 +2075,7 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
     NEED_INIT();
     F64_ONLY("ttn_als_linsolve", {b, x0, x}, {A});
     if (!A || !b || !x0 || !x) return fail(TTN_ERR_ARG, "null handle");
+    if (int rb = single_op(A, "ttn_als_linsolve")) return rb;
     if (sweep_count < 1) return fail(TTN_ERR_SWEEPS, "sweep_count must be >= 1");
     if (!same_dims(A->dims, b->dims) || !same_dims(b->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (b->batch != x0->batch || x->batch != x0->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
@@ -2360,6 +2388,7 @@ static int two_site_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, d
 
 int ttn_mals_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t rmax) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_mals_linsolve")) return rb;
     return two_site_linsolve(A, b, x0, x, tol, rmax, 0, {});
 }
 
@@ -2376,6 +2405,7 @@ static int dmrg_linsolve_impl(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, 
 int ttn_dmrg_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
                       const int64_t* rmax_schedule) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_dmrg_linsolve")) return rb;
     LocalSolver ls;                      // dense LU up to TTN_DENSE_LOCAL_MAX unknowns, matrix-free CG (tol 1e-8) above
     ls.tol = std::max(std::sqrt(std::max(tol, 0.0)), 1.0e-8);       // the reference's default linsolv_tol (dmrg.jl:394)
     return dmrg_linsolve_impl(A, b, x0, x, tol, n_stages, sweep_schedule, rmax_schedule, ls);
@@ -2384,6 +2414,7 @@ int ttn_dmrg_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double t
 int ttn_dmrg_linsolve_it(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
                          const int64_t* rmax_schedule, int it_solver, int64_t linsolv_maxiter, double linsolv_tol, int64_t itslv_thresh) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_dmrg_linsolve_it")) return rb;
     if (itslv_thresh < 0) return fail(TTN_ERR_ARG, "dmrg_linsolve: bad itslv_thresh");
     LocalSolver ls;
     ls.it_solver = it_solver ? 1 : 0; ls.itslv_thresh = itslv_thresh; ls.maxiter = linsolv_maxiter; ls.tol = linsolv_tol;
@@ -2427,6 +2458,7 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     if (!rmax_schedule || !E_out || !r_out) return err(TTN_ERR_ARG, "null schedule / history buffer");
     if (!same_dims(A->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != x0->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    if (int rb = op_batch_fits(A, x->batch)) return rb;
     const int d = x0->d;
     if (d < 2) return err(TTN_ERR_UNSUPPORTED, "needs at least two sites");
     if (!(tol >= 0.0) || maxiter < 1 || !(linsolv_tol >= 0.0) || itslv_thresh < 0) return err(TTN_ERR_ARG, "bad tol / linsolv_maxiter / linsolv_tol / itslv_thresh");
@@ -2621,6 +2653,7 @@ static int sandwich_launch(const char* who, ttn_tt_t x, ttn_tto_t A, ttn_tt_t y,
     F64_ONLY(who, {x, y}, {A});
     if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
+    if (int rb = op_batch_fits(A, x->batch)) return rb;
     const int d = x->d;
     if (d > EXPECT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: chains longer than 480 sites are not supported");
     if (x->stride >= (1LL << 31) || y->stride >= (1LL << 31) || A->off.back() >= (1LL << 31))
@@ -2821,6 +2854,7 @@ int ttn_sandwich_pullback(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, const double* del
     if (rc) return rc;
     if (A->el == 2) return refuse_c64("ttn_sandwich_pullback");
     const int d = x->d, batch = x->batch;
+    if (int rb = op_batch_fits(A, batch)) return rb;
     if (d > EXPECT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: chains longer than 480 sites are not supported");
     if (A->off.back() >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: an operator of 2^31 doubles or more");
     if (batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich_pullback: more than 65535 trains");
@@ -2898,6 +2932,7 @@ int ttn_apply_pullback(ttn_tto_t A, ttn_tt_t x, ttn_tt_t ybar, ttn_tt_t xbar) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!A || !x || !ybar || !xbar) return fail(TTN_ERR_ARG, "ttn_apply_pullback: null handle");
+    if (int rb = single_op(A, "ttn_apply_pullback")) return rb;
     if (xbar == x || xbar == ybar) return fail(TTN_ERR_ARG, "ttn_apply_pullback: the output must not alias an operand");
     if (!same_dims(A->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     int rc = grad_common("ttn_apply_pullback", {x, ybar, xbar});
@@ -4013,6 +4048,7 @@ int ttn_als_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, con
                      const double* noise_schedule, int64_t seed, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
                      int64_t hist_len, double* E) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_als_eigsolve")) return rb;
     return als_eig_impl(0, A, nullptr, x0, x, n_stages, sweep_schedule, rmax_schedule, noise_schedule, seed, it_solver, maxiter, linsolv_tol,
                         itslv_thresh, hist_len, E);
 }
@@ -4020,6 +4056,8 @@ int ttn_als_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, con
 int ttn_als_gen_eigsolve(ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t x, int64_t n_stages, const int64_t* sweep_schedule,
                          const int64_t* rmax_schedule, int it_solver, int64_t itslv_thresh, int64_t hist_len, double* E) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_als_gen_eigsolve")) return rb;
+    if (int rb = single_op(S, "ttn_als_gen_eigsolve")) return rb;
     return als_eig_impl(1, A, S, x0, x, n_stages, sweep_schedule, rmax_schedule, nullptr, 0, it_solver, 1, TTN_LOBPCG_TOL, itslv_thresh,
                         hist_len, E);
 }
@@ -4081,6 +4119,7 @@ int ttn_tt_increase_ranks(ttn_tt_t x, const int64_t* new_rks, double noise, uint
 int ttn_tto_set_ot(ttn_tto_t A, const int64_t* ot) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (!A || !ot) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_set_ot")) return rb;
     A->ot.assign(ot, ot + A->d);
     return TTN_OK;
 }
@@ -4099,6 +4138,7 @@ int ttn_tto_download(ttn_tto_t A, double* const* cores) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
     if (!A || !cores) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_download")) return rb;
     for (int k = 0; k < A->d; ++k) {
         if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_download: null core");
         const size_t sz = (size_t)A->el * A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1];
@@ -4114,6 +4154,8 @@ int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     NEED_INIT();
     F64_ONLY("ttn_tto_mul", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_mul")) return rb;
+    if (int rb = single_op(B, "ttn_tto_mul")) return rb;
     if (!same_dims(A->dims, B->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     const int d = A->d;
     std::vector<int64_t> rks(d + 1);
@@ -4147,6 +4189,8 @@ int ttn_tto_inner(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     NEED_INIT();
     F64_ONLY("ttn_tto_inner", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_inner")) return rb;
+    if (int rb = single_op(B, "ttn_tto_inner")) return rb;
     if (A->d != B->d) return fail(TTN_ERR_DIMS, "Inner core product requires operators with the same number of cores");
     const int d = A->d;
     std::vector<int64_t> rks(d + 1), dims(d);
@@ -4172,6 +4216,8 @@ int ttn_tto_add(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     NEED_INIT();
     F64_ONLY("ttn_tto_add", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_add")) return rb;
+    if (int rb = single_op(B, "ttn_tto_add")) return rb;
     if (!same_dims(A->dims, B->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     const int d = A->d;
     if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_tto_add: the reference's + is only defined for d >= 2");
@@ -4192,6 +4238,7 @@ int ttn_tto_scale(double a, ttn_tto_t A, ttn_tto_t* out) {
     NEED_INIT();
     F64_ONLY("ttn_tto_scale", {}, {A});
     if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_scale")) return rb;
     const int d = A->d;
     std::vector<int64_t> ot(A->ot);
     if (a == 0.0) std::fill(ot.begin(), ot.end(), 0);       // zeros_tto(dims, rks)
@@ -4215,6 +4262,8 @@ int ttn_tto_kron(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     NEED_INIT();
     F64_ONLY("ttn_tto_kron", {}, {A, B});
     if (!A || !B || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_kron")) return rb;
+    if (int rb = single_op(B, "ttn_tto_kron")) return rb;
     if (A->rks[A->d] != B->rks[0]) return fail(TTN_ERR_DIMS, "The final rank of the first TToperator must equal the initial rank of the second TToperator.");
     const int d = A->d + B->d;
     std::vector<int64_t> dims(A->dims), rks(A->rks.begin(), A->rks.end() - 1), ot(A->ot);
@@ -4320,6 +4369,7 @@ int ttn_tto_to_tt(ttn_tto_t A, ttn_tt_t y) {
     NEED_INIT();
     F64_ONLY("ttn_tto_to_tt", {y}, {A});
     if (!A || !y) return fail(TTN_ERR_ARG, "null handle");
+    if (int rb = single_op(A, "ttn_tto_to_tt")) return rb;
     const int d = A->d;
     if (y->d != d) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
     for (int k = 0; k < d; ++k) if (y->dims[k] != A->dims[k] * A->dims[k]) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -4367,6 +4417,7 @@ int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t swe
     NEED_INIT();
     F64_ONLY("ttn_tto_compress", {}, {A});
     if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (int rb = single_op(A, "ttn_tto_compress")) return rb;
     if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
     if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
     const int d = A->d;
@@ -4381,6 +4432,94 @@ int ttn_tto_compress(ttn_tto_t A, int64_t max_bond, double truncerr, int64_t swe
     if ((rc = ttn_compress(t.h, max_bond, truncerr, sweeps))) return rc;
     if ((rc = ttn_compress_status(t.h, nullptr))) return rc;
     return ttn_tto_from_tt(t.h, 0, out);
+}
+
+// ---- operator batches (include/ttn_opbatch.h, csrc/ttn_opbatch_kernels.h) -------------------------------------------------------------
+int ttn_tto_create_batch(int64_t d, const int64_t* dims, const int64_t* rks, int64_t batch, const double* const* cores, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!dims || !rks || !cores || !out || d < 1 || batch < 1) return fail(TTN_ERR_ARG, "ttn_tto_create_batch: bad argument");
+    for (int64_t k = 0; k < d; ++k) if (dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_tto_create_batch: dims must be >= 1");
+    for (int64_t m = 0; m <= d; ++m) if (rks[m] < 1) return fail(TTN_ERR_ARG, "ttn_tto_create_batch: ranks must be >= 1");
+    for (int64_t e = 0; e < batch * d; ++e) if (!cores[e]) return fail(TTN_ERR_ARG, "ttn_tto_create_batch: null core");
+    OwnedTTO A;
+    const int rc = tto_alloc(nullptr, 1, d, dims, rks, nullptr, cores, A, batch);
+    if (rc) return rc;
+    *out = A.release();
+    return TTN_OK;
+}
+
+int ttn_tto_from_tt_batch(ttn_tt_t v, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    F64_ONLY("ttn_tto_from_tt_batch", {v});
+    if (!v || !out) return fail(TTN_ERR_ARG, "null pointer");
+    const int d = v->d, batch = v->batch;
+    std::vector<int64_t> dims(d), rks(d + 1);
+    for (int k = 0; k < d; ++k) {
+        dims[k] = (int64_t)std::llround(std::sqrt((double)v->dims[k]));
+        if (dims[k] * dims[k] != v->dims[k]) return fail(TTN_ERR_DIMS, "DimensionMismatch: the dimensions of the train are not perfect squares");
+    }
+    // the one rank read: every train must hold the ranks of train 0 (they become the host-known ranks of the batch)
+    std::vector<long long> r64((size_t)batch * (d + 1));
+    HIPCHK(hipMemcpyAsync(r64.data(), v->d_rks, sizeof(long long) * r64.size(), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    for (int b = 1; b < batch; ++b)
+        for (int m = 0; m <= d; ++m)
+            if (r64[(size_t)b * (d + 1) + m] != r64[m])
+                return fail(TTN_ERR_DIMS, ("ttn_tto_from_tt_batch: the ranks of train " + std::to_string(b) + " differ from those of train 0 at bond " + std::to_string(m)
+                                           + " (" + std::to_string(r64[(size_t)b * (d + 1) + m]) + " against " + std::to_string(r64[m]) + "): one operator batch holds equal ranks").c_str());
+    long long maxsz = 1;
+    for (int m = 0; m <= d; ++m) {
+        rks[m] = r64[m];
+        if (rks[m] < 1 || rks[m] > v->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_tto_from_tt_batch: a rank of the trains is outside the capacity of their handle");
+    }
+    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)v->dims[k] * rks[k] * rks[k + 1]);
+    bool same_ot = true;
+    for (int b = 1; b < batch; ++b) for (int k = 0; k < d; ++k) same_ot = same_ot && v->ot[(size_t)b * d + k] == v->ot[k];
+    OwnedTTO Y;
+    int rc;
+    if ((rc = tto_alloc("ttn_tto_from_tt_batch", 1, d, dims.data(), rks.data(), same_ot ? v->ot.data() : nullptr, nullptr, Y, batch))) return rc;
+    HIPCHK(hipMemsetAsync(Y.h->d_data, 0, sizeof(double) * (size_t)std::max<long long>(Y.h->stride, 1) * batch, g_stream));     // the rounding gaps of odd cores
+    TTODev dst = Y.h->dev();
+    dst.stride = Y.h->stride;
+    hipLaunchKernelGGL(k_tto_pack, stream_grid((maxsz + 1) / 2, d, batch), dim3(TTN_STREAM_TB), 0, g_stream, v->dev(), dst, Y.h->d_data);
+    HIPCHK(hipGetLastError());
+    *out = Y.release();
+    return TTN_OK;
+}
+
+int ttn_tto_batch(ttn_tto_t A, int64_t* batch) {
+    if (!A || !batch) return fail(TTN_ERR_ARG, "null pointer");
+    *batch = A->batch;
+    return TTN_OK;
+}
+
+int ttn_tto_select(ttn_tto_t A, int64_t b, ttn_tto_t* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !out) return fail(TTN_ERR_ARG, "null pointer");
+    if (b < 0 || b >= A->batch) return fail(TTN_ERR_ARG, "ttn_tto_select: operator index outside the batch");
+    OwnedTTO Y;
+    int rc;
+    if ((rc = tto_alloc("ttn_tto_select", A->el, A->d, A->dims.data(), A->rks.data(), A->ot.data(), nullptr, Y))) return rc;
+    if (A->stride) HIPCHK(hipMemcpyAsync(Y.h->d_data, A->d_data + (size_t)b * A->stride, sizeof(double) * (size_t)A->stride, hipMemcpyDeviceToDevice, g_stream));
+    *out = Y.release();
+    return TTN_OK;
+}
+
+int ttn_tto_download_b(ttn_tto_t A, int64_t b, double* const* cores) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!A || !cores) return fail(TTN_ERR_ARG, "null pointer");
+    if (b < 0 || b >= A->batch) return fail(TTN_ERR_ARG, "ttn_tto_download_b: operator index outside the batch");
+    for (int k = 0; k < A->d; ++k) {
+        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_download_b: null core");
+        const size_t sz = (size_t)A->el * A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1];
+        HIPCHK(hipMemcpyAsync(cores[k], A->d_data + (size_t)b * A->stride + A->off[k], sizeof(double) * sz, hipMemcpyDeviceToHost, g_stream));
+    }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return TTN_OK;
 }
 
 // tto_decomp(tensor; index) from a dense array on the device (include/ttn_dense.h): k_dense_gather permutes the array into the layout

@@ -39,13 +39,15 @@ struct TTDev {
     int            batch;
 };
 
-// Device view of one TT operator.
+// Device view of one TT operator, or of a batch of operators of equal dims and ranks (include/ttn_opbatch.h): operator b, core k at
+// data + b*stride + off[k].  stride = 0: one operator serves every train.
 struct TTODev {
     const double*  data;
     const long long* off;     // [d+1] device
     const long long* rks;     // [d+1] device
     const int*     dims;      // [d] device
     int            d;
+    long long      stride;    // doubles per operator of a batch; 0 for a single operator
 };
 
 // A 2-level strided index: idx(i) = q ? (i % q)*lo + (i / q)*hi : i*lo.

@@ -458,7 +458,7 @@ struct EigArgs {
 };
 
 #define XC(i) (E.x.data + (long long)E.tb * E.x.stride + E.x.off[i])
-#define AC(i) (E.A.data + E.A.off[i])
+#define AC(i) (E.A.data + (long long)E.tb * E.A.stride + E.A.off[i])      // (stride 0: one operator for every train)
 #define GP(i) (E.scr + E.off[i])
 #define HP(i) (E.scr + E.off[2 * E.d + (i)])
 #define WG_FOR(total) for (long long e_ = threadIdx.x; e_ < (long long)(total); e_ += TTN_WG)

@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(TTN_WG) k_expgrad_chain(ExpGradArgs P) {
     __syncthreads();
     double* Xbase = X.data + (long long)t * X.stride;
     double* Ybase = Y.data + (long long)t * Y.stride;
-    double* Abase = const_cast<double*>(A.data);
+    double* Abase = const_cast<double*>(A.data) + (long long)t * A.stride;      // (stride 0: one operator for every train)
     double* E = P.env + ((long long)t * 2 + dir) * (d + 1) * P.W;
     double* wk = P.work + ((long long)t * 2 + dir) * P.wsz;
     if (dir == 0) {
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(EXPGRAD_TB) k_expgrad_core(ExpGradArgs P) {
     double* O = dst.data + (long long)t * dst.stride + dst.off[k];
     gmem_f64* L = (gmem_f64*)(P.env + ((long long)t * 2) * (d + 1) * P.W + (long long)k * P.W);
     gmem_f64* G = (gmem_f64*)(P.env + ((long long)t * 2 + 1) * (d + 1) * P.W + (long long)(k + 1) * P.W);
-    const double* Ak = P.A.data + P.A.off[k];
+    const double* Ak = P.A.data + (long long)t * P.A.stride + P.A.off[k];
     const double dl = P.delta ? P.delta[t] : 1.0;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
     const int nb = (T + 15) >> 4;                                         // waves that own a block of t
@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(TTN_WG) k_expgrad_core_gen(ExpGradArgs P) {
     const int n = uni32(P.x.dims[k]);
     double* Xk = unip(P.x.data + (long long)t * P.x.stride + P.x.off[k]);
     double* Yk = unip(P.y.data + (long long)t * P.y.stride + P.y.off[k]);
-    double* Ak = unip(const_cast<double*>(P.A.data) + P.A.off[k]);
+    double* Ak = unip(const_cast<double*>(P.A.data) + (long long)t * P.A.stride + P.A.off[k]);
     double* O = unip(dst.data + (long long)t * dst.stride + dst.off[k]);
     double* L = unip(P.env + ((long long)t * 2) * (d + 1) * P.W + (long long)k * P.W);                    // L_k[al + rx (rl + R bl)]
     double* G = unip(P.env + ((long long)t * 2 + 1) * (d + 1) * P.W + (long long)(k + 1) * P.W);          // G_{k+1}[a + rx2 (rho + R2 b)]

@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(TTN_WG) k_expect(ExpectArgs P) {
     __syncthreads();
     double* Xbase = X.data + (long long)t * X.stride;
     double* Ybase = Y.data + (long long)t * Y.stride;
-    double* Abase = const_cast<double*>(A.data);
+    double* Abase = const_cast<double*>(A.data) + (long long)t * A.stride;      // (stride 0: one operator for every train)
     if (RM > 0) {
         bool fit = true;
         for (int k = 0; k <= d; ++k) fit = fit && uni32(tab[EXPECT_TAB * k]) <= EXPECT_QTT_RMAX && uni32(tab[EXPECT_TAB * k + 1]) <= EXPECT_QTT_RMAX;

@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(TTN_STREAM_TB) k_apply_axpby(TTODev A, TTDev x
     const unsigned int cgroups = (uzr + TTN_AXPBY_K - 1) / TTN_AXPBY_K;
     const unsigned int items = (n == 2) ? uzl * cgroups : uzl * uzr;
     if (blockIdx.x * blockDim.x >= items) return;                         // (block-uniform: before the barrier below)
-    const double* Ak = A.data + A.off[k];
+    const double* Ak = A.data + (long long)b * A.stride + A.off[k];      // (stride 0: one operator for every train)
     const int asz = n * n * Rl * Rr;
     const bool in_lds = asz <= lds_a;
     if (in_lds) {

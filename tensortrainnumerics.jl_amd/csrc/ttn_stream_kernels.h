@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(TTN_STREAM_TB) k_apply(TTODev A, TTDev x, TTDe
     const int rl = (int)xr[k], rr = (int)xr[k + 1];
     const long long total = (long long)rl * rr;                       // input fibres
     const long long first = (long long)blockIdx.x * blockDim.x;
-    const double* Ak = A.data + A.off[k];
+    const double* Ak = A.data + (long long)b * A.stride + A.off[k];      // (stride 0: one operator for every train)
     const int asz = n * n * Rl * Rr;
     const bool in_lds = asz <= lds_a;
     // (the output-row mapping below counts rows x column groups, the mappings after it input fibres: a block beyond the work of its mapping leaves)

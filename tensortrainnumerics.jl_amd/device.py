@@ -19,7 +19,8 @@ from .tt import TToperator, TTvector, _f, _i64, _is_cplx, _ptrs, _z
 
 class DeviceTTO:
     """One TT operator in HBM (``ttn_tto``): immutable, ranks known on the host.  The algebra below (csrc/ttn_opalg_kernels.h) returns a
-    NEW ``DeviceTTO`` from every call and never crosses PCIe; ``download()`` brings the cores back."""
+    NEW ``DeviceTTO`` from every call and never crosses PCIe; ``download()`` brings the cores back.  ``batch`` > 1: an operator batch
+    (``stack`` / ``from_tt_batch`` / ``lincomb``), one operator per train of the trains it meets."""
 
     def __init__(self, A: TToperator):
         _lib.ensure_init()
@@ -36,8 +37,86 @@ class DeviceTTO:
             cores = [_f(c) for c in A.tto_vec]
             _lib.check(_lib.lib().ttn_tto_create(A.N, _i64(A.tto_dims), _i64(A.tto_rks), _ptrs(cores), C.byref(h)))
         self.h = h
+        self.batch = 1
         if any(self.ot):
             _lib.check(_lib.lib().ttn_tto_set_ot(self.h, _i64(self.ot)))
+
+    # operator batches (include/ttn_opbatch.h): B operators of equal dims and ranks in one handle, operator b for train b
+    @classmethod
+    def stack(cls, ops: Sequence[TToperator]) -> "DeviceTTO":
+        """A batch of host operators of equal dims and ranks in ONE handle (``ttn_tto_create_batch``): ``apply``, ``apply_axpby``,
+        ``sandwich`` / ``expect`` / ``rayleigh``, ``grad.sandwich_pullback``, ``dmrg_eigsolve_`` and ``mals_eigsolve_`` then use operator b
+        for train b; every other function refuses the handle (``select(b)`` gives it one operator).  Float64 only; gauge flags: zeros."""
+        ops = list(ops)
+        if not ops:
+            raise _lib.TTNError("stack: an operator batch needs at least one operator")
+        A0 = ops[0]
+        for b, A in enumerate(ops):
+            if _is_cplx(A.tto_vec):
+                raise _lib.TTNError(f"stack: operator {b} is complex; an operator batch is Float64 only")
+            if tuple(A.tto_dims) != tuple(A0.tto_dims) or A.N != A0.N:
+                raise _lib.TTNError(f"stack: the dims of operator {b} differ from those of operator 0; an operator batch holds equal dims")
+            if list(A.tto_rks) != list(A0.tto_rks):
+                raise _lib.TTNError(f"stack: the ranks of operator {b} differ from those of operator 0; an operator batch holds equal ranks")
+        _lib.ensure_init()
+        cores = [_f(c) for A in ops for c in A.tto_vec]
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tto_create_batch(A0.N, _i64(A0.tto_dims), _i64(A0.tto_rks), len(ops), _ptrs(cores), C.byref(h)))
+        return cls._adopt(h)
+
+    @classmethod
+    def from_tt_batch(cls, x: "DeviceTT") -> "DeviceTTO":
+        """ttv_to_tto of EVERY train of x (dims n_k^2) as one operator batch, on the device (``ttn_tto_from_tt_batch``, one packing
+        launch).  The trains must hold equal ranks (``TTNError`` otherwise).  Synchronises to read them."""
+        h = C.c_void_p()
+        rc = _lib.lib().ttn_tto_from_tt_batch(x.h, C.byref(h))
+        if rc:                      # (no assert of the reference stands behind this call: every refusal is a TTNError)
+            raise _lib.TTNError(f"ttn error {rc}: {_lib.last_error()}")
+        return cls._adopt(h)
+
+    @classmethod
+    def lincomb(cls, terms: Sequence["DeviceTTO"], coeffs) -> "DeviceTTO":
+        """The operator batch H_b = sum_j coeffs[b, j] * terms[j], assembled on the device: ``to_tt(B)`` -> ``scale_batch`` -> ``add`` ->
+        ``from_tt_batch``.  ``coeffs``: (B, J) real numbers.  The ranks are the sums of the terms' ranks, as for ``+`` (nothing is rounded)."""
+        terms = list(terms)
+        if not terms:
+            raise _lib.TTNError("lincomb: no terms")
+        for j, T in enumerate(terms):
+            if not isinstance(T, DeviceTTO):
+                raise TypeError(f"lincomb: term {j} is a {type(T).__name__}, expected a DeviceTTO")
+        c = np.asarray(coeffs, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != len(terms) or c.shape[0] < 1:
+            raise _lib.TTNError(f"lincomb: coeffs of shape {c.shape} for {len(terms)} terms (need (B, {len(terms)}) with B >= 1)")
+        for j, T in enumerate(terms):
+            if T.dims != terms[0].dims:
+                raise _lib.TTNError(f"lincomb: the dims of term {j} differ from those of term 0")
+            if T.dtype is np.complex128:
+                raise _lib.TTNError(f"lincomb: term {j} is complex; an operator batch is Float64 only")
+        B, N = int(c.shape[0]), terms[0].N
+        dims2 = [n * n for n in terms[0].dims]
+        acc = None
+        for j, T in enumerate(terms):
+            t = T.to_tt(B)                                   # (a term that is itself a batch is refused here)
+            s = DeviceTT(dims2, T.rks, B)
+            scale_batch(c[:, j], t, s)
+            t.free()
+            if acc is None:
+                acc = s
+                continue
+            rks = [1] + [acc.cap[m] + s.cap[m] for m in range(1, N)] + [1]
+            z = add(acc, s, DeviceTT(dims2, rks, B))
+            acc.free()
+            s.free()
+            acc = z
+        out = cls.from_tt_batch(acc)
+        acc.free()
+        return out
+
+    def select(self, b: int) -> "DeviceTTO":
+        """Operator b of the batch as a single ``DeviceTTO`` (one device copy)."""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ttn_tto_select(self.h, int(b), C.byref(h)))
+        return DeviceTTO._adopt(h)
 
     @classmethod
     def _adopt(cls, h: C.c_void_p) -> "DeviceTTO":
@@ -56,6 +135,9 @@ class DeviceTTO:
         cplx = C.c_int(0)
         _lib.check(L.ttn_tto_dtype(h, C.byref(cplx)))
         self.dtype = np.complex128 if cplx.value else np.float64
+        nb = C.c_int64(0)
+        _lib.check(L.ttn_tto_batch(h, C.byref(nb)))
+        self.batch = int(nb.value)
         return self
 
     def _binary(self, name: str, other: "DeviceTTO") -> "DeviceTTO":
@@ -165,9 +247,10 @@ class DeviceTTO:
     def ranks(self) -> List[int]:
         return list(self.rks)
 
-    def download(self) -> TToperator:
+    def download(self, b: int = 0) -> TToperator:
+        """The cores on the host; of an operator batch, those of operator b."""
         cores = [np.zeros((self.dims[k], self.dims[k], self.rks[k], self.rks[k + 1]), order="F", dtype=self.dtype) for k in range(self.N)]
-        _lib.check(_lib.lib().ttn_tto_download(self.h, _ptrs(cores)))
+        _lib.check(_lib.lib().ttn_tto_download_b(self.h, int(b), _ptrs(cores)))
         return TToperator(self.N, cores, self.dims, list(self.rks), list(self.ot))
 
     def free(self):

@@ -85,6 +85,12 @@ def _dev_op(A) -> DeviceTTO:
     return A if isinstance(A, DeviceTTO) else DeviceTTO(A)
 
 
+def _single_op(A, who: str) -> None:
+    """The linear solvers and the implicit steppers take one operator (the library's single_op refuses the rest of the list itself)."""
+    if isinstance(A, DeviceTTO) and A.batch > 1:
+        raise _lib.TTNError(f"{who}: an operator batch is not supported here (DeviceTTO.select(b) gives one operator of it)")
+
+
 def _host_level(run, A, *trains):
     """A stepper called with TTvectors: upload, run with batch 1, download; (TTvector, float) when the run returns an error too."""
     if not all(_is_host(t) for t in trains):
@@ -407,6 +413,7 @@ def krylov_linsolve(A, b: DeviceTT, guess: DeviceTT, max_bond: int = 0, krylov_s
                     ishermitian=None, isposdef: bool = False) -> DeviceTT:
     """src/solvers/euler.jl:34-74 on device-resident batches (A: TToperator or DeviceTTO; every train its own system)."""
     ishermitian = issymmetric if ishermitian is None else ishermitian
+    _single_op(A, "krylov_linsolve")
     dA = A if isinstance(A, DeviceTTO) else DeviceTTO(A)
     solver = "cg" if (krylov_solver == "auto" and isposdef and (issymmetric or ishermitian)) else krylov_solver   # :56
     if solver == "auto":
@@ -479,6 +486,7 @@ def _solve(tt_solver: str, lhs: DeviceTTO, rhs: DeviceTT, guess: DeviceTT, max_b
 
 def _implicit_stepper(who, A, u0, guess, steps, normalize, return_error, tt_solver, max_bond, crank, kw):
     _check_solver(who, tt_solver, kw)
+    _single_op(A, who)
     if _is_host(u0) or _is_host(guess):
         return _host_level(lambda dA, du, dg: _implicit_stepper(who, dA, du, dg, steps, normalize, return_error, tt_solver, max_bond, crank, kw),
                            A, u0, guess)
