@@ -5,7 +5,8 @@
 //   2. eigenvalues by multisection on Sturm counts (T lanes per eigenvalue, log2(T+1) bits per round, fast reciprocal:
 //      the count is that of a matrix whose off-diagonal squares are perturbed by 2^-50 relative);
 //   3. eigenvectors of the kept eigenvalues by one twisted factorisation each (Fernando 1997; LAPACK dlar1v without the
-//      representation tree): D+ and D- pivots in LDS, one lane per vector, no pivoting, no reorthogonalisation —
+//      representation tree): the pivots in ONE LDS array (D- in registers until the twist is known), one lane per vector, no
+//      pivoting, no reorthogonalisation —
 //      scratch/eig_feasibility2.py measures |U'U - I| ~ 1e-13 on merged matrices of the benchmark; the caller's a-posteriori
 //      check (FAST_CHECK_TOL) and its Householder + Jacobi fallback cover the rest;
 //   4. back-transformation by the stored reflectors (lane = column, wave = 8 rows).
@@ -27,9 +28,12 @@ __device__ __forceinline__ void fmac_bcast(double& a, double w, double s_) {
 }
 #define EIG_BCAST16(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
 // LDS map (doubles) inside the 128*128 + 512 Jacobi/GEMM image `L`:
-//   [0, 16384)            phase 1: vL, wL, xcol (3 x 128), part (8 x 128)   | phase 3: D+ then D- ([row][lane], 2 x 8192)
-//                         phase 4: partial dot products (2 x 16 x 64), then the output image X (ld 128)
-//   [16384, 16896)        dg, e, lam, beta (4 x 128)
+//   [0, 16384)            phase 1: vL, wL, xcol (3 x 128), part (8 x 128)   | phase 3: the pivot array D ([row][lane], N x 64)
+//                         phase 4: the staged reflectors, then the output image X (ld 128)
+//   [16384, 16896)        dg, e, lam, beta (4 x 128); e[N-1], which couples nothing, carries max e^2 from phase 2 to phase 3
+//   behind the GEMM descriptor (L + GEMM_LDS_DOUBLES + 32, the offset tables of the GEMMs, dead while the solver runs):
+//                         phase 3: the holders' twist candidates, |gamma| (4 x 64 doubles) and row (4 x 64 ints)
+// (the 512-thread build: an image of 8192 doubles, the tail at [8192, 8704))
 #define EIG_TAIL TTN_LDS_IMG
 
 // ---- 1. tridiagonalisation: dg[0..127], e[0..126] (e[k] couples k, k+1), reflectors v_k (rows of Vst, zeros up to k) and beta_k ----
@@ -276,7 +280,8 @@ __device__ void wg_bisect(int nev, double* lds) {
             emax_ = fmax(emax_, e2[t]);
         }
         glo_ = -wave_max(-glo_); ghi_ = wave_max(ghi_); emax_ = wave_max(emax_);
-        if (tid == 0) { e2[128] = glo_; e2[129] = ghi_; e2[130] = emax_; }
+        // e[N-1] (no coupling below the last row: never written by wg_tridiag, guarded at every read) keeps max e^2 for wg_twisted
+        if (tid == 0) { e2[128] = glo_; e2[129] = ghi_; e2[130] = emax_; e[N - 1] = emax_; }
     }
     __syncthreads();
     double glo = e2[128], ghi = e2[129];
@@ -319,38 +324,39 @@ __device__ void wg_bisect(int nev, double* lds) {
     __syncthreads();
 }
 
-// ---- 3. eigenvectors of lam[0..r-1] (r <= 64) by twisted factorisations; z (unnormalised) stays split over the D+ / D- arrays,
-//         twist index and 1/||z|| per vector in tw[], zn[].  One lane per vector; wave 0 runs the top-down recurrences (D+, then
-//         z above the twist), wave 1 the bottom-up ones (D-, z below the twist) at the same time.  The recurrences are dependent
-//         chains: the operands of 8 steps are fetched from LDS together. ----
-// D- (and the part of z below the twist) lives in LDS behind D+ when both fit the image (2 * N * 64 doubles), otherwise in global
-// memory (`Dmg`, N * 64 doubles: the dead Gram matrix) — [row][lane] there too, so every access is one coalesced 512-byte line,
-// the stores are fire-and-forget and the loads of 8 steps are issued together like the LDS ones.
+// ---- 3. eigenvectors of lam[0..r-1] (r <= 64) by twisted factorisations; z (unnormalised) is left in the pivot array D, twist index
+//         and 1/||z|| per vector in tw[], zn[].  One lane per vector.  The recurrences are dependent chains: the operands of 8
+//         steps are fetched from LDS together. ----
+// ONE pivot array D[row][lane] (N x 64 doubles: all the image holds for N = 128 in the 512-thread build) serves both factorisations:
+// once the twist index kb of a vector is known, D+ is needed in rows < kb only and D- in rows > kb.  Wave 0 runs the top-down
+// recurrence D+ into D.  D- stays in REGISTERS until the twist is known: EIG_HOLDERS waves each run the whole bottom-up recurrence
+// from row N - 1 down to their own rows (the same instructions on the same operands, so the same values in each) and each keeps
+// N / EIG_HOLDERS rows of it.  Every holder finds the first minimum of |gamma| over its rows; the candidates meet in LDS, combined
+// in ascending row order with a strict < (what one ascending scan finds, ties included); the holders then write D- over D+ in the
+// rows below each lane's twist, and wave 0 (upwards from the twist, D+) and wave 1 (downwards, D-) run the z chains in place.
+// No global memory anywhere, and G stays untouched.
+#define EIG_HOLDERS 4                                            // waves 1 .. 4; holder h keeps rows (N/4) h .. (N/4)(h + 1) - 1: at most 64 VGPRs
 template <int N>
-struct EigDm {
-    static constexpr bool IN_LDS = 2 * N * 64 <= TTN_LDS_IMG;
-    typedef __attribute__((address_space(1))) double gdouble;
-    lds_f64* l;
-    gdouble* g;
-    __device__ __forceinline__ double ld(int idx) const { if constexpr (IN_LDS) return l[idx]; else return g[idx]; }
-    __device__ __forceinline__ void st(int idx, double v) const { if constexpr (IN_LDS) l[idx] = v; else g[idx] = v; }
-};
-template <int N>
-__device__ void wg_twisted(int r, double* lds, int* tw /*LDS 64 ints*/, lds_f64* zn /*LDS 64 + 64 (partial norms)*/, double* Dmg) {
+__device__ void wg_twisted(int r, double* lds, int* tw /*LDS 64 ints*/, lds_f64* zn /*LDS 64 + 64 (partial norms)*/) {
+    static_assert(N % (8 * EIG_HOLDERS) == 0 && TTN_WG >= 64 * (EIG_HOLDERS + 1) && N * 64 <= TTN_LDS_IMG, "one array in the image; wave 0 and the holders");
+    static_assert(EIG_HOLDERS * 64 + EIG_HOLDERS * 32 <= GEMM_TAB_ENTRIES, "the twist candidates fit the table area");
+    constexpr int HC = N / 8 / EIG_HOLDERS;                      // 8-row chunks per holder
     lds_f64* L = (lds_f64*)lds;
     lds_f64 *dg = L + EIG_TAIL, *e = dg + 128, *lam = dg + 256;
-    lds_f64* Dp = L;                                           // [row][lane]
-    EigDm<N> Dm;
-    Dm.l = L + N * 64; Dm.g = (typename EigDm<N>::gdouble*)(unsigned long long)Dmg;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // (d_i, e_i) pairs in the reflector scalars' slot are not available: the bisection's pair array lives in L[256..512) = Dp rows
+    lds_f64* D = L;                                            // [row][lane]
+    // twist candidates (|gamma|, row) of every holder, per lane: the GEMM offset tables behind the image are dead while the solver runs
+    lds_f64* cg = L + GEMM_LDS_DOUBLES + 32;
+    lds_i32* ck = (lds_i32*)(cg + EIG_HOLDERS * 64);
+    const int tid = threadIdx.x, lane = tid & 63, wave = uni32(tid >> 6);
+    const bool holder = wave >= 1 && wave <= EIG_HOLDERS;
+    const int c0 = HC * (wave - 1);                              // a holder's first chunk
+    // (d_i, e_i) pairs in the reflector scalars' slot are not available: the bisection's pair array lives in L[256..512) = D rows
     // 4..7, so the chains read dg / e directly in chunks
-    double emax = 0.0;
-    for (int t = 0; t < N - 1; ++t) emax = fmax(emax, e[t] * e[t]);
-    const double pivmin = DBL_MIN * fmax(1.0, emax);
-    __syncthreads();                                             // the bisection's arrays (aliasing Dp) are no longer read
+    const double pivmin = DBL_MIN * fmax(1.0, e[N - 1]);         // max e^2, left there by wg_bisect
+    __syncthreads();                                             // the bisection's arrays (aliasing D) are no longer read
     const bool act = lane < r;
     const double lm = lam[act ? lane : 0];
+    double keep[HC][8];                                          // a holder's rows of D-
     if (wave == 0) {                                             // D+_0 = d_0 - lam ; D+_i = (d_i - lam) - e_{i-1}^2 / D+_{i-1}
         double q = 1.0;
         for (int i0 = 0; i0 < N; i0 += 8) {
@@ -361,71 +367,84 @@ __device__ void wg_twisted(int r, double* lds, int* tw /*LDS 64 ints*/, lds_f64*
             for (int t = 0; t < 8; ++t) {
                 q = fma(-(ee[t] * ee[t]), fast_rcp(q), dd[t] - lm);
                 if (fabs(q) < pivmin) q = -pivmin;
-                Dp[(i0 + t) * 64 + lane] = q;
+                D[(i0 + t) * 64 + lane] = q;
             }
         }
-    } else if (wave == 1) {                                      // D-_{n-1} = d_{n-1} - lam ; D-_i = (d_i - lam) - e_i^2 / D-_{i+1}
-        double q = 1.0;
-        for (int i0 = N - 8; i0 >= 0; i0 -= 8) {
+    } else if (holder) {                                         // D-_{n-1} = d_{n-1} - lam ; D-_i = (d_i - lam) - e_i^2 / D-_{i+1}
+        // one 8-row chunk, rows i0 + 7 down to i0
+        auto chunk = [&](int i0, double& q, auto put) {
             double dd[8], ee[8];
 #pragma unroll
-            for (int t = 0; t < 8; ++t) { dd[t] = dg[i0 + t]; ee[t] = (i0 + t < N - 1) ? e[i0 + t] : 0.0; }
+            for (int t = 7; t >= 0; --t) { dd[t] = dg[i0 + t]; ee[t] = (i0 + t < N - 1) ? e[i0 + t] : 0.0; }
 #pragma unroll
             for (int t = 7; t >= 0; --t) {
                 q = fma(-(ee[t] * ee[t]), fast_rcp(q), dd[t] - lm);
                 if (fabs(q) < pivmin) q = -pivmin;
-                Dm.st((i0 + t) * 64 + lane, q);
+                put(t, q);
+            }
+        };
+        double q = 1.0;
+        for (int ch = N / 8 - 1; ch >= c0 + HC; --ch) chunk(8 * ch, q, [](int, double) {});      // the rows below the kept ones: the chain alone
+#pragma unroll
+        for (int c = HC - 1; c >= 0; --c) chunk(8 * (c0 + c), q, [&](int t, double v) { keep[c][t] = v; });
+    }
+    lds_barrier();                                               // D+ is complete
+    if (holder) {
+        // twist index: argmin |gamma_i|, gamma_i = D+_i + D-_i - (d_i - lam); a holder's first minimum over its rows, ascending
+        double gbest = 1e300;
+        int kc = 0;
+#pragma unroll
+        for (int c = 0; c < HC; ++c) {
+            const int i0 = 8 * (c0 + c);
+            double dp[8], dd[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) { dp[t] = D[(i0 + t) * 64 + lane]; dd[t] = dg[i0 + t]; }
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const double g = fabs(dp[t] + keep[c][t] - (dd[t] - lm));
+                if (g < gbest) { gbest = g; kc = i0 + t; }
+            }
+        }
+        cg[(wave - 1) * 64 + lane] = gbest; ck[(wave - 1) * 64 + lane] = kc;
+    }
+    lds_barrier();
+    int kb = 0;
+    if (wave <= EIG_HOLDERS) {
+        double gbest = 1e300;
+#pragma unroll
+        for (int h = 0; h < EIG_HOLDERS; ++h) {
+            const double g = cg[h * 64 + lane];
+            const int k = ck[h * 64 + lane];
+            if (g < gbest) { gbest = g; kb = k; }
+        }
+    }
+    if (holder) {
+        // D- of the rows below the twist replaces D+ there (a per-lane predicate on a plain ds_write)
+#pragma unroll
+        for (int c = 0; c < HC; ++c) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const int row = 8 * (c0 + c) + t;
+                if (row > kb) D[row * 64 + lane] = keep[c][t];
             }
         }
     }
-    __syncthreads();                                             // (a workgroup barrier also completes the global stores of D-)
+    lds_barrier();                                               // wave 1 reads what the other holders wrote
     if (wave < 2) {
-        // twist index: argmin |gamma_i|, gamma_i = D+_i + D-_i - (d_i - lam)   (both waves, redundantly: independent iterations)
-        double gbest = 1e300;
-        int kb = 0;
-        for (int i0 = 0; i0 < N; i0 += 8) {
-            double dm[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) dm[t] = Dm.ld((i0 + t) * 64 + lane);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const double g = fabs(Dp[(i0 + t) * 64 + lane] + dm[t] - (dg[i0 + t] - lm));
-                if (g < gbest) { gbest = g; kb = i0 + t; }
-            }
-        }
         // z_k = 1; wave 0: upwards with D+, wave 1: downwards with D-; the entries replace the pivots they consumed
         double z = 1.0, nrm = 0.0;
         if (wave == 0) {
             for (int i = kb - 1; i >= 0; --i) {
-                z = -(e[i] * fast_rcp(Dp[i * 64 + lane])) * z;
-                Dp[i * 64 + lane] = z;
+                z = -(e[i] * fast_rcp(D[i * 64 + lane])) * z;
+                D[i * 64 + lane] = z;
                 nrm = fma(z, z, nrm);
             }
             if (act) { tw[lane] = kb; zn[lane] = nrm; }
         } else {
-            if constexpr (EigDm<N>::IN_LDS) {
-                for (int i = kb; i < N - 1; ++i) {
-                    z = -(e[i] * fast_rcp(Dm.ld((i + 1) * 64 + lane))) * z;
-                    Dm.st((i + 1) * 64 + lane, z);
-                    nrm = fma(z, z, nrm);
-                }
-            } else {
-                // global D-: the twist index differs per lane, so the chain runs over ALL rows in chunks of 8 with the loads of a
-                // chunk in flight together; rows at or above a lane's twist are left alone
-                for (int i0 = 0; i0 < N - 1; i0 += 8) {
-                    double dm[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) dm[t] = (i0 + t + 1 < N) ? Dm.ld((i0 + t + 1) * 64 + lane) : 1.0;
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const int i = i0 + t;
-                        if (i >= kb && i < N - 1) {
-                            z = -(e[i] * fast_rcp(dm[t])) * z;
-                            Dm.st((i + 1) * 64 + lane, z);
-                            nrm = fma(z, z, nrm);
-                        }
-                    }
-                }
+            for (int i = kb; i < N - 1; ++i) {
+                z = -(e[i] * fast_rcp(D[(i + 1) * 64 + lane])) * z;
+                D[(i + 1) * 64 + lane] = z;
+                nrm = fma(z, z, nrm);
             }
             if (act) zn[64 + lane] = nrm;
         }
@@ -439,9 +458,8 @@ __device__ void wg_twisted(int r, double* lds, int* tw /*LDS 64 ints*/, lds_f64*
 // Eigen-decomposition of the symmetric positive definite N x N matrix G (global, column-major, leading dimension ldg), N = 128 or
 // 64: the `nev` largest eigenvalues (descending) -> sig[j] = sqrt(lam_j) (global), and the image X (LDS, ld 128):
 // X[j*128 + row] = sqrt(lam_j) * u_j[row] for j < r (r <= 64, r <= nev).  Vst: 128 x 128 doubles of global scratch.
-// Returns 0, or 1 if a wanted eigenvalue is not positive.  When the D+ / D- arrays of the twisted factorisations do not both fit
-// the LDS image (N = 128 in the 512-thread build) G ITSELF IS OVERWRITTEN (its first N * 64 doubles hold D-): it is dead once
-// the tridiagonalisation has loaded it.
+// Returns 0, or 1 if a wanted eigenvalue is not positive.  G is only read.  Besides the image and its tail the routine uses the GEMM
+// offset-table area behind them (lds + GEMM_LDS_DOUBLES + 32, GEMM_TAB_ENTRIES doubles: the twist candidates of wg_twisted).
 template <int N>
 __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork /*LDS 64 ints*/,
                                      double* dwork /*LDS 128*/) {
@@ -465,13 +483,11 @@ __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int
         __builtin_amdgcn_s_setprio(0); TTN_SETPRIO_BASE();
         return 1;
     }
-    wg_twisted<N>(r, lds, iwork, (lds_f64*)dwork, const_cast<double*>(Gg));
+    wg_twisted<N>(r, lds, iwork, (lds_f64*)dwork);
     // Z into registers: waves 0..7; a row of 16 lanes owns TWO columns (8 per wave), lane rc of the row holds rows RPL*rc ..
     // RPL*rc + RPL-1 of both — the dot products v_k' z are reductions over the 16 lanes of a row (4 DPP adds each): no LDS
-    // reduction and no barrier in the loop.  The reflectors are staged in LDS once (the D+ / D- arrays are dead after the load of Z).
-    lds_f64* Dp = L;
-    EigDm<N> Dm;
-    Dm.l = L + N * 64; Dm.g = (typename EigDm<N>::gdouble*)(unsigned long long)Gg;
+    // reduction and no barrier in the loop.  The reflectors are staged in LDS once (the pivot array is dead after the load of Z).
+    lds_f64* D = L;                                             // rows < kb: z above the twist, rows > kb: z below it
     // lane groups as in the Jacobi (grp_sum): the 16 lanes {B + 4g + 16k} form group g; member index rc; the 16-lane sums of the
     // two dot products per reflector then run on the matrix pipe (2 x 2 v_mfma_f64_4x4x4 instead of 2 x 12 VALU instructions)
     const int rc = (lane & 3) | ((lane >> 4) << 2), col0 = 8 * (wave & 7) + 2 * ((lane >> 2) & 3);
@@ -484,7 +500,7 @@ __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int
 #pragma unroll
         for (int t = 0; t < RPL; ++t) {
             const int row = RPL * rc + t;
-            const double v = (row < kb) ? Dp[row * 64 + col] : ((row == kb) ? 1.0 : Dm.ld(row * 64 + col));
+            const double v = (row == kb) ? 1.0 : D[row * 64 + col];
             z[cc][t] = v * zn;
         }
     }
@@ -513,7 +529,7 @@ __device__ __noinline__ int wg_eig_n(const double* Gg, int ldg, double* Vst, int
         }
     }
     }
-    __syncthreads();                                              // everyone has consumed D+ / D-: the image may be written
+    __syncthreads();                                              // everyone is done with the staged reflectors: the image may be written
     if (wave < 8) {
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
