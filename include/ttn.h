@@ -651,6 +651,12 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * refuses it).  Declared in ttn_opbatch.h, which this header includes. */
 #include "ttn_opbatch.h"
 
+/* ---- site-resolved measurements (csrc/ttn_measure_kernels.h) --------------------------------------------------------
+ * The profile <x| O_k |x> / <x, x> of every site and the two-point functions <x| P_i Q_j |x> / <x, x> of ALL pairs, per train, from one
+ * pair of environment chains: ttn_site_expect, ttn_correlation and their _dev forms.  Declared in ttn_measure.h, which this header
+ * includes. */
+#include "ttn_measure.h"
+
 #ifdef __cplusplus
 }
 #endif

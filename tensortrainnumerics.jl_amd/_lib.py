@@ -220,6 +220,14 @@ OPBATCH_SIGNATURES = {
     "ttn_tto_download_b": (C.c_int, [handle, i64, pp_f64]),
 }
 
+# site-resolved measurements, include/ttn_measure.h (the tables are host arrays; `out` is host, `d_out` device memory)
+MEASURE_SIGNATURES = {
+    "ttn_site_expect": (C.c_int, [handle, i64, p_f64, i64, p_f64]),
+    "ttn_site_expect_dev": (C.c_int, [handle, i64, p_f64, i64, C.c_void_p]),
+    "ttn_correlation": (C.c_int, [handle, p_f64, p_f64, i64, p_f64]),
+    "ttn_correlation_dev": (C.c_int, [handle, p_f64, p_f64, i64, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -229,7 +237,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
     srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
              os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h"),
-             os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h")]
+             os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h"), os.path.join(INCLUDE, "ttn_measure.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -253,7 +261,8 @@ def lib() -> C.CDLL:
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
-            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()) + list(OPBATCH_SIGNATURES.items()):
+            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()) + list(OPBATCH_SIGNATURES.items())\
+            + list(MEASURE_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -623,6 +623,131 @@ def rayleigh(A: DeviceTTO, x: DeviceTT) -> np.ndarray:
     return expect(A, x) / dot(x, x)
 
 
+# ---- site-resolved measurements (include/ttn_measure.h, csrc/ttn_measure_kernels.h) ---------------------------------
+def _header_define(header: str, name: str) -> int:
+    import os
+    import re
+    m = re.search(r"#define\s+%s\s+(\d+)" % re.escape(name), open(os.path.join(_lib.INCLUDE, header)).read())
+    if m is None:
+        raise RuntimeError(f"{header} does not define {name}")
+    return int(m.group(1))
+
+
+MEASURE_MAX_OPS = _header_define("ttn_measure.h", "TTN_MEASURE_MAX_OPS")     # operator tables per site_expect call
+
+
+def _measure_table(who: str, name: str, op, dims: Sequence[int]) -> np.ndarray:
+    """One operator table of include/ttn_measure.h from ``op`` — an (n, n) array used at every site, or a sequence of d arrays —: the
+    per-site matrices column-major, back to back, float64.  Shape and dtype errors are raised here, before any device call."""
+    d = len(dims)
+    if isinstance(op, (list, tuple)) and len(op) > 0 and all(np.ndim(o) == 2 for o in op):
+        mats = list(op)
+    else:
+        a = np.asarray(op)
+        if a.dtype == object or a.ndim not in (2, 3):
+            raise _lib.TTNError(f"{who}: {name} must be an (n, n) array or a sequence of {d} such arrays, got shape {getattr(a, 'shape', None)}")
+        mats = [a] * d if a.ndim == 2 else list(a)
+    if len(mats) != d:
+        raise _lib.TTNError(f"{who}: {name} holds {len(mats)} matrices for {d} sites")
+    flat = []
+    for k, (m, n) in enumerate(zip(mats, dims)):
+        m = np.asarray(m)
+        if np.iscomplexobj(m):
+            raise _lib.TTNError(f"{who}: {name} at site {k} is complex: Float64 only (for sigma_y use [[0, 1], [-1, 0]] = i sigma_y in a correlator)")
+        if m.dtype == object or not (np.issubdtype(m.dtype, np.number) or m.dtype == bool):
+            raise _lib.TTNError(f"{who}: {name} at site {k} has dtype {m.dtype}, expected real numbers")
+        if m.shape != (n, n):
+            raise _lib.TTNError(f"{who}: {name} at site {k} has shape {m.shape}, expected ({n}, {n})")
+        flat.append(np.asarray(m, dtype=np.float64).flatten(order="F"))
+    return np.concatenate(flat)
+
+
+def _measure_train(who: str, x) -> None:
+    if not isinstance(x, DeviceTT):
+        raise TypeError(f"{who}: expected a DeviceTT, got {type(x).__name__}")
+
+
+def _p_f64(a: np.ndarray):
+    return a.ctypes.data_as(_lib.p_f64)
+
+
+def _site_expect_tables(x: DeviceTT, ops) -> np.ndarray:
+    _measure_train("site_expect", x)
+    if not ops:
+        raise _lib.TTNError("site_expect: no operator given")
+    return np.concatenate([_measure_table("site_expect", f"operator {t}", op, x.dims) for t, op in enumerate(ops)])
+
+
+def site_expect(x: DeviceTT, *ops, normalize: bool = True) -> np.ndarray:
+    """The profile E_O[k] = <x_b| O_k |x_b> / <x_b, x_b> of every site and train (ttn_site_expect): (batch, d) for one operator,
+    (batch, nops, d) for several (at most ``MEASURE_MAX_OPS``), all from ONE pair of environment chains.  Each ``op`` is an (n, n) array
+    used at every site or a sequence of d arrays; its first index meets the bra, as the output index of an operator in ``sandwich``.
+    The train is real, so only the symmetric part of an operator is seen: an antisymmetric one ([[0, 1], [-1, 0]] = i sigma_y) gives
+    zeros.  ``normalize=False`` leaves the division out; a zero train with ``normalize=True`` gives NaN (0 / 0).  Float64 only.
+    Synchronises, as ``dot``."""
+    tabs = _site_expect_tables(x, ops)
+    out = np.empty(x.batch * len(ops) * x.N, dtype=np.float64)
+    _lib.check(_lib.lib().ttn_site_expect(x.h, len(ops), _p_f64(tabs), 1 if normalize else 0, _p_f64(out)))
+    res = out.reshape(x.batch, len(ops), x.N)
+    return res[:, 0, :].copy() if len(ops) == 1 else res
+
+
+def site_expect_dev(x: DeviceTT, *ops, normalize: bool = True, out=None):
+    """``site_expect`` into a float64 device tensor (batch, nops, d) (``out``, or a new one), asynchronously on the library stream.  The
+    tensor must not be read on another stream before ``sync()``."""
+    import torch
+    tabs = _site_expect_tables(x, ops)
+    shape = (x.batch, len(ops), x.N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device="cuda")
+    if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError(f"site_expect_dev: out must be a contiguous float64 device tensor of shape {shape}")
+    _lib.check(_lib.lib().ttn_site_expect_dev(x.h, len(ops), _p_f64(tabs), 1 if normalize else 0, C.c_void_p(out.data_ptr())))
+    return out
+
+
+def _correlation_tables(x: DeviceTT, P, Q):
+    _measure_train("correlation_matrix", x)
+    tp = _measure_table("correlation_matrix", "P", P, x.dims)
+    tq = tp if (Q is None or Q is P) else _measure_table("correlation_matrix", "Q", Q, x.dims)
+    return tp, tq
+
+
+def correlation_matrix(x: DeviceTT, P, Q=None, normalize: bool = True, connected: bool = False) -> np.ndarray:
+    """C[b, i, j] = <x_b| P_i Q_j |x_b> / <x_b, x_b> for ALL pairs of sites (ttn_correlation): (batch, d, d).  ``P`` and ``Q`` are given
+    as in ``site_expect``; ``Q=None`` means Q = P.  The diagonal is the matrix product P_i Q_i on one site; off the diagonal the two
+    act on different sites and commute; the matrix is in general not symmetric when P != Q.  A correlator sees antisymmetric factors:
+    P = Q = [[0, 1], [-1, 0]] (= i sigma_y) gives MINUS <sigma_y sigma_y> — how a Float64 train yields its YY correlations.
+    ``connected=True`` subtracts E_P[i] E_Q[j] (on the diagonal E_P[i] E_Q[i]) with the profiles of ``site_expect`` at the same
+    ``normalize`` (a connected correlator is meant for ``normalize=True``).  Cost: the two chains, then one short walk per site and
+    triangle — one triangle when P and Q are equal bit for bit, the other mirrored.  Reproducible to rounding, not bitwise.
+    Synchronises."""
+    tp, tq = _correlation_tables(x, P, Q)
+    d = x.N
+    out = np.empty(x.batch * d * d, dtype=np.float64)
+    _lib.check(_lib.lib().ttn_correlation(x.h, _p_f64(tp), _p_f64(tq), 1 if normalize else 0, _p_f64(out)))
+    res = np.ascontiguousarray(out.reshape(x.batch, d, d).transpose(0, 2, 1))       # the ABI stores C[i, j] at i + d j
+    if connected:
+        ep = site_expect(x, P, normalize=normalize)
+        eq = ep if (Q is None or Q is P) else site_expect(x, Q, normalize=normalize)
+        res -= ep[:, :, None] * eq[:, None, :]
+    return res
+
+
+def correlation_matrix_dev(x: DeviceTT, P, Q=None, normalize: bool = True, out=None):
+    """``correlation_matrix`` (not connected) asynchronously on the library stream: returns the (batch, d, d) VIEW C[b, i, j] of a
+    float64 device tensor in the layout of the ABI (``out``, contiguous (batch, d, d) holding C[b, j, i], or a new one)."""
+    import torch
+    tp, tq = _correlation_tables(x, P, Q)
+    shape = (x.batch, x.N, x.N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device="cuda")
+    if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError(f"correlation_matrix_dev: out must be a contiguous float64 device tensor of shape {shape}")
+    _lib.check(_lib.lib().ttn_correlation_dev(x.h, _p_f64(tp), _p_f64(tq), 1 if normalize else 0, C.c_void_p(out.data_ptr())))
+    return out.transpose(1, 2)
+
+
 def norm(a: DeviceTT) -> np.ndarray:
     out = (C.c_double * a.batch)()
     _lib.check(_lib.lib().ttn_norm(a.h, out))

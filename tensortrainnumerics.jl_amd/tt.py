@@ -300,6 +300,37 @@ def rayleigh(A: TToperator, x: TTvector) -> float:
     return expect(A, x) / dot(x, x)
 
 
+def site_expect(x: TTvector, *ops, normalize: bool = True) -> np.ndarray:
+    """The profile <x| O_k |x> / <x, x> of every site (``device.site_expect``): (d,) for one operator, (nops, d) for several.  The train
+    is uploaded, the kernels run, the handle is freed.  Float64 only."""
+    from .device import DeviceTT, _measure_table, site_expect as dev_site_expect
+    for t, op in enumerate(ops):                    # the argument checks, before the upload
+        _measure_table("site_expect", f"operator {t}", op, x.ttv_dims)
+    dx = None
+    try:
+        dx = DeviceTT.from_host(x)
+        return dev_site_expect(dx, *ops, normalize=normalize)[0]
+    finally:
+        if dx is not None:
+            dx.free()
+
+
+def correlation_matrix(x: TTvector, P, Q=None, normalize: bool = True, connected: bool = False) -> np.ndarray:
+    """C[i, j] = <x| P_i Q_j |x> / <x, x> for all pairs of sites (``device.correlation_matrix``): (d, d).  Upload, call, free.
+    Float64 only."""
+    from .device import DeviceTT, _measure_table, correlation_matrix as dev_correlation_matrix
+    for name, op in (("P", P), ("Q", Q)):           # the argument checks, before the upload
+        if op is not None:
+            _measure_table("correlation_matrix", name, op, x.ttv_dims)
+    dx = None
+    try:
+        dx = DeviceTT.from_host(x)
+        return dev_correlation_matrix(dx, P, Q, normalize=normalize, connected=connected)[0]
+    finally:
+        if dx is not None:
+            dx.free()
+
+
 def norm(a: TTvector) -> float:
     """norm(a) — src/tt_operations.jl:465-470."""
     v = dot(a, a).real          # norm = sqrt(max(real(dot(a, a)), 0))
