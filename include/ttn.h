@@ -657,6 +657,12 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * includes. */
 #include "ttn_measure.h"
 
+/* ---- sampling (csrc/ttn_sample_kernels.h) ---------------------------------------------------------------------------
+ * Configurations drawn from p(z) = x(z)^2 / <x, x> (Born) or p(z) = x(z) / sum x (density) with their log-probabilities, per train, by
+ * the conditional sweep over the sites: ttn_tt_sample, ttn_tt_sample_dev, ttn_tt_sample_last_ms.  Declared in ttn_sample.h, which this
+ * header includes. */
+#include "ttn_sample.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,13 @@ MEASURE_SIGNATURES = {
     "ttn_correlation_dev": (C.c_int, [handle, p_f64, p_f64, i64, C.c_void_p]),
 }
 
+# sampling, include/ttn_sample.h (`d_u` is device memory or NULL; the plain form writes host arrays, the _dev form device memory)
+SAMPLE_SIGNATURES = {
+    "ttn_tt_sample": (C.c_int, [handle, i64, i64, i64, C.c_void_p, p_i64, p_f64, p_i64]),
+    "ttn_tt_sample_dev": (C.c_int, [handle, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ttn_tt_sample_last_ms": (C.c_int, [p_f64, p_f64]),
+}
+
 _lib = None
 
 
@@ -237,7 +244,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
     srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
              os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h"),
-             os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h"), os.path.join(INCLUDE, "ttn_measure.h")]
+             os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h"), os.path.join(INCLUDE, "ttn_measure.h"),
+             os.path.join(INCLUDE, "ttn_sample.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -262,7 +270,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
             + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()) + list(OPBATCH_SIGNATURES.items())\
-            + list(MEASURE_SIGNATURES.items()):
+            + list(MEASURE_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -103,6 +103,23 @@ def draw_indices(seed: int, kind: int, a: int, b: int, rows: int, highs) -> np.n
     return idx.reshape((rows, len(highs)), order="F")
 
 
+DRAW_SAMPLE = 6      # the uniforms of tt_sample (include/ttn_sample.h): sub-seed (seed, DRAW_SAMPLE, train, 0)
+
+
+def sample_uniforms(seed: int, batch: int, nsamples: int, d: int) -> np.ndarray:
+    """The (batch, nsamples, d) uniforms in [0, 1) that ``tt_sample`` / ``device.sample`` generate on the device for ``u=None``, bit for
+    bit: entry (b, s, k) is the 53-bit uniform of word 1 + k + d s of the splitmix64 stream of sub-seed (seed, DRAW_SAMPLE, b, 0), so
+    the first S samples of a train do not depend on S."""
+    batch, nsamples, d = int(batch), int(nsamples), int(d)
+    if batch < 1 or nsamples < 1 or d < 1:
+        raise _lib.TTNError(f"sample_uniforms: batch, nsamples and d must be at least 1, got {batch}, {nsamples}, {d}")
+    out = np.empty((batch, nsamples, d), dtype=np.float64)
+    for b in range(batch):
+        words = _splitmix64(nsamples * d, _subseed(seed, DRAW_SAMPLE, b, 0))
+        out[b] = ((words >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)).reshape(nsamples, d)
+    return out
+
+
 def _cap_ranks_(Rs, Is, rmax):
     """_cap_ranks! (:106-115) on 1-based lists (Rs[1..N+1], Is[1..N]; index 0 unused)."""
     N = len(Is) - 1

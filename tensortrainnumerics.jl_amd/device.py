@@ -748,6 +748,84 @@ def correlation_matrix_dev(x: DeviceTT, P, Q=None, normalize: bool = True, out=N
     return out.transpose(1, 2)
 
 
+# ---- sampling (include/ttn_sample.h, csrc/ttn_sample_kernels.h) ----------------------------------------------------------
+SAMPLE_MODES = {"born": _header_define("ttn_sample.h", "TTN_SAMPLE_BORN"), "density": _header_define("ttn_sample.h", "TTN_SAMPLE_DENSITY")}
+
+
+def _sample_args(who: str, nsamples, mode, seed, u, batch: int, d: int):
+    """The argument checks of a sampling call that need no device: (S, mode code, seed as int64, u).  ``u`` stays what it was (a NumPy
+    array is made float64 and contiguous); only its shape (batch, S, d) and its range are examined."""
+    if isinstance(nsamples, bool) or not isinstance(nsamples, (int, np.integer)) or nsamples < 1:
+        raise _lib.TTNError(f"{who}: nsamples must be an integer >= 1, got {nsamples!r}")
+    if not isinstance(mode, str) or mode not in SAMPLE_MODES:
+        raise _lib.TTNError(f"{who}: mode must be 'born' or 'density', got {mode!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise _lib.TTNError(f"{who}: seed must be an integer, got {seed!r}")
+    seed = int(seed) % (1 << 64)
+    seed = seed - (1 << 64) if seed >= (1 << 63) else seed                # the same 64 bits as an int64
+    if u is not None:
+        shape = (batch, int(nsamples), d)
+        if isinstance(u, np.ndarray) or not hasattr(u, "data_ptr"):
+            u = np.ascontiguousarray(np.asarray(u), dtype=np.float64)
+            if u.shape != shape:
+                raise _lib.TTNError(f"{who}: u has shape {u.shape}, expected {shape}")
+            if u.size and not (np.all(u >= 0.0) and np.all(u < 1.0)):
+                raise _lib.TTNError(f"{who}: u must lie in [0, 1)")
+        elif tuple(u.shape) != shape or str(u.dtype) != "torch.float64" or not u.is_cuda or not u.is_contiguous():
+            raise _lib.TTNError(f"{who}: a device u must be a contiguous float64 tensor of shape {shape}, got {tuple(u.shape)} {u.dtype}")
+    return int(nsamples), SAMPLE_MODES[mode], seed, u
+
+
+def sample_dev(x: DeviceTT, nsamples: int, mode: str = "born", seed: int = 0, u=None):
+    """``sample`` into device tensors (idx (B, S, d) int64, logp (B, S) float64, info (B, 2) int64), asynchronously on the library
+    stream: they must not be read on another stream before ``sync()``."""
+    import torch
+    _measure_train("sample", x)
+    S, code, seed, u = _sample_args("sample", nsamples, mode, seed, u, x.batch, x.N)
+    if isinstance(u, np.ndarray):
+        u = torch.from_numpy(u).to("cuda")
+    idx = torch.empty((x.batch, S, x.N), dtype=torch.int64, device="cuda")
+    logp = torch.empty((x.batch, S), dtype=torch.float64, device="cuda")
+    info = torch.empty((x.batch, 2), dtype=torch.int64, device="cuda")
+    if u is not None:
+        torch.cuda.current_stream().synchronize()                         # u was produced on the caller's stream, not the library's
+    _lib.check(_lib.lib().ttn_tt_sample_dev(x.h, code, S, seed, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                            C.c_void_p(idx.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(info.data_ptr())))
+    return idx, logp, info
+
+
+def sample(x: DeviceTT, nsamples: int, mode: str = "born", seed: int = 0, u=None):
+    """``nsamples`` configurations of every train of the batch (ttn_tt_sample), drawn by the conditional sweep over the sites:
+    ``mode="born"`` from p(z) = x(z)^2 / <x, x>, ``mode="density"`` from p(z) = x(z) / sum x for a train that represents a non-negative
+    function.  Returns NumPy arrays: ``idx`` (B, S, d) int64 with 1-based indices, ``logp`` (B, S) with log p(z) of each sample, and
+    ``info`` (B, 2): the weights that were negative and clamped to 0, and the DEAD samples — those that met a total weight of 0 or a
+    non-finite one; their remaining indices are 1 and their logp is -inf (nothing is raised).  ``u`` gives the uniforms, (B, S, d) in
+    [0, 1), as a NumPy array or a float64 device tensor; ``u=None`` generates them on the device from ``seed``, the numbers of
+    ``sample_uniforms(seed, B, S, d)``.  Reproducible to rounding: two calls can differ only in a sample whose draw lies within rounding
+    of a cumulative weight.  Float64 only.  Synchronises."""
+    _measure_train("sample", x)
+    S, code, seed, u = _sample_args("sample", nsamples, mode, seed, u, x.batch, x.N)
+    if isinstance(u, np.ndarray):
+        import torch
+        u = torch.from_numpy(u).to("cuda")
+    if u is not None:
+        import torch
+        torch.cuda.current_stream().synchronize()
+    idx = np.empty((x.batch, S, x.N), dtype=np.int64)
+    logp = np.empty((x.batch, S), dtype=np.float64)
+    info = np.empty((x.batch, 2), dtype=np.int64)
+    _lib.check(_lib.lib().ttn_tt_sample(x.h, code, S, seed, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                        idx.ctypes.data_as(_lib.p_i64), _p_f64(logp), info.ctypes.data_as(_lib.p_i64)))
+    return idx, logp, info
+
+
+def sample_last_ms():
+    """(environment ms, sweep ms) of the last ``sample`` / ``sample_dev`` call on the device (ttn_tt_sample_last_ms); synchronises."""
+    a, b = C.c_double(0.0), C.c_double(0.0)
+    _lib.check(_lib.lib().ttn_tt_sample_last_ms(C.byref(a), C.byref(b)))
+    return float(a.value), float(b.value)
+
+
 def norm(a: DeviceTT) -> np.ndarray:
     out = (C.c_double * a.batch)()
     _lib.check(_lib.lib().ttn_norm(a.h, out))

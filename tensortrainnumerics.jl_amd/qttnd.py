@@ -369,6 +369,25 @@ def qttv_to_array(q: QTTvector, device: bool = False):
         h.free()
 
 
+def qttv_sample(q: QTTvector, nsamples: int, mode: str = "density", seed: int = 0):
+    """``nsamples`` grid points drawn from a QTT vector on the device (``tt.tt_sample``): ``mode="density"`` from q / sum q for a
+    non-negative q (a probability density on the grid), ``mode="born"`` from q^2 / <q, q>.  Returns ``(grid, logp)``: ``grid`` is
+    (S, n_dims) int64, 0-based, with ``qttv_to_array(q)[tuple(grid[s])]`` the value of the train at the sampled bits (the bits are
+    decoded by q's own n_dims / bits_per_dim / ordering), ``logp`` (S,) the log-probability of each point; a dead sample (see
+    ``device.sample``) has logp = -inf."""
+    from .tt import tt_sample
+    if not isinstance(q, QTTvector):
+        raise TypeError(f"qttv_sample: expected a QTTvector, got {type(q).__name__}")
+    idx, logp, _ = tt_sample(q.ttvector(), nsamples, mode=mode, seed=seed)
+    weights = np.array([2 ** (q.bits_per_dim - 1 - site_dim_level(site, q.n_dims, q.bits_per_dim, q.ordering)[1]) for site in range(q.N)], dtype=np.int64)
+    dims = np.array([site_dim_level(site, q.n_dims, q.bits_per_dim, q.ordering)[0] for site in range(q.N)])
+    grid = np.zeros((idx.shape[0], q.n_dims), dtype=np.int64)
+    for dim in range(q.n_dims):
+        sel = dims == dim
+        grid[:, dim] = (idx[:, sel] - 1) @ weights[sel]
+    return grid, logp
+
+
 # ---- N-d Laplacian ----------------------------------------------------------------------------------------------------------------
 def qtt_laplacian(n_dims: int, bits_per_dim: int, ordering: str = "interleaved", a: float = 0.0, b: float = 1.0, bc: str = "DN") -> QTToperator:
     """qtt_laplacian(n_dims, bits_per_dim; ordering, a, b, bc) — src/tt_operators.jl:644-703: the Kronecker sum

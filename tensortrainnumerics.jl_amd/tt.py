@@ -331,6 +331,31 @@ def correlation_matrix(x: TTvector, P, Q=None, normalize: bool = True, connected
             dx.free()
 
 
+def tt_sample(x: TTvector, nsamples: int, mode: str = "born", seed: int = 0, u=None):
+    """``nsamples`` configurations of the train x drawn on the device (``device.sample``): ``mode="born"`` from x(z)^2 / <x, x>,
+    ``mode="density"`` from x(z) / sum x.  Returns ``(idx (S, d) int64, 1-based; logp (S,); info (2,): clamped weights, dead samples)``.
+    ``u``: optional (S, d) uniforms in [0, 1) (a leading axis of length 1 is accepted); without it they come from ``seed``
+    (``sample_uniforms(seed, 1, S, d)[0]``).  Upload, call, free; the argument checks run before the upload.  Float64 only."""
+    from .device import DeviceTT, _sample_args, sample as dev_sample
+    if not isinstance(x, TTvector):
+        raise TypeError(f"tt_sample: expected a TTvector, got {type(x).__name__}")
+    if any(np.iscomplexobj(c) for c in x.ttv_vec):
+        raise _lib.TTNError("tt_sample: Float64 only, a ComplexF64 train is not supported")
+    if u is not None and not hasattr(u, "data_ptr"):
+        u = np.asarray(u)
+        if u.ndim == 2:
+            u = u[None]
+    _sample_args("tt_sample", nsamples, mode, seed, u, 1, x.N)
+    dx = None
+    try:
+        dx = DeviceTT.from_host(x)
+        idx, logp, info = dev_sample(dx, nsamples, mode=mode, seed=seed, u=u)
+        return idx[0], logp[0], info[0]
+    finally:
+        if dx is not None:
+            dx.free()
+
+
 def norm(a: TTvector) -> float:
     """norm(a) — src/tt_operations.jl:465-470."""
     v = dot(a, a).real          # norm = sqrt(max(real(dot(a, a)), 0))
