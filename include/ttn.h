@@ -663,6 +663,11 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * header includes. */
 #include "ttn_sample.h"
 
+/* ---- excited states (csrc/ttn_eig_ortho_kernels.h) ------------------------------------------------------------------
+ * The two-site eigensolvers with a penalty against given trains, the local problem K + sum_j w_j p_j p_j^T: ttn_dmrg_eigsolve_ortho,
+ * ttn_mals_eigsolve_ortho.  Declared in ttn_eig_ortho.h, which this header includes. */
+#include "ttn_eig_ortho.h"
+
 #ifdef __cplusplus
 }
 #endif

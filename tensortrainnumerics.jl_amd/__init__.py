@@ -17,7 +17,7 @@ from .grad import expect_value_and_grad, sandwich_pullback, sandwich_rrule
 from .opalg import (concatenate, kron, operator_strides, outer_product, qtto_to_matrix, tto_add, tto_compress_, tto_decomp, tto_inner, tto_mul,
                     tto_scale, tto_sub, tto_to_tensor, tto_to_ttv, ttv_to_diag_tto, ttv_to_tto)
 from .solvers import (als_eigsolve, als_gen_eigsolv, crank_nicholson_method, dmrg_eigsolve, euler_method, implicit_euler_method, krylov_linsolve,
-                      mals_eigsolve, rk4_method)
+                      lowest_states, mals_eigsolve, rk4_method)
 from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_sample, qttv_to_array
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
 from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, correlation_matrix, div, dot, euclidean_distance,

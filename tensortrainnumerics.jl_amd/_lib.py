@@ -235,6 +235,14 @@ SAMPLE_SIGNATURES = {
     "ttn_tt_sample_last_ms": (C.c_int, [p_f64, p_f64]),
 }
 
+# excited states, include/ttn_eig_ortho.h (`phi` is a host array of handles; weights and ovl are host arrays [batch][n_ortho])
+EIG_ORTHO_SIGNATURES = {
+    "ttn_dmrg_eigsolve_ortho": (C.c_int, [handle, handle, handle, i64, p_handle, p_f64, C.c_double, i64, p_i64, p_i64, C.c_int, i64, C.c_double, i64,
+                                          i64, p_f64, p_i64, p_f64]),
+    "ttn_mals_eigsolve_ortho": (C.c_int, [handle, handle, handle, i64, p_handle, p_f64, C.c_double, i64, p_i64, p_i64, C.c_int, i64, C.c_double, i64,
+                                          i64, p_f64, p_i64, p_f64]),
+}
+
 _lib = None
 
 
@@ -245,7 +253,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
              os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h"),
              os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h"), os.path.join(INCLUDE, "ttn_measure.h"),
-             os.path.join(INCLUDE, "ttn_sample.h")]
+             os.path.join(INCLUDE, "ttn_sample.h"), os.path.join(INCLUDE, "ttn_eig_ortho.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -270,7 +278,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
             + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()) + list(OPBATCH_SIGNATURES.items())\
-            + list(MEASURE_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
+            + list(MEASURE_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(EIG_ORTHO_SIGNATURES.items()):
         fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -14,6 +14,7 @@
 #include "ttn_als_kernels.h"
 #include "ttn_als_grid.h"
 #include "ttn_eigsolve_kernels.h"
+#include "ttn_eig_ortho_kernels.h"
 #include "ttn_als_eig_kernels.h"
 #include "ttn_eig_kernels.h"
 #include "ttn_tdvp_kernels.h"
@@ -120,6 +121,7 @@ DevBuf g_lu_flag;          // singular-pivot word of the grid form of als_linsol
 DevBuf g_cg_iters;         // [batch] CG iterations of the last two-site linear solve
 DevBuf g_hist_E, g_hist_r; // [batch][hist_len] energy / rank history of the last two-site eigensolve
 DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-site eigensolve
+DevBuf g_eig_ortho;        // [3][batch][n_ortho] doubles of the last penalised eigensolve: weights, 1 / ||phi_j||, overlaps
 DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
 DevBuf g_cross_tab;        // core table of ttn_cross_eval
 DevBuf g_cross_info;       // status words of a ttn_cross_maxvol called without a device info
@@ -128,7 +130,7 @@ DevBuf g_grad_coef;        // [2][batch] doubles: Delta of ttn_dot_pullback, alp
 DevBuf g_measure_tab;      // [d] site offsets, then the operator tables of the last ttn_site_expect / ttn_correlation
 DevBuf g_sample_out;       // device outputs of the host form ttn_tt_sample: indices, log-probabilities, info words
 DevBuf* const g_bufs[] = {&g_sample_out, &g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
-                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_als_tab, &g_cross_tab, &g_cross_info, &g_grad_coef, &g_xb_tab, &g_measure_tab};
+                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_eig_ortho, &g_als_tab, &g_cross_tab, &g_cross_info, &g_grad_coef, &g_xb_tab, &g_measure_tab};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -289,6 +291,7 @@ int ttn_init(int device) {
         {(const void*)k_mals_linsolve, COMPRESS_LDS_BYTES},
         {(const void*)k_als_linsolve, COMPRESS_LDS_BYTES},
         {(const void*)k_two_site_eig, COMPRESS_LDS_BYTES},
+        {(const void*)k_two_site_eig_ortho, COMPRESS_LDS_BYTES},
         {(const void*)k_als_eig, COMPRESS_LDS_BYTES},
         {(const void*)k_increase_ranks, COMPRESS_LDS_BYTES},
         {(const void*)k_ttv_decomp, COMPRESS_LDS_BYTES},
@@ -2462,13 +2465,24 @@ int ttn_eigsolve_history_len(int mode, int64_t d, int64_t n_stages, const int64_
     return TTN_OK;
 }
 
+// The penalty of the _ortho entry points (include/ttn_eig_ortho.h): m trains, their host weights [batch][m] and the overlaps out.
+// m == 0 (or a null pointer to this) is the plain solve: k_two_site_eig, launched exactly as before the penalty existed.
+struct EigOrthoHost { int64_t m; const ttn_tt_t* phi; const double* weights; double* ovl; };
+
 static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t n_stages, const int64_t* sweep_schedule,
                              const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
-                             int64_t hist_len, double* E_out, int64_t* r_out) {
-    const char* who = mode == 1 ? "dmrg_eigsolve" : "mals_eigsolve";
+                             int64_t hist_len, double* E_out, int64_t* r_out, const EigOrthoHost* oh = nullptr) {
+    const char* who = oh ? (mode == 1 ? "ttn_dmrg_eigsolve_ortho" : "ttn_mals_eigsolve_ortho") : (mode == 1 ? "dmrg_eigsolve" : "mals_eigsolve");
     auto err = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
     NEED_INIT();
-    F64_ONLY("two-site eigensolver", {x0, x}, {A});
+    if (oh && (oh->m < 0 || oh->m > TTN_EIG_ORTHO_MAX)) return err(TTN_ERR_ARG, "n_ortho outside 0 .. 8");
+    const int m_pen = oh ? (int)oh->m : 0;
+    if (m_pen && (!oh->phi || !oh->weights || !oh->ovl)) return err(TTN_ERR_ARG, "null phi / weights / ovl");
+    for (int j = 0; j < m_pen; ++j) {
+        if (!oh->phi[j]) return err(TTN_ERR_ARG, "null handle among phi");
+        if (oh->phi[j]->el == 2) return refuse_c64(who);
+    }
+    F64_ONLY(oh ? who : "two-site eigensolver", {x0, x}, {A});
     if (!A || !x0 || !x) return err(TTN_ERR_ARG, "null handle");
     if (!rmax_schedule || !E_out || !r_out) return err(TTN_ERR_ARG, "null schedule / history buffer");
     if (!same_dims(A->dims, x0->dims) || !same_dims(x0->dims, x->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
@@ -2481,6 +2495,15 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     int rc = sweep_plan(who, TTN_ERR_ARG, n_stages, sweep_schedule, rmax_schedule, plan);
     if (rc) return rc;
     if (hist_len != eig_hist_len(mode, d, (int64_t)plan.size())) return err(TTN_ERR_ARG, "hist_len differs from ttn_eigsolve_history_len");
+    const int batch = x->batch;
+    for (int j = 0; j < m_pen; ++j) {
+        const ttn_tt_s* ph = oh->phi[j];
+        if (ph == x || ph == x0) return err(TTN_ERR_ARG, "a phi[j] is x or x0");
+        if (!same_dims(ph->dims, x->dims)) return err(TTN_ERR_DIMS, "a phi[j] has other dims than x");
+        if (ph->batch != batch && ph->batch != 1) return err(TTN_ERR_ARG, "the batch of a phi[j] is neither that of x nor 1");
+    }
+    for (int64_t k = 0; k < (int64_t)m_pen * batch; ++k)
+        if (!std::isfinite(oh->weights[k]) || !(oh->weights[k] > 0.0)) return err(TTN_ERR_ARG, "a weight is not finite or not > 0");
     // ---- every size check before anything is launched ----
     const std::vector<int64_t>& c = x->cap;
     for (int k = 0; k <= d; ++k) if (c[k] < x0->bound[k]) return fail(TTN_ERR_CAPACITY, "rank capacity of the result handle is below the start ranks");
@@ -2510,13 +2533,51 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     P.offQb = cur; cur += mmax * cmax;
     P.offRb = cur; cur += cmax * cmax;
     P.offTst = cur; cur += ((cmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64;
-    const int batch = x->batch;
+    EigOrthoArgs Og;
+    memset(&Og, 0, sizeof(Og));
+    if (m_pen) {                                            // the overlap chains, the projected vectors and their intermediates
+        Og.m = m_pen;
+        Og.nmax = Nmax;
+        Og.offChain = cur;
+        long long qmax = 1;
+        for (int j = 0; j < m_pen; ++j) {
+            long long q = 1;
+            for (int k = 0; k <= d; ++k) q = std::max<long long>(q, oh->phi[j]->bound[k]);
+            qmax = std::max(qmax, q);
+            Og.slot[j] = cmax * q;
+            Og.chain0[j] = cur - Og.offChain;
+            cur += 2 * (d + 1) * Og.slot[j];
+        }
+        Og.offP = cur; cur += (long long)m_pen * Nmax;
+        Og.offU = cur; cur += mmax * qmax;
+        Og.offW = cur; cur += mmax * qmax;
+        Og.offC = cur; cur += 8;
+    }
     {
         const size_t need = two_site_bytes(L, batch);
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
         if (need > g_scratch.bytes && need - g_scratch.bytes > free_b)
-            return err(TTN_ERR_CAPACITY, "the workspace of this capacity and batch (G / H slots, dense K, Lanczos basis) does not fit in device memory");
+            return err(TTN_ERR_CAPACITY, "the workspace of this capacity and batch (G / H slots, dense K, Lanczos basis, overlap chains) does not fit in device memory");
+    }
+    if (m_pen) {                                            // ||phi_j|| once per call (k_dot), the last check; then the device tables
+        std::vector<double> tab((size_t)2 * batch * m_pen), nn;
+        for (int j = 0; j < m_pen; ++j) {
+            const ttn_tt_t ph = oh->phi[j];
+            nn.assign((size_t)ph->batch, 0.0);
+            if ((rc = ttn_dot(ph, ph, nn.data()))) return rc;
+            for (int t = 0; t < ph->batch; ++t)
+                if (!std::isfinite(nn[t]) || !(nn[t] > 0.0)) return err(TTN_ERR_ARG, "the norm of a phi[j] is zero or not finite");
+            for (int t = 0; t < batch; ++t) tab[(size_t)batch * m_pen + (size_t)t * m_pen + j] = 1.0 / std::sqrt(nn[ph->batch == 1 ? 0 : t]);
+        }
+        for (size_t k = 0; k < (size_t)batch * m_pen; ++k) tab[k] = oh->weights[k];
+        if ((rc = g_eig_ortho.ensure(sizeof(double) * 3 * batch * m_pen))) return rc;
+        HIPCHK(hipMemcpyAsync(g_eig_ortho.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));            // tab is local
+        Og.weight = g_eig_ortho.as<double>();
+        Og.inv_norm = Og.weight + (size_t)batch * m_pen;
+        Og.ovl = g_eig_ortho.as<double>() + (size_t)2 * batch * m_pen;
+        for (int j = 0; j < m_pen; ++j) Og.phi[j] = oh->phi[j]->dev();
     }
     rc = ttn_orthogonalize(x0, 1, x);                       // dmrg.jl:522, mals.jl:355
     if (rc) return rc;
@@ -2534,8 +2595,10 @@ static int two_site_eigsolve(int mode, ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, dou
     Rg.lz_maxrestart = (int)std::min<int64_t>(maxiter, 1 << 30);
     Rg.lz_tol = linsolv_tol;
     Rg.lz_iters = g_lz_iters.as<int>(); Rg.lz_res = g_lz_res.as<double>();
-    hipLaunchKernelGGL(k_two_site_eig, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Rg);
+    if (m_pen) hipLaunchKernelGGL(k_two_site_eig_ortho, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Rg, Og);
+    else hipLaunchKernelGGL(k_two_site_eig, dim3(batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, Rg);
     HIPCHK(hipGetLastError());
+    if (m_pen) HIPCHK(hipMemcpyAsync(oh->ovl, Og.ovl, sizeof(double) * batch * m_pen, hipMemcpyDeviceToHost, g_stream));
     g_lz_iters_host.assign(batch, 0);
     g_lz_res_host.assign(batch, 0.0);
     std::vector<long long> hr(hn);
@@ -2563,6 +2626,24 @@ int ttn_mals_eigsolve(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t 
                       int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh, int64_t hist_len, double* E, int64_t* r_hist) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     return two_site_eigsolve(0, A, x0, x, tol, n_stages, sweep_schedule, rmax_schedule, it_solver, maxiter, linsolv_tol, itslv_thresh, hist_len, E, r_hist);
+}
+
+int ttn_dmrg_eigsolve_ortho(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, int64_t n_ortho, const ttn_tt_t* phi, const double* weights, double tol, int64_t n_stages,
+                            const int64_t* sweep_schedule, const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                            int64_t hist_len, double* E, int64_t* r_hist, double* ovl) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_dmrg_eigsolve_ortho")) return rb;
+    const EigOrthoHost oh{n_ortho, phi, weights, ovl};
+    return two_site_eigsolve(1, A, x0, x, tol, n_stages, sweep_schedule, rmax_schedule, it_solver, maxiter, linsolv_tol, itslv_thresh, hist_len, E, r_hist, &oh);
+}
+
+int ttn_mals_eigsolve_ortho(ttn_tto_t A, ttn_tt_t x0, ttn_tt_t x, int64_t n_ortho, const ttn_tt_t* phi, const double* weights, double tol, int64_t n_stages,
+                            const int64_t* sweep_schedule, const int64_t* rmax_schedule, int it_solver, int64_t maxiter, double linsolv_tol, int64_t itslv_thresh,
+                            int64_t hist_len, double* E, int64_t* r_hist, double* ovl) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int rb = single_op(A, "ttn_mals_eigsolve_ortho")) return rb;
+    const EigOrthoHost oh{n_ortho, phi, weights, ovl};
+    return two_site_eigsolve(0, A, x0, x, tol, n_stages, sweep_schedule, rmax_schedule, it_solver, maxiter, linsolv_tol, itslv_thresh, hist_len, E, r_hist, &oh);
 }
 
 int ttn_eigsolve_stats(int64_t batch, int64_t* lanczos_applies, double* lanczos_residual) {

@@ -206,7 +206,7 @@ def euler_method(A, u0, steps: Sequence[float], normalize: bool = True, return_e
 # ----------------------------------------------------------------------------------------------------------------------
 import numpy as np
 
-from .tt import TToperator
+from .tt import TToperator, TTvector
 
 
 def _tto_scale(a: float, A: TToperator) -> TToperator:
@@ -732,41 +732,113 @@ def eigsolve_history_len(mode: int, d: int, sweep_schedule: Sequence[int]) -> in
     return int(out.value)
 
 
+EIG_ORTHO_MAX = 8          # TTN_EIG_ORTHO_MAX of include/ttn_eig_ortho.h
+
+
+def _ortho_list(who, ortho_to, kind):
+    """ortho_to as a list: one train or a sequence of them, all of type `kind`."""
+    states = [ortho_to] if isinstance(ortho_to, kind) else list(ortho_to)
+    if any(not isinstance(p, kind) for p in states):
+        raise TypeError(f"{who}: ortho_to must be a {kind.__name__} or a sequence of them")
+    if len(states) > EIG_ORTHO_MAX:
+        raise _lib.TTNError(f"{who}: at most {EIG_ORTHO_MAX} states in ortho_to")
+    return states
+
+
+def _ortho_weights(who, weight, batch: int, m: int) -> np.ndarray:
+    """The (batch, m) weight table of a penalised solve from a scalar, one value per state, or a (batch, m) array.  Needs no device."""
+    if m == 0:                      # an empty ortho_to: the plain solve through the penalised entry point
+        return np.zeros((batch, 1))
+    if weight is None:
+        raise _lib.TTNError(f"{who}: ortho_to needs weight (the penalty must exceed the gap to the wanted level)")
+    try:
+        w = np.asarray(weight, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise _lib.TTNError(f"{who}: weight must be a number, one number per state, or a (batch, states) array") from None
+    if w.ndim == 0 or w.shape == (m,) or w.shape == (batch, m):
+        w = np.ascontiguousarray(np.broadcast_to(w, (batch, m)))
+    else:
+        raise _lib.TTNError(f"{who}: weight of shape {w.shape} fits neither ({m},) nor ({batch}, {m})")
+    if not np.all(np.isfinite(w)) or not np.all(w > 0.0):
+        raise _lib.TTNError(f"{who}: every weight must be finite and > 0")
+    return w
+
+
 def _two_site_eigsolve_(mode, A: DeviceTTO, x0: DeviceTT, x: DeviceTT, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter,
-                        linsolv_tol, itslv_thresh):
+                        linsolv_tol, itslv_thresh, ortho_to=None, weight=None):
     who = "dmrg_eigsolve" if mode == 1 else "mals_eigsolve"
+    if ortho_to is None and weight is not None:
+        raise _lib.TTNError(f"{who}: weight without ortho_to")
     ss, rs = _eig_schedules(who, sweep_schedule, rmax_schedule)
     if linsolv_tol is None:
         linsolv_tol = max(math.sqrt(tol), 1.0e-8)                              # dmrg.jl:510, mals.jl:340
-    hl = eigsolve_history_len(mode, len(x0.dims), ss)
     B = x0.batch
+    if ortho_to is not None:
+        states = _ortho_list(who, ortho_to, DeviceTT)
+        w = _ortho_weights(who, weight, B, len(states))
+    hl = eigsolve_history_len(mode, len(x0.dims), ss)
     E = np.zeros((B, max(hl, 1)))
     R = np.zeros((B, max(hl, 1)), dtype=np.int64)
     arr = C.c_int64 * len(ss)
-    fn = _lib.lib().ttn_dmrg_eigsolve if mode == 1 else _lib.lib().ttn_mals_eigsolve
-    _lib.check(fn(A.h, x0.h, x.h, float(tol), len(ss), arr(*ss), arr(*rs), 1 if it_solver else 0, int(linsolv_maxiter), float(linsolv_tol),
-                  int(itslv_thresh), hl, E.ctypes.data_as(_lib.p_f64), R.ctypes.data_as(_lib.p_i64)))
-    return [list(map(float, E[b, :hl])) for b in range(B)], [list(map(int, R[b, :hl])) for b in range(B)]
+    tail = (float(tol), len(ss), arr(*ss), arr(*rs), 1 if it_solver else 0, int(linsolv_maxiter), float(linsolv_tol), int(itslv_thresh), hl,
+            E.ctypes.data_as(_lib.p_f64), R.ctypes.data_as(_lib.p_i64))
+    hist = lambda: ([list(map(float, E[b, :hl])) for b in range(B)], [list(map(int, R[b, :hl])) for b in range(B)])
+    if ortho_to is None:
+        fn = _lib.lib().ttn_dmrg_eigsolve if mode == 1 else _lib.lib().ttn_mals_eigsolve
+        _lib.check(fn(A.h, x0.h, x.h, *tail))
+        return hist()
+    m = len(states)
+    if getattr(A, "batch", 1) > 1:
+        # The penalised entry points take one operator (every entry point outside ttn_opbatch.h's list refuses a batch): an operator
+        # batch is solved one operator at a time, train b with A.select(b) on single-train copies, bit for bit the single calls.
+        if A.batch != B:
+            raise _lib.TTNError(f"{who}: batch sizes differ (the operator batch and the trains)")
+        Es, Rs, ovl = [], [], np.zeros((B, m))
+        for b in range(B):
+            Ab, s0, s = A.select(b), DeviceTT.from_host(x0.download(b)), DeviceTT(x.dims, x.cap)
+            sp = [p if p.batch == 1 else DeviceTT.from_host(p.download(b)) for p in states]
+            e, r, o = _two_site_eigsolve_(mode, Ab, s0, s, tol, ss, rs, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh, sp,
+                                          w[b:b + 1, :m] if m else None)
+            s.max_ranks()
+            x.upload(b, s.download(0))
+            Es.append(e[0]); Rs.append(r[0]); ovl[b] = o[0]
+            for h in [Ab, s0, s] + [p for p, q in zip(sp, states) if p is not q]:
+                h.free()
+        return Es, Rs, ovl
+    ovl = np.zeros((B, max(m, 1)))
+    phi = (C.c_void_p * max(m, 1))(*[p.h for p in states])
+    fn = _lib.lib().ttn_dmrg_eigsolve_ortho if mode == 1 else _lib.lib().ttn_mals_eigsolve_ortho
+    _lib.check(fn(A.h, x0.h, x.h, m, phi, w.ctypes.data_as(_lib.p_f64), *tail, ovl.ctypes.data_as(_lib.p_f64)))
+    return hist() + (ovl[:, :m].copy(),)
 
 
 def dmrg_eigsolve_(A: DeviceTTO, x0: DeviceTT, x: DeviceTT, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
                    rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
-                   linsolv_tol: float | None = None, itslv_thresh: int = 256):
+                   linsolv_tol: float | None = None, itslv_thresh: int = 256, *, ortho_to=None, weight=None):
     """(E_b, r_hist_b) of dmrg_eigsolve(A, x0_b; N = 2, ...) for every train of the batch; x receives the eigenvectors (its capacity
-    bounds the adapted ranks).  Returns (E, r_hist): per-train lists."""
+    bounds the adapted ranks).  Returns (E, r_hist): per-train lists.
+
+    ortho_to (a DeviceTT or a sequence of up to 8; batch that of x0, or 1 = shared) with weight (a scalar, one value per state, or a
+    (batch, states) array; required) solves A + sum_j weight_j |phi_j><phi_j| / <phi_j, phi_j> instead (csrc/ttn_eig_ortho_kernels.h):
+    with the phi_j the levels below and the weights above the gap, the next level.  Returns (E, r_hist, overlaps) then: E holds the
+    local eigenvalues of the PENALISED problem (take the energy with device.rayleigh), overlaps (batch, states) the
+    <phi_j, x> / ||phi_j|| of the result.  With ortho_to an operator batch is solved one operator at a time (A.select(b) on copies of
+    train b, one launch per train: the C entry point takes one operator); eigsolve_stats then holds the last train's figures only."""
     if rmax_schedule is None:
         rmax_schedule = (math.isqrt(math.prod(x0.dims)),)                     # dmrg.jl:507
-    return _two_site_eigsolve_(1, A, x0, x, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+    return _two_site_eigsolve_(1, A, x0, x, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh,
+                               ortho_to, weight)
 
 
 def mals_eigsolve_(A: DeviceTTO, x0: DeviceTT, x: DeviceTT, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
                    rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
-                   linsolv_tol: float | None = None, itslv_thresh: int = 256):
+                   linsolv_tol: float | None = None, itslv_thresh: int = 256, *, ortho_to=None, weight=None):
     """(E_b, r_hist_b) of mals_eigsolve(A, x0_b; ...) for every train of the batch.  itslv_thresh is accepted and, as in the reference
-    (mals.jl:383-390, :403-410), not used: the local threshold is 256."""
+    (mals.jl:383-390, :403-410), not used: the local threshold is 256.  ortho_to / weight as in dmrg_eigsolve_."""
     if rmax_schedule is None:
         rmax_schedule = (int(round(math.sqrt(math.prod(x0.dims)))),)          # mals.jl:338
-    return _two_site_eigsolve_(0, A, x0, x, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+    return _two_site_eigsolve_(0, A, x0, x, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh,
+                               ortho_to, weight)
 
 
 def eigsolve_stats(batch: int):
@@ -778,39 +850,119 @@ def eigsolve_stats(batch: int):
 
 
 def _eig_host(mode, A: TToperator, tt_start: TTvector, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol,
-              itslv_thresh):
+              itslv_thresh, ortho_to=None, weight=None):
     who = "dmrg_eigsolve" if mode == 1 else "mals_eigsolve"
     dims = tuple(tt_start.ttv_dims)
     if rmax_schedule is None:
         rmax_schedule = (math.isqrt(math.prod(dims)),) if mode == 1 else (int(round(math.sqrt(math.prod(dims)))),)
     ss, rs = _eig_schedules(who, sweep_schedule, rmax_schedule)       # refusals before anything reaches the device
+    if ortho_to is None and weight is not None:
+        raise _lib.TTNError(f"{who}: weight without ortho_to")
+    if ortho_to is not None:
+        states = _ortho_list(who, ortho_to, TTvector)
+        weight = _ortho_weights(who, weight, 1, len(states))
     rtop = max(rs)
     cap = dmrg_capacity(dims, tt_start.ttv_rks, rtop)                  # n_i * rank <= 256 (TTNError for start ranks beyond it)
     dA = DeviceTTO(A)
     dx0 = DeviceTT.from_host(tt_start)
     dx = DeviceTT(dims, cap)
     fn = dmrg_eigsolve_ if mode == 1 else mals_eigsolve_
-    E, R = fn(dA, dx0, dx, tol, ss, rs, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+    if ortho_to is None:
+        E, R = fn(dA, dx0, dx, tol, ss, rs, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+    else:
+        dphi = [DeviceTT.from_host(p) for p in states]
+        try:
+            E, R, _ = fn(dA, dx0, dx, tol, ss, rs, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh, ortho_to=dphi,
+                         weight=weight if states else None)
+        finally:
+            for h in dphi:
+                h.free()
     dx.max_ranks()
     return E[0], dx.download(0), R[0]
 
 
 def dmrg_eigsolve(A: TToperator, tt_start: TTvector, N: int = 2, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
                   rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
-                  linsolv_tol: float | None = None, itslv_thresh: int = 256):
+                  linsolv_tol: float | None = None, itslv_thresh: int = 256, *, ortho_to=None, weight=None):
     """(E, x, r_hist) = dmrg_eigsolve(A, tt_start; N = 2, ...) (src/solvers/dmrg.jl:501-578) with the reference's keywords and defaults:
     E the eigenvalue of every micro-step, x the normalised eigenvector train, r_hist max(ttv_rks) after every micro-step.  The rank
-    capacity is the reference's buffer bound clamped to n_i * rank <= 256 (dmrg_capacity)."""
+    capacity is the reference's buffer bound clamped to n_i * rank <= 256 (dmrg_capacity).  ortho_to (a TTvector or a sequence of them)
+    with weight (a scalar or one value per state): the penalised solve of dmrg_eigsolve_, E then the penalised local eigenvalues."""
     if N != 2:
         raise _lib.TTNError("dmrg_eigsolve: only the two-site scheme N = 2 is offered")
-    return _eig_host(1, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+    return _eig_host(1, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh, ortho_to, weight)
 
 
 def mals_eigsolve(A: TToperator, tt_start: TTvector, tol: float = 1.0e-12, sweep_schedule: Sequence[int] = (2,),
                   rmax_schedule: Sequence[int] | None = None, it_solver: bool = False, linsolv_maxiter: int = 200,
-                  linsolv_tol: float | None = None, itslv_thresh: int = 256):
-    """(E, x, r_hist) = mals_eigsolve(A, tt_start; ...) (src/solvers/mals.jl:335-425); rmax_schedule defaults to round(sqrt(prod(dims)))."""
-    return _eig_host(0, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh)
+                  linsolv_tol: float | None = None, itslv_thresh: int = 256, *, ortho_to=None, weight=None):
+    """(E, x, r_hist) = mals_eigsolve(A, tt_start; ...) (src/solvers/mals.jl:335-425); rmax_schedule defaults to round(sqrt(prod(dims))).
+    ortho_to / weight as in dmrg_eigsolve."""
+    return _eig_host(0, A, tt_start, tol, sweep_schedule, rmax_schedule, it_solver, linsolv_maxiter, linsolv_tol, itslv_thresh, ortho_to, weight)
+
+
+def _level_weights(who, weight, j: int, batch: int):
+    """The weights of level j (against levels 0 .. j-1) from lowest_states' weight: a scalar, one value per state, or (batch, states)."""
+    w = np.asarray(weight, dtype=np.float64)
+    if w.ndim == 0:
+        return float(w)
+    if (w.ndim == 1 and w.shape[0] >= j) or (w.ndim == 2 and w.shape[0] == batch and w.shape[1] >= j):
+        return w[..., :j]
+    raise _lib.TTNError(f"{who}: weight of shape {w.shape} does not cover {j} states")
+
+
+def lowest_states_(A: DeviceTTO, x0s, k: int, weight, mode: str = "dmrg", **kw):
+    """The k lowest eigenpairs of A for every train of a batch, one level after the other: level j is the penalised solve
+    (dmrg_eigsolve_ / mals_eigsolve_ with ortho_to) against the results of levels 0 .. j-1.  x0s: one DeviceTT batch of start trains
+    per level, or one batch used for every level.  weight: a scalar, one value per state, or a (batch, states) array, above the
+    distance from level 0 to level k-1.  mode "dmrg" or "mals"; kw: the keywords of the solver.
+    Returns (xs, E, S): the k result handles, the (batch, k) energies device.rayleigh(A, xs[j]) and the (batch, k, k) overlaps
+    device.dot(xs[i], xs[j])."""
+    if mode not in ("dmrg", "mals"):
+        raise _lib.TTNError(f"lowest_states: mode must be 'dmrg' or 'mals', got {mode!r}")
+    k = int(k)
+    if not 1 <= k <= EIG_ORTHO_MAX + 1:
+        raise _lib.TTNError(f"lowest_states: k must lie in 1 .. {EIG_ORTHO_MAX + 1}")
+    starts = [x0s] * k if isinstance(x0s, DeviceTT) else list(x0s)
+    if len(starts) != k or any(not isinstance(s, DeviceTT) for s in starts):
+        raise _lib.TTNError("lowest_states: x0s must be one DeviceTT batch or one per level")
+    B = starts[0].batch
+    for j in range(1, k):
+        _level_weights("lowest_states", weight, j, B)                  # refusals before the first solve
+    dims = starts[0].dims
+    rs = kw.get("rmax_schedule")
+    if rs is None:
+        rs = kw["rmax_schedule"] = (math.isqrt(math.prod(dims)),) if mode == "dmrg" else (int(round(math.sqrt(math.prod(dims)))),)
+    fn = dmrg_eigsolve_ if mode == "dmrg" else mals_eigsolve_
+    xs = []
+    for j in range(k):
+        x = DeviceTT(dims, dmrg_capacity(dims, starts[j].max_ranks(), max(int(v) for v in rs)), B)
+        if j == 0:
+            fn(A, starts[j], x, **kw)
+        else:
+            fn(A, starts[j], x, ortho_to=xs, weight=_level_weights("lowest_states", weight, j, B), **kw)
+        xs.append(x)
+    E = np.stack([D.rayleigh(A, x) for x in xs], axis=1)
+    S = np.empty((B, k, k))
+    for i in range(k):
+        for j in range(i, k):
+            S[:, i, j] = S[:, j, i] = D.dot(xs[i], xs[j])
+    return xs, E, S
+
+
+def lowest_states(A: TToperator, x0s, k: int, weight, mode: str = "dmrg", **kw):
+    """Host form of lowest_states_ for one operator: x0s a TTvector (used for every level) or one per level.  Returns (E, xs, S): the k
+    energies (Rayleigh quotients of the results), the k TTvectors and their k x k overlap matrix."""
+    starts = [x0s] * int(k) if isinstance(x0s, TTvector) else list(x0s)
+    if any(not isinstance(s, TTvector) for s in starts):
+        raise TypeError("lowest_states: x0s must be a TTvector or a sequence of them")
+    if kw.get("N", 2) != 2:
+        raise _lib.TTNError("lowest_states: only the two-site scheme N = 2 is offered")
+    kw.pop("N", None)
+    xs, E, S = lowest_states_(DeviceTTO(A), [DeviceTT.from_host(s) for s in starts], k, weight, mode, **kw)
+    for x in xs:
+        x.max_ranks()
+    return E[0], [x.download(0) for x in xs], S[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
