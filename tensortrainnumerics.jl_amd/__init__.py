@@ -2,7 +2,8 @@
 
 Host-side mirror of the reference interface (tt.py), input generators (constructors.py),
 device-resident batched handles (device.py), core gradients (grad.py), TT operator algebra (opalg.py), the multi-dimensional QTT layer (qttnd.py) and the ctypes binding of the C ABI (_lib.py).
-The arithmetic lives in csrc/*.h, csrc/ttn_api.hip -> libttn_hip.so (hand-written HIP, gfx950).
+The arithmetic lives in csrc/*.h (the kernels, and the host API in csrc/ttn_host_*.h), built through csrc/ttn_api.hip and
+csrc/ttn_wg512.hip -> libttn_hip.so (hand-written HIP, gfx950).
 """
 from . import _lib, constructors, cross, device, grad, opalg, pipeline, qtt, qttnd, shard, solvers, tdvp, tt
 from ._lib import TTNError, build, ensure_init, finalize

@@ -247,13 +247,10 @@ _lib = None
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/ttn_api.hip for gfx950 into libttn_hip.so (in-tree).  hipcc cross-compiles
-    without a GPU."""
+    """Compile csrc/ttn_api.hip (the host API of csrc/ttn_host_*.h on the kernel headers) and csrc/ttn_wg512.hip for gfx950 into
+    libttn_hip.so (in-tree).  hipcc cross-compiles without a GPU."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
-    srcs += [os.path.join(INCLUDE, "ttn.h"), os.path.join(INCLUDE, "ttn_rect.h"), os.path.join(INCLUDE, "ttn_dense.h"), os.path.join(INCLUDE, "ttn_step.h"),
-             os.path.join(INCLUDE, "ttn_cross_batch.h"), os.path.join(INCLUDE, "ttn_expect.h"),
-             os.path.join(INCLUDE, "ttn_expect_grad.h"), os.path.join(INCLUDE, "ttn_opbatch.h"), os.path.join(INCLUDE, "ttn_measure.h"),
-             os.path.join(INCLUDE, "ttn_sample.h"), os.path.join(INCLUDE, "ttn_eig_ortho.h")]
+    srcs += [os.path.join(INCLUDE, f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(s) for s in srcs)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -276,12 +273,12 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RECT_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items())\
-            + list(CROSS_BATCH_SIGNATURES.items()) + list(EXPECT_SIGNATURES.items()) + list(EXPECT_GRAD_SIGNATURES.items()) + list(OPBATCH_SIGNATURES.items())\
-            + list(MEASURE_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(EIG_ORTHO_SIGNATURES.items()):
-        fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, RECT_SIGNATURES, DENSE_SIGNATURES, STEP_SIGNATURES, CROSS_BATCH_SIGNATURES, EXPECT_SIGNATURES, EXPECT_GRAD_SIGNATURES,
+                  OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
+            fn.restype = res
+            fn.argtypes = args
     _lib = L
     return L
 

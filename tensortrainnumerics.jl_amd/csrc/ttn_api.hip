@@ -1,4 +1,10 @@
 // ttn_api.hip — the C ABI of include/ttn.h on top of the HIP kernels (gfx950).
+// The host code is being cut into csrc/ttn_host_*.h, one header per feature (ttn_host_core.h describes the layering); what is not
+// cut yet stands below, in the order it always had, and ttn_init / ttn_finalize stand last because they see every module's state.
+// There is no block of globals: state that one feature alone uses is declared with that feature, here as in the host headers.
+//
+// The kernel headers.  Their order here is the order of the kernels in the code object: do not "tidy" it (sort it, or drop an
+// include because a host header pulls it in) — the device code would no longer be byte-identical to the build before.
 #include "../../include/ttn.h"
 #include "ttn_common.h"
 #include "ttn_stream_kernels.h"
@@ -33,15 +39,13 @@
 #include "ttn_measure_kernels.h"
 #include "ttn_sample_kernels.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <cstdlib>
-#include <mutex>
-#include <set>
-#include <string>
-#include <vector>
+// The host headers: the dynamic-LDS table first (it fixes the order of the kernel templates' instantiations, see there), then the
+// layers, lowest first.
+#include "ttn_host_lds.h"
+#include "ttn_host_core.h"
+#include "ttn_host_dot.h"
+#include "ttn_host_measure.h"
+#include "ttn_host_sample.h"
 
 // the 512-thread build of k_compress and its building blocks (ttn_wg512.hip: two workgroups per CU)
 extern "C" {
@@ -56,353 +60,7 @@ int ttn_wg512_selftest_gemm_ra2(int m1, int n1, int k1, double* A1, double* B1, 
                                 int m2, int n2, int k2, double* A2, double* B2, double* C2, double alpha2, int f2, int pair, hipStream_t stream);
 }
 
-// ------------------------------------------------------------------------------------------------
-// global state
-// ------------------------------------------------------------------------------------------------
-namespace {
-std::set<struct ttn_tt_s*> g_live;  // every live ttn_tt handle (ttn_status_all walks them)
-std::recursive_mutex g_mu;
-bool g_init = false;
-int g_device = -1;
-hipStream_t g_stream = nullptr;
-hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;                 // ttn_timer_begin / ttn_timer_end
-hipEvent_t g_launch_ev0 = nullptr, g_launch_ev1 = nullptr;   // the kernels of the last ttn_dot / ttn_orthogonalize (ttn_last_launch_ms)
-bool g_have_launch_ms = false;
-size_t g_ortho_state_off = 0;     // byte offset in g_scratch of the state words of the last ttn_orthogonalize (ttn_debug_ortho_state)
-int g_ortho_state_batch = 0;      // its batch; 0: none
-long long g_dense_plan[3] = {-1, 0, 0};   // cut m, TM, TN of the last ttn_tt_to_dense / ttn_tto_to_dense (ttn_debug_dense_plan); m < 0: none
-long long g_gather_plan[4] = {0, 0, 0, 0};   // TI, TO, ld, RO of the gather of the last ttn_tto_decomp_dev (ttn_debug_gather_plan); TI == 0: none
-std::string g_err = "";
-std::vector<hipEvent_t> g_slots;   // ttn_event_record slots
-std::vector<long long> g_xb_tab_host;   // ttn_cross_batch_eval: the host copy of the core table, kept until its upload has completed
-hipEvent_t g_xb_tab_ev = nullptr;       // recorded after that upload; waited for before the host copy is written again
-std::vector<double> g_measure_host;     // ttn_site_expect / ttn_correlation: the host copy of the site offsets and the operator tables, kept likewise
-hipEvent_t g_measure_ev = nullptr;
-std::vector<hipEvent_t> g_sample_ev;    // ttn_tt_sample, three per chunk of trains: before the environments, between the phases, after the sweeps
-int g_sample_chunks = 0;                // chunks of the last call (0: none has run)
-
-int fail(int code, const char* what) {
-    g_err = what;
-    return code;
-}
-int hipfail(hipError_t e, const char* where) {
-    g_err = std::string(where) + ": " + hipGetErrorString(e);
-    return (int)e > 0 ? (int)e : 999;
-}
-#define HIPCHK(call)                                  \
-    do {                                              \
-        hipError_t e_ = (call);                       \
-        if (e_ != hipSuccess) return hipfail(e_, #call); \
-    } while (0)
-#define NEED_INIT() \
-    if (!g_init) return fail(TTN_ERR_NOT_INIT, "ttn_init has not been called")
-
-// Device memory the library keeps between calls.  ensure() grows it to exactly `n` bytes (after the stream has drained: a launch
-// in flight may still read the old allocation) and keeps it when it is already large enough; ttn_finalize releases every one.
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t n) {
-        if (n <= bytes) return TTN_OK;
-        if (p) { HIPCHK(hipStreamSynchronize(g_stream)); HIPCHK(hipFree(p)); p = nullptr; bytes = 0; }
-        HIPCHK(hipMalloc(&p, n));
-        bytes = n;
-        return TTN_OK;
-    }
-    void release() { if (p) hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-DevBuf g_scratch;          // per-call workspace of every launch
-DevBuf g_dout;             // [batch] doubles: dot results, the factors of ttn_scale_batch
-DevBuf g_next_train;       // train counter of the persistent k_compress grid
-DevBuf g_pending_status;   // one bit per failure code of handles FREED before anybody queried them (ttn_status_all)
-DevBuf g_which;            // [batch] scaled core per train when the gauge flags differ (scaled_core)
-DevBuf g_lu_flag;          // singular-pivot word of the grid form of als_linsolve
-DevBuf g_cg_iters;         // [batch] CG iterations of the last two-site linear solve
-DevBuf g_hist_E, g_hist_r; // [batch][hist_len] energy / rank history of the last two-site eigensolve
-DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-site eigensolve
-DevBuf g_eig_ortho;        // [3][batch][n_ortho] doubles of the last penalised eigensolve: weights, 1 / ||phi_j||, overlaps
-DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
-DevBuf g_cross_tab;        // core table of ttn_cross_eval
-DevBuf g_cross_info;       // status words of a ttn_cross_maxvol called without a device info
-DevBuf g_xb_tab;           // core table of ttn_cross_batch_eval
-DevBuf g_grad_coef;        // [2][batch] doubles: Delta of ttn_dot_pullback, alpha and beta of ttn_tt_cores_axpby
-DevBuf g_measure_tab;      // [d] site offsets, then the operator tables of the last ttn_site_expect / ttn_correlation
-DevBuf g_sample_out;       // device outputs of the host form ttn_tt_sample: indices, log-probabilities, info words
-DevBuf* const g_bufs[] = {&g_sample_out, &g_scratch, &g_dout, &g_next_train, &g_pending_status, &g_which, &g_lu_flag, &g_cg_iters,
-                          &g_hist_E, &g_hist_r, &g_lz_iters, &g_lz_res, &g_eig_ortho, &g_als_tab, &g_cross_tab, &g_cross_info, &g_grad_coef, &g_xb_tab, &g_measure_tab};
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------
-// handles
-// ------------------------------------------------------------------------------------------------
-struct ttn_tt_s {
-    int d = 0, batch = 0;
-    int el = 1;                               // doubles per element: 1 Float64, 2 ComplexF64 (interleaved; d_dims then holds 2 n_k, see ttn_cplx_kernels.h)
-    std::vector<int64_t> dims, cap, bound;   // bound[m]: host upper bound on the current rank of any train
-    std::vector<long long> off;               // d+1 slot offsets
-    long long stride = 0;
-    double* d_data = nullptr;
-    long long* d_off = nullptr;
-    long long* d_rks = nullptr;
-    long long* d_cap = nullptr;
-    int* d_dims = nullptr;
-    std::vector<int64_t> ot;                  // [batch][d] host-side gauge flags (never data dependent)
-    int* d_status = nullptr;                  // [2][batch]: failure codes of the dense kernels that wrote THIS handle — sticky (kernels only
-                                              // store non-zero codes, ttn_compress_status reads and clears) — then the sweep counts of the last launch
-    // singular-value capture
-    bool sv_on = false;
-    double* d_sv = nullptr;
-    int sv_steps = 0, sv_pmax = 0;
-    TTDev dev() const {
-        TTDev t;
-        t.data = d_data; t.stride = stride; t.off = d_off; t.rks = d_rks; t.dims = d_dims; t.cap = d_cap;
-        t.d = d; t.batch = batch;
-        return t;
-    }
-};
-struct ttn_tto_s {
-    int d = 0;
-    int batch = 1;                            // operators in the handle (include/ttn_opbatch.h): equal dims and ranks, operator b at d_data + b * stride
-    long long stride = 0;                     // doubles per operator: off[d]
-    int el = 1;                               // 1 Float64, 2 ComplexF64 (slots of twice the doubles; d_dims keeps n_k, d_dims2 holds 2 n_k^2)
-    std::vector<int64_t> dims, rks;
-    std::vector<long long> off;
-    double* d_data = nullptr;
-    long long* d_off = nullptr;
-    long long* d_rks = nullptr;
-    int* d_dims = nullptr;
-    int* d_dims2 = nullptr;                   // [d] n_k^2: the dims of the operator seen as a vector (tto_to_ttv)
-    std::vector<int64_t> ot;                  // [d] gauge flags (tto_ot; zeros unless ttn_tto_set_ot or an operation sets them)
-    TTODev dev() const {
-        TTODev t;
-        t.data = d_data; t.off = d_off; t.rks = d_rks; t.dims = d_dims; t.d = d;
-        t.stride = batch > 1 ? stride : 0;    // 0: every train reads the one operator
-        return t;
-    }
-    // The operator as ONE train of physical dimensions n_k^2 whose capacity is its ranks: an operator core (n, n, r_l, r_r) is byte for
-    // byte the vector core (n^2, r_l, r_r), and the 16-byte slot rounding of both handle kinds gives the same offsets.
-    TTDev vdev() const {
-        TTDev t;
-        t.data = d_data; t.stride = off.empty() ? 0 : off.back(); t.off = d_off; t.rks = d_rks; t.dims = d_dims2; t.cap = d_rks;
-        t.d = d; t.batch = 1;
-        return t;
-    }
-};
-
-// A rectangular TT operator (include/ttn_rect.h): cores (n_out, n_in, R_l, R_r), Float64, immutable, ranks known on the host.  A type
-// of its own: no entry point written for square operators can be handed one.
-struct ttn_rtto_s {
-    int d = 0;                                // M, the number of sites
-    std::vector<int64_t> odims, idims, rks;
-    std::vector<int> singles;                 // 0-based sites with n_in == 1 (ttn_apply_rect needs exactly one)
-    std::vector<long long> off;
-    double* d_data = nullptr;
-    long long* d_off = nullptr;
-    long long* d_rks = nullptr;
-    int* d_dims = nullptr;                    // [2 M]: n_out, then n_in
-    RTTODev dev() const {
-        RTTODev t;
-        t.data = d_data; t.off = d_off; t.rks = d_rks; t.odims = d_dims; t.idims = d_dims + d; t.d = d;
-        t.s = singles.empty() ? -1 : singles[0];
-        return t;
-    }
-};
-
-static bool same_dims(const std::vector<int64_t>& a, const std::vector<int64_t>& b) { return a == b; }
-
-// A Float64-only entry point that receives a ComplexF64 handle is refused before any launch: it would read half a slot as a whole one.
-static bool any_c64(std::initializer_list<const ttn_tt_s*> tts, std::initializer_list<const ttn_tto_s*> ops = {}) {
-    for (const ttn_tt_s* h : tts) if (h && h->el == 2) return true;
-    for (const ttn_tto_s* h : ops) if (h && h->el == 2) return true;
-    return false;
-}
-static int refuse_c64(const char* who) {
-    g_err = std::string(who) + ": Float64 only, a ComplexF64 handle is not supported";
-    return TTN_ERR_UNSUPPORTED;
-}
-#define F64_ONLY(who, ...) do { if (any_c64(__VA_ARGS__)) return refuse_c64(who); } while (0)
-static int refuse_mixed(const char* who) {
-    g_err = std::string(who) + ": the element types (Float64 / ComplexF64) of the handles do not fit this call";
-    return TTN_ERR_UNSUPPORTED;
-}
-
-// An operator batch (include/ttn_opbatch.h) is taken by the entry points listed there; every other one refuses it before any launch: it
-// would read operator 0 for every train, or 1 train's worth of a batch of slots.
-static int single_op(const ttn_tto_s* A, const char* who) {
-    if (!A || A->batch <= 1) return TTN_OK;
-    g_err = std::string(who) + ": an operator batch is not supported here (ttn_opbatch.h lists the calls that take one; ttn_tto_select gives one operator of it)";
-    return TTN_ERR_UNSUPPORTED;
-}
-// ... and the ones that take it need one operator per train
-static int op_batch_fits(const ttn_tto_s* A, int batch) {
-    if (A->batch > 1 && A->batch != batch) { g_err = "batch sizes differ (the operator batch and the trains)"; return TTN_ERR_DIMS; }
-    return TTN_OK;
-}
-
-// ttn_tt_free / ttn_status_all: bit `code` of the library-level word for every failure code recorded on the handle (which one is
-// reported is decided on the host, by the order of status_table)
-__global__ void k_fold_status(const int* status, int batch, unsigned* pending) {
-    unsigned m = 0;
-    for (int b = threadIdx.x; b < batch; b += 64) if (status[b]) m |= 1u << status[b];
-    if (m) atomicOr(pending, m);
-}
-
-// Owner of a handle that a call builds or only needs until it returns: the destructor frees the handle, with whatever device memory it
-// holds by then, on every return path, unless release() has handed it to the caller.
-template <class H, int (*Free)(H*)>
-struct Owned {
-    H* h = nullptr;
-    Owned() = default;
-    Owned(const Owned&) = delete;
-    Owned& operator=(const Owned&) = delete;
-    ~Owned() { if (h) Free(h); }
-    H* release() { H* t = h; h = nullptr; return t; }
-};
-using OwnedTT = Owned<ttn_tt_s, ttn_tt_free>;
-using OwnedTTO = Owned<ttn_tto_s, ttn_tto_free>;
-using OwnedRTTO = Owned<ttn_rtto_s, ttn_rtto_free>;
-
 extern "C" {
-
-const char* ttn_version(void) { return "ttn-mi355x 0.1.0 (gfx950, fp64)"; }
-const char* ttn_last_error_string(void) { return g_err.c_str(); }
-
-int ttn_device_count(int* n) {
-    if (!n) return fail(TTN_ERR_ARG, "null pointer");
-    int c = 0;
-    hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) { *n = 0; return hipfail(e, "hipGetDeviceCount"); }
-    *n = c;
-    return TTN_OK;
-}
-
-int ttn_init(int device) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (g_init && device == g_device) return TTN_OK;
-    if (g_init) return fail(TTN_ERR_ARG, "ttn_init: already bound to another device (call ttn_finalize first)");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&g_ev0, &g_ev1, &g_launch_ev0, &g_launch_ev1}) HIPCHK(hipEventCreate(e));
-    // the kernels that use more than the default 64 KiB of dynamic LDS
-    const struct { const void* fn; size_t lds; } lds_limits[] = {
-        {(const void*)k_compress, COMPRESS_LDS_BYTES},
-        {(const void*)k_selftest_eig128, COMPRESS_LDS_BYTES},
-        {(const void*)k_mals_linsolve, COMPRESS_LDS_BYTES},
-        {(const void*)k_als_linsolve, COMPRESS_LDS_BYTES},
-        {(const void*)k_two_site_eig, COMPRESS_LDS_BYTES},
-        {(const void*)k_two_site_eig_ortho, COMPRESS_LDS_BYTES},
-        {(const void*)k_als_eig, COMPRESS_LDS_BYTES},
-        {(const void*)k_increase_ranks, COMPRESS_LDS_BYTES},
-        {(const void*)k_ttv_decomp, COMPRESS_LDS_BYTES},
-        {(const void*)k_split_sites, COMPRESS_LDS_BYTES},
-        {(const void*)k_swap_chain, COMPRESS_LDS_BYTES},
-        {(const void*)k_orthogonalize, ORTHO_LDS_BYTES},
-        {(const void*)k_ortho512, O5_LDS_BYTES(TTN_MAX_D * 8)},
-        {(const void*)k_dot_fused, DOT_LDS_BYTES(DOT_MAX_D)},
-        {(const void*)k_grad_chain, DOT_LDS_BYTES(DOT_MAX_D)},
-        {(const void*)k_selftest_gemm, sizeof(double) * GEMM_LDS_TOTAL},
-        {(const void*)k_selftest_syrk2, sizeof(double) * GEMM_LDS_TOTAL},
-        {(const void*)k_selftest_gemm_ra2, sizeof(double) * GEMM_LDS_TOTAL},
-        {(const void*)k_tdvp, TDVP_LDS_BYTES},
-        {(const void*)k_lu_panel, LU_PANEL_LDS_BYTES},
-        {(const void*)k_lu_trail, sizeof(double) * GEMM_LDS_TOTAL},
-        {(const void*)k_selftest_lu, COMPRESS_LDS_BYTES},
-        {(const void*)k_selftest_two_site_apply, COMPRESS_LDS_BYTES},
-        {(const void*)k_cross_maxvol<false>, TTN_XV_LDS_BYTES},
-        {(const void*)k_cross_maxvol<true>, TTN_XV_LDS_BYTES},
-        {(const void*)k_zcompress, TTN_ZC_LDS_BYTES},
-        {(const void*)k_cross_batch_site, TTN_XB_LDS_BYTES},
-        {(const void*)k_expect<0>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expect<1>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expect<2>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expect<3>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expect<4>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expect<5>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_chain<0>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_chain<1>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_chain<2>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_chain<3>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_chain<4>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_chain<5>, EXPECT_LDS_BYTES(EXPECT_MAX_D)},
-        {(const void*)k_expgrad_core_gen<false>, sizeof(double) * GEMM_LDS_TOTAL},
-        {(const void*)k_expgrad_core_gen<true>, sizeof(double) * GEMM_LDS_TOTAL},
-        {(const void*)k_measure_open, MEASURE_LDS_BYTES(MEASURE_MAX_D)},
-        {(const void*)k_measure_walk, MEASURE_LDS_BYTES(MEASURE_MAX_D)},
-        {(const void*)k_sample_sweep, SAMPLE_LDS_BYTES},
-    };
-    for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
-    { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
-    if (ttn_wg512_compress_args_bytes() != sizeof(CompressArgs)) return fail(TTN_ERR_ARG, "ttn_init: the two kernel builds disagree on CompressArgs");
-    { int rc = g_next_train.ensure(sizeof(int)); if (rc) return rc; }
-    { int rc = g_pending_status.ensure(sizeof(unsigned)); if (rc) return rc; }
-    HIPCHK(hipMemset(g_pending_status.p, 0, sizeof(unsigned)));
-    g_device = device;
-    g_init = true;
-    return TTN_OK;
-}
-
-int ttn_finalize(void) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!g_init) return TTN_OK;
-    hipStreamSynchronize(g_stream);
-    for (DevBuf* b : g_bufs) b->release();
-    for (hipEvent_t e : {g_ev0, g_ev1, g_launch_ev0, g_launch_ev1}) hipEventDestroy(e);
-    g_have_launch_ms = false;
-    g_ortho_state_batch = 0;
-    for (auto e : g_slots) if (e) hipEventDestroy(e);
-    g_slots.clear();
-    if (g_xb_tab_ev) { hipEventDestroy(g_xb_tab_ev); g_xb_tab_ev = nullptr; }
-    if (g_measure_ev) { hipEventDestroy(g_measure_ev); g_measure_ev = nullptr; }
-    for (hipEvent_t e : g_sample_ev) hipEventDestroy(e);
-    g_sample_ev.clear();
-    g_sample_chunks = 0;
-    hipStreamDestroy(g_stream);
-    g_stream = nullptr; g_init = false; g_device = -1;
-    return TTN_OK;
-}
-
-int ttn_sync(void) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
-int ttn_timer_begin(void) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    HIPCHK(hipEventRecord(g_ev0, g_stream));
-    return TTN_OK;
-}
-int ttn_timer_end(float* ms) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!ms) return fail(TTN_ERR_ARG, "null pointer");
-    HIPCHK(hipEventRecord(g_ev1, g_stream));
-    HIPCHK(hipEventSynchronize(g_ev1));
-    HIPCHK(hipEventElapsedTime(ms, g_ev0, g_ev1));
-    return TTN_OK;
-}
-
-int ttn_event_record(int64_t slot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (slot < 0 || slot >= 4096) return fail(TTN_ERR_ARG, "event slot out of range");
-    if ((int64_t)g_slots.size() <= slot) g_slots.resize(slot + 1, nullptr);
-    if (!g_slots[slot]) HIPCHK(hipEventCreate(&g_slots[slot]));
-    HIPCHK(hipEventRecord(g_slots[slot], g_stream));
-    return TTN_OK;
-}
-int ttn_event_elapsed(int64_t a, int64_t b, float* ms) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!ms || a < 0 || b < 0 || a >= (int64_t)g_slots.size() || b >= (int64_t)g_slots.size() || !g_slots[a] || !g_slots[b])
-        return fail(TTN_ERR_ARG, "event slot not recorded");
-    HIPCHK(hipEventSynchronize(g_slots[b]));
-    HIPCHK(hipEventElapsedTime(ms, g_slots[a], g_slots[b]));
-    return TTN_OK;
-}
 
 // r_and_d_to_rks with Julia's wrapping Int64 products (src/tt_tools.jl:407-425)
 static int64_t wrap_prod(const int64_t* v, int64_t lo, int64_t hi) {  // product of v[lo..hi)
@@ -953,6 +611,7 @@ int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
     return TTN_OK;
 }
 
+static DevBuf g_which;            // [batch] scaled core per train when the gauge flags differ (scaled_core)
 // The core scalar multiplication scales: the first one with ot == 0, else the first (tt_operations.jl:262).  Uniform over the batch
 // -> `which`; trains with different gauge flags (uploaded one by one, or zeroed by ttn_scale_batch) -> a per-train device table.
 // ot: [batch][d] gauge flags.
@@ -1053,6 +712,7 @@ int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
     return scale_impl("ttn_scale_batch", 0.0, 0.0, a, x, y);
 }
 
+static DevBuf g_grad_coef;        // [2][batch] doubles: Delta of ttn_dot_pullback, alpha and beta of ttn_tt_cores_axpby
 // z = alpha x + beta (A y) (include/ttn_step.h): k_apply_axpby, one launch for ttn_apply -> ttn_scale_batch x 2 -> ttn_add.  Factors that
 // are the same for every train travel as kernel arguments; only a pair that differs over the batch is uploaded (and waited for).
 int ttn_apply_axpby(const double* alpha, ttn_tt_t x, const double* beta, ttn_tto_t A, ttn_tt_t y, ttn_tt_t z) {
@@ -1146,6 +806,7 @@ int ttn_compress_rank_bound(int64_t d, const int64_t* dims, const int64_t* rks, 
     return TTN_OK;
 }
 
+static DevBuf g_next_train;       // train counter of the persistent k_compress grid
 // Which build runs a compress launch, and on how many workgroup slots.  More trains than CUs: the 512-thread build on a PERSISTENT
 // grid of two workgroups per CU that pull trains from a counter (scratch per slot); otherwise one 1024-thread workgroup per train
 // (lowest latency for a single train).  TTN_WG512=1 / 0 forces / forbids the 512-thread build (diagnostics, parity tests).
@@ -1780,6 +1441,8 @@ int ttn_tt_merge_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* merge_numbers, int
 }
 
 // ---- train -> dense tensor (csrc/ttn_grid_kernels.h) --------------------------------------------------------------------------------
+static long long g_dense_plan[3] = {-1, 0, 0};   // cut m, TM, TN of the last ttn_tt_to_dense / ttn_tto_to_dense (ttn_debug_dense_plan); m < 0: none
+static long long g_gather_plan[4] = {0, 0, 0, 0};   // TI, TO, ld, RO of the gather of the last ttn_tto_decomp_dev (ttn_debug_gather_plan); TI == 0: none
 // One side's partial products, enqueued step by step: the small steps share single-workgroup launches, a large step gets the grid.
 // Returns the buffer (0 / 1) that holds the last step's result.  `dims` / `bound`: the host copies of the view's dimensions and rank bounds.
 static int dense_chain(const TTDev& tt, const int64_t* dims, const int64_t* bound, int batch, int side, int k_first, int nsteps, double* buf0,
@@ -2008,6 +1671,7 @@ int ttn_qtt_grid_points(int64_t n_dims, int64_t bits, int interleaved, double a,
 
 // ---- als_linsolve ------------------------------------------------------------------------------------------------
 #define TTN_DENSE_LOCAL_MAX_ALS 2048
+static DevBuf g_lu_flag;          // singular-pivot word of the grid form of als_linsolve
 // The grid form of als_linsolve (csrc/ttn_als_grid.h): for every train in turn the half sweeps of src/solvers/als.jl:199-219 walked on
 // the host — per site the assembly of K (grid), the blocked LU with partial pivoting panel by panel (panel: one workgroup; row
 // interchanges + U12: grid; trailing MFMA update: grid), the back substitution, then the core move and environment update (phase 2 / 3
@@ -2184,38 +1848,6 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
     return TTN_OK;
 }
 
-// ---- failure codes ------------------------------------------------------------------------------------------------
-// What each per-train code of the dense kernels (TtnStatus, csrc/ttn_common.h) means to a caller.  The first entry whose code any
-// train carries is the one reported.
-const struct { int code, err; const char* msg; } status_table[] = {
-    {TTN_ST_LANCZOS, TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol"},
-    {TTN_ST_NONFINITE, TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)"},
-    {TTN_ST_SINGULAR, TTN_ERR_SINGULAR, "a local system K is singular (als_linsolve), or a local metric S_s is not positive definite (als_gen_eigsolv)"},
-    {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "a train's ranks differ from the ranks the call needs (als_linsolve: the start handle; ttn_apply_pullback: R .* x; ttn_tt_cores_axpby: x)"},
-    {TTN_ST_RANK_OVERFLOW, TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)"},
-    {TTN_ST_JACOBI, TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit"},
-};
-
-// `seen`: bit c set for every code c recorded (k_fold_status builds the same word on the device).  `who` prefixes the message.
-static int status_error(unsigned seen, const char* who = nullptr) {
-    for (const auto& s : status_table)
-        if (seen & (1u << s.code)) return fail(s.err, who ? (std::string(who) + ": " + s.msg).c_str() : s.msg);
-    return TTN_OK;
-}
-
-// Failure codes of every dense kernel that wrote `h` since the last call, as bits of one word (synchronises).  The codes are sticky
-// on the device — a kernel only ever stores a non-zero code, so a failure inside a chain of launches survives the launches after
-// it — and are cleared here, on read.
-static int take_status(ttn_tt_t h, unsigned& seen) {
-    std::vector<int> st(h->batch);
-    HIPCHK(hipMemcpyAsync(st.data(), h->d_status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int) * h->batch, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    seen = 0;
-    for (int c : st) if (c) seen |= 1u << c;
-    return TTN_OK;
-}
-
 // ---- the two-site solvers (mals_linsolve / dmrg_linsolve, mals_eigsolve / dmrg_eigsolve) ---------------------------------------
 // The sweep plan of a stage schedule: plan[s] = the rank cap of full sweep s (rmax_schedule null: 1).  The reference's while-loops
 // (dmrg.jl:421-426, :523-528, mals.jl:372-378) only terminate for positive, strictly increasing stage ends.  Messages start with `who`;
@@ -2345,6 +1977,7 @@ static void two_site_epilogue(ttn_tt_t x, int mode, const std::vector<int64_t>& 
 #define TTN_DENSE_LOCAL_MAX 2048
 #define TTN_KRYLOVDIM_DEFAULT 30       // KrylovKit.KrylovDefaults.krylovdim
 struct LocalSolver { int it_solver = 0; int64_t itslv_thresh = TTN_DENSE_LOCAL_MAX; int64_t maxiter = 200; double tol = 1.0e-8; };
+static DevBuf g_cg_iters;         // [batch] CG iterations of the last two-site linear solve
 static std::vector<int> g_cg_iters_host;       // total CG iterations per train of the last two-site solve (ttn_dmrg_cg_iterations)
 
 static int two_site_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, double tol, int64_t rmax, int mode, const std::vector<int64_t>& plan,
@@ -2449,6 +2082,9 @@ int ttn_dmrg_cg_iterations(int64_t batch, int64_t* iters) {
 // ---- dmrg_eigsolve / mals_eigsolve (csrc/ttn_eigsolve_kernels.h) ---------------------------------------------------------------
 // Both walk full sweeps of the same plan as dmrg_linsolve (sweep_plan): DMRG windows 0..d-3 forward, d-2..1 backward, then the closing
 // solve at window 0 (one history entry more); MALS windows 0..d-2 forward, d-2..0 backward (mals.jl:393-418, sweep s capped at plan[s]).
+static DevBuf g_hist_E, g_hist_r; // [batch][hist_len] energy / rank history of the last two-site eigensolve
+static DevBuf g_lz_iters, g_lz_res;   // [batch] Lanczos statistics of the last two-site eigensolve
+static DevBuf g_eig_ortho;        // [3][batch][n_ortho] doubles of the last penalised eigensolve: weights, 1 / ||phi_j||, overlaps
 static std::vector<int> g_lz_iters_host;       // Lanczos operator applications per train of the last eigensolve (ttn_eigsolve_stats)
 static std::vector<double> g_lz_res_host;      // largest final Lanczos residual per train of the last eigensolve
 
@@ -2680,171 +2316,6 @@ int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps) {
     unsigned seen = 0;
     const int rc = take_status(psi, seen);
     return rc ? rc : status_error(seen);
-}
-
-// dot on ComplexF64 handles (k_zdot): out receives `batch` interleaved (re, im) pairs
-static int zdot(ttn_tt_t a, ttn_tt_t b, double* out) {
-    const int d = a->d;
-    long long wmax = 1, tmax = 1;
-    for (int m = 0; m <= d; ++m) wmax = std::max<long long>(wmax, a->bound[m] * b->bound[m]);
-    for (int k = 0; k < d; ++k) tmax = std::max<long long>(tmax, a->dims[k] * a->bound[k] * b->bound[k + 1]);
-    const long long per_train = 2 * (wmax + tmax);
-    const int in_lds = per_train <= TTN_ZDOT_LDS_DOUBLES ? 1 : 0;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * a->batch);
-    if (rc) return rc;
-    rc = g_dout.ensure(sizeof(double) * 2 * a->batch);
-    if (rc) return rc;
-    ZDotArgs P;
-    P.a = a->dev(); P.b = b->dev();
-    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
-    P.wmax = wmax; P.tmax = tmax; P.in_lds = in_lds;
-    P.out = g_dout.as<double>();
-    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
-    hipLaunchKernelGGL(k_zdot, dim3(a->batch), dim3(TTN_ZC_WG), in_lds ? sizeof(double) * (size_t)per_train : 0, g_stream, P);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
-    g_have_launch_ms = true;
-    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * 2 * a->batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
-int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!a || !b || !out) return fail(TTN_ERR_ARG, "null pointer");
-    if (!same_dims(a->dims, b->dims)) return fail(TTN_ERR_DIMS, "TT dimensions are not compatible");
-    if (a->batch != b->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (a->el != b->el) return refuse_mixed("ttn_dot");
-    if (a->el == 2) return zdot(a, b, out);
-    const int d = a->d;
-    if (d > DOT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot: chains longer than 480 sites are not supported");
-    if (a->stride >= (1LL << 31) || b->stride >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot: a train of 2^31 doubles or more");
-    long long ramax = 1, rbmax = 1, nmax = 1;
-    for (int m = 0; m <= d; ++m) { ramax = std::max<long long>(ramax, a->bound[m]); rbmax = std::max<long long>(rbmax, b->bound[m]); }
-    for (int k = 0; k < d; ++k) nmax = std::max<long long>(nmax, a->dims[k]);
-    const long long per_train = (2 + nmax) * ramax * rbmax + 16;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * a->batch);
-    if (rc) return rc;
-    rc = g_dout.ensure(sizeof(double) * a->batch);
-    if (rc) return rc;
-    DotArgs P;
-    P.a = a->dev(); P.b = b->dev();
-    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
-    P.ramax = (int)ramax; P.rbmax = (int)rbmax; P.nmax = (int)nmax;
-    P.out = g_dout.as<double>();
-    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
-    hipLaunchKernelGGL(k_dot_fused, dim3(a->batch), dim3(TTN_WG), DOT_LDS_BYTES(d), g_stream, P);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));       // ttn_last_launch_ms: the kernel alone (this call goes on to copy and synchronise)
-    g_have_launch_ms = true;
-    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * a->batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
-// <x, A y> (include/ttn_expect.h): k_expect, one workgroup per train; d_out is device memory
-static_assert(EXPECT_QTT_RMAX == TTN_EXPECT_QTT_MAX_RANK && EXPECT_QTT_OPR_MAX == TTN_EXPECT_QTT_MAX_OP_RANK, "ttn_expect.h and ttn_expect_kernels.h disagree");
-static int sandwich_launch(const char* who, ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, double* d_out) {
-    F64_ONLY(who, {x, y}, {A});
-    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (int rb = op_batch_fits(A, x->batch)) return rb;
-    const int d = x->d;
-    if (d > EXPECT_MAX_D) return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: chains longer than 480 sites are not supported");
-    if (x->stride >= (1LL << 31) || y->stride >= (1LL << 31) || A->off.back() >= (1LL << 31))
-        return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: a train or an operator of 2^31 doubles or more");
-    long long rxmax = 1, rymax = 1, Rmax = 1, nmax = 1;
-    for (int m = 0; m <= d; ++m) {
-        rxmax = std::max<long long>(rxmax, x->bound[m]); rymax = std::max<long long>(rymax, y->bound[m]); Rmax = std::max<long long>(Rmax, A->rks[m]);
-    }
-    bool qtt = Rmax <= EXPECT_QTT_OPR_MAX;
-    for (int k = 0; k < d; ++k) { nmax = std::max<long long>(nmax, x->dims[k]); qtt = qtt && x->dims[k] == 2; }
-    // 32-bit element offsets in the workgroup GEMM: the workspace of one train stays below 2^31 doubles
-    if (rxmax >= (1LL << 31) || rymax >= (1LL << 31) || Rmax >= (1LL << 31) || rxmax * rymax >= (1LL << 31) || rxmax * rymax * Rmax >= (1LL << 31)
-        || (2 + 2 * nmax) * rxmax * rymax * Rmax >= (1LL << 31))
-        return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: ranks too large (the three-layer state of one train reaches 2^31 doubles)");
-    const long long general = (2 + 2 * nmax) * rxmax * rymax * Rmax;
-    const long long per_train = std::max<long long>(general, qtt ? Rmax * EXPECT_IMG_STATE : 0) + 16;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch);
-    if (rc) return rc;
-    ExpectArgs P;
-    P.x = x->dev(); P.y = y->dev(); P.A = A->dev();
-    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
-    P.rxmax = (int)rxmax; P.rymax = (int)rymax; P.Rmax = (int)Rmax; P.nmax = (int)nmax;
-    P.out = d_out;
-    const dim3 grid(x->batch), block(TTN_WG);
-    const size_t lds = EXPECT_LDS_BYTES(d);
-    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
-    switch (qtt ? (int)Rmax : 0) {
-        case 1: hipLaunchKernelGGL(k_expect<1>, grid, block, lds, g_stream, P); break;
-        case 2: hipLaunchKernelGGL(k_expect<2>, grid, block, lds, g_stream, P); break;
-        case 3: hipLaunchKernelGGL(k_expect<3>, grid, block, lds, g_stream, P); break;
-        case 4: hipLaunchKernelGGL(k_expect<4>, grid, block, lds, g_stream, P); break;
-        case 5: hipLaunchKernelGGL(k_expect<5>, grid, block, lds, g_stream, P); break;
-        default: hipLaunchKernelGGL(k_expect<0>, grid, block, lds, g_stream, P); break;
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
-    g_have_launch_ms = true;
-    return TTN_OK;
-}
-
-int ttn_sandwich_dev(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, double* d_out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !A || !y || !d_out) return fail(TTN_ERR_ARG, "null pointer");
-    return sandwich_launch("ttn_sandwich_dev", x, A, y, d_out);
-}
-
-int ttn_sandwich(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, double* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !A || !y || !out) return fail(TTN_ERR_ARG, "null pointer");
-    int rc = g_dout.ensure(sizeof(double) * x->batch);
-    if (rc) return rc;
-    if ((rc = sandwich_launch("ttn_sandwich", x, A, y, g_dout.as<double>()))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * x->batch, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
-// diagnostics: the per-train state words of the last orthogonalize (next site, buffers, sites taken by k_ortho512), read from the
-// workspace where that call left them (the workspace only grows, so the words stay in bounds until ttn_finalize)
-int ttn_debug_ortho_state(int64_t b, int64_t* out4) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!out4 || b < 0 || b >= g_ortho_state_batch) return fail(TTN_ERR_ARG, "ttn_debug_ortho_state: no orthogonalize of a batch with train b yet");
-    int tmp[4];
-    HIPCHK(hipMemcpyAsync(tmp, g_scratch.as<char>() + g_ortho_state_off + sizeof(tmp) * b, sizeof(tmp), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int i = 0; i < 4; ++i) out4[i] = tmp[i];
-    return TTN_OK;
-}
-
-int ttn_last_launch_ms(float* ms) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!ms) return fail(TTN_ERR_ARG, "null pointer");
-    if (!g_have_launch_ms) return fail(TTN_ERR_ARG, "ttn_last_launch_ms: no ttn_dot / ttn_norm / ttn_orthogonalize / ttn_tto_mul / ttn_tto_decomp_dev launch yet");
-    HIPCHK(hipEventSynchronize(g_launch_ev1));
-    HIPCHK(hipEventElapsedTime(ms, g_launch_ev0, g_launch_ev1));
-    return TTN_OK;
-}
-
-int ttn_norm(ttn_tt_t a, double* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (a && out && a->el == 2) {               // norm = sqrt(max(real(dot(a, a)), 0))
-        std::vector<double> z(2 * (size_t)a->batch);
-        const int rcz = ttn_dot(a, a, z.data());
-        if (rcz) return rcz;
-        for (int b = 0; b < a->batch; ++b) out[b] = std::sqrt(std::max(z[2 * b], 0.0));
-        return TTN_OK;
-    }
-    int rc = ttn_dot(a, a, out);
-    if (rc) return rc;
-    for (int b = 0; b < a->batch; ++b) { double v = out[b]; v = v < 0 ? 0.0 : v; out[b] = std::sqrt(v); }
-    return TTN_OK;
 }
 
 // ---- core gradients (csrc/ttn_grad_kernels.h) ------------------------------------------------------------------------------------
@@ -3083,80 +2554,6 @@ int ttn_tt_cores_dot(ttn_tt_t x, ttn_tt_t y, double* out) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, g_dout.p, sizeof(double) * x->batch, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
-int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    F64_ONLY("ttn_orthogonalize", {x, y});
-    if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x == y) return fail(TTN_ERR_ARG, "ttn_orthogonalize: output must not alias the input");
-    const int d = x->d;
-    if (center < 1 || center > d) return fail(TTN_ERR_CENTER, "Impossible orthogonalization");
-    // y ranks start from r_and_d_to_rks(x.rks, dims) but a left QR step sets r_{j+1} = min(rows, cols), which can
-    // exceed that cap (the reference reassigns the rank, tt_tools.jl:522); they never exceed x's own ranks.
-    std::vector<int64_t> yb(x->bound);
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < yb[m]) return fail(TTN_ERR_CAPACITY, "ttn_orthogonalize: destination capacity too small");
-    long long rmax = 1, nmax = 1;
-    for (int m = 0; m <= d; ++m) rmax = std::max<long long>(rmax, x->bound[m]);
-    for (int k = 0; k < d; ++k) nmax = std::max<long long>(nmax, x->dims[k]);
-    const long long mm = nmax * rmax;           // rows of the tall matrices
-    const long long per_train = 2 * mm * rmax + 4 * rmax * rmax + 2 * QR_NB * mm + ((rmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64   // Tm, Qb, 4 R, Vb, Wb, T panels
-                                + 3 * 128 * 128;                                                                                  // Gram matrices / L1 of the Cholesky-QR steps
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch + sizeof(int) * (5 * (size_t)x->batch + 16) + 64);
-    if (rc) return rc;
-    rc = g_dout.ensure(sizeof(double) * x->batch);
-    if (rc) return rc;
-    OrthoArgs P;
-    P.x = x->dev(); P.y = y->dev();
-    P.center = (int)center - 1;
-    P.scratch = g_scratch.as<double>(); P.scratch_stride = per_train;
-    P.mmax = (int)mm; P.rmax = (int)rmax;
-    { const char* e = getenv("TTN_ORTHO_CHOLQR"); P.no_cholqr = (e && atoi(e) == 1) ? 2 : 0; }
-    // Rank <= 64 QTT trains: the ramp sites at the right end by one wave per train (csrc/ttn_ortho_ramp.h), the tall sites and the
-    // centre core by the 512-thread kernel (two workgroups per CU, csrc/ttn_ortho512.h), the 1024-thread kernel before them for the
-    // left sweep and after them only for the trains they did not finish.  Measured against the single launch (d = 30, rank 64, centre
-    // 1): 1.24 vs 1.28 ms for one train, 1.28 vs 1.48 at 8, 1.41 vs 1.89 at 256, 3.36 vs 6.89 at 1024.  TTN_ORTHO512 = 0 / 1 forbids /
-    // forces it.
-    bool use512 = nmax == 2 && rmax <= 64 && d <= TTN_MAX_D * 8 && center < d;
-    for (int k = 0; k < d; ++k) use512 = use512 && x->dims[k] == 2;
-    { const char* e = getenv("TTN_ORTHO512"); if (e) use512 = atoi(e) != 0 && nmax == 2 && rmax <= 64 && d <= TTN_MAX_D * 8; }
-    P.mode = 0; P.trains = nullptr;
-    g_ortho_state_off = sizeof(double) * (size_t)per_train * x->batch;
-    g_ortho_state_batch = x->batch;
-    P.state = reinterpret_cast<int*>(g_scratch.as<char>() + g_ortho_state_off);
-    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
-    if (use512) {
-        P.mode = 1;
-        int* left = P.state + 4 * (size_t)x->batch;                            // count, then the list of trains k_ortho512 did not finish
-        HIPCHK(hipMemsetAsync(left, 0, sizeof(int), g_stream));
-        // the ramp sites at the right end (wide / square LQ steps) go to one wave per train (csrc/ttn_ortho_ramp.h); the 1024-thread
-        // kernel then only runs the left sweep, and not at all when the centre is the first site.
-        if (P.center > 0) hipLaunchKernelGGL(k_orthogonalize, dim3(x->batch), dim3(TTN_WG), ORTHO_LDS_BYTES, g_stream, P);
-        P.mode = P.center > 0 ? 4 : 5;
-        hipLaunchKernelGGL(k_ortho_ramp, dim3((x->batch + ORAMP_WG / 64 - 1) / (ORAMP_WG / 64)), dim3(ORAMP_WG), 0, g_stream, P, (int)x->batch);
-        hipLaunchKernelGGL(k_ortho512, dim3(x->batch), dim3(O5_WG), O5_LDS_BYTES(d), g_stream, P);
-        // the 512-thread kernel finishes a train (centre core included) unless it had to stop — a refused step, a site outside its
-        // class: the third launch takes only those trains (1024 heavy workgroups cost 4 ms of dispatch even when they do nothing)
-        int h_left = 0;
-        HIPCHK(hipMemcpyAsync(&h_left, left, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        if (h_left > 0) {
-            P.mode = 3;
-            P.trains = left + 1;
-            hipLaunchKernelGGL(k_orthogonalize, dim3(h_left), dim3(TTN_WG), ORTHO_LDS_BYTES, g_stream, P);
-        }
-    } else {
-        hipLaunchKernelGGL(k_orthogonalize, dim3(x->batch), dim3(TTN_WG), ORTHO_LDS_BYTES, g_stream, P);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
-    g_have_launch_ms = true;
-    y->bound = yb;
-    for (int b = 0; b < y->batch; ++b)
-        for (int k = 0; k < d; ++k) y->ot[(size_t)b * d + k] = (k < center - 1) ? 1 : (k > center - 1 ? -1 : 0);
     return TTN_OK;
 }
 
@@ -3513,6 +2910,8 @@ int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* 
 }
 
 // ---- TT-cross (csrc/ttn_cross_kernels.h) --------------------------------------------------------------------------------------
+static DevBuf g_cross_tab;        // core table of ttn_cross_eval
+static DevBuf g_cross_info;       // status words of a ttn_cross_maxvol called without a device info
 int ttn_cross_maxvol(int cplx, int64_t m, int64_t r, const double* A, double tol, int64_t maxiter, int64_t* piv, double* C, int64_t* dinfo,
                      int64_t* hinfo) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
@@ -3612,6 +3011,9 @@ int ttn_cross_eval(int cplx, int64_t N, int64_t P, const double* const* cores, c
 }
 
 // ---- MaxVol cross for a batch of functions (include/ttn_cross_batch.h, csrc/ttn_cross_batch_kernels.h) ----------------------------
+static DevBuf g_xb_tab;           // core table of ttn_cross_batch_eval
+static std::vector<long long> g_xb_tab_host;   // ttn_cross_batch_eval: the host copy of the core table, kept until its upload has completed
+static hipEvent_t g_xb_tab_ev = nullptr;       // recorded after that upload; waited for before the host copy is written again
 int ttn_cross_batch_points(int mode, int64_t A, int64_t N, int64_t site, int64_t n, int64_t rl, int64_t rr, const int64_t* L, const int64_t* R,
                            const int64_t* idx_in, int64_t P, const int64_t* doff, const double* dom, int64_t* idx_out, double* X) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
@@ -3967,6 +3369,7 @@ int ttn_apply_compress_c64(int64_t d, const int64_t* dims, const double* const* 
 }
 
 // ---- als_eigsolve / als_gen_eigsolv (csrc/ttn_als_eig_kernels.h) ---------------------------------------------------------------
+static DevBuf g_als_tab;          // slot table and stage ranks of the one-site eigensolvers
 // The host walks the stages of the schedule (als.jl:284-300, :370-397): k_als_eig runs a stage's full sweeps at fixed ranks, writing
 // its part of the history; between stages k_increase_ranks pads x into a temporary handle of x's capacity at the ranks
 // r_and_d_to_rks(fill(rmax)) and ttn_orthogonalize brings it back into x (it does not allow aliasing).  The environments of every
@@ -4765,332 +4168,99 @@ int ttn_tto_decomp_dev(int64_t d64, const int64_t* dims, const double* d_tensor,
     return ttn_tto_from_tt(t.h, 0, out);
 }
 
-// ---- site-resolved measurements (include/ttn_measure.h, csrc/ttn_measure_kernels.h) ------------------------------------
-static_assert(MEASURE_MAX_OPS == TTN_MEASURE_MAX_OPS, "ttn_measure.h and ttn_measure_kernels.h disagree");
-// What one train needs in g_scratch (doubles), checked before anything is launched: both chains of k_grad_chain, the states V^O_k of
-// `ntab` tables, and — only when a site can lie outside the on-chip class — the general route's workspace of every workgroup.
-struct MeasurePlan {
-    long long W = 1, tsz = 1, S = 0, wgs = 0, per_train = 0;
-    bool gen = false;
-};
-static int measure_plan(const char* who, const ttn_tt_s* x, int ntab, int npass, MeasurePlan& M) {
-    F64_ONLY(who, {x});
-    const int d = x->d;
-    const std::string w(who);
-    if (d > MEASURE_MAX_D) return fail(TTN_ERR_UNSUPPORTED, (w + ": chains longer than 480 sites are not supported").c_str());
-    if (x->stride >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (w + ": a train of 2^31 doubles or more").c_str());
-    long long rmax = 1, nmax = 1;
-    for (int m = 0; m <= d; ++m) rmax = std::max<long long>(rmax, x->bound[m]);
-    for (int k = 0; k < d; ++k) {
-        nmax = std::max<long long>(nmax, x->dims[k]);
-        M.S += x->dims[k] * x->dims[k];
-        M.gen = M.gen || x->dims[k] != 2;
-    }
-    M.gen = M.gen || rmax > DOT_RMAX;
-    const char* big = ": ranks too large (the workspace of one train reaches 2^31 doubles)";
-    if (rmax >= (1LL << 16) || nmax >= (1LL << 31) || nmax * rmax * rmax >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (w + big).c_str());
-    M.W = (rmax * rmax + 1) & ~1LL;
-    M.tsz = (nmax * rmax * rmax + 1) & ~1LL;
-    M.wgs = M.gen ? std::max<long long>((long long)ntab * d, (long long)npass * (d - 1)) : 0;
-    M.per_train = 2 * (d + 1) * M.W + 2 * M.tsz + (long long)ntab * d * M.W + M.wgs * (2 * M.tsz + 2 * M.W);
-    if (M.per_train >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (w + big).c_str());
+// ---- version, errors, ttn_init / ttn_finalize, sync, timers and event slots ------------------------------------------------------
+// Last: ttn_finalize is the one teardown and names the state of every module, in this file and in the host headers.
+static hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;                 // ttn_timer_begin / ttn_timer_end
+static std::vector<hipEvent_t> g_slots;   // ttn_event_record slots
+const char* ttn_version(void) { return "ttn-mi355x 0.1.0 (gfx950, fp64)"; }
+const char* ttn_last_error_string(void) { return g_err.c_str(); }
+
+int ttn_device_count(int* n) {
+    if (!n) return fail(TTN_ERR_ARG, "null pointer");
+    int c = 0;
+    hipError_t e = hipGetDeviceCount(&c);
+    if (e != hipSuccess) { *n = 0; return hipfail(e, "hipGetDeviceCount"); }
+    *n = c;
     return TTN_OK;
 }
 
-// The three phases for `ntab` host tables of M.S doubles each; d_out is device memory.  Tables t < nemit write their profile to
-// d_out[b ob + t ot + k ok]; npass passes of walks (tables o1 / o2 per pass) fill d_out[b d d + ...] off the diagonal.
-static int measure_run(ttn_tt_t x, const MeasurePlan& M, int ntab, const double* const* tabs, int nemit, long long ob, long long ot, long long ok, int npass,
-                       const int* o1, const int* o2, bool mirror, int64_t normalize, double* d_out) {
-    const int d = x->d, batch = x->batch;
-    // the offsets and the tables travel from a host copy that stays untouched until the upload has completed
-    if (!g_measure_ev) HIPCHK(hipEventCreateWithFlags(&g_measure_ev, hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(g_measure_ev));
-    g_measure_host.assign((size_t)d + (size_t)ntab * M.S, 0.0);
-    {
-        long long off = 0;
-        for (int k = 0; k < d; ++k) { memcpy(&g_measure_host[k], &off, sizeof(off)); off += x->dims[k] * x->dims[k]; }
-        for (int t = 0; t < ntab; ++t) memcpy(&g_measure_host[(size_t)d + (size_t)t * M.S], tabs[t], sizeof(double) * (size_t)M.S);
-    }
-    const long long chunk = std::max<long long>(1, std::min<long long>(std::min<long long>(batch, 65535),
-                                                                       TTN_MEASURE_CHUNK_BYTES / (long long)(sizeof(double) * M.per_train)));
-    int rc;
-    if ((rc = g_scratch.ensure(sizeof(double) * (size_t)M.per_train * (size_t)chunk))) return rc;
-    if ((rc = g_measure_tab.ensure(sizeof(double) * g_measure_host.size()))) return rc;
-    HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
-    HIPCHK(hipMemcpyAsync(g_measure_tab.p, g_measure_host.data(), sizeof(double) * g_measure_host.size(), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipEventRecord(g_measure_ev, g_stream));
-    for (long long b0 = 0; b0 < batch; b0 += chunk) {
-        const int nb = (int)std::min<long long>(chunk, batch - b0);
-        TTDev xd = x->dev();
-        xd.data += b0 * x->stride; xd.rks += b0 * (d + 1); xd.batch = nb;
-        GradChainArgs C_;
-        C_.a = xd; C_.b = xd;
-        C_.env = g_scratch.as<double>();
-        C_.tbuf = C_.env + (size_t)2 * (d + 1) * M.W * nb;
-        C_.W = M.W; C_.tsz = M.tsz;
-        C_.out = nullptr;
-        hipLaunchKernelGGL(k_grad_chain, dim3(nb, 2), dim3(TTN_WG), DOT_LDS_BYTES(d), g_stream, C_);
-        HIPCHK(hipGetLastError());
-        MeasureArgs P;
-        memset(&P, 0, sizeof(P));
-        P.x = xd;
-        P.env = C_.env; P.W = M.W;
-        P.toff = g_measure_tab.as<long long>();
-        P.tabs = g_measure_tab.as<double>() + d;
-        P.S = M.S; P.ntab = ntab;
-        P.V = C_.tbuf + (size_t)2 * M.tsz * nb;
-        P.work = P.V + (size_t)ntab * d * M.W * nb;
-        P.csz = M.tsz; P.tsz = M.tsz; P.wstride = 2 * M.tsz + 2 * M.W;
-        P.out = d_out + b0 * ob;
-        P.ob = ob; P.ot = ot; P.ok = ok; P.nemit = nemit;
-        P.normalize = normalize ? 1 : 0;
-        for (int p = 0; p < npass; ++p) { P.o1[p] = o1[p]; P.o2[p] = o2[p]; }
-        P.mirror = mirror ? 1 : 0;
-        hipLaunchKernelGGL(k_measure_open, dim3(d * ntab, nb), dim3(TTN_WG), MEASURE_LDS_BYTES(d), g_stream, P);
-        HIPCHK(hipGetLastError());
-        if (npass > 0 && d > 1) {
-            hipLaunchKernelGGL(k_measure_walk, dim3(d - 1, nb, npass), dim3(TTN_WG), MEASURE_LDS_BYTES(d), g_stream, P);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    HIPCHK(hipEventRecord(g_launch_ev1, g_stream));
-    g_have_launch_ms = true;
+int ttn_init(int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (g_init && device == g_device) return TTN_OK;
+    if (g_init) return fail(TTN_ERR_ARG, "ttn_init: already bound to another device (call ttn_finalize first)");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&g_ev0, &g_ev1, &g_launch_ev0, &g_launch_ev1}) HIPCHK(hipEventCreate(e));
+    for (const auto& a : lds_limits) HIPCHK(hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));
+    { const int rc512 = ttn_wg512_init(); if (rc512) return hipfail((hipError_t)rc512, "ttn_wg512_init"); }
+    if (ttn_wg512_compress_args_bytes() != sizeof(CompressArgs)) return fail(TTN_ERR_ARG, "ttn_init: the two kernel builds disagree on CompressArgs");
+    { int rc = g_next_train.ensure(sizeof(int)); if (rc) return rc; }
+    { int rc = g_pending_status.ensure(sizeof(unsigned)); if (rc) return rc; }
+    HIPCHK(hipMemset(g_pending_status.p, 0, sizeof(unsigned)));
+    g_device = device;
+    g_init = true;
     return TTN_OK;
 }
 
-static int site_expect_launch(const char* who, ttn_tt_t x, int64_t nops, const double* ops, int64_t normalize, double* d_out) {
-    if (nops < 1 || nops > TTN_MEASURE_MAX_OPS) return fail(TTN_ERR_ARG, (std::string(who) + ": nops must be in 1:16").c_str());
-    MeasurePlan M;
-    int rc;
-    if ((rc = measure_plan(who, x, (int)nops, 0, M))) return rc;
-    std::vector<const double*> tabs((size_t)nops);
-    for (int64_t t = 0; t < nops; ++t) tabs[t] = ops + t * M.S;
-    return measure_run(x, M, (int)nops, tabs.data(), (int)nops, (long long)x->d * nops, x->d, 1, 0, nullptr, nullptr, false, normalize, d_out);
+int ttn_finalize(void) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!g_init) return TTN_OK;
+    hipStreamSynchronize(g_stream);
+    for (DevBuf* b = DevBuf::head; b; b = b->next) b->release();
+    for (hipEvent_t e : {g_ev0, g_ev1, g_launch_ev0, g_launch_ev1}) hipEventDestroy(e);
+    g_have_launch_ms = false;
+    g_ortho_state_batch = 0;
+    for (auto e : g_slots) if (e) hipEventDestroy(e);
+    g_slots.clear();
+    if (g_xb_tab_ev) { hipEventDestroy(g_xb_tab_ev); g_xb_tab_ev = nullptr; }
+    if (g_measure_ev) { hipEventDestroy(g_measure_ev); g_measure_ev = nullptr; }
+    for (hipEvent_t e : g_sample_ev) hipEventDestroy(e);
+    g_sample_ev.clear();
+    g_sample_chunks = 0;
+    hipStreamDestroy(g_stream);
+    g_stream = nullptr; g_init = false; g_device = -1;
+    return TTN_OK;
 }
 
-int ttn_site_expect_dev(ttn_tt_t x, int64_t nops, const double* ops, int64_t normalize, double* d_out) {
+int ttn_sync(void) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    if (!x || !ops || !d_out) return fail(TTN_ERR_ARG, "null pointer");
-    return site_expect_launch("ttn_site_expect_dev", x, nops, ops, normalize, d_out);
-}
-
-int ttn_site_expect(ttn_tt_t x, int64_t nops, const double* ops, int64_t normalize, double* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !ops || !out) return fail(TTN_ERR_ARG, "null pointer");
-    if (nops < 1 || nops > TTN_MEASURE_MAX_OPS) return fail(TTN_ERR_ARG, "ttn_site_expect: nops must be in 1:16");
-    const size_t bytes = sizeof(double) * (size_t)x->d * (size_t)nops * (size_t)x->batch;
-    int rc;
-    { MeasurePlan M; if ((rc = measure_plan("ttn_site_expect", x, (int)nops, 0, M))) return rc; }      // every check before the first allocation
-    if ((rc = g_dout.ensure(bytes))) return rc;
-    if ((rc = site_expect_launch("ttn_site_expect", x, nops, ops, normalize, g_dout.as<double>()))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g_dout.p, bytes, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return TTN_OK;
 }
 
-// Tables of a correlation: 0 = P_k Q_k (the diagonal, built here), 1 = P, 2 = Q (absent when Q equals P bitwise).
-static int correlation_launch(const char* who, ttn_tt_t x, const double* Pt, const double* Qt, int64_t normalize, double* d_out) {
-    MeasurePlan M;
-    int rc;
-    if ((rc = measure_plan(who, x, 3, 2, M))) return rc;
-    const int d = x->d;
-    const bool same = Pt == Qt || memcmp(Pt, Qt, sizeof(double) * (size_t)M.S) == 0;
-    if (same) { M = MeasurePlan(); if ((rc = measure_plan(who, x, 2, 1, M))) return rc; }
-    std::vector<double> PQ((size_t)M.S);
-    {
-        size_t off = 0;
-        for (int k = 0; k < d; ++k) {
-            const int n = (int)x->dims[k];
-            for (int c = 0; c < n; ++c)
-                for (int r = 0; r < n; ++r) {
-                    double acc = 0.0;
-                    for (int w = 0; w < n; ++w) acc += Pt[off + r + (size_t)n * w] * Qt[off + w + (size_t)n * c];
-                    PQ[off + r + (size_t)n * c] = acc;
-                }
-            off += (size_t)n * n;
-        }
-    }
-    const double* tabs[3] = {PQ.data(), Pt, Qt};
-    const int o1[2] = {same ? 1 : 2, 1}, o2[2] = {1, 2};              // pass 0: (O1, O2) = (Q, P), the upper triangle; pass 1: (P, Q), the lower
-    return measure_run(x, M, same ? 2 : 3, tabs, 1, (long long)d * d, 0, d + 1, same ? 1 : 2, o1, o2, same, normalize, d_out);
-}
-
-int ttn_correlation_dev(ttn_tt_t x, const double* P, const double* Q, int64_t normalize, double* d_out) {
+int ttn_timer_begin(void) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    if (!x || !P || !Q || !d_out) return fail(TTN_ERR_ARG, "null pointer");
-    return correlation_launch("ttn_correlation_dev", x, P, Q, normalize, d_out);
+    HIPCHK(hipEventRecord(g_ev0, g_stream));
+    return TTN_OK;
 }
-
-int ttn_correlation(ttn_tt_t x, const double* P, const double* Q, int64_t normalize, double* out) {
+int ttn_timer_end(float* ms) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    if (!x || !P || !Q || !out) return fail(TTN_ERR_ARG, "null pointer");
-    const size_t bytes = sizeof(double) * (size_t)x->d * (size_t)x->d * (size_t)x->batch;
-    int rc;
-    { MeasurePlan M; if ((rc = measure_plan("ttn_correlation", x, 3, 2, M))) return rc; }
-    if ((rc = g_dout.ensure(bytes))) return rc;
-    if ((rc = correlation_launch("ttn_correlation", x, P, Q, normalize, g_dout.as<double>()))) return rc;
-    HIPCHK(hipMemcpyAsync(out, g_dout.p, bytes, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
+    if (!ms) return fail(TTN_ERR_ARG, "null pointer");
+    HIPCHK(hipEventRecord(g_ev1, g_stream));
+    HIPCHK(hipEventSynchronize(g_ev1));
+    HIPCHK(hipEventElapsedTime(ms, g_ev0, g_ev1));
     return TTN_OK;
 }
 
-// ---- sampling (include/ttn_sample.h, csrc/ttn_sample_kernels.h) ----------------------------------------------------------
-static_assert(SAMPLE_TILE == TTN_SAMPLE_TILE, "ttn_sample.h and ttn_sample_kernels.h disagree");
-// What one train needs for its environments and one tile of samples for the general route's products (doubles), checked before anything
-// is launched.
-struct SamplePlan {
-    long long W = 1, tsz = 1, gss = 1, per_train = 0, per_tile = 0, vsz = 0, wsz = 0;
-    bool born = true;
-};
-static int sample_plan(const char* who, const ttn_tt_s* x, int64_t mode, int64_t nsamples, SamplePlan& M) {
-    const std::string w(who);
-    if (nsamples < 1) return fail(TTN_ERR_ARG, (w + ": nsamples must be at least 1").c_str());
-    if (mode != TTN_SAMPLE_BORN && mode != TTN_SAMPLE_DENSITY) return fail(TTN_ERR_ARG, (w + ": mode must be TTN_SAMPLE_BORN (0) or TTN_SAMPLE_DENSITY (1)").c_str());
-    F64_ONLY(who, {x});
-    const int d = x->d;
-    if (d > SAMPLE_MAX_D) return fail(TTN_ERR_UNSUPPORTED, (w + ": chains longer than 480 sites are not supported").c_str());
-    if (x->stride >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (w + ": a train of 2^31 doubles or more").c_str());
-    long long rmax = 1, nmax = 1;
-    bool gen = false;
-    for (int m = 0; m <= d; ++m) rmax = std::max<long long>(rmax, x->bound[m]);
-    for (int k = 0; k < d; ++k) {
-        nmax = std::max<long long>(nmax, x->dims[k]);
-        gen = gen || x->dims[k] != 2;
-    }
-    gen = gen || rmax > DOT_RMAX;
-    const char* big = ": ranks too large (the workspace of one train reaches 2^31 doubles)";
-    if (rmax >= (1LL << 16) || nmax >= (1LL << 31) || nmax * rmax * rmax >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (w + big).c_str());
-    M.born = mode == TTN_SAMPLE_BORN;
-    M.W = (rmax * rmax + 1) & ~1LL;
-    M.tsz = (nmax * rmax * rmax + 1) & ~1LL;
-    M.gss = M.born ? M.W : ((rmax + 1) & ~1LL);
-    M.per_train = M.born ? 2 * (d + 1) * M.W + 2 * M.tsz : (d + 1) * M.gss;
-    M.vsz = gen ? SAMPLE_TILE * rmax : 0;
-    M.wsz = gen ? SAMPLE_TILE * nmax * rmax : 0;
-    M.per_tile = gen ? M.vsz + 2 * M.wsz + SAMPLE_TILE * nmax : 0;
-    if (M.per_train + M.per_tile >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, (w + big).c_str());
-    return TTN_OK;
-}
-
-static int sample_run(ttn_tt_t x, const SamplePlan& M, int64_t nsamples, int64_t seed, const double* d_u, int64_t* d_idx, double* d_logp, int64_t* d_info) {
-    const int d = x->d, batch = x->batch;
-    const long long S = nsamples, budget = TTN_SAMPLE_CHUNK_BYTES / (long long)sizeof(double);
-    // trains per chunk: their environments take at most half the bound; tiles per launch: what the rest holds (one at least)
-    const long long chunk = std::max<long long>(1, std::min<long long>(std::min<long long>(batch, 65535), budget / 2 / M.per_train));
-    const long long tiles_all = (S + SAMPLE_TILE - 1) / SAMPLE_TILE;
-    long long tiles = std::min<long long>(tiles_all, 1LL << 20);
-    if (M.per_tile) tiles = std::max<long long>(1, std::min<long long>(tiles, (budget - chunk * M.per_train) / (chunk * M.per_tile)));
-    int rc;
-    if ((rc = g_scratch.ensure(sizeof(double) * (size_t)(chunk * M.per_train + chunk * tiles * M.per_tile)))) return rc;
-    int nchunks = 0;
-    if (d_info) HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int64_t) * 2 * (size_t)batch, g_stream));
-    for (long long b0 = 0; b0 < batch; b0 += chunk) {
-        const int nb = (int)std::min<long long>(chunk, batch - b0);
-        TTDev xd = x->dev();
-        xd.data += b0 * x->stride; xd.rks += b0 * (d + 1); xd.batch = nb;
-        double* env = g_scratch.as<double>();
-        while (g_sample_ev.size() < (size_t)3 * (nchunks + 1)) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            g_sample_ev.push_back(e);
-        }
-        hipEvent_t* ev = &g_sample_ev[(size_t)3 * nchunks++];
-        HIPCHK(hipEventRecord(ev[0], g_stream));
-        SampleArgs P;
-        memset(&P, 0, sizeof(P));
-        if (M.born) {
-            GradChainArgs C_;
-            C_.a = xd; C_.b = xd;
-            C_.env = env;
-            C_.tbuf = env + (size_t)2 * (d + 1) * M.W * nb;
-            C_.W = M.W; C_.tsz = M.tsz;
-            C_.out = nullptr;
-            hipLaunchKernelGGL(k_grad_chain, dim3(nb, 2), dim3(TTN_WG), DOT_LDS_BYTES(d), g_stream, C_);
-            HIPCHK(hipGetLastError());
-            P.genv = env + (size_t)(d + 1) * M.W;                         // the G half of train 0: G_1 .. G_{d+1}
-            P.gbs = 2 * (d + 1) * M.W; P.gss = M.W;
-        } else {
-            SampleEnvArgs E_;
-            E_.x = xd; E_.g = env; E_.gbs = (d + 1) * M.gss; E_.gss = M.gss;
-            hipLaunchKernelGGL(k_sample_genv, dim3(nb), dim3(TTN_WG), 0, g_stream, E_);
-            HIPCHK(hipGetLastError());
-            P.genv = env; P.gbs = E_.gbs; P.gss = M.gss;
-        }
-        HIPCHK(hipEventRecord(ev[1], g_stream));
-        P.x = xd;
-        P.born = M.born ? 1 : 0;
-        P.S = S;
-        P.seed = (unsigned long long)seed;
-        P.b0 = b0;
-        P.u = d_u ? d_u + (size_t)b0 * S * d : nullptr;
-        P.idx = (long long*)d_idx + (size_t)b0 * S * d;
-        P.logp = d_logp + (size_t)b0 * S;
-        P.info = d_info ? (unsigned long long*)d_info + 2 * b0 : nullptr;
-        P.work = env + (size_t)M.per_train * nb;
-        P.wstride = M.per_tile; P.vsz = M.vsz; P.wsz = M.wsz;
-        for (long long t0 = 0; t0 < tiles_all; t0 += tiles) {
-            const long long nt = std::min<long long>(tiles, tiles_all - t0);
-            P.s0 = t0 * SAMPLE_TILE;
-            P.s1 = std::min<long long>(S, (t0 + nt) * SAMPLE_TILE);
-            hipLaunchKernelGGL(k_sample_sweep, dim3((unsigned)nt, nb), dim3(TTN_WG), SAMPLE_LDS_BYTES, g_stream, P);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(ev[2], g_stream));
-    }
-    g_sample_chunks = nchunks;
-    return TTN_OK;
-}
-
-int ttn_tt_sample_dev(ttn_tt_t x, int64_t mode, int64_t nsamples, int64_t seed, const double* d_u, int64_t* d_idx, double* d_logp, int64_t* d_info) {
+int ttn_event_record(int64_t slot) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    if (!x || !d_idx || !d_logp) return fail(TTN_ERR_ARG, "null pointer");
-    SamplePlan M;
-    int rc;
-    if ((rc = sample_plan("ttn_tt_sample_dev", x, mode, nsamples, M))) return rc;
-    return sample_run(x, M, nsamples, seed, d_u, d_idx, d_logp, d_info);
-}
-
-int ttn_tt_sample(ttn_tt_t x, int64_t mode, int64_t nsamples, int64_t seed, const double* d_u, int64_t* idx, double* logp, int64_t* info) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !idx || !logp) return fail(TTN_ERR_ARG, "null pointer");
-    SamplePlan M;
-    int rc;
-    if ((rc = sample_plan("ttn_tt_sample", x, mode, nsamples, M))) return rc;         // every check before the first allocation
-    const size_t rows = (size_t)x->batch * (size_t)nsamples;
-    const size_t b_idx = sizeof(int64_t) * rows * (size_t)x->d, b_lp = sizeof(double) * rows, b_info = sizeof(int64_t) * 2 * (size_t)x->batch;
-    if ((rc = g_sample_out.ensure(b_idx + b_lp + b_info))) return rc;
-    int64_t* d_idx = g_sample_out.as<int64_t>();
-    double* d_logp = (double*)((char*)g_sample_out.p + b_idx);
-    int64_t* d_info = (int64_t*)((char*)g_sample_out.p + b_idx + b_lp);
-    if ((rc = sample_run(x, M, nsamples, seed, d_u, d_idx, d_logp, d_info))) return rc;
-    HIPCHK(hipMemcpyAsync(idx, d_idx, b_idx, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(logp, d_logp, b_lp, hipMemcpyDeviceToHost, g_stream));
-    if (info) HIPCHK(hipMemcpyAsync(info, d_info, b_info, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
+    if (slot < 0 || slot >= 4096) return fail(TTN_ERR_ARG, "event slot out of range");
+    if ((int64_t)g_slots.size() <= slot) g_slots.resize(slot + 1, nullptr);
+    if (!g_slots[slot]) HIPCHK(hipEventCreate(&g_slots[slot]));
+    HIPCHK(hipEventRecord(g_slots[slot], g_stream));
     return TTN_OK;
 }
-
-int ttn_tt_sample_last_ms(double* env_ms, double* sweep_ms) {
+int ttn_event_elapsed(int64_t a, int64_t b, float* ms) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     NEED_INIT();
-    if (!env_ms || !sweep_ms) return fail(TTN_ERR_ARG, "null pointer");
-    if (!g_sample_chunks) return fail(TTN_ERR_ARG, "ttn_tt_sample_last_ms: no ttn_tt_sample call has run");
-    HIPCHK(hipEventSynchronize(g_sample_ev[(size_t)3 * g_sample_chunks - 1]));
-    double a = 0.0, b = 0.0;
-    for (int c = 0; c < g_sample_chunks; ++c) {
-        float fa = 0.f, fb = 0.f;
-        HIPCHK(hipEventElapsedTime(&fa, g_sample_ev[3 * c], g_sample_ev[3 * c + 1]));
-        HIPCHK(hipEventElapsedTime(&fb, g_sample_ev[3 * c + 1], g_sample_ev[3 * c + 2]));
-        a += fa; b += fb;
-    }
-    *env_ms = a; *sweep_ms = b;
+    if (!ms || a < 0 || b < 0 || a >= (int64_t)g_slots.size() || b >= (int64_t)g_slots.size() || !g_slots[a] || !g_slots[b])
+        return fail(TTN_ERR_ARG, "event slot not recorded");
+    HIPCHK(hipEventSynchronize(g_slots[b]));
+    HIPCHK(hipEventElapsedTime(ms, g_slots[a], g_slots[b]));
     return TTN_OK;
 }
-
 }  // extern "C"

@@ -70,7 +70,7 @@ __host__ __device__ inline View tview(View v) { return View{v.p, v.c, v.r}; }
 __host__ __device__ inline View mkview(double* p, Idx r, Idx c) { return View{p, r, c}; }
 __host__ __device__ inline long long minstride(const Idx& d) { return d.q ? (d.lo < d.hi ? d.lo : d.hi) : d.lo; }
 
-// Per-train failure codes of the dense kernels.  The host maps each to a TTN_ERR_* code and a message (ttn_api.hip: status_table).
+// Per-train failure codes of the dense kernels.  The host maps each to a TTN_ERR_* code and a message (ttn_host_core.h: status_table).
 enum TtnStatus : int {
     TTN_ST_JACOBI = 1,           // a Jacobi SVD hit its sweep limit
     TTN_ST_RANK_OVERFLOW = 2,    // a rank grew beyond the capacity of its handle / working slot

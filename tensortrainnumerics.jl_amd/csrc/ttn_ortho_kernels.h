@@ -13,7 +13,7 @@ struct OrthoArgs {
     double* scratch;
     long long scratch_stride;
     int mmax, rmax;
-    // Three-launch form for large batches of rank <= 64 QTT trains (ttn_api.hip; csrc/ttn_ortho512.h): mode 1 = the left sweep and the
+    // Three-launch form for large batches of rank <= 64 QTT trains (ttn_host_dot.h; csrc/ttn_ortho512.h): mode 1 = the left sweep and the
     // right sweep up to the first site the 512-thread kernel takes, state saved; mode 3 = resume the right sweep from the saved state
     // with every route, then the centre core; mode 0 = everything in one launch.  state: int [batch][4] = {next right-sweep site,
     // buffer of the last right R (0: Rc, 1: Rd), buffer of the last left R (0: Rb0, 1: Rb1), train finished by k_ortho512}; behind it one

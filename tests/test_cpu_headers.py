@@ -16,6 +16,16 @@ def test_headers_discovered():
     assert "ttn_common.h" in HEADERS           # an empty list would make the parametrised test vanish silently
 
 
+def test_host_headers_belong_to_ttn_api_alone():
+    """The host API (csrc/ttn_host_*.h) has internal linkage and one copy of the library state: ttn_api.hip includes every host header,
+    and ttn_wg512.hip sees none of them."""
+    host = [h for h in HEADERS if h.startswith("ttn_host_")]
+    assert host
+    api = open(os.path.join(CSRC, "ttn_api.hip")).read()
+    assert {l.split('"')[1] for l in api.splitlines() if l.startswith("#include ") and "ttn_host_" in l} == set(host)
+    assert "ttn_host_" not in "".join(l for l in open(os.path.join(CSRC, "ttn_wg512.hip")).read().splitlines() if l.lstrip().startswith("#include"))
+
+
 @pytest.mark.parametrize("header", HEADERS)
 def test_header_compiles_alone(header, tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

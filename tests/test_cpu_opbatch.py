@@ -1,5 +1,6 @@
 """CPU-side tests (no GPU) of the operator batches (include/ttn_opbatch.h): every entry point with a ttn_tto_t operand either takes a batch
-or refuses it through single_op before anything else can happen (a source check of csrc/ttn_api.hip against the headers), the new header
+or refuses it through single_op before anything else can happen (a source check of the host API, csrc/ttn_api.hip with the csrc/ttn_host_*.h
+it includes, against the headers), the new header
 stands alone for a C compiler and agrees with the ctypes table, and the argument checks of DeviceTTO.lincomb / stack raise before any
 device call."""
 import ctypes
@@ -13,7 +14,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
-API = os.path.join(ROOT, "tensortrainnumerics.jl_amd", "csrc", "ttn_api.hip")
+CSRC = os.path.join(ROOT, "tensortrainnumerics.jl_amd", "csrc")
+HOST_HEADERS = sorted(f for f in os.listdir(CSRC) if f.startswith("ttn_host_") and f.endswith(".h"))
+# the source of the host API: ttn_api.hip and every host header, found by listing so that a new one is covered as it appears
+API = "".join(open(os.path.join(CSRC, f)).read() for f in ["ttn_api.hip"] + HOST_HEADERS)
 
 # entry points that accept an operator batch: the consumers (they check the batch against the trains) and the handle's own calls
 CONSUMERS = {"ttn_apply", "ttn_apply_axpby", "ttn_sandwich", "ttn_sandwich_dev", "ttn_sandwich_pullback", "ttn_dmrg_eigsolve", "ttn_mals_eigsolve"}
@@ -67,7 +71,8 @@ def _operator_entry_points():
 
 
 def test_every_operator_entry_point_takes_a_batch_or_refuses_it():
-    src = open(API).read()
+    assert HOST_HEADERS, "no csrc/ttn_host_*.h found"
+    src = API
     entries = _operator_entry_points()
     names = {n for n, _ in entries}
     assert len(entries) >= 30 and CONSUMERS <= names and HANDLE_CALLS <= names, sorted(names)
@@ -86,7 +91,7 @@ def test_every_operator_entry_point_takes_a_batch_or_refuses_it():
 
 def test_kernels_add_the_stride_where_they_form_the_operator_pointer():
     """Every kernel on the list reads the operator at data + train * stride; k_compress's fused merge (refused on the host) does not."""
-    csrc = os.path.dirname(API)
+    csrc = CSRC
 
     def text(f):
         return open(os.path.join(csrc, f)).read()

@@ -102,6 +102,32 @@ def one_round():
     T.qtt.hadamard_ttm_(T.DeviceTT.from_host(to_product(hx)), T.DeviceTT.from_host(to_product(hy)), dz, tol=1e-10, work_cap=16)
     D.compress_status(dz)
     digest(h, dz.download(0))
+    # site_expect and sample on one rank-3 batch of 2 (the measurement table and its event; the sample outputs and events)
+    ms = [to_product(O.rand_tt((2,) * d, 3, rng)) for _ in range(2)]
+    dm = T.DeviceTT((2,) * d, ms[0].ttv_rks, batch=2)
+    for b in range(2):
+        dm.upload(b, ms[b])
+    h.update(np.ascontiguousarray(D.site_expect(dm, np.diag([1.0, -1.0]))).tobytes())
+    idx, logp, _ = D.sample(dm, 64, "born", seed=7)
+    h.update(np.ascontiguousarray(idx).tobytes())
+    h.update(np.ascontiguousarray(logp).tobytes())
+    # dot_pullback with one factor per train (the coefficient table)
+    gs = [to_product(O.rand_tt((2,) * d, 3, rng)) for _ in range(2)]
+    dg = T.DeviceTT((2,) * d, gs[0].ttv_rks, batch=2)
+    for b in range(2):
+        dg.upload(b, gs[b])
+    _, abar, bbar = T.grad.dot_pullback(dm, dg, delta=[0.5, -2.0])
+    for b in range(2):
+        digest(h, abar.download(b))
+        digest(h, bbar.download(b))
+    # dmrg_eigsolve penalised against the states found above (weights, norms and overlaps kept on the device)
+    e1 = T.DeviceTT.from_host(to_product(O.rand_tt((2,) * d, 4, rng)), batch=2)
+    ev1 = T.DeviceTT((2,) * d, T.solvers.dmrg_capacity((2,) * d, e1.cap, 8), batch=2)
+    E1, rh1, ovl = T.solvers.dmrg_eigsolve_(ising, e1, ev1, 1e-12, [3], [8], ortho_to=[ev], weight=10.0)
+    h.update(np.asarray(E1, dtype=np.float64).tobytes())
+    h.update(np.asarray(rh1, dtype=np.int64).tobytes())
+    h.update(np.asarray(ovl, dtype=np.float64).tobytes())
+    digest(h, ev1.download(0))
     D.status_all()
     return h.hexdigest()
 
