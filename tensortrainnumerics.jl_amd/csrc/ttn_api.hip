@@ -40,1022 +40,21 @@
 #include "ttn_sample_kernels.h"
 
 // The host headers: the dynamic-LDS table first (it fixes the order of the kernel templates' instantiations, see there), then the
-// layers, lowest first.
+// layers, lowest first — every header stands after the ones it includes (tests/test_cpu_headers.py).
 #include "ttn_host_lds.h"
 #include "ttn_host_core.h"
 #include "ttn_host_dot.h"
 #include "ttn_host_measure.h"
 #include "ttn_host_sample.h"
+#include "ttn_host_handles.h"
+#include "ttn_host_stream.h"
+#include "ttn_host_rect.h"
+#include "ttn_host_compress.h"
 
-// the 512-thread build of k_compress and its building blocks (ttn_wg512.hip: two workgroups per CU)
-extern "C" {
-int ttn_wg512_init(void);
-size_t ttn_wg512_compress_args_bytes(void);
-int ttn_wg512_launch_compress(const void* args, size_t nbytes, int grid, hipStream_t stream);
-int ttn_wg512_selftest_eig(const double* G, double* Vst, int n, int r, int nev, double* sig, double* Xout, long long* clk, hipStream_t stream);
-int ttn_wg512_selftest_gemm(int m, int n, int k, double* A, double* B, double* C, double alpha, double beta, int ta, int tb, hipStream_t stream);
-int ttn_wg512_selftest_syrk2(int p1, int q1, double* A1, double* G1, double alpha1, int ta1, int p2, int q2, double* A2, double* G2, double alpha2, int ta2,
-                             int pair, hipStream_t stream);
-int ttn_wg512_selftest_gemm_ra2(int m1, int n1, int k1, double* A1, double* B1, double* C1, double alpha1, int f1,
-                                int m2, int n2, int k2, double* A2, double* B2, double* C2, double alpha2, int f2, int pair, hipStream_t stream);
-}
+// the 512-thread build of k_compress and its building blocks (ttn_wg512.hip: two workgroups per CU), declared once for both units
+#include "ttn_wg512.h"
 
 extern "C" {
-
-// r_and_d_to_rks with Julia's wrapping Int64 products (src/tt_tools.jl:407-425)
-static int64_t wrap_prod(const int64_t* v, int64_t lo, int64_t hi) {  // product of v[lo..hi)
-    uint64_t p = 1;
-    for (int64_t i = lo; i < hi; ++i) p *= (uint64_t)v[i];
-    return (int64_t)p;
-}
-int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int64_t* rks, int64_t rmax, int64_t* out) {
-    if (!dims || !rks || !out || d < 0 || n_rks < 0) return fail(TTN_ERR_ARG, "bad argument");
-    for (int64_t i = 0; i < n_rks; ++i) out[i] = 1;
-    for (int64_t i = 0; i < d && i < n_rks; ++i) {
-        const int64_t q = wrap_prod(dims, i, d), p = wrap_prod(dims, 0, i);
-        int64_t v = rks[i];
-        if (q > 0) {
-            if (p > 0) v = std::min(std::min(v, p), std::min(q, rmax));
-            else v = std::min(v, std::min(q, rmax));
-        } else {
-            if (p > 0) v = std::min(v, std::min(p, rmax));
-            else v = std::min(v, rmax);
-        }
-        out[i] = v;
-    }
-    return TTN_OK;
-}
-
-// ---- ttn_tt ---------------------------------------------------------------------------------------
-static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out, int el);
-int ttn_tt_create(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out) { return tt_create_impl(d, dims, cap_rks, batch, out, 1); }
-int ttn_tt_create_c64(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out) { return tt_create_impl(d, dims, cap_rks, batch, out, 2); }
-int ttn_tt_dtype(ttn_tt_t h, int* cplx) {
-    if (!h || !cplx) return fail(TTN_ERR_ARG, "null pointer");
-    *cplx = h->el == 2 ? 1 : 0;
-    return TTN_OK;
-}
-int ttn_tto_dtype(ttn_tto_t h, int* cplx) {
-    if (!h || !cplx) return fail(TTN_ERR_ARG, "null pointer");
-    *cplx = h->el == 2 ? 1 : 0;
-    return TTN_OK;
-}
-static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks, int64_t batch, ttn_tt_t* out, int el) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!dims || !cap_rks || !out || d < 1 || batch < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: bad argument");
-    for (int64_t k = 0; k < d; ++k) if (dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: dims must be >= 1");
-    for (int64_t k = 0; k <= d; ++k) if (cap_rks[k] < 1) return fail(TTN_ERR_ARG, "ttn_tt_create: ranks must be >= 1");
-    OwnedTT own;
-    ttn_tt_s* h = own.h = new ttn_tt_s();
-    h->d = (int)d; h->batch = (int)batch; h->el = el;
-    h->dims.assign(dims, dims + d);
-    h->cap.assign(cap_rks, cap_rks + d + 1);
-    h->bound.assign(d + 1, 1);          // every train starts as the rank-1 zero train
-    h->off.resize(d + 1);
-    long long o = 0;
-    for (int64_t k = 0; k < d; ++k) {
-        h->off[k] = o;
-        long long sz = (long long)el * dims[k] * cap_rks[k] * cap_rks[k + 1];
-        sz = (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
-        o += sz;
-    }
-    h->off[d] = o;
-    h->stride = o;
-    h->ot.assign((size_t)batch * d, 0);
-    std::vector<int> idims(d);
-    for (int64_t k = 0; k < d; ++k) idims[k] = (int)(el * dims[k]);
-    std::vector<long long> cap64(cap_rks, cap_rks + d + 1);
-    std::vector<long long> rk0((size_t)batch * (d + 1));
-    for (int64_t b = 0; b < batch; ++b) for (int64_t m = 0; m <= d; ++m) rk0[b * (d + 1) + m] = 1;
-    hipError_t e;
-    if ((e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)o * batch)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_off, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_cap, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (size_t)batch * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * d)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_status, sizeof(int) * 2 * (size_t)batch)) != hipSuccess)
-        return hipfail(e, "hipMalloc(ttn_tt)");
-    HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_cap, cap64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_rks, rk0.data(), sizeof(long long) * rk0.size(), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * d, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemsetAsync(h->d_data, 0, sizeof(double) * (size_t)o * batch, g_stream));
-    HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int) * 2 * (size_t)batch, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    g_live.insert(h);
-    *out = own.release();
-    return TTN_OK;
-}
-
-int ttn_tt_free(ttn_tt_t h) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!h) return TTN_OK;
-    const bool was_live = g_live.erase(h) > 0;
-    if (g_init && was_live && h->d_status) {
-        // a failure recorded on this handle that nobody has queried survives the handle (ttn_status_all)
-        hipLaunchKernelGGL(k_fold_status, dim3(1), dim3(64), 0, g_stream, (const int*)h->d_status, h->batch, g_pending_status.as<unsigned>());
-    }
-    if (g_init) hipStreamSynchronize(g_stream);
-    if (h->d_data) hipFree(h->d_data);
-    if (h->d_off) hipFree(h->d_off);
-    if (h->d_cap) hipFree(h->d_cap);
-    if (h->d_rks) hipFree(h->d_rks);
-    if (h->d_dims) hipFree(h->d_dims);
-    if (h->d_sv) hipFree(h->d_sv);
-    if (h->d_status) hipFree(h->d_status);
-    delete h;
-    return TTN_OK;
-}
-
-int ttn_tt_batch(ttn_tt_t h, int64_t* batch) {
-    if (!h || !batch) return fail(TTN_ERR_ARG, "null pointer");
-    *batch = h->batch;
-    return TTN_OK;
-}
-
-int ttn_tt_upload(ttn_tt_t h, int64_t b, const double* const* cores, const int64_t* rks, const int64_t* ot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!h || !cores || !rks || b < 0 || b >= h->batch) return fail(TTN_ERR_ARG, "ttn_tt_upload: bad argument");
-    const int d = h->d;
-    for (int m = 0; m <= d; ++m) {
-        if (rks[m] < 1) return fail(TTN_ERR_ARG, "ttn_tt_upload: ranks must be >= 1");
-        if (rks[m] > h->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_tt_upload: rank exceeds the handle's capacity");
-    }
-    std::vector<long long> r64(rks, rks + d + 1);
-    HIPCHK(hipMemcpyAsync(h->d_rks + (size_t)b * (d + 1), r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    for (int k = 0; k < d; ++k) {
-        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tt_upload: null core");
-        const size_t sz = (size_t)h->el * h->dims[k] * rks[k] * rks[k + 1];
-        HIPCHK(hipMemcpyAsync(h->d_data + (size_t)b * h->stride + h->off[k], cores[k], sizeof(double) * sz, hipMemcpyHostToDevice, g_stream));
-    }
-    HIPCHK(hipStreamSynchronize(g_stream));   // host buffers may be released by the caller
-    for (int k = 0; k < d; ++k) h->ot[(size_t)b * d + k] = ot ? ot[k] : 0;
-    // host-side upper bound on the current ranks of any train of the batch
-    for (int m = 0; m <= d; ++m) h->bound[m] = (h->batch == 1) ? rks[m] : std::max<int64_t>(h->bound[m], rks[m]);
-    return TTN_OK;
-}
-
-int ttn_tt_replicate(ttn_tt_t h, int64_t src_b) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!h || src_b < 0 || src_b >= h->batch) return fail(TTN_ERR_ARG, "ttn_tt_replicate: bad argument");
-    if (h->batch > 1) {
-        dim3 grid((unsigned)std::min<long long>((h->stride + TTN_STREAM_TB - 1) / TTN_STREAM_TB, 1024), (unsigned)h->batch);
-        hipLaunchKernelGGL(k_replicate, grid, dim3(TTN_STREAM_TB), 0, g_stream, h->dev(), (int)src_b);
-        HIPCHK(hipGetLastError());
-    }
-    for (int b = 0; b < h->batch; ++b)
-        for (int k = 0; k < h->d; ++k) h->ot[(size_t)b * h->d + k] = h->ot[(size_t)src_b * h->d + k];
-    return TTN_OK;
-}
-
-int ttn_tt_ranks(ttn_tt_t h, int64_t b, int64_t* rks, int64_t* ot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!h || b < 0 || b >= h->batch) return fail(TTN_ERR_ARG, "ttn_tt_ranks: bad argument");
-    const int d = h->d;
-    if (rks) {
-        std::vector<long long> r64(d + 1);
-        HIPCHK(hipMemcpyAsync(r64.data(), h->d_rks + (size_t)b * (d + 1), sizeof(long long) * (d + 1), hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        for (int m = 0; m <= d; ++m) rks[m] = r64[m];
-    }
-    if (ot) for (int k = 0; k < d; ++k) ot[k] = h->ot[(size_t)b * d + k];
-    return TTN_OK;
-}
-
-int ttn_tt_max_ranks(ttn_tt_t h, int64_t* bound) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!h) return fail(TTN_ERR_ARG, "null handle");
-    const int d = h->d;
-    std::vector<long long> r64((size_t)h->batch * (d + 1));
-    HIPCHK(hipMemcpyAsync(r64.data(), h->d_rks, sizeof(long long) * r64.size(), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int m = 0; m <= d; ++m) {
-        long long mx = 1;
-        for (int b = 0; b < h->batch; ++b) mx = std::max(mx, r64[(size_t)b * (d + 1) + m]);
-        h->bound[m] = mx;
-        if (bound) bound[m] = mx;
-    }
-    return TTN_OK;
-}
-
-int ttn_tt_download(ttn_tt_t h, int64_t b, double* const* cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!h || !cores || b < 0 || b >= h->batch) return fail(TTN_ERR_ARG, "ttn_tt_download: bad argument");
-    const int d = h->d;
-    std::vector<long long> r64(d + 1);
-    HIPCHK(hipMemcpyAsync(r64.data(), h->d_rks + (size_t)b * (d + 1), sizeof(long long) * (d + 1), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    for (int k = 0; k < d; ++k) {
-        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tt_download: null core");
-        const size_t sz = (size_t)h->el * h->dims[k] * r64[k] * r64[k + 1];
-        HIPCHK(hipMemcpyAsync(cores[k], h->d_data + (size_t)b * h->stride + h->off[k], sizeof(double) * sz, hipMemcpyDeviceToHost, g_stream));
-    }
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
-int ttn_tt_copy(ttn_tt_t dst, ttn_tt_t src) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!dst || !src) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(dst->dims, src->dims) || dst->batch != src->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (dst->el != src->el) return refuse_mixed("ttn_tt_copy");
-    for (int m = 0; m <= src->d; ++m) if (dst->cap[m] < src->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_tt_copy: destination capacity too small");
-    // scale kernel with a = 1 on core -1 is a plain per-core copy that honours the two slot layouts
-    const int d = src->d;
-    long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)src->el * src->dims[k] * src->bound[k] * src->bound[k + 1]);
-    hipLaunchKernelGGL(k_ranks_copy, dim3(src->batch), dim3(64), 0, g_stream, dst->dev(), src->dev());
-    dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((maxsz + TTN_STREAM_TB - 1) / TTN_STREAM_TB, 2048)), (unsigned)d, (unsigned)src->batch);
-    hipLaunchKernelGGL(k_scale, grid, dim3(TTN_STREAM_TB), 0, g_stream, src->dev(), dst->dev(), 1.0, -1, 0, (const int*)nullptr);
-    HIPCHK(hipGetLastError());
-    dst->bound = src->bound;
-    dst->ot = src->ot;
-    return TTN_OK;
-}
-
-// ---- ttn_tto --------------------------------------------------------------------------------------
-// k_apply / k_hadamard / k_add count the fibres (p, q) of a core with 32-bit indices (ttn_stream_kernels.h): refuse larger cores here
-static bool stream_fibres_too_many(long long fibres) { return fibres >= (1LL << 31); }
-
-// The one place that lays out and allocates an operator handle: slots, device tables and, with `cores`, their upload.  A ttn_tto is
-// immutable and its ranks are host-known, so every operation of the operator algebra allocates its result here (`who`: its name) with
-// the cores left uninitialised: an output core beyond the 32-bit fibre indices of the streaming kernels is refused, and a result the
-// device cannot hold is TTN_ERR_CAPACITY (nothing is launched).  ttn_tto_create passes no `who` and reports the HIP error itself.
-static int tto_alloc(const char* who, int el, int64_t d, const int64_t* dims, const int64_t* rks, const int64_t* ot, const double* const* cores,
-                     OwnedTTO& out, int64_t batch = 1 /* operators of these dims and ranks; cores: [batch * d] */) {
-    if (who)
-        for (int64_t k = 0; k < d; ++k)
-            if (stream_fibres_too_many((long long)rks[k] * rks[k + 1]))
-                return fail(TTN_ERR_UNSUPPORTED, (std::string(who) + ": 2^31 or more fibres in one output core (32-bit element indices)").c_str());
-    ttn_tto_s* h = out.h = new ttn_tto_s();
-    h->d = (int)d; h->el = el; h->batch = (int)batch;
-    h->dims.assign(dims, dims + d);
-    h->rks.assign(rks, rks + d + 1);
-    h->ot.assign(d, 0);
-    if (ot) h->ot.assign(ot, ot + d);
-    h->off.resize(d + 1);
-    long long o = 0;
-    for (int64_t k = 0; k < d; ++k) {
-        h->off[k] = o;
-        const long long sz = (long long)el * dims[k] * dims[k] * rks[k] * rks[k + 1];
-        o += (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
-    }
-    h->off[d] = o;
-    h->stride = o;
-    std::vector<int> idims(2 * d);
-    for (int64_t k = 0; k < d; ++k) { idims[k] = (int)dims[k]; idims[d + k] = (int)(el * dims[k] * dims[k]); }
-    std::vector<long long> r64(rks, rks + d + 1);
-    hipError_t e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1) * (size_t)batch);
-    if (e != hipSuccess && who) {
-        (void)hipGetLastError();
-        h->d_data = nullptr;
-        return fail(TTN_ERR_CAPACITY, (std::string(who) + ": the result does not fit in device memory").c_str());
-    }
-    if (e != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_off, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (d + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * d)) != hipSuccess)
-        return hipfail(e, "hipMalloc(ttn_tto)");
-    h->d_dims2 = h->d_dims + d;
-    std::vector<double> flat;                           // the cores at their slots, the rounding gaps zero
-    if (cores) {
-        flat.assign((size_t)o * (size_t)batch, 0.0);
-        for (int64_t b = 0; b < batch; ++b)
-            for (int64_t k = 0; k < d; ++k)
-                std::memcpy(flat.data() + (size_t)b * (size_t)o + h->off[k], cores[b * d + k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);
-        HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * flat.size(), hipMemcpyHostToDevice, g_stream));
-    }
-    HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * d, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));          // the tables and `flat` are locals, `cores` is caller memory
-    return TTN_OK;
-}
-
-static int tto_create_impl(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out, int el) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!dims || !rks || !cores || !out || d < 1) return fail(TTN_ERR_ARG, "ttn_tto_create: bad argument");
-    for (int64_t k = 0; k < d; ++k) if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_create: null core");
-    OwnedTTO A;
-    const int rc = tto_alloc(nullptr, el, d, dims, rks, nullptr, cores, A);
-    if (rc) return rc;
-    *out = A.release();
-    return TTN_OK;
-}
-int ttn_tto_create(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 1); }
-int ttn_tto_create_c64(int64_t d, const int64_t* dims, const int64_t* rks, const double* const* cores, ttn_tto_t* out) { return tto_create_impl(d, dims, rks, cores, out, 2); }
-
-int ttn_tto_free(ttn_tto_t h) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!h) return TTN_OK;
-    if (g_init) hipStreamSynchronize(g_stream);
-    if (h->d_data) hipFree(h->d_data);
-    if (h->d_off) hipFree(h->d_off);
-    if (h->d_rks) hipFree(h->d_rks);
-    if (h->d_dims) hipFree(h->d_dims);
-    delete h;
-    return TTN_OK;
-}
-
-// ---- streaming ops --------------------------------------------------------------------------------
-static dim3 stream_grid(long long max_items, int d, int batch) {
-    long long gx = (max_items + TTN_STREAM_TB - 1) / TTN_STREAM_TB;
-    gx = std::max<long long>(1, std::min<long long>(gx, 4096));
-    return dim3((unsigned)gx, (unsigned)d, (unsigned)batch);
-}
-
-// The two steps every form of A * x shares (ttn_apply, ttn_apply_compress, ttn_apply_begin).  apply_capacity: y can hold the product's
-// ranks A.rks .* x.rks.  apply_ranks: y receives them, on the device and as host bounds, with the gauge flags of zeros_tt
-// (tt_operations.jl:103).
-static int apply_capacity(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
-    for (int m = 0; m <= x->d; ++m) if (y->cap[m] < A->rks[m] * x->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply: destination capacity too small");
-    return TTN_OK;
-}
-static int apply_ranks(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
-    hipLaunchKernelGGL(k_ranks_mul_op, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
-    HIPCHK(hipGetLastError());
-    for (int m = 0; m <= x->d; ++m) y->bound[m] = A->rks[m] * x->bound[m];
-    std::fill(y->ot.begin(), y->ot.end(), 0);
-    return TTN_OK;
-}
-
-// Float64 operator and trains: k_apply.  A complex operator and / or a complex train into a complex y: k_zapply.
-int ttn_apply(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (x == y) return fail(TTN_ERR_ARG, "ttn_apply: output must not alias the input");
-    if (int rb = op_batch_fits(A, x->batch)) return rb;
-    const bool cplx = A->el == 2 || x->el == 2 || y->el == 2;
-    if (cplx) { if (int rb = single_op(A, "ttn_apply (ComplexF64)")) return rb; }
-    if (cplx && y->el != 2) return refuse_mixed("ttn_apply (a complex operand needs a ComplexF64 output handle)");
-    if (cplx && A->el != 2 && x->el != 2) return refuse_mixed("ttn_apply (a ComplexF64 output needs a complex operator or train)");
-    const int d = x->d;
-    int rc = apply_capacity(A, x, y);
-    if (rc) return rc;
-    const dim3 tb(TTN_STREAM_TB);
-    if (cplx) {
-        long long items = 1;
-        for (int k = 0; k < d; ++k) {
-            const long long P = (long long)A->rks[k] * x->bound[k], Q = (long long)A->rks[k + 1] * x->bound[k + 1];
-            if (stream_fibres_too_many(P * Q)) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
-            items = std::max(items, P * ((Q + TTN_ZAPPLY_K - 1) / TTN_ZAPPLY_K));
-        }
-        if ((rc = apply_ranks(A, x, y))) return rc;
-        const dim3 grid = stream_grid(items, d, x->batch);
-        if (A->el == 2 && x->el == 2) hipLaunchKernelGGL((k_zapply<true, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
-        else if (A->el == 2) hipLaunchKernelGGL((k_zapply<true, false>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
-        else hipLaunchKernelGGL((k_zapply<false, true>), grid, tb, 0, g_stream, A->dev(), x->dev(), y->dev());
-    } else {
-        long long maxfib = 0;
-        for (int k = 0; k < d; ++k) maxfib = std::max<long long>(maxfib, (long long)x->bound[k] * x->bound[k + 1]);
-        if (stream_fibres_too_many(maxfib * std::max<long long>(1, A->rks[0]))) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one core (32-bit element indices)");
-        for (int k = 0; k < d; ++k) if (stream_fibres_too_many((long long)y->cap[k] * y->cap[k + 1])) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply: 2^31 or more fibres in one output core (32-bit element indices)");
-        if ((rc = apply_ranks(A, x, y))) return rc;
-        // LDS of k_apply: the largest operator core (if it fits TTN_APPLY_LDS_DOUBLES) + the store-transpose buffer for the largest left rank
-        long long amax_ = 0, rlmax_ = 1;
-        for (int k = 0; k < d; ++k) { amax_ = std::max<long long>(amax_, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]); rlmax_ = std::max<long long>(rlmax_, A->rks[k]); }
-        const int lds_a = amax_ <= TTN_APPLY_LDS_DOUBLES ? (int)amax_ : 0;
-        const int lds_rl = rlmax_ <= TTN_APPLY_MAX_RL ? (int)rlmax_ : 0;
-        const size_t apply_lds = sizeof(double) * (size_t)((lds_a + 1) & ~1) + sizeof(double) * 2 * (size_t)(TTN_STREAM_TB / 64) * lds_rl * 64;
-        // grid: output rows x groups of TTN_APPLY_K output columns when every site has n = 2 and the operator cores fit the LDS (the mapping
-        // of k_apply's fast path), input fibres otherwise
-        long long apply_items = maxfib;
-        {
-            bool qtt = lds_a > 0;
-            for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
-            if (qtt) {
-                apply_items = 0;
-                for (int k = 0; k < d; ++k)
-                    apply_items = std::max<long long>(apply_items, (long long)A->rks[k] * x->bound[k] * (((long long)A->rks[k + 1] * x->bound[k + 1] + TTN_APPLY_K - 1) / TTN_APPLY_K));
-            }
-        }
-        hipLaunchKernelGGL(k_apply, stream_grid(apply_items, d, x->batch), tb, apply_lds, g_stream, A->dev(), x->dev(), y->dev(), lds_a, lds_rl);
-    }
-    HIPCHK(hipGetLastError());
-    return TTN_OK;
-}
-
-// ---- rectangular operators (csrc/ttn_rect_kernels.h) ------------------------------------------------------------------------------
-int ttn_rtto_create(int64_t M, const int64_t* out_dims, const int64_t* in_dims, const int64_t* rks, const double* const* cores, ttn_rtto_t* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!out_dims || !in_dims || !rks || !cores || !out || M < 1 || M > TTN_MAX_D) return fail(TTN_ERR_ARG, "ttn_rtto_create: bad argument");
-    for (int64_t k = 0; k < M; ++k) {
-        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_rtto_create: null core");
-        if (out_dims[k] < 1 || in_dims[k] < 1) return fail(TTN_ERR_ARG, "ttn_rtto_create: dims must be >= 1");
-    }
-    for (int64_t k = 0; k <= M; ++k) if (rks[k] < 1) return fail(TTN_ERR_ARG, "ttn_rtto_create: ranks must be >= 1");
-    OwnedRTTO own;
-    ttn_rtto_s* h = own.h = new ttn_rtto_s();
-    h->d = (int)M;
-    h->odims.assign(out_dims, out_dims + M);
-    h->idims.assign(in_dims, in_dims + M);
-    h->rks.assign(rks, rks + M + 1);
-    h->off.resize(M + 1);
-    long long o = 0;
-    for (int64_t k = 0; k < M; ++k) {
-        h->off[k] = o;
-        if (in_dims[k] == 1) h->singles.push_back((int)k);
-        const long long sz = (long long)out_dims[k] * in_dims[k] * rks[k] * rks[k + 1];
-        o += (sz + 1) & ~1LL;      // keep every slot 16-byte aligned
-    }
-    h->off[M] = o;
-    std::vector<int> idims(2 * M);
-    for (int64_t k = 0; k < M; ++k) { idims[k] = (int)out_dims[k]; idims[M + k] = (int)in_dims[k]; }
-    std::vector<long long> r64(rks, rks + M + 1);
-    std::vector<double> flat((size_t)o, 0.0);                           // the cores at their slots, the rounding gaps zero
-    for (int64_t k = 0; k < M; ++k) std::memcpy(flat.data() + h->off[k], cores[k], sizeof(double) * (size_t)out_dims[k] * in_dims[k] * rks[k] * rks[k + 1]);
-    hipError_t e;
-    if ((e = hipMalloc((void**)&h->d_data, sizeof(double) * (size_t)o)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_off, sizeof(long long) * (M + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_rks, sizeof(long long) * (M + 1))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_dims, sizeof(int) * 2 * M)) != hipSuccess)
-        return hipfail(e, "hipMalloc(ttn_rtto)");
-    HIPCHK(hipMemcpyAsync(h->d_data, flat.data(), sizeof(double) * (size_t)o, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_off, h->off.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_rks, r64.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * 2 * M, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));          // the tables and `flat` are locals, `cores` is caller memory
-    *out = own.release();
-    return TTN_OK;
-}
-
-int ttn_rtto_free(ttn_rtto_t h) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!h) return TTN_OK;
-    if (g_init) hipStreamSynchronize(g_stream);
-    if (h->d_data) hipFree(h->d_data);
-    if (h->d_off) hipFree(h->d_off);
-    if (h->d_rks) hipFree(h->d_rks);
-    if (h->d_dims) hipFree(h->d_dims);
-    delete h;
-    return TTN_OK;
-}
-
-int ttn_rtto_ranks(ttn_rtto_t h, int64_t* M, int64_t* out_dims, int64_t* in_dims, int64_t* rks) {
-    if (!h) return fail(TTN_ERR_ARG, "null handle");
-    if (M) *M = h->d;
-    for (int k = 0; k < h->d; ++k) { if (out_dims) out_dims[k] = h->odims[k]; if (in_dims) in_dims[k] = h->idims[k]; }
-    if (rks) for (int m = 0; m <= h->d; ++m) rks[m] = h->rks[m];
-    return TTN_OK;
-}
-
-// y = A * x for a rectangular A (src/tt_operations.jl:116-148).  Every check runs before y is touched.
-int ttn_apply_rect(ttn_rtto_t A, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_rect: output must not alias the input");
-    F64_ONLY("ttn_apply_rect", {x, y});
-    const int M = A->d, N = x->d;
-    if (M != N + 1) return fail(TTN_ERR_DIMS, "Rectangular TToperator must have one additional output site");
-    if (A->singles.size() != 1) return fail(TTN_ERR_DIMS, "Rectangular TToperator must have exactly one singleton input site");
-    const int s = A->singles[0];
-    for (int k = 0; k < N; ++k) if (A->idims[k < s ? k : k + 1] != x->dims[k]) return fail(TTN_ERR_DIMS, "Incompatible input dimensions");
-    if (x->bound[N] != 1) return fail(TTN_ERR_DIMS, "Input TTvector must have a closed right boundary rank");
-    if (y->d != M || !same_dims(A->odims, y->dims)) return fail(TTN_ERR_DIMS, "ttn_apply_rect: the destination's dimensions are not the operator's output dimensions");
-    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    std::vector<int64_t> yb(M + 1);
-    for (int m = 0; m <= M; ++m) yb[m] = A->rks[m] * x->bound[m > s ? m - 1 : m];
-    for (int m = 0; m <= M; ++m) if (y->cap[m] < yb[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply_rect: destination capacity too small");
-    for (int k = 0; k < M; ++k)
-        if (stream_fibres_too_many((long long)y->cap[k] * y->cap[k + 1])) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_rect: 2^31 or more fibres in one output core (32-bit element indices)");
-    // LDS: the largest operator core that takes the n_out = 2 mapping and fits TTN_APPLY_LDS_DOUBLES; grid: the most items of any site
-    long long lds_a = 0, items = 1;
-    for (int k = 0; k < M; ++k) {
-        const long long asz = (long long)A->odims[k] * A->idims[k] * A->rks[k] * A->rks[k + 1];
-        const bool fast = A->odims[k] == 2 && A->idims[k] == (k == s ? 1 : 2) && asz <= TTN_APPLY_LDS_DOUBLES;
-        if (fast) lds_a = std::max<long long>(lds_a, asz);
-        items = std::max<long long>(items, fast ? yb[k] * ((yb[k + 1] + TTN_RECT_K - 1) / TTN_RECT_K) : yb[k] * yb[k + 1]);
-    }
-    hipLaunchKernelGGL(k_ranks_mul_rect, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), A->dev(), x->dev());
-    HIPCHK(hipGetLastError());
-    y->bound = yb;
-    std::fill(y->ot.begin(), y->ot.end(), 0);
-    hipLaunchKernelGGL(k_apply_rect, stream_grid(items, M, x->batch), dim3(TTN_STREAM_TB), sizeof(double) * (size_t)((lds_a + 1) & ~1LL), g_stream,
-                       A->dev(), x->dev(), y->dev(), (int)lds_a);
-    HIPCHK(hipGetLastError());
-    return TTN_OK;
-}
-
-int ttn_hadamard(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible TT dimensions");
-    if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_hadamard: output must not alias an input");
-    if (x->el != y->el || x->el != z->el) return refuse_mixed("ttn_hadamard");
-    const int d = x->d;
-    long long maxpq = 0;
-    for (int m = 0; m <= d; ++m) if (z->cap[m] < x->bound[m] * y->bound[m]) return fail(TTN_ERR_CAPACITY, "ttn_hadamard: destination capacity too small");
-    for (int k = 0; k < d; ++k) maxpq = std::max<long long>(maxpq, (long long)x->bound[k] * y->bound[k] * x->bound[k + 1] * y->bound[k + 1]);
-    if (stream_fibres_too_many(maxpq)) return fail(TTN_ERR_UNSUPPORTED, "ttn_hadamard: 2^31 or more fibres in one core (32-bit element indices)");
-    hipLaunchKernelGGL(k_ranks_mul, dim3(x->batch), dim3(64), 0, g_stream, z->dev(), x->dev(), y->dev());
-    bool qtt = true;
-    for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
-    if (x->el == 2) hipLaunchKernelGGL(k_zhadamard, stream_grid((maxpq + TTN_ZHAD_K - 1) / TTN_ZHAD_K, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), z->dev());
-    else
-    hipLaunchKernelGGL(k_hadamard, stream_grid(qtt ? (maxpq + TTN_HAD_K - 1) / TTN_HAD_K : maxpq, d, x->batch), dim3(TTN_STREAM_TB), 0, g_stream, x->dev(), y->dev(), z->dev());
-    HIPCHK(hipGetLastError());
-    for (int m = 0; m <= d; ++m) z->bound[m] = x->bound[m] * y->bound[m];
-    std::fill(z->ot.begin(), z->ot.end(), 0);
-    return TTN_OK;
-}
-
-// The largest number of fibres r_k r_{k+1} of a core with ranks r, and the k_add launch z = x + y for result ranks zr.  n2: every
-// physical dimension of the trains as k_add reads them is 2 (its mapping of TTN_ADD_K fibres per thread), one fibre per thread otherwise.
-static long long max_fibres(const std::vector<int64_t>& r) {
-    long long m = 0;
-    for (size_t k = 0; k + 1 < r.size(); ++k) m = std::max<long long>(m, (long long)r[k] * r[k + 1]);
-    return m;
-}
-static void launch_add(const TTDev& x, const TTDev& y, const TTDev& z, const std::vector<int64_t>& zr, bool n2, int batch) {
-    const long long maxpq = max_fibres(zr);
-    hipLaunchKernelGGL(k_add, stream_grid(n2 ? (maxpq + TTN_ADD_K - 1) / TTN_ADD_K : maxpq, (int)zr.size() - 1, batch), dim3(TTN_STREAM_TB), 0, g_stream, x, y, z);
-}
-
-int ttn_add(ttn_tt_t x, ttn_tt_t y, ttn_tt_t z) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_add: output must not alias an input");
-    if (x->el != y->el || x->el != z->el) return refuse_mixed("ttn_add");
-    const int d = x->d;
-    if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: the reference's + is only defined for d >= 2");
-    std::vector<int64_t> zb(d + 1);
-    for (int m = 0; m <= d; ++m) zb[m] = (m == 0 || m == d) ? 1 : x->bound[m] + y->bound[m];
-    for (int m = 0; m <= d; ++m) if (z->cap[m] < zb[m]) return fail(TTN_ERR_CAPACITY, "ttn_add: destination capacity too small");
-    if (stream_fibres_too_many(max_fibres(zb))) return fail(TTN_ERR_UNSUPPORTED, "ttn_add: 2^31 or more fibres in one core (32-bit element indices)");
-    hipLaunchKernelGGL(k_ranks_add, dim3(x->batch), dim3(64), 0, g_stream, z->dev(), x->dev(), y->dev());
-    // (a complex core (n, r, r') is byte for byte the real core (2n, r, r') and + only copies: k_add runs on that view)
-    bool qtt = x->el == 1;
-    for (int k = 0; k < d; ++k) qtt = qtt && x->dims[k] == 2;
-    launch_add(x->dev(), y->dev(), z->dev(), zb, qtt, x->batch);
-    HIPCHK(hipGetLastError());
-    z->bound = zb;
-    std::fill(z->ot.begin(), z->ot.end(), 0);
-    return TTN_OK;
-}
-
-static DevBuf g_which;            // [batch] scaled core per train when the gauge flags differ (scaled_core)
-// The core scalar multiplication scales: the first one with ot == 0, else the first (tt_operations.jl:262).  Uniform over the batch
-// -> `which`; trains with different gauge flags (uploaded one by one, or zeroed by ttn_scale_batch) -> a per-train device table.
-// ot: [batch][d] gauge flags.
-static int scaled_core(const int64_t* ot, int d, int batch, int& which, const int*& which_b) {
-    std::vector<int> h_which(batch, 0);
-    bool uniform = true;
-    for (int b = 0; b < batch; ++b) {
-        for (int k = 0; k < d; ++k) if (ot[(size_t)b * d + k] == 0) { h_which[b] = k; break; }
-        uniform = uniform && h_which[b] == h_which[0];
-    }
-    which = h_which[0];
-    which_b = nullptr;
-    if (uniform) return TTN_OK;
-    const int rc = g_which.ensure(sizeof(int) * batch);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g_which.p, h_which.data(), sizeof(int) * batch, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));              // h_which is a local
-    which_b = g_which.as<int>();
-    return TTN_OK;
-}
-
-// The launch of y = a * x on trains of element type `el` (an operator passes its vector view): k_scale with the factor ar, k_scale_batch
-// with one factor per train (ab: device), k_zscale with the complex factor (ar, ai) or one per train (ab: device, interleaved).
-// dims / rks: physical dimensions (in elements) and rank bounds of x; zero: the one factor is 0.
-static void launch_scale(int el, int d, int batch, const int64_t* dims, const int64_t* rks, const TTDev& x, const TTDev& y, double ar, double ai,
-                         const double* ab, int which, const int* which_b, bool zero) {
-    long long maxsz = 0;
-    for (int k = 0; k < d; ++k) maxsz = std::max<long long>(maxsz, (long long)dims[k] * rks[k] * rks[k + 1]);
-    const dim3 tb(TTN_STREAM_TB);
-    if (el == 2) hipLaunchKernelGGL(k_zscale, stream_grid((maxsz + 3) / 4, d, batch), tb, 0, g_stream, x, y, ar, ai, which, zero ? 1 : 0, which_b, ab);
-    else if (ab) hipLaunchKernelGGL(k_scale_batch, stream_grid((maxsz + 7) / 8, d, batch), tb, 0, g_stream, x, y, ab, which, which_b);
-    else hipLaunchKernelGGL(k_scale, stream_grid((maxsz + 7) / 8, d, batch), tb, 0, g_stream, x, y, ar, which, zero ? 1 : 0, which_b);
-}
-
-// y = a * x on handles of one element type, behind every exported scale of a train.  The factor is (ar, ai) (ai: ComplexF64 only), or,
-// with a_b, one per train: `batch` host values of x's element type.
-static int scale_impl(const char* who, double ar, double ai, const double* a_b, ttn_tt_t x, ttn_tt_t y) {
-    const int d = x->d, el = x->el;
-    for (int m = 0; m <= d; ++m) if (y->cap[m] < x->bound[m]) return fail(TTN_ERR_CAPACITY, (std::string(who) + ": destination capacity too small").c_str());
-    if (a_b) {
-        const int rc = g_dout.ensure(sizeof(double) * el * x->batch);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(g_dout.p, a_b, sizeof(double) * el * x->batch, hipMemcpyHostToDevice, g_stream));
-    }
-    // i = findfirst(==(0), ot), else 1  (tt_operations.jl:262), per train
-    int which = 0;
-    const int* which_b = nullptr;
-    { int rc_ = scaled_core(x->ot.data(), d, x->batch, which, which_b); if (rc_) return rc_; }
-    const bool zero = !a_b && ar == 0.0 && ai == 0.0;
-    if (x != y) hipLaunchKernelGGL(k_ranks_copy, dim3(x->batch), dim3(64), 0, g_stream, y->dev(), x->dev());
-    launch_scale(el, d, x->batch, x->dims.data(), x->bound.data(), x->dev(), y->dev(), ar, ai, a_b ? g_dout.as<const double>() : nullptr, which, which_b, zero);
-    HIPCHK(hipGetLastError());
-    if (a_b) HIPCHK(hipStreamSynchronize(g_stream));      // `a_b` is caller memory and g_dout is reused by ttn_dot
-    y->bound = x->bound;
-    if (zero) std::fill(y->ot.begin(), y->ot.end(), 0); else y->ot = x->ot;
-    if (a_b)
-        for (int b = 0; b < x->batch; ++b) {
-            bool zero_b = true;
-            for (int c = 0; c < el; ++c) zero_b = zero_b && a_b[(size_t)el * b + c] == 0.0;
-            if (zero_b) for (int k = 0; k < d; ++k) y->ot[(size_t)b * d + k] = 0;
-        }
-    return TTN_OK;
-}
-
-int ttn_scale_c64(double re, double im, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->el != 2 || y->el != 2) return refuse_mixed("ttn_scale_c64 (both handles must be ComplexF64)");
-    return scale_impl("ttn_scale_c64", re, im, nullptr, x, y);
-}
-
-int ttn_scale_batch_c64(const double* a, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!a || !x || !y) return fail(TTN_ERR_ARG, "null pointer");
-    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->el != 2 || y->el != 2) return refuse_mixed("ttn_scale_batch_c64 (both handles must be ComplexF64)");
-    return scale_impl("ttn_scale_batch_c64", 0.0, 0.0, a, x, y);
-}
-
-int ttn_scale(double a, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->el != y->el) return refuse_mixed("ttn_scale");
-    return scale_impl("ttn_scale", a, 0.0, nullptr, x, y);
-}
-
-int ttn_scale_batch(const double* a, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!a || !x || !y) return fail(TTN_ERR_ARG, "null pointer");
-    if (!same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    F64_ONLY("ttn_scale_batch (ComplexF64 handles: ttn_scale_batch_c64)", {x, y});
-    return scale_impl("ttn_scale_batch", 0.0, 0.0, a, x, y);
-}
-
-static DevBuf g_grad_coef;        // [2][batch] doubles: Delta of ttn_dot_pullback, alpha and beta of ttn_tt_cores_axpby
-// z = alpha x + beta (A y) (include/ttn_step.h): k_apply_axpby, one launch for ttn_apply -> ttn_scale_batch x 2 -> ttn_add.  Factors that
-// are the same for every train travel as kernel arguments; only a pair that differs over the batch is uploaded (and waited for).
-int ttn_apply_axpby(const double* alpha, ttn_tt_t x, const double* beta, ttn_tto_t A, ttn_tt_t y, ttn_tt_t z) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!A || !x || !y || !z) return fail(TTN_ERR_ARG, "null handle");
-    F64_ONLY("ttn_apply_axpby", {x, y, z}, {A});
-    if (!same_dims(A->dims, y->dims) || !same_dims(x->dims, y->dims) || !same_dims(x->dims, z->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->batch != y->batch || x->batch != z->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (z == x || z == y) return fail(TTN_ERR_ARG, "ttn_apply_axpby: output must not alias an input");
-    if (int rb = op_batch_fits(A, x->batch)) return rb;
-    const int d = x->d, batch = x->batch;
-    if (d < 2) return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_axpby: the reference's + is only defined for d >= 2");
-    std::vector<int64_t> zb(d + 1);
-    for (int m = 0; m <= d; ++m) zb[m] = (m == 0 || m == d) ? 1 : x->bound[m] + A->rks[m] * y->bound[m];
-    for (int m = 0; m <= d; ++m) if (z->cap[m] < zb[m]) return fail(TTN_ERR_CAPACITY, "ttn_apply_axpby: destination capacity too small");
-    long long maxfib = 0;
-    for (int k = 0; k < d; ++k) maxfib = std::max<long long>(maxfib, (long long)y->bound[k] * y->bound[k + 1]);
-    if (stream_fibres_too_many(maxfib * std::max<long long>(1, A->rks[0])) || stream_fibres_too_many(max_fibres(zb)))
-        return fail(TTN_ERR_UNSUPPORTED, "ttn_apply_axpby: 2^31 or more fibres in one core (32-bit element indices)");
-    bool uniform = true;
-    for (int b = 1; b < batch; ++b) uniform = uniform && (!alpha || alpha[b] == alpha[0]) && (!beta || beta[b] == beta[0]);
-    const double* d_ab = nullptr;
-    if (!uniform) {
-        std::vector<double> ab(2 * (size_t)batch, 1.0);
-        for (int b = 0; b < batch; ++b) { if (alpha) ab[b] = alpha[b]; if (beta) ab[(size_t)batch + b] = beta[b]; }
-        const int rc = g_grad_coef.ensure(sizeof(double) * 2 * batch);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(g_grad_coef.p, ab.data(), sizeof(double) * 2 * batch, hipMemcpyHostToDevice, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));              // ab is a local
-        d_ab = g_grad_coef.as<const double>();
-    }
-    int which = 0;
-    const int* which_b = nullptr;
-    { const int rc = scaled_core(x->ot.data(), d, batch, which, which_b); if (rc) return rc; }
-    hipLaunchKernelGGL(k_ranks_axpby, dim3(batch), dim3(64), 0, g_stream, z->dev(), x->dev(), A->dev(), y->dev());
-    // LDS: the largest operator core, if it fits the bound of k_apply; grid: rows x groups of TTN_AXPBY_K columns on binary sites,
-    // fibres elsewhere
-    long long amax_ = 0, items = 1;
-    for (int k = 0; k < d; ++k) {
-        amax_ = std::max<long long>(amax_, (long long)A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1]);
-        items = std::max<long long>(items, x->dims[k] == 2 ? (long long)zb[k] * ((zb[k + 1] + TTN_AXPBY_K - 1) / TTN_AXPBY_K) : (long long)zb[k] * zb[k + 1]);
-    }
-    const int lds_a = amax_ <= TTN_APPLY_LDS_DOUBLES ? (int)amax_ : 0;
-    hipLaunchKernelGGL(k_apply_axpby, stream_grid(items, d, batch), dim3(TTN_STREAM_TB), sizeof(double) * (size_t)lds_a, g_stream, A->dev(), x->dev(), y->dev(),
-                       z->dev(), alpha ? alpha[0] : 1.0, beta ? beta[0] : 1.0, d_ab, which, which_b, lds_a);
-    HIPCHK(hipGetLastError());
-    z->bound = zb;
-    std::fill(z->ot.begin(), z->ot.end(), 0);
-    return TTN_OK;
-}
-
-// ---- dense ops ------------------------------------------------------------------------------------
-// Upper bounds on the ranks during / after tt_compress! (or one _tt_bond_truncate!).  The reference sets
-// r = min(length(s), max_bond) with length(s) = min(n_k r_{k-1}, n_{k+1} r_{k+1}) (tt_cross_interpolation.jl:152,164),
-// so a bond rank can GROW when it was below both of those (rank-deficient input).  need[m] = largest rank bond m can
-// take at any time (buffers / handle capacity must hold it), fin[m] = bound after the call.
-static void rank_bounds(int d, const int64_t* dims, const int64_t* rks, int64_t max_bond, int64_t sweeps, int64_t k_single,
-                        std::vector<int64_t>& need, std::vector<int64_t>& fin, long long& pmax, long long& qmax,
-                        int64_t k_first = 0, int64_t k_last = 0 /* 0-based bond range when k_single < 0 */) {
-    fin.assign(rks, rks + d + 1);
-    need = fin;
-    pmax = 1; qmax = 1;
-    auto stepk = [&](int k) {      // 0-based bond between cores k, k+1
-        const long long mr = dims[k] * fin[k], mc = dims[k + 1] * fin[k + 2];
-        const long long p = std::min(mr, mc), q = std::max(mr, mc);
-        pmax = std::max(pmax, p); qmax = std::max(qmax, q);
-        fin[k + 1] = std::min<long long>(p, max_bond);
-        need[k + 1] = std::max(need[k + 1], fin[k + 1]);
-    };
-    if (k_single > 0) { stepk((int)k_single - 1); return; }
-    if (k_single < 0) {
-        if (k_first <= k_last) { for (int64_t k = k_first; k <= k_last; ++k) stepk((int)k); }
-        else { for (int64_t k = k_first; k >= k_last; --k) stepk((int)k); }
-        return;
-    }
-    for (int64_t sw = 0; sw < sweeps; ++sw) {
-        for (int k = 0; k + 1 < d; ++k) stepk(k);
-        for (int k = d - 2; k >= 0; --k) stepk(k);
-    }
-}
-
-int ttn_compress_rank_bound(int64_t d, const int64_t* dims, const int64_t* rks, int64_t max_bond, int64_t sweeps, int64_t k,
-                            int64_t* need_out, int64_t* final_out) {
-    if (!dims || !rks || d < 1 || max_bond < 1 || sweeps < 1 || k < 0 || k > d - 1)
-        return fail(TTN_ERR_ARG, "bad argument");
-    std::vector<int64_t> need, fin;
-    long long pm, qm;
-    rank_bounds((int)d, dims, rks, max_bond, sweeps, k, need, fin, pm, qm);
-    for (int64_t m = 0; m <= d; ++m) { if (need_out) need_out[m] = need[m]; if (final_out) final_out[m] = fin[m]; }
-    return TTN_OK;
-}
-
-static DevBuf g_next_train;       // train counter of the persistent k_compress grid
-// Which build runs a compress launch, and on how many workgroup slots.  More trains than CUs: the 512-thread build on a PERSISTENT
-// grid of two workgroups per CU that pull trains from a counter (scratch per slot); otherwise one 1024-thread workgroup per train
-// (lowest latency for a single train).  TTN_WG512=1 / 0 forces / forbids the 512-thread build (diagnostics, parity tests).
-#define TTN_NUM_CUS 256
-static bool compress_use_wg512(int batch) {
-    const char* e = getenv("TTN_WG512");
-    if (e) return atoi(e) != 0;
-    return batch > TTN_NUM_CUS;
-}
-static int compress_slots(int batch) { return compress_use_wg512(batch) ? std::min(batch, 2 * TTN_NUM_CUS) : batch; }
-
-// Limits of k_zcompress (include/ttn.h): short side <= 512, long side <= 8192 complex
-#define TTN_ZC_PMAX 512
-#define TTN_ZC_QMAX 8192
-// Everything that can refuse a compress launch — capacity of the handle for the ranks the sweep can reach from `bound`, the size
-// limits of the merged matrices, the scratch allocation — checked WITHOUT touching the handle (ttn_apply_compress runs this on the
-// product's ranks before it overwrites y's).
-// The two element types differ in those limits and in the scratch of a train (per_train, in doubles).
-static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, int64_t k_single, int64_t max_bond, int64_t sweeps,
-                             int64_t k_first, int64_t k_last, std::vector<int64_t>& fin, long long& pmax, long long& qmax, long long& per_train) {
-    const int d = psi->d;
-    std::vector<int64_t> need;
-    pmax = 1; qmax = 1;
-    rank_bounds(d, psi->dims.data(), bound.data(), max_bond, sweeps, k_single, need, fin, pmax, qmax, k_first, k_last);
-    for (int m = 0; m <= d; ++m)
-        if (need[m] > psi->cap[m]) return fail(TTN_ERR_CAPACITY, "ttn_compress: a bond rank can grow beyond the handle's capacity (see ttn_compress_rank_bound)");
-    if (psi->el == 2) {                        // k_zcompress: one workgroup per train
-        if (pmax > TTN_ZC_PMAX || qmax > TTN_ZC_QMAX) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress (ComplexF64): merged matrix larger than 512 x 8192");
-        per_train = zcompress_scratch(pmax, qmax);
-        return g_scratch.ensure(sizeof(double) * (size_t)per_train * psi->batch);
-    }
-    if (pmax > 4096 || qmax > 16384) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress: merged matrix larger than 4096 x 16384");
-    per_train = 2 * pmax * qmax + QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64 + 6 * 128 * 128;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * compress_slots(psi->batch));
-    if (rc) return rc;
-    return g_dout.ensure(sizeof(double) * psi->batch);
-}
-
-static int launch_compress(ttn_tt_t psi, int64_t k_single, int64_t max_bond, double truncerr, int64_t sweeps,
-                           int64_t k_first = 0, int64_t k_last = 0, ttn_tto_t fuseA = nullptr, ttn_tt_t fusex = nullptr, int fused_first_real = 0) {
-    const int d = psi->d;
-    if (d < 2 && k_single == 0) return TTN_OK;
-    std::vector<int64_t> fin;
-    long long pmax = 1, qmax = 1, per_train = 0;
-    int rc = compress_precheck(psi, psi->bound, k_single, max_bond, sweeps, k_first, k_last, fin, pmax, qmax, per_train);
-    if (rc) return rc;
-    if (psi->el == 2) {                        // ComplexF64: k_zcompress (no fused merge, no singular-value capture, no 512-thread build)
-        ZCompressArgs P;
-        P.tt = psi->dev();
-        P.max_bond = max_bond; P.truncerr = truncerr; P.sweeps = (int)sweeps;
-        P.k_single = (int)k_single; P.k_first = (int)k_first; P.k_last = (int)k_last;
-        P.scratch = g_scratch.as<double>();
-        P.scratch_stride = per_train;
-        P.pmax = (int)pmax; P.qmax = (int)qmax;
-        P.status = psi->d_status;
-        P.sweep_stats = psi->d_status + psi->batch;
-        hipLaunchKernelGGL(k_zcompress, dim3(psi->batch), dim3(TTN_ZC_WG), TTN_ZC_LDS_BYTES, g_stream, P);
-        HIPCHK(hipGetLastError());
-        psi->bound = fin;
-        return TTN_OK;
-    }
-    const int steps = k_single > 0 ? 1 : (k_single < 0 ? (int)(std::llabs(k_last - k_first) + 1) : (int)(2 * (d - 1) * sweeps));
-    if (psi->sv_on) {
-        if (psi->sv_steps < steps || psi->sv_pmax < pmax) {
-            if (psi->d_sv) { HIPCHK(hipStreamSynchronize(g_stream)); HIPCHK(hipFree(psi->d_sv)); psi->d_sv = nullptr; }
-            HIPCHK(hipMalloc((void**)&psi->d_sv, sizeof(double) * (size_t)psi->batch * steps * pmax));
-        }
-        psi->sv_steps = steps;
-        psi->sv_pmax = (int)pmax;
-    }
-    CompressArgs P;
-    P.tt = psi->dev();
-    P.max_bond = max_bond;
-    P.truncerr = truncerr;
-    P.sweeps = (int)sweeps;
-    P.k_single = (int)k_single;
-    P.k_first = (int)k_first; P.k_last = (int)k_last;
-    P.scratch = g_scratch.as<double>();
-    P.scratch_stride = per_train;
-    P.pmax = (int)pmax; P.qmax = (int)qmax;
-    P.sv_out = psi->sv_on ? psi->d_sv : nullptr;
-    P.sv_steps = steps;
-    P.status = psi->d_status;
-    P.sweep_stats = psi->d_status + psi->batch;
-    P.rank_rule = 0;
-    P.fused = (fuseA && fusex) ? 1 : 0;
-    P.fused_first_real = fused_first_real;
-    if (P.fused) { P.op = fuseA->dev(); P.x = fusex->dev(); }
-    else { memset(&P.op, 0, sizeof(P.op)); memset(&P.x, 0, sizeof(P.x)); }
-    { const char* e = getenv("TTN_FAST"); P.fast = e ? atoi(e) : 1; }
-    if (compress_use_wg512(psi->batch)) {
-        HIPCHK(hipMemsetAsync(g_next_train.p, 0, sizeof(int), g_stream));
-        P.next_train = g_next_train.as<int>();
-        const int rc512 = ttn_wg512_launch_compress(&P, sizeof(P), compress_slots(psi->batch), g_stream);
-        if (rc512) return hipfail((hipError_t)rc512, "k_compress (512-thread build)");
-    } else {
-        P.next_train = nullptr;
-        hipLaunchKernelGGL(k_compress, dim3(psi->batch), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, P);
-        HIPCHK(hipGetLastError());
-    }
-    psi->bound = fin;
-    return TTN_OK;
-}
-
-int ttn_compress(ttn_tt_t psi, int64_t max_bond, double truncerr, int64_t sweeps) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!psi) return fail(TTN_ERR_ARG, "null handle");
-    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    return launch_compress(psi, 0, max_bond, truncerr, sweeps);
-}
-
-int ttn_bond_truncate(ttn_tt_t psi, int64_t k, int64_t max_bond, double truncerr) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!psi) return fail(TTN_ERR_ARG, "null handle");
-    if (k < 1 || k >= psi->d) return fail(TTN_ERR_BOND_INDEX, "k must be in 1:(N-1)");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    return launch_compress(psi, k, max_bond, truncerr, 1);
-}
-
-int ttn_sweep(ttn_tt_t psi, int64_t k_first, int64_t k_last, int64_t max_bond, double truncerr) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!psi) return fail(TTN_ERR_ARG, "null handle");
-    if (k_first < 1 || k_first >= psi->d || k_last < 1 || k_last >= psi->d) return fail(TTN_ERR_BOND_INDEX, "k must be in 1:(N-1)");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    return launch_compress(psi, -1, max_bond, truncerr, 1, k_first - 1, k_last - 1);
-}
-
-// ---- boundary-core hand-off of core-wise sharded chains --------------------------------------------
-// A core is stored compactly (current ranks) at the start of its slot, so the first dims[k]*bound[k]*bound[k+1] doubles
-// of every train's slot carry it; they move to / from a dense [batch][that many] device buffer with one 2-D copy.
-int ttn_tt_core_extent(ttn_tt_t h, int64_t k, int64_t* doubles_per_train, int64_t* bound_left, int64_t* bound_right) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    F64_ONLY("ttn_tt_core_extent", {h});
-    if (!h || k < 1 || k > h->d) return fail(TTN_ERR_ARG, "bad core index");
-    const int64_t bl = h->bound[k - 1], br = h->bound[k];
-    if (doubles_per_train) *doubles_per_train = h->dims[k - 1] * bl * br;
-    if (bound_left) *bound_left = bl;
-    if (bound_right) *bound_right = br;
-    return TTN_OK;
-}
-
-int ttn_tt_core_export(ttn_tt_t h, int64_t k, double* dev_buf, int64_t* dev_rks2) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    F64_ONLY("ttn_tt_core_export", {h});
-    if (!h || !dev_buf || !dev_rks2 || k < 1 || k > h->d) return fail(TTN_ERR_ARG, "bad argument");
-    const size_t w = sizeof(double) * (size_t)(h->dims[k - 1] * h->bound[k - 1] * h->bound[k]);
-    HIPCHK(hipMemcpy2DAsync(dev_buf, w, h->d_data + h->off[k - 1], sizeof(double) * (size_t)h->stride, w, h->batch,
-                            hipMemcpyDeviceToDevice, g_stream));
-    HIPCHK(hipMemcpy2DAsync(dev_rks2, 2 * sizeof(long long), h->d_rks + (k - 1), sizeof(long long) * (size_t)(h->d + 1),
-                            2 * sizeof(long long), h->batch, hipMemcpyDeviceToDevice, g_stream));
-    return TTN_OK;
-}
-
-int ttn_tt_core_import(ttn_tt_t h, int64_t k, const double* dev_buf, const int64_t* dev_rks2, int64_t bound_left, int64_t bound_right) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    F64_ONLY("ttn_tt_core_import", {h});
-    if (!h || !dev_buf || !dev_rks2 || k < 1 || k > h->d || bound_left < 1 || bound_right < 1) return fail(TTN_ERR_ARG, "bad argument");
-    if (bound_left > h->cap[k - 1] || bound_right > h->cap[k]) return fail(TTN_ERR_CAPACITY, "ttn_tt_core_import: core does not fit the slot");
-    const size_t w = sizeof(double) * (size_t)(h->dims[k - 1] * bound_left * bound_right);
-    HIPCHK(hipMemcpy2DAsync(h->d_data + h->off[k - 1], sizeof(double) * (size_t)h->stride, dev_buf, w, w, h->batch,
-                            hipMemcpyDeviceToDevice, g_stream));
-    HIPCHK(hipMemcpy2DAsync(h->d_rks + (k - 1), sizeof(long long) * (size_t)(h->d + 1), dev_rks2, 2 * sizeof(long long),
-                            2 * sizeof(long long), h->batch, hipMemcpyDeviceToDevice, g_stream));
-    h->bound[k - 1] = bound_left;
-    h->bound[k] = bound_right;
-    return TTN_OK;
-}
-
-int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, double truncerr, int64_t sweeps) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (sweeps < 1) return fail(TTN_ERR_SWEEPS, "sweeps must be >= 1");
-    if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    if (int rb = single_op(A, "ttn_apply_compress")) return rb;
-    const bool cplx = A->el == 2 || x->el == 2 || y->el == 2;     // ComplexF64: apply, then round (no fused complex merge)
-    const char* nf = getenv("TTN_NOFUSE");
-    if (!cplx && (x->d < 2 || (nf && atoi(nf)))) {          // nothing to fuse into / diagnostic switch
-        int rc = ttn_apply(A, x, y);
-        if (rc) return rc;
-        return ttn_compress(y, max_bond, truncerr, sweeps);
-    }
-    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (cplx) {
-        if (y->el != 2 || (A->el != 2 && x->el != 2)) return refuse_mixed("ttn_apply_compress");
-    } else {
-        if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-        if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_compress: output must not alias the input");
-    }
-    const int d = x->d;
-    int rc = apply_capacity(A, x, y);
-    if (rc) return rc;
-    // every check that can refuse the rounding runs on the product's ranks BEFORE y is touched: on an error return y still holds
-    // what it held (ranks, bounds, gauge flags and cores)
-    std::vector<int64_t> yb(d + 1), fin_;
-    for (int m = 0; m <= d; ++m) yb[m] = A->rks[m] * x->bound[m];
-    if (d >= 2) { long long pm_, qm_, pt_; if ((rc = compress_precheck(y, yb, 0, max_bond, sweeps, 0, 0, fin_, pm_, qm_, pt_))) return rc; }
-    if (cplx) {
-        if ((rc = ttn_apply(A, x, y))) return rc;
-        return ttn_compress(y, max_bond, truncerr, sweeps);
-    }
-    // FUSED: y = A*x is never written to HBM.  y only receives its ranks (A.rks .* x.rks, tt_operations.jl:103); the first
-    // L->R sweep of k_compress builds each merged matrix straight from core k of y, x_{k+1} and A_{k+1}.
-    if ((rc = apply_ranks(A, x, y))) return rc;
-    return launch_compress(y, 0, max_bond, truncerr, sweeps, 0, 0, A, x);
-}
-
-// ---- fused apply for core-wise sharded chains: the product's ranks first, then ONE L->R pass over a bond range whose right cores
-// are still virtual.  Between the two calls a boundary core may be imported into y (ttn_tt_core_import).
-int ttn_apply_begin(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    F64_ONLY("ttn_apply_begin", {x, y}, {A});
-    if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (int rb = single_op(A, "ttn_apply_begin")) return rb;
-    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims)) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (x->batch != y->batch) return fail(TTN_ERR_DIMS, "batch sizes differ");
-    if (x == y) return fail(TTN_ERR_ARG, "ttn_apply_begin: output must not alias the input");
-    const int rc = apply_capacity(A, x, y);
-    return rc ? rc : apply_ranks(A, x, y);
-}
-
-int ttn_apply_sweep(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t k_first, int64_t k_last, int64_t max_bond, double truncerr, int first_core_real) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    F64_ONLY("ttn_apply_sweep", {x, y}, {A});
-    if (!A || !x || !y) return fail(TTN_ERR_ARG, "null handle");
-    if (int rb = single_op(A, "ttn_apply_sweep")) return rb;
-    if (!same_dims(A->dims, x->dims) || !same_dims(x->dims, y->dims) || x->batch != y->batch) return fail(TTN_ERR_DIMS, "Incompatible dimensions");
-    if (k_first < 1 || k_first >= y->d || k_last < k_first || k_last >= y->d) return fail(TTN_ERR_BOND_INDEX, "ttn_apply_sweep: need 1 <= k_first <= k_last <= N-1 (one L->R pass)");
-    if (max_bond < 1) return fail(TTN_ERR_ARG, "max_bond must be >= 1");
-    return launch_compress(y, -1, max_bond, truncerr, 1, k_first - 1, k_last - 1, A, x, first_core_real ? 1 : 0);
-}
-
-// The HIP stream every call of this library is enqueued on (hipStream_t): lets a caller order its own streams against the
-// library's work with events instead of host synchronisation (the boundary-core hand-offs of pipeline.py)
-int ttn_stream_handle(void** stream) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!stream) return fail(TTN_ERR_ARG, "null pointer");
-    *stream = (void*)g_stream;
-    return TTN_OK;
-}
 
 // ---- site-swap chains: hadamard_ttm and reorder -----------------------------------------------------
 // Launch of k_swap_chain.  `ops` = (type, slotA, slotB) triples; kind 1 works in an arena of 2d uniform slots carved out of
@@ -2290,34 +1289,6 @@ int ttn_eigsolve_stats(int64_t batch, int64_t* lanczos_applies, double* lanczos_
     return TTN_OK;
 }
 
-int ttn_status_all(void) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    unsigned seen = 0;
-    for (ttn_tt_s* h : g_live)
-        if (h->d_status) hipLaunchKernelGGL(k_fold_status, dim3(1), dim3(64), 0, g_stream, (const int*)h->d_status, h->batch, g_pending_status.as<unsigned>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&seen, g_pending_status.p, sizeof(unsigned), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemsetAsync(g_pending_status.p, 0, sizeof(unsigned), g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return status_error(seen);
-}
-
-int ttn_compress_status(ttn_tt_t psi, int64_t* total_jacobi_sweeps) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!psi) return fail(TTN_ERR_ARG, "null handle");
-    if (total_jacobi_sweeps) {
-        std::vector<int> st(psi->batch);
-        HIPCHK(hipMemcpyAsync(st.data(), psi->d_status + psi->batch, sizeof(int) * psi->batch, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        for (int b = 0; b < psi->batch; ++b) total_jacobi_sweeps[b] = st[b];
-    }
-    unsigned seen = 0;
-    const int rc = take_status(psi, seen);
-    return rc ? rc : status_error(seen);
-}
-
 // ---- core gradients (csrc/ttn_grad_kernels.h) ------------------------------------------------------------------------------------
 // What the four calls check alike before anything is launched: Float64 handles of equal dims and batch, trains below 2^31 doubles.
 static int grad_common(const char* who, std::initializer_list<const ttn_tt_s*> tts) {
@@ -2766,29 +1737,6 @@ int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, dou
     return TTN_OK;
 }
 
-// ---- singular-value capture -----------------------------------------------------------------------
-int ttn_sv_capture(ttn_tt_t h, int enable) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    F64_ONLY("ttn_sv_capture", {h});
-    if (!h) return fail(TTN_ERR_ARG, "null handle");
-    h->sv_on = enable != 0;
-    return TTN_OK;
-}
-int ttn_sv_get(ttn_tt_t h, int64_t b, int64_t step, double* out, int64_t cap, int64_t* n) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!h || !out || !n || b < 0 || b >= h->batch) return fail(TTN_ERR_ARG, "bad argument");
-    if (!h->d_sv || step < 0 || step >= h->sv_steps) return fail(TTN_ERR_ARG, "no captured singular values for that step");
-    std::vector<double> tmp(h->sv_pmax);
-    HIPCHK(hipMemcpyAsync(tmp.data(), h->d_sv + ((size_t)b * h->sv_steps + step) * h->sv_pmax, sizeof(double) * h->sv_pmax, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    int64_t cnt = 0;
-    for (int i = 0; i < h->sv_pmax && tmp[i] >= 0.0; ++i) { if (cnt < cap) out[cnt] = tmp[i]; ++cnt; }
-    *n = std::min(cnt, cap);
-    return TTN_OK;
-}
-
-// ---- stateless host-pointer entry points ----------------------------------------------------------
 // ---- TDVP local contractions (src/solvers/tdvp.jl:29-43, :205-208), batched, real or complex -------------------------------------
 // Device-pointer forms: every tensor is an array of `batch` column-major tensors laid out back to back (stride = its size; M may be
 // shared by the batch: m_shared != 0).  The host forms (…_f64) stage host arrays of the same layout through the device.
@@ -3615,38 +2563,6 @@ int ttn_tt_increase_ranks(ttn_tt_t x, const int64_t* new_rks, double noise, uint
 
 // ---- TT operator algebra (csrc/ttn_opalg_kernels.h) ----------------------------------------------------------------------------
 // Every operation allocates its result with tto_alloc (an operator handle is immutable).
-int ttn_tto_set_ot(ttn_tto_t A, const int64_t* ot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!A || !ot) return fail(TTN_ERR_ARG, "null pointer");
-    if (int rb = single_op(A, "ttn_tto_set_ot")) return rb;
-    A->ot.assign(ot, ot + A->d);
-    return TTN_OK;
-}
-
-int ttn_tto_ranks(ttn_tto_t A, int64_t* d, int64_t* dims, int64_t* rks, int64_t* ot) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (!A) return fail(TTN_ERR_ARG, "null handle");
-    if (d) *d = A->d;
-    if (dims) for (int k = 0; k < A->d; ++k) dims[k] = A->dims[k];
-    if (rks) for (int m = 0; m <= A->d; ++m) rks[m] = A->rks[m];
-    if (ot) for (int k = 0; k < A->d; ++k) ot[k] = A->ot[k];
-    return TTN_OK;
-}
-
-int ttn_tto_download(ttn_tto_t A, double* const* cores) {
-    std::lock_guard<std::recursive_mutex> lk(g_mu);
-    NEED_INIT();
-    if (!A || !cores) return fail(TTN_ERR_ARG, "null pointer");
-    if (int rb = single_op(A, "ttn_tto_download")) return rb;
-    for (int k = 0; k < A->d; ++k) {
-        if (!cores[k]) return fail(TTN_ERR_ARG, "ttn_tto_download: null core");
-        const size_t sz = (size_t)A->el * A->dims[k] * A->dims[k] * A->rks[k] * A->rks[k + 1];
-        HIPCHK(hipMemcpyAsync(cores[k], A->d_data + A->off[k], sizeof(double) * sz, hipMemcpyDeviceToHost, g_stream));
-    }
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return TTN_OK;
-}
-
 // *(A::TToperator, B::TToperator)   src/tt_operations.jl:162-172
 int ttn_tto_mul(ttn_tto_t A, ttn_tto_t B, ttn_tto_t* out) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);

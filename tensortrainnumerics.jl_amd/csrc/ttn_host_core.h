@@ -1,10 +1,13 @@
 // ttn_host_core.h — host API, lowest layer: the state every call needs, errors, DevBuf, the handle types, failure codes.
 //
 // The host API (the C ABI of include/ttn.h) is being cut into csrc/ttn_host_*.h, one header per feature, layered: a header includes the
-// lower ones it uses; ttn_api.hip includes them lowest first, holds the features not cut out yet, and ends with ttn_init /
-// ttn_finalize, which see every module's state.  State that one module alone reads or writes is declared in that module's header;
-// only what several share stands here.  These headers are included by ttn_api.hip ONLY — ttn_wg512.hip never sees one: everything in
-// them has internal linkage (`static`, unnamed namespace) and the library state must exist exactly once.
+// lower ones whose helpers or state it uses (an entry point of another feature is called through its declaration in include/, like
+// any caller's); ttn_api.hip includes them lowest first, holds the features not cut out yet, and ends with ttn_init / ttn_finalize,
+// which see every module's state.  So far, lowest first: _lds, _core, then _dot, _measure, _sample, _handles, _stream, _rect, _compress.
+// State that one module alone reads or writes is declared in that module's header; what two modules share stands with the lower of
+// them, whose head comment names the other; only what many share stands here.  These headers are included by ttn_api.hip ONLY —
+// ttn_wg512.hip never sees one: everything in them has internal linkage (`static`, unnamed namespace) and the library state must
+// exist exactly once.  What crosses to ttn_wg512.hip is declared in ttn_wg512.h.
 #ifndef TTN_HOST_CORE_H
 #define TTN_HOST_CORE_H
 #include "../../include/ttn.h"

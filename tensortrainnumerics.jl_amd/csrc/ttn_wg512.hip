@@ -12,6 +12,8 @@
 #include <float.h>
 #include <string.h>
 
+#include "ttn_wg512.h"          // the launchers below, declared once for both translation units
+
 #define TTN_WG 512
 namespace ttn_wg512 {
 #include "ttn_common.h"

@@ -48,9 +48,9 @@ def _prototypes(header):
 
 
 def _body(src, name):
-    """The body of function `name` in ttn_api.hip (brace matching from its definition)."""
+    """The body of function `name` in the host API (brace matching from its definition)."""
     m = re.search(r"^(?:static )?int %s\(" % re.escape(name), src, flags=re.M)
-    assert m, f"{name} is not defined in ttn_api.hip"
+    assert m, f"{name} is not defined in the host API"
     i = src.index("{", m.end())
     depth, j = 0, i
     while True:
