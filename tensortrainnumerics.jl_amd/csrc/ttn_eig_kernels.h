@@ -262,6 +262,7 @@ __device__ __noinline__ int sturm_count_guarded(const lds_f64* de, double x, int
 // ---- 2. eigenvalues lam[0..nev-1] in DESCENDING order (the nev largest), multisection with TL lanes per eigenvalue ----
 template <int N, int TL>
 __device__ void wg_bisect(int nev, double* lds) {
+    static_assert(TL == 4 || TL == 8, "a group's lanes are one or two quads of a row (the DPP sum of nf)");
     lds_f64* L = (lds_f64*)lds;
     lds_f64 *dg = L + EIG_TAIL, *e = dg + 128, *lam = dg + 256;
     lds_f64* e2 = L;                                             // phase-1 work area is free
@@ -293,26 +294,31 @@ __device__ void wg_bisect(int nev, double* lds) {
 #pragma unroll
     for (int g = 0; g < N / 16; ++g) { dreg[g] = de[2 * (16 * g + (tid & 15))]; ereg[g] = de[2 * (16 * g + (tid & 15)) + 1]; }
     asm volatile("s_nop 1");
+    // Nothing in the rounds is shared between waves (the matrix in dreg / ereg, a group's TL lanes inside one wave, `de` only read,
+    // a converged group's interval frozen), so every wave runs its own loop: no workgroup barrier per round, a wave leaves when
+    // its own groups are done (the tolerance is relative to each eigenvalue: the waves of the small ones need more rounds), and a
+    // wave whose groups are all beyond nev never enters.  The one barrier is the one before `lam` is consumed.
     for (int g0 = 0; g0 < nev; g0 += TTN_WG / TL) {
         const int gi = g0 + tid / TL, sub = tid % TL;
         const bool act = gi < nev;
         const int jasc = N - 1 - (act ? gi : 0);            // ascending index of this group's eigenvalue
         double lo = glo, hi = ghi;
+        if (g0 + (tid & ~63) / TL >= nev) continue;         // wave-uniform
         // rounds: (TL + 1)-section; stop when the interval is at rounding level
         for (int round = 0; round < 64; ++round) {
             const double wdt = hi - lo;
             const bool done = !(wdt > 2.0 * DBL_EPSILON * fmax(fabs(lo), fabs(hi)) + 2.0 * pivmin);
-            if (__syncthreads_and(done || !act)) break;
+            if (__builtin_amdgcn_ballot_w64(!done && act) == 0) break;      // whole-wave control flow: the DPP broadcasts of the count need every lane
             const double x = lo + wdt * ((double)(sub + 1) / (double)(TL + 1));
-            // waves whose groups are all beyond nev skip the count (wave-uniform branch): they would only compete for issue slots
-            const bool wave_act = g0 + (tid & ~63) / TL < nev;
             bool zero = false;
-            int cnt = wave_act ? sturm_count<N>(dreg, ereg, x, zero) : 0;
+            int cnt = sturm_count<N>(dreg, ereg, x, zero);
             if (zero) cnt = sturm_count_guarded(de, x, N);
-            // nf = number of section points with count <= jasc (monotone in sub): the eigenvalue lies right of point nf-1
+            // nf = number of section points with count <= jasc (monotone in sub): the eigenvalue lies right of point nf-1; summed over
+            // the group's lanes by DPP (quads, then the two quads of a half row), not through the LDS crossbar of ds_bpermute
             int nf = (cnt <= jasc) ? 1 : 0;
-#pragma unroll
-            for (int m = 1; m < TL; m <<= 1) nf += __shfl_xor(nf, m);
+            nf += __builtin_amdgcn_update_dpp(0, nf, 0xB1, 0xF, 0xF, true);       // quad_perm [1,0,3,2]
+            nf += __builtin_amdgcn_update_dpp(0, nf, 0x4E, 0xF, 0xF, true);       // quad_perm [2,3,0,1]
+            if constexpr (TL == 8) nf += __builtin_amdgcn_update_dpp(0, nf, 0x141, 0xF, 0xF, true);      // row_half_mirror
             if (!done) {
                 const double nlo = (nf > 0) ? lo + wdt * ((double)nf / (double)(TL + 1)) : lo;
                 const double nhi = (nf < TL) ? lo + wdt * ((double)(nf + 1) / (double)(TL + 1)) : hi;
