@@ -46,7 +46,9 @@ struct CompressArgs {
     int* sweep_stats;      // [batch] device: total Jacobi sweeps (diagnostics)
     int fast;              // 0: Householder route only; odd: try the Gram / factored fast paths (verified a posteriori) first.
                            // Diagnostic bits (TTN_FAST): 2 no eigensolver in route G (Cholesky + Jacobi), 4 none in route F,
-                           // 8 no diagonal-left shortcut in route F, 16 no Jacobi polish after a failed conditioning test
+                           // 8 no diagonal-left shortcut in route F, 16 no Jacobi polish after a failed conditioning test,
+                           // 32 a route-F step whose B' was handed over in the staging area treats its a-posteriori check as failed
+                           //    (the restore path of the hand-over: Rf is in the dead core already, then the step falls back)
     // fused apply (ttn_apply_compress): psi = A * x is never materialised.  During the FIRST L->R sweep core k+1 of psi
     // is still virtual (= A_{k+1} applied to x_{k+1}); psi's ranks already hold A.rks .* x.rks.
     int fused;
@@ -1025,6 +1027,43 @@ __device__ __noinline__ int wg_bond_small(SmallStepArgs Q, double* ck, double* c
 __device__ int wg_eig128(const double* Gg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork);
 __device__ int wg_eig64(const double* Gg, int ldg, double* Vst, int r, int nev, double* sig, double* lds, int* iwork, double* dwork);
 
+// Hand-over of the left factor between consecutive right-to-left route-F steps.  Step k stages Lf (p x r,
+// column-major) in the slot's scratch; step k-1 reads that core exactly once, as its B', and then overwrites all of it.  With
+// p = n2' rm' the staged matrix IS the next step's B' as a plain column-major rm' x q' matrix (ld = rm'), so the producer leaves the
+// commit copy out and sets the slot's note: "core k lives in staging area note-1".  S.M is cut in three: two areas of pq/3 doubles that
+// alternate (the reader's B' stays intact while it writes its own Lf, and until its commit: a fallback needs it) and the rest for the
+// Rf^T of a reader that cannot store Rf straight into the (dead) core k+1.  The READER decides (wg_bond_step): a step that finds the
+// note set and will not read from staging first puts the core back (wg_handover_restore), and so does one that read from staging
+// and then leaves route F, before its merge.  The producer only hands over to a step of the same loop (handover_next), so no note
+// outlives a launch or a train.
+__device__ inline long long handover_area(const CompressArgs& P) { return (long long)P.pmax * P.qmax / 3; }
+// the reader's B' (rm x q) and its own Lf (p x rk, rk <= rm) each fit an area
+__device__ inline bool handover_fits(const CompressArgs& P, int p, int q, int rm) {
+    const long long h = handover_area(P);
+    return (long long)p * rm <= h && (long long)rm * q <= h;
+}
+// the step after `step` of k_compress's loop is bond k-1 on real cores
+__device__ inline bool handover_next(const CompressArgs& P, int step) {
+    if (P.k_single > 0) return false;
+    if (P.k_single < 0) return P.k_first > P.k_last && step < P.k_first - P.k_last && !P.fused;
+    const int d = P.tt.d, i = step % (2 * (d - 1));
+    return i >= d - 1 && i + 1 < 2 * (d - 1);
+}
+__device__ inline int* handover_note(const CompressArgs& P) {      // the upper half of the slot's `perm` words (perm itself takes pmax ints)
+    double* scr = P.scratch + (long long)blockIdx.x * P.scratch_stride;
+    const long long pq = (long long)P.pmax * P.qmax;
+    double* sigs = scr + 2 * pq + (long long)QR_NB * P.qmax + (long long)P.pmax * QR_NB + 2LL * P.pmax * P.pmax + P.pmax;
+    return reinterpret_cast<int*>(sigs + P.pmax) + P.pmax;
+}
+// core[s2, ga, be] = stage[(ga + rm s2) + n2 rm be]: the commit copy the producer left out; clears the note
+__device__ __noinline__ void wg_handover_restore(double* core, const double* stage, int n2, int rm, int Dr, int* note) {
+    core = unip(core); stage = unip(stage); n2 = uni32(n2); rm = uni32(rm); Dr = uni32(Dr); note = unip(note);
+    __syncthreads();
+    wg_copy_to_view(mkview(core, Idx{rm, (long long)n2, 1}, plain((long long)n2 * rm)), stage, n2 * rm, Dr, 1, (long long)n2 * rm, Dr, 1);
+    if (threadIdx.x == 0) *note = 0;
+    __syncthreads();
+}
+
 struct BondIO {
     double *ck, *ck1;            // the two cores (slots)
     int n1, n2, Dl, rm, Dr;      // physical dimensions and the three ranks
@@ -1099,7 +1138,15 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         // scales
         double sa = 0.0, sb = 0.0;
         sa = wg_absmax(ck, (long long)n1 * Dl * rm, S.red);
-        sb = wg_absmax(ck1, (long long)n2 * rm * Dr, S.red);
+        // Handed over (the slot's note is 1 or 2; wg_bond_step has checked that this step is wide, on real cores and that the areas
+        // fit): B' is the plain column-major rm x q matrix in that staging area, the left factor as the step before staged it.  The
+        // note is READ AGAIN wherever it matters instead of being kept, and the two-team calls take the alternative operand next to the
+        // usual one (they store it over the descriptor): a view chosen at run time, field by field, is what the register budget of
+        // k_compress cannot take (64 more spilled VGPRs).
+#define HANDOVER_PEND() ((SWAP == 0) ? uni32(*handover_note(P)) : 0)
+#define HANDOVER_BS(pn) mkview(S.M + ((pn) == 2 ? handover_area(P) : 0), plain(1), plain(rm))       /* the staged B' (pn != 0) */
+#define HANDOVER_B(pn) ((pn) ? HANDOVER_BS(pn) : Bp)
+        { const int pn = HANDOVER_PEND(); sb = wg_absmax(pn ? S.M + (pn == 2 ? handover_area(P) : 0) : ck1, (long long)n2 * rm * Dr, S.red); }      // (the same set of numbers)
         bool ok = (sa > 0.0) && (sb > 0.0);
         const double sA = wide ? sa : sb, sB = wide ? sb : sa;       // scale of A', B'
         const double s0 = sA * sB;
@@ -1109,7 +1156,7 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
         bool diagA = false;
         if (ok) {
             // A'^T A' and B' B'^T: independent, one two-team call (two wg_syrk calls where rm > 64)
-            wg_syrk2(rm, p, tview(Ap), Gav, 1.0 / (sA * sA), rm, q, Bp, Gbv, 1.0 / (sB * sB), lds);
+            { const int pn = HANDOVER_PEND(); wg_syrk2(rm, p, tview(Ap), Gav, 1.0 / (sA * sA), rm, q, Bp, Gbv, 1.0 / (sB * sB), lds, pn, HANDOVER_BS(pn)); }
             // A' = U D^(1/2) with orthonormal U (the left core of a bond step is left as U sqrt(S) by the step before it, so every
             // R->L step of a sweep that follows an L->R sweep sees this): then M = U (D^(1/2) B') and the SVD of M is U times the SVD
             // of the rm x q matrix N = D^(1/2) B' — no Cholesky factors, no core matrix, two output GEMMs instead of five.
@@ -1192,13 +1239,24 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             }
             const View T1v = mkview(S.T1, plain(1), plain(128));
             const View T2v = mkview(S.T2, plain(1), plain(128));
-            double* LfT = S.M;                                              // p x rk, column-major (ld = p)
-            double* RfT = S.M + (long long)p * rk;                          // rk x q, row-major (ld = q)
-            const View Lft = mkview(LfT, plain(1), plain(p));
-            const View Rft = mkview(RfT, plain(q), plain(1));
+            // Lf goes to the staging area that does not hold this step's B'.  B' read from staging: core k+1 holds nothing live, Rf
+            // goes straight into it unless zero rows have to follow (a step that leaves route F gets B' put back over it)
+#define HANDOVER_LFT(pn) (S.M + ((pn) == 1 ? handover_area(P) : 0))                                  /* p x rk, column-major (ld = p) */
+#define HANDOVER_RFT(pn) ((pn) ? S.M + 2 * handover_area(P) : S.M + (long long)p * rk)              /* rk x q, row-major (ld = q) */
+#define HANDOVER_RFS(pn) mkview(HANDOVER_RFT(pn), plain(q), plain(1))                                /* Rf^T staged */
+#define HANDOVER_RFC() mkview(ck1, plain(n2), Idx{n2, 1, (long long)n2 * r})                         /* Rf in core k+1 (pn != 0, rk == r) */
+#define HANDOVER_RF(pn) (((pn) && rk == r) ? HANDOVER_RFC() : HANDOVER_RFS(pn))
+            const int pn = HANDOVER_PEND();
+            const View Lft = mkview(HANDOVER_LFT(pn), plain(1), plain(p));
+            const View Rft = HANDOVER_RF(pn);
+            // the operands of the two-team calls below that depend on the hand-over, left in LDS by thread 0 for itself (S.taus is
+            // the Householder route's): B' and where Rf goes
+            View* hv = reinterpret_cast<View*>(S.taus);
+            static_assert(2 * sizeof(View) <= QR_NB * sizeof(double), "two views in S.taus");
+            if (tid == 0) { hv[0] = HANDOVER_B(pn); hv[1] = Rft; }
             if (diagA) {
                 // Lf^T = T1^T A'^T and Rf = T2^T B': the short operands in registers, both products in one two-team call
-                wg_gemm_ra2(rk, p, rm, tview(T1v), tview(Ap), tview(Lft), 1.0, rk, q, rm, tview(T2v), Bp, Rft, 1.0, lds);
+                wg_gemm_ra2(rk, p, rm, tview(T1v), tview(Ap), tview(Lft), 1.0, rk, q, rm, tview(T2v), Bp, mkview(S.M + (long long)p * rk, plain(q), plain(1)), 1.0, lds, hv);
             } else {
             // Lf = A' * (L_B * (C^T * X_s))     (ldsX is free again: use it as the second temporary)
             wg_gemm(rm, rk, rm, tview(Ccv), T1v, mkview(S.T3, plain(1), plain(128)), 1.0, 0.0, lds);
@@ -1206,11 +1264,14 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             wg_gemm(p, rk, rm, Ap, T1v, Lft, 1.0, 0.0, lds);
             // Rf = (L_A * X_t)^T * B'
             wg_gemm(rm, rk, rm, Gav, T2v, mkview(S.T3, plain(1), plain(128)), 1.0, 0.0, lds);
-            wg_gemm(rk, q, rm, tview(mkview(S.T3, plain(1), plain(128))), Bp, Rft, 1.0, 0.0, lds);
+            wg_gemm(rk, q, rm, tview(mkview(S.T3, plain(1), plain(128))), HANDOVER_B(pn), Rft, 1.0, 0.0, lds);
             }
             // a-posteriori check: Lf^T Lf = Sigma, Rf Rf^T = Sigma
-            wg_syrk2(rk, p, tview(Lft), mkview(S.T1, plain(1), plain(128)), 1.0, rk, q, Rft, mkview(S.T2, plain(1), plain(128)), 1.0, lds);
+            { const int pc = HANDOVER_PEND();
+              wg_syrk2(rk, p, tview(mkview(HANDOVER_LFT(pc), plain(1), plain(p))), mkview(S.T1, plain(1), plain(128)), 1.0, rk, q, mkview(S.M + (long long)p * rk, plain(q), plain(1)), mkview(S.T2, plain(1), plain(128)), 1.0, lds,
+                       0, View{}, reinterpret_cast<const View*>(S.taus) + 1); }
             ok = wg_check_diag_tab2(S.sigs, S.T1, S.T2, 128, rk, s0, S.Ts, S.red) <= FAST_CHECK_TOL;       // both checks, one pass
+            if ((P.fast & 32) && HANDOVER_PEND()) ok = false;               // diagnostic: the restore path
             if (ok) {
                 if (P.sv_out && step < P.sv_steps) {
                     double* so = P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax;
@@ -1220,10 +1281,13 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                 const View Rfv = mkview(ck1, plain(n2), Idx{n2, 1, (long long)n2 * r});
                 const View Lo = wide ? Lfv : tview(Rfv);       // p x r
                 const View Ro = wide ? Rfv : tview(Lfv);       // r x q
+                // the next step can take Lf from its staging area: no copy into core k (wg_bond_step reads the note)
+                const bool hand = SWAP == 0 && wide && rk == r && handover_next(P, step);
+                const int pc = HANDOVER_PEND();
                 __syncthreads();
-                wg_copy_to_view(Lo, LfT, p, r, 1, p, rk, 1);               // Lo[row, j] = LfT[row + p j], columns j >= rk zero
-                wg_copy_to_view(Ro, RfT, r, q, q, 1, rk, 0);               // Ro[j, col] = RfT[j q + col], rows j >= rk zero
-                if (tid == 0) *io.rank_out = r;
+                if (!hand) wg_copy_to_view(Lo, HANDOVER_LFT(pc), p, r, 1, p, rk, 1);               // Lo[row, j] = LfT[row + p j], columns j >= rk zero
+                if (!(pc && rk == r)) wg_copy_to_view(Ro, HANDOVER_RFT(pc), r, q, q, 1, rk, 0);    // Ro[j, col] = RfT[j q + col], rows j >= rk zero
+                if (tid == 0) { *io.rank_out = r; if (pc || hand) *handover_note(P) = hand ? (pc == 1 ? 2 : 1) : 0; }
                 __syncthreads();
                 done = true;
             }
@@ -1231,6 +1295,23 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
     }
 
     if (!done) {
+        // read B' from staging and leaves route F: the core back in its slot first (the merge writes S.M; core k+1 held nothing live,
+        // Rf at most).  core[s2, ga, be] = stage[(ga + rm s2) + n2 rm be], as wg_handover_restore
+        if (const int pn = HANDOVER_PEND()) {
+            const double* stage = S.M + (pn == 2 ? handover_area(P) : 0);
+            __syncthreads();
+            for (int e = tid; e < n2 * rm * Dr; e += TTN_WG) { const int s2 = e % n2, ga = (e / n2) % rm, be = e / (n2 * rm); ck1[e] = stage[ga + rm * s2 + n2 * rm * be]; }
+            if (tid == 0) *handover_note(P) = 0;
+            __syncthreads();
+        }
+#undef HANDOVER_PEND
+#undef HANDOVER_B
+#undef HANDOVER_BS
+#undef HANDOVER_RFS
+#undef HANDOVER_RFC
+#undef HANDOVER_LFT
+#undef HANDOVER_RFT
+#undef HANDOVER_RF
         // ---- merge: M = A' * B'  (p x q), scaled to max|M| = 1 ----
         const View Mv = mkview(S.M, plain(q), plain(1));
         // M stays UNSCALED in memory: max|M| comes out of the GEMM epilogue and the consumers (Gram, LQ copy, output GEMM)
@@ -1505,12 +1586,22 @@ __device__ __forceinline__ void wg_bond_step(const CompressArgs& P, int b, int k
     io.ck = T.data + (long long)b * T.stride + T.off[k];
     io.ck1 = T.data + (long long)b * T.stride + T.off[k + 1];
     io.rank_out = rks + k + 1;
-    // tiny steps (short side <= 8): everything in LDS, no GEMM / LQ / image machinery.  Dispatched HERE, not inside the force-inlined
-    // step: one more call site with live views in that function cost it 280 spilled VGPRs (-7 % on the whole benchmark, measured).
+    const int mr = io.n1 * io.Dl, mc = io.n2 * io.Dr;
+    const int p = mr <= mc ? mr : mc, q = mr <= mc ? mc : mr;
+    const bool small = P.fast && p >= 2 && p <= SMALL_STEP_PMAX && q <= SMALL_STEP_QMAX && P.pmax >= p;
+    // the hand-over note of the step before (see handover_area): taken by a wide route-F step on real cores whose areas fit.  Every
+    // other step puts the core back in its slot before anything reads it.  (A step that took it and then leaves route F puts it
+    // back itself, with a plain loop: a call site inside the force-inlined step is what its register budget cannot take.)
+    int pend = uni32(*handover_note(P));
     {
-        const int mr = io.n1 * io.Dl, mc = io.n2 * io.Dr;
-        const int p = mr <= mc ? mr : mc, q = mr <= mc ? mc : mr;
-        if (P.fast && p >= 2 && p <= SMALL_STEP_PMAX && q <= SMALL_STEP_QMAX && P.pmax >= p) {
+        const bool take = !small && !virt && P.fast && mr <= mc && io.rm < p && io.rm <= TTN_LDS_COLS && io.rm >= 2 && handover_fits(P, p, q, io.rm);
+        if (pend && !take) {
+            wg_handover_restore(io.ck1, P.scratch + (long long)blockIdx.x * P.scratch_stride + (pend == 2 ? handover_area(P) : 0), io.n2, io.rm, io.Dr, handover_note(P));
+            pend = 0;
+        }
+        // tiny steps (short side <= 8): everything in LDS, no GEMM / LQ / image machinery.  Dispatched HERE, not inside the force-inlined
+        // step: one more call site with live views in that function cost it 280 spilled VGPRs (-7 % on the whole benchmark, measured).
+        if (small) {
             if (virt) wg_materialize_core(P, b, k + 1);
             SmallStepArgs Q;
             Q.truncerr = P.truncerr; Q.max_bond = P.max_bond; Q.rank_rule = P.rank_rule; Q.pmax = P.pmax;
@@ -1546,7 +1637,7 @@ __global__ void TTN_KERNEL_BOUNDS k_compress(CompressArgs P) {
                                                                : P.sweeps * per_sweep;
     int b = blockIdx.x;
     while (b < P.tt.batch) {
-        if (threadIdx.x == 0) P.sweep_stats[b] = 0;        // (P.status is sticky: only failures are stored, the host clears on read)
+        if (threadIdx.x == 0) { P.sweep_stats[b] = 0; *handover_note(P) = 0; }        // (P.status is sticky: only failures are stored, the host clears on read)
         __syncthreads();
         // fused apply: the left core of the first bond is written out (unless it was imported), every core to its right stays
         // virtual until the front of the first L->R pass reaches it

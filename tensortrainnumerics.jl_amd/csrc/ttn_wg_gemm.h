@@ -640,8 +640,15 @@ __device__ inline void wg_syrk(int p, int q, View A, View G, double alpha, doubl
 // back to back, two of them pay that latency twice; here each runs on half of the workgroup's waves and both wait together.  Every
 // accumulator sees the MFMAs of its k-steps in ascending order with the operands wg_syrk gives it (the chunks are 48 k instead of 96,
 // the accumulators carry over), so the results are those of two wg_syrk calls bit for bit.  Other shapes take the two calls.
-__device__ inline void wg_syrk2(int p1, int q1, View A1, View G1, double alpha1, int p2, int q2, View A2, View G2, double alpha2, double* lds) {
+// alt2 != 0: the second product's operand is A2alt instead of A2 (the bond step's B' handed over in its staging area); ovr2: it is
+// the view THREAD 0 left at that LDS address (Rf, wherever the step put it).  Thread 0 stores either over the descriptor it has just
+// written: as a view chosen by the caller (a select on every field of A2) the same choice costs k_compress 64 more spilled VGPRs
+// (DESIGN.md section 4.2, r03n).
+__device__ inline void wg_syrk2(int p1, int q1, View A1, View G1, double alpha1, int p2, int q2, View A2, View G2, double alpha2, double* lds,
+                                int alt2 = 0, View A2alt = View{}, const View* ovr2 = nullptr) {
     if (p1 > 64 || p2 > 64 || q1 > SYRK2_QMAX || q2 > SYRK2_QMAX) {
+        if (alt2) A2 = A2alt;
+        if (ovr2) { __syncthreads(); A2 = uniView(*ovr2); }
         wg_syrk(p1, q1, A1, G1, alpha1, lds);
         wg_syrk(p2, q2, A2, G2, alpha2, lds);
         return;
@@ -652,6 +659,8 @@ __device__ inline void wg_syrk2(int p1, int q1, View A1, View G1, double alpha1,
     if (threadIdx.x == 0) {
         dsc[0].m = p1; dsc[0].n = p1; dsc[0].k = q1; dsc[0].pad = 0; dsc[0].A = A1; dsc[0].C = G1; dsc[0].alpha = alpha1; dsc[0].beta = 0.0; dsc[0].amax = nullptr;
         dsc[1].m = p2; dsc[1].n = p2; dsc[1].k = q2; dsc[1].pad = 0; dsc[1].A = A2; dsc[1].C = G2; dsc[1].alpha = alpha2; dsc[1].beta = 0.0; dsc[1].amax = nullptr;
+        if (alt2) dsc[1].A = A2alt;
+        if (ovr2) dsc[1].A = *ovr2;
     }
     __syncthreads();
     TTN_SETPRIO_GEMM();
@@ -889,9 +898,11 @@ __device__ __noinline__ void wg_gemm_ra2_impl(const GemmDesc* dsc_, double* lds)
 }
 #endif
 
-// two products C_i = alpha_i A_i B_i; the two-team form where both shapes allow it (the 512-thread build, m, k <= 64), else two wg_gemm_ra
+// two products C_i = alpha_i A_i B_i; the two-team form where both shapes allow it (the 512-thread build, m, k <= 64), else two wg_gemm_ra.
+// ovr2: the second product reads ovr2[0] and stores into ovr2[1], the views THREAD 0 left at that LDS address, instead of B2 and C2
+// (stored over the descriptor by thread 0, as in wg_syrk2)
 __device__ inline void wg_gemm_ra2(int m1, int n1, int k1, View A1, View B1, View C1, double alpha1,
-                                   int m2, int n2, int k2, View A2, View B2, View C2, double alpha2, double* lds) {
+                                   int m2, int n2, int k2, View A2, View B2, View C2, double alpha2, double* lds, const View* ovr2 = nullptr) {
 #if TTN_WG == 512
     if (m1 <= 64 && m2 <= 64 && k1 <= 64 && k2 <= 64 && n1 >= 64 && n2 >= 64 && n1 <= GEMM_RA2_NMAX && n2 <= GEMM_RA2_NMAX) {
         GemmDesc* dsc = reinterpret_cast<GemmDesc*>(lds + GEMM_LDS_DOUBLES);
@@ -899,6 +910,7 @@ __device__ inline void wg_gemm_ra2(int m1, int n1, int k1, View A1, View B1, Vie
         if (threadIdx.x == 0) {
             dsc[0].m = m1; dsc[0].n = n1; dsc[0].k = k1; dsc[0].pad = 0; dsc[0].A = A1; dsc[0].B = B1; dsc[0].C = C1; dsc[0].alpha = alpha1; dsc[0].beta = 0.0; dsc[0].amax = nullptr;
             dsc[1].m = m2; dsc[1].n = n2; dsc[1].k = k2; dsc[1].pad = 0; dsc[1].A = A2; dsc[1].B = B2; dsc[1].C = C2; dsc[1].alpha = alpha2; dsc[1].beta = 0.0; dsc[1].amax = nullptr;
+            if (ovr2) { dsc[1].B = ovr2[0]; dsc[1].C = ovr2[1]; }
         }
         __syncthreads();
         TTN_SETPRIO_GEMM();
@@ -908,5 +920,6 @@ __device__ inline void wg_gemm_ra2(int m1, int n1, int k1, View A1, View B1, Vie
     }
 #endif
     wg_gemm_ra(m1, n1, k1, A1, B1, C1, alpha1, lds);
+    if (ovr2) { __syncthreads(); B2 = uniView(ovr2[0]); C2 = uniView(ovr2[1]); }
     wg_gemm_ra(m2, n2, k2, A2, B2, C2, alpha2, lds);
 }
