@@ -668,6 +668,12 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * ttn_mals_eigsolve_ortho.  Declared in ttn_eig_ortho.h, which this header includes. */
 #include "ttn_eig_ortho.h"
 
+/* ---- <x| A |y> on ComplexF64 operands (csrc/ttn_braket_kernels.h) ---------------------------------------------------
+ * sum_{i, j} conj(x_i) A_ij y_j per train without forming A y, for complex or real trains and a complex or real operator: ttn_braket
+ * (result on the host, synchronises as ttn_dot) and ttn_braket_dev (device memory, asynchronous).  Declared in ttn_braket.h, which
+ * this header includes. */
+#include "ttn_braket.h"
+
 #ifdef __cplusplus
 }
 #endif

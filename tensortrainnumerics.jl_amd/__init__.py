@@ -21,8 +21,8 @@ from .solvers import (als_eigsolve, als_gen_eigsolv, crank_nicholson_method, dmr
                       lowest_states, mals_eigsolve, rk4_method)
 from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_sample, qttv_to_array
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
-from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, correlation_matrix, div, dot, euclidean_distance,
-                 expect, hadamard, increase_ranks, norm, orthogonalize, r_and_d_to_rks, rayleigh, sandwich, scale, site_expect, sub, tt_compress_, tt_sample, tt_up_rks,
+from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, braket, correlation_matrix, div, dot, energy,
+                 euclidean_distance, expect, hadamard, increase_ranks, norm, orthogonalize, r_and_d_to_rks, rayleigh, sandwich, scale, site_expect, sub, tt_compress_, tt_sample, tt_up_rks,
                  ttv_to_tensor)
 
 __all__ = [n for n in dir() if not n.startswith("__")]

@@ -243,6 +243,12 @@ EIG_ORTHO_SIGNATURES = {
                                           i64, p_f64, p_i64, p_f64]),
 }
 
+# <x| A |y> on ComplexF64 or Float64 operands, include/ttn_braket.h (`out`: 2 * batch host doubles, `d_out`: device memory)
+BRAKET_SIGNATURES = {
+    "ttn_braket": (C.c_int, [handle, handle, handle, p_f64]),
+    "ttn_braket_dev": (C.c_int, [handle, handle, handle, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -274,7 +280,7 @@ def lib() -> C.CDLL:
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     for table in (SIGNATURES, RECT_SIGNATURES, DENSE_SIGNATURES, STEP_SIGNATURES, CROSS_BATCH_SIGNATURES, EXPECT_SIGNATURES, EXPECT_GRAD_SIGNATURES,
-                  OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES):
+                  OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES, BRAKET_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res

@@ -357,6 +357,15 @@ def rand_tt(dims: Sequence[int], rks, seed: int = 0) -> TTvector:
 _PAULI_X = np.array([[0.0, 1.0], [1.0, 0.0]])
 _PAULI_Z = np.array([[1.0, 0.0], [0.0, -1.0]])
 _Y_REAL = np.array([[0.0, -1.0], [1.0, 0.0]])        # sigma_y = i * _Y_REAL
+_PAULI_Y = np.array([[0.0, -1.0j], [1.0j, 0.0]])
+
+
+def _pauli_dtype(dtype):
+    """np.float64 (the default: real operators, a lone sigma_y refused) or np.complex128 (every axis, complex cores)."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise TypeError(f"dtype must be float64 or complex128, got {dt}")
+    return dt == np.dtype(np.complex128)
 
 
 def _pauli_axis(mu) -> str:
@@ -431,25 +440,39 @@ def xy_tto(d: int, jx: float = 1.0, jy: float = 1.0, h: float = 0.0, field="z") 
 
 # Pauli sums (src/tt_operators.jl:45-151): the one- and two-site building blocks of the Hamiltonians above as operators of their own —
 # what a measurement such as the magnetisation sum_k Z_k contracts against a state (device.expect).
-def pauli_matrix(mu) -> np.ndarray:
-    """The Pauli matrix of axis x or z (src/tt_operators.jl:45-54).  sigma_y alone is complex: TTNError, as in _pauli_pair_factors."""
+def pauli_matrix(mu, dtype=np.float64) -> np.ndarray:
+    """The Pauli matrix of axis x or z (src/tt_operators.jl:45-54).  sigma_y alone is complex: TTNError, as in _pauli_pair_factors —
+    unless ``dtype=np.complex128``, which gives any of the three as a complex matrix."""
     a = _pauli_axis(mu)
+    if _pauli_dtype(dtype):
+        return {"x": _PAULI_X.astype(np.complex128), "y": _PAULI_Y.copy(), "z": _PAULI_Z.astype(np.complex128)}[a]
     if a == "y":
         from ._lib import TTNError
         raise TTNError("a single sigma_y factor is complex: only real (Float64) operators are offered")
     return (_PAULI_X if a == "x" else _PAULI_Z).copy()
 
 
-def pauli_sum_tto(mu, d: int) -> TToperator:
+def _complex_cores(out: TToperator) -> TToperator:
+    out.tto_vec = [np.asfortranarray(c, dtype=np.complex128) for c in out.tto_vec]
+    return out
+
+
+def pauli_sum_tto(mu, d: int, dtype=np.float64) -> TToperator:
     """H_mu = sum_k I (x) ... (x) P_mu (x) ... (x) I on d spin-1/2 sites, open boundaries, ranks [1, 2, ..., 2, 1]
-    (src/tt_operators.jl:75-107): bond state 1 = "P not placed yet", bond state 0 = "placed"; d == 1 is the single core P."""
+    (src/tt_operators.jl:75-107): bond state 1 = "P not placed yet", bond state 0 = "placed"; d == 1 is the single core P.
+    ``dtype=np.complex128``: complex cores, any axis (sigma_y included)."""
     assert d >= 1, "number of spin sites must be at least 1"
-    P, Id = pauli_matrix(mu), np.eye(2)
+    cplx = _pauli_dtype(dtype)
+    P, Id = pauli_matrix(mu, dtype), np.eye(2)
     if d == 1:
         out = zeros_tto((2,), [1, 1])
+        if cplx:
+            _complex_cores(out)
         out.tto_vec[0][:, :, 0, 0] = P
         return out
     out = zeros_tto((2,) * d, [1] + [2] * (d - 1) + [1])
+    if cplx:
+        _complex_cores(out)
     c = out.tto_vec[0]
     c[:, :, 0, 0], c[:, :, 0, 1] = P, Id
     for k in range(1, d - 1):
@@ -460,14 +483,20 @@ def pauli_sum_tto(mu, d: int) -> TToperator:
     return out
 
 
-def pauli_pair_sum_tto(mu, nu, d: int) -> TToperator:
+def pauli_pair_sum_tto(mu, nu, d: int, dtype=np.float64) -> TToperator:
     """H_{mu,nu} = sum_k I (x) ... (x) P_mu (x) P_nu (x) ... (x) I (sites k, k + 1), open boundaries, ranks [1, 3, ..., 3, 1]
     (src/tt_operators.jl:118-148): bond state 2 = "nothing placed", 1 = "P_mu placed, P_nu is due", 0 = "both placed".  Mixed pairs
-    with one sigma_y are complex: TTNError; (y, y) is real."""
+    with one sigma_y are complex: TTNError; (y, y) is real.  ``dtype=np.complex128``: complex cores, all nine pairs."""
     assert d >= 2, "nearest-neighbor Pauli pair sum needs at least 2 spin sites"
-    P1, P2 = _pauli_pair_factors(mu, nu)
+    cplx = _pauli_dtype(dtype)
+    if cplx and not (_pauli_axis(mu) == "y" and _pauli_axis(nu) == "y"):      # (y, y) keeps its real factors, as in the reference
+        P1, P2 = pauli_matrix(mu, dtype), pauli_matrix(nu, dtype)
+    else:
+        P1, P2 = _pauli_pair_factors(mu, nu)
     Id = np.eye(2)
     out = zeros_tto((2,) * d, [1] + [3] * (d - 1) + [1])
+    if cplx:
+        _complex_cores(out)
     c = out.tto_vec[0]
     c[:, :, 0, 1], c[:, :, 0, 2] = P1, Id
     for k in range(1, d - 1):
@@ -478,14 +507,14 @@ def pauli_pair_sum_tto(mu, nu, d: int) -> TToperator:
     return out
 
 
-def H_mu(mu, d: int) -> TToperator:
+def H_mu(mu, d: int, dtype=np.float64) -> TToperator:
     """Alias of pauli_sum_tto (src/tt_operators.jl:150)."""
-    return pauli_sum_tto(mu, d)
+    return pauli_sum_tto(mu, d, dtype)
 
 
-def H_munu(mu, nu, d: int) -> TToperator:
+def H_munu(mu, nu, d: int, dtype=np.float64) -> TToperator:
     """Alias of pauli_pair_sum_tto (src/tt_operators.jl:151)."""
-    return pauli_pair_sum_tto(mu, nu, d)
+    return pauli_pair_sum_tto(mu, nu, d, dtype)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@
 #include "ttn_expect_grad_kernels.h"
 #include "ttn_measure_kernels.h"
 #include "ttn_sample_kernels.h"
+#include "ttn_braket_kernels.h"
 
 #include <cstddef>
 
@@ -78,6 +79,15 @@ const struct { const void* fn; size_t lds; } lds_limits[] = {
     {(const void*)k_measure_open, MEASURE_LDS_BYTES(MEASURE_MAX_D)},
     {(const void*)k_measure_walk, MEASURE_LDS_BYTES(MEASURE_MAX_D)},
     {(const void*)k_sample_sweep, SAMPLE_LDS_BYTES},
+    {(const void*)k_zexpect<true, true, 0>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<true, true, 1>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<true, true, 2>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<false, true, 0>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<false, true, 1>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<false, true, 2>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<true, false, 0>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<true, false, 1>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_zexpect<true, false, 2>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
 };
 }  // namespace
 #endif  // TTN_HOST_LDS_H

@@ -636,6 +636,50 @@ def _header_define(header: str, name: str) -> int:
 MEASURE_MAX_OPS = _header_define("ttn_measure.h", "TTN_MEASURE_MAX_OPS")     # operator tables per site_expect call
 
 
+# ---- <x| A |y> with x conjugated, on ComplexF64 or Float64 operands (include/ttn_braket.h, csrc/ttn_braket_kernels.h) -----
+# limits of the on-chip route of ttn_braket: every n_k = 2, train ranks and operator ranks up to these; beyond them a train takes the
+# general route — the same number
+BRAKET_QTT_MAX_RANK = _header_define("ttn_braket.h", "TTN_BRAKET_QTT_MAX_RANK")
+BRAKET_QTT_MAX_OP_RANK = _header_define("ttn_braket.h", "TTN_BRAKET_QTT_MAX_OP_RANK")
+
+
+def _braket_args(x: DeviceTT, A: DeviceTTO, y: DeviceTT):
+    if not isinstance(A, DeviceTTO):
+        raise TypeError(f"braket: expected a DeviceTTO, got {type(A).__name__}")
+    if not isinstance(x, DeviceTT) or not isinstance(y, DeviceTT):
+        raise TypeError("braket: expected DeviceTT trains")
+
+
+def braket(x: DeviceTT, A: DeviceTTO, y: DeviceTT) -> np.ndarray:
+    """<x_b| A |y_b> = sum_ij conj(x_b[i]) A[i, j] y_b[j] per train in one sweep over the three cores of every site (ttn_braket): what
+    ``dot(x, apply(A, y))`` returns up to rounding, without the train A y.  x and y share an element type, the operator is real or
+    complex on its own; x may be y.  A complex128 array of ``batch`` entries (all operands Float64: ``sandwich``'s numbers, imaginary
+    parts 0).  Synchronises, as ``dot``."""
+    _braket_args(x, A, y)
+    out = (C.c_double * (2 * x.batch))()
+    _lib.check(_lib.lib().ttn_braket(x.h, A.h, y.h, out))
+    return np.array(out[:]).view(np.complex128)
+
+
+def braket_dev(x: DeviceTT, A: DeviceTTO, y: DeviceTT, out=None):
+    """``braket`` into a complex128 device tensor of ``batch`` entries (``out``, or a new one), asynchronously on the library stream:
+    no number crosses to the host.  The tensor must not be read on another stream before ``sync()``."""
+    import torch
+    _braket_args(x, A, y)
+    if out is None:
+        out = torch.empty(x.batch, dtype=torch.complex128, device="cuda")
+    if out.dtype != torch.complex128 or not out.is_cuda or not out.is_contiguous() or out.numel() != x.batch:
+        raise TypeError("braket_dev: out must be a contiguous complex128 device tensor with one entry per train")
+    _lib.check(_lib.lib().ttn_braket_dev(x.h, A.h, y.h, C.c_void_p(out.data_ptr())))
+    return out
+
+
+def energy(A: DeviceTTO, x: DeviceTT) -> np.ndarray:
+    """real(<x_b| A |x_b>) / real(<x_b, x_b>) per train — the reference's ``real(dot(psi, H * psi)) / real(dot(psi, psi))``, for either
+    element type."""
+    return np.real(braket(x, A, x)) / np.real(dot(x, x))
+
+
 def _measure_table(who: str, name: str, op, dims: Sequence[int]) -> np.ndarray:
     """One operator table of include/ttn_measure.h from ``op`` — an (n, n) array used at every site, or a sequence of d arrays —: the
     per-site matrices column-major, back to back, float64.  Shape and dtype errors are raised here, before any device call."""

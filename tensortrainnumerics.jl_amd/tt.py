@@ -300,6 +300,36 @@ def rayleigh(A: TToperator, x: TTvector) -> float:
     return expect(A, x) / dot(x, x)
 
 
+def braket(x: TTvector, A: TToperator, y: TTvector) -> complex:
+    """<x| A |y> = dot(x, A * y), x conjugated, in one sweep over the three cores of every site (ttn_braket): A * y is never formed.  The
+    trains and the operator are uploaded, the kernel runs, the handles are freed.  x and y share an element type (a real one next to a
+    complex one is promoted on the host, as in ``dot``); the operator keeps its own."""
+    from .device import DeviceTT, DeviceTTO, braket as dev_braket
+    assert tuple(A.tto_dims) == tuple(x.ttv_dims) == tuple(y.ttv_dims), "Incompatible dimensions"
+    dtype = np.complex128 if _is_cplx(x.ttv_vec, y.ttv_vec) else np.float64
+    dx = dA = dy = None
+    try:
+        dx = DeviceTT(x.ttv_dims, x.ttv_rks, 1, dtype=dtype)
+        dx.upload(0, x)
+        if y is x:
+            dy = dx
+        else:
+            dy = DeviceTT(y.ttv_dims, y.ttv_rks, 1, dtype=dtype)
+            dy.upload(0, y)
+        dA = DeviceTTO(A)
+        return complex(dev_braket(dx, dA, dy)[0])
+    finally:
+        for h in (dA, dy if dy is not dx else None, dx):
+            if h is not None:
+                h.free()
+
+
+def energy(A: TToperator, x: TTvector) -> float:
+    """real(<x| A |x>) / real(<x, x>) — the reference's ``real(dot(psi, H * psi)) / real(dot(psi, psi))`` without the train H * psi, for
+    real or complex psi and H."""
+    return float(np.real(braket(x, A, x)) / np.real(dot(x, x)))
+
+
 def site_expect(x: TTvector, *ops, normalize: bool = True) -> np.ndarray:
     """The profile <x| O_k |x> / <x, x> of every site (``device.site_expect``): (d,) for one operator, (nops, d) for several.  The train
     is uploaded, the kernels run, the handle is freed.  Float64 only."""
