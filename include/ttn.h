@@ -504,6 +504,18 @@ int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, doub
  * N x N, column-major, symmetric (both triangles); lam[k] = the k smallest eigenvalues ascending, Y[N*k] = their orthonormal vectors as
  * columns (no sign normalisation).  1 <= N <= 2048, 1 <= k <= min(N, 16); TTN_ERR_ARG otherwise, before anything is launched. */
 int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, double* Y);
+/* poison mode, a test switch (host side only, off by default).  While on: the per-call workspace is filled with the 8-byte
+ * `pattern` at every acquisition, before the entry point's first launch or copy into it; a new ttn_tt arena holds the pattern outside the
+ * live block of its rank-1 zero trains (the first el * n_k doubles of every slot stay zero); a new ttn_tto arena holds it wherever no core
+ * is uploaded; the self-test hooks above fill their workspace and output allocations with it instead of clearing them or leaving them
+ * raw.  No kernel differs.  on = 0 ends the mode (pattern ignored), and so does ttn_finalize.  Always TTN_OK. */
+int ttn_selftest_poison(int on, uint64_t pattern);
+/* probe: takes nbytes (>= 8) of the per-call workspace as an entry point does and returns the first 8 bytes and the last whole 8-byte
+ * word of the whole buffer (in poison mode: the pattern, twice) */
+int ttn_selftest_workspace_peek(int64_t nbytes, uint64_t* out_first8, uint64_t* out_last8);
+/* probe: a raw read of n doubles of train b's arena from double `offset` on (slot k starts at the sum of the earlier slots'
+ * el * n_j * cap_j * cap_{j+1}, each rounded up to even), live block and slack alike; offset + n within the train's arena */
+int ttn_selftest_tt_peek(ttn_tt_t h, int64_t b, int64_t offset, int64_t n, double* out);
 /* diagnostics of the last ttn_orthogonalize when it took the multi-launch form (csrc/ttn_ortho_ramp.h, ttn_ortho512.h): the four state
  * words of train b = {next site of the right-to-left sweep, buffer of the last right factor, buffer of the last left factor,
  * 1 if k_ortho512 finished the train (0: the 1024-thread kernel took it over from `next site`)}.  Read from the library's workspace:

@@ -124,6 +124,9 @@ SIGNATURES = {
     "ttn_tdvp_contract_f64": (C.c_int, [C.c_int, C.c_int, i64, p_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ttn_selftest_eig128": (C.c_int, [C.c_void_p, i64, i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ttn_selftest_sym_eig": (C.c_int, [i64, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ttn_selftest_poison": (C.c_int, [C.c_int, C.c_uint64]),
+    "ttn_selftest_workspace_peek": (C.c_int, [i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ttn_selftest_tt_peek": (C.c_int, [handle, i64, i64, i64, p_f64]),
     "ttn_add": (C.c_int, [handle, handle, handle]),
     "ttn_scale": (C.c_int, [C.c_double, handle, handle]),
     "ttn_scale_batch": (C.c_int, [p_f64, handle, handle]),

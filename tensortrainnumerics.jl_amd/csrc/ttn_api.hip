@@ -72,7 +72,7 @@ static int launch_chain(int kind, ttn_tt_t x, ttn_tt_t y, ttn_tt_t z, int n, int
     const long long srk_stride = 2 * nslots + 2;
     const long long per_train = per_compress + srk_stride + (long long)nslots * slot_doubles;
     const size_t tab_ints = ops.size() + final_slots.size();
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * batch + sizeof(int) * tab_ints + 64);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * batch + sizeof(int) * tab_ints + 64);
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
@@ -225,7 +225,7 @@ static int ttv_decomp_impl(ttn_tt_t z, const double* tensors, int64_t index, dou
     const long long per_scr = QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64;
     const long long per_train = 3 * total + per_scr;
     const int batch = z->batch;
-    int rc = g_scratch.ensure(sizeof(double) * ((size_t)per_train * batch + (on_device ? 0 : (size_t)total * batch)));
+    int rc = scratch_take(sizeof(double) * ((size_t)per_train * batch + (on_device ? 0 : (size_t)total * batch)));
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
@@ -321,7 +321,7 @@ int ttn_tt_split_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* nsplit, const int6
     carry = (carry + 1) & ~1LL; m2max = (m2max + 1) & ~1LL;
     const long long per_scr = QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64;
     const long long per_train = 2 * carry + m2max + per_scr;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * batch);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * batch);
     if (rc) return rc;
     double* base = g_scratch.as<double>();
     SplitArgs H;
@@ -411,7 +411,7 @@ int ttn_tt_merge_sites(ttn_tt_t x, ttn_tt_t z, const int64_t* merge_numbers, int
         for (int step = 1; step < maxcnt; ++step)
             if (step_tiles(g0, ng, step) >= (1LL << 31)) return fail(TTN_ERR_UNSUPPORTED, "ttn_tt_merge_sites: more than 2^31 output tiles in one core");
     }
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)std::max<long long>(2, wtot) * batch);
+    int rc = scratch_take(sizeof(double) * (size_t)std::max<long long>(2, wtot) * batch);
     if (rc) return rc;
     for (int g0 = 0; g0 < (int)ngroups; g0 += TTN_MERGE_GROUPS) {
         const int ng = std::min<int>(TTN_MERGE_GROUPS, (int)ngroups - g0);
@@ -546,7 +546,7 @@ static int dense_export(const char* who, const TTDev& tt, const int64_t* dims, c
     auto pad4 = [](long long v) { return (v + 3) & ~3LL; };
     const long long o_unit = 0, o_offL = 4, o_offR = o_offL + pad4(PL), o_rowL = o_offR + pad4(PR), o_colR = o_rowL + pad4((PL + 1) / 2),
                     o_L = o_colR + pad4((PR + 1) / 2), o_R = o_L + 2 * szL * batch, o_end = o_R + 2 * szR * batch;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)o_end);
+    int rc = scratch_take(sizeof(double) * (size_t)o_end);
     if (rc) return rc;
     double* base = g_scratch.as<double>();
     if (m == 0) {
@@ -810,7 +810,7 @@ int ttn_als_linsolve(ttn_tto_t A, ttn_tt_t b, ttn_tt_t x0, ttn_tt_t x, int64_t s
     const long long per_train = cur;
     const int batch = x->batch;
     const int nslots = grid_path ? 1 : batch;          // the grid form works on one train at a time (K alone can be gigabytes)
-    rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * nslots + sizeof(long long) * (size_t)(5 * d + 1) + 64);
+    rc = scratch_take(sizeof(double) * (size_t)per_train * nslots + sizeof(long long) * (size_t)(5 * d + 1) + 64);
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
@@ -933,7 +933,7 @@ static size_t two_site_bytes(const TwoSiteLayout& L, int batch) {
 static int two_site_prelude(MalsArgs& Q, const TwoSiteLayout& L, ttn_tto_t A, ttn_tt_t b, ttn_tt_t x, double tol, int64_t rmax, int mode,
                             const std::vector<int64_t>& plan) {
     const int batch = x->batch;
-    int rc = g_scratch.ensure(two_site_bytes(L, batch));
+    int rc = scratch_take(two_site_bytes(L, batch));
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * batch);
     if (rc) return rc;
@@ -1354,7 +1354,7 @@ int ttn_dot_pullback(ttn_tt_t a, ttn_tt_t b, const double* delta, ttn_tt_t abar,
     }
     if (tiles >= (1LL << 31) || batch > 65535) return fail(TTN_ERR_UNSUPPORTED, "ttn_dot_pullback: more than 2^31 output tiles in one core, or more than 65535 trains");
     const size_t per_train = (size_t)(2 * (d + 1) * W + 2 * tsz);
-    if ((rc = g_scratch.ensure(sizeof(double) * per_train * batch))) return rc;
+    if ((rc = scratch_take(sizeof(double) * per_train * batch))) return rc;
     if ((rc = g_dout.ensure(sizeof(double) * batch))) return rc;
     const double* d_delta = nullptr;
     if ((rc = grad_coef(delta, batch, 0, d_delta))) return rc;
@@ -1425,7 +1425,7 @@ int ttn_sandwich_pullback(ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, const double* del
     const long long gw = all_chip ? 0 : 4LL * d * nmax * S;
     // and, behind it all, one 32-bit route word per train.
     const size_t per_train = (size_t)(2LL * (d + 1) * W + 2 * wsz + gw);
-    if ((rc = g_scratch.ensure(sizeof(double) * per_train * batch + sizeof(int) * batch))) return rc;
+    if ((rc = scratch_take(sizeof(double) * per_train * batch + sizeof(int) * batch))) return rc;
     if ((rc = g_dout.ensure(sizeof(double) * batch))) return rc;
     const double* d_delta = nullptr;
     if ((rc = grad_coef(delta, batch, 0, d_delta))) return rc;
@@ -1542,7 +1542,8 @@ int ttn_selftest_gemm(int64_t m, int64_t n, int64_t k, const double* A, const do
     HIPCHK(hipMalloc((void**)&dC, sizeof(double) * m * n));
     HIPCHK(hipMemcpyAsync(dA, A, sizeof(double) * m * k, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dB, B, sizeof(double) * k * n, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(dC, C, sizeof(double) * m * n, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dC, C, sizeof(double) * m * n, hipMemcpyHostToDevice, g_stream));   // C is an accumulator (beta * C): uploaded whole; no
+                                                                                              // allocation of this hook is left for poison mode to fill
     if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {       // the same test against the 512-thread build
         const int rc512 = ttn_wg512_selftest_gemm((int)m, (int)n, (int)k, dA, dB, dC, alpha, beta, ta, tb, g_stream);
         if (rc512) return hipfail((hipError_t)rc512, "k_selftest_gemm (512-thread build)");
@@ -1573,7 +1574,7 @@ int ttn_selftest_syrk2(int64_t p1, int64_t q1, const double* A1, double* G1, dou
     HIPCHK(hipMemcpyAsync(dA1, A1, sizeof(double) * p1 * q1, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dA2, A2, sizeof(double) * p2 * q2, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dG1, G1, sizeof(double) * p1 * p1, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(dG2, G2, sizeof(double) * p2 * p2, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(dG2, G2, sizeof(double) * p2 * p2, hipMemcpyHostToDevice, g_stream));   // G_i are in/out by contract and uploaded whole (poison mode: nothing to fill)
     if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {       // the same test against the 512-thread build
         const int rc512 = ttn_wg512_selftest_syrk2((int)p1, (int)q1, dA1, dG1, alpha1, ta1, (int)p2, (int)q2, dA2, dG2, alpha2, ta2, pair, g_stream);
         if (rc512) return hipfail((hipError_t)rc512, "k_selftest_syrk2 (512-thread build)");
@@ -1608,7 +1609,7 @@ int ttn_selftest_gemm_ra2(int64_t m1, int64_t n1, int64_t k1, const double* A1, 
         HIPCHK(hipMalloc((void**)&dC[i], sizeof(double) * dm[i] * dn[i]));
         HIPCHK(hipMemcpyAsync(dA[i], hA[i], sizeof(double) * dm[i] * dk[i], hipMemcpyHostToDevice, g_stream));
         HIPCHK(hipMemcpyAsync(dB[i], hB[i], sizeof(double) * dk[i] * dn[i], hipMemcpyHostToDevice, g_stream));
-        HIPCHK(hipMemcpyAsync(dC[i], hC[i], sizeof(double) * dm[i] * dn[i], hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipMemcpyAsync(dC[i], hC[i], sizeof(double) * dm[i] * dn[i], hipMemcpyHostToDevice, g_stream));   // in/out by contract, uploaded whole (poison mode: nothing to fill)
     }
     if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {       // the same test against the 512-thread build
         const int rc512 = ttn_wg512_selftest_gemm_ra2((int)m1, (int)n1, (int)k1, dA[0], dB[0], dC[0], alpha1, f1, (int)m2, (int)n2, (int)k2, dA[1], dB[1], dC[1],
@@ -1642,7 +1643,8 @@ int ttn_selftest_lu_solve(int64_t N, const double* K, const double* rhs, double*
     HIPCHK(hipMalloc((void**)&dP, sizeof(int) * N));
     HIPCHK(hipMemcpyAsync(dK, K, sizeof(double) * N * N, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dR, rhs, sizeof(double) * N, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemsetAsync(dP, 0xff, sizeof(int) * N, g_stream));                     // -1: a column the elimination never reached
+    HIPCHK(hipMemsetAsync(dP, 0xff, sizeof(int) * N, g_stream));                     // -1: a column the elimination never reached — a sentinel the
+                                                                                     // caller reads by contract, so it stays in poison mode; K and rhs are uploaded whole
     HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g_stream));
     if (form == 0) hipLaunchKernelGGL(k_selftest_lu, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, (int)N, dK, dR, dP, d_flag);
     else lu_grid_solve(dK, dR, (int)N, dP, d_flag);
@@ -1675,7 +1677,8 @@ int ttn_selftest_two_site_apply(int64_t na, int64_t nb, int64_t Rz, const double
     HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * na * na * Rz, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dH, H, sizeof(double) * nb * nb * Rz, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(dv, v, sizeof(double) * N, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemsetAsync(dout, 0, sizeof(double) * N, g_stream));
+    // out is written whole, W is workspace: zeros / raw by default, the pattern in poison mode
+    { int rc; if ((rc = fresh_fill(dout, sizeof(double) * N, true)) || (rc = fresh_fill(dW, sizeof(double) * N * Rz, false))) return rc; }
     hipLaunchKernelGGL(k_selftest_two_site_apply, dim3(1), dim3(TTN_WG), COMPRESS_LDS_BYTES, g_stream, (int)na, (int)nb, (int)Rz, dG, dH, dv, dout, dW);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * N, hipMemcpyDeviceToHost, g_stream));
@@ -1697,8 +1700,12 @@ int ttn_selftest_eig128(const double* G, int64_t n, int64_t r, int64_t nev, doub
     HIPCHK(hipMalloc((void**)&dS, sizeof(double) * 128));
     HIPCHK(hipMalloc((void**)&dX, sizeof(double) * 128 * 64));
     HIPCHK(hipMalloc((void**)&dC, sizeof(long long) * 2));
+    // X, sig and the counters are outputs, V is workspace; none is an accumulator.  G is 128 x 128 however small n is: the routine is handed
+    // the n x n block only, so the rest is slack
+    if (g_poison) { const int rc = poison_fill(dG, sizeof(double) * 128 * 128); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * n * n, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemsetAsync(dX, 0, sizeof(double) * 128 * 64, g_stream));
+    { int rc; if ((rc = fresh_fill(dX, sizeof(double) * 128 * 64, true)) || (rc = fresh_fill(dV, sizeof(double) * 128 * 128, false)) ||
+                  (rc = fresh_fill(dS, sizeof(double) * 128, false)) || (rc = fresh_fill(dC, sizeof(long long) * 2, false))) return rc; }
     if (getenv("TTN_WG512_SELFTEST") && atoi(getenv("TTN_WG512_SELFTEST"))) {
         const int rc512 = ttn_wg512_selftest_eig(dG, dV, (int)n, (int)r, (int)nev, dS, dX, dC, g_stream);
         if (rc512) return hipfail((hipError_t)rc512, "k_selftest_eig128 (512-thread build)");
@@ -1729,13 +1736,44 @@ int ttn_selftest_sym_eig(int64_t N, int64_t k, const double* A, double* lam, dou
     HIPCHK(hipMalloc((void**)&dY, sizeof(double) * N * k));
     HIPCHK(hipMalloc((void**)&dW, sizeof(double) * (3 * N + 5 * N * k)));
     HIPCHK(hipMemcpyAsync(dA, A, sizeof(double) * N * N, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemsetAsync(dY, 0, sizeof(double) * N * k, g_stream));
+    // lam and Y are written whole, W is the routine's workspace (a slice of the per-call workspace in production)
+    { int rc; if ((rc = fresh_fill(dY, sizeof(double) * N * k, true)) || (rc = fresh_fill(dL, sizeof(double) * k, false)) ||
+                  (rc = fresh_fill(dW, sizeof(double) * (3 * N + 5 * N * k), false))) return rc; }
     hipLaunchKernelGGL(k_selftest_sym_eig, dim3(1), dim3(TTN_WG), 0, g_stream, (int)N, (int)k, dA, dL, dY, dW);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(lam, dL, sizeof(double) * k, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(Y, dY, sizeof(double) * N * k, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     hipFree(dA); hipFree(dL); hipFree(dY); hipFree(dW);
+    return TTN_OK;
+}
+
+// Poison mode (ttn_host_core.h) and the two probes that let a test prove the fills happen.  Host side only.
+int ttn_selftest_poison(int on, uint64_t pattern) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    g_poison = on != 0;
+    g_poison_pat = g_poison ? (unsigned long long)pattern : 0ULL;
+    return TTN_OK;
+}
+// Takes `nbytes` of the per-call workspace as an entry point does; the first 8 bytes and the last whole 8-byte word of the WHOLE buffer.
+int ttn_selftest_workspace_peek(int64_t nbytes, uint64_t* out_first8, uint64_t* out_last8) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (nbytes < 8 || !out_first8 || !out_last8) return fail(TTN_ERR_ARG, "ttn_selftest_workspace_peek: need nbytes >= 8 and two outputs");
+    const int rc = scratch_take((size_t)nbytes);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out_first8, g_scratch.p, 8, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(out_last8, g_scratch.as<char>() + (g_scratch.bytes / 8 - 1) * 8, 8, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return TTN_OK;
+}
+// Raw read of n doubles of train b's arena from `offset` on (slot offsets: the handle's layout, include/ttn.h), live or slack alike.
+int ttn_selftest_tt_peek(ttn_tt_t h, int64_t b, int64_t offset, int64_t n, double* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    NEED_INIT();
+    if (!h || !out || b < 0 || b >= h->batch || offset < 0 || n < 0 || offset > h->stride || n > h->stride - offset) return fail(TTN_ERR_ARG, "ttn_selftest_tt_peek: bad argument");
+    if (n) HIPCHK(hipMemcpyAsync(out, h->d_data + (size_t)b * h->stride + offset, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
     return TTN_OK;
 }
 
@@ -1765,7 +1803,7 @@ static int tdvp_launch(int op, int cplx, int64_t batch, int64_t Dl, int64_t d, i
     const long long mb = m_shared ? 1 : batch;
     const size_t work_d = (size_t)(w1 + w2) * es * batch;
     const size_t stage_d = host ? (size_t)es * ((nFL + nFR + nX + nOut) * batch + (nM1 + nM2) * mb) : 0;
-    int rc = g_scratch.ensure(sizeof(double) * (work_d + stage_d));
+    int rc = scratch_take(sizeof(double) * (work_d + stage_d));
     if (rc) return rc;
     double* base = g_scratch.as<double>();
     TdvpArgs P;
@@ -1828,7 +1866,7 @@ int ttn_dense_qr(int cplx, int64_t m, int64_t n, double* A, double* Q, double* R
     if (!A || !Q || !R || m < 1 || n < 1) return fail(TTN_ERR_ARG, "ttn_dense_qr: bad argument");
     if (m > (1 << 20) || n > (1 << 20)) return fail(TTN_ERR_UNSUPPORTED, "ttn_dense_qr: matrix too large");
     const int64_t r = std::min(m, n);
-    int rc = g_scratch.ensure(sizeof(double) * 2 * (size_t)r + 64);
+    int rc = scratch_take(sizeof(double) * 2 * (size_t)r + 64);
     if (rc) return rc;
     if (cplx) hipLaunchKernelGGL(k_dense_qr<true>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, Q, R, g_scratch.as<double>());
     else hipLaunchKernelGGL(k_dense_qr<false>, dim3(1), dim3(TTN_DF_WG), 0, g_stream, (int)m, (int)n, A, Q, R, g_scratch.as<double>());
@@ -1843,7 +1881,7 @@ int ttn_dense_svd(int cplx, int64_t m, int64_t n, double* A, double* U, double* 
     if (m > (1 << 20) || n > 4096) return fail(TTN_ERR_UNSUPPORTED, "ttn_dense_svd: matrix too large");
     const size_t w = cplx ? 2 : 1;
     const size_t vw = sizeof(double) * w * (size_t)n * n, dwb = sizeof(double) * ((size_t)n + (size_t)m);
-    int rc = g_scratch.ensure(vw + dwb + sizeof(int) * ((size_t)n + 2) + 64);
+    int rc = scratch_take(vw + dwb + sizeof(int) * ((size_t)n + 2) + 64);
     if (rc) return rc;
     double* Vw = g_scratch.as<double>();
     double* dw = Vw + w * (size_t)n * n;
@@ -1872,7 +1910,7 @@ int ttn_cross_maxvol(int cplx, int64_t m, int64_t r, const double* A, double tol
     const size_t w = cplx ? 2 : 1, cbytes = sizeof(double) * w * (size_t)m * (size_t)r;
     const int use_lds = cbytes <= TTN_XV_LDS_C ? 1 : 0;
     const size_t wbytes = use_lds ? 0 : cbytes;
-    int rc = g_scratch.ensure(wbytes + sizeof(int) * (size_t)m + 64);
+    int rc = scratch_take(wbytes + sizeof(int) * (size_t)m + 64);
     if (rc) return rc;
     if (!dinfo) {
         if ((rc = g_cross_info.ensure(sizeof(int64_t) * 2))) return rc;
@@ -2005,7 +2043,7 @@ int ttn_cross_batch_site(int64_t A, int dir, int64_t N, int64_t site, int64_t n,
     const size_t sz = (size_t)m * (size_t)r;
     const int use_lds = 2 * sizeof(double) * sz <= TTN_XB_LDS_MAT ? 1 : 0;
     const size_t stride = (use_lds ? 0 : 2 * sz) + (dir == 0 ? 0 : sz) + ((size_t)m + 1) / 2;       // doubles per function
-    int rc = g_scratch.ensure(sizeof(double) * stride * (size_t)A + 64);
+    int rc = scratch_take(sizeof(double) * stride * (size_t)A + 64);
     if (rc) return rc;
     const size_t lds = (use_lds ? 2 * sizeof(double) * sz : 0) + TTN_XB_LDS_SMALL(r);
     const int mi = (int)std::min<int64_t>(maxiter, 1 << 30);
@@ -2450,7 +2488,7 @@ static int als_eig_impl(int gen, ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t
     int64_t hoff = 0;
     for (int64_t j = 0; j < n_stages; ++j) {
         if (j > 0) {                                                   // increase_ranks -> orthogonalize (als.jl:291-292, :377-378)
-            if ((rc = g_scratch.ensure(need))) return rc;
+            if ((rc = scratch_take(need))) return rc;                  // nothing survives: k_increase_ranks only writes Tm .. Tst before it reads them
             HIPCHK(hipMemcpyAsync(d_rn, stage_rks[j].data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
             IncArgs Ia;
             memset(&Ia, 0, sizeof(Ia));
@@ -2468,7 +2506,9 @@ static int als_eig_impl(int gen, ttn_tto_t A, ttn_tto_t S, ttn_tt_t x0, ttn_tt_t
         }
         const int64_t nsw = sweep_schedule[j] - (j ? sweep_schedule[j - 1] : 1);
         if (nsw > 0) {
-            if ((rc = g_scratch.ensure(need))) return rc;              // ttn_orthogonalize shares the workspace: taken again every stage
+            // ttn_orthogonalize shares the workspace, so it is taken again every stage — and nothing of the stage before survives:
+            // k_als_eig rebuilds G_1 and every H_i from the cores first thing (init_env), whatever the workspace holds
+            if ((rc = scratch_take(need))) return rc;
             Rg.x = x->dev();
             Rg.scratch = g_scratch.as<double>(); Rg.scratch_stride = per_train;
             Rg.nsweeps = (int)nsw;
@@ -2549,7 +2589,7 @@ int ttn_tt_increase_ranks(ttn_tt_t x, const int64_t* new_rks, double noise, uint
     Ia.offWb = cur; cur += QR_NB * mmax;
     Ia.offTst = cur; cur += ((cmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64;
     const long long per_train = noise != 0.0 ? cur : 1;                 // (zero padding alone touches no scratch)
-    if ((rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * batch)) || (rc = g_als_tab.ensure(sizeof(long long) * (d + 1)))) return rc;
+    if ((rc = scratch_take(sizeof(double) * (size_t)per_train * batch)) || (rc = g_als_tab.ensure(sizeof(long long) * (d + 1)))) return rc;
     std::vector<long long> rn(new_rks, new_rks + d + 1);
     HIPCHK(hipMemcpyAsync(g_als_tab.p, rn.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     Ia.x = x->dev(); Ia.y = y->dev(); Ia.rn = g_als_tab.as<const long long>();
@@ -2897,7 +2937,8 @@ int ttn_tto_from_tt_batch(ttn_tt_t v, ttn_tto_t* out) {
     OwnedTTO Y;
     int rc;
     if ((rc = tto_alloc("ttn_tto_from_tt_batch", 1, d, dims.data(), rks.data(), same_ot ? v->ot.data() : nullptr, nullptr, Y, batch))) return rc;
-    HIPCHK(hipMemsetAsync(Y.h->d_data, 0, sizeof(double) * (size_t)std::max<long long>(Y.h->stride, 1) * batch, g_stream));     // the rounding gaps of odd cores
+    if (!g_poison)                                                     // the rounding gaps of odd cores (poison mode: tto_alloc's pattern stays in them)
+        HIPCHK(hipMemsetAsync(Y.h->d_data, 0, sizeof(double) * (size_t)std::max<long long>(Y.h->stride, 1) * batch, g_stream));
     TTODev dst = Y.h->dev();
     dst.stride = Y.h->stride;
     hipLaunchKernelGGL(k_tto_pack, stream_grid((maxsz + 1) / 2, d, batch), dim3(TTN_STREAM_TB), 0, g_stream, v->dev(), dst, Y.h->d_data);
@@ -3128,6 +3169,7 @@ int ttn_finalize(void) {
     for (hipEvent_t e : {g_ev0, g_ev1, g_launch_ev0, g_launch_ev1}) hipEventDestroy(e);
     g_have_launch_ms = false;
     g_ortho_state_batch = 0;
+    g_poison = false;                   // a test switch does not outlive the library state it was set on
     for (auto e : g_slots) if (e) hipEventDestroy(e);
     g_slots.clear();
     if (g_xb_tab_ev) { hipEventDestroy(g_xb_tab_ev); g_xb_tab_ev = nullptr; }

@@ -73,7 +73,7 @@ static int braket_launch(const char* who, ttn_tt_t x, ttn_tto_t A, ttn_tt_t y, d
     const bool any_general = !qtt || rxmax > BRAKET_QTT_RMAX || rymax > BRAKET_QTT_RMAX;
     const long long general = any_general ? 2 * (2 + 2 * nmax) * rxmax * rymax * Rmax : 0;
     const long long per_train = std::max<long long>(general, qtt ? 2 * Rmax * BRAKET_IMG : 0) + 16;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * x->batch);
     if (rc) return rc;
     BraketArgs P;
     P.x = x->dev(); P.y = y->dev(); P.A = A->dev();

@@ -85,11 +85,11 @@ static int compress_precheck(ttn_tt_t psi, const std::vector<int64_t>& bound, in
     if (psi->el == 2) {                        // k_zcompress: one workgroup per train
         if (pmax > TTN_ZC_PMAX || qmax > TTN_ZC_QMAX) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress (ComplexF64): merged matrix larger than 512 x 8192");
         per_train = zcompress_scratch(pmax, qmax);
-        return g_scratch.ensure(sizeof(double) * (size_t)per_train * psi->batch);
+        return scratch_take(sizeof(double) * (size_t)per_train * psi->batch);
     }
     if (pmax > 4096 || qmax > 16384) return fail(TTN_ERR_UNSUPPORTED, "ttn_compress: merged matrix larger than 4096 x 16384");
     per_train = 2 * pmax * qmax + QR_NB * qmax + pmax * QR_NB + 2 * pmax * pmax + 4 * pmax + 64 + 6 * 128 * 128;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * compress_slots(psi->batch));
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * compress_slots(psi->batch));
     if (rc) return rc;
     return g_dout.ensure(sizeof(double) * psi->batch);
 }
@@ -258,6 +258,7 @@ int ttn_apply_compress(ttn_tto_t A, ttn_tt_t x, ttn_tt_t y, int64_t max_bond, do
     // what it held (ranks, bounds, gauge flags and cores)
     std::vector<int64_t> yb(d + 1), fin_;
     for (int m = 0; m <= d; ++m) yb[m] = A->rks[m] * x->bound[m];
+    // (the workspace is taken here for its size alone — launch_compress takes it again, nothing is in it in between)
     if (d >= 2) { long long pm_, qm_, pt_; if ((rc = compress_precheck(y, yb, 0, max_bond, sweeps, 0, 0, fin_, pm_, qm_, pt_))) return rc; }
     if (cplx) {
         if ((rc = ttn_apply(A, x, y))) return rc;

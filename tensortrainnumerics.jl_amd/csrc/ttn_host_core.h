@@ -79,7 +79,44 @@ struct DevBuf {
 DevBuf g_scratch;          // per-call workspace of every launch
 DevBuf g_dout;             // [batch] doubles: dot results, the factors of ttn_scale_batch
 DevBuf g_pending_status;   // one bit per failure code of handles FREED before anybody queried them (ttn_status_all)
+
+// Poison mode (ttn_selftest_poison): a test switch, host side only.  While it is on, the per-call workspace is filled with
+// an 8-byte pattern at every acquisition, and new handle arenas and the self-test hooks' allocations are filled with it instead of being
+// cleared or left raw — a kernel that reads a byte nobody wrote then computes with the pattern instead of with zeros or plausible stale
+// numbers.  Off (the default) it costs one host-side test per acquisition or creation and launches nothing.
+bool g_poison = false;
+unsigned long long g_poison_pat = 0;
 }  // namespace
+
+__global__ void k_poison_fill(unsigned long long* p, size_t n, unsigned long long pat) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = pat;
+}
+// `bytes` of device memory at p (8-byte aligned) <- the pattern, on the library stream; the up to 7 bytes behind the last whole word: 0xff
+static int poison_fill(void* p, size_t bytes) {
+    const size_t n = bytes / 8;
+    if (n) {
+        hipLaunchKernelGGL(k_poison_fill, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, g_stream,
+                           static_cast<unsigned long long*>(p), n, g_poison_pat);
+        HIPCHK(hipGetLastError());
+    }
+    if (bytes % 8) HIPCHK(hipMemsetAsync(static_cast<char*>(p) + 8 * n, 0xff, bytes % 8, g_stream));
+    return TTN_OK;
+}
+// The acquisition of the per-call workspace: every entry point that launches on g_scratch takes it here, before its first launch or
+// copy into it.  Nothing an earlier call left there may be read afterwards; in poison mode the whole buffer is overwritten to prove it.
+static int scratch_take(size_t n) {
+    const int rc = g_scratch.ensure(n);
+    if (rc || !g_poison) return rc;
+    return poison_fill(g_scratch.p, g_scratch.bytes);
+}
+// There is no non-filling form: no entry point needs workspace contents across a second acquisition today (DESIGN §4.32 lists the
+// candidates and why each rebuilds what it reads).  One that does must add such a form here and say what survives it, and why.
+// A fresh device allocation of a handle or a self-test hook: the pattern in poison mode, else zeros (`clear`) or left raw
+static int fresh_fill(void* p, size_t bytes, bool clear) {
+    if (g_poison) return poison_fill(p, bytes);
+    if (clear) HIPCHK(hipMemsetAsync(p, 0, bytes, g_stream));
+    return TTN_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // handles

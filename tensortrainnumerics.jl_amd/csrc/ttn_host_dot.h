@@ -23,7 +23,7 @@ static int zdot(ttn_tt_t a, ttn_tt_t b, double* out) {
     for (int k = 0; k < d; ++k) tmax = std::max<long long>(tmax, a->dims[k] * a->bound[k] * b->bound[k + 1]);
     const long long per_train = 2 * (wmax + tmax);
     const int in_lds = per_train <= TTN_ZDOT_LDS_DOUBLES ? 1 : 0;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * a->batch);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * a->batch);
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * 2 * a->batch);
     if (rc) return rc;
@@ -57,7 +57,7 @@ int ttn_dot(ttn_tt_t a, ttn_tt_t b, double* out) {
     for (int m = 0; m <= d; ++m) { ramax = std::max<long long>(ramax, a->bound[m]); rbmax = std::max<long long>(rbmax, b->bound[m]); }
     for (int k = 0; k < d; ++k) nmax = std::max<long long>(nmax, a->dims[k]);
     const long long per_train = (2 + nmax) * ramax * rbmax + 16;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * a->batch);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * a->batch);
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * a->batch);
     if (rc) return rc;
@@ -99,7 +99,7 @@ static int sandwich_launch(const char* who, ttn_tt_t x, ttn_tto_t A, ttn_tt_t y,
         return fail(TTN_ERR_UNSUPPORTED, "ttn_sandwich: ranks too large (the three-layer state of one train reaches 2^31 doubles)");
     const long long general = (2 + 2 * nmax) * rxmax * rymax * Rmax;
     const long long per_train = std::max<long long>(general, qtt ? Rmax * EXPECT_IMG_STATE : 0) + 16;
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * x->batch);
     if (rc) return rc;
     ExpectArgs P;
     P.x = x->dev(); P.y = y->dev(); P.A = A->dev();
@@ -199,7 +199,7 @@ int ttn_orthogonalize(ttn_tt_t x, int64_t center, ttn_tt_t y) {
     const long long mm = nmax * rmax;           // rows of the tall matrices
     const long long per_train = 2 * mm * rmax + 4 * rmax * rmax + 2 * QR_NB * mm + ((rmax + QR_NB - 1) / QR_NB) * QR_NB * QR_NB + 64   // Tm, Qb, 4 R, Vb, Wb, T panels
                                 + 3 * 128 * 128;                                                                                  // Gram matrices / L1 of the Cholesky-QR steps
-    int rc = g_scratch.ensure(sizeof(double) * (size_t)per_train * x->batch + sizeof(int) * (5 * (size_t)x->batch + 16) + 64);
+    int rc = scratch_take(sizeof(double) * (size_t)per_train * x->batch + sizeof(int) * (5 * (size_t)x->batch + 16) + 64);
     if (rc) return rc;
     rc = g_dout.ensure(sizeof(double) * x->batch);
     if (rc) return rc;

@@ -85,7 +85,10 @@ static int tt_create_impl(int64_t d, const int64_t* dims, const int64_t* cap_rks
     HIPCHK(hipMemcpyAsync(h->d_cap, cap64.data(), sizeof(long long) * (d + 1), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_rks, rk0.data(), sizeof(long long) * rk0.size(), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(h->d_dims, idims.data(), sizeof(int) * d, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemsetAsync(h->d_data, 0, sizeof(double) * (size_t)o * batch, g_stream));
+    { const int rc = fresh_fill(h->d_data, sizeof(double) * (size_t)o * batch, true); if (rc) return rc; }
+    if (g_poison)                                      // the live block of the rank-1 zero train: el * n_k doubles at the start of every slot
+        for (int64_t k = 0; k < d; ++k)
+            HIPCHK(hipMemset2DAsync(h->d_data + h->off[k], sizeof(double) * (size_t)o, 0, sizeof(double) * (size_t)el * dims[k], (size_t)batch, g_stream));
     HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int) * 2 * (size_t)batch, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     g_live.insert(h);
@@ -270,8 +273,13 @@ static int tto_alloc(const char* who, int el, int64_t d, const int64_t* dims, co
         return hipfail(e, "hipMalloc(ttn_tto)");
     h->d_dims2 = h->d_dims + d;
     std::vector<double> flat;                           // the cores at their slots, the rounding gaps zero
-    if (cores) {
-        flat.assign((size_t)o * (size_t)batch, 0.0);
+    if (!cores) {                                       // the producing kernels write every core whole; raw unless poison mode fills it
+        const int rc = fresh_fill(h->d_data, sizeof(double) * (size_t)std::max<long long>(o, 1) * (size_t)batch, false);
+        if (rc) return rc;
+    } else {
+        double gap = 0.0;                               // (poison mode: the pattern in the gaps)
+        if (g_poison) std::memcpy(&gap, &g_poison_pat, sizeof(gap));
+        flat.assign((size_t)o * (size_t)batch, gap);
         for (int64_t b = 0; b < batch; ++b)
             for (int64_t k = 0; k < d; ++k)
                 std::memcpy(flat.data() + (size_t)b * (size_t)o + h->off[k], cores[b * d + k], sizeof(double) * (size_t)el * dims[k] * dims[k] * rks[k] * rks[k + 1]);

@@ -62,7 +62,7 @@ static int measure_run(ttn_tt_t x, const MeasurePlan& M, int ntab, const double*
     const long long chunk = std::max<long long>(1, std::min<long long>(std::min<long long>(batch, 65535),
                                                                        TTN_MEASURE_CHUNK_BYTES / (long long)(sizeof(double) * M.per_train)));
     int rc;
-    if ((rc = g_scratch.ensure(sizeof(double) * (size_t)M.per_train * (size_t)chunk))) return rc;
+    if ((rc = scratch_take(sizeof(double) * (size_t)M.per_train * (size_t)chunk))) return rc;
     if ((rc = g_measure_tab.ensure(sizeof(double) * g_measure_host.size()))) return rc;
     HIPCHK(hipEventRecord(g_launch_ev0, g_stream));
     HIPCHK(hipMemcpyAsync(g_measure_tab.p, g_measure_host.data(), sizeof(double) * g_measure_host.size(), hipMemcpyHostToDevice, g_stream));

@@ -60,7 +60,7 @@ static int sample_run(ttn_tt_t x, const SamplePlan& M, int64_t nsamples, int64_t
     long long tiles = std::min<long long>(tiles_all, 1LL << 20);
     if (M.per_tile) tiles = std::max<long long>(1, std::min<long long>(tiles, (budget - chunk * M.per_train) / (chunk * M.per_tile)));
     int rc;
-    if ((rc = g_scratch.ensure(sizeof(double) * (size_t)(chunk * M.per_train + chunk * tiles * M.per_tile)))) return rc;
+    if ((rc = scratch_take(sizeof(double) * (size_t)(chunk * M.per_train + chunk * tiles * M.per_tile)))) return rc;
     int nchunks = 0;
     if (d_info) HIPCHK(hipMemsetAsync(d_info, 0, sizeof(int64_t) * 2 * (size_t)batch, g_stream));
     for (long long b0 = 0; b0 < batch; b0 += chunk) {

@@ -41,6 +41,13 @@ def to_oracle(x):
     return O.TToperator(x.N, [np.array(c) for c in x.tto_vec], tuple(x.tto_dims), list(x.tto_rks), list(x.tto_ot))
 
 
+def worst_of(*vals):
+    """max() for folding errors that KEEPS a NaN.  Python's max(0.0, nan) is 0.0: a fold `worst = max(worst, err)` drops a NaN error and
+    the `worst <= tol` behind it passes.  With this one it fails, as `nan <= tol` is false."""
+    vals = [float(v) for v in vals]
+    return float("nan") if any(v != v for v in vals) else max(vals)
+
+
 def tt_norm_stable(x):
     """||x|| without the cancellation of dot(x,x) on differences: orthogonalize to site 1 (oracle) and take
     the Frobenius norm of the centre core."""

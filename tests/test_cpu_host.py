@@ -45,7 +45,7 @@ def _ctypes_of(ctype: str):
     """ctypes types a C parameter type of ttn.h may be bound as (device pointers travel as c_void_p)."""
     L = ctypes
     table = {
-        "int": [L.c_int], "int64_t": [L.c_int64], "double": [L.c_double],
+        "int": [L.c_int], "int64_t": [L.c_int64], "double": [L.c_double], "uint64_t": [L.c_uint64], "uint64_t*": [L.POINTER(L.c_uint64)],
         "int*": [L.POINTER(L.c_int), L.c_void_p], "int64_t*": [L.POINTER(L.c_int64), L.c_void_p],
         "double*": [L.POINTER(L.c_double), L.c_void_p], "float*": [L.POINTER(L.c_float)],
         "double**": [L.POINTER(L.POINTER(L.c_double))], "void**": [L.POINTER(L.c_void_p)],

@@ -14,7 +14,7 @@ import pytest
 from oracle import tt_oracle as O
 from tests import expect_grad_reference as ER
 from tests import grad_reference as GR
-from tests.helpers import to_oracle, to_product
+from tests.helpers import to_oracle, to_product, worst_of
 from tests.test_cpu_expect import mixed_case
 from tests.test_cpu_expect_grad import mixed5_case
 from tests.test_cpu_grad import _rand_op
@@ -58,7 +58,7 @@ def _share(got, ref, bound):
         assert np.all(err <= bd), "entry beyond its bound: worst ratio %.3g" % float(np.max(err / np.maximum(bd, 1e-300)))
         nz = bd > 0
         if np.any(nz):
-            worst = max(worst, float(np.max(err[nz] / bd[nz])))
+            worst = worst_of(worst, float(np.max(err[nz] / bd[nz])))
     return worst
 
 
@@ -84,7 +84,7 @@ def _check_abs(T, name, xs, A, ys, deltas, same):
         dl = 1.0 if deltas is None else float(np.broadcast_to(deltas, (len(xs),))[t])
         rv, rx, ry = ER.sandwich_pullback(x, aA, y, dl)
         bv, bx, by = ER.sandwich_pullback_bound(x, aA, y, dl)
-        worst = max(worst, _share(xbar.download(t).ttv_vec, rx, bx), _share(ybar.download(t).ttv_vec, ry, by))
+        worst = worst_of(worst, _share(xbar.download(t).ttv_vec, rx, bx), _share(ybar.download(t).ttv_vec, ry, by))
         assert abs(val[t] - rv) <= bv
     print("sandwich_pullback %s, absolute values: largest share of the bound %.3g" % (name, worst))
     _free(hx, hy, hA, xbar, ybar)
@@ -112,7 +112,7 @@ def _check(T, name, xs, A, ys, deltas=None, same=False, capx=None, capy=None):
         _, bx, by = ER.sandwich_pullback_bound(x, A, y, dl)
         gx, gy = xbar.download(t), ybar.download(t)
         assert gx.ttv_rks == list(x.ttv_rks) and gy.ttv_rks == list(y.ttv_rks) and gx.ttv_ot == [0] * x.N and gy.ttv_ot == [0] * y.N
-        worst = max(worst, _share(gx.ttv_vec, rx, bx), _share(gy.ttv_vec, ry, by))
+        worst = worst_of(worst, _share(gx.ttv_vec, rx, bx), _share(gy.ttv_vec, ry, by))
         sc = _scale(x, A, y)
         assert abs(val[t] - rv) <= 1e-12 * sc and abs(val[t] - sand[t]) <= 1e-12 * sc
         # Euler: N pairings, each another summation order of s
@@ -247,7 +247,7 @@ def test_open_boundary_ranks(T, name):
             bv, bx, by = ER.sandwich_pullback_bound(x, A_, y, deltas[t])
             gx, gy = xbar.download(t), ybar.download(t)
             assert gx.ttv_rks == list(x.ttv_rks) and gy.ttv_rks == list(y.ttv_rks)
-            w = max(w, _share(gx.ttv_vec, rx_, bx), _share(gy.ttv_vec, ry_, by))
+            w = worst_of(w, _share(gx.ttv_vec, rx_, bx), _share(gy.ttv_vec, ry_, by))
             assert abs(val[t] - rv) <= bv
         worst.append(w)
         _same(hx, xs_)

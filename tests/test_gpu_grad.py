@@ -13,7 +13,7 @@ import pytest
 
 from oracle import tt_oracle as O
 from tests import grad_reference as GR
-from tests.helpers import to_oracle, to_product
+from tests.helpers import to_oracle, to_product, worst_of
 from tests.test_cpu_grad import FD_EPS, _close, _dirs, _ising, _rand_op, check_descent, descent_setup
 
 pytestmark = pytest.mark.gpu
@@ -56,7 +56,7 @@ def _share(got, ref, bound):
         assert np.all(err <= bd), "entry beyond 2 p eps S_abs: worst ratio %.3g" % float(np.max(err / np.maximum(bd, 1e-300)))
         nz = bd > 0
         if np.any(nz):
-            worst = max(worst, float(np.max(err[nz] / bd[nz])))
+            worst = worst_of(worst, float(np.max(err[nz] / bd[nz])))
     return worst
 
 
@@ -71,7 +71,7 @@ def _check_dot_pullback(T, name, As, Bs, deltas, same_handle=False):
         _, ba, bb = GR.dot_pullback_bound(A, B, dl)
         ga, gb = abar.download(t), bbar.download(t)
         assert ga.ttv_rks == list(A.ttv_rks) and gb.ttv_rks == list(B.ttv_rks) and ga.ttv_ot == [0] * A.N
-        worst = max(worst, _share(ga.ttv_vec, ra, ba), _share(gb.ttv_vec, rb, bb))
+        worst = worst_of(worst, _share(ga.ttv_vec, ra, ba), _share(gb.ttv_vec, rb, bb))
         assert abs(val[t] - O.dot(A, B)) <= 1e-12 * O.norm(A) * O.norm(B)            # the tolerance of the dot parity tests
         assert abs(val[t] - rv) <= 1e-12 * O.norm(A) * O.norm(B)
     print("dot_pullback %s: largest share of the bound %.3g" % (name, worst))
@@ -149,7 +149,7 @@ def _check_apply_pullback(T, name, H, xs):
         ref = GR.apply_pullback(H, ybs[t].ttv_vec, xt.ttv_rks)
         got = xb.download(t)
         assert got.ttv_rks == list(xt.ttv_rks)
-        worst = max(worst, _share(got.ttv_vec, ref, GR.apply_pullback_bound(H, ybs[t].ttv_vec, xt.ttv_rks)))
+        worst = worst_of(worst, _share(got.ttv_vec, ref, GR.apply_pullback_bound(H, ybs[t].ttv_vec, xt.ttv_rks)))
     print("apply_pullback %s: largest share of the bound %.3g" % (name, worst))
     _same(T, x, xs)
     _same(T, yb, ybs)

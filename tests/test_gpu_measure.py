@@ -14,6 +14,7 @@ import pytest
 
 import ttn_amd as T
 from tests import measure_reference as R
+from tests.helpers import worst_of
 from ttn_amd import device as D
 
 pytestmark = pytest.mark.gpu
@@ -124,8 +125,8 @@ def test_batch_beyond_one_workspace_chunk():
     E = D.site_expect(h, P)
     refC, refE = R.dense_correlation(trains[0], P, Q), R.dense_site_expect(trains[0], P)
     assert C.shape == (B, d, d) and E.shape == (B, d)
-    errC = max(float(np.max(np.abs(C[b] - refC) / np.outer(pn, qn))) for b in range(B))
-    errE = max(float(np.max(np.abs(E[b] - refE) / pn)) for b in range(B))
+    errC = worst_of(*(float(np.max(np.abs(C[b] - refC) / np.outer(pn, qn))) for b in range(B)))
+    errE = worst_of(*(float(np.max(np.abs(E[b] - refE) / pn)) for b in range(B)))
     print(f"{B} trains in chunks: worst err/scale C {errC:.2e} E {errE:.2e}")
     assert errC <= TOL and errE <= TOL
     h.free()
@@ -249,7 +250,7 @@ def test_tie_to_sandwich_d30():
             hA = T.DeviceTTO(A)
             ref = D.sandwich(h, hA, h)[0] / nn
             hA.free()
-            worst = max(worst, abs(C[a, b] - ref) / scale)
+            worst = worst_of(worst, abs(C[a, b] - ref) / scale)
     print(f"five pairs, both orders, against sandwich / dot: worst err/scale {worst:.2e}")
     assert worst <= TOL
     h.free()

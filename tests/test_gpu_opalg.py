@@ -15,7 +15,7 @@ import pytest
 import ttn_amd as T
 from oracle import tt_oracle as O
 from tests import opalg_reference as R
-from tests.helpers import to_oracle, to_product
+from tests.helpers import to_oracle, to_product, worst_of
 from ttn_amd import _lib
 from ttn_amd import device as D
 
@@ -74,7 +74,7 @@ def test_mul(dims, ra, rb):
     for k in range(len(dims)):
         assert got.tto_vec[k].shape == ref.tto_vec[k].shape
         err = np.abs(got.tto_vec[k] - ref.tto_vec[k])
-        worst = max(worst, float((err / np.maximum(bound[k], 1e-300)).max()))
+        worst = worst_of(worst, float((err / np.maximum(bound[k], 1e-300)).max()))
         assert (err <= bound[k]).all(), (k, worst)
     print(f"mul {dims} {ra} x {rb}: max error / bound = {worst:.3f}")
     for h in (dA, dB, Y):

@@ -14,6 +14,7 @@ import pytest
 
 import ttn_amd as T
 from tests import sample_reference as R
+from tests.helpers import worst_of
 from ttn_amd import cross
 from ttn_amd import device as D
 
@@ -66,8 +67,8 @@ def check_parity(tag, trains, res, got, born):
         assert int((~ok).sum()) <= R.FRAGILE_SHARE * S
         bad = np.flatnonzero(ok & np.any(idx[b] != ridx, axis=1))
         assert bad.size == 0, f"{tag} train {b}: {bad.size} samples differ, first {bad[:5]}: {idx[b][bad[:2]]} vs {ridx[bad[:2]]}"
-        worst = max(worst, float(np.max(np.abs(logp[b][ok] - rlogp[ok]))))
-        worst_t = max(worst_t, float(np.max(np.abs(logp[b] - target_logp(cores, idx[b], born)))))
+        worst = worst_of(worst, float(np.max(np.abs(logp[b][ok] - rlogp[ok]))))
+        worst_t = worst_of(worst_t, float(np.max(np.abs(logp[b] - target_logp(cores, idx[b], born)))))
         assert tuple(info[b]) == (clamps, dead)
     print(f"{tag} {mode_of(born)}: logp against the reference {worst:.2e}, against the target {worst_t:.2e}, fragile {nfrag}")
     assert worst <= TOL and worst_t <= TOL
@@ -178,7 +179,7 @@ def test_batch_beyond_one_launch_chunk(born):
             ok = margin >= R.FRAGILE
             nfrag += int((~ok).sum())
             assert np.array_equal(idx[b][ok], ridx[ok]), b
-            worst = max(worst, float(np.max(np.abs(logp[b][ok] - rlogp[ok]), initial=0.0)))
+            worst = worst_of(worst, float(np.max(np.abs(logp[b][ok] - rlogp[ok]), initial=0.0)))
         print(f"B = {B} {mode_of(born)}: logp against the reference {worst:.2e}, against the closed form {err_t:.2e}, fragile {nfrag}")
         assert worst <= TOL and err_t <= TOL and nfrag <= 1
     finally:

@@ -15,7 +15,7 @@ import ttn_amd as T
 from oracle import tt_oracle as O
 from tests import opalg_reference as OR
 from tests import stepper_reference as R
-from tests.helpers import to_oracle, to_product, tt_rel_diff
+from tests.helpers import to_oracle, to_product, tt_rel_diff, worst_of
 from tests.test_gpu_opalg import CASES
 from ttn_amd import device as D
 from ttn_amd import solvers as S
@@ -194,7 +194,7 @@ def run_both(method, solver, d, nsteps, normalize, max_bond, kw, seed):
         ref = g(A, u0, u0, steps, normalize=normalize, tt_solver=solver, max_bond=max_bond, **kw)
         got = to_oracle(sol.download(b))
         assert got.ttv_rks == ref.ttv_rks, (b, got.ttv_rks, ref.ttv_rks)
-        worst = max(worst, tt_rel_diff(got, ref))
+        worst = worst_of(worst, tt_rel_diff(got, ref))
     print(f"{method} {solver} d={d} steps={nsteps} normalize={normalize} max_bond={max_bond} {kw}: worst tt_rel_diff {worst:.2e}")
     assert worst <= nsteps * ONE_STEP[solver], worst
     sol.free(); du.free()

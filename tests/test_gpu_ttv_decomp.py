@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import tt_oracle as O
-from tests.helpers import sign_fix_compare, to_oracle
+from tests.helpers import sign_fix_compare, to_oracle, worst_of
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +26,10 @@ def _gauge_err(tt):
         n, rl, rr = c.shape
         if tt.ttv_ot[k] == -1:
             m = c.transpose(1, 0, 2).reshape(rl * n, rr)
-            worst = max(worst, float(np.max(np.abs(m.T @ m - np.eye(rr)))))
+            worst = worst_of(worst, float(np.max(np.abs(m.T @ m - np.eye(rr)))))
         elif tt.ttv_ot[k] == 1:
             m = c.transpose(1, 0, 2).reshape(rl, n * rr)
-            worst = max(worst, float(np.max(np.abs(m @ m.T - np.eye(rl)))))
+            worst = worst_of(worst, float(np.max(np.abs(m @ m.T - np.eye(rl)))))
     return worst
 
 
