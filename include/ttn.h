@@ -686,6 +686,11 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * this header includes. */
 #include "ttn_braket.h"
 
+/* ---- the fixed-rank TT manifold (csrc/ttn_tangent_kernels.h) ----------------------------------------------------------
+ * The orthogonal projection of a train onto the tangent space at a point given by its two gauges, and the train alpha x + beta xi of a
+ * tangent at twice the ranks: ttn_tangent_project, ttn_tangent_to_tt.  Declared in ttn_tangent.h, which this header includes. */
+#include "ttn_tangent.h"
+
 #ifdef __cplusplus
 }
 #endif

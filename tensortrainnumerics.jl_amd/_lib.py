@@ -252,6 +252,12 @@ BRAKET_SIGNATURES = {
     "ttn_braket_dev": (C.c_int, [handle, handle, handle, C.c_void_p]),
 }
 
+# the fixed-rank manifold, include/ttn_tangent.h (`out`, `alpha`, `beta`: host arrays of `batch` doubles, or NULL)
+TANGENT_SIGNATURES = {
+    "ttn_tangent_project": (C.c_int, [handle, handle, handle, handle, p_f64]),
+    "ttn_tangent_to_tt": (C.c_int, [handle, handle, handle, p_f64, p_f64, handle]),
+}
+
 _lib = None
 
 
@@ -283,7 +289,8 @@ def lib() -> C.CDLL:
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     for table in (SIGNATURES, RECT_SIGNATURES, DENSE_SIGNATURES, STEP_SIGNATURES, CROSS_BATCH_SIGNATURES, EXPECT_SIGNATURES, EXPECT_GRAD_SIGNATURES,
-                  OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES, BRAKET_SIGNATURES):
+                  OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES, BRAKET_SIGNATURES,
+                  TANGENT_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res

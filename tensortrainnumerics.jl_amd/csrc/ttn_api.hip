@@ -39,6 +39,7 @@
 #include "ttn_measure_kernels.h"
 #include "ttn_sample_kernels.h"
 #include "ttn_braket_kernels.h"
+#include "ttn_tangent_kernels.h"
 
 // The host headers: the dynamic-LDS table first (it fixes the order of the kernel templates' instantiations, see there), then the
 // layers, lowest first — every header stands after the ones it includes (tests/test_cpu_headers.py).
@@ -52,6 +53,7 @@
 #include "ttn_host_rect.h"
 #include "ttn_host_compress.h"
 #include "ttn_host_braket.h"
+#include "ttn_host_tangent.h"
 
 // the 512-thread build of k_compress and its building blocks (ttn_wg512.hip: two workgroups per CU), declared once for both units
 #include "ttn_wg512.h"

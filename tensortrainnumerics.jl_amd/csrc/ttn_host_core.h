@@ -4,7 +4,7 @@
 // lower ones whose helpers or state it uses (an entry point of another feature is called through its declaration in include/, like
 // any caller's); ttn_api.hip includes them lowest first, holds the features not cut out yet, and ends with ttn_init / ttn_finalize,
 // which see every module's state.  So far, lowest first: _lds, _core, then _dot, _measure, _sample, _handles, _stream, _rect, _compress,
-// _braket (above _dot: its all-Float64 form is k_expect's launch).
+// _braket (above _dot: its all-Float64 form is k_expect's launch), _tangent (above _stream: its coefficients travel in g_grad_coef).
 // State that one module alone reads or writes is declared in that module's header; what two modules share stands with the lower of
 // them, whose head comment names the other; only what many share stands here.  These headers are included by ttn_api.hip ONLY —
 // ttn_wg512.hip never sees one: everything in them has internal linkage (`static`, unnamed namespace) and the library state must
@@ -256,7 +256,7 @@ const struct { int code, err; const char* msg; } status_table[] = {
     {TTN_ST_LANCZOS, TTN_ERR_NO_CONVERGENCE, "a Lanczos local solve exhausted linsolv_maxiter restarts above 1e3 * linsolv_tol"},
     {TTN_ST_NONFINITE, TTN_ERR_NO_CONVERGENCE, "a local eigenvalue or eigenvector was not finite (NaN or Inf in the operator or the start train)"},
     {TTN_ST_SINGULAR, TTN_ERR_SINGULAR, "a local system K is singular (als_linsolve), or a local metric S_s is not positive definite (als_gen_eigsolv)"},
-    {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "a train's ranks differ from the ranks the call needs (als_linsolve: the start handle; ttn_apply_pullback: R .* x; ttn_tt_cores_axpby: x)"},
+    {TTN_ST_RANKS_DIFFER, TTN_ERR_DIMS, "a train's ranks differ from the ranks the call needs (als_linsolve: the start handle; ttn_apply_pullback: R .* x; ttn_tt_cores_axpby: x; ttn_tangent_project / ttn_tangent_to_tt: U, V and xi)"},
     {TTN_ST_RANK_OVERFLOW, TTN_ERR_CAPACITY, "a rank grew beyond the rank capacity of its handle / working slot (site-swap chain or ttv_decomp)"},
     {TTN_ST_JACOBI, TTN_ERR_NO_CONVERGENCE, "Jacobi SVD hit its sweep limit"},
 };

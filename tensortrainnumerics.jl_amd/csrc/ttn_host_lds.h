@@ -29,6 +29,7 @@
 #include "ttn_measure_kernels.h"
 #include "ttn_sample_kernels.h"
 #include "ttn_braket_kernels.h"
+#include "ttn_tangent_kernels.h"
 
 #include <cstddef>
 
@@ -88,6 +89,7 @@ const struct { const void* fn; size_t lds; } lds_limits[] = {
     {(const void*)k_zexpect<true, false, 0>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
     {(const void*)k_zexpect<true, false, 1>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
     {(const void*)k_zexpect<true, false, 2>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
+    {(const void*)k_tangent_chain, DOT_LDS_BYTES(DOT_MAX_D)},
 };
 }  // namespace
 #endif  // TTN_HOST_LDS_H
