@@ -70,6 +70,23 @@ __host__ __device__ inline View tview(View v) { return View{v.p, v.c, v.r}; }
 __host__ __device__ inline View mkview(double* p, Idx r, Idx c) { return View{p, r, c}; }
 __host__ __device__ inline long long minstride(const Idx& d) { return d.q ? (d.lo < d.hi ? d.lo : d.hi) : d.lo; }
 
+// The dense kernels work "in units of s0 = max|M|", but their products do not: a Gram route takes 1 / (s0 s0) and sums squares of
+// UNSCALED entries, an unscaled Householder reflector sums squares too, the output GEMM of a bond step multiplies a factor of size
+// sqrt(s0) into the unscaled M (s0^1.5), the swap form carries s0^2, the rank rule squares sigma s0.  All of that is in range while
+// the size of the matrix is within SCALE_SAFE.  Outside it the fast routes decline and the general routes take an exact power of two
+// out of the matrix first and give it back to their outputs: extra passes for such a step only.
+#define SCALE_SAFE_MIN 0x1p-256
+#define SCALE_SAFE_MAX 0x1p+256
+__host__ __device__ inline bool scale_safe(double s) { return s >= SCALE_SAFE_MIN && s <= SCALE_SAFE_MAX; }      // (false for 0, Inf and NaN)
+// the exponent e (|e| <= 1020, even if `even`) with s / 2^e in [1/2, 2); 0 when s is within SCALE_SAFE, zero or not finite
+__device__ inline int scale_rescue_exponent(double s, bool even) {
+    if (!(s > 0.0) || !(s <= 1.7976931348623157e308) || scale_safe(s)) return 0;
+    int e;
+    (void)frexp(s, &e);
+    e = e < -1020 ? -1020 : (e > 1020 ? 1020 : e);
+    return even ? (e & ~1) : e;
+}
+
 // Per-train failure codes of the dense kernels.  The host maps each to a TTN_ERR_* code and a message (ttn_host_core.h: status_table).
 enum TtnStatus : int {
     TTN_ST_JACOBI = 1,           // a Jacobi SVD hit its sweep limit

@@ -236,6 +236,7 @@ __device__ void zc_bond_step(const ZCompressArgs& P, int b, int k, double* Rl_, 
     double* Rp = (n <= TTN_ZC_LDS_N) ? Rl_ : Rg;
 
     // ---- 1. merge ----
+    double amx = 0.0;
     for (long long e = tid; e < (long long)Mr * Mc; e += TTN_ZC_WG) {
         const int R = (int)(e % Mr), Cc = (int)(e / Mr);
         const int al = R % Dl, s1 = R / Dl, s2 = Cc % n2, be = Cc / n2;
@@ -244,8 +245,18 @@ __device__ void zc_bond_step(const ZCompressArgs& P, int b, int k, double* Rl_, 
             acc = zfma(zload(C1, s1 + (long long)n1 * (al + (long long)Dl * g)), zload(C2, s2 + (long long)n2 * (g + (long long)Dm * be)), acc);
         if (tall) zstore(G, R + (long long)m * Cc, acc);
         else zstore(G, Cc + (long long)m * R, zc::conj(acc));
+        amx = fmax(amx, fmax(fabs(acc.x), fabs(acc.y)));
     }
+    // The step below is UNSCALED (reflector norms, column norms and the rank rule sum squares; the rotation test has an absolute floor):
+    // a merged matrix whose size is outside SCALE_SAFE (ttn_common.h) is divided by an exact, even power of two here, and each of the
+    // two cores gets the root of it back at the end.
+    const int kexp = scale_rescue_exponent(wg_max(amx, red), true);
     __syncthreads();
+    if (kexp != 0) {
+        const double f = ldexp(1.0, -kexp);
+        for (long long e = tid; e < (long long)m * n; e += TTN_ZC_WG) zstore(G, e, zc::scale(zload(G, e), f));
+        __syncthreads();
+    }
     // ---- 2. Householder QR of G ----
     for (int kk = 0; kk < n; ++kk) {
         double part = 0.0;
@@ -414,6 +425,12 @@ __device__ void zc_bond_step(const ZCompressArgs& P, int b, int k, double* Rl_, 
         const int s2 = Cc % n2, be = Cc / n2;
         const zt v = tall ? zc::scale(zload(V, Cc + (long long)n * perm[j]), sqrt(dw[perm[j]])) : zload(Z, Cc + (long long)m * j);
         zstore(C2, s2 + (long long)n2 * (j + (long long)r * be), zc::conj(v));
+    }
+    if (kexp != 0) {
+        const double f = ldexp(1.0, kexp / 2);
+        __syncthreads();
+        for (long long e = tid; e < (long long)Mr * r; e += TTN_ZC_WG) zstore(C1, e, zc::scale(zload(C1, e), f));
+        for (long long e = tid; e < (long long)Mc * r; e += TTN_ZC_WG) zstore(C2, e, zc::scale(zload(C2, e), f));
     }
     if (tid == 0) rks[k + 1] = r;
     __syncthreads();

@@ -70,6 +70,8 @@ struct CompressArgs {
 #define FAST_POLISH_DROP 1.0e-12      // ... and only if the singular values it drops carry at most this share of ||M||_F^2 (i.e. are noise)
 #define FAST_DIAG_TOL 2.0e-12         // route F: A'^T A' counts as diagonal below this (relative to sqrt(G_ii G_jj))
 #define FAST_CHECK_TOL 2.0e-11        // a-posteriori bound on |Rf Rf^T - Sigma| (and Lf^T Lf - Sigma), relative
+// (the size of M itself: SCALE_SAFE of ttn_common.h — outside it route F declines and the general step divides M by an exact, even
+// power of two first and multiplies its outputs by the root of it afterwards)
 
 struct BondCtx {
     // LDS
@@ -1064,6 +1066,36 @@ __device__ __noinline__ void wg_handover_restore(double* core, const double* sta
     __syncthreads();
 }
 
+// SCALE_SAFE (ttn_common.h), out of line so that the bond step's own body gains one call at each end and no live value.
+// wg_scale_takeout: the n contiguous doubles of M divided by 2^e in place when amax = max|M| is outside the safe range (e even if
+// `even`); e is left in *keep, an LDS word, and max|M| after the division is returned.  Inside the range: e = 0, nothing is touched.
+__device__ __noinline__ double wg_scale_takeout(double* M, long long n, double amax, int even, double* keep) {
+    M = unip(M); n = uni64(n); keep = unip(keep); amax = unif64(amax);
+    const int e = uni32(scale_rescue_exponent(amax, even != 0));
+    if (threadIdx.x == 0) *keep = (double)e;
+    if (e == 0) return amax;
+    __syncthreads();
+    wg_copy_scale(M, M, n, ldexp(1.0, -e));
+    __syncthreads();
+    return ldexp(amax, -e);
+}
+// wg_scale_giveback: the power of two a step took out (*keep) goes back into its outputs — half of it into each core (tt_compress!:
+// U sqrt(S), sqrt(S) Vt; per_rank doubles of a core for each of the *rank kept directions), or all of it into core k+1 (swap:
+// S Vt) — and into the captured singular values (sv: p of them, or null).  *keep = 0 or *rank <= 0: nothing is touched.
+__device__ __noinline__ void wg_scale_giveback(double* ck, long long per_rank_k, double* ck1, long long per_rank_k1, const long long* rank,
+                                               const double* keep, int swap, double* sv, int p) {
+    ck = unip(ck); per_rank_k = uni64(per_rank_k); ck1 = unip(ck1); per_rank_k1 = uni64(per_rank_k1); rank = unip(rank); keep = unip(keep);
+    swap = uni32(swap); sv = unip(sv); p = uni32(p);
+    const int e = uni32((int)*keep);
+    if (e == 0) return;
+    const long long rr = uni64(*rank);
+    if (rr <= 0) return;
+    if (!swap) wg_copy_scale(ck, ck, per_rank_k * rr, ldexp(1.0, e / 2));
+    wg_copy_scale(ck1, ck1, per_rank_k1 * rr, ldexp(1.0, swap ? e : e / 2));
+    if (sv) for (int i = threadIdx.x; i < p; i += TTN_WG) sv[i] = ldexp(sv[i], e);
+    __syncthreads();
+}
+
 struct BondIO {
     double *ck, *ck1;            // the two cores (slots)
     int n1, n2, Dl, rm, Dr;      // physical dimensions and the three ranks
@@ -1147,7 +1179,8 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
 #define HANDOVER_BS(pn) mkview(S.M + ((pn) == 2 ? handover_area(P) : 0), plain(1), plain(rm))       /* the staged B' (pn != 0) */
 #define HANDOVER_B(pn) ((pn) ? HANDOVER_BS(pn) : Bp)
         { const int pn = HANDOVER_PEND(); sb = wg_absmax(pn ? S.M + (pn == 2 ? handover_area(P) : 0) : ck1, (long long)n2 * rm * Dr, S.red); }      // (the same set of numbers)
-        bool ok = (sa > 0.0) && (sb > 0.0);
+        // (1 / (sA sA), 1 / (sB sB) and the squares behind them, s0 = sA sB in the rank rule: in range or the step is the general one's)
+        bool ok = scale_safe(sa) && scale_safe(sb) && scale_safe(sa * sb);
         const double sA = wide ? sa : sb, sB = wide ? sb : sa;       // scale of A', B'
         const double s0 = sA * sB;
         const View Gav = mkview(S.Ga, plain(1), plain(128));
@@ -1335,7 +1368,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
                     __syncthreads();
                 }
         } else if (!merged) wg_gemm(p, q, rm, Ap, Bp, Mv, 1.0, 0.0, lds, S.scal + 6);
-        const double mx = (SWAP != 0) ? mx_swap : unif64(S.scal[6]);
+        // max|M| outside SCALE_SAFE: M / 2^e in place (e even, so that the sqrt(S) split of the outputs is exact too); the step then runs
+        // on a matrix of size 1 and its outputs get the power back at the end (the exponent waits in S.scal[7])
+        const double mx = wg_scale_takeout(S.M, (long long)p * q, (SWAP != 0) ? mx_swap : unif64(S.scal[6]), 1, S.scal + 7);
         const double s0 = (mx > 0.0) ? mx : 1.0;
         const double inv_s0 = 1.0 / s0;
         const bool need_lq = q > p;
@@ -1568,6 +1603,9 @@ __device__ __forceinline__ void wg_bond_step_io(const CompressArgs& P, int b, co
             __syncthreads();
             done = true;
         }
+        if (done)
+            wg_scale_giveback(ck, (long long)n1 * Dl, ck1, (long long)n2 * Dr, io.rank_out, S.scal + 7, SWAP != 0,
+                              (P.sv_out && step < P.sv_steps) ? P.sv_out + ((long long)b * P.sv_steps + step) * P.pmax : nullptr, p);
     }
     if (tid == 0) P.sweep_stats[b] += nsw_total;
     __syncthreads();

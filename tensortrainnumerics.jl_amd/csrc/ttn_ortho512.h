@@ -285,7 +285,9 @@ __device__ __noinline__ int o5_step(double* lds, const double* Xj, double* Yj, c
     __syncthreads();
     const double dmax = unif64(misc[2]);
     const double dmin = 64.0 * DBL_EPSILON * dmax;
-    bool good = dmax > 0.0;
+    // (dmax, the largest squared column norm of W, outside SCALE_SAFE squared: the Gram matrix has overflowed or lost its small entries
+    //  to underflow — refused, the general kernel takes a power of two out of W first)
+    bool good = dmax >= SCALE_SAFE_MIN * SCALE_SAFE_MIN && dmax <= SCALE_SAFE_MAX * SCALE_SAFE_MAX;
     if (good) {
         for (int i = rl + tid; i < 16 * nat; i += O5_WG) Gb[O5_IMG(i, i)] = dmax;
         __syncthreads();

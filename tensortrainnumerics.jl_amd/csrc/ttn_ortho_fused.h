@@ -186,7 +186,9 @@ __device__ __noinline__ int ortho_step_fused(const double* Xj, double* Yj, const
     const double dmin = 64.0 * DBL_EPSILON * dmax;
     // the padding of the last block takes the scale of the matrix (a unit diagonal would fail the pivot test of a train whose carried
     // factor has grown to 1e26: the norm of a random rank-64 chain accumulates in FL)
-    if (!(dmax > 0.0)) return 0;
+    // dmax = the largest squared column norm of W: outside SCALE_SAFE squared the Gram matrix has overflowed or lost its small entries
+    // to underflow — the general step takes a power of two out of W first (wg_ortho_prescale)
+    if (!(dmax >= SCALE_SAFE_MIN * SCALE_SAFE_MIN && dmax <= SCALE_SAFE_MAX * SCALE_SAFE_MAX)) return 0;
     for (int i = rl + tid; i < 16 * nat; i += TTN_WG) G[OF_G(i, i)] = dmax;
     __syncthreads();
     for (int jb = 0; jb < nat; ++jb) {

@@ -88,6 +88,15 @@ __device__ __noinline__ int wg_qr_cholqr(int mm, int nn, double* Tm, double* Qb,
     return p;
 }
 
+// The site matrix T = (carried factor) x (core) is factored UNSCALED (Gram products, reflector norms: sums of squares), and the
+// carried factor accumulates the norm of the whole train.  max|T| (from the epilogue of the product that formed T) outside SCALE_SAFE:
+// T / 2^e in place, exact (wg_scale_takeout); Q does not change and R gets 2^e back.
+__device__ __noinline__ void wg_ortho_postscale(double* Rn, long long n, int e) {
+    Rn = unip(Rn); n = uni64(n); e = uni32(e);
+    wg_copy_scale(Rn, Rn, n, ldexp(1.0, e));
+    __syncthreads();
+}
+
 // device restatement of r_and_d_to_rks (src/tt_tools.jl:407-425) with Julia's wrapping Int64 products
 __device__ void dev_r_and_d_to_rks(int d, const int* dims, const long long* rks, long long rmax, long long* out) {
     for (int i = 0; i <= d; ++i) out[i] = 1;
@@ -168,10 +177,14 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
         // Tm[(al + yl*s), be] = sum_ga FR[al,ga] X_j[s,ga,be]
         const View Xv = mkview(Xj, plain(n), Idx{n, 1, (long long)n * rl});            // [ga, (s + n*be)]
         const View Tv = mkview(Tm, plain(1), Idx{n, (long long)yl, (long long)mm});   // [al, (s + n*be)]
-        wg_gemm(yl, n * rr, rl, FR, Xv, Tv, 1.0, 0.0, lds);
+        wg_gemm(yl, n * rr, rl, FR, Xv, Tv, 1.0, 0.0, lds, W.taus);         // (W.taus: an LDS word that is dead outside wg_lq_blocked)
+        wg_scale_takeout(Tm, (long long)mm * rr, W.taus[0], 0, W.taus + 1);
+        __syncthreads();                                                     // (thread 0 wrote the exponent)
+        const int tex = uni32((int)W.taus[1]);
         double* Rn = which ? Rb0 : Rb1;
         int rnew = (rr <= 64 && mm > rr) ? wg_qr_cholqr(mm, rr, Tm, Qb, Rn, Cw, lds) : 0;
         if (!rnew) rnew = wg_qr_explicit(mm, rr, Tm, Qb, Rn, W, lds);
+        if (tex) wg_ortho_postscale(Rn, (long long)rnew * rr, tex);
         // Y_j[s, al, be] = Q[al + yl*s, be]
         for (long long e = tid; e < (long long)mm * rnew; e += TTN_WG) {
             const int row = (int)(e % mm), be = (int)(e / mm);
@@ -211,9 +224,13 @@ __global__ void TTN_KERNEL_BOUNDS k_orthogonalize(OrthoArgs P) {
         // Tt[(be + ynext*s), al] = sum_ga FL[ga,be] X_j[s,al,ga]  ==  (FL^T) * X2,  X2[ga, (s + n*al)]
         const View X2 = mkview(Xj, plain((long long)n * rl), plain(1));
         const View Tv = mkview(Tm, plain(1), Idx{n, (long long)ynext, (long long)mm});
-        wg_gemm(ynext, n * rl, rr, tview(FL), X2, Tv, 1.0, 0.0, lds);
+        wg_gemm(ynext, n * rl, rr, tview(FL), X2, Tv, 1.0, 0.0, lds, W.taus);
+        wg_scale_takeout(Tm, (long long)mm * rl, W.taus[0], 0, W.taus + 1);
+        __syncthreads();                                                     // (thread 0 wrote the exponent)
+        const int tex = uni32((int)W.taus[1]);
         rnew = (rl <= 64 && mm > rl) ? wg_qr_cholqr(mm, rl, Tm, Qb, Rn, Cw, lds) : 0;
         if (!rnew) rnew = wg_qr_explicit(mm, rl, Tm, Qb, Rn, W, lds);
+        if (tex) wg_ortho_postscale(Rn, (long long)rnew * rl, tex);
         // Y_j[s, al, be] = Qt[(be + ynext*s), al]   (core shape (n, rnew, ynext))
         for (int e = tid; e < mm * rnew; e += TTN_WG) {
             const int row = e % mm, al = e / mm;

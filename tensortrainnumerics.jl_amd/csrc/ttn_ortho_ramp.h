@@ -87,7 +87,7 @@ __device__ __forceinline__ void oramp_phase(double (&a)[ROWS], double (&b)[ROWS]
 // One site.  In: Rp[be] (lane ga) = FL[ga][be] for be < ROWS / 2 (zero beyond ynext and beyond rr).  Out: Y_j, R to Rn (ld = rows),
 // Rp = this site's R for the next one (when ROWS <= 32).
 template <int ROWS>
-__device__ __forceinline__ void oramp_site(double (&Rp)[32], const double* __restrict__ Xj, double* __restrict__ Yj, double* __restrict__ Rn,
+__device__ __forceinline__ bool oramp_site(double (&Rp)[32], const double* __restrict__ Xj, double* __restrict__ Yj, double* __restrict__ Rn,
                                            int rl, int rr, int ynext) {
     const int lane = threadIdx.x & 63;
     const int rows = 2 * ynext;
@@ -114,6 +114,18 @@ __device__ __forceinline__ void oramp_site(double (&Rp)[32], const double* __res
             }
         }
     }
+    // The reflectors below are UNSCALED (sums of squares of W's entries, 1 / (beta u_k)): a W whose size is outside SCALE_SAFE is not
+    // this kernel's — nothing of the site is written then (`took` guards every store; the arithmetic below runs on, it cannot fault), the
+    // sweep stops here and the kernels after this one go on (the general one takes a power of two out of W first).  An all-zero W
+    // passes: its reflectors are the identity.
+    bool took;
+    {
+        double mx = 0.0;
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) mx = fmax(mx, fabs(a[i]));
+        mx = wave_max(mx);
+        took = mx == 0.0 || scale_safe(mx);
+    }
     // ---- Householder steps k = 0 .. rows - 2 (the last row needs none) on W, accumulated into B = Q^T ----
     const int klast = rows - 1;
     oramp_phase<ROWS, 0, CH>(a, b, 0, klast < CH ? klast : CH);
@@ -127,19 +139,20 @@ __device__ __forceinline__ void oramp_site(double (&Rp)[32], const double* __res
 #pragma unroll
         for (int i = 0; i < ROWS; ++i) {
             const double r = (i <= lane && i < rows) ? a[i] : 0.0;
-            if (lane < rl && i < rows) Rn[i + rows * lane] = r;
+            if (took && lane < rl && i < rows) Rn[i + rows * lane] = r;
             if (i < 32) Rp[i] = (lane < rl) ? r : 0.0;
         }
 #pragma unroll
         for (int i = (ROWS < 32 ? ROWS : 32); i < 32; ++i) Rp[i] = 0.0;
     }
     // ---- Y_j[s, al', be] = Q[2 be + s][al'] = B[al'][2 be + s]: lane i = 2 be + s holds column i of B, register al' its row al' ----
-    if (lane < rows) {
+    if (took && lane < rows) {
         double* yl = Yj + (lane & 1) + 2LL * rows * (lane >> 1);
 #pragma unroll
         for (int al = 0; al < ROWS; ++al)
             if (al < rows) yl[2 * al] = b[al];
     }
+    return took;
 }
 
 // mode 5: no launch ran before (the centre is site 0: there is no left sweep) — this kernel also initialises the ranks of y and the
@@ -180,12 +193,14 @@ __global__ void __launch_bounds__(ORAMP_WG) k_ortho_ramp(OrthoArgs P, int batch)
             double* Yj = Ybase + Y.off[j];
             double* Rn = whichL ? Rc : Rd;
             const int rows = 2 * ynext;
-            if (rows <= 2) oramp_site<2>(Rp, Xj, Yj, Rn, rl, rr, ynext);
-            else if (rows <= 4) oramp_site<4>(Rp, Xj, Yj, Rn, rl, rr, ynext);
-            else if (rows <= 8) oramp_site<8>(Rp, Xj, Yj, Rn, rl, rr, ynext);
-            else if (rows <= 16) oramp_site<16>(Rp, Xj, Yj, Rn, rl, rr, ynext);
-            else if (rows <= 32) oramp_site<32>(Rp, Xj, Yj, Rn, rl, rr, ynext);
-            else oramp_site<64>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            bool took;
+            if (rows <= 2) took = oramp_site<2>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            else if (rows <= 4) took = oramp_site<4>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            else if (rows <= 8) took = oramp_site<8>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            else if (rows <= 16) took = oramp_site<16>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            else if (rows <= 32) took = oramp_site<32>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            else took = oramp_site<64>(Rp, Xj, Yj, Rn, rl, rr, ynext);
+            if (!took) break;
             if (lane == 0) yr[j] = rows;
             ynext = rows;
             whichL ^= 1;

@@ -387,10 +387,27 @@ def tt_sample(x: TTvector, nsamples: int, mode: str = "born", seed: int = 0, u=N
 
 
 def norm(a: TTvector) -> float:
-    """norm(a) — src/tt_operations.jl:465-470."""
-    v = dot(a, a).real          # norm = sqrt(max(real(dot(a, a)), 0))
+    """norm(a) — src/tt_operations.jl:465-470.  dot(a, a) squares every core, so a core of size 2^+-600 leaves the double range in the
+    partial products though the norm itself does not (2^800 in one core and 2^-800 in the next gave 0).  Each core is divided by the
+    power of two of its largest entry first and the root gets the powers back: exact, the same bits as sqrt(dot(a, a)) wherever
+    that is in range."""
+    total, cores = 0, []
+    for c in a.ttv_vec:
+        m = float(np.max(np.abs(c))) if c.size else 0.0
+        k = int(np.frexp(m)[1]) if (m > 0.0 and math.isfinite(m)) else 0
+        total += k
+        if k == 0:
+            cores.append(c)
+        elif np.iscomplexobj(c):
+            s = np.empty_like(c)
+            s.real, s.imag = np.ldexp(c.real, -k), np.ldexp(c.imag, -k)
+            cores.append(s)
+        else:
+            cores.append(np.ldexp(c, -k))
+    b = TTvector(a.N, cores, a.ttv_dims, a.ttv_rks, a.ttv_ot)
+    v = dot(b, b).real          # norm = sqrt(max(real(dot(a, a)), 0))
     v = 0.0 if v < 0 else v
-    return math.sqrt(v)
+    return float(np.ldexp(math.sqrt(v), total))
 
 
 def euclidean_distance(a: TTvector, b: TTvector) -> float:
