@@ -691,6 +691,11 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * tangent at twice the ranks: ttn_tangent_project, ttn_tangent_to_tt.  Declared in ttn_tangent.h, which this header includes. */
 #include "ttn_tangent.h"
 
+/* ---- partial contraction of a train (csrc/ttn_contract_kernels.h) ------------------------------------------------------
+ * A subset of the sites contracted against weight vectors, the result a train on the remaining sites — marginals, slices and moments
+ * of function-valued trains without a dense array: ttn_tt_contract_sites.  Declared in ttn_contract.h, which this header includes. */
+#include "ttn_contract.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,9 +20,10 @@ from .opalg import (concatenate, kron, operator_strides, outer_product, qtto_to_
                     tto_scale, tto_sub, tto_to_tensor, tto_to_ttv, ttv_to_diag_tto, ttv_to_tto)
 from .solvers import (als_eigsolve, als_gen_eigsolv, crank_nicholson_method, dmrg_eigsolve, euler_method, implicit_euler_method, krylov_linsolve,
                       lowest_states, mals_eigsolve, rk4_method)
-from .qttnd import QTToperator, QTTvector, check_compat, entanglemententropy, function_to_qttv, grid_strides, qtt_laplacian, qttv_sample, qttv_to_array
+from .qttnd import (QTToperator, QTTvector, check_compat, dim_sites, entanglemententropy, function_to_qttv, grid_strides, marginal, moments, qtt_laplacian,
+                    qttv_sample, qttv_to_array, reduced_meta, slice_dim)
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
-from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, braket, correlation_matrix, div, dot, energy,
+from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, braket, contract_sites, correlation_matrix, div, dot, energy,
                  euclidean_distance, expect, hadamard, increase_ranks, norm, orthogonalize, r_and_d_to_rks, rayleigh, sandwich, scale, site_expect, sub, tt_compress_, tt_sample, tt_up_rks,
                  ttv_to_tensor)
 

@@ -258,6 +258,11 @@ TANGENT_SIGNATURES = {
     "ttn_tangent_to_tt": (C.c_int, [handle, handle, handle, p_f64, p_f64, handle]),
 }
 
+# partial contraction, include/ttn_contract.h (`sites` and `weights` are host arrays)
+CONTRACT_SIGNATURES = {
+    "ttn_tt_contract_sites": (C.c_int, [handle, i64, p_i64, i64, p_f64, handle]),
+}
+
 _lib = None
 
 
@@ -290,7 +295,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     for table in (SIGNATURES, RECT_SIGNATURES, DENSE_SIGNATURES, STEP_SIGNATURES, CROSS_BATCH_SIGNATURES, EXPECT_SIGNATURES, EXPECT_GRAD_SIGNATURES,
                   OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES, BRAKET_SIGNATURES,
-                  TANGENT_SIGNATURES):
+                  TANGENT_SIGNATURES, CONTRACT_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res

@@ -40,6 +40,7 @@
 #include "ttn_sample_kernels.h"
 #include "ttn_braket_kernels.h"
 #include "ttn_tangent_kernels.h"
+#include "ttn_contract_kernels.h"
 
 // The host headers: the dynamic-LDS table first (it fixes the order of the kernel templates' instantiations, see there), then the
 // layers, lowest first — every header stands after the ones it includes (tests/test_cpu_headers.py).
@@ -54,6 +55,7 @@
 #include "ttn_host_compress.h"
 #include "ttn_host_braket.h"
 #include "ttn_host_tangent.h"
+#include "ttn_host_contract.h"
 
 // the 512-thread build of k_compress and its building blocks (ttn_wg512.hip: two workgroups per CU), declared once for both units
 #include "ttn_wg512.h"
@@ -3176,6 +3178,7 @@ int ttn_finalize(void) {
     g_slots.clear();
     if (g_xb_tab_ev) { hipEventDestroy(g_xb_tab_ev); g_xb_tab_ev = nullptr; }
     if (g_measure_ev) { hipEventDestroy(g_measure_ev); g_measure_ev = nullptr; }
+    if (g_contract_ev) { hipEventDestroy(g_contract_ev); g_contract_ev = nullptr; }
     for (hipEvent_t e : g_sample_ev) hipEventDestroy(e);
     g_sample_ev.clear();
     g_sample_chunks = 0;

@@ -4,7 +4,8 @@
 // lower ones whose helpers or state it uses (an entry point of another feature is called through its declaration in include/, like
 // any caller's); ttn_api.hip includes them lowest first, holds the features not cut out yet, and ends with ttn_init / ttn_finalize,
 // which see every module's state.  So far, lowest first: _lds, _core, then _dot, _measure, _sample, _handles, _stream, _rect, _compress,
-// _braket (above _dot: its all-Float64 form is k_expect's launch), _tangent (above _stream: its coefficients travel in g_grad_coef).
+// _braket (above _dot: its all-Float64 form is k_expect's launch), _tangent (above _stream: its coefficients travel in g_grad_coef),
+// _contract (on _core alone).
 // State that one module alone reads or writes is declared in that module's header; what two modules share stands with the lower of
 // them, whose head comment names the other; only what many share stands here.  These headers are included by ttn_api.hip ONLY —
 // ttn_wg512.hip never sees one: everything in them has internal linkage (`static`, unnamed namespace) and the library state must

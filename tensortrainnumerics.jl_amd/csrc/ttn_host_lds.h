@@ -30,6 +30,7 @@
 #include "ttn_sample_kernels.h"
 #include "ttn_braket_kernels.h"
 #include "ttn_tangent_kernels.h"
+#include "ttn_contract_kernels.h"
 
 #include <cstddef>
 
@@ -90,6 +91,8 @@ const struct { const void* fn; size_t lds; } lds_limits[] = {
     {(const void*)k_zexpect<true, false, 1>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
     {(const void*)k_zexpect<true, false, 2>, BRAKET_LDS_BYTES(BRAKET_MAX_D)},
     {(const void*)k_tangent_chain, DOT_LDS_BYTES(DOT_MAX_D)},
+    {(const void*)k_contract_chip, CONTRACT_CHIP_LDS_BYTES},
+    {(const void*)k_contract_gen, sizeof(double) * GEMM_LDS_TOTAL},
 };
 }  // namespace
 #endif  // TTN_HOST_LDS_H

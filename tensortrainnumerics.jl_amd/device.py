@@ -417,6 +417,19 @@ class DeviceTT:
         _lib.check(_lib.lib().ttn_tt_merge_sites(self.h, z.h, _i64(mn), len(mn)))
         return z
 
+    # partial contraction (include/ttn_contract.h)
+    def contract_sites(self, weights, cap_rks: Sequence[int] | None = None) -> "DeviceTT":
+        """``contract_sites(self, weights)`` into a NEW handle on the kept sites; ``cap_rks``: its rank capacity (default: this handle's
+        capacity at the bonds the result keeps, ``contract_rank_capacity``)."""
+        sites, _, _ = _contract_tables("contract_sites", self.dims, self.batch, weights)
+        kept, _ = contract_kept(self.N, sites)
+        y = DeviceTT([self.dims[k] for k in kept], cap_rks if cap_rks is not None else contract_rank_capacity(self.cap, sites), self.batch)
+        try:
+            return contract_sites(self, weights, y)
+        except Exception:
+            y.free()
+            raise
+
     # increase_ranks (include/ttn_step.h)
     def increase_ranks(self, max_bond: int, rks: Sequence[int] | None = None, noise: float = 0.0, seed: int = 0,
                        cap_rks: Sequence[int] | None = None) -> "DeviceTT":
@@ -523,6 +536,72 @@ def apply_rect(A: DeviceRectTTO, x: DeviceTT, y: DeviceTT) -> DeviceTT:
     if not isinstance(A, DeviceRectTTO):
         raise TypeError(f"apply_rect: expected a DeviceRectTTO, got {type(A).__name__}")
     _lib.check(_lib.lib().ttn_apply_rect(A.h, x.h, y.h))
+    return y
+
+
+def contract_kept(N: int, sites: Sequence[int]):
+    """(kept, start), both 0-based, for the 1-based contracted ``sites`` of a train of N sites: the kept sites in order, and for each
+    the first site of the run of contracted sites in front of it (the kept site itself when there is none)."""
+    gone = {int(s) - 1 for s in sites}
+    kept, start, run = [], [], 0
+    for k in range(N):
+        if k not in gone:
+            kept.append(k)
+            start.append(run)
+            run = k + 1
+    return kept, start
+
+
+def contract_rank_capacity(x_cap: Sequence[int], sites: Sequence[int]) -> List[int]:
+    """Rank capacity of ``contract_sites``' result: the bond left of a kept site carries x's bond left of the run in front of it, the right
+    end x's right end."""
+    _, start = contract_kept(len(x_cap) - 1, sites)
+    return [int(x_cap[s]) for s in start] + [int(x_cap[-1])]
+
+
+def _contract_tables(who: str, dims: Sequence[int], batch: int, weights):
+    """The argument checks of ``contract_sites`` that need no device, and the C ABI's arguments: (sites, wbatch, table) with ``sites``
+    1-based ascending and ``table`` a C-contiguous (wbatch, sum n_k) float64 array."""
+    if not isinstance(weights, dict) or not weights:
+        raise _lib.TTNError(f"{who}: weights must be a non-empty dict {{site: vector}} (sites are 1-based)")
+    N = len(dims)
+    for s in weights:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 1 <= int(s) <= N:
+            raise _lib.TTNError(f"{who}: site {s!r} is not in 1:{N}")
+    sites = sorted(int(s) for s in weights)
+    if len(sites) >= N:
+        raise _lib.TTNError(f"{who}: no kept site (a full contraction is dot with the rank-1 train of the weights)")
+    vecs, wbatch = [], 1
+    for s in sites:
+        v = np.asarray(weights[s])
+        if np.iscomplexobj(v):
+            raise _lib.TTNError(f"{who}: the weights of site {s} are complex; Float64 only")
+        v = np.asarray(v, dtype=np.float64)
+        n = int(dims[s - 1])
+        if v.shape == (n,):
+            pass
+        elif v.shape == (batch, n):
+            wbatch = batch
+        else:
+            raise _lib.TTNError(f"{who}: the weights of site {s} have shape {v.shape}; expected ({n},) or ({batch}, {n})")
+        vecs.append(v)
+    table = np.ascontiguousarray(np.concatenate([np.broadcast_to(v, (wbatch, v.shape[-1])) for v in vecs], axis=1), dtype=np.float64)
+    return sites, wbatch, table
+
+
+def contract_sites(x: DeviceTT, weights, y: DeviceTT | None = None) -> DeviceTT:
+    """Contract the sites ``weights`` names (a dict {site: vector}, sites 1-based, each vector of shape (n_k,) for every train or
+    (batch, n_k) for one per train) against their vectors, train by train (ttn_tt_contract_sites): the result is the train on the
+    remaining sites — a run of contracted sites is multiplied into the kept site behind it, the run behind the last kept site into that
+    one.  Fills ``y`` (the kept dims, a rank capacity, x's batch) or returns a new handle.  Asynchronous; Float64 only."""
+    if not isinstance(x, DeviceTT):
+        raise TypeError(f"contract_sites: expected a DeviceTT, got {type(x).__name__}")
+    if y is None:
+        return x.contract_sites(weights)
+    if not isinstance(y, DeviceTT):
+        raise TypeError(f"contract_sites: expected a DeviceTT as y, got {type(y).__name__}")
+    sites, wbatch, table = _contract_tables("contract_sites", x.dims, x.batch, weights)
+    _lib.check(_lib.lib().ttn_tt_contract_sites(x.h, len(sites), _i64(sites), wbatch, _p_f64(table), y.h))
     return y
 
 

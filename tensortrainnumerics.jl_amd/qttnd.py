@@ -388,6 +388,172 @@ def qttv_sample(q: QTTvector, nsamples: int, mode: str = "density", seed: int = 
     return grid, logp
 
 
+# ---- marginals, slices, moments (include/ttn_contract.h) -----------------------------------------------------------------
+# What the PDE examples of the reference take from the dense array (sum(P) * h^2, sum(P, dims = 2), P[:, j], the means, variances and
+# the covariance) computed on the train: a subset of the sites is contracted against weight vectors (contract_sites) and the rest stays a
+# train.  Every function takes a QTTvector and returns QTTvectors, or takes a pair (DeviceTT, (n_dims, bits_per_dim, ordering)) — a
+# resident batch with its metadata — and returns such pairs (new handles; per-train numbers as arrays over the batch).  Dimensions and
+# grid indices are 0-based, as in site_dim_level and in the array qttv_to_array returns.
+def dim_sites(dim: int, n_dims: int, bits_per_dim: int, ordering: str) -> List[int]:
+    """The 0-based sites that hold the bits of dimension ``dim``, level 0 (the most significant bit) first."""
+    return [s for s in range(n_dims * bits_per_dim) if site_dim_level(s, n_dims, bits_per_dim, ordering)[0] == dim]
+
+
+def reduced_meta(n_dims: int, bits_per_dim: int, ordering: str, keep):
+    """Metadata of the train that is left when only the dimensions ``keep`` remain: they keep their relative order, and both orderings
+    stay what they are (interleaved: level-major with the kept dimensions in order inside a level; serial: the kept blocks in order)."""
+    return len(_keep_list("reduced_meta", keep, n_dims)), int(bits_per_dim), ordering
+
+
+def _keep_list(who, keep, n_dims):
+    keep = [keep] if isinstance(keep, (int, np.integer)) else list(keep)
+    out = sorted({int(k) for k in keep})
+    if len(out) != len(keep) or any(not 0 <= k < n_dims for k in out):
+        raise _lib.TTNError(f"{who}: keep must hold distinct dimensions in 0:{n_dims - 1} (got {tuple(keep)})")
+    return out
+
+
+def _qtt_parts(who, q):
+    """(train, (n_dims, bits_per_dim, ordering), resident)"""
+    from .device import DeviceTT
+    if isinstance(q, QTTvector):
+        if _eltype(q.ttv_vec) != "Float64":
+            raise _lib.TTNError(f"{who}: Float64 only, a ComplexF64 train is not supported")
+        return q.ttvector(), (q.n_dims, q.bits_per_dim, q.ordering), False
+    if isinstance(q, tuple) and len(q) == 2 and isinstance(q[0], DeviceTT):
+        n_dims, bits, ordering = q[1]
+        _check_meta(q[0].N, q[0].dims, int(n_dims), int(bits), ordering, "x")
+        if q[0].dtype is not np.float64:
+            raise _lib.TTNError(f"{who}: Float64 only, a ComplexF64 handle is not supported")
+        return q[0], (int(n_dims), int(bits), ordering), True
+    raise TypeError(f"{who}: expected a QTTvector or a pair (DeviceTT, (n_dims, bits_per_dim, ordering)), got {type(q).__name__}")
+
+
+def _contract(train, meta, vectors, keep, resident):
+    """contract the 0-based sites of ``vectors``; the result carries the metadata of the kept dimensions"""
+    weights = {s + 1: v for s, v in vectors.items()}
+    new_meta = reduced_meta(*meta, keep)
+    if resident:
+        return train.contract_sites(weights), new_meta
+    return QTTvector(_tt.contract_sites(train, weights), *new_meta)
+
+
+def _contract_all(train, vectors, resident):
+    """every site contracted: dot with the rank-1 train of the weights (a float; an array over the batch for a resident batch)"""
+    from .device import DeviceTT, dot as dev_dot
+    N = train.N
+    batch = train.batch if resident else 1
+    vs = [np.broadcast_to(np.asarray(vectors[s], dtype=np.float64), (batch, 2)) for s in range(N)]
+
+    def rank1(b):
+        return TTvector(N, [np.asfortranarray(vs[s][b].reshape(2, 1, 1)) for s in range(N)], (2,) * N, [1] * (N + 1), [0] * N)
+
+    if not resident:
+        return _tt.dot(train, rank1(0))
+    w = DeviceTT((2,) * N, [1] * (N + 1), batch)
+    try:
+        for b in range(batch):
+            w.upload(b, rank1(b))
+        return dev_dot(train, w)
+    finally:
+        w.free()
+
+
+def marginal(q, keep, h=None):
+    """Sum out every dimension that is not in ``keep`` (0-based dimensions; an int or a collection): the rectangle rule of the reference's
+    examples, ``sum(P, dims = ...) * h`` per summed dimension when ``h`` is given.  The result lives on the kept dimensions, in their
+    order, with q's bits_per_dim and ordering.  ``keep=()`` sums everything and returns the number (the mass ``sum(P) * h^n``) through
+    dot with the rank-1 train of the weights; keeping every dimension returns a copy."""
+    train, meta, resident = _qtt_parts("marginal", q)
+    n_dims, bits, ordering = meta
+    keep = _keep_list("marginal", keep, n_dims)
+    vectors = {}
+    for dim in range(n_dims):
+        if dim not in keep:
+            for level, s in enumerate(dim_sites(dim, *meta)):
+                vectors[s] = np.full(2, float(h) if (h is not None and level == 0) else 1.0)
+    if not keep:
+        return _contract_all(train, vectors, resident)
+    if len(keep) == n_dims:
+        if not resident:
+            return q.copy()
+        from .device import DeviceTT
+        y = DeviceTT(train.dims, train.cap, train.batch)
+        _lib.check(_lib.lib().ttn_tt_copy(y.h, train.h))
+        return y, meta
+    return _contract(train, meta, vectors, keep, resident)
+
+
+def slice_dim(q, dim: int, index):
+    """Fix dimension ``dim`` at the grid index ``index`` (both 0-based): ``np.take(qttv_to_array(q), index, axis=dim)`` as a train on the
+    other dimensions.  The weight of the site that holds level l of ``dim`` is the unit vector of bit ``(index >> (bits - 1 - l)) & 1``
+    (level 0 is the most significant bit, site_dim_level).  For a resident batch ``index`` may hold one index per train: B replicas are
+    cut at B positions in one launch.  With one dimension the result is the value itself."""
+    train, meta, resident = _qtt_parts("slice_dim", q)
+    n_dims, bits, ordering = meta
+    dim = int(dim)
+    if not 0 <= dim < n_dims:
+        raise _lib.TTNError(f"slice_dim: dim must be in 0:{n_dims - 1} (got {dim})")
+    idx = np.asarray(index)
+    if idx.dtype.kind not in "iu" or idx.ndim > 1 or (idx.ndim == 1 and (not resident or idx.shape[0] != train.batch)):
+        raise _lib.TTNError("slice_dim: index must be an integer, or one integer per train of a resident batch")
+    if np.any(idx < 0) or np.any(idx >= 2 ** bits):
+        raise _lib.TTNError(f"slice_dim: index out of 0:{2 ** bits - 1}")
+    vectors = {s: np.eye(2)[(idx >> (bits - 1 - level)) & 1] for level, s in enumerate(dim_sites(dim, *meta))}
+    if n_dims == 1:
+        return _contract_all(train, vectors, resident)
+    return _contract(train, meta, vectors, [k for k in range(n_dims) if k != dim], resident)
+
+
+def _moments_host(m1, m2, mass, a, b, bits, ordering):
+    """means, covariance from the 1-d marginals m1[i] and the 2-d marginals m2[i, j] (i < j), all QTTvectors that carry h per summed dimension"""
+    from . import constructors as K
+    n = len(m1)
+    h = (b - a) / (2 ** bits - 1)
+    mean, cov = np.zeros(n), np.zeros((n, n))
+    for i in range(n):
+        mean[i] = _tt.dot(m1[i].ttvector(), K.qtt_polynom([0.0, 1.0], bits, a, b)) * h
+    for i in range(n):
+        cov[i, i] = _tt.dot(m1[i].ttvector(), K.qtt_polynom([mean[i] ** 2, -2.0 * mean[i], 1.0], bits, a, b)) * h
+        for j in range(i + 1, n):
+            w = opalg.kron(K.qtt_polynom([-mean[i], 1.0], bits, a, b), K.qtt_polynom([-mean[j], 1.0], bits, a, b))      # serial: dimension i first
+            if ordering == "interleaved":
+                w = qtt.reorder(w, 2, bits, "interleaved", 0.0)
+            cov[i, j] = cov[j, i] = _tt.dot(m2[i, j].ttvector(), w) * h * h
+    return mass, mean, cov
+
+
+def moments(q, a: float, b: float):
+    """(mass, mean, cov) of a density sampled on the grid of [a, b]^n, by the formulas of the reference's Ornstein2D example (rectangle
+    rule, h = (b - a) / (2^bits - 1); nothing is divided by the mass):
+        mass = sum(P) h^n,   mean[i] = sum(x_i P) h^n,   cov[i, j] = sum((x_i - mean[i]) (x_j - mean[j]) P) h^n
+    from the one- and two-dimensional marginals and dot with the trains of qtt_polynom (and their kron): nothing dense is formed.
+    For a resident batch the marginals are taken for all trains at once and the three results gain a leading batch axis."""
+    train, meta, resident = _qtt_parts("moments", q)
+    n, bits, ordering = meta
+    if bits < 2:
+        raise _lib.TTNError("moments: bits_per_dim must be at least 2 (qtt_polynom)")
+    a, b = float(a), float(b)
+    h = (b - a) / (2 ** bits - 1)
+    mass = marginal(q, (), h)
+    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    m1 = [q if n == 1 else marginal(q, (i,), h) for i in range(n)]
+    m2 = {(i, j): (q if n == 2 else marginal(q, (i, j), h)) for (i, j) in pairs}
+    if not resident:
+        return _moments_host(m1, m2, mass, a, b, bits, ordering)
+    try:
+        out = []
+        for t in range(train.batch):
+            h1 = [QTTvector(m[0].download(t), *m[1]) for m in m1]
+            h2 = {ij: QTTvector(m[0].download(t), *m[1]) for ij, m in m2.items()}
+            out.append(_moments_host(h1, h2, float(mass[t]), a, b, bits, ordering))
+        return np.array([o[0] for o in out]), np.stack([o[1] for o in out]), np.stack([o[2] for o in out])
+    finally:
+        for m in list(m1) + list(m2.values()):
+            if m[0] is not train:
+                m[0].free()
+
+
 # ---- N-d Laplacian ----------------------------------------------------------------------------------------------------------------
 def qtt_laplacian(n_dims: int, bits_per_dim: int, ordering: str = "interleaved", a: float = 0.0, b: float = 1.0, bc: str = "DN") -> QTToperator:
     """qtt_laplacian(n_dims, bits_per_dim; ordering, a, b, bc) — src/tt_operators.jl:644-703: the Kronecker sum

@@ -386,6 +386,27 @@ def tt_sample(x: TTvector, nsamples: int, mode: str = "born", seed: int = 0, u=N
             dx.free()
 
 
+def contract_sites(x: TTvector, weights) -> TTvector:
+    """The train on the sites ``weights`` (a dict {site: vector of n_k numbers}, sites 1-based) does not name, with the named sites
+    contracted against their vectors (``device.contract_sites``): marginals, slices and moments of a function-valued train without its
+    dense array.  Upload, call, free; the argument checks run before the upload.  Float64 only."""
+    from .device import DeviceTT, _contract_tables
+    if not isinstance(x, TTvector):
+        raise TypeError(f"contract_sites: expected a TTvector, got {type(x).__name__}")
+    if any(np.iscomplexobj(c) for c in x.ttv_vec):
+        raise _lib.TTNError("contract_sites: Float64 only, a ComplexF64 train is not supported")
+    _contract_tables("contract_sites", x.ttv_dims, 1, weights)
+    dx = dy = None
+    try:
+        dx = DeviceTT.from_host(x)
+        dy = dx.contract_sites(weights)
+        return dy.download(0)
+    finally:
+        for h in (dy, dx):
+            if h is not None:
+                h.free()
+
+
 def norm(a: TTvector) -> float:
     """norm(a) — src/tt_operations.jl:465-470.  dot(a, a) squares every core, so a core of size 2^+-600 leaves the double range in the
     partial products though the norm itself does not (2^800 in one core and 2^-800 in the next gave 0).  Each core is divided by the
