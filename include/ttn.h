@@ -696,6 +696,12 @@ int ttn_r_and_d_to_rks(int64_t d, const int64_t* dims, int64_t n_rks, const int6
  * of function-valued trains without a dense array: ttn_tt_contract_sites.  Declared in ttn_contract.h, which this header includes. */
 #include "ttn_contract.h"
 
+/* ---- site-resolved measurements on ComplexF64 trains (csrc/ttn_zmeasure_kernels.h) -------------------------------------
+ * The complex profile <x| O_k |x> / <x|x> of every site and the two-point functions <x| P_i Q_j |x> / <x|x> of ALL pairs, per train, the
+ * bra conjugated and the tables complex (a lone sigma_y included): ttn_zsite_expect, ttn_zcorrelation and their _dev forms.  Declared
+ * in ttn_zmeasure.h, which this header includes. */
+#include "ttn_zmeasure.h"
+
 #ifdef __cplusplus
 }
 #endif

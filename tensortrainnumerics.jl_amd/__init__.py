@@ -25,6 +25,6 @@ from .qttnd import (QTToperator, QTTvector, check_compat, dim_sites, entanglemen
 from .qtt import bubble_sort_swaps, hadamard_ttm, reorder, reorder_op, reorder_perm, to_qtt, to_ttv, ttv_decomp
 from .tt import (TToperator, TTvector, _tt_bond_truncate_, add, add_, apply, apply_compress, apply_rect, braket, contract_sites, correlation_matrix, div, dot, energy,
                  euclidean_distance, expect, hadamard, increase_ranks, norm, orthogonalize, r_and_d_to_rks, rayleigh, sandwich, scale, site_expect, sub, tt_compress_, tt_sample, tt_up_rks,
-                 ttv_to_tensor)
+                 ttv_to_tensor, zcorrelation_matrix, zsite_expect)
 
 __all__ = [n for n in dir() if not n.startswith("__")]

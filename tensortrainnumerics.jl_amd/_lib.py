@@ -263,6 +263,14 @@ CONTRACT_SIGNATURES = {
     "ttn_tt_contract_sites": (C.c_int, [handle, i64, p_i64, i64, p_f64, handle]),
 }
 
+# site-resolved measurements on ComplexF64 trains, include/ttn_zmeasure.h (interleaved host tables; `out` is host, `d_out` device memory)
+ZMEASURE_SIGNATURES = {
+    "ttn_zsite_expect": (C.c_int, [handle, i64, p_f64, i64, p_f64]),
+    "ttn_zsite_expect_dev": (C.c_int, [handle, i64, p_f64, i64, C.c_void_p]),
+    "ttn_zcorrelation": (C.c_int, [handle, p_f64, p_f64, i64, p_f64]),
+    "ttn_zcorrelation_dev": (C.c_int, [handle, p_f64, p_f64, i64, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -295,7 +303,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     for table in (SIGNATURES, RECT_SIGNATURES, DENSE_SIGNATURES, STEP_SIGNATURES, CROSS_BATCH_SIGNATURES, EXPECT_SIGNATURES, EXPECT_GRAD_SIGNATURES,
                   OPBATCH_SIGNATURES, MEASURE_SIGNATURES, SAMPLE_SIGNATURES, EIG_ORTHO_SIGNATURES, BRAKET_SIGNATURES,
-                  TANGENT_SIGNATURES, CONTRACT_SIGNATURES):
+                  TANGENT_SIGNATURES, CONTRACT_SIGNATURES, ZMEASURE_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(L, name)       # AttributeError if the .so does not export a declared symbol
             fn.restype = res

@@ -41,6 +41,7 @@
 #include "ttn_braket_kernels.h"
 #include "ttn_tangent_kernels.h"
 #include "ttn_contract_kernels.h"
+#include "ttn_zmeasure_kernels.h"
 
 // The host headers: the dynamic-LDS table first (it fixes the order of the kernel templates' instantiations, see there), then the
 // layers, lowest first — every header stands after the ones it includes (tests/test_cpu_headers.py).
@@ -56,6 +57,7 @@
 #include "ttn_host_braket.h"
 #include "ttn_host_tangent.h"
 #include "ttn_host_contract.h"
+#include "ttn_host_zmeasure.h"
 
 // the 512-thread build of k_compress and its building blocks (ttn_wg512.hip: two workgroups per CU), declared once for both units
 #include "ttn_wg512.h"
@@ -3179,6 +3181,7 @@ int ttn_finalize(void) {
     if (g_xb_tab_ev) { hipEventDestroy(g_xb_tab_ev); g_xb_tab_ev = nullptr; }
     if (g_measure_ev) { hipEventDestroy(g_measure_ev); g_measure_ev = nullptr; }
     if (g_contract_ev) { hipEventDestroy(g_contract_ev); g_contract_ev = nullptr; }
+    if (g_zmeasure_ev) { hipEventDestroy(g_zmeasure_ev); g_zmeasure_ev = nullptr; }
     for (hipEvent_t e : g_sample_ev) hipEventDestroy(e);
     g_sample_ev.clear();
     g_sample_chunks = 0;

@@ -31,6 +31,7 @@
 #include "ttn_braket_kernels.h"
 #include "ttn_tangent_kernels.h"
 #include "ttn_contract_kernels.h"
+#include "ttn_zmeasure_kernels.h"
 
 #include <cstddef>
 
@@ -93,6 +94,12 @@ const struct { const void* fn; size_t lds; } lds_limits[] = {
     {(const void*)k_tangent_chain, DOT_LDS_BYTES(DOT_MAX_D)},
     {(const void*)k_contract_chip, CONTRACT_CHIP_LDS_BYTES},
     {(const void*)k_contract_gen, sizeof(double) * GEMM_LDS_TOTAL},
+    {(const void*)k_zmeasure_chain<true>, ZM_LDS_BYTES(ZMEASURE_MAX_D)},
+    {(const void*)k_zmeasure_chain<false>, ZM_LDS_BYTES(ZMEASURE_MAX_D)},
+    {(const void*)k_zmeasure_open<true>, ZM_LDS_BYTES(ZMEASURE_MAX_D)},
+    {(const void*)k_zmeasure_open<false>, ZM_LDS_BYTES(ZMEASURE_MAX_D)},
+    {(const void*)k_zmeasure_walk<true>, ZM_LDS_BYTES(ZMEASURE_MAX_D)},
+    {(const void*)k_zmeasure_walk<false>, ZM_LDS_BYTES(ZMEASURE_MAX_D)},
 };
 }  // namespace
 #endif  // TTN_HOST_LDS_H

@@ -871,6 +871,123 @@ def correlation_matrix_dev(x: DeviceTT, P, Q=None, normalize: bool = True, out=N
     return out.transpose(1, 2)
 
 
+# ---- site-resolved measurements on ComplexF64 trains (include/ttn_zmeasure.h, csrc/ttn_zmeasure_kernels.h) -------------
+ZMEASURE_MAX_OPS = _header_define("ttn_zmeasure.h", "TTN_ZMEASURE_MAX_OPS")     # operator tables per zsite_expect call
+
+
+def _zmeasure_table(who: str, name: str, op, dims: Sequence[int]) -> np.ndarray:
+    """One operator table of include/ttn_zmeasure.h from ``op`` — an (n, n) array used at every site, or a sequence of d arrays, real
+    or complex —: the per-site matrices column-major, back to back, complex128.  Shape and dtype errors are raised here, before any
+    device call."""
+    d = len(dims)
+    if isinstance(op, (list, tuple)) and len(op) > 0 and all(np.ndim(o) == 2 for o in op):
+        mats = list(op)
+    else:
+        a = np.asarray(op)
+        if a.dtype == object or a.ndim not in (2, 3):
+            raise _lib.TTNError(f"{who}: {name} must be an (n, n) array or a sequence of {d} such arrays, got shape {getattr(a, 'shape', None)}")
+        mats = [a] * d if a.ndim == 2 else list(a)
+    if len(mats) != d:
+        raise _lib.TTNError(f"{who}: {name} holds {len(mats)} matrices for {d} sites")
+    flat = []
+    for k, (m, n) in enumerate(zip(mats, dims)):
+        m = np.asarray(m)
+        if m.dtype == object or not (np.issubdtype(m.dtype, np.number) or m.dtype == bool):
+            raise _lib.TTNError(f"{who}: {name} at site {k} has dtype {m.dtype}, expected real or complex numbers")
+        if m.shape != (n, n):
+            raise _lib.TTNError(f"{who}: {name} at site {k} has shape {m.shape}, expected ({n}, {n})")
+        flat.append(np.asarray(m, dtype=np.complex128).flatten(order="F"))
+    return np.concatenate(flat)
+
+
+def _zmeasure_train(who: str, x) -> None:
+    if not isinstance(x, DeviceTT):
+        raise TypeError(f"{who}: expected a DeviceTT, got {type(x).__name__}")
+    if x.dtype is not np.complex128:
+        raise _lib.TTNError(f"{who}: ComplexF64 only; a Float64 handle is measured by site_expect / correlation_matrix")
+
+
+def _p_c128(a: np.ndarray):
+    return a.view(np.float64).ctypes.data_as(_lib.p_f64)
+
+
+def _zsite_expect_tables(who: str, x: DeviceTT, ops) -> np.ndarray:
+    _zmeasure_train(who, x)
+    if not ops:
+        raise _lib.TTNError(f"{who}: no operator given")
+    if len(ops) > ZMEASURE_MAX_OPS:
+        raise _lib.TTNError(f"{who}: {len(ops)} operators, at most {ZMEASURE_MAX_OPS} per call")
+    return np.concatenate([_zmeasure_table(who, f"operator {t}", op, x.dims) for t, op in enumerate(ops)])
+
+
+def zsite_expect(x: DeviceTT, *ops, normalize: bool = True) -> np.ndarray:
+    """The complex profile E_O[k] = <x_b| O_k |x_b> / <x_b|x_b> of every site and train of a ComplexF64 handle (ttn_zsite_expect):
+    complex128, (batch, d) for one operator, (batch, nops, d) for several (at most ``ZMEASURE_MAX_OPS``), all from ONE pair of
+    environment chains.  Each ``op`` is an (n, n) array used at every site or a sequence of d arrays, real or complex; its first index
+    meets the conjugated bra, as the output index of an operator in ``braket``.  A lone sigma_y is measured as it stands; a Hermitian
+    table gives a real profile up to rounding.  ``normalize=False`` leaves the division by real(<x|x>) out; a zero train with
+    ``normalize=True`` gives NaN (0 / 0).  Reproducible to rounding, not bitwise.  Synchronises, as ``dot``."""
+    tabs = _zsite_expect_tables("zsite_expect", x, ops)
+    out = np.empty(x.batch * len(ops) * x.N, dtype=np.complex128)
+    _lib.check(_lib.lib().ttn_zsite_expect(x.h, len(ops), _p_c128(tabs), 1 if normalize else 0, _p_c128(out)))
+    res = out.reshape(x.batch, len(ops), x.N)
+    return res[:, 0, :].copy() if len(ops) == 1 else res
+
+
+def zsite_expect_dev(x: DeviceTT, *ops, normalize: bool = True, out=None):
+    """``zsite_expect`` into a complex128 device tensor (batch, nops, d) (``out``, or a new one), asynchronously on the library stream.
+    The tensor must not be read on another stream before ``sync()``."""
+    import torch
+    tabs = _zsite_expect_tables("zsite_expect_dev", x, ops)
+    shape = (x.batch, len(ops), x.N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex128, device="cuda")
+    if out.dtype != torch.complex128 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError(f"zsite_expect_dev: out must be a contiguous complex128 device tensor of shape {shape}")
+    _lib.check(_lib.lib().ttn_zsite_expect_dev(x.h, len(ops), _p_c128(tabs), 1 if normalize else 0, C.c_void_p(out.data_ptr())))
+    return out
+
+
+def _zcorrelation_tables(who: str, x: DeviceTT, P, Q):
+    _zmeasure_train(who, x)
+    tp = _zmeasure_table(who, "P", P, x.dims)
+    tq = tp if (Q is None or Q is P) else _zmeasure_table(who, "Q", Q, x.dims)
+    return tp, tq
+
+
+def zcorrelation_matrix(x: DeviceTT, P, Q=None, normalize: bool = True, connected: bool = False) -> np.ndarray:
+    """C[b, i, j] = <x_b| P_i Q_j |x_b> / <x_b|x_b> for ALL pairs of sites of a ComplexF64 handle (ttn_zcorrelation): complex128,
+    (batch, d, d).  ``P`` and ``Q`` are given as in ``zsite_expect``; ``Q=None`` means Q = P.  The diagonal is the matrix product
+    P_i Q_i on one site; off the diagonal the two act on different sites and commute.  ``connected=True`` subtracts E_P[i] E_Q[j] (on
+    the diagonal E_P[i] E_Q[i]) with the profiles of ``zsite_expect`` at the same ``normalize``.  Cost: the two chains, then one short
+    walk per site and triangle — one triangle when P and Q are equal bit for bit, the other its plain copy.  Reproducible to rounding,
+    not bitwise.  Synchronises."""
+    tp, tq = _zcorrelation_tables("zcorrelation_matrix", x, P, Q)
+    d = x.N
+    out = np.empty(x.batch * d * d, dtype=np.complex128)
+    _lib.check(_lib.lib().ttn_zcorrelation(x.h, _p_c128(tp), _p_c128(tq), 1 if normalize else 0, _p_c128(out)))
+    res = np.ascontiguousarray(out.reshape(x.batch, d, d).transpose(0, 2, 1))       # the ABI stores C[i, j] at i + d j
+    if connected:
+        ep = zsite_expect(x, P, normalize=normalize)
+        eq = ep if (Q is None or Q is P) else zsite_expect(x, Q, normalize=normalize)
+        res -= ep[:, :, None] * eq[:, None, :]
+    return res
+
+
+def zcorrelation_matrix_dev(x: DeviceTT, P, Q=None, normalize: bool = True, out=None):
+    """``zcorrelation_matrix`` (not connected) asynchronously on the library stream: returns the (batch, d, d) VIEW C[b, i, j] of a
+    complex128 device tensor in the layout of the ABI (``out``, contiguous (batch, d, d) holding C[b, j, i], or a new one)."""
+    import torch
+    tp, tq = _zcorrelation_tables("zcorrelation_matrix_dev", x, P, Q)
+    shape = (x.batch, x.N, x.N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex128, device="cuda")
+    if out.dtype != torch.complex128 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise TypeError(f"zcorrelation_matrix_dev: out must be a contiguous complex128 device tensor of shape {shape}")
+    _lib.check(_lib.lib().ttn_zcorrelation_dev(x.h, _p_c128(tp), _p_c128(tq), 1 if normalize else 0, C.c_void_p(out.data_ptr())))
+    return out.transpose(1, 2)
+
+
 # ---- sampling (include/ttn_sample.h, csrc/ttn_sample_kernels.h, DESIGN.md 4.29) ----------------------------------------------------------
 SAMPLE_MODES = {"born": _header_define("ttn_sample.h", "TTN_SAMPLE_BORN"), "density": _header_define("ttn_sample.h", "TTN_SAMPLE_DENSITY")}
 

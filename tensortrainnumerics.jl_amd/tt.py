@@ -361,6 +361,54 @@ def correlation_matrix(x: TTvector, P, Q=None, normalize: bool = True, connected
             dx.free()
 
 
+def _zmeasure_upload(x: TTvector):
+    """x as train 0 of a ComplexF64 handle: a real train is promoted on the host."""
+    from .device import DeviceTT
+    dx = DeviceTT(x.ttv_dims, x.ttv_rks, 1, dtype=np.complex128)
+    try:
+        dx.upload(0, x)
+    except BaseException:
+        dx.free()
+        raise
+    return dx
+
+
+def zsite_expect(x: TTvector, *ops, normalize: bool = True) -> np.ndarray:
+    """The complex profile <x| O_k |x> / <x|x> of every site (``device.zsite_expect``): complex128, (d,) for one operator, (nops, d) for
+    several; the tables may be complex.  The train is uploaded as ComplexF64 — a real train is promoted, which is how it yields its
+    sigma_y numbers —, the kernels run, the handle is freed."""
+    from .device import _zmeasure_table, zsite_expect as dev_zsite_expect
+    if not isinstance(x, TTvector):
+        raise TypeError(f"zsite_expect: expected a TTvector, got {type(x).__name__}")
+    for t, op in enumerate(ops):                    # the argument checks, before the upload
+        _zmeasure_table("zsite_expect", f"operator {t}", op, x.ttv_dims)
+    dx = None
+    try:
+        dx = _zmeasure_upload(x)
+        return dev_zsite_expect(dx, *ops, normalize=normalize)[0]
+    finally:
+        if dx is not None:
+            dx.free()
+
+
+def zcorrelation_matrix(x: TTvector, P, Q=None, normalize: bool = True, connected: bool = False) -> np.ndarray:
+    """C[i, j] = <x| P_i Q_j |x> / <x|x> for all pairs of sites (``device.zcorrelation_matrix``): complex128, (d, d); complex tables and
+    a complex or real train (promoted).  Upload, call, free."""
+    from .device import _zmeasure_table, zcorrelation_matrix as dev_zcorrelation_matrix
+    if not isinstance(x, TTvector):
+        raise TypeError(f"zcorrelation_matrix: expected a TTvector, got {type(x).__name__}")
+    for name, op in (("P", P), ("Q", Q)):           # the argument checks, before the upload
+        if op is not None:
+            _zmeasure_table("zcorrelation_matrix", name, op, x.ttv_dims)
+    dx = None
+    try:
+        dx = _zmeasure_upload(x)
+        return dev_zcorrelation_matrix(dx, P, Q, normalize=normalize, connected=connected)[0]
+    finally:
+        if dx is not None:
+            dx.free()
+
+
 def tt_sample(x: TTvector, nsamples: int, mode: str = "born", seed: int = 0, u=None):
     """``nsamples`` configurations of the train x drawn on the device (``device.sample``): ``mode="born"`` from x(z)^2 / <x, x>,
     ``mode="density"`` from x(z) / sum x.  Returns ``(idx (S, d) int64, 1-based; logp (S,); info (2,): clamped weights, dead samples)``.
